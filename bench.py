@@ -9,6 +9,11 @@ A step = one full optimiser step of ``CSMTrainer.train_step`` on one fixed synth
 (+ teacher-forced depth decoder on 1/16 of the frames, "mode C" of SURVEY 8d) -> backward -> bf16 gradient all-reduce
 (N>1) -> global-norm clip -> fused AdamW.  tokens/s = N * B * S / step time (metric definition of the reference's own
 harness, src/csm/training/run_lora_benchmark.py:357-361).  Inputs and weights are resident in HBM before the timed region.
+
+A plain run sets up, warms up, times --steps steps (the last one with per-GEMM events for the roofline fields) and prints
+the result line.  --dump-outputs DIR also writes what the last timed step computed (dump_outputs); the inputs are seeded,
+so the same arguments give the same inputs on every run.  --full adds everything else the benchmark measures or checks:
+the extra legs and, on one GPU, the CPU baseline with its loss parity check.
 """
 import argparse
 import json
@@ -41,11 +46,16 @@ def parse():
     ap.add_argument("--lora", action="store_true", help="configs[2]: LoRA r=8 q_proj/v_proj instead of full-param")
     ap.add_argument("--zero1", action="store_true", help="N > 1: reduce-scatter + sharded AdamW + parameter all-gather (ZeRO-1) "
                     "instead of the gradient all-reduce (also: CSM_DP_ZERO1=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run what it does not need: the extra legs (loss modes A / B, config-2 batch parity, "
+                         "LoRA B=8, generate 10 s; N > 1: config 4 at 8 sequences/GPU) and the CPU baseline with its loss parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps: write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seq", type=int, default=2048, help="positions of the CPU-baseline sample (SURVEY 8d protocol: B=1, S=2048)")
     ap.add_argument("--cpu-budget", type=float, default=340.0, help="seconds the CPU-baseline leg may take (bounds the sample)")
     ap.add_argument("--gemm-shapes", action="store_true", help="stderr: the instrumented step's GEMM launches grouped by shape")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra legs (loss modes A / B, LoRA B=8, generate 10 s)")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra legs (loss modes A / B, LoRA B=8, generate 10 s)")
     ap.add_argument("--tiny", action="store_true", help="tiny model (plumbing check only; the number is not the metric)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous plumbing only (gloo on the CPU, no model, no GPU): what tests/test_cpu.py runs")
@@ -361,6 +371,34 @@ def cpu_baseline(model, cfg_fn, seq, seed, sw, aw, budget_s):
                 loss=loss0), (tokens, mask, targets)
 
 
+def dump_outputs(path, optimizer, loss, det, seed=4321, per_kind=1 << 20):
+    """What the last timed step computed, so that two builds can be compared output for output: what ``train_step``
+    returns (total loss and its two terms) and the state the step left behind for the next one (fp32 master weights and
+    both AdamW moments).  The state is a fixed seeded sample of ``per_kind`` elements per kind, spread over the optimiser's
+    groups (at most 3 x 4 MB); float32 throughout."""
+    import re
+    import numpy as np
+    arrays = {"loss": loss, "semantic_loss": det["semantic_loss"], "acoustic_loss": det["acoustic_loss"]}
+    groups = [g for g in optimizer.param_groups if g["numel"] > 0]
+    for i, g in enumerate(groups):
+        name, st = g["name"], optimizer.state[g["name"]]
+        k = min(g["numel"], per_kind // len(groups))
+        idx = (torch.arange(k) if k == g["numel"] else
+               torch.randint(g["numel"], (k,), generator=torch.Generator().manual_seed(seed + i)).sort().values).to(g["param"].device)
+        if "lo" in st:
+            from csm.training.optim import join_master
+            master = join_master(g["param"].reshape(-1)[idx], st["lo"].reshape(-1)[idx])
+        else:
+            master = st["master"].reshape(-1)[idx]
+        tag = re.sub(r"[^A-Za-z0-9_.-]", "_", name)
+        arrays[f"master_{tag}"] = master
+        arrays[f"adam_m_{tag}"] = st["m"].reshape(-1)[idx]
+        arrays[f"adam_v_{tag}"] = st["v"].reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().reshape(-1).cpu().numpy())
+
+
 def comm_census(world, backend, local):
     """Who is in the job: every rank reports (rank, device index, device name) through the process group itself, so the
     result line proves that N ranks on N different GPUs took part in the collectives (the driver reads ``rccl.world``)."""
@@ -505,7 +543,7 @@ def main():
         nb = batch["input_tokens"].shape[0]
         per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(max(1, steps - 1))) or [dt / steps * 1e3]
         return dict(dt=dt, steps=steps, ms=dt / steps * 1e3, tokens_per_s=world * nb * a.seq / (dt / steps), gt=gt, loss=float(loss),
-                    per_step=per_step, nb=nb)
+                    per_step=per_step, nb=nb, loss_t=loss, det=det)
 
     def step_flops(model, res):
         """GEMM FLOPs of the instrumented step + algorithmic attention FLOPs (causal half, SURVEY 8d: 3x forward for fwd+bwd)."""
@@ -525,6 +563,8 @@ def main():
                 "roofline": {"bound": "mfma", "what": "whole step: GEMM + attention FLOP / step time", "achieved": round(tf, 1),
                              "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(tf / MFMA_BF16_PEAK_TFLOPS, 4)}}
 
+    # the depth decoder's frame subsets come from torch's global generator: seeded, so the same arguments give the same inputs
+    torch.manual_seed(4321 + rank)
     model = Model(args, device=f"cuda:{local}", seed=0)          # random init, same on every rank (and broadcast from rank 0)
     model.acoustic_mode = {"A": "off", "B": "all", "C": "amortized"}[a.mode]
     tr = make_trainer(model, a.lora)
@@ -535,11 +575,13 @@ def main():
     res = run(tr, batch, a.warmup, a.steps)
     dt, ms, tokens_per_s, gt, loss = res["dt"], res["ms"], res["tokens_per_s"], res["gt"], res["loss"]
     exposed = tr.grad_sync.exposed_comm_ms()[-a.steps:] if tr.grad_sync is not None else None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr.optimizer, res["loss_t"], res["det"])
 
     # ---- N > 1: BASELINE config 4 proper is 8 sequences per GPU (global batch 64 on 8 GPUs).  The headline keeps 4 per GPU
     # at every N so that the driver's scaling curve compares equal per-GPU work; config 4's own number is reported beside it.
     dp_b8 = None
-    if world > 1 and not a.tiny and not a.lora and a.batch != 8:
+    if a.full and world > 1 and not a.tiny and not a.lora and a.batch != 8:
         r8 = run(tr, make_batch(8), 2, 5, with_timer=False)
         dp_b8 = {"workload": f"BASELINE config 4: full-param bf16 DP, seq={a.seq}, 8 sequences/GPU, global batch {8 * world}",
                  "ms_per_step": round(r8["ms"], 3), "tokens_per_s": round(r8["tokens_per_s"], 1), "steps": r8["steps"],
@@ -608,7 +650,7 @@ def main():
 
     # ---- extra legs (1 GPU only, outside the headline's timed region): the other loss modes of SURVEY 8d, BASELINE
     # configs 3 (LoRA r=8 q/v, B=8) and 5 (generate 10 s of audio)
-    if world == 1 and not a.no_extras and not a.tiny and not a.lora and a.mode == "C":
+    if a.full and world == 1 and not a.no_extras and not a.tiny and not a.lora and a.mode == "C":
         for mode, (w, k) in (("A", (3, 10)), ("B", (1, 3))):
             model.acoustic_mode = {"A": "off", "B": "all"}[mode]
             r = run(tr, batch, w, k)
@@ -668,7 +710,7 @@ def main():
     if rank == 0:
         if extra:
             out["extra"] = extra
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             from oracle import csm_oracle as O
             cb, (ct, cm, cg) = cpu_baseline(model, (O.tiny_cfg if a.tiny else O.csm_1b_cfg), min(a.cpu_seq, a.seq), 4321, 100.0, 1.0,
                                             a.cpu_budget)

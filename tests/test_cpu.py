@@ -46,7 +46,11 @@ def test_oracle_train_step_fixture():
         if key.startswith("grad::"):
             g = params[key[6:]].grad
             g = g[..., :64] if g.dim() > 1 else g
-            assert torch.allclose(g, torch.from_numpy(z[key]), rtol=1e-4, atol=1e-6), key
+            ref = torch.from_numpy(z[key])
+            # atol 1e-6 per unit of the tensor's largest entry: the fixture holds fp32 sums, and on another host CPU's BLAS
+            # path entries that cancel to ~0 in a tensor of scale ~30 (text embeddings) move by ~1e-5
+            assert torch.allclose(g, ref, rtol=1e-4, atol=1e-6 * max(1.0, float(ref.abs().max()))), key
+            assert float((g - ref).norm()) <= 1e-5 * float(ref.norm()), key
 
 
 def test_oracle_sampler_and_rvq_fixture():
@@ -390,6 +394,42 @@ def test_gradsync_bucket_plan_for_model():
     # a backbone layer is one contiguous slice
     lay = [(s.offset, s.numel) for n, s in m._slots.items() if n.startswith("backbone.layers.1.")]
     assert len(GradSync._merge(lay)) == 1
+
+
+def test_bench_dump_outputs_writes_fixed_float32_samples(tmp_path):
+    """``bench.py --dump-outputs``: the step's losses and a seeded sample of the optimiser state it left, float32 .npy, the
+    same indices on every call, exact fp32 masters from the split (bf16 + low half) storage, small groups whole."""
+    import importlib.util
+    from types import SimpleNamespace
+    from csm.training.optim import split_master
+    spec = importlib.util.spec_from_file_location("csm_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    master = torch.randn(3_000_000, generator=g)
+    param = torch.empty(3_000_000, dtype=torch.bfloat16)
+    lo = split_master(master, param)
+    opt = SimpleNamespace(param_groups=[dict(name="backbone", numel=master.numel(), param=param),
+                                        dict(name="other@8", numel=10, param=torch.zeros(10, dtype=torch.bfloat16))],
+                          state={"backbone": dict(lo=lo, m=2 * master, v=master * master),
+                                 "other@8": dict(master=torch.arange(10.0), m=torch.ones(10), v=torch.ones(10))})
+    det = {"semantic_loss": torch.tensor(1.5), "acoustic_loss": torch.tensor(2.5)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), opt, torch.tensor(152.5), det)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["loss.npy", "semantic_loss.npy", "acoustic_loss.npy"] +
+                           [f"{k}_{t}.npy" for k in ("master", "adam_m", "adam_v") for t in ("backbone", "other_8")])
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == 152.5
+    mb, m_b = np.load(tmp_path / "a" / "master_backbone.npy"), np.load(tmp_path / "a" / "adam_m_backbone.npy")
+    assert 0 < mb.size < master.numel() and np.array_equal(2 * mb, m_b)      # exact masters, same indices for every kind
+    assert np.isin(mb, master.numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "master_other_8.npy"), np.arange(10, dtype=np.float32))
 
 
 def test_bench_launches_and_verifies_its_own_ranks():

@@ -3,6 +3,7 @@ tensors, so the collective itself is not RCCL here; everything else - hooks, buc
 1/world, clip on reduced gradients - is the production path)."""
 import os
 import sys
+import tempfile
 
 import pytest
 import torch
@@ -28,7 +29,7 @@ def _worker(rank, world, port, q, mode):
     cfg = O.tiny_cfg()
     m = Model(ModelArgs("llama-tiny-backbone", "llama-tiny-decoder", cfg.text_vocab, cfg.audio_vocab, cfg.n_codebooks), device="cuda:0", seed=3)
     m.acoustic_mode = "all"
-    tr = CSMTrainer("", f"/tmp/csm_dp_test_{port}_{rank}", device="cuda:0")
+    tr = CSMTrainer("", tempfile.mkdtemp(prefix=f"csm_dp_test_{port}_{rank}_"), device="cuda:0")
     tr.logger.setLevel(40)
     tr.model = m
     if mode == "lora":
@@ -64,7 +65,7 @@ def _single(mode):
     cfg = O.tiny_cfg()
     m = Model(ModelArgs("llama-tiny-backbone", "llama-tiny-decoder", cfg.text_vocab, cfg.audio_vocab, cfg.n_codebooks), device="cuda:0", seed=3)
     m.acoustic_mode = "all"
-    tr = CSMTrainer("", "/tmp/csm_dp_test_single", device="cuda:0")
+    tr = CSMTrainer("", tempfile.mkdtemp(prefix="csm_dp_test_single_"), device="cuda:0")
     tr.logger.setLevel(40)
     tr.model = m
     if mode == "lora":
@@ -341,7 +342,7 @@ def _rccl_worker(port, q):
     def build(seed):
         m = Model(ModelArgs("llama-tiny-backbone", "llama-tiny-decoder", cfg.text_vocab, cfg.audio_vocab, cfg.n_codebooks), device="cuda:0", seed=seed)
         m.acoustic_mode = "all"
-        tr = CSMTrainer("", f"/tmp/csm_rccl_test_{port}_{seed}", device="cuda:0")
+        tr = CSMTrainer("", tempfile.mkdtemp(prefix=f"csm_rccl_test_{port}_{seed}_"), device="cuda:0")
         tr.logger.setLevel(40)
         tr.model = m
         return m, tr

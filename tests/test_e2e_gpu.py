@@ -139,7 +139,7 @@ def test_train_step_full(dev):
         assert torch.equal(dict(m.named_parameters())[k].detach().contiguous().view(torch.int16).cpu(), want), k
 
 
-def test_post_adamw_parameters_match_fixture(dev):
+def test_post_adamw_parameters_match_fixture(dev, tmp_path):
     """the parameters AFTER one CSMTrainer step (clip 1.0, four learning-rate groups x0.1 / x1 / x0.5 / x1,
     weight decay 0.01) against values produced by torch's own clip_grad_norm_ + AdamW on the oracle's fp32 gradients."""
     from csm.training.trainer import CSMTrainer
@@ -151,7 +151,7 @@ def test_post_adamw_parameters_match_fixture(dev):
     tokens, mask, targets = (torch.from_numpy(z[k]) for k in ("tokens", "mask", "targets"))
     B, S = tokens.shape[:2]
     rows = torch.arange(0, B * (S - 1), meta["train_step"]["rows_stride"])
-    tr = CSMTrainer("", "/tmp/csm_post_adamw", device=str(dev), learning_rate=cfgp["lr"], backbone_lr_multiplier=cfgp["multipliers"][0],
+    tr = CSMTrainer("", str(tmp_path), device=str(dev), learning_rate=cfgp["lr"], backbone_lr_multiplier=cfgp["multipliers"][0],
                     decoder_lr_multiplier=cfgp["multipliers"][1], embedding_lr_multiplier=cfgp["multipliers"][2], weight_decay=cfgp["weight_decay"])
     tr.logger.setLevel(40)
     tr.model = m
@@ -902,7 +902,7 @@ def test_full_size_model_properties(dev):
     assert rel(tg, to) < 1e-3, (float(tg), float(to))
 
 
-def test_full_size_acoustic_and_adamw_vs_oracle(dev):
+def test_full_size_acoustic_and_adamw_vs_oracle(dev, tmp_path):
     """CSM-1B (real widths, 16 + 4 layers) at a sequence short enough for the CPU oracle: semantic AND acoustic loss terms,
     the global gradient norm, and one clipped AdamW step with the reference's four learning-rate groups, against the
     oracle run on the same weights (bf16 values widened to fp32)."""
@@ -916,7 +916,7 @@ def test_full_size_acoustic_and_adamw_vs_oracle(dev):
     batch = collate_variable_length([SyntheticCSMDataset(1, S, seed=91)[0]])
     rows = torch.tensor([3, 17, 29, 30, 41, 52, 60, 62])
     lr = 1e-3
-    tr = CSMTrainer("", "/tmp/csm_full_adamw", device=str(dev), learning_rate=lr)
+    tr = CSMTrainer("", str(tmp_path), device=str(dev), learning_rate=lr)
     tr.logger.setLevel(40)
     tr.model = m
     params = {k: v.float().cpu() for k, v in m._views(m.arena).items()}          # before the step
