@@ -34,9 +34,33 @@ def parse_args(argv=None):
     t.add_argument("--acoustic-mode", choices=["off", "all", "amortized"], default="off")
     p.add_argument("--log-level", type=str, default="info")
     p.add_argument("--debug", action="store_true")
-    p.add_argument("--generate-samples", action="store_true")
+    p.add_argument("--generate-samples", action="store_true",
+                   help="after saving, write {output-dir}/sample.wav from the trained adapters (needs --mimi-weights, --text-tokenizer)")
     p.add_argument("--sample-prompt", type=str, default="Hello, this is a test of the fine-tuned voice.")
     return p.parse_args(argv)
+
+
+def sample_tokenizers(args, device):
+    """(text tokenizer, Mimi codec) for ``--generate-samples``: the local files ``--text-tokenizer`` / ``--mimi-weights`` stand for
+    what the reference downloads (cli/generate.py)."""
+    from ..codec import load_mimi
+    from ..generator import load_llama3_tokenizer
+    text = load_llama3_tokenizer(args.text_tokenizer) if args.text_tokenizer else None
+    audio = load_mimi(args.mimi_weights, device=device) if args.mimi_weights else None
+    return text, audio
+
+
+def generate_sample(trainer, args, device):
+    """Reference finetune_lora.py:462-476: a sample from the final adapters; a failure is logged, the run still succeeds."""
+    path = f"{args.output_dir}/sample.wav"
+    try:
+        text_tok, audio_tok = sample_tokenizers(args, device)
+        trainer.generate_sample(args.sample_prompt, args.speaker_id, path, text_tokenizer=text_tok, audio_tokenizer=audio_tok)
+        trainer.logger.info(f"Generated sample: {path}")
+    except Exception as e:                         # noqa: BLE001 - a sample is a by-product of the run
+        trainer.logger.error(f"Error generating sample: {e}")
+        return None
+    return path
 
 
 def main(argv=None):
@@ -61,6 +85,8 @@ def main(argv=None):
     if rank == 0:
         trainer.save_model(f"{args.output_dir}/final", args.save_mode)
         trainer.logger.info(f"best validation loss: {best}")
+        if args.generate_samples:
+            generate_sample(trainer, args, f"cuda:{local}")
     return 0
 
 

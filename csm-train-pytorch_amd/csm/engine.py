@@ -12,6 +12,7 @@ With 288 GB of HBM nothing is recomputed.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Dict, List, Optional
 
 import torch
@@ -48,6 +49,34 @@ EMB_KEYSORT = _os.environ.get("CSM_EMB_KEYSORT", "1") == "1"
 DECODE_POS_HOST = _os.environ.get("CSM_DECODE_POS_HOST", "1") == "1"
 # LoRA groups ride on the frozen projections' GEMMs as K-extension operands (training/lora.py); 0 = per-adapter products
 LORA_FUSE = _os.environ.get("CSM_LORA_FUSE", "1") != "0"
+
+
+@contextmanager
+def generation_lora(model):
+    """What generation does with the adapters of ``model`` around a pass through the training forward (prefill, recompute):
+    yields the LoRAState to apply, or None.  Adapters are read, never trained: dropout is off (``lora.training`` False, the
+    previous value restored afterwards, also on an error; no mask is drawn, ``lora.draws`` does not move) and the transposed
+    copies the fused forward reads (``refresh``) are renewed, as the adapters may have moved since the last loss.  Adapters that
+    ``merge_lora_weights`` folded into the base weights stay attached but are not applied a second time."""
+    lo = model.lora
+    if lo is None:
+        yield None
+        return
+    if lo.merged:
+        model.lora = None
+        try:
+            yield None
+        finally:
+            model.lora = lo
+        return
+    was = lo.training
+    lo.training = False
+    try:
+        if LORA_FUSE:
+            lo.refresh()
+        yield lo
+    finally:
+        lo.training = was
 
 
 class _Stack:
@@ -774,6 +803,10 @@ class Engine:
     @torch.no_grad()
     def _generate_frame_recompute(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None):
         """Reference model.py:140-195.  The KV state is the token history (prefix recompute)."""
+        with generation_lora(self.m):
+            return self._generate_frame_recompute_body(tokens, tokens_mask, input_pos, temperature, topk, noise)
+
+    def _generate_frame_recompute_body(self, tokens, tokens_mask, input_pos, temperature, topk, noise):
         m, a = self.m, self.m.args
         dev = m.device
         K, V, Vp = a.audio_num_codebooks, a.audio_vocab_size, m.vocab_pad
@@ -841,6 +874,8 @@ class _DecodeStack:
         self.fuse_attn = B == 1 and s_max <= 64 and hd == 128 and os.environ.get("CSM_DECODE_FUSE_ATTN", "1") == "1"
         # the position as a host integer where the caller knows it (the depth decoder: step i is at position i): see ops.gemv_attn
         self.pos_host = None
+        # LoRA groups (DecodeState.__init__): per layer {group name: (At, Bx, bias or None)}, and the [B, KX] extension operand
+        self.lora, self.lora_scale, self.lt = None, 1.0, None
 
     def fill_from(self, acts, B, S):
         """Copy the post-RoPE K / V rows of a prefilled prompt into the caches."""
@@ -868,6 +903,9 @@ class _DecodeStack:
         table = st.m.rope_table(st.prefix)
         cur, nxt = x, self.xa
         for i in range(c.num_layers):
+            if self.lora is not None and self.lora[i]:
+                cur, nxt = self._lora_layer(i, cur, nxt, table)
+                continue
             # five launches per layer (four in the depth decoder): the norms ride in the prologue of the following matrix-vector
             # product, RoPE and the cache append inside the attention kernel, SwiGLU in the epilogue of the w13 product
             ops.gemv_ex(cur, st.w(f"layers.{i}.attn.qkv"), self.qkv, norm_scale=st.w(f"layers.{i}.sa_norm.scale"), eps=c.norm_eps)
@@ -887,14 +925,71 @@ class _DecodeStack:
         ops.rmsnorm_fwd(cur, st.w("norm.scale"), self.xf, None, c.norm_eps)
         return self.xf
 
+    def _lora_product(self, G, x, W, y, **kw):
+        """One product of a layer step: plain (``G`` None) or extended by a LoRA group - t = s x^ At, then the same product
+        with (t, Bx, bias) as K-extension (norm prologue, SwiGLU and residual stay fused exactly as in the plain step)."""
+        if G is None:
+            return ops.gemv_ex(x, W, y, **kw)
+        At, Bx, bias = G
+        t = self.lt[:, :At.shape[1]]
+        ops.lora_project(x, At, t, self.lora_scale, norm_scale=kw.get("norm_scale"), eps=kw.get("eps", 1e-5))
+        return ops.gemv_kext(x, W, y, t, Bx, bias=bias, **kw)
+
+    def _lora_layer(self, i, cur, nxt, table):
+        """``step``'s layer ``i`` with adapters: each group present runs its projection and the extended product in place of
+        the plain one.  An ``attn_out`` group takes the unfused attention (attn_decode_rope, then the extended product)."""
+        st, c, L = self.stack, self.stack.c, self.lora[i]
+        H, KV, hd = c.num_heads, c.num_kv_heads, c.head_dim
+        self._lora_product(L.get("attn_in"), cur, st.w(f"layers.{i}.attn.qkv"), self.qkv, norm_scale=st.w(f"layers.{i}.sa_norm.scale"),
+                           eps=c.norm_eps)
+        if self.fuse_attn and "attn_out" not in L:
+            ops.gemv_attn(self.qkv, self.k[i], self.v[i], self.pos, table, st.w(f"layers.{i}.attn.output_proj.weight"), self.h, cur,
+                          H, KV, hd, pos_host=self.pos_host)
+        else:
+            ops.attn_decode_rope(self.qkv, self.k[i], self.v[i], self.o, self.pos, table, H, KV, hd, pos_host=self.pos_host)
+            self._lora_product(L.get("attn_out"), self.o, st.w(f"layers.{i}.attn.output_proj.weight"), self.h, residual=cur)
+        self._lora_product(L.get("mlp_in"), self.h, st.w(f"layers.{i}.mlp.w13"), self.act, norm_scale=st.w(f"layers.{i}.mlp_norm.scale"),
+                           eps=c.norm_eps, swiglu=True)
+        self._lora_product(L.get("mlp_out"), self.act, st.w(f"layers.{i}.mlp.w2.weight"), nxt, residual=self.h)
+        return nxt, (self.xb if nxt is self.xa else self.xa)
+
+    def attach_lora(self, lo):
+        """Bind the active adapters of this stack: arena views of every group's At / Bx (read in place, so a captured graph
+        sees what ``load_lora_weights`` or an optimiser writes there) and the group's bias vector in the fused projection's row
+        order, built once here (the same pattern as ``DecodeState.head_t``)."""
+        st, c = self.stack, self.stack.c
+        hq, hk, F, d = c.num_heads * c.head_dim, c.num_kv_heads * c.head_dim, c.intermediate_dim, c.embed_dim
+        rows = {"q_proj": slice(0, hq), "k_proj": slice(hq, hq + hk), "v_proj": slice(hq + hk, hq + 2 * hk), "output_proj": slice(0, d),
+                "w1": slice(0, 2 * F, 2), "w3": slice(1, 2 * F, 2), "w2": slice(0, d)}
+        plan, kmax = [], 0
+        for i in range(c.num_layers):
+            L = {}
+            for gname in ("attn_in", "attn_out", "mlp_in", "mlp_out"):
+                G = lo.group(st.prefix, i, gname)
+                if G is None:
+                    continue
+                if G.kx > 512:
+                    raise ValueError(f"generate with LoRA adapters: {G.kx} extension columns in {G.name} (the decode kernels take "
+                                     "at most 512: rank x adapters per fused projection)")
+                bias = None
+                if any(ad.bias is not None for ad in G.adapters.values()):
+                    bias = torch.zeros(G.Bx.shape[0], dtype=BF16, device=G.Bx.device)
+                    for mod, ad in G.adapters.items():
+                        if ad.bias is not None:
+                            bias[rows[mod]] = ad.bias
+                L[gname] = (G.At, G.Bx, bias)
+                kmax = max(kmax, G.kx)
+            plan.append(L)
+        if kmax:
+            self.lora, self.lora_scale = plan, lo.scaling
+            self.lt = torch.zeros(self.B, kmax, dtype=BF16, device=self.k[0].device)
+
 
 class DecodeState:
     """Everything ``generate_frame`` keeps between calls: the two stacks' caches and small persistent buffers."""
 
     def __init__(self, engine: "Engine", B: int):
         m = engine.m
-        if m.lora is not None:
-            raise NotImplementedError("generate with un-merged LoRA adapters: call model.merge_lora_weights() first")
         if B > 4:
             raise ValueError("the decode kernels handle up to 4 sequences at a time")
         self.e, self.B = engine, B
@@ -913,6 +1008,10 @@ class DecodeState:
         # audio_head is stored [K-1][d'][V] (reference layout, a K-major matrix for x @ W); the decode path wants one
         # output row per wave, so it keeps a [K-1][V][d'] copy made from the current weights when the state is created
         self.head_t = m.block("audio_head.padded").transpose(1, 2).contiguous()
+        # live LoRA adapters ride on the decode products as K-extensions (merged ones are already in the weights)
+        if m.lora is not None and not m.lora.merged:
+            self.bb.attach_lora(m.lora)
+            self.dc.attach_lora(m.lora)
 
     def fill_noise(self, noise=None):
         """``noise``: K tensors [B, V] of Exp(1) draws (pins the sampler), or None for fresh draws from torch's generator."""
@@ -932,7 +1031,8 @@ class DecodeState:
         mk = masks.reshape(M, K1).to(torch.uint8).contiguous()
         h0 = torch.empty(M, m.bb.embed_dim, dtype=BF16, device=m.device)
         ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
-        hidden = e.backbone.forward(h0, B, S, True)
+        with generation_lora(m):
+            hidden = e.backbone.forward(h0, B, S, True)
         self.bb.fill_from(e.backbone.acts, B, S)
         e.backbone.acts = []
         self.bb.pos.fill_(S - 1)
@@ -952,7 +1052,8 @@ class DecodeState:
             mk = mk.to(device=m.device, dtype=torch.uint8).contiguous()
             h0 = torch.empty(S, m.bb.embed_dim, dtype=BF16, device=m.device)
             ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
-            hidden = e.backbone.forward(h0, 1, S, True)
+            with generation_lora(m):
+                hidden = e.backbone.forward(h0, 1, S, True)
             self.bb.fill_row(e.backbone.acts, b, S)
             e.backbone.acts = []
             self.bb.pos[b] = S - 1

@@ -414,6 +414,38 @@ def gemv_ex(x, W, y, residual=None, norm_scale=None, eps=1e-5, swiglu=False, row
     return y
 
 
+def lora_project(x, At, t, scale, norm_scale=None, eps=1e-5):
+    """t[B, kx] = scale * x^ At (bf16), x^ = x or its RMSNorm (norm_scale): the extension operand of ``gemv_kext`` for a LoRA
+    group whose At [K, kx] is read in place (training/lora.py)."""
+    B, K = x.shape
+    kx = At.shape[1]
+    assert At.shape[0] == K and t.shape == (B, kx) and x.stride(1) == 1 and At.stride(1) == 1 and t.stride(1) == 1
+    assert x.dtype == At.dtype == t.dtype == BF16
+    check(lib.csm_lora_project_bf16(x.data_ptr(), At.data_ptr(), t.data_ptr(), B, K, kx, x.stride(0), At.stride(0), t.stride(0),
+                                    float(scale), _ptr(norm_scale), float(eps), _stream()), "csm_lora_project_bf16")
+    return t
+
+
+def gemv_kext(x, W, y, ext_t, ext_B, residual=None, norm_scale=None, eps=1e-5, swiglu=False, row_index=None, row_offset=0,
+              bias=None):
+    """``gemv_ex`` with a LoRA group as K-extension: y = epilogue(x^ W^T + ext_t ext_B^T + bias).  ext_t [B, kx] from
+    ``lora_project``; ext_B [N, kx] and bias [N] in W's row order."""
+    B = y.shape[0]
+    K = x.shape[1]
+    N = W.shape[0]
+    kx = ext_B.shape[1]
+    assert W.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W.stride(1) == 1 and y.stride(1) == 1
+    assert row_index is not None or x.shape[0] == B
+    assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
+    assert ext_t.shape == (B, kx) and ext_B.shape[0] == N and ext_t.stride(1) == 1 and ext_B.stride(1) == 1
+    assert bias is None or (bias.shape == (N,) and bias.is_contiguous() and bias.dtype == BF16)
+    check(lib.csm_gemv_bf16_kext(x.data_ptr(), W.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K, W.stride(0), x.stride(0),
+                                 y.stride(0), int(y.dtype == torch.float32), _ptr(norm_scale), float(eps), int(swiglu),
+                                 _ptr(row_index), int(row_offset), ext_t.data_ptr(), ext_B.data_ptr(), kx, ext_t.stride(0),
+                                 ext_B.stride(0), _ptr(bias), _stream()), "csm_gemv_bf16_kext")
+    return y
+
+
 def attn_decode_rope(qkv, kcache, vcache, out, pos_i32, table, H, KV, HD, pos_host=None):
     """rope(q, new k) + append(new k, v) + one-position attention against the caches, one launch.  ``pos_host``: the position all
     rows share, as a host integer (the depth decoder's step; HD = 128, H = 4 KV, S_max <= 32): the launch that issues every load

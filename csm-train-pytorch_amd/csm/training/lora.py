@@ -175,6 +175,8 @@ class LoRAState:
         self.r, self.r_pad, self.alpha, self.dropout, self.scaling = r, (r + 7) // 8 * 8, alpha, dropout, alpha / r
         self.target_modules, self.target_layers, self.use_bias = list(target_modules), target_layers, use_bias
         self.training, self.draws = True, 0        # dropout is live only while training; draws counts masks drawn
+        # set by merge_lora_weights: the adapters are also in the base weights, so generation must not apply them again
+        self.merged = False
         for mod in target_modules:
             if mod not in GROUP_OF:
                 raise ValueError(f"unknown LoRA target module {mod!r}")
@@ -303,5 +305,6 @@ def merge_lora_weights(model):
         sub = "attn" if mod in ATTN else "mlp"
         W = views[f"{prefix}.layers.{i}.{sub}.{mod}.weight"]
         ops.gemm(ad.B, ad.At, W, W, False, False, alpha=lo.scaling)
+    lo.merged = True
     model.params_rewritten(lora=False)        # an optimiser over the base weights must not keep the old lower halves
     return model

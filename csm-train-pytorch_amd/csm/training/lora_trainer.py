@@ -209,10 +209,11 @@ class CSMLoRATrainer:
                 json.dump(meta, f, indent=2)
         if save_mode in ("full", "both"):
             path = base + ("_full" if save_mode == "both" else "") + ".safetensors"
-            backup = self.model.arena.clone()
+            backup, was_merged = self.model.arena.clone(), lo.merged
             merge_lora_weights(self.model)
             sd = {k: v.detach().cpu().contiguous() for k, v in self.model._views(self.model.arena).items()}
             self.model.arena.copy_(backup)
+            lo.merged = was_merged
             self.model.params_rewritten(lora=False)
             save_file(sd, path)
         return base
@@ -233,10 +234,22 @@ class CSMLoRATrainer:
         if self.optimizer is not None and "lora" in self.optimizer.state:
             self.optimizer.set_master("lora", self.model.lora.arena.float())
 
-    def generate_sample(self, text: str, speaker_id: int = 0, output_path: str = "sample.wav") -> str:
-        """Reference lora_trainer.py:635-700."""
+    def generate_sample(self, text: str, speaker_id: int = 0, output_path: str = "sample.wav", *, text_tokenizer=None,
+                        audio_tokenizer=None, max_audio_length_ms: float = 10_000, temperature: float = 0.9, topk: int = 50) -> str:
+        """Reference lora_trainer.py:635-700: speech from the live adapters (no merge, no copy of the weights).  The two
+        tokenizers the reference loads from the hub are injected (``Generator``).  Generation runs the adapters without
+        dropout and leaves them, the optimiser state and ``lora.training`` as they were: training continues as if no sample
+        had been drawn (the sampler's noise comes from torch's generator, as in ``Generator.generate``)."""
         from ..generator import Generator
-        gen = Generator(self.model)
-        audio = gen.generate(text=text, speaker=speaker_id, context=[])
+        gen = Generator(self.model, text_tokenizer=text_tokenizer, audio_tokenizer=audio_tokenizer)
+        try:
+            audio = gen.generate(text=text, speaker=speaker_id, context=[], max_audio_length_ms=max_audio_length_ms,
+                                 temperature=temperature, topk=topk)
+        finally:
+            self.model.reset_caches()             # the decode state (KV caches, captured graph) is not kept past the sample
+        d = os.path.dirname(output_path)
+        if d:
+            os.makedirs(d, exist_ok=True)
         gen.save_wav(output_path, audio)
+        self.logger.info(f"Sample written to {output_path} ({audio.numel() / gen.sample_rate:.2f} s)")
         return output_path

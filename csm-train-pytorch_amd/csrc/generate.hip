@@ -321,6 +321,33 @@ extern "C" int csm_rvq_decode(const long long* codes, const float* codebooks, fl
 // between waves) and reduce with wave shuffles.
 namespace {
 
+// K-extension of a decode product (a LoRA group, training/lora.py): output row n also takes sum_j t[b][j] Bx[n][j] (+ bias[n])
+// - the group's adapters as extra k-steps of the frozen projection, before the residual / SwiGLU / fp32-output epilogue, as
+// csm_gemm_bf16_kext does in training.  The kernels below take it as a trailing argument PACK: the plain instantiations have an
+// empty pack, so their signature and code are what they were.  Lane l owns the extension's 8-element chunk l (kx <= 512), loaded
+// beside the weights; its products are added to the lane's partial sum AFTER the main k-loop (the main partial sums keep their
+// order: Bx = 0 leaves every bit of the plain product) by explicit fused multiply-adds in ascending j - the same operations in
+// every kernel, so a B-row launch stays bit-equal per row to the one-row launch.
+struct GemvExt {
+    const bf16_t* t;      // [B][ldt]  s x^ At, bf16 (csm_lora_project_bf16)
+    const bf16_t* Bx;     // [N][ldb]  rows in the fused projection's order (w13: gate / up interleaved)
+    const bf16_t* bias;   // [N] or NULL
+    int kx, ldt, ldb;
+};
+__device__ __forceinline__ const GemvExt& ext_arg(const GemvExt& e) { return e; }
+__device__ __forceinline__ U4 ext_load(const bf16_t* row, int lane, int kx) {
+    U4 z = {0u, 0u, 0u, 0u};
+    return lane < (kx >> 3) ? *reinterpret_cast<const U4*>(row + lane * 8) : z;
+}
+__device__ __forceinline__ float ext_fma(float acc, const U4& b, const U4& t) {
+    float bf[8], tf[8];
+    unpack8(b, bf);
+    unpack8(t, tf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc = __builtin_fmaf(bf[j], tf[j], acc);
+    return acc;
+}
+
 // y[b][n] = sum_k x[b][k] * W[n][k] (+ R[b][n]);  one wave per output row, NB <= 4 batch rows share every weight load.
 // Two optional fusions remove the tiny kernels that otherwise sit between the matrix-vector products of a decode step:
 //   norm_w != NULL : x is RMS-normalised on its way into LDS (same arithmetic and summation order as rmsnorm_fwd_kernel:
@@ -328,11 +355,12 @@ namespace {
 //   SWIGLU         : W holds gate/up rows interleaved (w13); a wave computes rows 2i and 2i+1 and writes
 //                    y[b][i] = silu(g) * u with g, u rounded to bf16 first (what swiglu_fwd_kernel reads back);
 //   row_index      : batch row b of x is row (row_index[b] + row_offset) of a table (the embedding of a sampled code).
-template <int NB, typename OutT, bool SWIGLU>
+template <int NB, typename OutT, bool SWIGLU, typename... Ext>
 __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, OutT* __restrict__ y,
                                                    const bf16_t* __restrict__ R, int N, int K, int ldw, int ldx, int ldy,
                                                    const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
-                                                   int row_offset) {
+                                                   int row_offset, Ext... ext) {
+    constexpr bool EXT = sizeof...(Ext) > 0;
     extern __shared__ __attribute__((aligned(16))) char smem_x[];
     bf16_t* xs = reinterpret_cast<bf16_t*>(smem_x);            // [NB][K]
     __shared__ float rs[4];
@@ -393,11 +421,28 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
                     for (int j = 0; j < 8; ++j) acc[r][b] += wf[r][j] * xf[j];
             }
         }
+        float bias[RW];
+#pragma unroll
+        for (int r = 0; r < RW; ++r) bias[r] = 0.f;
+        if constexpr (EXT) {
+            __builtin_amdgcn_sched_barrier(0);                // (the extension's loads stay behind the main products: registers)
+            const GemvExt& e = ext_arg(ext...);
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                const U4 eb = ext_load(e.Bx + (size_t)(n * RW + r) * e.ldb, lane, e.kx);
+#pragma unroll
+                for (int b = 0; b < NB; ++b) acc[r][b] = ext_fma(acc[r][b], eb, ext_load(e.t + (size_t)b * e.ldt, lane, e.kx));
+                if (e.bias) bias[r] = bf2f(e.bias[n * RW + r]);
+            }
+        }
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             float v = wave_sum(acc[0][b]);
+            if constexpr (EXT) v += bias[0];
             if constexpr (SWIGLU) {
-                const float g = bf2f(f2bf(v)), u = bf2f(f2bf(wave_sum(acc[1][b])));
+                float us = wave_sum(acc[1][b]);
+                if constexpr (EXT) us += bias[1];
+                const float g = bf2f(f2bf(v)), u = bf2f(f2bf(us));
                 v = silu(g) * u;
             }
             if (lane == 0) {
@@ -422,11 +467,12 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
 // row sums share one butterfly: v_permlane32_swap(gate, up) leaves the gate partials in lanes 0-31 and the up partials in lanes
 // 32-63, the remaining xor-16 .. xor-1 steps never cross the halves - the same additions as two separate wave_sum() calls, so the
 // same bits.
-template <int KCH, typename OutT, bool SWIGLU, bool NT, int RPW = 1>
+template <int KCH, typename OutT, bool SWIGLU, bool NT, int RPW = 1, typename... Ext>
 __global__ __launch_bounds__(256) void gemv_reg_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, OutT* __restrict__ y,
                                                        const bf16_t* __restrict__ R, int N, int ldw, int ldx, int ldy,
                                                        const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
-                                                       int row_offset) {
+                                                       int row_offset, Ext... ext) {
+    constexpr bool EXT = sizeof...(Ext) > 0;
     constexpr int K = 512 * KCH;
     constexpr int RW = SWIGLU ? 2 : 1;
     const int lane = threadIdx.x & 63;
@@ -506,6 +552,23 @@ __global__ __launch_bounds__(256) void gemv_reg_kernel(const bf16_t* __restrict_
             }
     }
     STAMP(4);
+    float bias[RPW][RW];
+#pragma unroll
+    for (int o = 0; o < RPW; ++o)
+#pragma unroll
+        for (int r = 0; r < RW; ++r) bias[o][r] = 0.f;
+    if constexpr (EXT) {
+        __builtin_amdgcn_sched_barrier(0);                    // (the extension's loads stay behind the main products: registers)
+        const GemvExt& e = ext_arg(ext...);
+        const U4 et = ext_load(e.t, lane, e.kx);
+#pragma unroll
+        for (int o = 0; o < RPW; ++o)
+#pragma unroll
+            for (int r = 0; r < RW; ++r) {
+                acc[o][r] = ext_fma(acc[o][r], ext_load(e.Bx + (size_t)(min(n0 + o, NO - 1) * RW + r) * e.ldb, lane, e.kx), et);
+                if (e.bias) bias[o][r] = bf2f(e.bias[min(n0 + o, NO - 1) * RW + r]);
+            }
+    }
 #pragma unroll
     for (int o = 0; o < RPW; ++o) {
         float v;
@@ -514,12 +577,14 @@ __global__ __launch_bounds__(256) void gemv_reg_kernel(const bf16_t* __restrict_
             auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[o][0]), __float_as_uint(acc[o][1]), false, false);
             float t = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
             t += lane_xor<16>(t); t += lane_xor<8>(t); t += lane_xor<4>(t); t += lane_xor<2>(t); t += lane_xor<1>(t);
-            const float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
-            const float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+            float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
+            float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+            if constexpr (EXT) { gs += bias[o][0]; us += bias[o][1]; }
             const float g = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
             v = silu(g) * u;
         } else {
             v = wave_sum(acc[o][0]);
+            if constexpr (EXT) v += bias[o][0];
         }
         if (lane == 0 && n0 + o < NO) {
             if (R) v += bf2f(R[n0 + o]);
@@ -543,11 +608,12 @@ __global__ __launch_bounds__(256) void gemv_reg_kernel(const bf16_t* __restrict_
 typedef float csm_f2 __attribute__((ext_vector_type(2)));
 // SC = chunks per segment: K = 8192 (KCH = 16) walks x in four segments of four chunks (the fp32 rows stay in LDS, 128 KB at four
 // rows; a segment's elements are in registers while its weight chunks are multiplied), K <= 2048 is one segment.
-template <int KCH, int NB, typename OutT, bool SWIGLU, bool NT, int SC = KCH>
+template <int KCH, int NB, typename OutT, bool SWIGLU, bool NT, int SC = KCH, typename... Ext>
 __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, OutT* __restrict__ y,
                                                         const bf16_t* __restrict__ R, int N, int ldw, int ldx, int ldy,
                                                         const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
-                                                        int row_offset) {
+                                                        int row_offset, Ext... ext) {
+    constexpr bool EXT = sizeof...(Ext) > 0;
     constexpr int K = 512 * KCH;
     constexpr int RW = SWIGLU ? 2 : 1;
     constexpr int NP = (NB + 1) / 2;                                        // row pairs (the last one half empty for odd NB)
@@ -641,21 +707,39 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
             }
         }
     }
+    float bias[RW];
+    U4 eb[RW];
+#pragma unroll
+    for (int r = 0; r < RW; ++r) bias[r] = 0.f;
+    if constexpr (EXT) {
+        __builtin_amdgcn_sched_barrier(0);                    // (the extension's loads stay behind the main products: registers)
+        const GemvExt& e = ext_arg(ext...);
+#pragma unroll
+        for (int r = 0; r < RW; ++r) {
+            eb[r] = ext_load(e.Bx + (size_t)((live ? n : NO - 1) * RW + r) * e.ldb, lane, e.kx);
+            if (e.bias) bias[r] = bf2f(e.bias[(live ? n : NO - 1) * RW + r]);
+        }
+    }
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        const float a0 = (b & 1) ? acc[0][b >> 1].y : acc[0][b >> 1].x;
+        float a0 = (b & 1) ? acc[0][b >> 1].y : acc[0][b >> 1].x;
+        U4 et;
+        if constexpr (EXT) { et = ext_load(ext_arg(ext...).t + (size_t)b * ext_arg(ext...).ldt, lane, ext_arg(ext...).kx); a0 = ext_fma(a0, eb[0], et); }
         float v;
         if constexpr (SWIGLU) {
-            const float a1 = (b & 1) ? acc[1][b >> 1].y : acc[1][b >> 1].x;
+            float a1 = (b & 1) ? acc[1][b >> 1].y : acc[1][b >> 1].x;
+            if constexpr (EXT) a1 = ext_fma(a1, eb[1], et);
             auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
             float t = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
             t += lane_xor<16>(t); t += lane_xor<8>(t); t += lane_xor<4>(t); t += lane_xor<2>(t); t += lane_xor<1>(t);
-            const float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
-            const float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+            float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
+            float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+            if constexpr (EXT) { gs += bias[0]; us += bias[1]; }
             const float g = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
             v = silu(g) * u;
         } else {
             v = wave_sum(a0);
+            if constexpr (EXT) v += bias[0];
         }
         if (lane == 0 && live) {
             if (R) v += bf2f(R[(size_t)b * ldy + n]);
@@ -1305,6 +1389,72 @@ __global__ __launch_bounds__(256) void attn_decode_at_kernel(const bf16_t* __res
     }
 }
 
+// The first half of a LoRA group's K-extension at decode time: t[b][0:kx] = s * x^[b] . At, rounded to bf16 once (the rounding of
+// LoRAGroup.project in training), x^ = x or - norm_w != NULL - x RMS-normalised exactly as the gemv prologues leave it (sum of
+// squares over lane-strided 8-element chunks of one wave, wave_sum, x * rstd * w rounded to bf16), so the adapters see the same
+// input as the frozen product they extend.  At [K][lda] is read in its arena layout.  One workgroup per 8 columns of t; thread i
+// takes rows k = i, i + 512, ... of At (16 bytes each) and every batch row; partials are reduced by wave butterflies and then
+// across the eight waves in a fixed order: deterministic, and row b never depends on the other rows.
+template <int NB>
+__global__ __launch_bounds__(512) void lora_project_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ At, bf16_t* __restrict__ t,
+                                                           int K, int ldx, int lda, int ldt, const bf16_t* __restrict__ norm_w, float eps,
+                                                           float scale) {
+    __shared__ float rs[4];
+    __shared__ float part[8][NB][8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = blockIdx.x * 8;
+    if (norm_w) {
+        if (wave < NB) {
+            float ss = 0.f;
+            for (int c = lane; c < (K >> 3); c += 64) {
+                float f[8];
+                unpack8(*reinterpret_cast<const U4*>(x + (size_t)wave * ldx + c * 8), f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ss += f[j] * f[j];
+            }
+            ss = wave_sum(ss);
+            if (lane == 0) rs[wave] = rsqrtf(ss / (float)K + eps);
+        }
+        __syncthreads();
+    }
+    float r[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) r[b] = norm_w ? rs[b] : 1.f;
+    float acc[NB][8];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[b][j] = 0.f;
+#pragma unroll 4
+    for (int k = threadIdx.x; k < K; k += 512) {
+        float a[8];
+        unpack8(*reinterpret_cast<const U4*>(At + (size_t)k * lda + c0), a);
+        const float w = norm_w ? bf2f(norm_w[k]) : 1.f;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            float xv = bf2f(x[(size_t)b * ldx + k]);
+            if (norm_w) xv = bf2f(f2bf(xv * r[b] * w));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[b][j] += xv * a[j];
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float v = wave_sum(acc[b][j]);
+            if (lane == 0) part[wave][b][j] = v;
+        }
+    __syncthreads();
+    if ((int)threadIdx.x < NB * 8) {
+        const int b = threadIdx.x >> 3, j = threadIdx.x & 7;
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) v += part[w][b][j];
+        t[(size_t)b * ldt + c0 + j] = f2bf(scale * v);
+    }
+}
+
 }  // namespace
 
 #ifdef CSM_DECODE_STAMPS
@@ -1328,9 +1478,11 @@ extern "C" int csm_set_decode_tuning(int key, int value) {
     else if (key == 3) g_gemv_regn = value; else return 1;
     return 0;
 }
+// ext: empty (the plain products) or one GemvExt (csm_gemv_bf16_kext): the same dispatch, the kernels' trailing pack
+template <typename... Ext>
 static int gemv_launch(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
                        int out_f32, const void* norm_w, float eps, int swiglu, const int* row_index, int row_offset,
-                       hipStream_t stream) {
+                       hipStream_t stream, Ext... ext) {
     CSM_REQUIRE(x && W && y && B >= 1 && B <= 4 && N > 0 && K > 0 && (K & 7) == 0 && (ldw & 7) == 0 && (ldx & 7) == 0,
                 "csm_gemv_bf16: bad arguments (B=%d N=%d K=%d)", B, N, K);
     CSM_REQUIRE((size_t)B * K * 2 <= 65536, "csm_gemv_bf16: B*K too large for the LDS copy of x");
@@ -1341,16 +1493,16 @@ static int gemv_launch(const void* x, const void* W, void* y, const void* residu
         // per frame: non-temporal
         int grid = (no + 3) / 4;
         const bool nt = g_gemv_nt && (K == 2048 || (K == 8192 && N == 2048));
-#define LR(KCH, T, SW, NT_) hipLaunchKernelGGL((gemv_reg_kernel<KCH, T, SW, NT_>), dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, N, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset)
+#define LR(KCH, T, SW, NT_) hipLaunchKernelGGL((gemv_reg_kernel<KCH, T, SW, NT_, 1, Ext...>), dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, N, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset, ext...)
 #define LK(T, SW, NT_) do { if (K == 1024) LR(2, T, SW, NT_); else if (K == 2048) LR(4, T, SW, NT_); else LR(16, T, SW, NT_); } while (0)
         if (swiglu && K == 1024 && !nt && g_gemv_rpw > 1 && no >= 2048) {
             // the depth decoder's w13: several gate/up pairs per wave (one normalisation of x per wave instead of per pair)
             if (g_gemv_rpw == 2) {
                 grid = (no + 7) / 8;
-                hipLaunchKernelGGL((gemv_reg_kernel<2, bf16_t, true, false, 2>), dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (bf16_t*)y, (const bf16_t*)residual, N, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset);
+                hipLaunchKernelGGL((gemv_reg_kernel<2, bf16_t, true, false, 2, Ext...>), dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (bf16_t*)y, (const bf16_t*)residual, N, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset, ext...);
             } else {
                 grid = (no + 15) / 16;
-                hipLaunchKernelGGL((gemv_reg_kernel<2, bf16_t, true, false, 4>), dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (bf16_t*)y, (const bf16_t*)residual, N, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset);
+                hipLaunchKernelGGL((gemv_reg_kernel<2, bf16_t, true, false, 4, Ext...>), dim3(grid), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (bf16_t*)y, (const bf16_t*)residual, N, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset, ext...);
             }
         }
         else if (swiglu) { if (nt) LK(bf16_t, true, true); else LK(bf16_t, true, false); }
@@ -1366,9 +1518,9 @@ static int gemv_launch(const void* x, const void* W, void* y, const void* residu
         const int gridn = (no + 3) / 4;
         const bool nt = g_gemv_nt && (K == 2048 || (K == 8192 && N == 2048));
         const size_t ldsn = (size_t)B * K * sizeof(float);
-#define LN(KCH, NB, T, SW, NT_, SC_) do { auto kf = gemv_regn_kernel<KCH, NB, T, SW, NT_, SC_>;                                       \
+#define LN(KCH, NB, T, SW, NT_, SC_) do { auto kf = gemv_regn_kernel<KCH, NB, T, SW, NT_, SC_, Ext...>;                                       \
             if (ldsn > 65536) { static bool done_ = false; if (!done_) { (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsn); done_ = true; } } \
-            hipLaunchKernelGGL(kf, dim3(gridn), dim3(256), ldsn, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, N, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset); } while (0)
+            hipLaunchKernelGGL(kf, dim3(gridn), dim3(256), ldsn, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, N, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset, ext...); } while (0)
 #define LNB(KCH, T, SW, NT_, SC_) do { if (B == 2) LN(KCH, 2, T, SW, NT_, SC_); else if (B == 3) LN(KCH, 3, T, SW, NT_, SC_); else LN(KCH, 4, T, SW, NT_, SC_); } while (0)
 #define LNK(T, SW) do { if (K == 1024) LNB(2, T, SW, false, 2); else if (nt) LNB(4, T, SW, true, 4); else LNB(4, T, SW, false, 4); } while (0)
         if (K == 8192) { if (nt) LNB(16, bf16_t, false, true, 4); else LNB(16, bf16_t, false, false, 4); }
@@ -1381,7 +1533,7 @@ static int gemv_launch(const void* x, const void* W, void* y, const void* residu
     }
     const int grid = no / 4 < 1 ? 1 : (no / 4 > 2048 ? 2048 : no / 4);
     const size_t lds = (size_t)B * K * 2;
-#define L(NB, T, SW) hipLaunchKernelGGL((gemv_kernel<NB, T, SW>), dim3(grid), dim3(256), lds, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, N, K, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset)
+#define L(NB, T, SW) hipLaunchKernelGGL((gemv_kernel<NB, T, SW, Ext...>), dim3(grid), dim3(256), lds, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, N, K, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset, ext...)
     if (swiglu) { if (B == 1) L(1, bf16_t, true); else if (B == 2) L(2, bf16_t, true); else if (B == 3) L(3, bf16_t, true); else L(4, bf16_t, true); }
     else if (out_f32) { if (B == 1) L(1, float, false); else if (B == 2) L(2, float, false); else if (B == 3) L(3, float, false); else L(4, float, false); }
     else { if (B == 1) L(1, bf16_t, false); else if (B == 2) L(2, bf16_t, false); else if (B == 3) L(3, bf16_t, false); else L(4, bf16_t, false); }
@@ -1399,6 +1551,34 @@ extern "C" int csm_gemv_bf16_ex(const void* x, const void* W, void* y, const voi
                                 int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index,
                                 int row_offset, hipStream_t stream) {
     return gemv_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_scale, eps, swiglu, row_index, row_offset, stream);
+}
+
+// csm_gemv_bf16_ex with a LoRA group's K-extension (GemvExt): y = epilogue(x^ W^T + ext_t ext_B^T + bias), ext_t from
+// csm_lora_project_bf16.  Bit-identical to csm_gemv_bf16_ex when ext_B is all zeros.
+extern "C" int csm_gemv_bf16_kext(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw,
+                                  int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index,
+                                  int row_offset, const void* ext_t, const void* ext_B, int kx, int ld_ext_t, int ld_ext_B,
+                                  const void* bias, hipStream_t stream) {
+    CSM_REQUIRE(ext_t && ext_B && kx > 0 && kx <= 512 && (kx & 7) == 0 && ld_ext_t >= kx && ld_ext_B >= kx && (ld_ext_t & 7) == 0 &&
+                (ld_ext_B & 7) == 0 && ((uintptr_t)ext_t & 15) == 0 && ((uintptr_t)ext_B & 15) == 0,
+                "csm_gemv_bf16_kext: bad extension (kx=%d ld_t=%d ld_B=%d: needs kx <= 512, multiples of 8, 16-byte aligned rows)",
+                kx, ld_ext_t, ld_ext_B);
+    GemvExt e;
+    e.t = (const bf16_t*)ext_t; e.Bx = (const bf16_t*)ext_B; e.bias = (const bf16_t*)bias;
+    e.kx = kx; e.ldt = ld_ext_t; e.ldb = ld_ext_B;
+    return gemv_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_scale, eps, swiglu, row_index, row_offset, stream, e);
+}
+
+extern "C" int csm_lora_project_bf16(const void* x, const void* At, void* t, int B, int K, int kx, int ldx, int lda, int ldt,
+                                     float scale, const void* norm_scale, float eps, hipStream_t stream) {
+    CSM_REQUIRE(x && At && t && B >= 1 && B <= 4 && K > 0 && (K & 7) == 0 && kx > 0 && (kx & 7) == 0 && lda >= kx && ldt >= kx &&
+                (lda & 7) == 0 && ((uintptr_t)At & 15) == 0 && (!norm_scale || ((ldx & 7) == 0 && ((uintptr_t)x & 15) == 0)),
+                "csm_lora_project_bf16: bad arguments (B=%d K=%d kx=%d lda=%d ldt=%d)", B, K, kx, lda, ldt);
+#define L(NB) hipLaunchKernelGGL((lora_project_kernel<NB>), dim3(kx / 8), dim3(512), 0, stream, (const bf16_t*)x, (const bf16_t*)At, (bf16_t*)t, K, ldx, lda, ldt, (const bf16_t*)norm_scale, eps, scale)
+    if (B == 1) L(1); else if (B == 2) L(2); else if (B == 3) L(3); else L(4);
+#undef L
+    CSM_CHECK_LAUNCH("csm_lora_project_bf16");
+    return 0;
 }
 
 extern "C" int csm_gemv_t_bf16(const void* x, const void* W, void* y, int B, int N, int K, int ldw, int ldx, int ldy,

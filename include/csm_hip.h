@@ -226,6 +226,19 @@ int csm_gemv_bf16(const void* x, const void* W, void* y, const void* residual, i
 int csm_gemv_bf16_ex(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
                      int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index, int row_offset,
                      csm_stream_t stream);
+/* LoRA groups at decode time (since ABI 3, additive): t[b][0:kx] = scale * x^[b] . At (At [K][lda], a group's arena matrix),
+ * rounded to bf16 once; x^ = x, or with norm_scale != NULL the RMSNorm of x exactly as csm_gemv_bf16_ex's prologue computes it.
+ * B <= 4, kx a multiple of 8. */
+int csm_lora_project_bf16(const void* x, const void* At, void* t, int B, int K, int kx, int ldx, int lda, int ldt, float scale,
+                          const void* norm_scale, float eps, csm_stream_t stream);
+/* csm_gemv_bf16_ex with a K-extension: output row n also takes sum_j ext_t[b][j] ext_B[n][j] (+ bias[n], bias may be NULL) before
+ * the residual / SwiGLU / fp32-output epilogue (ext_B rows in W's row order: interleaved gate/up for swiglu).  kx <= 512, a
+ * multiple of 8, 16-byte aligned rows.  ext_B all zeros (no bias): bit-identical to csm_gemv_bf16_ex; row b of a B-row launch is
+ * bit-identical to the one-row launch on that row. */
+int csm_gemv_bf16_kext(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
+                       int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index, int row_offset,
+                       const void* ext_t, const void* ext_B, int kx, int ld_ext_t, int ld_ext_B, const void* bias,
+                       csm_stream_t stream);
 /* y[b][n] = sum_k x[b][k] W[k][n]  (K-major weights: audio_head[i] = [decoder_dim][vocab]) */
 int csm_gemv_t_bf16(const void* x, const void* W, void* y, int B, int N, int K, int ldw, int ldx, int ldy, int out_f32,
                     csm_stream_t stream);

@@ -2,7 +2,8 @@
 """BASELINE config 5: generate() - Mimi encode of the context + AR multi-codebook decode of 10 s of audio (125 frames) +
 Mimi decode, on one MI355X, CSM-1B random init.  Neither tokenizer can be fetched offline: the text side is a byte-level
 stand-in, the audio side is the real GPU codec (csm.codec.MimiCodec) with seeded random weights in the Hugging Face
-layout (GEN_CODEC=rvq swaps in the quantiser-only stand-in when transformers is unavailable)."""
+layout (GEN_CODEC=rvq swaps in the quantiser-only stand-in when transformers is unavailable).  GEN_LORA=q_proj,v_proj (or
+all): decode frames/s with live LoRA adapters against the same adapters merged, alternated in one process."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -100,7 +101,65 @@ def run_batch(model, nb=4, frames=125):
             "x_real_time_aggregate": round(tot * 0.08 / dt, 2)}
 
 
+def decode_fps(model, frames=100, prompt=40):
+    """Decode frames/s of ``model`` on its own: a ``prompt``-position text prompt is prefilled, then ``frames`` frames are
+    generated (frame graph replays) and timed, without codec or prefill."""
+    dev = model.device
+    K = model.args.audio_num_codebooks
+    model.setup_caches(1)
+    model.reset_caches()
+    g = torch.Generator().manual_seed(0)
+    tok = torch.zeros(1, prompt, K + 1, dtype=torch.long)
+    tok[0, :, K] = torch.randint(0, model.args.text_vocab_size, (prompt,), generator=g)
+    msk = torch.zeros(1, prompt, K + 1, dtype=torch.bool)
+    msk[0, :, K] = True
+    amask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], 1).unsqueeze(1).to(dev)
+    pad = torch.zeros(1, 1, dtype=torch.long, device=dev)
+    pos = torch.arange(prompt).unsqueeze(0).to(dev)
+    f = model.generate_frame(tok.to(dev), msk.to(dev), pos, 0.9, 50)
+    for _ in range(3):                                                       # eager frame, capture, first replay
+        pos = pos[:, -1:] + 1
+        f = model.generate_frame(torch.cat([f.long(), pad], 1).unsqueeze(1), amask, pos, 0.9, 50)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    for _ in range(frames):
+        pos = pos[:, -1:] + 1
+        f = model.generate_frame(torch.cat([f.long(), pad], 1).unsqueeze(1), amask, pos, 0.9, 50)
+    torch.cuda.synchronize()
+    return frames / (time.time() - t0)
+
+
+def lora_main(mods):
+    """GEN_LORA=q_proj,v_proj (config 3) or GEN_LORA=all: decode frames/s with live adapters (K-extension kernels) against the
+    same adapters merged into a second model's weights, alternated in one process (GEN_ROUNDS rounds)."""
+    from csm.training.lora import apply_lora_to_model, merge_lora_weights
+    dev = "cuda:0"
+    mods = ["q_proj", "k_proj", "v_proj", "output_proj", "w1", "w2", "w3"] if mods == "all" else mods.split(",")
+    models = {}
+    for name in ("live", "merged"):
+        m = Model(csm_1b_args(), device=dev, seed=0)
+        apply_lora_to_model(m, r=8, alpha=16.0, target_modules=mods)
+        with torch.no_grad():
+            gb = torch.Generator(device=dev).manual_seed(1)
+            for ad in m.lora.adapters.values():
+                ad.B[:, :8].copy_((torch.randn(ad.B.shape[0], 8, generator=gb, device=dev) * 0.02).to(torch.bfloat16))
+        if name == "merged":
+            merge_lora_weights(m)
+            m.lora = None
+        models[name] = m
+    res = {"live": [], "merged": []}
+    for _ in range(int(os.environ.get("GEN_ROUNDS", 3))):
+        for name in ("merged", "live"):
+            res[name].append(decode_fps(models[name], int(os.environ.get("GEN_FRAMES", 100))))
+    best = {k: max(v) for k, v in res.items()}
+    print(f"LoRA {','.join(mods)} r=8: decode frames/s live {[round(x, 1) for x in res['live']]} merged "
+          f"{[round(x, 1) for x in res['merged']]} -> best live {best['live']:.1f} / merged {best['merged']:.1f} = "
+          f"{best['live'] / best['merged']:.3f}x")
+
+
 def main():
+    if os.environ.get("GEN_LORA"):
+        return lora_main(os.environ["GEN_LORA"])
     dev = "cuda:0"
     model = Model(csm_1b_args(), device=dev, seed=0)
     codec = make_codec(dev)
