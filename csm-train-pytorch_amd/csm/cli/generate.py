@@ -3,6 +3,10 @@ reference downloads from the hub are passed as local files (``--mimi-weights``, 
 ``csm.data.load_audio`` / ``Generator.save_wav`` because torchaudio is not installed."""
 import argparse
 import os
+import time
+import wave
+
+import torch
 
 from ..data import load_audio, resample
 from ..generator import Segment, load_csm_1b
@@ -29,6 +33,8 @@ def parse_args(argv=None):
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--mimi-weights", type=str, required=True, help="local Mimi weights (transformers.MimiModel state dict)")
     p.add_argument("--text-tokenizer", type=str, required=True, help="local directory of the Llama-3.2 tokenizer files")
+    p.add_argument("--stream", action="store_true", help="write the WAV chunk by chunk while the frames are generated")
+    p.add_argument("--chunk-frames", type=int, default=4, help="80-ms frames per streamed chunk (default: 4)")
     return p.parse_args(argv)
 
 
@@ -52,11 +58,36 @@ def main(argv=None):
     speaker_id = VOICE_PRESETS[args.voice] if args.voice else args.speaker
     generator = load_csm_1b(args.model_path, args.device, mimi_weights=args.mimi_weights, tokenizer_path=args.text_tokenizer)
     context = build_context(args, generator.sample_rate)
+    if args.stream:
+        return stream_to_wav(generator, args, speaker_id, context)
     audio = generator.generate(text=args.text, speaker=speaker_id, context=context, max_audio_length_ms=args.max_audio_length_ms,
                                temperature=args.temperature, topk=args.topk)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     generator.save_wav(args.output, audio)
     print(f"Audio saved to {args.output} ({audio.numel() / generator.sample_rate:.2f} s at {generator.sample_rate} Hz)")
+    return 0
+
+
+def stream_to_wav(generator, args, speaker_id, context):
+    """--stream: each chunk of ``generate_stream`` is appended to the WAV as it arrives (``wave`` patches the header's
+    length on close); the samples are converted exactly as ``Generator.save_wav`` converts them, so the file is the same."""
+    os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
+    t0 = time.perf_counter()
+    n = 0
+    with wave.open(args.output, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(generator.sample_rate))
+        for chunk in generator.generate_stream(text=args.text, speaker=speaker_id, context=context,
+                                               max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature,
+                                               topk=args.topk, chunk_frames=args.chunk_frames):
+            pcm = (chunk.detach().float().cpu().clamp(-1, 1) * 32767.0).to(torch.int16).numpy().tobytes()
+            if n == 0:
+                print(f"first chunk after {time.perf_counter() - t0:.3f} s")
+            w.writeframes(pcm)
+            n += chunk.numel()
+    print(f"Audio saved to {args.output} ({n / generator.sample_rate:.2f} s at {generator.sample_rate} Hz, streamed in "
+          f"{time.perf_counter() - t0:.2f} s)")
     return 0
 
 

@@ -6,7 +6,8 @@ that is neither vendored nor installed here, and whose weights come from the hub
 scale and a 250-frame window, stride-2 down / up-sampling to 12.5 Hz, split residual VQ with 1 semantic + 31 acoustic
 codebooks of 2048 x 256) on hand-written fp32 HIP kernels, taking the weights as a state dict with the key names of the
 Hugging Face port (``transformers.MimiModel.state_dict()``; the moshi checkpoint maps onto it 1:1).  It exposes exactly
-what ``Generator`` touches: ``encode([1,1,N]) -> [1,K,T]`` int64, ``decode([1,K,T]) -> [1,1,N]``, ``sample_rate``.
+what ``Generator`` touches: ``encode([1,1,N]) -> [1,K,T]`` int64, ``decode([1,K,T]) -> [1,1,N]``, ``sample_rate``, and
+``decode_stream()``: a stateful decoder that turns successive chunks of frames into their audio, bit-identical to ``decode``.
 """
 import math
 from typing import Dict, Optional
@@ -20,6 +21,31 @@ F32 = torch.float32
 
 def _s():
     return torch.cuda.current_stream().cuda_stream
+
+
+def decoder_conv_layers(ratios=(8, 6, 5, 4)):
+    """The causal convolutions ``MimiCodec.decode`` runs, in order, as (weight prefix, kind, k, stride, input ELU): kind
+    "convt" = transposed conv (the 2x upsample, then one per SEANet ratio), "conv" = stride-1 conv."""
+    layers = [("upsample", "convt", 4, 2, False), ("decoder.layers.0", "conv", 7, 1, False)]
+    idx = 1
+    for r in ratios:
+        layers += [(f"decoder.layers.{idx + 1}", "convt", 2 * r, r, True),
+                   (f"decoder.layers.{idx + 2}.block.1", "conv", 3, 1, True),
+                   (f"decoder.layers.{idx + 2}.block.3", "conv", 1, 1, True)]
+        idx += 3
+    layers.append((f"decoder.layers.{idx + 1}", "conv", 3, 1, True))
+    return layers
+
+
+def history_len(kind: str, k: int, stride: int = 1, dilation: int = 1) -> int:
+    """Input columns a streaming layer carries between chunks: (k-1)*dil for a causal conv, ceil(k/stride)-1 for a transposed
+    conv whose overhang is cropped on the right."""
+    return (k - 1) * dilation if kind == "conv" else (k - 1) // stride
+
+
+def ring_slot(pos: int, ring: int) -> int:
+    """Slot of absolute transformer position ``pos`` in a K/V ring of ``ring`` rows (csm_attn_window_stream_f32)."""
+    return pos % ring
 
 
 class MimiCodec:
@@ -101,8 +127,10 @@ class MimiCodec:
         check(lib.csm_transpose_f32(x.data_ptr(), y.data_ptr(), R, Cn, _s()), "csm_transpose_f32")
         return y
 
-    def _transformer(self, x, tr):
-        """x [T, hidden] -> [T, hidden]: pre-LN, rotate-half RoPE, causal window attention, GELU MLP, layer scale."""
+    def _transformer(self, x, tr, pos0=0, kv=None):
+        """x [T, hidden] -> [T, hidden]: pre-LN, rotate-half RoPE, causal window attention, GELU MLP, layer scale.
+        Streaming (``kv`` = one (k, v) ring cache pair [ring, hidden] per layer): the T rows sit at positions pos0.. and
+        attend to the cached keys before them; each attention launch covers at most ring - window + 1 rows."""
         T, D = x.shape
         H, hd, w = self.heads, D // self.heads, self.w
         for i in range(self.n_layers):
@@ -111,9 +139,15 @@ class MimiCodec:
             check(lib.csm_layernorm_f32(x.data_ptr(), w[f"{p}.input_layernorm.weight"].data_ptr(), w[f"{p}.input_layernorm.bias"].data_ptr(),
                                         xn.data_ptr(), T, D, self.eps, _s()), "csm_layernorm_f32")
             qkv = self._linear(xn, w[f"{p}.self_attn.qkv"])
-            check(lib.csm_rope_half_f32(qkv.data_ptr(), T, H, hd, self.theta, 0, _s()), "csm_rope_half_f32")
+            check(lib.csm_rope_half_f32(qkv.data_ptr(), T, H, hd, self.theta, pos0, _s()), "csm_rope_half_f32")
             o = torch.empty(T, D, dtype=F32, device=self.dev)
-            check(lib.csm_attn_window_f32(qkv.data_ptr(), o.data_ptr(), T, H, hd, self.window, _s()), "csm_attn_window_f32")
+            if kv is None:
+                check(lib.csm_attn_window_f32(qkv.data_ptr(), o.data_ptr(), T, H, hd, self.window, _s()), "csm_attn_window_f32")
+            else:
+                kc, vc = kv[i]
+                rows = kc.shape[0] - self.window + 1
+                for r0 in range(0, T, rows):
+                    ops.attn_window_stream_f32(qkv[r0:r0 + rows], kc, vc, o[r0:r0 + rows], pos0 + r0, H, self.window)
             x = self._linear(o, w[f"{p}.self_attn.o_proj.weight"], scale=w[f"{p}.self_attn_layer_scale.scale"], res=x)
             check(lib.csm_layernorm_f32(x.data_ptr(), w[f"{p}.post_attention_layernorm.weight"].data_ptr(),
                                         w[f"{p}.post_attention_layernorm.bias"].data_ptr(), xn.data_ptr(), T, D, self.eps, _s()),
@@ -151,9 +185,8 @@ class MimiCodec:
             ops.rvq_encode(self._linear(lat, self.w[f"{q}.in"]), self.cb["acoustic"][:na].contiguous(), codes[self.n_sem:], 0)
         return codes.unsqueeze(0)
 
-    @torch.no_grad()
-    def decode(self, codes: torch.Tensor) -> torch.Tensor:
-        c = codes[0].to(self.dev, torch.int64).contiguous()
+    def _dequantize(self, c):
+        """codes [K, T] int64 -> latent [T, hidden] (both residual VQs + their output projections)."""
         K, T = c.shape
         lat = torch.zeros(T, self.hidden, dtype=F32, device=self.dev)
         for name, lo, hi in (("semantic", 0, min(K, self.n_sem)), ("acoustic", self.n_sem, K)):
@@ -163,6 +196,12 @@ class MimiCodec:
             zq = torch.empty(T, self.cdim, dtype=F32, device=self.dev)
             ops.rvq_decode(c[lo:hi].contiguous(), self.cb[name][:hi - lo].contiguous(), zq)
             lat = self._linear(zq, self.w[f"{q}.out"], res=lat)
+        return lat
+
+    @torch.no_grad()
+    def decode(self, codes: torch.Tensor) -> torch.Tensor:
+        c = codes[0].to(self.dev, torch.int64).contiguous()
+        lat = self._dequantize(c)
         x = self._convt(self._transpose(lat), "upsample", 4, 2)                       # [hidden, 2T]
         x = self._transformer(self._transpose(x), "decoder_transformer")
         x = self._conv(self._transpose(x), "decoder.layers.0", 7)
@@ -172,4 +211,89 @@ class MimiCodec:
             x = self._resblock(x, f"decoder.layers.{idx + 2}")
             idx += 3
         x = self._conv(x, f"decoder.layers.{idx + 1}", 3, elu=True)                  # [1, N]
+        return x.reshape(1, 1, -1)
+
+    def decode_stream(self, max_chunk_frames: int = 32) -> "MimiDecodeStream":
+        """A stateful decoder: ``step(codes [1,K,n])`` returns the n * 1920 samples of the next n frames, and the concatenated
+        steps equal ``decode`` of all the frames, bit for bit."""
+        return MimiDecodeStream(self, max_chunk_frames)
+
+
+class MimiDecodeStream:
+    """Streaming state of ``MimiCodec.decode``.  Every decoder op is causal (stride-1 convs with left zero padding, transposed
+    convs cropped on the right, a causal windowed transformer), so frame t's samples depend on codes 0..t only, and every
+    kernel computes an output with a reduction order that does not depend on the sequence length.  The state is:
+      * per conv / transposed conv layer, the last ``history_len`` input columns ([C_in, H] fp32), in two buffers that
+        alternate each step (the kernel reads one and writes the next history into the other);
+      * per decoder-transformer layer, a K/V ring of ``window + 2 * max_chunk_frames - 1`` post-RoPE rows (position p in slot
+        p % ring): larger than the window so that one launch can append a chunk's keys while its earlier queries still read
+        the keys those slots held;
+      * the number of frames decoded so far.
+    ``step`` makes no host synchronisation; chunks may be any size >= 1 (more than ``max_chunk_frames`` costs extra attention
+    launches)."""
+
+    def __init__(self, codec: MimiCodec, max_chunk_frames: int = 32):
+        if max_chunk_frames < 1:
+            raise ValueError("max_chunk_frames must be >= 1")
+        self.codec = codec
+        dev, w = codec.dev, codec.w
+        self.hist = {}
+        for name, kind, k, stride, _ in decoder_conv_layers(codec.ratios):
+            wt = w[f"{name}.conv.weight"]
+            H = history_len(kind, k, stride)
+            C_in = wt.shape[0] if kind == "convt" else wt.shape[1]
+            self.hist[name] = [torch.zeros(C_in, H, dtype=F32, device=dev) for _ in range(2)] if H else None
+        self.ring = codec.window + 2 * max_chunk_frames - 1
+        self.kv = [tuple(torch.zeros(self.ring, codec.hidden, dtype=F32, device=dev) for _ in range(2)) for _ in range(codec.n_layers)]
+        self.reset()
+
+    def reset(self):
+        """Start a new utterance."""
+        for bufs in self.hist.values():
+            if bufs is not None:
+                bufs[0].zero_()
+        self._par = 0                      # hist[name][_par] holds the current history
+        self.cols = {name: 0 for name in self.hist}
+        self.pos = 0                       # frames decoded so far
+
+    def _hist(self, name):
+        bufs = self.hist[name]
+        return (None, None) if bufs is None else (bufs[self._par], bufs[self._par ^ 1])
+
+    def _conv(self, x, name, elu=False, res=None):
+        wt, b = self.codec.w[f"{name}.conv.weight"], self.codec.w.get(f"{name}.conv.bias")
+        h, h_next = self._hist(name)
+        y = torch.empty(wt.shape[0], x.shape[1], dtype=F32, device=self.codec.dev)
+        return ops.conv1d_stream_f32(h, x, wt, b, y, h_next, 1, elu, res)
+
+    def _convt(self, x, name, stride, elu=False):
+        wt, b = self.codec.w[f"{name}.conv.weight"], self.codec.w.get(f"{name}.conv.bias")
+        C_in, cout_g, _ = wt.shape
+        groups = 1 if cout_g != 1 or C_in == 1 else C_in          # as MimiCodec._convt
+        h, h_next = self._hist(name)
+        y = torch.empty(cout_g * groups, x.shape[1] * stride, dtype=F32, device=self.codec.dev)
+        ops.conv_transpose1d_stream_f32(h, x, wt, b, y, h_next, self.cols[name], stride, groups, elu)
+        self.cols[name] += x.shape[1]
+        return y
+
+    @torch.no_grad()
+    def step(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes [1, K, n] -> the next n frames of audio [1, 1, n * 1920]."""
+        cd = self.codec
+        c = codes[0].to(cd.dev, torch.int64).contiguous()
+        n = c.shape[1]
+        if n < 1:
+            raise ValueError("step needs at least one frame")
+        x = self._convt(cd._transpose(cd._dequantize(c)), "upsample", 2)                         # [hidden, 2n]
+        x = cd._transformer(cd._transpose(x), "decoder_transformer", pos0=2 * self.pos, kv=self.kv)
+        x = self._conv(cd._transpose(x), "decoder.layers.0")
+        idx = 1
+        for r in cd.ratios:
+            x = self._convt(x, f"decoder.layers.{idx + 1}", r, elu=True)
+            h = self._conv(x, f"decoder.layers.{idx + 2}.block.1", elu=True)
+            x = self._conv(h, f"decoder.layers.{idx + 2}.block.3", elu=True, res=x)
+            idx += 3
+        x = self._conv(x, f"decoder.layers.{idx + 1}", elu=True)                                 # [1, n * 1920]
+        self._par ^= 1
+        self.pos += n
         return x.reshape(1, 1, -1)

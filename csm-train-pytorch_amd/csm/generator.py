@@ -10,7 +10,7 @@ failure is reported as-is.  The audio tokenizer protocol is Mimi's: ``encode([1,
 and is not applied here (out of scope).
 """
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import Iterator, List, Optional, Tuple
 
 import torch
 
@@ -54,6 +54,7 @@ class Generator:
         self._audio_tokenizer = audio_tokenizer
         self.sample_rate = audio_tokenizer.sample_rate
         self.device = model.device
+        self._run = 0                  # bumped by every generate*: an open generate_stream stops when it changes
 
     def _tokenize_text_segment(self, text: str, speaker: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference generator.py:77-100: ``f"[{speaker}]{text}"`` ids into the last column."""
@@ -90,24 +91,11 @@ class Generator:
         frame, generator.py:196-199); here the all-zero test runs on the device and the host looks at it once per
         ``eos_check_every`` frames, so the frame graphs are enqueued back to back.  The audio returned is the same: frames
         sampled past the EOS frame are dropped."""
+        self._run += 1
         self._model.reset_caches()
         max_audio_frames = int(max_audio_length_ms / 80)
-        tokens, masks = [], []
-        for seg in context:
-            t, m = self._tokenize_segment(seg)
-            tokens.append(t)
-            masks.append(m)
-        t, m = self._tokenize_text_segment(text, speaker)
-        tokens.append(t)
-        masks.append(m)
-        prompt_tokens = torch.cat(tokens, dim=0).long().to(self.device)
-        prompt_mask = torch.cat(masks, dim=0).bool().to(self.device)
+        curr_tokens, curr_mask, curr_pos = self._prompt(text, speaker, context, max_audio_frames)
         samples = []
-        curr_tokens, curr_mask = prompt_tokens.unsqueeze(0), prompt_mask.unsqueeze(0)
-        curr_pos = torch.arange(0, prompt_tokens.size(0)).unsqueeze(0).long().to(self.device)
-        max_seq_len = self._model.bb.max_seq_len - max_audio_frames
-        if curr_tokens.size(1) >= max_seq_len:
-            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {max_seq_len}")
         K = self._model.args.audio_num_codebooks
         audio_mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(self.device)
         pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
@@ -131,6 +119,73 @@ class Generator:
         codes = torch.stack(samples).permute(1, 2, 0).long()
         return self._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
 
+    def _prompt(self, text: str, speaker: int, context: List[Segment], max_audio_frames: int):
+        """Prompt frames of ``generate`` / ``generate_stream``: (tokens [1,S,K+1], mask [1,S,K+1], positions [1,S])."""
+        tokens, masks = [], []
+        for seg in context:
+            t, m = self._tokenize_segment(seg)
+            tokens.append(t)
+            masks.append(m)
+        t, m = self._tokenize_text_segment(text, speaker)
+        tokens.append(t)
+        masks.append(m)
+        prompt_tokens = torch.cat(tokens, dim=0).long().to(self.device)
+        prompt_mask = torch.cat(masks, dim=0).bool().to(self.device)
+        curr_pos = torch.arange(0, prompt_tokens.size(0)).unsqueeze(0).long().to(self.device)
+        max_seq_len = self._model.bb.max_seq_len - max_audio_frames
+        if prompt_tokens.size(0) >= max_seq_len:
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {max_seq_len}")
+        return prompt_tokens.unsqueeze(0), prompt_mask.unsqueeze(0), curr_pos
+
+    def generate_stream(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
+                        temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4) -> Iterator[torch.Tensor]:
+        """``generate`` that hands the audio out while it is being made: an iterator of 1-D device tensors of
+        ``chunk_frames * 1920`` samples (the last one may be shorter), decoded by the audio tokenizer's stateful
+        ``decode_stream()``.  The frames are sampled by the same ``generate_frame`` calls in the same order as ``generate``,
+        so under the same torch seed the concatenated chunks equal ``generate``'s audio.  The host looks for EOS once per
+        chunk; frames from EOS on are never decoded.  A later ``generate`` / ``generate_batch`` / ``generate_stream`` on this
+        Generator invalidates the stream (its next ``next()`` raises ``RuntimeError``); abandoning it is harmless."""
+        if int(chunk_frames) != chunk_frames or chunk_frames < 1:
+            raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
+        if not callable(getattr(self._audio_tokenizer, "decode_stream", None)):
+            raise TypeError(f"{type(self._audio_tokenizer).__name__} has no decode_stream(): streaming needs a stateful decoder "
+                            "(decoding chunks independently would be wrong at the chunk edges)")
+        self._run += 1
+        return self._stream(self._run, text, speaker, context, max_audio_length_ms, temperature, topk, int(chunk_frames))
+
+    @torch.inference_mode()
+    def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames):
+        def check():
+            if self._run != run:
+                raise RuntimeError("this stream was invalidated: a later generate / generate_batch / generate_stream call on "
+                                   "the same Generator took over the model's caches")
+
+        check()
+        self._model.reset_caches()
+        max_audio_frames = int(max_audio_length_ms / 80)
+        curr_tokens, curr_mask, curr_pos = self._prompt(text, speaker, context, max_audio_frames)
+        decoder = self._audio_tokenizer.decode_stream()
+        K = self._model.args.audio_num_codebooks
+        audio_mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(self.device)
+        pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
+        pending = []
+        for i in range(max_audio_frames):
+            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk)
+            pending.append(sample)
+            if len(pending) == chunk_frames or i == max_audio_frames - 1:
+                codes = torch.stack(pending).permute(1, 2, 0).long()                       # [1, K, n]
+                hit = (codes[0] == 0).all(dim=0).nonzero()                                  # the chunk's one host look
+                n = int(hit[0]) if hit.numel() else codes.shape[2]
+                if n:
+                    yield decoder.step(codes[:, :, :n]).reshape(-1)
+                    check()
+                if hit.numel():
+                    return
+                pending = []
+            curr_tokens = torch.cat([sample.long(), pad], dim=1).unsqueeze(1)
+            curr_mask = audio_mask
+            curr_pos = curr_pos[:, -1:] + 1
+
     @torch.inference_mode()
     def generate_batch(self, texts: List[str], speakers: List[int], contexts: List[List[Segment]],
                        max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
@@ -139,6 +194,7 @@ class Generator:
         (different lengths) are prefilled one by one into their rows of the KV caches, then every decode frame advances all
         rows together - the decode kernels share each weight load between the batch rows, so B utterances cost about as
         much as one.  A row stops contributing at its own EOS frame; the loop ends when every row has one."""
+        self._run += 1
         B = len(texts)
         if not (1 <= B <= 4 and len(speakers) == B and len(contexts) == B):
             raise ValueError("generate_batch takes 1..4 utterances with one speaker id and one context list each")

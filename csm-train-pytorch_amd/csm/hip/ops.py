@@ -527,3 +527,55 @@ def rvq_decode(codes_i64, codebooks_f32, out_f32):
     check(lib.csm_rvq_decode(codes_i64.data_ptr(), codebooks_f32.data_ptr(), out_f32.data_ptr(), T, K, Cn, D, _stream()),
           "csm_rvq_decode")
     return out_f32
+
+
+def _f32(t, name):
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), (name, t.dtype, t.shape, t.stride())
+    return t.data_ptr()
+
+
+def conv1d_stream_f32(hist, x, w, bias, y, hist_out, dilation=1, elu_in=False, residual=None):
+    """One chunk of a causal stride-1 conv (csm_conv1d_stream_f32): x [C_in, n] new columns after ``hist`` [C_in, (k-1)*dil]
+    -> y [C_out, n] (+ residual [C_out, n]); the next history goes to ``hist_out`` (same shape as hist, a different buffer).
+    hist / hist_out may be None when k == 1.  w: [C_out, C_in/groups, k]."""
+    C_in, n = x.shape
+    C_out, cin_g, k = w.shape
+    H = (k - 1) * dilation
+    assert y.shape == (C_out, n) and C_in % cin_g == 0
+    if H:
+        assert hist.shape == (C_in, H) and hist_out.shape == (C_in, H) and hist.data_ptr() != hist_out.data_ptr()
+    check(lib.csm_conv1d_stream_f32(_f32(hist, "hist") if H else None, _f32(x, "x"), _f32(w, "w"),
+                                    None if bias is None else _f32(bias, "bias"), None if residual is None else _f32(residual, "res"),
+                                    _f32(y, "y"), _f32(hist_out, "hist_out") if H else None, C_in, C_out, n, k, dilation,
+                                    C_in // cin_g, int(elu_in), _stream()), "csm_conv1d_stream_f32")
+    return y
+
+
+def conv_transpose1d_stream_f32(hist, x, w, bias, y, hist_out, pos0, stride, groups=1, elu_in=False):
+    """One chunk of a causal transposed conv (csm_conv_transpose1d_stream_f32): x [C_in, n] new columns at input position
+    ``pos0`` after ``hist`` [C_in, ceil(k/stride)-1] -> y [C_out, n*stride]; next history to ``hist_out``.
+    w: [C_in, C_out/groups, k] (torch layout)."""
+    C_in, n = x.shape
+    C_in_w, cout_g, k = w.shape
+    H = (k - 1) // stride
+    C_out = cout_g * groups
+    assert C_in_w == C_in and y.shape == (C_out, n * stride)
+    if H:
+        assert hist.shape == (C_in, H) and hist_out.shape == (C_in, H) and hist.data_ptr() != hist_out.data_ptr()
+    check(lib.csm_conv_transpose1d_stream_f32(_f32(hist, "hist") if H else None, _f32(x, "x"), _f32(w, "w"),
+                                              None if bias is None else _f32(bias, "bias"), _f32(y, "y"),
+                                              _f32(hist_out, "hist_out") if H else None, C_in, C_out, n, int(pos0), k, stride,
+                                              groups, int(elu_in), _stream()), "csm_conv_transpose1d_stream_f32")
+    return y
+
+
+def attn_window_stream_f32(qkv, kcache, vcache, out, pos0, heads, window):
+    """Sliding-window attention of the n rows of qkv [n, 3*D] (post-RoPE) at positions pos0..pos0+n-1 against the ring caches
+    kcache / vcache [ring, D] (position p in slot p % ring), appending the new k / v rows (csm_attn_window_stream_f32).
+    out: [n, D].  Needs ring >= window + n - 1."""
+    n, D3 = qkv.shape
+    ring, D = kcache.shape
+    assert D3 == 3 * D and vcache.shape == (ring, D) and out.shape == (n, D)
+    check(lib.csm_attn_window_stream_f32(_f32(qkv, "qkv"), _f32(kcache, "kcache"), _f32(vcache, "vcache"), _f32(out, "out"), n,
+                                         int(pos0), heads, D // heads, window, ring, _stream()), "csm_attn_window_stream_f32")
+    return out

@@ -11,7 +11,49 @@
 
 namespace {
 
-__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }
+// ELU (alpha 1).  expm1f is evaluated for every x and then selected, never branched around: a branch on the loaded value
+// would make every load of an unrolled tap loop wait before the next one is issued.
+__device__ __forceinline__ float elu1(float x) {
+    const float em = expm1f(x);
+    return x > 0.f ? x : em;
+}
+
+// Per-output accumulations shared by the full-sequence kernels and the streaming ones (csm_*_stream_f32), so that both
+// compute every output with the same operations in the same order: a streaming decoder is then bit-identical to decode().
+
+// acc += sum_{ci < cin_g} sum_{j < k} wrow[ci][j] * act(load(ci, j))   (ci outer, j inner)
+// The (ci, j) taps run as one flat loop, unrolled so that the loads of several taps are in flight at once: the sum is a
+// chain of cin_g * k dependent FMAs whatever the sequence length, and a short (streaming) launch is bound by its latency.
+template <class Load>
+__device__ __forceinline__ float conv1d_accum(float acc, const float* __restrict__ wrow, int cin_g, int k, int elu_in, Load load) {
+    int ci = 0, j = 0;
+#pragma unroll 8
+    for (int e = 0; e < cin_g * k; ++e) {
+        float v = load(ci, j);
+        if (elu_in) v = elu1(v);   // ELU(0) = 0, so applying it to zero padding changes nothing
+        acc += wrow[e] * v;        // wrow[ci * k + j]
+        if (++j == k) { j = 0; ++ci; }
+    }
+    return acc;
+}
+
+// acc += sum_{j = tf % stride, step stride} sum_ci act(load(ci, ti)) w[grp*cin_g + ci][co_g][j], ti = (tf - j) / stride,
+// taps with ti outside [0, ti_end) skipped (j outer, ci inner)
+template <class Load>
+__device__ __forceinline__ float convt_accum(float acc, const float* __restrict__ w, int grp, int cin_g, int cout_g, int co_g, int k,
+                                             int stride, int tf, int ti_end, int elu_in, Load load) {
+    for (int j = tf % stride; j < k; j += stride) {
+        const int ti = (tf - j) / stride;
+        if (ti < 0 || ti >= ti_end) continue;
+#pragma unroll 8
+        for (int ci = 0; ci < cin_g; ++ci) {
+            float v = load(ci, ti);
+            if (elu_in) v = elu1(v);
+            acc += v * w[((size_t)(grp * cin_g + ci) * cout_g + co_g) * k + j];
+        }
+    }
+    return acc;
+}
 
 // y[co][t] = bias[co] + sum_{ci in group} sum_j w[co][ci][j] * act(xpad[ci][t*stride + j*dil - pad_left]) (+ res[co][t])
 // xpad: zero (pad_mode 0) or edge-replicated (pad_mode 1) outside [0, T_in).  One wave-row of threads shares `co`, so the
@@ -25,23 +67,47 @@ __global__ __launch_bounds__(256) void conv1d_kernel(const float* __restrict__ x
     const int grp = co / cout_g;
     const float* wrow = w + (size_t)co * cin_g * k;
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < T_out; t += gridDim.x * blockDim.x) {
-        float acc = bias ? bias[co] : 0.f;
         const int base = t * stride - pad_left;
-        for (int ci = 0; ci < cin_g; ++ci) {
+        float acc = conv1d_accum(bias ? bias[co] : 0.f, wrow, cin_g, k, elu_in, [&](int ci, int j) {
             const float* xr = x + (size_t)(grp * cin_g + ci) * T_in;
-            for (int j = 0; j < k; ++j) {
-                int p = base + j * dil;
-                float v;
-                if (p >= 0 && p < T_in) v = xr[p];
-                else if (pad_mode == 1) v = xr[p < 0 ? 0 : T_in - 1];
-                else v = 0.f;
-                if (elu_in) v = elu1(v);   // ELU(0) = 0, so applying it to zero padding changes nothing
-                acc += wrow[ci * k + j] * v;
-            }
-        }
+            const int p = base + j * dil;
+            if (p >= 0 && p < T_in) return xr[p];
+            if (pad_mode == 1) return xr[p < 0 ? 0 : T_in - 1];
+            return 0.f;
+        });
         if (res) acc += res[(size_t)co * T_out + t];
         y[(size_t)co * T_out + t] = acc;
     }
+}
+
+// Streaming causal stride-1 conv: the input is [hist | x] with hist = the last H = (k-1)*dil input columns of the previous
+// chunk (zeros before the first: decode()'s zero padding).  Writes y[co][0..n) as conv1d_kernel does for the same absolute
+// outputs, and the next history (the last H columns of [hist | x]) into hist_out - a different buffer (the host ping-pongs).
+__global__ __launch_bounds__(256) void conv1d_stream_kernel(const float* __restrict__ hist, const float* __restrict__ x,
+                                                            const float* __restrict__ w, const float* __restrict__ bias,
+                                                            const float* __restrict__ res, float* __restrict__ y,
+                                                            float* __restrict__ hist_out, int C_in, int C_out, int n, int k, int dil,
+                                                            int groups, int elu_in) {
+    const int co = blockIdx.y;
+    const int H = (k - 1) * dil;
+    const int cin_g = C_in / groups, cout_g = C_out / groups;
+    const int grp = co / cout_g;
+    const float* wrow = w + (size_t)co * cin_g * k;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+        float acc = conv1d_accum(bias ? bias[co] : 0.f, wrow, cin_g, k, elu_in, [&](int ci, int j) {
+            const int c = grp * cin_g + ci, p = t + j * dil;            // column of [hist | x]
+            // select the address, then load unconditionally: a load under a branch cannot be hoisted out of the unrolled loop
+            const float* src = p < H ? hist + (size_t)c * H + p : x + (size_t)c * n + (p - H);
+            return *src;
+        });
+        if (res) acc += res[(size_t)co * n + t];
+        y[(size_t)co * n + t] = acc;
+    }
+    for (int c = blockIdx.y; c < C_in; c += gridDim.y)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < H; i += gridDim.x * blockDim.x) {
+            const int p = n + i;
+            hist_out[(size_t)c * H + i] = p < H ? hist[(size_t)c * H + p] : x[(size_t)c * n + p - H];
+        }
 }
 
 // ConvTranspose1d (torch weight layout [C_in][C_out/groups][k]) cropped to [crop_left, crop_left + T_out):
@@ -54,19 +120,39 @@ __global__ __launch_bounds__(256) void conv_transpose1d_kernel(const float* __re
     const int cin_g = C_in / groups, cout_g = C_out / groups;
     const int grp = co / cout_g, co_g = co % cout_g;
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < T_out; t += gridDim.x * blockDim.x) {
-        float acc = bias ? bias[co] : 0.f;
-        const int tf = t + crop_left;
-        for (int j = tf % stride; j < k; j += stride) {
-            const int ti = (tf - j) / stride;
-            if (ti < 0 || ti >= T_in) continue;
-            for (int ci = 0; ci < cin_g; ++ci) {
-                float v = x[(size_t)(grp * cin_g + ci) * T_in + ti];
-                if (elu_in) v = elu1(v);
-                acc += v * w[((size_t)(grp * cin_g + ci) * cout_g + co_g) * k + j];
-            }
-        }
+        const float acc = convt_accum(bias ? bias[co] : 0.f, w, grp, cin_g, cout_g, co_g, k, stride, t + crop_left, T_in, elu_in,
+                                      [&](int ci, int ti) { return x[(size_t)(grp * cin_g + ci) * T_in + ti]; });
         y[(size_t)co * T_out + t] = acc;
     }
+}
+
+// Streaming causal (crop_left 0) transposed conv: chunk of n input columns at absolute input position pos0, history = the last
+// H = ceil(k/stride) - 1 input columns before it.  Writes the n*stride outputs that conv_transpose1d_kernel gives for absolute
+// outputs [pos0*stride, (pos0+n)*stride) - the taps of inputs before position 0 are skipped, as there - and the next history.
+__global__ __launch_bounds__(256) void conv_transpose1d_stream_kernel(const float* __restrict__ hist, const float* __restrict__ x,
+                                                                      const float* __restrict__ w, const float* __restrict__ bias,
+                                                                      float* __restrict__ y, float* __restrict__ hist_out, int C_in,
+                                                                      int C_out, int n, int pos0, int k, int stride, int groups,
+                                                                      int elu_in) {
+    const int co = blockIdx.y;
+    const int H = (k - 1) / stride;
+    const int cin_g = C_in / groups, cout_g = C_out / groups;
+    const int grp = co / cout_g, co_g = co % cout_g;
+    const int T_out = n * stride;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < T_out; t += gridDim.x * blockDim.x) {
+        const float acc = convt_accum(bias ? bias[co] : 0.f, w, grp, cin_g, cout_g, co_g, k, stride, pos0 * stride + t, pos0 + n, elu_in,
+                                      [&](int ci, int ti) {
+                                          const int c = grp * cin_g + ci, p = ti - pos0 + H;      // column of [hist | x]
+                                          const float* src = p < H ? hist + (size_t)c * H + p : x + (size_t)c * n + (p - H);
+                                          return *src;
+                                      });
+        y[(size_t)co * T_out + t] = acc;
+    }
+    for (int c = blockIdx.y; c < C_in; c += gridDim.y)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < H; i += gridDim.x * blockDim.x) {
+            const int p = n + i;
+            hist_out[(size_t)c * H + i] = p < H ? hist[(size_t)c * H + p] : x[(size_t)c * n + p - H];
+        }
 }
 
 // y[t][:] = (x[t] - mean) * rsqrt(var + eps) * w + b      (one wave per row)
@@ -83,6 +169,15 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     for (int c = lane; c < D; c += 64) { const float d = xr[c] - mean; v += d * d; }
     const float r = rsqrtf(wave_sum(v) / D + eps);
     for (int c = lane; c < D; c += 64) y[(size_t)row * D + c] = (xr[c] - mean) * r * w[c] + b[c];
+}
+
+// act 1 = exact GELU; scale != NULL -> res + scale[n] * v (layer scale + residual); else v (+ res)
+__device__ __forceinline__ float linear_epilogue(float v, const float* __restrict__ scale, const float* __restrict__ res, int t, int n,
+                                                 int N, int act) {
+    if (act == 1) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+    if (scale) v = res[(size_t)t * N + n] + scale[n] * v;
+    else if (res) v += res[(size_t)t * N + n];
+    return v;
 }
 
 // y[T][N] = epilogue(x[T][K] W[N][K]^T): 64x64 tile per 256-thread block, 4x4 outputs per thread, K in steps of 16
@@ -121,13 +216,45 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(const float* __restrict
         for (int j = 0; j < 4; ++j) {
             const int n = n0 + tx * 4 + j;
             if (n >= N) continue;
-            float v = acc[i][j];
-            if (act == 1) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
-            if (scale) v = res[(size_t)t * N + n] + scale[n] * v;
-            else if (res) v += res[(size_t)t * N + n];
-            y[(size_t)t * N + n] = v;
+            y[(size_t)t * N + n] = linear_epilogue(acc[i][j], scale, res, t, n, N, act);
         }
     }
+}
+
+// linear_f32_kernel's products for a few rows (the streaming decoder's 2n positions): one thread per output, the same
+// k-ascending chain of FMAs from 0 and the same epilogue, so every output has the tiled kernel's bits.  The tiled kernel
+// pays a global -> LDS round trip and two barriers per 16 k on only N/64 blocks; here each thread streams its weight row
+// with 16-byte loads, the next V float4 in flight while the current V are consumed.  Needs K % (4 V) == 0, W 16-B aligned.
+template <int V>
+__global__ __launch_bounds__(256) void linear_f32_rows_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                              const float* __restrict__ scale, const float* __restrict__ res,
+                                                              float* __restrict__ y, int T, int N, int K, int ldx, int act) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
+    if (n >= N) return;
+    const float4* w4 = reinterpret_cast<const float4*>(W + (size_t)n * K);
+    const float* xr = x + (size_t)t * ldx;
+    const int nb = K / (4 * V);
+    float4 cur[V], nxt[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) cur[v] = w4[v];
+    float acc = 0.f;
+    for (int b = 0; b < nb; ++b) {
+        if (b + 1 < nb) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) nxt[v] = w4[(b + 1) * V + v];
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float* xk = xr + (b * V + v) * 4;
+            acc = fmaf(xk[0], cur[v].x, acc);
+            acc = fmaf(xk[1], cur[v].y, acc);
+            acc = fmaf(xk[2], cur[v].z, acc);
+            acc = fmaf(xk[3], cur[v].w, acc);
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) cur[v] = nxt[v];
+    }
+    y[(size_t)t * N + n] = linear_epilogue(acc, scale, res, t, n, N, act);
 }
 
 // rotate-half RoPE (HF / moshi convention) in place on the q and k parts of qkv [T][3*H*hd]; theta_i = base^(-2i/hd)
@@ -150,19 +277,15 @@ __global__ __launch_bounds__(256) void rope_half_kernel(float* __restrict__ qkv,
     }
 }
 
-// causal sliding-window attention, one block per (query, head); keys in (q - window, q]
-template <int HD>
-__global__ __launch_bounds__(64) void attn_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int H, int window) {
-    extern __shared__ float sc[];   // [window]
-    const int q = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
-    const int ld = 3 * H * HD;
-    const float* qp = qkv + (size_t)q * ld + h * HD;
-    const int k_lo = q - window + 1 > 0 ? q - window + 1 : 0;
-    const int n = q - k_lo + 1;
+// One query row of causal sliding-window attention over n keys: key s (logical order) on lane s % 64, row pointers from
+// krow(s) / vrow(s); sc = LDS scores [n].  Shared by the full-sequence and the streaming kernel.
+template <int HD, class KRow, class VRow>
+__device__ __forceinline__ void attn_window_row(const float* __restrict__ qp, float* __restrict__ outp, float* sc, int n, int lane,
+                                                KRow krow, VRow vrow) {
     const float scale = rsqrtf((float)HD);
     float mx = -INFINITY;
     for (int s = lane; s < n; s += 64) {
-        const float* kp = qkv + (size_t)(k_lo + s) * ld + (H + h) * HD;
+        const float* kp = krow(s);
         float d = 0.f;
 #pragma unroll 8
         for (int c = 0; c < HD; ++c) d += qp[c] * kp[c];
@@ -177,9 +300,51 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(const float* __restrict__ 
     __syncthreads();
     for (int c = lane; c < HD; c += 64) {
         float acc = 0.f;
-        for (int s = 0; s < n; ++s) acc += sc[s] * qkv[(size_t)(k_lo + s) * ld + (2 * H + h) * HD + c];
-        out[(size_t)q * H * HD + h * HD + c] = acc / sum;
+        for (int s = 0; s < n; ++s) acc += sc[s] * vrow(s)[c];
+        outp[c] = acc / sum;
     }
+}
+
+// causal sliding-window attention, one block per (query, head); keys in (q - window, q]
+template <int HD>
+__global__ __launch_bounds__(64) void attn_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int H, int window) {
+    extern __shared__ float sc[];   // [window]
+    const int q = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+    const int ld = 3 * H * HD;
+    const int k_lo = q - window + 1 > 0 ? q - window + 1 : 0;
+    attn_window_row<HD>(qkv + (size_t)q * ld + h * HD, out + (size_t)q * H * HD + h * HD, sc, q - k_lo + 1, lane,
+                        [&](int s) { return qkv + (size_t)(k_lo + s) * ld + (H + h) * HD; },
+                        [&](int s) { return qkv + (size_t)(k_lo + s) * ld + (2 * H + h) * HD; });
+}
+
+// The same for n new rows of qkv at absolute positions pos0 .. pos0+n-1.  Keys before pos0 come from the K/V ring caches
+// ([ring][H*HD], position p in slot p % ring, post-RoPE), the chunk's own keys straight from qkv; block (q, h) also appends
+// its k / v head row to slot (pos0 + q) % ring.  The slots written, (pos0 .. pos0+n-1), and the slots read from the cache,
+// (pos0-window+1 .. pos0-1), are n + window - 1 consecutive positions: distinct when ring >= window + n - 1 (checked by the
+// host wrapper), so no block overwrites a key another block of the launch still reads.  A ring of exactly `window` slots
+// would not do: the slot of new position p holds p - window, which earlier queries of the same chunk still need.
+template <int HD>
+__global__ __launch_bounds__(64) void attn_f32_stream_kernel(const float* __restrict__ qkv, float* __restrict__ kc, float* __restrict__ vc,
+                                                             float* __restrict__ out, int pos0, int H, int window, int ring) {
+    extern __shared__ float sc[];   // [window]
+    const int qi = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
+    const int ld = 3 * H * HD, ldc = H * HD;
+    const int q = pos0 + qi;
+    const size_t slot = (size_t)(q % ring) * ldc + h * HD;
+    for (int c = lane; c < HD; c += 64) {
+        kc[slot + c] = qkv[(size_t)qi * ld + (H + h) * HD + c];
+        vc[slot + c] = qkv[(size_t)qi * ld + (2 * H + h) * HD + c];
+    }
+    const int k_lo = q - window + 1 > 0 ? q - window + 1 : 0;
+    attn_window_row<HD>(qkv + (size_t)qi * ld + h * HD, out + (size_t)qi * H * HD + h * HD, sc, q - k_lo + 1, lane,
+                        [&](int s) {
+                            const int p = k_lo + s;
+                            return p >= pos0 ? qkv + (size_t)(p - pos0) * ld + (H + h) * HD : kc + (size_t)(p % ring) * ldc + h * HD;
+                        },
+                        [&](int s) {
+                            const int p = k_lo + s;
+                            return p >= pos0 ? qkv + (size_t)(p - pos0) * ld + (2 * H + h) * HD : vc + (size_t)(p % ring) * ldc + h * HD;
+                        });
 }
 
 // out[c][r] = in[r][c]
@@ -231,8 +396,12 @@ extern "C" int csm_layernorm_f32(const float* x, const float* w, const float* b,
 extern "C" int csm_linear_f32(const float* x, const float* W, const float* scale, const float* residual, float* y, int T, int N,
                               int K, int ldx, int act, hipStream_t stream) {
     CSM_REQUIRE(x && W && y && T > 0 && N > 0 && K > 0 && ldx >= K && (!scale || residual), "csm_linear_f32: bad arguments");
-    hipLaunchKernelGGL(linear_f32_kernel, dim3((N + 63) / 64, (T + 63) / 64), dim3(256), 0, stream, x, W, scale, residual, y, T, N,
-                       K, ldx, act);
+    if (T <= 16 && K % 32 == 0 && ((uintptr_t)W & 15) == 0)        // a few rows: one thread per output (same bits)
+        hipLaunchKernelGGL(linear_f32_rows_kernel<8>, dim3((N + 255) / 256, T), dim3(256), 0, stream, x, W, scale, residual, y, T, N,
+                           K, ldx, act);
+    else
+        hipLaunchKernelGGL(linear_f32_kernel, dim3((N + 63) / 64, (T + 63) / 64), dim3(256), 0, stream, x, W, scale, residual, y, T, N,
+                           K, ldx, act);
     CSM_CHECK_LAUNCH("csm_linear_f32");
     return 0;
 }
@@ -251,6 +420,48 @@ extern "C" int csm_attn_window_f32(const float* qkv, float* out, int T, int H, i
     CSM_REQUIRE(head_dim == 64, "csm_attn_window_f32: head_dim %d unsupported (64)", head_dim);
     hipLaunchKernelGGL((attn_f32_kernel<64>), dim3(T, H), dim3(64), (size_t)window * sizeof(float), stream, qkv, out, T, H, window);
     CSM_CHECK_LAUNCH("csm_attn_window_f32");
+    return 0;
+}
+
+extern "C" int csm_conv1d_stream_f32(const float* hist, const float* x, const float* w, const float* bias, const float* residual,
+                                     float* y, float* hist_out, int C_in, int C_out, int n, int k, int dilation, int groups, int elu_in,
+                                     hipStream_t stream) {
+    CSM_REQUIRE(x && w && y && C_in > 0 && C_out > 0 && n > 0 && k > 0 && dilation > 0 && groups > 0 && C_in % groups == 0 &&
+                    C_out % groups == 0 && C_out <= 65535, "csm_conv1d_stream_f32: bad arguments");
+    CSM_REQUIRE(k == 1 || (hist && hist_out && hist != hist_out), "csm_conv1d_stream_f32: k > 1 needs two distinct history buffers");
+    int bx = (n + 255) / 256;
+    if (bx > 4096) bx = 4096;
+    hipLaunchKernelGGL(conv1d_stream_kernel, dim3(bx, C_out), dim3(256), 0, stream, hist, x, w, bias, residual, y, hist_out, C_in, C_out,
+                       n, k, dilation, groups, elu_in);
+    CSM_CHECK_LAUNCH("csm_conv1d_stream_f32");
+    return 0;
+}
+
+extern "C" int csm_conv_transpose1d_stream_f32(const float* hist, const float* x, const float* w, const float* bias, float* y,
+                                               float* hist_out, int C_in, int C_out, int n, int pos0, int k, int stride, int groups,
+                                               int elu_in, hipStream_t stream) {
+    CSM_REQUIRE(x && w && y && C_in > 0 && C_out > 0 && n > 0 && pos0 >= 0 && k > 0 && stride > 0 && groups > 0 &&
+                    C_in % groups == 0 && C_out % groups == 0 && C_out <= 65535 && (long long)(pos0 + (long long)n) * stride < (1LL << 31),
+                "csm_conv_transpose1d_stream_f32: bad arguments");
+    CSM_REQUIRE(k <= stride || (hist && hist_out && hist != hist_out),
+                "csm_conv_transpose1d_stream_f32: k > stride needs two distinct history buffers");
+    int bx = (n * stride + 255) / 256;
+    if (bx > 4096) bx = 4096;
+    hipLaunchKernelGGL(conv_transpose1d_stream_kernel, dim3(bx, C_out), dim3(256), 0, stream, hist, x, w, bias, y, hist_out, C_in, C_out,
+                       n, pos0, k, stride, groups, elu_in);
+    CSM_CHECK_LAUNCH("csm_conv_transpose1d_stream_f32");
+    return 0;
+}
+
+extern "C" int csm_attn_window_stream_f32(const float* qkv, float* kcache, float* vcache, float* out, int n, int pos0, int H,
+                                          int head_dim, int window, int ring, hipStream_t stream) {
+    CSM_REQUIRE(qkv && kcache && vcache && out && n > 0 && pos0 >= 0 && H > 0 && window > 0 && window <= 8192 && n <= 65535,
+                "csm_attn_window_stream_f32: bad arguments");
+    CSM_REQUIRE(ring >= window + n - 1, "csm_attn_window_stream_f32: ring %d < window %d + n %d - 1", ring, window, n);
+    CSM_REQUIRE(head_dim == 64, "csm_attn_window_stream_f32: head_dim %d unsupported (64)", head_dim);
+    hipLaunchKernelGGL((attn_f32_stream_kernel<64>), dim3(n, H), dim3(64), (size_t)window * sizeof(float), stream, qkv, kcache, vcache, out,
+                       pos0, H, window, ring);
+    CSM_CHECK_LAUNCH("csm_attn_window_stream_f32");
     return 0;
 }
 

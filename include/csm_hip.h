@@ -290,6 +290,22 @@ int csm_linear_f32(const float* x, const float* W, const float* scale, const flo
 int csm_rope_half_f32(float* qkv, int T, int H, int head_dim, float base, int pos0, csm_stream_t stream);
 int csm_attn_window_f32(const float* qkv, float* out, int T, int H, int head_dim, int window, csm_stream_t stream);
 int csm_transpose_f32(const float* in, float* out, int R, int C, csm_stream_t stream);
+/* Streaming (chunk-by-chunk) forms of the causal decoder ops, additive since ABI 3.  Each computes every output with the same
+ * arithmetic as its full-sequence twin, so a decoder that carries the state below is bit-identical to a whole-sequence decode.
+ * conv1d: causal stride-1 conv over [hist | x], x = [C_in][n] new columns, hist = the previous (k-1)*dilation input columns
+ * (zeros at the start of a sequence; may be NULL when k == 1); y = [C_out][n] (bias / residual / input ELU as csm_conv1d_f32);
+ * the next history (last (k-1)*dilation columns of [hist | x]) goes to hist_out, which must not alias hist. */
+int csm_conv1d_stream_f32(const float* hist, const float* x, const float* w, const float* bias, const float* residual, float* y,
+                          float* hist_out, int C_in, int C_out, int n, int k, int dilation, int groups, int elu_in, csm_stream_t stream);
+/* transposed conv (causal: crop_left 0) for n new input columns at absolute input position pos0; hist = the previous
+ * ceil(k/stride)-1 input columns; y = [C_out][n*stride]; next history to hist_out (as above). */
+int csm_conv_transpose1d_stream_f32(const float* hist, const float* x, const float* w, const float* bias, float* y, float* hist_out,
+                                    int C_in, int C_out, int n, int pos0, int k, int stride, int groups, int elu_in, csm_stream_t stream);
+/* csm_attn_window_f32 for the n rows of qkv [n][3*H*head_dim] (post-RoPE) at positions pos0..pos0+n-1: keys before pos0 are read
+ * from kcache / vcache ([ring][H*head_dim], position p in slot p % ring) and the n new k / v rows are appended there.  Needs
+ * ring >= window + n - 1 (the slots read and written in one launch must not overlap). */
+int csm_attn_window_stream_f32(const float* qkv, float* kcache, float* vcache, float* out, int n, int pos0, int H, int head_dim,
+                               int window, int ring, csm_stream_t stream);
 
 #ifdef __cplusplus
 }

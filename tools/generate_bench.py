@@ -3,7 +3,9 @@
 Mimi decode, on one MI355X, CSM-1B random init.  Neither tokenizer can be fetched offline: the text side is a byte-level
 stand-in, the audio side is the real GPU codec (csm.codec.MimiCodec) with seeded random weights in the Hugging Face
 layout (GEN_CODEC=rvq swaps in the quantiser-only stand-in when transformers is unavailable).  GEN_LORA=q_proj,v_proj (or
-all): decode frames/s with live LoRA adapters against the same adapters merged, alternated in one process."""
+all): decode frames/s with live LoRA adapters against the same adapters merged, alternated in one process.  GEN_STREAM=1:
+generate_stream() with chunk_frames 1, 2 and 4 against generate() on the same setting, alternated in one process: time from
+the call to the first chunk on the host, total wall time and frames/s."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -157,9 +159,60 @@ def lora_main(mods):
           f"{best['live'] / best['merged']:.3f}x")
 
 
+def stream_main():
+    """GEN_STREAM=1: for each chunk size, generate() and generate_stream() alternate (GEN_ROUNDS rounds, same seed, so the
+    same frames); the first chunk counts as arrived when its samples are on the host."""
+    dev = "cuda:0"
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=make_codec(dev))
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+    frames = int(os.environ.get("GEN_FRAMES", 125))
+    ms = 80 * frames
+    gen.generate(text, 1, ctx, max_audio_length_ms=80 * 5)                           # warm-up: allocator, graph capture
+    for _ in gen.generate_stream(text, 1, ctx, max_audio_length_ms=80 * 5, chunk_frames=2):
+        pass
+
+    def plain():
+        torch.manual_seed(0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        audio = gen.generate(text, 1, ctx, max_audio_length_ms=ms)
+        audio.cpu()
+        dt = time.perf_counter() - t0
+        return dt, dt, audio.numel() / 1920
+
+    def streamed(c):
+        torch.manual_seed(0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        first, n = None, 0
+        for chunk in gen.generate_stream(text, 1, ctx, max_audio_length_ms=ms, chunk_frames=c):
+            chunk.cpu()
+            if first is None:
+                first = time.perf_counter() - t0
+            n += chunk.numel()
+        return first, time.perf_counter() - t0, n / 1920
+
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    for c in (1, 2, 4):
+        res = {"generate": [], "stream": []}
+        for _ in range(rounds):
+            res["generate"].append(plain())
+            res["stream"].append(streamed(c))
+        for name, runs in res.items():
+            first, total, nfr = min(runs, key=lambda r: r[1])
+            print(f"chunk_frames={c} {name:8s}: first audio {first * 1e3:7.1f} ms, total {total * 1e3:7.1f} ms, {nfr:.0f} frames, "
+                  f"{nfr / total:.1f} frames/s (best of {rounds}; totals {[round(r[1] * 1e3, 1) for r in runs]} ms)")
+        ratio = min(r[1] for r in res["stream"]) / min(r[1] for r in res["generate"])
+        print(f"chunk_frames={c}: stream / generate total wall time = {ratio:.3f}")
+
+
 def main():
     if os.environ.get("GEN_LORA"):
         return lora_main(os.environ["GEN_LORA"])
+    if os.environ.get("GEN_STREAM") == "1":
+        return stream_main()
     dev = "cuda:0"
     model = Model(csm_1b_args(), device=dev, seed=0)
     codec = make_codec(dev)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Mimi codec on the GPU: encode / decode time for 10 s of 24 kHz audio (seeded random weights with the HF key names)."""
+"""Mimi codec on the GPU: encode / decode time for 10 s of 24 kHz audio (seeded random weights with the HF key names), then
+the streaming decoder: microseconds per ``MimiDecodeStream.step`` of n = 1, 2, 4 frames and the kernel launches per step."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -24,3 +25,40 @@ def t(fn, n=3):
 te, codes = t(lambda: codec.encode(wav))
 td, out = t(lambda: codec.decode(codes))
 print(f"encode 10 s: {te*1e3:.1f} ms ({10/te:.0f}x real time) -> codes {tuple(codes.shape)};  decode: {td*1e3:.1f} ms ({10/td:.0f}x real time) -> {tuple(out.shape)}")
+
+
+class _Counting:
+    """Counts the C-ABI calls made through a module's ``lib`` (each is one kernel launch for these ops)."""
+    def __init__(self, lib):
+        self._lib, self.n = lib, 0
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        def call(*a):
+            self.n += 1
+            return fn(*a)
+        return call
+
+
+import csm.codec.mimi as mimi_mod
+from csm.hip import ops as ops_mod
+stream = codec.decode_stream()
+for n in (1, 2, 4):
+    steps = 48 // n
+    chunk = codes[:, :, :n]
+    stream.reset()
+    for _ in range(4):
+        stream.step(chunk)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        stream.step(chunk)
+    torch.cuda.synchronize()
+    us = (time.perf_counter() - t0) / steps * 1e6
+    counters = [_Counting(mimi_mod.lib), _Counting(ops_mod.lib)]
+    mimi_mod.lib, ops_mod.lib = counters
+    stream.step(chunk)
+    mimi_mod.lib, ops_mod.lib = counters[0]._lib, counters[1]._lib
+    launches = counters[0].n + counters[1].n + 1          # + the latent's zero fill
+    print(f"stream step n={n}: {us:.0f} us per step ({us / n:.0f} us per 80-ms frame, {n * 80e3 / us:.0f}x real time), "
+          f"{launches} launches per step")
