@@ -752,7 +752,7 @@ class Engine:
 
     @torch.no_grad()
     def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None):
-        """Batched generation (up to 4 utterances): prefill B prompts of different lengths and sample the
+        """Batched generation (up to 16 utterances): prefill B prompts of different lengths and sample the
         first frame of each; later frames go through ``generate_frame`` with ``[B, 1, K+1]`` tokens and a non-zero
         ``input_pos``, exactly as for one utterance."""
         m = self.m
@@ -990,8 +990,12 @@ class DecodeState:
 
     def __init__(self, engine: "Engine", B: int):
         m = engine.m
-        if B > 4:
-            raise ValueError("the decode kernels handle up to 4 sequences at a time")
+        if not 1 <= B <= 16:
+            raise ValueError(f"the decode kernels handle 1 to 16 sequences at a time (got {B})")
+        if B > 4 and m.lora is not None and not m.lora.merged:
+            # (the K-extension kernels of live adapters take at most 4 rows: csm_gemv_bf16_kext, csm_lora_project_bf16)
+            raise ValueError(f"generate with live (un-merged) LoRA adapters takes at most 4 sequences at a time (got {B}): "
+                             "merge them first (merge_lora_weights) or decode at most 4 utterances")
         self.e, self.B = engine, B
         dev = m.device
         self.bb = _DecodeStack(engine.backbone, B, m.bb.max_seq_len)

@@ -190,14 +190,16 @@ class Generator:
     def generate_batch(self, texts: List[str], speakers: List[int], contexts: List[List[Segment]],
                        max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
                        eos_check_every: int = 8) -> List[torch.Tensor]:
-        """``generate`` for up to 4 utterances at once (not in the reference, whose loop is single-utterance): the prompts
+        """``generate`` for up to 16 utterances at once (not in the reference, whose loop is single-utterance): the prompts
         (different lengths) are prefilled one by one into their rows of the KV caches, then every decode frame advances all
         rows together - the decode kernels share each weight load between the batch rows, so B utterances cost about as
-        much as one.  A row stops contributing at its own EOS frame; the loop ends when every row has one."""
+        much as one.  A row stops contributing at its own EOS frame; the loop ends when every row has one.  Up to 4 rows
+        each row's codes are those of a one-utterance run; 5..16 rows go through the MFMA decode products, whose rows are
+        the same bits for any batch size in 5..16 (not those of 1..4).  Live (un-merged) LoRA adapters: at most 4."""
         self._run += 1
         B = len(texts)
-        if not (1 <= B <= 4 and len(speakers) == B and len(contexts) == B):
-            raise ValueError("generate_batch takes 1..4 utterances with one speaker id and one context list each")
+        if not (1 <= B <= 16 and len(speakers) == B and len(contexts) == B):
+            raise ValueError("generate_batch takes 1..16 utterances with one speaker id and one context list each")
         self._model.reset_caches()
         max_audio_frames = int(max_audio_length_ms / 80)
         K = self._model.args.audio_num_codebooks

@@ -390,7 +390,8 @@ def adamw_step_split(master_lo, m, v, param, grad, lr, beta1, beta2, eps, wd, st
 
 
 def gemv(x, W, y, residual=None):
-    """y[B,N] = x[B,K] W[N,K]^T (+ residual), B <= 4."""
+    """y[B,N] = x[B,K] W[N,K]^T (+ residual), B <= 16.  B <= 4: the VALU kernels, each row bit-equal to a one-row launch;
+    B = 5..16 (K % 32 == 0): the MFMA kernel, each row bit-equal across every B in 5..16, position and batch-mate."""
     B, K = x.shape
     N = W.shape[0]
     assert W.shape[1] == K and y.shape == (B, N) and x.stride(1) == 1 and W.stride(1) == 1 and y.stride(1) == 1
@@ -401,7 +402,8 @@ def gemv(x, W, y, residual=None):
 
 def gemv_ex(x, W, y, residual=None, norm_scale=None, eps=1e-5, swiglu=False, row_index=None, row_offset=0):
     """gemv with an RMSNorm prologue on x (norm_scale), the SwiGLU pairing of interleaved gate/up rows (y is [B, N/2]) and /
-    or x gathered from a table: batch row b = x[row_index[b] + row_offset] (row_index int32 [B] on the device)."""
+    or x gathered from a table: batch row b = x[row_index[b] + row_offset] (row_index int32 [B] on the device).  B <= 16 as
+    for ``gemv`` (every fusion on both kernel families)."""
     B = y.shape[0]
     K = x.shape[1]
     N = W.shape[0]

@@ -749,6 +749,141 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
     }
 }
 
+// Five to sixteen batch rows (generate_batch at B > 4): the product as MFMA tiles, D[n][b] = sum_k W[n][k] x^[b][k] with
+// v_mfma_f32_16x16x32_bf16, A = 16 weight rows, B = x^ transposed with the batch rows padded to 16 by zeros (never stored).
+// A workgroup owns one tile of 16 weight rows (8 gate/up pairs under SWIGLU) and its eight waves split K: wave w takes the
+// 64-k steps s = w, w + 8, w + 16, ...  In a step lane l (column c = l & 15, k group g = l >> 4) loads 32 contiguous bytes of
+// weight row n0 + c at k = 64 s + 16 g - two loads, so the four lanes of a row fetch its whole 128-byte line - and uses the first
+// and the second 16 bytes as the fragments of two MFMAs.  The fragment's k order is thereby permuted (element j of group g is
+// k = 16 g + j, resp. 16 g + 8 + j): the B fragment is loaded with the same permutation, x^[c][64 s + 16 g ..], straight from
+// global memory (x is a few KB, L2 resident).  No LDS copy of x: every element of x^ is multiplied by exactly one wave of the
+// workgroup, so staging it would add a round trip and a barrier and save nothing.  Weights go global -> VGPRs, a segment of
+// SEG steps in flight per lane before the first MFMA waits for them (non-temporal under the g_gemv_nt policy).
+// RMSNorm prologue: the workgroup's waves compute rstd of the batch rows with gemv_kernel's order (lane-strided 8-element
+// chunks, wave_sum) behind one barrier that keeps the weight loads in flight; x^ = bf16(x rstd w) as gemv_regn_kernel rounds it.
+// The eight partial tiles meet in LDS and are summed in wave order 0..7 (no atomics).  Every output column sees only its own
+// batch row's operands in an order fixed by K, so a row's result is the same bits for any B in 5..16, any position of the row in
+// the batch and any contents of the other rows (tests/test_generate_wide_batch_gpu.py).  It is not bit-equal to the B <= 4
+// kernels, which sum in another order.
+template <int SEG, typename OutT, bool SWIGLU, bool NT>
+__global__ __launch_bounds__(512) void gemv_mfma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, OutT* __restrict__ y,
+                                                        const bf16_t* __restrict__ R, int B, int N, int K, int ldw, int ldx, int ldy,
+                                                        const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
+                                                        int row_offset) {
+    constexpr int NW = 8;
+    __shared__ float rs[16];
+    __shared__ float part[NW][16][17];                        // [wave][weight row of the tile][batch row] (+1: no bank conflicts)
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int g = lane >> 4, c = lane & 15;
+    const int n0 = blockIdx.x * 16;
+    const int S = (K + 63) >> 6;                              // 64-k steps; with K % 64 == 32 the last one has groups 0, 1 only
+    const bf16_t* wrow = W + (size_t)min(n0 + c, N - 1) * ldw + 16 * g;       // (rows past N re-read row N-1, never stored)
+    const bool brow = c < B;
+    const size_t xr = brow ? (row_index ? (size_t)(row_index[c] + row_offset) : (size_t)c) : (size_t)0;
+    const bf16_t* xrow = x + xr * ldx + 16 * g;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    const int nseg = (S + NW * SEG - 1) / (NW * SEG);
+    for (int sg = 0; sg < nseg; ++sg) {
+        U4 wq[SEG][2], xq[SEG][2];
+        const U4 z = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) {
+            const int s = (sg * SEG + i) * NW + wv;
+            const int k = 64 * s + 16 * g;
+            wq[i][0] = z; wq[i][1] = z;
+            if (s < S && k < K) {
+                const U4* p = reinterpret_cast<const U4*>(wrow + 64 * s);
+                wq[i][0] = NT ? __builtin_nontemporal_load(p) : p[0];
+                wq[i][1] = NT ? __builtin_nontemporal_load(p + 1) : p[1];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) {
+            const int s = (sg * SEG + i) * NW + wv;
+            const int k = 64 * s + 16 * g;
+            xq[i][0] = z; xq[i][1] = z;
+            if (brow && s < S && k < K) {
+                const U4* p = reinterpret_cast<const U4*>(xrow + 64 * s);
+                xq[i][0] = p[0]; xq[i][1] = p[1];
+            }
+        }
+        if (norm_w) {
+            if (sg == 0) {
+                // rstd of batch rows wv, wv + 8 (gemv_kernel's summation order); one barrier, LDS only: the weights stay in flight
+                for (int b = wv; b < B; b += NW) {
+                    const bf16_t* xb = x + (row_index ? (size_t)(row_index[b] + row_offset) : (size_t)b) * ldx;
+                    float ss = 0.f;
+                    for (int q = lane; q < (K >> 3); q += 64) {
+                        float f[8];
+                        unpack8(*reinterpret_cast<const U4*>(xb + q * 8), f);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) ss += f[j] * f[j];
+                    }
+                    ss = wave_sum(ss);
+                    if (lane == 0) rs[b] = rsqrtf(ss / (float)K + eps);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            }
+            if (brow) {
+                const float r = rs[c];
+#pragma unroll
+                for (int i = 0; i < SEG; ++i) {
+                    const int s = (sg * SEG + i) * NW + wv;
+                    const int k = 64 * s + 16 * g;
+                    if (s < S && k < K) {
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            float f[8], w8[8];
+                            unpack8(xq[i][h], f);
+                            unpack8(*reinterpret_cast<const U4*>(norm_w + k + 8 * h), w8);
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) f[j] = f[j] * r * w8[j];
+                            xq[i][h] = pack8(f);                      // the bf16 rounding of gemv_regn_kernel's x^
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < SEG; ++i) {
+            const int s = (sg * SEG + i) * NW + wv;
+            if (s < S) {                                              // (wave-uniform)
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wq[i][0]), __builtin_bit_cast(bf16x8, xq[i][0]), acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wq[i][1]), __builtin_bit_cast(bf16x8, xq[i][1]), acc, 0, 0, 0);
+            }
+        }
+    }
+    // lane holds D[weight row 4 g + r][batch row c]; the eight K slices are added in wave order
+#pragma unroll
+    for (int r = 0; r < 4; ++r) part[wv][4 * g + r][c] = acc[r];
+    __syncthreads();
+    const int t = threadIdx.x;
+    if constexpr (SWIGLU) {
+        const int i = t & 7, b = t >> 3;                      // output n0 / 2 + i of batch row b: gate row 2 i, up row 2 i + 1
+        if (b < B && n0 + 2 * i < N) {
+            float gs = part[0][2 * i][b], us = part[0][2 * i + 1][b];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) { gs += part[w][2 * i][b]; us += part[w][2 * i + 1][b]; }
+            const float gg = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
+            float v = silu(gg) * u;
+            const int n = (n0 >> 1) + i;
+            if (R) v += bf2f(R[(size_t)b * ldy + n]);
+            y[(size_t)b * ldy + n] = f2bf(v);
+        }
+    } else {
+        const int rr = t & 15, b = t >> 4;
+        const int n = n0 + rr;
+        if (b < B && n < N) {
+            float v = part[0][rr][b];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) v += part[w][rr][b];
+            if (R) v += bf2f(R[(size_t)b * ldy + n]);
+            if constexpr (sizeof(OutT) == 2) y[(size_t)b * ldy + n] = f2bf(v);
+            else y[(size_t)b * ldy + n] = v;
+        }
+    }
+}
+
 // y[b][n] = sum_k x[b][k] * W[k][n]  (weights stored K-major, e.g. audio_head[i] = [d'][V]): a thread owns 8 columns.
 template <int NB, typename OutT>
 __global__ __launch_bounds__(256) void gemv_t_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, OutT* __restrict__ y,
@@ -1472,10 +1607,31 @@ extern "C" int csm_decode_stamps(unsigned long long* host, int max_records) {
 #endif
 // (g_gemv_rpw: gate/up pairs per wave in the depth decoder's w13 product.  Measured at 1 / 2 / 4: 207.5 / 207.5 / 204 frames/s -
 //  that launch streams 32 MB and is bound by its loads, not by the per-wave normalisation: one pair per wave stays the default)
-static int g_gemv_reg = 1, g_gemv_nt = 1, g_gemv_rpw = 1, g_gemv_regn = 1;       // csm_set_decode_tuning (A/B: tools/probes)
+// (g_gemv_mfma_small: B = 2..4 through gemv_mfma_kernel as well - A/B measurement only, off by default: it gives up the B <= 4
+//  products' bit-equality with the one-row kernels)
+static int g_gemv_reg = 1, g_gemv_nt = 1, g_gemv_rpw = 1, g_gemv_regn = 1, g_gemv_mfma_small = 0;   // csm_set_decode_tuning (A/B: tools/probes)
 extern "C" int csm_set_decode_tuning(int key, int value) {
     if (key == 0) g_gemv_reg = value; else if (key == 1) g_gemv_nt = value; else if (key == 2) g_gemv_rpw = value;
-    else if (key == 3) g_gemv_regn = value; else return 1;
+    else if (key == 3) g_gemv_regn = value; else if (key == 4) g_gemv_mfma_small = value; else return 1;
+    return 0;
+}
+// B = 5..16 (or 2..4 under g_gemv_mfma_small): gemv_mfma_kernel, one workgroup per 16 weight rows; SEG = 64-k steps per wave
+// and segment, sized so that K <= 2048 runs as one segment (K = 8192: two of eight steps)
+static int gemv_mfma_launch(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx,
+                            int ldy, int out_f32, const void* norm_w, float eps, int swiglu, const int* row_index, int row_offset,
+                            hipStream_t stream) {
+    CSM_REQUIRE((K & 31) == 0, "csm_gemv_bf16: B=%d needs K %% 32 == 0 (K=%d)", B, K);
+    const int grid = (N + 15) / 16;
+    const int spw = ((K + 63) / 64 + 7) / 8;                  // 64-k steps per wave
+    const bool nt = g_gemv_nt && (K == 2048 || (K == 8192 && N == 2048));
+#define LM(SEG, T, SW, NT_) hipLaunchKernelGGL((gemv_mfma_kernel<SEG, T, SW, NT_>), dim3(grid), dim3(512), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, B, N, K, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset)
+#define LMS(T, SW, NT_) do { if (spw <= 1) LM(1, T, SW, NT_); else if (spw <= 2) LM(2, T, SW, NT_); else if (spw <= 4) LM(4, T, SW, NT_); else LM(8, T, SW, NT_); } while (0)
+    if (swiglu) { if (nt) LMS(bf16_t, true, true); else LMS(bf16_t, true, false); }
+    else if (out_f32) { if (nt) LMS(float, false, true); else LMS(float, false, false); }
+    else { if (nt) LMS(bf16_t, false, true); else LMS(bf16_t, false, false); }
+#undef LMS
+#undef LM
+    CSM_CHECK_LAUNCH("csm_gemv_bf16");
     return 0;
 }
 // ext: empty (the plain products) or one GemvExt (csm_gemv_bf16_kext): the same dispatch, the kernels' trailing pack
@@ -1483,10 +1639,16 @@ template <typename... Ext>
 static int gemv_launch(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
                        int out_f32, const void* norm_w, float eps, int swiglu, const int* row_index, int row_offset,
                        hipStream_t stream, Ext... ext) {
-    CSM_REQUIRE(x && W && y && B >= 1 && B <= 4 && N > 0 && K > 0 && (K & 7) == 0 && (ldw & 7) == 0 && (ldx & 7) == 0,
-                "csm_gemv_bf16: bad arguments (B=%d N=%d K=%d)", B, N, K);
-    CSM_REQUIRE((size_t)B * K * 2 <= 65536, "csm_gemv_bf16: B*K too large for the LDS copy of x");
+    CSM_REQUIRE(x && W && y && B >= 1 && B <= 16 && N > 0 && K > 0 && (K & 7) == 0 && (ldw & 7) == 0 && (ldx & 7) == 0,
+                "csm_gemv_bf16: bad arguments (B=%d N=%d K=%d: needs 1 <= B <= 16)", B, N, K);
     CSM_REQUIRE(!swiglu || ((N & 1) == 0 && !out_f32), "csm_gemv_bf16_ex: the SwiGLU form needs an even N and bf16 output");
+    if constexpr (sizeof...(Ext) == 0) {
+        if (B > 4 || (B >= 2 && g_gemv_mfma_small && (K & 31) == 0))
+            return gemv_mfma_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_w, eps, swiglu, row_index, row_offset, stream);
+    } else {
+        CSM_REQUIRE(B <= 4, "csm_gemv_bf16_kext: B=%d: the K-extension (live LoRA adapters) takes at most 4 batch rows", B);
+    }
+    CSM_REQUIRE((size_t)B * K * 2 <= 65536, "csm_gemv_bf16: B*K too large for the LDS copy of x");
     const int no = swiglu ? N / 2 : N;
     if (B == 1 && g_gemv_reg && (K == 1024 || K == 2048 || K == 8192)) {
         // one batch row: x in registers, no LDS, no barrier (gemv_reg_kernel); matrices of the 2048-wide stack are streamed once

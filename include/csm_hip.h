@@ -211,11 +211,14 @@ int csm_sample_topk(const float* logits, const float* q, int* out, int rows, int
                     csm_stream_t stream);
 
 /* ---- K15: batch-1 decode of Model.generate_frame (model.py:161-195) against KV caches ------------------------------ *
- * y[b][n] = sum_k x[b][k] W[n][k] (+ residual[b][n]), B <= 4 (weight-streaming matrix-vector product) */
+ * y[b][n] = sum_k x[b][k] W[n][k] (+ residual[b][n]), B <= 16 (weight-streaming matrix-vector product).  B <= 4: VALU kernels,
+ * row b bit-identical to a one-row launch on that row.  B = 5..16 (ABI 3, additive range extension; needs K % 32 == 0): MFMA
+ * tiles, row b bit-identical across every B in 5..16, every position in the batch and any other rows - not to the B <= 4 result */
 /* tuning switches for A/B runs (since ABI 3): key 0 = one-row products keep x in registers (no LDS copy, no barrier; default 1),
  * key 1 = the 2048-wide stack's weights are loaded non-temporally in decode (default 1),
  * key 2 = gate/up pairs per wave in the depth decoder's w13 product (1, 2 or 4; default 1: measured equal or slower above),
- * key 3 = two to four batch rows: K = 1024 / 2048 products keep every row of x in registers (default 1; 0 = the LDS kernel) */
+ * key 3 = two to four batch rows: K = 1024 / 2048 products keep every row of x in registers (default 1; 0 = the LDS kernel),
+ * key 4 = two to four batch rows through the B = 5..16 MFMA kernel (default 0; A/B measurement only) */
 int csm_set_decode_tuning(int key, int value);
 int csm_gemv_bf16(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
                   int out_f32, csm_stream_t stream);
@@ -234,7 +237,7 @@ int csm_lora_project_bf16(const void* x, const void* At, void* t, int B, int K, 
 /* csm_gemv_bf16_ex with a K-extension: output row n also takes sum_j ext_t[b][j] ext_B[n][j] (+ bias[n], bias may be NULL) before
  * the residual / SwiGLU / fp32-output epilogue (ext_B rows in W's row order: interleaved gate/up for swiglu).  kx <= 512, a
  * multiple of 8, 16-byte aligned rows.  ext_B all zeros (no bias): bit-identical to csm_gemv_bf16_ex; row b of a B-row launch is
- * bit-identical to the one-row launch on that row. */
+ * bit-identical to the one-row launch on that row.  B <= 4. */
 int csm_gemv_bf16_kext(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
                        int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index, int row_offset,
                        const void* ext_t, const void* ext_B, int kx, int ld_ext_t, int ld_ext_B, const void* bias,

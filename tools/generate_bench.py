@@ -5,7 +5,8 @@ stand-in, the audio side is the real GPU codec (csm.codec.MimiCodec) with seeded
 layout (GEN_CODEC=rvq swaps in the quantiser-only stand-in when transformers is unavailable).  GEN_LORA=q_proj,v_proj (or
 all): decode frames/s with live LoRA adapters against the same adapters merged, alternated in one process.  GEN_STREAM=1:
 generate_stream() with chunk_frames 1, 2 and 4 against generate() on the same setting, alternated in one process: time from
-the call to the first chunk on the host, total wall time and frames/s."""
+the call to the first chunk on the host, total wall time and frames/s.  GEN_BATCH_SWEEP=1: generate_batch() at 1, 4, 8 and 16
+utterances from one process, one line each (aggregate frames/s, seconds per frame)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -208,7 +209,31 @@ def stream_main():
         print(f"chunk_frames={c}: stream / generate total wall time = {ratio:.3f}")
 
 
+def sweep_main():
+    """GEN_BATCH_SWEEP=1: ``run_batch``'s setting (5 s of context on alternate rows, GEN_FRAMES frames) for every batch size of
+    GEN_BATCH_SIZES (default 1,4,8,16) on one model; one line per size."""
+    dev = "cuda:0"
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=make_codec(dev))
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    frames = int(os.environ.get("GEN_FRAMES", 125))
+    for nb in [int(v) for v in os.environ.get("GEN_BATCH_SIZES", "1,4,8,16").split(",")]:
+        texts = [f"utterance number {i}: the quick brown fox jumps over the lazy dog" for i in range(nb)]
+        ctxs = [ctx if i % 2 == 0 else [] for i in range(nb)]
+        for _ in range(2):                                                   # the first run captures the batch's frame graph
+            torch.cuda.synchronize()
+            t0 = time.time()
+            outs = gen.generate_batch(texts, list(range(nb)), ctxs, max_audio_length_ms=80 * frames)
+            torch.cuda.synchronize()
+            dt = time.time() - t0
+        tot = sum(o.numel() for o in outs) / 1920
+        print(f"GEN_BATCH_SWEEP B={nb:2d}: {tot:.0f} frames in {dt:.3f} s -> {tot / dt:.1f} frames/s aggregate, "
+              f"{dt / max(tot / nb, 1) * 1e3:.2f} ms per batch frame ({tot * 0.08 / dt:.2f}x real time aggregate)", flush=True)
+
+
 def main():
+    if os.environ.get("GEN_BATCH_SWEEP") == "1":
+        return sweep_main()
     if os.environ.get("GEN_LORA"):
         return lora_main(os.environ["GEN_LORA"])
     if os.environ.get("GEN_STREAM") == "1":
