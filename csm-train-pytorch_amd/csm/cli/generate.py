@@ -35,6 +35,8 @@ def parse_args(argv=None):
     p.add_argument("--text-tokenizer", type=str, required=True, help="local directory of the Llama-3.2 tokenizer files")
     p.add_argument("--stream", action="store_true", help="write the WAV chunk by chunk while the frames are generated")
     p.add_argument("--chunk-frames", type=int, default=4, help="80-ms frames per streamed chunk (default: 4)")
+    p.add_argument("--lora-adapter", type=str, default=None,
+                   help="LoRA adapter file written by csm-finetune-lora (.safetensors with its _metadata.json), applied without merging")
     return p.parse_args(argv)
 
 
@@ -58,17 +60,21 @@ def main(argv=None):
     speaker_id = VOICE_PRESETS[args.voice] if args.voice else args.speaker
     generator = load_csm_1b(args.model_path, args.device, mimi_weights=args.mimi_weights, tokenizer_path=args.text_tokenizer)
     context = build_context(args, generator.sample_rate)
+    adapter = None
+    if args.lora_adapter:
+        adapter = "cli"
+        generator.load_adapter(adapter, args.lora_adapter)
     if args.stream:
-        return stream_to_wav(generator, args, speaker_id, context)
+        return stream_to_wav(generator, args, speaker_id, context, adapter)
     audio = generator.generate(text=args.text, speaker=speaker_id, context=context, max_audio_length_ms=args.max_audio_length_ms,
-                               temperature=args.temperature, topk=args.topk)
+                               temperature=args.temperature, topk=args.topk, adapter=adapter)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     generator.save_wav(args.output, audio)
     print(f"Audio saved to {args.output} ({audio.numel() / generator.sample_rate:.2f} s at {generator.sample_rate} Hz)")
     return 0
 
 
-def stream_to_wav(generator, args, speaker_id, context):
+def stream_to_wav(generator, args, speaker_id, context, adapter=None):
     """--stream: each chunk of ``generate_stream`` is appended to the WAV as it arrives (``wave`` patches the header's
     length on close); the samples are converted exactly as ``Generator.save_wav`` converts them, so the file is the same."""
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
@@ -80,7 +86,7 @@ def stream_to_wav(generator, args, speaker_id, context):
         w.setframerate(int(generator.sample_rate))
         for chunk in generator.generate_stream(text=args.text, speaker=speaker_id, context=context,
                                                max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature,
-                                               topk=args.topk, chunk_frames=args.chunk_frames):
+                                               topk=args.topk, chunk_frames=args.chunk_frames, adapter=adapter):
             pcm = (chunk.detach().float().cpu().clamp(-1, 1) * 32767.0).to(torch.int16).numpy().tobytes()
             if n == 0:
                 print(f"first chunk after {time.perf_counter() - t0:.3f} s")

@@ -79,6 +79,20 @@ def generation_lora(model):
         lo.training = was
 
 
+@contextmanager
+def row_lora(model, state):
+    """``generation_lora`` with ``state`` (a bank entry, csm/lora_bank.py; None = no adapter) standing in for ``model.lora`` for
+    the duration: a prefill row of a per-row-adapter batch runs the training forward exactly as a one-utterance generation with
+    that adapter live as ``model.lora`` would.  ``model.lora`` is restored afterwards, also on an error."""
+    prev = model.lora
+    model.lora = state
+    try:
+        with generation_lora(model) as lo:
+            yield lo
+    finally:
+        model.lora = prev
+
+
 class _Stack:
     """One Llama stack (backbone or decoder) bound to a model's arenas."""
 
@@ -714,16 +728,20 @@ class Engine:
         return self.backbone.forward(h0, B, S, False).view(B, S, -1)
 
     @torch.no_grad()
-    def generate_frame(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None):
+    def generate_frame(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None, adapters=None):
         """Reference model.py:140-195: backbone position(s) -> c0 -> 31 depth-decoder steps, against KV caches.
 
         The prompt (``input_pos`` starting at 0) is prefilled with the training forward kernels and its post-RoPE K/V
         rows are copied into the backbone cache; every later call is a single-position decode step (matrix-vector
         kernels + cache attention).  The decoder cache is reset every frame, as the reference does (model.py:181).
         ``model.use_kv_cache = False`` selects the cache-free prefix-recompute path (same arithmetic, kept as a check).
+        ``adapters`` (read on the first call of a generation, ignored later): a LoRAState or None per batch row - per-utterance
+        adapters from a bank (csm/lora_bank.py).
         """
         m, a = self.m, self.m.args
         self._need()
+        if int(input_pos[0, 0]) == 0:
+            m._gen_adapters = list(adapters) if adapters is not None and any(x is not None for x in adapters) else None
         if not getattr(m, "use_kv_cache", True):
             return self._generate_frame_recompute(tokens, tokens_mask, input_pos, temperature, topk, noise)
         dev = m.device
@@ -737,7 +755,7 @@ class Engine:
             raise RuntimeError("generate_frame: a non-first call (input_pos > 0) needs the state of a prompt prefilled with the "
                                "same batch size (call it with input_pos starting at 0 first)")
         if first:
-            st = m._decode_state = DecodeState(self, Bn)
+            st = m._decode_state = DecodeState(self, Bn, adapters)
         if first:
             last_h = st.prefill(tokens, tokens_mask)
             return self._frame_tail(st, last_h, temperature, topk, noise)
@@ -751,13 +769,13 @@ class Engine:
         return self._decode_frame(st, tokens, tokens_mask, temperature, topk, noise)
 
     @torch.no_grad()
-    def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None):
+    def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None, adapters=None):
         """Batched generation (up to 16 utterances): prefill B prompts of different lengths and sample the
         first frame of each; later frames go through ``generate_frame`` with ``[B, 1, K+1]`` tokens and a non-zero
         ``input_pos``, exactly as for one utterance."""
         m = self.m
         self._need()
-        st = m._decode_state = DecodeState(self, len(tokens_list))
+        st = m._decode_state = DecodeState(self, len(tokens_list), adapters)
         last_h = st.prefill_ragged(tokens_list, masks_list)
         return self._frame_tail(st, last_h, temperature, topk, noise)
 
@@ -803,6 +821,16 @@ class Engine:
     @torch.no_grad()
     def _generate_frame_recompute(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None):
         """Reference model.py:140-195.  The KV state is the token history (prefix recompute)."""
+        ads = getattr(self.m, "_gen_adapters", None)
+        if ads is not None:
+            # (the cache-free check path runs ONE adapter set for the whole batch: the training forward has no per-row adapters)
+            if self.m.lora is not None and not self.m.lora.merged:
+                raise ValueError("generate with per-utterance LoRA adapters while live (un-merged) adapters are attached as "
+                                 "model.lora: detach or merge them first")
+            if any(a is not ads[0] for a in ads):
+                raise ValueError("the recompute path (use_kv_cache = False) takes one adapter for all rows, not one per row")
+            with row_lora(self.m, ads[0]):
+                return self._generate_frame_recompute_body(tokens, tokens_mask, input_pos, temperature, topk, noise)
         with generation_lora(self.m):
             return self._generate_frame_recompute_body(tokens, tokens_mask, input_pos, temperature, topk, noise)
 
@@ -876,6 +904,8 @@ class _DecodeStack:
         self.pos_host = None
         # LoRA groups (DecodeState.__init__): per layer {group name: (At, Bx, bias or None)}, and the [B, KX] extension operand
         self.lora, self.lora_scale, self.lt = None, 1.0, None
+        # per-row adapters (attach_lora_rows): (row_adapter int32 [B], scale fp32 [A]) and the tensors the pointer tables name
+        self.lora_rows, self.lora_keep = None, []
 
     def fill_from(self, acts, B, S):
         """Copy the post-RoPE K / V rows of a prefilled prompt into the caches."""
@@ -930,6 +960,12 @@ class _DecodeStack:
         with (t, Bx, bias) as K-extension (norm prologue, SwiGLU and residual stay fused exactly as in the plain step)."""
         if G is None:
             return ops.gemv_ex(x, W, y, **kw)
+        if self.lora_rows is not None:
+            # per-row adapters: the same two launches over pointer tables, each row with its own adapter (or none)
+            At_tab, Bx_tab, bias_tab, kx, lda, ldb = G
+            ra, scale = self.lora_rows
+            ops.lora_project_rows(x, At_tab, self.lt, ra, scale, kx, lda, norm_scale=kw.get("norm_scale"), eps=kw.get("eps", 1e-5))
+            return ops.gemv_kext_rows(x, W, y, self.lt, Bx_tab, ra, kx, ldb, bias_tab=bias_tab, **kw)
         At, Bx, bias = G
         t = self.lt[:, :At.shape[1]]
         ops.lora_project(x, At, t, self.lora_scale, norm_scale=kw.get("norm_scale"), eps=kw.get("eps", 1e-5))
@@ -984,15 +1020,91 @@ class _DecodeStack:
             self.lora, self.lora_scale = plan, lo.scaling
             self.lt = torch.zeros(self.B, kmax, dtype=BF16, device=self.k[0].device)
 
+    def attach_lora_rows(self, states):
+        """``attach_lora`` for one adapter per batch row (``states``: a LoRAState or None per row, bank entries of one layout).
+        The adapters used are compacted to indices 0..A-1 (``row_adapter``, -1 = none); per layer and group the device tables
+        hold the addresses of each adapter's At / Bx arena views (read in place: a captured graph sees later writes to the
+        adapters' weights) and of its bias in the fused projection's row order (built once here, as ``attach_lora`` does)."""
+        st, c = self.stack, self.stack.c
+        dev = self.k[0].device
+        hq, hk, F, d = c.num_heads * c.head_dim, c.num_kv_heads * c.head_dim, c.intermediate_dim, c.embed_dim
+        rows = {"q_proj": slice(0, hq), "k_proj": slice(hq, hq + hk), "v_proj": slice(hq + hk, hq + 2 * hk), "output_proj": slice(0, d),
+                "w1": slice(0, 2 * F, 2), "w3": slice(1, 2 * F, 2), "w2": slice(0, d)}
+        used, idx = [], []
+        for s in states:
+            if s is None:
+                idx.append(-1)
+                continue
+            k = next((j for j, u in enumerate(used) if u is s), None)
+            if k is None:
+                used.append(s)
+                k = len(used) - 1
+            idx.append(k)
+        if not used:
+            return
+
+        def table(ptrs):
+            return torch.tensor(ptrs, dtype=torch.int64, device=dev)
+
+        plan, kmax, keep = [], 0, []
+        for i in range(c.num_layers):
+            L = {}
+            for gname in ("attn_in", "attn_out", "mlp_in", "mlp_out"):
+                Gs = [s.group(st.prefix, i, gname) for s in used]
+                if all(G is None for G in Gs):
+                    continue
+                if any(G is None or G.kx != Gs[0].kx or G.At.stride(0) != Gs[0].At.stride(0) or G.Bx.stride(0) != Gs[0].Bx.stride(0)
+                       for G in Gs):
+                    raise ValueError(f"per-row LoRA adapters: {st.prefix} layer {i} {gname}: the adapters do not share one layout")
+                kx = Gs[0].kx
+                if kx > 512:
+                    raise ValueError(f"generate with LoRA adapters: {kx} extension columns in {Gs[0].name} (the decode kernels take "
+                                     "at most 512: rank x adapters per fused projection)")
+                for G in Gs:
+                    if G.At.data_ptr() % 16 or G.Bx.data_ptr() % 16 or G.At.stride(1) != 1 or G.Bx.stride(1) != 1:
+                        raise ValueError(f"per-row LoRA adapters: {G.name} is not a 16-byte aligned row-major arena view")
+                bias_tab = None
+                if any(ad.bias is not None for G in Gs for ad in G.adapters.values()):
+                    ptrs = []
+                    for G in Gs:
+                        if any(ad.bias is not None for ad in G.adapters.values()):
+                            bias = torch.zeros(G.Bx.shape[0], dtype=BF16, device=dev)
+                            for mod, ad in G.adapters.items():
+                                if ad.bias is not None:
+                                    bias[rows[mod]] = ad.bias
+                            keep.append(bias)
+                            ptrs.append(bias.data_ptr())
+                        else:
+                            ptrs.append(0)
+                    bias_tab = table(ptrs)
+                L[gname] = (table([G.At.data_ptr() for G in Gs]), table([G.Bx.data_ptr() for G in Gs]), bias_tab, kx,
+                            Gs[0].At.stride(0), Gs[0].Bx.stride(0))
+                kmax = max(kmax, kx)
+            plan.append(L)
+        if kmax:
+            self.lora = plan
+            self.lora_rows = (torch.tensor(idx, dtype=torch.int32, device=dev),
+                              torch.tensor([s.scaling for s in used], dtype=torch.float32, device=dev))
+            # the adapters' arenas must outlive the state: the tables hold raw addresses
+            self.lora_keep = keep + [s.arena for s in used]
+            self.lt = torch.zeros(self.B, kmax, dtype=BF16, device=dev)
+
 
 class DecodeState:
     """Everything ``generate_frame`` keeps between calls: the two stacks' caches and small persistent buffers."""
 
-    def __init__(self, engine: "Engine", B: int):
+    def __init__(self, engine: "Engine", B: int, adapters=None):
         m = engine.m
         if not 1 <= B <= 16:
             raise ValueError(f"the decode kernels handle 1 to 16 sequences at a time (got {B})")
-        if B > 4 and m.lora is not None and not m.lora.merged:
+        # per-row adapters (csm/lora_bank.py): a LoRAState or None per row; all None is the same as no adapters
+        if adapters is not None and len(adapters) != B:
+            raise ValueError(f"per-row LoRA adapters: {len(adapters)} entries for {B} sequences")
+        self.adapters = list(adapters) if adapters is not None and any(a is not None for a in adapters) else None
+        if self.adapters is not None and m.lora is not None and not m.lora.merged:
+            raise ValueError("generate with per-utterance LoRA adapters while live (un-merged) adapters are attached as model.lora: "
+                             "detach them (model.lora = None), merge them (merge_lora_weights) or add them to the bank instead")
+        if B > 4 and self.adapters is None and m.lora is not None and not m.lora.merged:
             # (the K-extension kernels of live adapters take at most 4 rows: csm_gemv_bf16_kext, csm_lora_project_bf16)
             raise ValueError(f"generate with live (un-merged) LoRA adapters takes at most 4 sequences at a time (got {B}): "
                              "merge them first (merge_lora_weights) or decode at most 4 utterances")
@@ -1013,7 +1125,10 @@ class DecodeState:
         # output row per wave, so it keeps a [K-1][V][d'] copy made from the current weights when the state is created
         self.head_t = m.block("audio_head.padded").transpose(1, 2).contiguous()
         # live LoRA adapters ride on the decode products as K-extensions (merged ones are already in the weights)
-        if m.lora is not None and not m.lora.merged:
+        if self.adapters is not None:
+            self.bb.attach_lora_rows(self.adapters)
+            self.dc.attach_lora_rows(self.adapters)
+        elif m.lora is not None and not m.lora.merged:
             self.bb.attach_lora(m.lora)
             self.dc.attach_lora(m.lora)
 
@@ -1027,6 +1142,8 @@ class DecodeState:
 
     def prefill(self, tokens, masks):
         e, m = self.e, self.e.m
+        if self.adapters is not None:                        # (per-row adapters: every row's prefill with its own adapter)
+            return self.prefill_ragged(list(tokens), list(masks))
         B, S, K1 = tokens.shape
         if S > m.bb.max_seq_len:
             raise ValueError("prompt longer than max_seq_len")
@@ -1056,7 +1173,7 @@ class DecodeState:
             mk = mk.to(device=m.device, dtype=torch.uint8).contiguous()
             h0 = torch.empty(S, m.bb.embed_dim, dtype=BF16, device=m.device)
             ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
-            with generation_lora(m):
+            with (row_lora(m, self.adapters[b]) if self.adapters is not None else generation_lora(m)):
                 hidden = e.backbone.forward(h0, 1, S, True)
             self.bb.fill_row(e.backbone.acts, b, S)
             e.backbone.acts = []

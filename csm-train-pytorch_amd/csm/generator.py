@@ -55,6 +55,36 @@ class Generator:
         self.sample_rate = audio_tokenizer.sample_rate
         self.device = model.device
         self._run = 0                  # bumped by every generate*: an open generate_stream stops when it changes
+        self._bank = None              # LoRA adapters chosen per utterance (add_adapter / load_adapter)
+
+    # ---- per-utterance LoRA adapters (csm/lora_bank.py) -----------------------------------------------------------------
+    def _lora_bank(self):
+        if self._bank is None:
+            from .lora_bank import LoRABank
+            self._bank = LoRABank(self._model)
+        return self._bank
+
+    def add_adapter(self, name: str, state):
+        """Register a ``LoRAState`` of this model (e.g. ``CSMLoRATrainer``'s live ``model.lora``) under ``name``; generation
+        reads it in place.  Every adapter of the bank must share target modules, target layers, bias use and padded rank."""
+        return self._lora_bank().add(name, state)
+
+    def load_adapter(self, name: str, path: str):
+        """Load an adapter file written by ``csm-finetune-lora`` / ``CSMLoRATrainer.save_model(save_mode="lora")`` under
+        ``name`` (no merge: the base weights are shared by every adapter)."""
+        return self._lora_bank().load(name, path)
+
+    @property
+    def adapters(self) -> List[str]:
+        """Names of the loaded adapters."""
+        return [] if self._bank is None else self._bank.names
+
+    def _resolve_adapters(self, names):
+        if all(n is None for n in names):
+            return None
+        if self._bank is None:
+            raise ValueError(f"unknown LoRA adapter {next(n for n in names if n is not None)!r} (none loaded)")
+        return self._bank.resolve(names)
 
     def _tokenize_text_segment(self, text: str, speaker: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference generator.py:77-100: ``f"[{speaker}]{text}"`` ids into the last column."""
@@ -86,11 +116,13 @@ class Generator:
 
     @torch.inference_mode()
     def generate(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
-                 temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8) -> torch.Tensor:
-        """Reference generator.py:147-218.  The reference tests every frame for EOS on the host (one device sync per
+                 temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8, adapter: Optional[str] = None) -> torch.Tensor:
+        """Reference generator.py:147-218.  ``adapter``: the name of a bank adapter (``add_adapter`` / ``load_adapter``) to
+        speak with, or None.  The reference tests every frame for EOS on the host (one device sync per
         frame, generator.py:196-199); here the all-zero test runs on the device and the host looks at it once per
         ``eos_check_every`` frames, so the frame graphs are enqueued back to back.  The audio returned is the same: frames
         sampled past the EOS frame are dropped."""
+        ads = self._resolve_adapters([adapter])
         self._run += 1
         self._model.reset_caches()
         max_audio_frames = int(max_audio_length_ms / 80)
@@ -102,7 +134,7 @@ class Generator:
         checked = 0                                   # frames [0, checked) are known not to be EOS
         step = max(1, int(eos_check_every))
         for i in range(max_audio_frames):
-            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk)
+            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads)
             samples.append(sample)
             if len(samples) - checked >= step or i == max_audio_frames - 1:
                 eos = (torch.cat(samples[checked:], 0) == 0).all(dim=1)                 # one host look per chunk
@@ -138,23 +170,26 @@ class Generator:
         return prompt_tokens.unsqueeze(0), prompt_mask.unsqueeze(0), curr_pos
 
     def generate_stream(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
-                        temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4) -> Iterator[torch.Tensor]:
+                        temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4,
+                        adapter: Optional[str] = None) -> Iterator[torch.Tensor]:
         """``generate`` that hands the audio out while it is being made: an iterator of 1-D device tensors of
         ``chunk_frames * 1920`` samples (the last one may be shorter), decoded by the audio tokenizer's stateful
         ``decode_stream()``.  The frames are sampled by the same ``generate_frame`` calls in the same order as ``generate``,
         so under the same torch seed the concatenated chunks equal ``generate``'s audio.  The host looks for EOS once per
         chunk; frames from EOS on are never decoded.  A later ``generate`` / ``generate_batch`` / ``generate_stream`` on this
-        Generator invalidates the stream (its next ``next()`` raises ``RuntimeError``); abandoning it is harmless."""
+        Generator invalidates the stream (its next ``next()`` raises ``RuntimeError``); abandoning it is harmless.
+        ``adapter``: as for ``generate``."""
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
         if not callable(getattr(self._audio_tokenizer, "decode_stream", None)):
             raise TypeError(f"{type(self._audio_tokenizer).__name__} has no decode_stream(): streaming needs a stateful decoder "
                             "(decoding chunks independently would be wrong at the chunk edges)")
+        ads = self._resolve_adapters([adapter])
         self._run += 1
-        return self._stream(self._run, text, speaker, context, max_audio_length_ms, temperature, topk, int(chunk_frames))
+        return self._stream(self._run, text, speaker, context, max_audio_length_ms, temperature, topk, int(chunk_frames), ads)
 
     @torch.inference_mode()
-    def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames):
+    def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames, ads=None):
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later generate / generate_batch / generate_stream call on "
@@ -170,7 +205,7 @@ class Generator:
         pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
         pending = []
         for i in range(max_audio_frames):
-            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk)
+            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads)
             pending.append(sample)
             if len(pending) == chunk_frames or i == max_audio_frames - 1:
                 codes = torch.stack(pending).permute(1, 2, 0).long()                       # [1, K, n]
@@ -189,17 +224,22 @@ class Generator:
     @torch.inference_mode()
     def generate_batch(self, texts: List[str], speakers: List[int], contexts: List[List[Segment]],
                        max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
-                       eos_check_every: int = 8) -> List[torch.Tensor]:
+                       eos_check_every: int = 8, adapters: Optional[List[Optional[str]]] = None) -> List[torch.Tensor]:
         """``generate`` for up to 16 utterances at once (not in the reference, whose loop is single-utterance): the prompts
         (different lengths) are prefilled one by one into their rows of the KV caches, then every decode frame advances all
         rows together - the decode kernels share each weight load between the batch rows, so B utterances cost about as
         much as one.  A row stops contributing at its own EOS frame; the loop ends when every row has one.  Up to 4 rows
         each row's codes are those of a one-utterance run; 5..16 rows go through the MFMA decode products, whose rows are
-        the same bits for any batch size in 5..16 (not those of 1..4).  Live (un-merged) LoRA adapters: at most 4."""
-        self._run += 1
+        the same bits for any batch size in 5..16 (not those of 1..4).  Live (un-merged) LoRA adapters: at most 4.
+        ``adapters``: one bank adapter name or None per utterance (``add_adapter`` / ``load_adapter``), 1..16 rows; with it, a
+        live ``model.lora`` must be absent or merged."""
         B = len(texts)
         if not (1 <= B <= 16 and len(speakers) == B and len(contexts) == B):
             raise ValueError("generate_batch takes 1..16 utterances with one speaker id and one context list each")
+        if adapters is not None and len(adapters) != B:
+            raise ValueError(f"generate_batch: {len(adapters)} adapter names for {B} utterances (one name or None each)")
+        ads = self._resolve_adapters(list(adapters)) if adapters is not None else None
+        self._run += 1
         self._model.reset_caches()
         max_audio_frames = int(max_audio_length_ms / 80)
         K = self._model.args.audio_num_codebooks
@@ -217,7 +257,7 @@ class Generator:
             msks.append(torch.cat(m_, 0).bool().to(self.device))
             if toks[-1].size(0) >= self._model.bb.max_seq_len - max_audio_frames:
                 raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {self._model.bb.max_seq_len - max_audio_frames}")
-        frames = [self._model.engine.generate_first_frames(toks, msks, temperature, topk)]          # [B, K] each
+        frames = [self._model.engine.generate_first_frames(toks, msks, temperature, topk, adapters=ads)]          # [B, K] each
         mask = torch.cat([torch.ones(B, K, dtype=torch.bool), torch.zeros(B, 1, dtype=torch.bool)], 1).unsqueeze(1).to(self.device)
         pad = torch.zeros(B, 1, dtype=torch.long, device=self.device)
         pos = torch.ones(B, 1, dtype=torch.long, device=self.device)       # only "not the prompt" matters: positions live on the device

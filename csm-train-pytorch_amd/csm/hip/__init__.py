@@ -76,6 +76,8 @@ _SIGS = {
     "csm_gemv_bf16": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_gemv_bf16_kext": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _i, _p, _p, _i, _i, _i, _p, _p], _i),
     "csm_lora_project_bf16": ([_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _f, _p], _i),
+    "csm_lora_project_rows_bf16": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _p], _i),
+    "csm_gemv_bf16_kext_rows": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "csm_gemv_t_bf16": ([_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_gemv_bf16_ex": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _i, _p], _i),
     "csm_attn_decode_rope": ([_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),

@@ -448,6 +448,48 @@ def gemv_kext(x, W, y, ext_t, ext_B, residual=None, norm_scale=None, eps=1e-5, s
     return y
 
 
+def lora_project_rows(x, At_tab, t, row_adapter, scale, kx, lda, norm_scale=None, eps=1e-5):
+    """``lora_project`` with one adapter per batch row (a bank of adapters, csm/lora_bank.py): t[b] = scale[a] * x^[b] At[a],
+    a = row_adapter[b] (int32 [B] on the device, -1 = none: a zero row).  ``At_tab`` int64 [A] holds the device addresses of the
+    adapters' At [K, lda] (16-byte aligned), ``scale`` fp32 [A]; B = 1..16.  Each row is the bits of a one-row ``lora_project``
+    with its own At and scale."""
+    B, K = x.shape
+    A = At_tab.numel()
+    assert t.shape[0] == B and t.shape[1] >= kx and x.stride(1) == 1 and t.stride(1) == 1 and x.dtype == t.dtype == BF16
+    assert At_tab.dtype == torch.int64 and At_tab.is_contiguous() and At_tab.is_cuda
+    assert scale.dtype == torch.float32 and scale.numel() == A and scale.is_contiguous() and scale.is_cuda
+    assert row_adapter.dtype == torch.int32 and row_adapter.numel() == B and row_adapter.is_contiguous() and row_adapter.is_cuda
+    check(lib.csm_lora_project_rows_bf16(x.data_ptr(), At_tab.data_ptr(), t.data_ptr(), row_adapter.data_ptr(), scale.data_ptr(), A,
+                                         B, K, int(kx), x.stride(0), int(lda), t.stride(0), _ptr(norm_scale), float(eps), _stream()),
+          "csm_lora_project_rows_bf16")
+    return t
+
+
+def gemv_kext_rows(x, W, y, ext_t, Bx_tab, row_adapter, kx, ldb, residual=None, norm_scale=None, eps=1e-5, swiglu=False,
+                   row_index=None, row_offset=0, bias_tab=None):
+    """``gemv_ex`` with row b extended by its own adapter a = row_adapter[b]: y = epilogue(x^ W^T + ext_t[b] Bx[a]^T + bias[a]).
+    ``Bx_tab`` / ``bias_tab`` int64 [A]: device addresses of each adapter's Bx [N, ldb] (W's row order) and bias [N] (0 = none;
+    ``bias_tab`` None = no adapter has one).  B = 1..16: B <= 4 row b is the bits of a one-row ``gemv_kext`` with adapter a; 5..16
+    a row's bits depend on its own operands only; a row without adapter is the plain ``gemv_ex`` at the same B."""
+    B = y.shape[0]
+    K = x.shape[1]
+    N = W.shape[0]
+    A = Bx_tab.numel()
+    assert W.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W.stride(1) == 1 and y.stride(1) == 1
+    assert row_index is not None or x.shape[0] == B
+    assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
+    assert ext_t.shape[0] == B and ext_t.shape[1] >= kx and ext_t.stride(1) == 1 and ext_t.dtype == BF16
+    assert Bx_tab.dtype == torch.int64 and Bx_tab.is_contiguous() and Bx_tab.is_cuda
+    assert bias_tab is None or (bias_tab.dtype == torch.int64 and bias_tab.numel() == A and bias_tab.is_contiguous() and bias_tab.is_cuda)
+    assert row_adapter.dtype == torch.int32 and row_adapter.numel() == B and row_adapter.is_contiguous() and row_adapter.is_cuda
+    check(lib.csm_gemv_bf16_kext_rows(x.data_ptr(), W.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K, W.stride(0), x.stride(0),
+                                      y.stride(0), int(y.dtype == torch.float32), _ptr(norm_scale), float(eps), int(swiglu),
+                                      _ptr(row_index), int(row_offset), ext_t.data_ptr(), Bx_tab.data_ptr(), _ptr(bias_tab),
+                                      row_adapter.data_ptr(), A, int(kx), ext_t.stride(0), int(ldb), _stream()),
+          "csm_gemv_bf16_kext_rows")
+    return y
+
+
 def attn_decode_rope(qkv, kcache, vcache, out, pos_i32, table, H, KV, HD, pos_host=None):
     """rope(q, new k) + append(new k, v) + one-position attention against the caches, one launch.  ``pos_host``: the position all
     rows share, as a host integer (the depth decoder's step; HD = 128, H = 4 KV, S_max <= 32): the launch that issues every load

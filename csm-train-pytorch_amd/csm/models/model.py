@@ -427,8 +427,9 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def generate_frame(self, tokens: torch.Tensor, tokens_mask: torch.Tensor, input_pos: torch.Tensor, temperature: float,
-                       topk: int, noise: Optional[List[torch.Tensor]] = None) -> torch.Tensor:
+                       topk: int, noise: Optional[List[torch.Tensor]] = None, adapters=None) -> torch.Tensor:
         """Reference model.py:140-195: one frame of K codes, [B, K] int32.  ``noise`` (K tensors [B, V_a] of Exp(1)
-        draws) pins the sampler for parity tests."""
+        draws) pins the sampler for parity tests.  ``adapters``: a LoRAState or None per batch row (csm/lora_bank.py), read
+        on a generation's first call."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
-        return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise)
+        return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise, adapters)

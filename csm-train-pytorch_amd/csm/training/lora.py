@@ -163,7 +163,7 @@ class LoRAState:
     """All adapters of a model in one bf16 arena (+ gradient arena)."""
 
     def __init__(self, model, r: int, alpha: float, dropout: float, target_modules: List[str],
-                 target_layers: Optional[List[int]], use_bias: bool, seed: int = 0):
+                 target_layers: Optional[List[int]], use_bias: bool, seed: int = 0, grad: bool = True):
         if not 0.0 <= float(dropout) < 1.0:
             raise ValueError("lora_dropout must be in [0, 1)")
         if r < 1:
@@ -202,7 +202,8 @@ class LoRAState:
         total = (total + 7) // 8 * 8
         dev = model.device
         self.arena = torch.zeros(total, dtype=BF16, device=dev)
-        self.grad_arena = torch.zeros(total, dtype=BF16, device=dev)
+        # grad=False: a generation-only state (an adapter bank entry, csm/lora_bank.py) - no gradient arena, the gradient views are None
+        self.grad_arena = torch.zeros(total, dtype=BF16, device=dev) if grad else None
         self.adapters: Dict[tuple, LoRAAdapter] = OrderedDict()
         self.groups: Dict[tuple, LoRAGroup] = OrderedDict()
         g = torch.Generator(device=dev)
@@ -211,7 +212,8 @@ class LoRAState:
 
         def take(n, shape):
             nonlocal off
-            w, gr = self.arena[off:off + n].view(shape), self.grad_arena[off:off + n].view(shape)
+            w = self.arena[off:off + n].view(shape)
+            gr = self.grad_arena[off:off + n].view(shape) if self.grad_arena is not None else None
             off += n
             return w, gr
 
@@ -229,7 +231,8 @@ class LoRAState:
             Bx_all, gBx_all = take(L * rows * kx, (L, rows, kx))
             grps = []
             for li, (_, i, _, _, _, _) in enumerate(entries):
-                grp = LoRAGroup(self, f"{prefix}.layers.{i}.{gname}", At_all[li], Bx_all[li], gAt_all[li], gBx_all[li])
+                grp = LoRAGroup(self, f"{prefix}.layers.{i}.{gname}", At_all[li], Bx_all[li],
+                                gAt_all[li] if gAt_all is not None else None, gBx_all[li] if gBx_all is not None else None)
                 built[(prefix, i, gname)] = (grp, present, in_f, rows)
                 grps.append(grp)
             self.stacks.append((At_all, Bx_all, grps))
@@ -244,8 +247,9 @@ class LoRAState:
                     bias, gbias = take(out_f, (out_f,))
                 sub = "attn" if mod in ATTN else "mlp"
                 At[:, c0:c0 + r].copy_((torch.randn(r, in_f, generator=g, device=dev) / math.sqrt(in_f)).to(BF16).t())
-                ad = LoRAAdapter(f"{prefix}.layers.{i}.{sub}.{mod}", At[:, c0:c0 + rp], Bx[sl, c0:c0 + rp], gAt[:, c0:c0 + rp],
-                                 gBx[sl, c0:c0 + rp], self.scaling, bias, gbias, dropout, seed * 1000003 + len(self.adapters), self)
+                ad = LoRAAdapter(f"{prefix}.layers.{i}.{sub}.{mod}", At[:, c0:c0 + rp], Bx[sl, c0:c0 + rp],
+                                 gAt[:, c0:c0 + rp] if gAt is not None else None, gBx[sl, c0:c0 + rp] if gBx is not None else None,
+                                 self.scaling, bias, gbias, dropout, seed * 1000003 + len(self.adapters), self)
                 covered[sl, c0:c0 + rp] = 1
                 self.adapters[(prefix, i, mod)] = ad
                 grp.adapters[mod] = ad

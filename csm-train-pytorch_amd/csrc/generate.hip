@@ -335,6 +335,30 @@ struct GemvExt {
     int kx, ldt, ldb;
 };
 __device__ __forceinline__ const GemvExt& ext_arg(const GemvExt& e) { return e; }
+// The per-row ("gathered") form (csm_gemv_bf16_kext_rows: a bank of adapters, one per batch row): row b takes its extension from
+// adapter a = row_adapter[b] - Bx[a], bias[a] (the table itself or an entry may be NULL) - with the same operations in the same
+// order as GemvExt, so row b is bit-identical to a one-row GemvExt launch with adapter a.  a = -1 (or out of range): no extension
+// at all, the plain product's bits.  t is [B][ldt] as for GemvExt (csm_lora_project_rows_bf16 leaves each row's own adapter's t).
+struct GemvExtRows {
+    const bf16_t* t;                  // [B][ldt]
+    const bf16_t* const* Bx;          // [nad] -> [N][ldb]
+    const bf16_t* const* bias;        // [nad] -> [N] or NULL; NULL: no adapter has a bias
+    const int* row_adapter;           // [B], -1 = none
+    int nad, kx, ldt, ldb;
+};
+__device__ __forceinline__ const GemvExtRows& ext_rows_arg(const GemvExtRows& e) { return e; }
+// 0: the plain products (empty pack), 1: GemvExt, 2: GemvExtRows
+template <typename... E> struct ExtKind { static constexpr int v = 0; };
+template <> struct ExtKind<GemvExt> { static constexpr int v = 1; };
+template <> struct ExtKind<GemvExtRows> { static constexpr int v = 2; };
+__device__ __forceinline__ int ext_row_adapter(const GemvExtRows& e, int b) {      // (wave-uniform) the row's adapter or -1
+    const int a = e.row_adapter[b];
+    return a < e.nad ? a : -1;
+}
+__device__ __forceinline__ float ext_row_bias(const GemvExtRows& e, int a, int n) {
+    const bf16_t* bb = e.bias ? e.bias[a] : nullptr;
+    return bb ? bf2f(bb[n]) : 0.f;
+}
 __device__ __forceinline__ U4 ext_load(const bf16_t* row, int lane, int kx) {
     U4 z = {0u, 0u, 0u, 0u};
     return lane < (kx >> 3) ? *reinterpret_cast<const U4*>(row + lane * 8) : z;
@@ -360,7 +384,8 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
                                                    const bf16_t* __restrict__ R, int N, int K, int ldw, int ldx, int ldy,
                                                    const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
                                                    int row_offset, Ext... ext) {
-    constexpr bool EXT = sizeof...(Ext) > 0;
+    constexpr int EK = ExtKind<Ext...>::v;
+    constexpr bool EXT = EK == 1;
     extern __shared__ __attribute__((aligned(16))) char smem_x[];
     bf16_t* xs = reinterpret_cast<bf16_t*>(smem_x);            // [NB][K]
     __shared__ float rs[4];
@@ -435,13 +460,36 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
                 if (e.bias) bias[r] = bf2f(e.bias[n * RW + r]);
             }
         }
+        float rbias[RW][NB];                                  // (GemvExtRows: each row's own adapter)
+        bool ron[NB];
+        if constexpr (EK == 2) {
+            __builtin_amdgcn_sched_barrier(0);
+            const GemvExtRows& e = ext_rows_arg(ext...);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const int a = ext_row_adapter(e, b);
+                ron[b] = a >= 0;
+#pragma unroll
+                for (int r = 0; r < RW; ++r) rbias[r][b] = 0.f;
+                if (a >= 0) {
+                    const U4 tb = ext_load(e.t + (size_t)b * e.ldt, lane, e.kx);
+#pragma unroll
+                    for (int r = 0; r < RW; ++r) {
+                        acc[r][b] = ext_fma(acc[r][b], ext_load(e.Bx[a] + (size_t)(n * RW + r) * e.ldb, lane, e.kx), tb);
+                        rbias[r][b] = ext_row_bias(e, a, n * RW + r);
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             float v = wave_sum(acc[0][b]);
             if constexpr (EXT) v += bias[0];
+            if constexpr (EK == 2) { if (ron[b]) v += rbias[0][b]; }
             if constexpr (SWIGLU) {
                 float us = wave_sum(acc[1][b]);
                 if constexpr (EXT) us += bias[1];
+                if constexpr (EK == 2) { if (ron[b]) us += rbias[1][b]; }
                 const float g = bf2f(f2bf(v)), u = bf2f(f2bf(us));
                 v = silu(g) * u;
             }
@@ -472,11 +520,12 @@ __global__ __launch_bounds__(256) void gemv_reg_kernel(const bf16_t* __restrict_
                                                        const bf16_t* __restrict__ R, int N, int ldw, int ldx, int ldy,
                                                        const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
                                                        int row_offset, Ext... ext) {
-    constexpr bool EXT = sizeof...(Ext) > 0;
+    constexpr int EK = ExtKind<Ext...>::v;
+    constexpr bool EXT = EK == 1;
     constexpr int K = 512 * KCH;
     constexpr int RW = SWIGLU ? 2 : 1;
     const int lane = threadIdx.x & 63;
-    const int n0 = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW;
+    const int n0 =(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * RPW;
     const int NO = N / RW;
     if (n0 >= NO) return;
     STAMP_DECL;
@@ -569,6 +618,23 @@ __global__ __launch_bounds__(256) void gemv_reg_kernel(const bf16_t* __restrict_
                 if (e.bias) bias[o][r] = bf2f(e.bias[min(n0 + o, NO - 1) * RW + r]);
             }
     }
+    bool ron = false;                                         // (GemvExtRows: the one row's own adapter)
+    if constexpr (EK == 2) {
+        __builtin_amdgcn_sched_barrier(0);
+        const GemvExtRows& e = ext_rows_arg(ext...);
+        const int a = ext_row_adapter(e, 0);
+        ron = a >= 0;
+        if (ron) {
+            const U4 et = ext_load(e.t, lane, e.kx);
+#pragma unroll
+            for (int o = 0; o < RPW; ++o)
+#pragma unroll
+                for (int r = 0; r < RW; ++r) {
+                    acc[o][r] = ext_fma(acc[o][r], ext_load(e.Bx[a] + (size_t)(min(n0 + o, NO - 1) * RW + r) * e.ldb, lane, e.kx), et);
+                    bias[o][r] = ext_row_bias(e, a, min(n0 + o, NO - 1) * RW + r);
+                }
+        }
+    }
 #pragma unroll
     for (int o = 0; o < RPW; ++o) {
         float v;
@@ -580,11 +646,13 @@ __global__ __launch_bounds__(256) void gemv_reg_kernel(const bf16_t* __restrict_
             float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
             float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
             if constexpr (EXT) { gs += bias[o][0]; us += bias[o][1]; }
+            if constexpr (EK == 2) { if (ron) { gs += bias[o][0]; us += bias[o][1]; } }
             const float g = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
             v = silu(g) * u;
         } else {
             v = wave_sum(acc[o][0]);
             if constexpr (EXT) v += bias[o][0];
+            if constexpr (EK == 2) { if (ron) v += bias[o][0]; }
         }
         if (lane == 0 && n0 + o < NO) {
             if (R) v += bf2f(R[n0 + o]);
@@ -613,7 +681,8 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
                                                         const bf16_t* __restrict__ R, int N, int ldw, int ldx, int ldy,
                                                         const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
                                                         int row_offset, Ext... ext) {
-    constexpr bool EXT = sizeof...(Ext) > 0;
+    constexpr int EK = ExtKind<Ext...>::v;
+    constexpr bool EXT = EK == 1;
     constexpr int K = 512 * KCH;
     constexpr int RW = SWIGLU ? 2 : 1;
     constexpr int NP = (NB + 1) / 2;                                        // row pairs (the last one half empty for odd NB)
@@ -725,21 +794,41 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
         float a0 = (b & 1) ? acc[0][b >> 1].y : acc[0][b >> 1].x;
         U4 et;
         if constexpr (EXT) { et = ext_load(ext_arg(ext...).t + (size_t)b * ext_arg(ext...).ldt, lane, ext_arg(ext...).kx); a0 = ext_fma(a0, eb[0], et); }
+        // GemvExtRows: row b's own adapter - its Bx chunk and bias are loaded here, then the same ext_fma as GemvExt's
+        bool ron = false;
+        float rb[RW];
+        if constexpr (EK == 2) {
+            const GemvExtRows& e = ext_rows_arg(ext...);
+            const int a = ext_row_adapter(e, b);
+            ron = a >= 0;
+            if (ron) {
+                et = ext_load(e.t + (size_t)b * e.ldt, lane, e.kx);
+#pragma unroll
+                for (int r = 0; r < RW; ++r) {
+                    eb[r] = ext_load(e.Bx[a] + (size_t)((live ? n : NO - 1) * RW + r) * e.ldb, lane, e.kx);
+                    rb[r] = ext_row_bias(e, a, (live ? n : NO - 1) * RW + r);
+                }
+                a0 = ext_fma(a0, eb[0], et);
+            }
+        }
         float v;
         if constexpr (SWIGLU) {
             float a1 = (b & 1) ? acc[1][b >> 1].y : acc[1][b >> 1].x;
             if constexpr (EXT) a1 = ext_fma(a1, eb[1], et);
+            if constexpr (EK == 2) { if (ron) a1 = ext_fma(a1, eb[1], et); }
             auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
             float t = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
             t += lane_xor<16>(t); t += lane_xor<8>(t); t += lane_xor<4>(t); t += lane_xor<2>(t); t += lane_xor<1>(t);
             float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
             float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
             if constexpr (EXT) { gs += bias[0]; us += bias[1]; }
+            if constexpr (EK == 2) { if (ron) { gs += rb[0]; us += rb[1]; } }
             const float g = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
             v = silu(g) * u;
         } else {
             v = wave_sum(a0);
             if constexpr (EXT) v += bias[0];
+            if constexpr (EK == 2) { if (ron) v += rb[0]; }
         }
         if (lane == 0 && live) {
             if (R) v += bf2f(R[(size_t)b * ldy + n]);
@@ -765,11 +854,22 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
 // batch row's operands in an order fixed by K, so a row's result is the same bits for any B in 5..16, any position of the row in
 // the batch and any contents of the other rows (tests/test_generate_wide_batch_gpu.py).  It is not bit-equal to the B <= 4
 // kernels, which sum in another order.
-template <int SEG, typename OutT, bool SWIGLU, bool NT>
+// Trailing pack (empty: the plain product, or one GemvExtRows): the epilogue thread of output (n, b) adds row b's own adapter's
+// extension sum_j t[b][j] Bx[a_b][n][j] to the wave-ordered sum, one fmaf per j in ascending j (then the adapter's bias), before
+// the rounding / SwiGLU / residual epilogue.  It reads only row b's operands, so a row keeps its bits for any B in 5..16, any
+// position and any batch-mates and their adapters; a row without adapter takes no extension: the plain product's bits.
+__device__ __forceinline__ float ext_dot(float v, const bf16_t* __restrict__ bx, const bf16_t* __restrict__ t, int kx) {
+    for (int j = 0; j < kx; j += 8)
+        v = ext_fma(v, *reinterpret_cast<const U4*>(bx + j), *reinterpret_cast<const U4*>(t + j));
+    return v;
+}
+template <int SEG, typename OutT, bool SWIGLU, bool NT, typename... Ext>
 __global__ __launch_bounds__(512) void gemv_mfma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, OutT* __restrict__ y,
                                                         const bf16_t* __restrict__ R, int B, int N, int K, int ldw, int ldx, int ldy,
                                                         const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
-                                                        int row_offset) {
+                                                        int row_offset, Ext... ext) {
+    constexpr int EK = ExtKind<Ext...>::v;
+    static_assert(EK != 1, "gemv_mfma_kernel takes the per-row extension only");
     constexpr int NW = 8;
     __shared__ float rs[16];
     __shared__ float part[NW][16][17];                        // [wave][weight row of the tile][batch row] (+1: no bank conflicts)
@@ -864,6 +964,16 @@ __global__ __launch_bounds__(512) void gemv_mfma_kernel(const bf16_t* __restrict
             float gs = part[0][2 * i][b], us = part[0][2 * i + 1][b];
 #pragma unroll
             for (int w = 1; w < NW; ++w) { gs += part[w][2 * i][b]; us += part[w][2 * i + 1][b]; }
+            if constexpr (EK == 2) {
+                const GemvExtRows& e = ext_rows_arg(ext...);
+                const int a = ext_row_adapter(e, b);
+                if (a >= 0) {
+                    gs = ext_dot(gs, e.Bx[a] + (size_t)(n0 + 2 * i) * e.ldb, e.t + (size_t)b * e.ldt, e.kx);
+                    us = ext_dot(us, e.Bx[a] + (size_t)(n0 + 2 * i + 1) * e.ldb, e.t + (size_t)b * e.ldt, e.kx);
+                    gs += ext_row_bias(e, a, n0 + 2 * i);
+                    us += ext_row_bias(e, a, n0 + 2 * i + 1);
+                }
+            }
             const float gg = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
             float v = silu(gg) * u;
             const int n = (n0 >> 1) + i;
@@ -877,6 +987,11 @@ __global__ __launch_bounds__(512) void gemv_mfma_kernel(const bf16_t* __restrict
             float v = part[0][rr][b];
 #pragma unroll
             for (int w = 1; w < NW; ++w) v += part[w][rr][b];
+            if constexpr (EK == 2) {
+                const GemvExtRows& e = ext_rows_arg(ext...);
+                const int a = ext_row_adapter(e, b);
+                if (a >= 0) v = ext_dot(v, e.Bx[a] + (size_t)n * e.ldb, e.t + (size_t)b * e.ldt, e.kx) + ext_row_bias(e, a, n);
+            }
             if (R) v += bf2f(R[(size_t)b * ldy + n]);
             if constexpr (sizeof(OutT) == 2) y[(size_t)b * ldy + n] = f2bf(v);
             else y[(size_t)b * ldy + n] = v;
@@ -1590,6 +1705,83 @@ __global__ __launch_bounds__(512) void lora_project_kernel(const bf16_t* __restr
     }
 }
 
+// lora_project_kernel with one adapter per batch row (csm_lora_project_rows_bf16): row b reads At[a_b] and scales by scale[a_b],
+// a_b = row_adapter[b]; -1 (or out of range) writes exact zeros.  Rows go in groups of NB <= 4 per workgroup on the grid's second
+// axis.  A row's operations and their order are lora_project_kernel's for that row (thread-strided k, wave_sum, the waves' partials
+// in fixed order - none of which depends on NB or on the other rows), so each row is bit-identical to a one-row
+// csm_lora_project_bf16 launch with its own At and scale.
+template <int NB>
+__global__ __launch_bounds__(512) void lora_project_rows_kernel(const bf16_t* __restrict__ x, const bf16_t* const* __restrict__ At_tab,
+                                                                bf16_t* __restrict__ t, const int* __restrict__ row_adapter,
+                                                                const float* __restrict__ scale_tab, int nad, int B, int K, int ldx,
+                                                                int lda, int ldt, const bf16_t* __restrict__ norm_w, float eps) {
+    __shared__ float rs[4];
+    __shared__ float part[8][NB][8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c0 = blockIdx.x * 8, b0 = blockIdx.y * NB;
+    int ad[NB];
+    const bf16_t* At[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int a = b0 + b < B ? row_adapter[b0 + b] : -1;
+        ad[b] = a < nad ? a : -1;
+        At[b] = ad[b] >= 0 ? At_tab[ad[b]] : nullptr;
+    }
+    if (norm_w) {
+        if (wave < NB && ad[wave] >= 0) {
+            float ss = 0.f;
+            for (int c = lane; c < (K >> 3); c += 64) {
+                float f[8];
+                unpack8(*reinterpret_cast<const U4*>(x + (size_t)(b0 + wave) * ldx + c * 8), f);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) ss += f[j] * f[j];
+            }
+            ss = wave_sum(ss);
+            if (lane == 0) rs[wave] = rsqrtf(ss / (float)K + eps);
+        }
+        __syncthreads();
+    }
+    float r[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) r[b] = (norm_w && ad[b] >= 0) ? rs[b] : 1.f;
+    float acc[NB][8];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[b][j] = 0.f;
+#pragma unroll 4
+    for (int k = threadIdx.x; k < K; k += 512) {
+        const float w = norm_w ? bf2f(norm_w[k]) : 1.f;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            if (ad[b] < 0) continue;                             // (workgroup-uniform)
+            float a[8];
+            unpack8(*reinterpret_cast<const U4*>(At[b] + (size_t)k * lda + c0), a);
+            float xv = bf2f(x[(size_t)(b0 + b) * ldx + k]);
+            if (norm_w) xv = bf2f(f2bf(xv * r[b] * w));
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[b][j] += xv * a[j];
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float v = wave_sum(acc[b][j]);
+            if (lane == 0) part[wave][b][j] = v;
+        }
+    __syncthreads();
+    if ((int)threadIdx.x < NB * 8) {
+        const int b = threadIdx.x >> 3, j = threadIdx.x & 7;
+        if (b0 + b < B) {
+            float v = 0.f;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) v += part[w][b][j];
+            t[(size_t)(b0 + b) * ldt + c0 + j] = ad[b] >= 0 ? f2bf(scale_tab[ad[b]] * v) : f2bf(0.f);
+        }
+    }
+}
+
 }  // namespace
 
 #ifdef CSM_DECODE_STAMPS
@@ -1617,14 +1809,15 @@ extern "C" int csm_set_decode_tuning(int key, int value) {
 }
 // B = 5..16 (or 2..4 under g_gemv_mfma_small): gemv_mfma_kernel, one workgroup per 16 weight rows; SEG = 64-k steps per wave
 // and segment, sized so that K <= 2048 runs as one segment (K = 8192: two of eight steps)
+template <typename... Ext>
 static int gemv_mfma_launch(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx,
                             int ldy, int out_f32, const void* norm_w, float eps, int swiglu, const int* row_index, int row_offset,
-                            hipStream_t stream) {
+                            hipStream_t stream, Ext... ext) {
     CSM_REQUIRE((K & 31) == 0, "csm_gemv_bf16: B=%d needs K %% 32 == 0 (K=%d)", B, K);
     const int grid = (N + 15) / 16;
     const int spw = ((K + 63) / 64 + 7) / 8;                  // 64-k steps per wave
     const bool nt = g_gemv_nt && (K == 2048 || (K == 8192 && N == 2048));
-#define LM(SEG, T, SW, NT_) hipLaunchKernelGGL((gemv_mfma_kernel<SEG, T, SW, NT_>), dim3(grid), dim3(512), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, B, N, K, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset)
+#define LM(SEG, T, SW, NT_) hipLaunchKernelGGL((gemv_mfma_kernel<SEG, T, SW, NT_, Ext...>), dim3(grid), dim3(512), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, B, N, K, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset, ext...)
 #define LMS(T, SW, NT_) do { if (spw <= 1) LM(1, T, SW, NT_); else if (spw <= 2) LM(2, T, SW, NT_); else if (spw <= 4) LM(4, T, SW, NT_); else LM(8, T, SW, NT_); } while (0)
     if (swiglu) { if (nt) LMS(bf16_t, true, true); else LMS(bf16_t, true, false); }
     else if (out_f32) { if (nt) LMS(float, false, true); else LMS(float, false, false); }
@@ -1642,9 +1835,10 @@ static int gemv_launch(const void* x, const void* W, void* y, const void* residu
     CSM_REQUIRE(x && W && y && B >= 1 && B <= 16 && N > 0 && K > 0 && (K & 7) == 0 && (ldw & 7) == 0 && (ldx & 7) == 0,
                 "csm_gemv_bf16: bad arguments (B=%d N=%d K=%d: needs 1 <= B <= 16)", B, N, K);
     CSM_REQUIRE(!swiglu || ((N & 1) == 0 && !out_f32), "csm_gemv_bf16_ex: the SwiGLU form needs an even N and bf16 output");
-    if constexpr (sizeof...(Ext) == 0) {
+    if constexpr (ExtKind<Ext...>::v != 1) {             // (the plain products and the per-row extension dispatch alike)
         if (B > 4 || (B >= 2 && g_gemv_mfma_small && (K & 31) == 0))
-            return gemv_mfma_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_w, eps, swiglu, row_index, row_offset, stream);
+            return gemv_mfma_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_w, eps, swiglu, row_index, row_offset, stream,
+                                    ext...);
     } else {
         CSM_REQUIRE(B <= 4, "csm_gemv_bf16_kext: B=%d: the K-extension (live LoRA adapters) takes at most 4 batch rows", B);
     }
@@ -1729,6 +1923,39 @@ extern "C" int csm_gemv_bf16_kext(const void* x, const void* W, void* y, const v
     e.t = (const bf16_t*)ext_t; e.Bx = (const bf16_t*)ext_B; e.bias = (const bf16_t*)bias;
     e.kx = kx; e.ldt = ld_ext_t; e.ldb = ld_ext_B;
     return gemv_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_scale, eps, swiglu, row_index, row_offset, stream, e);
+}
+
+// csm_gemv_bf16_kext with one adapter per batch row (GemvExtRows; a bank of adapters that share kx, ldb): B = 1..16.
+extern "C" int csm_gemv_bf16_kext_rows(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw,
+                                       int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu,
+                                       const int* row_index, int row_offset, const void* ext_t, const void* const* ext_B,
+                                       const void* const* bias, const int* row_adapter, int n_adapters, int kx, int ld_ext_t,
+                                       int ld_ext_B, hipStream_t stream) {
+    CSM_REQUIRE(B >= 1 && B <= 16, "csm_gemv_bf16_kext_rows: B=%d: the per-row K-extension takes 1 to 16 batch rows", B);
+    CSM_REQUIRE(ext_t && ext_B && row_adapter && n_adapters >= 1 && kx > 0 && kx <= 512 && (kx & 7) == 0 && ld_ext_t >= kx &&
+                ld_ext_B >= kx && (ld_ext_t & 7) == 0 && (ld_ext_B & 7) == 0 && ((uintptr_t)ext_t & 15) == 0,
+                "csm_gemv_bf16_kext_rows: bad extension (adapters=%d kx=%d ld_t=%d ld_B=%d: needs kx <= 512, multiples of 8, "
+                "16-byte aligned rows)", n_adapters, kx, ld_ext_t, ld_ext_B);
+    GemvExtRows e;
+    e.t = (const bf16_t*)ext_t; e.Bx = (const bf16_t* const*)ext_B; e.bias = (const bf16_t* const*)bias;
+    e.row_adapter = row_adapter; e.nad = n_adapters; e.kx = kx; e.ldt = ld_ext_t; e.ldb = ld_ext_B;
+    return gemv_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_scale, eps, swiglu, row_index, row_offset, stream, e);
+}
+
+extern "C" int csm_lora_project_rows_bf16(const void* x, const void* const* At, void* t, const int* row_adapter, const float* scale,
+                                          int n_adapters, int B, int K, int kx, int ldx, int lda, int ldt, const void* norm_scale,
+                                          float eps, hipStream_t stream) {
+    CSM_REQUIRE(B >= 1 && B <= 16, "csm_lora_project_rows_bf16: B=%d: takes 1 to 16 batch rows", B);
+    CSM_REQUIRE(x && At && t && row_adapter && scale && n_adapters >= 1 && K > 0 && (K & 7) == 0 && kx > 0 && (kx & 7) == 0 &&
+                lda >= kx && ldt >= kx && (lda & 7) == 0 && (!norm_scale || ((ldx & 7) == 0 && ((uintptr_t)x & 15) == 0)),
+                "csm_lora_project_rows_bf16: bad arguments (B=%d K=%d kx=%d lda=%d ldt=%d adapters=%d)", B, K, kx, lda, ldt, n_adapters);
+    const int nb = B < 4 ? B : 4;
+    const dim3 grid(kx / 8, (B + nb - 1) / nb);
+#define L(NB) hipLaunchKernelGGL((lora_project_rows_kernel<NB>), grid, dim3(512), 0, stream, (const bf16_t*)x, (const bf16_t* const*)At, (bf16_t*)t, row_adapter, scale, n_adapters, B, K, ldx, lda, ldt, (const bf16_t*)norm_scale, eps)
+    if (nb == 1) L(1); else if (nb == 2) L(2); else if (nb == 3) L(3); else L(4);
+#undef L
+    CSM_CHECK_LAUNCH("csm_lora_project_rows_bf16");
+    return 0;
 }
 
 extern "C" int csm_lora_project_bf16(const void* x, const void* At, void* t, int B, int K, int kx, int ldx, int lda, int ldt,

@@ -242,6 +242,23 @@ int csm_gemv_bf16_kext(const void* x, const void* W, void* y, const void* residu
                        int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index, int row_offset,
                        const void* ext_t, const void* ext_B, int kx, int ld_ext_t, int ld_ext_B, const void* bias,
                        csm_stream_t stream);
+/* Per-row LoRA adapters at decode time (since ABI 3, additive): a bank of n_adapters adapters that share kx and the strides; batch
+ * row b uses adapter row_adapter[b] (int32 [B] on the device; -1 = none).  At / ext_B / bias are DEVICE arrays of n_adapters
+ * pointers (each 16-byte aligned; a bias entry, or the whole bias table, may be NULL), scale fp32 [n_adapters] on the device.
+ * B = 1..16.
+ * csm_lora_project_rows_bf16: t[b] = scale[a] * x^[b] . At[a], a = row_adapter[b]; each row bit-identical to a one-row
+ * csm_lora_project_bf16 launch with that row's At and scale; rows without adapter get zeros. */
+int csm_lora_project_rows_bf16(const void* x, const void* const* At, void* t, const int* row_adapter, const float* scale,
+                               int n_adapters, int B, int K, int kx, int ldx, int lda, int ldt, const void* norm_scale, float eps,
+                               csm_stream_t stream);
+/* csm_gemv_bf16_kext_rows: csm_gemv_bf16_ex with row b extended by its own adapter a = row_adapter[b]: sum_j ext_t[b][j]
+ * ext_B[a][n][j] (+ bias[a][n]).  B <= 4: row b bit-identical to a one-row csm_gemv_bf16_kext with adapter a.  B = 5..16: a row's
+ * bits depend only on its own operands (any B in 5..16, any position, any batch-mates).  A row without adapter is bit-identical to
+ * csm_gemv_bf16_ex at the same B. */
+int csm_gemv_bf16_kext_rows(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx,
+                            int ldy, int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index, int row_offset,
+                            const void* ext_t, const void* const* ext_B, const void* const* bias, const int* row_adapter,
+                            int n_adapters, int kx, int ld_ext_t, int ld_ext_B, csm_stream_t stream);
 /* y[b][n] = sum_k x[b][k] W[k][n]  (K-major weights: audio_head[i] = [decoder_dim][vocab]) */
 int csm_gemv_t_bf16(const void* x, const void* W, void* y, int B, int N, int K, int ldw, int ldx, int ldy, int out_f32,
                     csm_stream_t stream);

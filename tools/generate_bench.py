@@ -6,7 +6,9 @@ layout (GEN_CODEC=rvq swaps in the quantiser-only stand-in when transformers is 
 all): decode frames/s with live LoRA adapters against the same adapters merged, alternated in one process.  GEN_STREAM=1:
 generate_stream() with chunk_frames 1, 2 and 4 against generate() on the same setting, alternated in one process: time from
 the call to the first chunk on the host, total wall time and frames/s.  GEN_BATCH_SWEEP=1: generate_batch() at 1, 4, 8 and 16
-utterances from one process, one line each (aggregate frames/s, seconds per frame)."""
+utterances from one process, one line each (aggregate frames/s, seconds per frame).  GEN_LORA_BANK=q_proj,v_proj (or all): decode
+frames/s with a different LoRA adapter per utterance (16 adapters, some rows without) against the same batch without adapters
+and against the same utterances one at a time with their adapter live as model.lora, alternated in one process."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -160,6 +162,77 @@ def lora_main(mods):
           f"{best['live'] / best['merged']:.3f}x")
 
 
+def decode_fps_batch(model, B, adapters=None, frames=50, prompt=40):
+    """``decode_fps`` for B utterances decoded together (aggregate frames/s); ``adapters``: a LoRAState or None per row."""
+    dev = model.device
+    K = model.args.audio_num_codebooks
+    model.setup_caches(B)
+    model.reset_caches()
+    g = torch.Generator().manual_seed(0)
+    tok = torch.zeros(B, prompt, K + 1, dtype=torch.long)
+    tok[:, :, K] = torch.randint(0, model.args.text_vocab_size, (B, prompt), generator=g)
+    msk = torch.zeros(B, prompt, K + 1, dtype=torch.bool)
+    msk[:, :, K] = True
+    amask = torch.cat([torch.ones(B, K, dtype=torch.bool), torch.zeros(B, 1, dtype=torch.bool)], 1).unsqueeze(1).to(dev)
+    pad = torch.zeros(B, 1, dtype=torch.long, device=dev)
+    pos = torch.arange(prompt).unsqueeze(0).repeat(B, 1).to(dev)
+    f = model.generate_frame(tok.to(dev), msk.to(dev), pos, 0.9, 50, adapters=adapters)
+    for _ in range(3):                                                       # eager frame, capture, first replay
+        pos = pos[:, -1:] + 1
+        f = model.generate_frame(torch.cat([f.long(), pad], 1).unsqueeze(1), amask, pos, 0.9, 50)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    for _ in range(frames):
+        pos = pos[:, -1:] + 1
+        f = model.generate_frame(torch.cat([f.long(), pad], 1).unsqueeze(1), amask, pos, 0.9, 50)
+    torch.cuda.synchronize()
+    return B * frames / (time.time() - t0)
+
+
+def lora_bank_main(mods):
+    """GEN_LORA_BANK=q_proj,v_proj (or all): CSM-1B random init, 16 random r = 8 adapters with non-zero B.  For B = 4, 8, 16
+    (GEN_BANK_SIZES): (a) one adapter per utterance - distinct adapters, every fourth row without; (b) the same batch without
+    adapters; (c) the utterances one at a time, each with its adapter live as model.lora (today's only option; its aggregate
+    frames/s is the one-utterance rate whatever B).  Alternated in one process, GEN_ROUNDS rounds, best of each."""
+    from csm.training.lora import LoRAState
+    dev = "cuda:0"
+    mods = ["q_proj", "k_proj", "v_proj", "output_proj", "w1", "w2", "w3"] if mods == "all" else mods.split(",")
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    bank = []
+    for s in range(16):
+        st = LoRAState(model, 8, 16.0, 0.0, mods, None, False, seed=s, grad=False)
+        with torch.no_grad():
+            gb = torch.Generator(device=dev).manual_seed(100 + s)
+            for ad in st.adapters.values():
+                ad.B[:, :8].copy_((torch.randn(ad.B.shape[0], 8, generator=gb, device=dev) * 0.02).to(torch.bfloat16))
+        bank.append(st)
+    frames = int(os.environ.get("GEN_FRAMES", 50))
+    sizes = [int(v) for v in os.environ.get("GEN_BANK_SIZES", "4,8,16").split(",")]
+    rounds = int(os.environ.get("GEN_ROUNDS", 2))
+    res = {}
+    for _ in range(rounds):
+        for B in sizes:
+            rows = [None if b % 4 == 3 else bank[b] for b in range(B)]
+            res.setdefault(("none", B), []).append(decode_fps_batch(model, B, None, frames))
+            res.setdefault(("bank", B), []).append(decode_fps_batch(model, B, rows, frames))
+        one = []
+        for s in (0, 1):                                                     # (c): live adapter, one utterance
+            model.lora = bank[s]
+            try:
+                one.append(decode_fps(model, frames))
+            finally:
+                model.lora = None
+        res.setdefault(("live1", 1), []).append(max(one))
+    live1 = max(res[("live1", 1)])
+    print(f"LoRA bank {','.join(mods)} r=8, 16 adapters: one utterance at a time with its adapter live (c): "
+          f"{[round(x, 1) for x in res[('live1', 1)]]} -> best {live1:.1f} frames/s", flush=True)
+    for B in sizes:
+        a, b = max(res[("bank", B)]), max(res[("none", B)])
+        print(f"GEN_LORA_BANK B={B:2d}: (a) per-row adapters {[round(x, 1) for x in res[('bank', B)]]} (b) no adapters "
+              f"{[round(x, 1) for x in res[('none', B)]]} frames/s aggregate -> best (a) {a:.1f} / (b) {b:.1f} = {a / b:.3f}x; "
+              f"(a) / (c) = {a / live1:.2f}x", flush=True)
+
+
 def stream_main():
     """GEN_STREAM=1: for each chunk size, generate() and generate_stream() alternate (GEN_ROUNDS rounds, same seed, so the
     same frames); the first chunk counts as arrived when its samples are on the host."""
@@ -234,6 +307,8 @@ def sweep_main():
 def main():
     if os.environ.get("GEN_BATCH_SWEEP") == "1":
         return sweep_main()
+    if os.environ.get("GEN_LORA_BANK"):
+        return lora_bank_main(os.environ["GEN_LORA_BANK"])
     if os.environ.get("GEN_LORA"):
         return lora_main(os.environ["GEN_LORA"])
     if os.environ.get("GEN_STREAM") == "1":
