@@ -37,7 +37,14 @@ def parse_args(argv=None):
     p.add_argument("--chunk-frames", type=int, default=4, help="80-ms frames per streamed chunk (default: 4)")
     p.add_argument("--lora-adapter", type=str, default=None,
                    help="LoRA adapter file written by csm-finetune-lora (.safetensors with its _metadata.json), applied without merging")
-    return p.parse_args(argv)
+    p.add_argument("--next-text", type=str, action="append", default=None,
+                   help="a further line, spoken after --text in the same conversation with the KV cache kept (repeatable)")
+    p.add_argument("--next-speaker", type=int, action="append", default=None,
+                   help="speaker ID of the corresponding --next-text (repeatable; default: the speaker of --text)")
+    args = p.parse_args(argv)
+    if args.next_speaker and len(args.next_speaker) != len(args.next_text or []):
+        p.error("--next-speaker must be given once per --next-text (or not at all)")
+    return args
 
 
 def build_context(args, sample_rate):
@@ -64,6 +71,8 @@ def main(argv=None):
     if args.lora_adapter:
         adapter = "cli"
         generator.load_adapter(adapter, args.lora_adapter)
+    if args.next_text:
+        return converse_to_wav(generator, args, speaker_id, context, adapter)
     if args.stream:
         return stream_to_wav(generator, args, speaker_id, context, adapter)
     audio = generator.generate(text=args.text, speaker=speaker_id, context=context, max_audio_length_ms=args.max_audio_length_ms,
@@ -93,6 +102,44 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
             w.writeframes(pcm)
             n += chunk.numel()
     print(f"Audio saved to {args.output} ({n / generator.sample_rate:.2f} s at {generator.sample_rate} Hz, streamed in "
+          f"{time.perf_counter() - t0:.2f} s)")
+    return 0
+
+
+def _pcm(audio):
+    return (audio.detach().float().cpu().clamp(-1, 1) * 32767.0).to(torch.int16).numpy().tobytes()
+
+
+def converse_to_wav(generator, args, speaker_id, context, adapter=None):
+    """--next-text: --text and every further line are the turns of one ``Generator.conversation`` (the KV cache is kept between
+    them); all turns go to --output in order, chunk by chunk with --stream.  Samples are converted as ``Generator.save_wav``
+    converts them."""
+    os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
+    lines = [(args.text, speaker_id)] + list(zip(args.next_text, args.next_speaker or [speaker_id] * len(args.next_text)))
+    conv = generator.conversation(context=context, adapter=adapter)
+    kw = dict(max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature, topk=args.topk)
+    t0 = time.perf_counter()
+    n = 0
+    with wave.open(args.output, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(generator.sample_rate))
+        for i, (text, spk) in enumerate(lines):
+            t1 = time.perf_counter()
+            if args.stream:
+                first = None
+                for chunk in conv.generate_stream(text, spk, chunk_frames=args.chunk_frames, **kw):
+                    pcm = _pcm(chunk)
+                    first = first if first is not None else time.perf_counter() - t1
+                    w.writeframes(pcm)
+                    n += chunk.numel()
+                print(f"turn {i + 1}: first chunk after {first if first is not None else float('nan'):.3f} s")
+            else:
+                audio = conv.generate(text, spk, **kw)
+                w.writeframes(_pcm(audio))
+                n += audio.numel()
+                print(f"turn {i + 1}: {audio.numel() / generator.sample_rate:.2f} s of audio in {time.perf_counter() - t1:.2f} s")
+    print(f"Audio saved to {args.output} ({n / generator.sample_rate:.2f} s at {generator.sample_rate} Hz, {len(lines)} turns in "
           f"{time.perf_counter() - t0:.2f} s)")
     return 0
 

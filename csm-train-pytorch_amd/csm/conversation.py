@@ -1,0 +1,262 @@
+"""Multi-turn generation that keeps the backbone's KV cache between turns (not in the reference, whose ``generate`` starts from
+nothing every call: it Mimi-encodes every context segment again and prefills the whole history from position 0).
+
+A ``Conversation`` owns the token history the model has been conditioned on and one ``DecodeState`` (KV caches, captured frame
+graph).  A turn feeds only what the cache does not hold yet - ``history[cached:]`` plus the new line's text frames - through
+``DecodeState.append`` (``csm_attn_append``: the new positions attend to the cached ones), so the time to the first frame
+depends on the new line, not on the length of the conversation.  The frames the model speaks stay in the cache as they were
+sampled; the other party's audio is Mimi-encoded once, when it is ``add``ed.
+"""
+from contextlib import contextmanager
+from typing import Iterator, List, Optional
+
+import torch
+
+from .engine import DecodeState
+
+OVERFLOW = ("error", "drop_oldest")
+
+
+class _Turn:
+    """A spoken turn in flight: the sampled frames, how many of them were fed back into the cache, how many were handed out."""
+
+    def __init__(self, base: int, n_text: int):
+        self.base, self.n_text = base, n_text      # history length (= cached positions) after the text frames
+        self.samples: List[torch.Tensor] = []
+        self.fed = 0                               # samples[:fed] have been fed to the backbone (one position each)
+        self.kept = 0                              # frames handed to the caller so far (stream) / kept (generate)
+        self.done = False
+
+
+class Conversation:
+    """``Generator.conversation(...)``.  One dialogue, B = 1.
+
+    ``tokens`` / ``mask`` ([L, K+1]) are the frame history the model has been conditioned on, laid out as the reference lays out
+    its context: per turn the text frames, the audio frames, one all-zero EOS frame - for a spoken turn the codes are the ones
+    the model sampled, not a re-encoding of its audio.  ``cached`` leading positions of it have their K / V in the cache; the
+    rest goes in with the next turn.  Under the same torch seed the first ``generate`` equals ``Generator.generate`` with the
+    same context bit for bit; later turns differ from a stateless call by design (own codes instead of re-encoded ones).
+
+    The conversation owns its ``DecodeState`` and installs it as the model's only while one of its calls samples a frame, so
+    ``Generator.generate*`` calls between turns and other conversations do not disturb it; only its own open
+    ``generate_stream`` is invalidated by its own next call (the frames already handed out are kept, the rest rolled back -
+    the same happens when a stream is abandoned).  The caches of a conversation take 67 MB at CSM-1B (16 layers x K and V x
+    8 kv heads x 2048 positions x 64 x bf16) plus the depth decoder's 0.5 MB.
+
+    The cache is only valid for the weights it was computed with: after training steps, an adapter swap or a merge call
+    ``reset()`` - the history is kept and prefilled again by the next turn.
+    """
+
+    def __init__(self, gen, context=(), adapter: Optional[str] = None, on_overflow: str = "error"):
+        if on_overflow not in OVERFLOW:
+            raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
+        self._gen, self._m = gen, gen._model
+        self._ads = gen._resolve_adapters([adapter])
+        self._on_overflow = on_overflow
+        K1 = self._m.args.audio_num_codebooks + 1
+        self._tokens = torch.zeros(0, K1, dtype=torch.long, device=gen.device)
+        self._mask = torch.zeros(0, K1, dtype=torch.bool, device=gen.device)
+        self._turns: List[int] = []                # lengths of the turns that make up the history
+        self._cached = 0
+        self._state: Optional[DecodeState] = None
+        self._run = 0
+        self._open: Optional[_Turn] = None
+        for seg in context:
+            self.add(seg)
+
+    # ---- read-only views ---------------------------------------------------------------------------------------------------
+    @property
+    def tokens(self) -> torch.Tensor:
+        return self._tokens
+
+    @property
+    def mask(self) -> torch.Tensor:
+        return self._mask
+
+    @property
+    def cached(self) -> int:
+        return self._cached
+
+    # ---- history -----------------------------------------------------------------------------------------------------------
+    @torch.inference_mode()
+    def add(self, segment) -> None:
+        """The other party's turn (or any context segment): only THIS segment is tokenised and Mimi-encoded.  It enters the cache
+        with the next spoken turn."""
+        self._run += 1
+        self._settle()
+        t, m = self._gen._tokenize_segment(segment)
+        self._push(t.long(), m.bool())
+
+    def reset(self) -> None:
+        """Drop the cache (and the captured frame graph), keep the history: the next turn prefills it from position 0 with the
+        weights and adapters of that moment."""
+        self._run += 1
+        self._settle()
+        self._state, self._cached = None, 0
+
+    def _push(self, t, m):
+        self._tokens = torch.cat([self._tokens, t.to(self._tokens.device)], 0)
+        self._mask = torch.cat([self._mask, m.to(self._mask.device)], 0)
+        self._turns.append(t.shape[0])
+
+    def _fit(self, n_new: int, max_audio_frames: int):
+        """The reference's length rule (generator.py:168-170) on history + new text; ``drop_oldest`` drops whole leading turns
+        until it holds - cached keys are rotated for their positions and cannot slide, so what is kept is prefilled again."""
+        limit = self._m.bb.max_seq_len - max_audio_frames
+        if self._tokens.shape[0] + n_new < limit:
+            return
+        drop, left = 0, self._tokens.shape[0]
+        if self._on_overflow == "drop_oldest":
+            while drop < len(self._turns) and left + n_new >= limit:
+                left -= self._turns[drop]
+                drop += 1
+        if left + n_new >= limit:
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
+        cut = self._tokens.shape[0] - left
+        self._tokens, self._mask, self._turns = self._tokens[cut:], self._mask[cut:], self._turns[drop:]
+        self._cached = 0
+
+    # ---- a spoken turn -----------------------------------------------------------------------------------------------------
+    @contextmanager
+    def _installed(self):
+        m = self._m
+        prev = getattr(m, "_decode_state", None)
+        m._decode_state = self._state
+        try:
+            yield
+        finally:
+            m._decode_state = prev
+
+    def _begin(self, text, speaker, max_audio_frames, temperature, topk) -> _Turn:
+        """Feed what the cache lacks plus the new line's text frames, sample the first frame."""
+        m, e = self._m, self._m.engine
+        if not getattr(m, "use_kv_cache", True):
+            raise RuntimeError("a Conversation keeps the KV cache between turns: model.use_kv_cache must be on")
+        tt, tm = self._gen._tokenize_text_segment(text, speaker)
+        self._fit(tt.shape[0], max_audio_frames)
+        new_t = torch.cat([self._tokens[self._cached:], tt.long()], 0)
+        new_m = torch.cat([self._mask[self._cached:], tm.bool()], 0)
+        e._need()
+        if self._state is None:
+            self._state = DecodeState(e, 1, self._ads)
+        st = self._state
+        if self._cached == 0:
+            last_h = st.prefill(new_t.unsqueeze(0), new_m.unsqueeze(0))
+        else:
+            last_h = st.append(new_t, new_m)
+        self._push(tt.long(), tm.bool())
+        self._cached = self._tokens.shape[0]
+        turn = self._open = _Turn(self._cached, tt.shape[0])
+        turn.samples.append(e._frame_tail(st, last_h, temperature, topk, None))
+        return turn
+
+    def _next_frame(self, turn: _Turn, temperature, topk):
+        """Feed the last sampled frame, sample the next one (``Model.generate_frame`` on this conversation's state)."""
+        K = self._m.args.audio_num_codebooks
+        dev = self._gen.device
+        tokens = torch.cat([turn.samples[-1].long(), torch.zeros(1, 1, dtype=torch.long, device=dev)], dim=1).unsqueeze(1)
+        mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(dev)
+        with self._installed():
+            s = self._m.generate_frame(tokens, mask, torch.ones(1, 1, dtype=torch.long), temperature, topk)
+        turn.fed += 1
+        turn.samples.append(s)
+
+    def _settle(self):
+        """Close the turn in flight, if any: the history gets its kept frames and one all-zero EOS frame (the layout of
+        ``Generator._tokenize_segment``), the cache is rolled back to the last position that is part of the history."""
+        turn, self._open = self._open, None
+        if turn is None or turn.done:
+            return
+        turn.done = True
+        K = self._m.args.audio_num_codebooks
+        k = turn.kept
+        frames = torch.zeros(k + 1, K + 1, dtype=torch.long, device=self._tokens.device)
+        if k:
+            frames[:k, :K] = torch.cat(turn.samples[:k], 0).long()
+        fmask = torch.zeros(k + 1, K + 1, dtype=torch.bool, device=self._mask.device)
+        fmask[:, :K] = True
+        self._tokens = torch.cat([self._tokens, frames], 0)
+        self._mask = torch.cat([self._mask, fmask], 0)
+        self._turns[-1] += k + 1                                   # the text frames opened this turn
+        # positions base .. base+fed-1 hold samples[:fed]; of those the kept frames stay.  The EOS frame always enters with the
+        # next turn's append, also where eos_check_every > 1 had fed it already (a decode step and an append round differently):
+        # what the cache holds after a turn does not depend on how often the host looked for EOS
+        keep = min(turn.fed, k)
+        if turn.fed > keep:
+            self._state.truncate(turn.base + keep)
+        self._cached = turn.base + keep
+
+    @torch.inference_mode()
+    def generate(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
+                 eos_check_every: int = 8) -> torch.Tensor:
+        """Speak ``text`` as ``speaker`` with the whole history as context; arguments and EOS handling as ``Generator.generate``."""
+        self._run += 1
+        self._settle()
+        max_audio_frames = int(max_audio_length_ms / 80)
+        step = max(1, int(eos_check_every))
+        turn, checked = None, 0
+        try:
+            for i in range(max_audio_frames):
+                if turn is None:
+                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk)
+                else:
+                    self._next_frame(turn, temperature, topk)
+                n = len(turn.samples)
+                if n - checked >= step or i == max_audio_frames - 1:
+                    hit = (torch.cat(turn.samples[checked:], 0) == 0).all(dim=1).nonzero()          # one host look per chunk
+                    if hit.numel():
+                        turn.kept = checked + int(hit[0])
+                        break
+                    checked = turn.kept = n
+        finally:
+            samples = turn.samples[:turn.kept] if turn is not None else []
+            self._settle()
+        if not samples:
+            return torch.zeros(0, device=self._gen.device)
+        codes = torch.stack(samples).permute(1, 2, 0).long()
+        return self._gen._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
+
+    def generate_stream(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9,
+                        topk: int = 50, chunk_frames: int = 4) -> Iterator[torch.Tensor]:
+        """``generate`` handing the audio out chunk by chunk, as ``Generator.generate_stream`` does; under the same seed the
+        chunks concatenate to ``generate``'s audio.  A later call on THIS conversation invalidates the stream."""
+        if int(chunk_frames) != chunk_frames or chunk_frames < 1:
+            raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
+        codec = self._gen._audio_tokenizer
+        if not callable(getattr(codec, "decode_stream", None)):
+            raise TypeError(f"{type(codec).__name__} has no decode_stream(): streaming needs a stateful decoder "
+                            "(decoding chunks independently would be wrong at the chunk edges)")
+        self._run += 1
+        self._settle()
+        return self._stream(self._run, text, speaker, max_audio_length_ms, temperature, topk, int(chunk_frames))
+
+    @torch.inference_mode()
+    def _stream(self, run, text, speaker, max_audio_length_ms, temperature, topk, chunk_frames):
+        def check():
+            if self._run != run:
+                raise RuntimeError("this stream was invalidated: a later call on the same Conversation took its turn")
+
+        check()
+        max_audio_frames = int(max_audio_length_ms / 80)
+        decoder = self._gen._audio_tokenizer.decode_stream()
+        turn, done = None, 0
+        try:
+            for i in range(max_audio_frames):
+                if turn is None:
+                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk)
+                else:
+                    self._next_frame(turn, temperature, topk)
+                if len(turn.samples) - done == chunk_frames or i == max_audio_frames - 1:
+                    codes = torch.stack(turn.samples[done:]).permute(1, 2, 0).long()               # [1, K, n]
+                    hit = (codes[0] == 0).all(dim=0).nonzero()                                     # the chunk's one host look
+                    n = int(hit[0]) if hit.numel() else codes.shape[2]
+                    turn.kept = done + n
+                    done = len(turn.samples)
+                    if n:
+                        yield decoder.step(codes[:, :, :n]).reshape(-1)
+                        check()
+                    if hit.numel():
+                        return
+        finally:
+            if turn is not None and self._open is turn:
+                self._settle()

@@ -117,7 +117,10 @@ class _Stack:
 
     # -------------------------------------------------------------------------------------------- forward
     def forward(self, x: torch.Tensor, B: int, S: int, save: bool, pos: Optional[torch.Tensor] = None,
-                fuse_rope: bool = True, on_layer_start=None) -> torch.Tensor:
+                fuse_rope: bool = True, on_layer_start=None, append=None) -> torch.Tensor:
+        """``append`` = (decode stack, batch row, pos0): the S rows are positions pos0 .. pos0+S-1 of the sequence whose earlier
+        positions sit in that stack's KV caches (B = 1, ``pos`` given, nothing saved) - every layer's attention appends its K / V
+        rows to the caches and attends to them (``ops.attn_append``) instead of the from-scratch ``ops.attn_fwd``."""
         c, dev = self.c, x.device
         M, d = x.shape
         H, KV, hd, F = c.num_heads, c.num_kv_heads, c.head_dim, c.intermediate_dim
@@ -152,8 +155,14 @@ class _Stack:
                         a[f"t_{mod}"] = ad.forward(xn, qkv[:, lo_:hi_])
                 ops.rope(qkv, table, S, H + KV, hd, pos=pos)
             o = torch.empty(M, H * hd, dtype=BF16, device=dev)
-            lse = torch.empty(B, H, S, dtype=F32, device=dev)
-            ops.attn_fwd(qkv, o, lse, B, S, H, KV, hd)
+            if append is None:
+                lse = torch.empty(B, H, S, dtype=F32, device=dev)
+                ops.attn_fwd(qkv, o, lse, B, S, H, KV, hd)
+            else:
+                assert B == 1 and pos is not None and not save
+                ds, row, pos0 = append
+                lse = None
+                ops.attn_append(qkv, ds.k[i], ds.v[i], o, row, pos0, H, KV, hd)
             h = torch.empty(M, d, dtype=BF16, device=dev)
             G, fused = self._group(i, "attn_out")
             if fused:
@@ -1090,6 +1099,25 @@ class _DecodeStack:
             self.lt = torch.zeros(self.B, kmax, dtype=BF16, device=dev)
 
 
+_graph_rng_primed = None
+
+
+def _prime_graph_rng(device):
+    """The process's first graph capture creates the CUDA generator's capture-state tensors and every later capture updates
+    them in place.  Created under ``torch.inference_mode`` (``Generator.generate``, a ``Conversation`` turn) they would be
+    inference tensors and a later capture outside it (``Model.generate_frame`` called directly) would be refused - so the first
+    capture of the process is a one-element one made here, outside inference mode, and its graph is kept for the life of the
+    process (the generator drops those tensors when the last graph that registered with it goes)."""
+    global _graph_rng_primed
+    if _graph_rng_primed is not None:
+        return
+    with torch.inference_mode(False):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            torch.zeros(1, device=device)
+    _graph_rng_primed = g
+
+
 class DecodeState:
     """Everything ``generate_frame`` keeps between calls: the two stacks' caches and small persistent buffers."""
 
@@ -1160,6 +1188,43 @@ class DecodeState:
         self.cur = S - 1                       # host mirror of the device-side position (no sync per frame)
         return hidden.view(B, S, -1)[:, -1, :].contiguous()
 
+    def append(self, tokens, masks):
+        """Feed n more positions ([n, K+1] or [1, n, K+1] frames) after the ``cur + 1`` the caches hold - the next turn of a
+        conversation: the training forward's kernels for the n rows, with every layer's attention running against the state's own
+        caches (``ops.attn_append``: the rows' K / V are appended, nothing is prefilled again).  Returns the last position's hidden
+        row [1, d] for ``Engine._frame_tail``, as ``prefill`` does.  Adapters apply as in ``prefill`` (live ``model.lora``, or
+        the state's own bank adapter).  The captured frame graph reads the position from device memory and stays valid."""
+        e, m = self.e, self.e.m
+        if self.B != 1:
+            raise ValueError(f"append takes a one-sequence state (this one has {self.B} rows)")
+        if self.cur < 0:
+            raise RuntimeError("append needs a prefilled state (prefill the first turn)")
+        K1 = tokens.shape[-1]
+        tk = tokens.reshape(-1, K1).to(device=m.device, dtype=torch.int64).contiguous()
+        mk = masks.reshape(-1, K1).to(device=m.device, dtype=torch.uint8).contiguous()
+        n, pos0 = tk.shape[0], self.cur + 1
+        if n < 1:
+            raise ValueError("append needs at least one position")
+        if pos0 + n > m.bb.max_seq_len:
+            raise ValueError("sequence exceeds max_seq_len")
+        h0 = torch.empty(n, m.bb.embed_dim, dtype=BF16, device=m.device)
+        ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
+        pos = torch.arange(pos0, pos0 + n, dtype=torch.int32, device=m.device)
+        with (row_lora(m, self.adapters[0]) if self.adapters is not None else generation_lora(m)):
+            hidden = e.backbone.forward(h0, 1, n, False, pos=pos, append=(self.bb, 0, pos0))
+        self.bb.pos.fill_(pos0 + n - 1)
+        self.cur = pos0 + n - 1
+        return hidden[-1:].contiguous()
+
+    def truncate(self, length: int):
+        """Forget every position from ``length`` on (1 <= length <= cur + 1): the device position and its host mirror move back
+        to ``length - 1``.  Nothing is cleared - cache rows past the position are never read and the next step overwrites them."""
+        length = int(length)
+        if not 1 <= length <= self.cur + 1:
+            raise ValueError(f"truncate to {length} positions: the caches hold {self.cur + 1}")
+        self.bb.pos.fill_(length - 1)
+        self.cur = length - 1
+
     def prefill_ragged(self, tokens_list, masks_list):
         """Prompts of different lengths, one per batch row: each is prefilled on its own ([1, S_b] through the training
         forward) into its row of the caches; positions are per row from then on (``pos`` is a device vector)."""
@@ -1209,6 +1274,7 @@ class DecodeState:
             self.in_msk = masks.to(torch.uint8).clone()
             self.fill_noise(noise)
             torch.cuda.synchronize()
+            _prime_graph_rng(m.device)
             g = torch.cuda.CUDAGraph()
             # No cyclic garbage collection while the stream is capturing: a collection that happens to run inside the ~700
             # launches may finalise objects whose destructors call the runtime (an older model's captured graph, events) - not

@@ -283,6 +283,15 @@ class Generator:
                 out.append(self._audio_tokenizer.decode(codes_all[b:b + 1, :, :n]).squeeze(0).squeeze(0))
         return out
 
+    def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error"):
+        """A multi-turn dialogue that keeps its KV cache between turns (csm/conversation.py): ``conv.generate(text, speaker)`` /
+        ``conv.generate_stream(...)`` speak the next line with every earlier turn as context, ``conv.add(Segment)`` adds the
+        other party's turn.  ``adapter``: a bank adapter name for the whole conversation.  ``on_overflow``: ``"error"`` raises
+        the reference's "Inputs too long" error when history + line + max_audio_frames reach max_seq_len, ``"drop_oldest"``
+        drops whole leading turns and prefills what is left."""
+        from .conversation import Conversation
+        return Conversation(self, context or [], adapter, on_overflow)
+
     def save_wav(self, path: str, audio: torch.Tensor):
         """16-bit PCM writer (torchaudio is not available in this image)."""
         import wave

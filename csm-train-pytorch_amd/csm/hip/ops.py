@@ -2,11 +2,12 @@
 
 PyTorch is plumbing here (device memory, streams); every arithmetic op is a hand-written gfx950 kernel.
 """
+import math
 from typing import Optional
 
 import torch
 
-from . import check, lib
+from . import CsmHipError, check, lib
 
 BF16 = torch.bfloat16
 
@@ -532,6 +533,21 @@ def gemv_t(x, W, y):
     check(lib.csm_gemv_t_bf16(x.data_ptr(), W.data_ptr(), y.data_ptr(), B, N, K, W.stride(0), x.stride(0), y.stride(0),
                               int(y.dtype == torch.float32), _stream()), "csm_gemv_t_bf16")
     return y
+
+
+def attn_append(qkv, kcache, vcache, out, row, pos0, H, KV, HD):
+    """The n = ``qkv.shape[0]`` new positions ``pos0 .. pos0+n-1`` of the sequence in batch row ``row`` of the caches
+    ([B, KV, S_max, HD]): appends their K / V rows (q and k already rotated for those positions) and attends every new query to
+    cache positions ``0 .. its own``.  A row's bits do not depend on how the new positions are split into launches."""
+    B, _, S_max, _ = kcache.shape
+    n = qkv.shape[0]
+    assert qkv.is_contiguous() and out.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()
+    assert qkv.shape == (n, (H + 2 * KV) * HD) and out.shape == (n, H * HD) and vcache.shape == kcache.shape == (B, KV, S_max, HD)
+    if not 0 <= int(row) < B:
+        raise CsmHipError(f"csm_attn_append failed (code 1): batch row {row} outside the caches ({B} rows)")
+    check(lib.csm_attn_append(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), int(row), int(pos0), n, H, KV, HD,
+                              S_max, 1.0 / math.sqrt(HD), _stream()), "csm_attn_append")
+    return out
 
 
 def kv_append(qkv, kcache, vcache, pos_i32, H, KV, HD):

@@ -697,3 +697,235 @@ extern "C" int csm_attn_bwd_rope(const void* qkv, const void* out, const void* d
     CSM_REQUIRE(rope_table, "csm_attn_bwd_rope: null table");
     return attn_bwd_impl(qkv, out, dout, lse, dqkv, delta_ws, rope_table, B, S, H, KV, HD, stream);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Append: n new positions pos0 .. pos0+n-1 of ONE sequence against its KV cache (a conversation's next turn: the new text frames,
+// or the other party's audio, with every earlier turn already cached).  The skeleton is the forward's - swapped S^T = K Q^T, P^T
+// straight from the accumulators, V^T by transposed LDS reads - with three differences:
+//  * a workgroup is one tile of 16 queries of ONE kv head; wave (hh, ks) takes q head hh of the group and the 64-key blocks
+//    j = ks, ks + KS, ... (ascending), so the REP head-waves of a split share one staging of each V block;
+//  * keys below pos0 come from the cache, keys pos0 .. pos0+n-1 from the qkv rows of this launch (the same bits the workgroup
+//    of their tile writes into the cache: no workgroup reads a cache row another one is writing), later keys read as zero;
+//  * the KS partial (m, l, O) of a head are combined in LDS in split order 0, 1, ...
+// Invariant (tests/test_conversation_gpu.py): the bits of an output row depend only on its q, its absolute position and the
+// keys / values up to that position.  Key blocks are aligned to absolute multiples of 64 and dealt to splits by block index, the
+// element order inside an MFMA is a function of the key's index in its block, a row of an MFMA tile does not see the other rows,
+// and a key above a row's position enters as p = exp2(-inf) = +0 exactly: a fully masked block leaves m, l and O as they were
+// (alpha = exp2(0) = 1), so the number of blocks a tile's waves walk - which does depend on the tile's last row - cannot show.
+template <int REP, int KS>
+__global__ __launch_bounds__(64 * REP * KS) void attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
+                                                                      bf16_t* __restrict__ vc, bf16_t* __restrict__ out, int pos0,
+                                                                      int n, int H, int KV, int S_max, float scale) {
+    constexpr int HD = 64, NKS = 2, NDT = 4, NT = 64 * REP * KS, ST = 64 * REP;      // ST = threads that stage one split's V block
+    using I = Img<HD>;
+    static_assert((KS - 1) * REP * 18 * 64 * 4 <= KS * 2 * I::BYTES, "the partials reuse the V images");
+    __shared__ __attribute__((aligned(16))) char smem[KS * 2 * I::BYTES];
+    const int lane = threadIdx.x & 63, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int hh = wave % REP, ks = wave / REP;
+    const int tile = gridDim.x - 1 - blockIdx.x, kvh = blockIdx.y;              // the tiles with the most keys start first
+    const int h = kvh * REP + hh;
+    const int ld = (H + 2 * KV) * HD;
+    const int last_new = pos0 + n - 1;
+    const bf16_t* Kn = qkv + (H + kvh) * HD;                                    // new rows: key pos0 + i is row i
+    const bf16_t* Vn = qkv + (H + KV + kvh) * HD;
+    bf16_t* Kc = kc + (size_t)kvh * S_max * HD;
+    bf16_t* Vc = vc + (size_t)kvh * S_max * HD;
+    auto v_img = [&](int st) { return smem + (ks * 2 + st) * I::BYTES; };
+
+    // this tile's new K / V rows into the cache (16 rows x 8 chunks, K and V)
+    for (int idx = threadIdx.x; idx < 256; idx += NT) {
+        const int r = (idx >> 3) & 15, c = idx & 7, i = tile * 16 + r;
+        if (i < n) {
+            const bf16_t* src = (idx < 128 ? Kn : Vn) + (size_t)i * ld + c * 8;
+            bf16_t* dst = (idx < 128 ? Kc : Vc) + (size_t)(pos0 + i) * HD + c * 8;
+            *reinterpret_cast<U4*>(dst) = *reinterpret_cast<const U4*>(src);
+        }
+    }
+
+    const int r0 = tile * 16;
+    const int qi = r0 + (lane & 15);                                            // row of the launch; position pos0 + qi
+    const int qpos = pos0 + qi;
+    bf16x8 qf[NKS];
+    load_rowfrags<HD>(qkv + h * HD, ld, qi < n ? qi : n - 1, qf, lane);
+    const float c2 = scale * 1.4426950408889634f;
+
+    int tl = pos0 + r0 + 15;
+    tl = tl < last_new ? tl : last_new;
+    const int nkb = tl / 64 + 1;                                                // key blocks 0 .. nkb-1 hold keys some row of the tile sees
+    const int iters = (nkb + KS - 1) / KS;
+
+    // one 16-byte chunk of key row `key`: the cache below pos0, this launch's rows up to last_new, zero beyond (never a stale row)
+    auto row_chunk = [&](const bf16_t* cache, const bf16_t* fresh, int key, int d0) -> U4 {
+        U4 z = {0u, 0u, 0u, 0u};
+        if (key > last_new) return z;
+        const bf16_t* p = key < pos0 ? cache + (size_t)key * HD + d0 : fresh + (size_t)(key - pos0) * ld + d0;
+        return *reinterpret_cast<const U4*>(p);
+    };
+    constexpr int NVR = 512 / ST;                                               // V chunks per staging thread
+    const int st_tid = threadIdx.x - ks * ST;
+    auto load_v = [&](int j, U4 (&vr)[NVR]) {
+#pragma unroll
+        for (int i = 0; i < NVR; ++i) {
+            const int idx = st_tid + ST * i;
+            vr[i] = row_chunk(Vc, Vn, j * 64 + (idx >> 3), (idx & 7) * 8);
+        }
+    };
+    auto store_v = [&](char* img, const U4 (&vr)[NVR]) {
+#pragma unroll
+        for (int i = 0; i < NVR; ++i) {
+            const int idx = st_tid + ST * i;
+            *reinterpret_cast<U4*>(img + I::row_off(idx >> 3, idx & 7)) = vr[i];
+        }
+    };
+    // A fragments of the block's four key tiles: row = key 16 kt + lane&15, k = d 32 s + 8 g + j, straight from global memory
+    auto load_k = [&](int j, U4 (&kr)[4][NKS]) {
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int s = 0; s < NKS; ++s) kr[kt][s] = row_chunk(Kc, Kn, j * 64 + 16 * kt + (lane & 15), 32 * s + 8 * g);
+    };
+
+    f32x4 o[NDT];
+    float m = -INFINITY, l = 0.f;
+#pragma unroll
+    for (int i = 0; i < NDT; ++i) o[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    U4 vreg[NVR], kcur[4][NKS], knext[4][NKS];
+    if (ks < nkb) {
+        load_v(ks, vreg);
+        load_k(ks, kcur);
+        store_v(v_img(0), vreg);
+    }
+    __syncthreads();
+
+    for (int it = 0; it < iters; ++it) {
+        const int st = it & 1, j = it * KS + ks, jn = j + KS;
+        const bool more = it + 1 < iters && jn < nkb;                           // wave-uniform
+        if (more) {
+            load_v(jn, vreg);
+            load_k(jn, knext);
+        }
+        if (j < nkb) {
+            const int key0 = j * 64;
+            f32x4 s[4];
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt) {
+                s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int x = 0; x < NKS; ++x) s[kt] = MFMA(*reinterpret_cast<const bf16x8*>(&kcur[kt][x]), qf[x], s[kt]);
+            }
+            // s[kt][r] = S[key = key0 + 16 kt + 4 g + r][q = qi]
+            if (key0 + 63 > pos0 + r0) {
+#pragma unroll
+                for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (key0 + 16 * kt + 4 * g + r > qpos) s[kt][r] = -INFINITY;
+            }
+            float mx = max3(s[0][0], s[0][1], s[0][2]);
+            mx = max3(mx, s[0][3], s[1][0]);
+            mx = max3(mx, s[1][1], s[1][2]);
+            mx = max3(mx, s[1][3], s[2][0]);
+            mx = max3(mx, s[2][1], s[2][2]);
+            mx = max3(mx, s[2][3], s[3][0]);
+            mx = max3(mx, s[3][1], s[3][2]);
+            const float m_new = rows_max(max3(mx, s[3][3], m));
+            const float m_use = m_new == -INFINITY ? 0.f : m_new;               // a row that has seen no key yet: p = 0, alpha = 0
+            const float alpha = fast_exp2((m - m_use) * c2);
+            l *= alpha;
+#pragma unroll
+            for (int i = 0; i < NDT; ++i) o[i] *= alpha;
+            m = m_new;
+            const float nb = -m_use * c2;
+            float sum = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float p = fast_exp2(fmaf(s[kt][r], c2, nb));
+                    s[kt][r] = p;
+                    sum += p;
+                }
+            l += rows_sum(sum);
+            const bf16x8 pf0 = frag_from_acc(s[0], s[1]), pf1 = frag_from_acc(s[2], s[3]);
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                o[dt] = MFMA(frag_tr<HD>(v_img(st), dt, 0, lane), pf0, o[dt]);
+                o[dt] = MFMA(frag_tr<HD>(v_img(st), dt, 1, lane), pf1, o[dt]);
+            }
+        }
+        if (more) {
+            store_v(v_img(st ^ 1), vreg);
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                for (int x = 0; x < NKS; ++x) kcur[kt][x] = knext[kt][x];
+        }
+        __syncthreads();
+    }
+
+    // combine the splits of a head in split order: split ks > 0 leaves (m, l, O) in LDS [wave][element][lane], split 0 adds them up
+    float* part = reinterpret_cast<float*>(smem);
+    if (ks > 0) {
+        float* p = part + ((ks - 1) * REP + hh) * 18 * 64 + lane;
+        p[0] = m; p[64] = l;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[(2 + dt * 4 + r) * 64] = o[dt][r];
+    }
+    __syncthreads();
+    if (ks > 0) return;
+    float pm[KS], M = m;                                                        // split 0 holds key 0, which every row sees: M is finite
+    pm[0] = m;
+#pragma unroll
+    for (int k = 1; k < KS; ++k) {
+        pm[k] = part[((k - 1) * REP + hh) * 18 * 64 + lane];
+        M = fmaxf(M, pm[k]);
+    }
+    float a = fast_exp2((pm[0] - M) * c2);
+    l *= a;
+#pragma unroll
+    for (int i = 0; i < NDT; ++i) o[i] *= a;
+#pragma unroll
+    for (int k = 1; k < KS; ++k) {
+        const float* p = part + ((k - 1) * REP + hh) * 18 * 64 + lane;
+        a = fast_exp2((pm[k] - M) * c2);                                        // a split without a visible key: exp2(-inf) = 0
+        l += p[64] * a;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[dt][r] += p[(2 + dt * 4 + r) * 64] * a;
+    }
+    if (qi >= n) return;
+    // o[dt][r] = O^T[d = 16 dt + 4 g + r][q = qi]
+    const float inv = 1.f / l;
+    bf16_t* op = out + (size_t)qi * (H * HD) + h * HD;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+        uint2 w; w.x = pack2bf(o[dt][0] * inv, o[dt][1] * inv); w.y = pack2bf(o[dt][2] * inv, o[dt][3] * inv);
+        *reinterpret_cast<uint2*>(op + 16 * dt + 4 * g) = w;
+    }
+}
+
+extern "C" int csm_attn_append(const void* qkv, void* kcache, void* vcache, void* out, int row, int pos0, int n, int H, int KV,
+                               int HD, int S_max, float scale, hipStream_t stream) {
+    CSM_REQUIRE(qkv && kcache && vcache && out, "csm_attn_append: null pointer");
+    CSM_REQUIRE(H > 0 && KV > 0 && H % KV == 0 && S_max > 0, "csm_attn_append: bad shape H=%d KV=%d S_max=%d", H, KV, S_max);
+    CSM_REQUIRE(HD == 64, "csm_attn_append: head_dim %d unsupported (64)", HD);
+    const int rep = H / KV;
+    CSM_REQUIRE(rep == 1 || rep == 2 || rep == 4, "csm_attn_append: %d query heads per kv head unsupported (1, 2 or 4)", rep);
+    CSM_REQUIRE(row >= 0, "csm_attn_append: batch row %d", row);
+    CSM_REQUIRE(n >= 1, "csm_attn_append: n = %d new positions (at least 1)", n);
+    CSM_REQUIRE(pos0 >= 0 && (long long)pos0 + n <= S_max, "csm_attn_append: positions %d .. %lld outside the cache (%d rows)", pos0,
+                (long long)pos0 + n - 1, S_max);
+    bf16_t* kc = (bf16_t*)kcache + (size_t)row * KV * S_max * HD;
+    bf16_t* vc = (bf16_t*)vcache + (size_t)row * KV * S_max * HD;
+    const dim3 grid((n + 15) / 16, KV);
+#define L(REP) hipLaunchKernelGGL((attn_append_kernel<REP, 2>), grid, dim3(64 * REP * 2), 0, stream, (const bf16_t*)qkv, kc, vc, (bf16_t*)out, pos0, n, H, KV, S_max, scale)
+    if (rep == 4) L(4); else if (rep == 2) L(2); else L(1);
+#undef L
+    CSM_CHECK_LAUNCH("csm_attn_append");
+    return 0;
+}

@@ -288,6 +288,15 @@ int csm_attn_decode(const void* qkv, const void* kcache, const void* vcache, voi
  * csm_rope + csm_kv_append + csm_attn_decode. qkv is the UNROTATED fused projection row. */
 int csm_attn_decode_rope(const void* qkv, void* kcache, void* vcache, void* out, const int* pos, const float* rope_table, int B,
                          int H, int KV, int HD, int S_max, int ld, csm_stream_t stream);
+/* n new positions pos0 .. pos0+n-1 of ONE sequence (batch row `row` of the caches) against what the cache already holds - a
+ * conversation's next turn.  qkv [n][(H+2KV)*HD] with q and k ALREADY rotated for those positions (csm_rope with pos); the kernel
+ * writes the n new K / V rows into cache rows pos0 .. pos0+n-1 and computes, for query i, softmax over cache positions 0 .. pos0+i
+ * (fp32 statistics and accumulation) into out [n][H*HD].  Nothing is read back by the host.  HD = 64, H / KV in {1, 2, 4}.
+ * The bits of an output row depend only on that row's q, its absolute position and the keys / values up to that position - not
+ * on n, pos0 or the other rows of the launch: one launch of n rows equals any split of it into consecutive launches.
+ * The number of batch rows of the caches is not an argument: `row` < B is the caller's to check (csm/hip/ops.py does). */
+int csm_attn_append(const void* qkv, void* kcache, void* vcache, void* out, int row, int pos0, int n, int H, int KV, int HD,
+                    int S_max, float scale, csm_stream_t stream);
 
 /* ---- K16 (RVQ part): Mimi split residual VQ behind generator.py:117,209 ------------------------------------------ */
 int csm_rvq_encode(const float* x, const float* codebooks, long long* codes, int T, int K, int C, int D, int n_semantic,

@@ -8,7 +8,12 @@ generate_stream() with chunk_frames 1, 2 and 4 against generate() on the same se
 the call to the first chunk on the host, total wall time and frames/s.  GEN_BATCH_SWEEP=1: generate_batch() at 1, 4, 8 and 16
 utterances from one process, one line each (aggregate frames/s, seconds per frame).  GEN_LORA_BANK=q_proj,v_proj (or all): decode
 frames/s with a different LoRA adapter per utterance (16 adapters, some rows without) against the same batch without adapters
-and against the same utterances one at a time with their adapter live as model.lora, alternated in one process."""
+and against the same utterances one at a time with their adapter live as model.lora, alternated in one process.
+GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
+through a Conversation (KV cache kept between turns) and statelessly (generate_stream with the accumulated Segment list - every
+turn encodes and prefills the whole history again), alternated in one process after a warm-up dialogue of each: per spoken turn the
+host time from the call to the first chunk (chunk_frames=2) and the turn's total; plus csm_attn_append alone next to the
+csm_attn_fwd launch that would recompute the whole sequence."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -304,7 +309,121 @@ def sweep_main():
               f"{dt / max(tot / nb, 1) * 1e3:.2f} ms per batch frame ({tot * 0.08 / dt:.2f}x real time aggregate)", flush=True)
 
 
+def attn_append_micro(dev, H=32, KV=8, HD=64, S_max=2048, iters=200):
+    """csm_attn_append at (n, pos0) against csm_attn_fwd at S = pos0 + n (CSM-1B backbone heads): device time per launch."""
+    for n, pos0 in ((64, 1024), (200, 1800)):
+        S = pos0 + n
+        qkv = torch.randn(S, (H + 2 * KV) * HD, device=dev).to(torch.bfloat16)
+        kc = torch.randn(1, KV, S_max, HD, device=dev).to(torch.bfloat16)
+        vc = torch.randn(1, KV, S_max, HD, device=dev).to(torch.bfloat16)
+        new = qkv[pos0:].contiguous()
+        o_app = torch.empty(n, H * HD, dtype=torch.bfloat16, device=dev)
+        o_fwd = torch.empty(S, H * HD, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(1, H, S, dtype=torch.float32, device=dev)
+        calls = {"csm_attn_append": lambda: ops.attn_append(new, kc, vc, o_app, 0, pos0, H, KV, HD),
+                 "csm_attn_fwd": lambda: ops.attn_fwd(qkv, o_fwd, lse, 1, S, H, KV, HD)}
+        us = {k: [] for k in calls}
+        for _ in range(5):                                       # alternated repeats; the first one also warms up
+            for name, f in calls.items():
+                for _ in range(20):
+                    f()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(iters):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                us[name].append(a.elapsed_time(b) * 1e3 / iters)
+        fl = 4.0 * n * (pos0 + (n + 1) / 2) * HD * H
+        print(f"attn micro n={n:3d} pos0={pos0:4d}: csm_attn_append {min(us['csm_attn_append']):6.1f} us "
+              f"({[round(x, 1) for x in us['csm_attn_append']]}; {fl / min(us['csm_attn_append']) / 1e6:.1f} TFLOP/s) vs csm_attn_fwd S={S} "
+              f"{min(us['csm_attn_fwd']):6.1f} us ({[round(x, 1) for x in us['csm_attn_fwd']]})")
+
+
+def conversation_main():
+    """GEN_CONVERSATION=1 (see the module docstring).  GEN_ROUNDS timed dialogues of each kind (default 5), alternated; the
+    first chunk counts as arrived when its samples are on the host."""
+    dev = "cuda:0"
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=make_codec(dev))
+    frames = int(os.environ.get("GEN_FRAMES", 63))
+    turns = int(os.environ.get("GEN_TURNS", 8))
+    rounds = int(os.environ.get("GEN_ROUNDS", 5))
+    ms = 80 * frames
+    g = torch.Generator(device=dev).manual_seed(1)
+    script = []
+    for t in range(turns):
+        if t % 2 == 0:
+            script.append(("say", t % 4 // 2, f"turn {t + 1}: the quick brown fox jumps over the lazy dog"))
+        else:
+            script.append(("hear", 1 - (t - 1) % 4 // 2, f"turn {t + 1}: and what did the dog do",
+                           torch.randn(5 * 24000, device=dev, generator=g) * 0.1))
+
+    def timed(stream):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        first, parts = None, []
+        for chunk in stream():
+            chunk.cpu()
+            if first is None:
+                first = time.perf_counter() - t0
+            parts.append(chunk)
+        return first, time.perf_counter() - t0, torch.cat(parts)
+
+    def dialogue(kind):
+        """One pass over the script; per turn (first chunk s or None, total s)."""
+        torch.manual_seed(0)
+        conv, segs, out = (gen.conversation() if kind == "conversation" else None), [], []
+        for item in script:
+            if item[0] == "say":
+                _, spk, text = item
+                if conv is not None:
+                    first, total, audio = timed(lambda: conv.generate_stream(text, spk, max_audio_length_ms=ms, chunk_frames=2))
+                else:
+                    first, total, audio = timed(lambda: gen.generate_stream(text, spk, segs, max_audio_length_ms=ms, chunk_frames=2))
+                    segs.append(Segment(spk, text, audio))
+                assert audio.numel() == frames * 1920, "a random-init model should not emit EOS"
+                out.append((first, total))
+            else:
+                _, spk, text, audio = item
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if conv is not None:
+                    conv.add(Segment(spk, text, audio))
+                    torch.cuda.synchronize()
+                else:
+                    segs.append(Segment(spk, text, audio))
+                out.append((None, time.perf_counter() - t0))
+        return out, (conv.tokens.shape[0] if conv is not None else None)
+
+    for kind in ("conversation", "stateless"):                      # warm-up dialogue of each: allocator, graph capture, every shape
+        dialogue(kind)
+    res = {"conversation": [], "stateless": []}
+    hist = None
+    for _ in range(rounds):
+        for kind in res:
+            out, n = dialogue(kind)
+            res[kind].append(out)
+            hist = n or hist
+    med = lambda xs: sorted(xs)[len(xs) // 2]                        # noqa: E731
+    print(f"GEN_CONVERSATION: {turns} turns, {frames} frames per spoken turn, chunk_frames=2, {rounds} alternated rounds; history at "
+          f"the end {hist} positions.  ms as median [min..max]")
+    for t, item in enumerate(script):
+        line = f"turn {t + 1} ({item[0]:4s})"
+        for kind in res:
+            tot = [r[t][1] * 1e3 for r in res[kind]]
+            if item[0] == "say":
+                fc = [r[t][0] * 1e3 for r in res[kind]]
+                line += f" | {kind}: first chunk {med(fc):7.1f} [{min(fc):6.1f}..{max(fc):6.1f}], total {med(tot):7.1f} [{min(tot):6.1f}..{max(tot):6.1f}]"
+            else:
+                line += f" | {kind}: add {med(tot):6.1f} [{min(tot):5.1f}..{max(tot):5.1f}]"
+        print(line)
+    attn_append_micro(dev)
+
+
 def main():
+    if os.environ.get("GEN_CONVERSATION") == "1":
+        return conversation_main()
     if os.environ.get("GEN_BATCH_SWEEP") == "1":
         return sweep_main()
     if os.environ.get("GEN_LORA_BANK"):
