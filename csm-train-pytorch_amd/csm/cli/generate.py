@@ -37,6 +37,9 @@ def parse_args(argv=None):
     p.add_argument("--chunk-frames", type=int, default=4, help="80-ms frames per streamed chunk (default: 4)")
     p.add_argument("--lora-adapter", type=str, default=None,
                    help="LoRA adapter file written by csm-finetune-lora (.safetensors with its _metadata.json), applied without merging")
+    p.add_argument("--decode-weights", type=str, choices=["bf16", "fp8"], default="bf16",
+                   help="weights streamed by the decode steps: bf16 (default) or fp8 (weight-only e4m3, one scale per output row; "
+                        "not with --lora-adapter)")
     p.add_argument("--next-text", type=str, action="append", default=None,
                    help="a further line, spoken after --text in the same conversation with the KV cache kept (repeatable)")
     p.add_argument("--next-speaker", type=int, action="append", default=None,
@@ -65,7 +68,8 @@ def build_context(args, sample_rate):
 def main(argv=None):
     args = parse_args(argv)
     speaker_id = VOICE_PRESETS[args.voice] if args.voice else args.speaker
-    generator = load_csm_1b(args.model_path, args.device, mimi_weights=args.mimi_weights, tokenizer_path=args.text_tokenizer)
+    extra = {} if args.decode_weights == "bf16" else {"decode_weights": args.decode_weights}     # (the default needs no word)
+    generator = load_csm_1b(args.model_path, args.device, mimi_weights=args.mimi_weights, tokenizer_path=args.text_tokenizer, **extra)
     context = build_context(args, generator.sample_rate)
     adapter = None
     if args.lora_adapter:

@@ -915,6 +915,29 @@ class _DecodeStack:
         self.lora, self.lora_scale, self.lt = None, 1.0, None
         # per-row adapters (attach_lora_rows): (row_adapter int32 [B], scale fp32 [A]) and the tensors the pointer tables name
         self.lora_rows, self.lora_keep = None, []
+        # FP8 mode (model.decode_weights = "fp8", attach_fp8): {weight name: (e4m3 codes uint8 [N, K], scale fp32 [N])}
+        self.w8 = None
+
+    def attach_fp8(self):
+        """Quantised copies of the layer products' weights (csm_quantize_rows_fp8), made from the current weights - the same
+        staleness rule as ``DecodeState.head_t``.  The depth decoder's fused attention + output projection at one utterance keeps
+        its bf16 weights (2 MB per launch, latency-bound: DESIGN.md section 4, 'FP8 weights'); CSM_FP8_FUSE_ATTN=0 runs it
+        unfused on FP8 weights instead (measurement only)."""
+        import os
+        st = self.stack
+        if self.fuse_attn and os.environ.get("CSM_FP8_FUSE_ATTN", "1") != "1":
+            self.fuse_attn = False
+        names = ["attn.qkv", "mlp.w13", "mlp.w2.weight"] + ([] if self.fuse_attn else ["attn.output_proj.weight"])
+        self.w8 = {f"layers.{i}.{n}": ops.quantize_rows_fp8(st.w(f"layers.{i}.{n}")) for i in range(st.c.num_layers) for n in names}
+
+    def weight_bytes(self):
+        """Bytes of layer-product weights one decode step of this stack streams (codes + scales in FP8 mode)."""
+        st, tot = self.stack, 0
+        for i in range(st.c.num_layers):
+            for n in ("attn.qkv", "attn.output_proj.weight", "mlp.w13", "mlp.w2.weight"):
+                q = self.w8.get(f"layers.{i}.{n}") if self.w8 is not None else None
+                tot += q[0].numel() + 4 * q[1].numel() if q is not None else 2 * st.w(f"layers.{i}.{n}").numel()
+        return tot
 
     def fill_from(self, acts, B, S):
         """Copy the post-RoPE K / V rows of a prefilled prompt into the caches."""
@@ -945,6 +968,9 @@ class _DecodeStack:
             if self.lora is not None and self.lora[i]:
                 cur, nxt = self._lora_layer(i, cur, nxt, table)
                 continue
+            if self.w8 is not None:
+                cur, nxt = self._fp8_layer(i, cur, nxt, table)
+                continue
             # five launches per layer (four in the depth decoder): the norms ride in the prologue of the following matrix-vector
             # product, RoPE and the cache append inside the attention kernel, SwiGLU in the epilogue of the w13 product
             ops.gemv_ex(cur, st.w(f"layers.{i}.attn.qkv"), self.qkv, norm_scale=st.w(f"layers.{i}.sa_norm.scale"), eps=c.norm_eps)
@@ -963,6 +989,22 @@ class _DecodeStack:
             return cur
         ops.rmsnorm_fwd(cur, st.w("norm.scale"), self.xf, None, c.norm_eps)
         return self.xf
+
+    def _fp8_layer(self, i, cur, nxt, table):
+        """``step``'s layer ``i`` on e4m3 weights: the same launches with csm_gemv_fp8w in place of csm_gemv_bf16(_ex)."""
+        st, c, q = self.stack, self.stack.c, self.w8
+        H, KV, hd = c.num_heads, c.num_kv_heads, c.head_dim
+        ops.gemv_fp8w(cur, *q[f"layers.{i}.attn.qkv"], self.qkv, norm_scale=st.w(f"layers.{i}.sa_norm.scale"), eps=c.norm_eps)
+        if self.fuse_attn:
+            ops.gemv_attn(self.qkv, self.k[i], self.v[i], self.pos, table, st.w(f"layers.{i}.attn.output_proj.weight"), self.h, cur,
+                          H, KV, hd, pos_host=self.pos_host)
+        else:
+            ops.attn_decode_rope(self.qkv, self.k[i], self.v[i], self.o, self.pos, table, H, KV, hd, pos_host=self.pos_host)
+            ops.gemv_fp8w(self.o, *q[f"layers.{i}.attn.output_proj.weight"], self.h, residual=cur)
+        ops.gemv_fp8w(self.h, *q[f"layers.{i}.mlp.w13"], self.act, norm_scale=st.w(f"layers.{i}.mlp_norm.scale"), eps=c.norm_eps,
+                      swiglu=True)
+        ops.gemv_fp8w(self.act, *q[f"layers.{i}.mlp.w2.weight"], nxt, residual=self.h)
+        return nxt, (self.xb if nxt is self.xa else self.xa)
 
     def _lora_product(self, G, x, W, y, **kw):
         """One product of a layer step: plain (``G`` None) or extended by a LoRA group - t = s x^ At, then the same product
@@ -1136,6 +1178,11 @@ class DecodeState:
             # (the K-extension kernels of live adapters take at most 4 rows: csm_gemv_bf16_kext, csm_lora_project_bf16)
             raise ValueError(f"generate with live (un-merged) LoRA adapters takes at most 4 sequences at a time (got {B}): "
                              "merge them first (merge_lora_weights) or decode at most 4 utterances")
+        self.decode_weights = getattr(m, "decode_weights", "bf16")
+        if self.decode_weights == "fp8" and (self.adapters is not None or (m.lora is not None and not m.lora.merged)):
+            raise ValueError('decode_weights = "fp8" with live (un-merged) LoRA adapters or a per-utterance adapter bank: the '
+                             'K-extension decode kernels are bf16-only - merge the adapters first (merge_lora_weights) or set '
+                             'model.decode_weights = "bf16"')
         self.e, self.B = engine, B
         dev = m.device
         self.bb = _DecodeStack(engine.backbone, B, m.bb.max_seq_len)
@@ -1152,6 +1199,10 @@ class DecodeState:
         # audio_head is stored [K-1][d'][V] (reference layout, a K-major matrix for x @ W); the decode path wants one
         # output row per wave, so it keeps a [K-1][V][d'] copy made from the current weights when the state is created
         self.head_t = m.block("audio_head.padded").transpose(1, 2).contiguous()
+        # FP8 mode: e4m3 copies + row scales of the layer products' weights, made here from the current weights like head_t
+        if self.decode_weights == "fp8":
+            self.bb.attach_fp8()
+            self.dc.attach_fp8()
         # live LoRA adapters ride on the decode products as K-extensions (merged ones are already in the weights)
         if self.adapters is not None:
             self.bb.attach_lora_rows(self.adapters)

@@ -304,9 +304,9 @@ class Generator:
 
 
 def load_csm_1b(ckpt_path: str = "ckpt.pt", device: str = "cuda", text_tokenizer=None, audio_tokenizer=None,
-                mimi_weights: str = None, tokenizer_path: str = None) -> Generator:
+                mimi_weights: str = None, tokenizer_path: str = None, decode_weights: str = "bf16") -> Generator:
     """Reference generator.py:221-244.  ``mimi_weights`` / ``tokenizer_path`` name local files for the two tokenizers the
-    reference pulls from the hub."""
+    reference pulls from the hub.  ``decode_weights``: "bf16" or "fp8" (``Model.decode_weights``: weight-only e4m3 decode)."""
     if audio_tokenizer is None and mimi_weights:
         from .codec import load_mimi
         audio_tokenizer = load_mimi(mimi_weights, device=device)
@@ -316,4 +316,5 @@ def load_csm_1b(ckpt_path: str = "ckpt.pt", device: str = "cuda", text_tokenizer
                      audio_vocab_size=2051, audio_num_codebooks=32)
     model = Model(args, device=device)
     model.load_state_dict(torch.load(ckpt_path, map_location="cpu", weights_only=False))
+    model.decode_weights = decode_weights
     return Generator(model, text_tokenizer=text_tokenizer, audio_tokenizer=audio_tokenizer)

@@ -417,6 +417,39 @@ def gemv_ex(x, W, y, residual=None, norm_scale=None, eps=1e-5, swiglu=False, row
     return y
 
 
+def quantize_rows_fp8(W, W8=None, scale=None):
+    """W bf16 [N, K] -> (W8 uint8 [N, K] of OCP e4m3fn codes, scale fp32 [N]): per row scale = max|w| / 448 (1.0 for an all-zero
+    row), code = e4m3fn(w / scale), round to nearest even, saturating (csm_quantize_rows_fp8; csm/quant.py restates the rule in
+    torch and agrees bit for bit).  Rows keep W's order."""
+    assert W.is_cuda and W.dtype == BF16 and W.dim() == 2 and W.stride(1) == 1, (W.dtype, W.shape, W.stride())
+    N, K = W.shape
+    if W8 is None:
+        W8 = torch.empty(N, (K + 15) // 16 * 16, dtype=torch.uint8, device=W.device)[:, :K]     # (16-byte aligned rows)
+    if scale is None:
+        scale = torch.empty(N, dtype=torch.float32, device=W.device)
+    assert W8.dtype == torch.uint8 and W8.shape == (N, K) and W8.stride(1) == 1 and scale.dtype == torch.float32 and scale.numel() == N
+    check(lib.csm_quantize_rows_fp8(W.data_ptr(), W8.data_ptr(), scale.data_ptr(), N, K, W.stride(0), W8.stride(0), _stream()),
+          "csm_quantize_rows_fp8")
+    return W8, scale
+
+
+def gemv_fp8w(x, W8, scale, y, residual=None, norm_scale=None, eps=1e-5, swiglu=False, row_index=None, row_offset=0):
+    """``gemv_ex`` with e4m3 weights and one fp32 scale per output row (``quantize_rows_fp8``): y[b][n] = epilogue(scale[n] *
+    sum_k x^[b][k] q[n][k]), bf16 activations, fp32 products and sum, the scale applied once after the reduction.  Same fusions,
+    same B <= 16 and the same bit-level invariants as the bf16 products; K % 16 == 0, 16-byte aligned weight rows."""
+    B = y.shape[0]
+    K = x.shape[1]
+    N = W8.shape[0]
+    assert W8.dtype == torch.uint8 and scale.dtype == torch.float32 and scale.numel() == N and scale.is_contiguous() and x.dtype == BF16
+    assert W8.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W8.stride(1) == 1 and y.stride(1) == 1
+    assert row_index is not None or x.shape[0] == B
+    assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
+    check(lib.csm_gemv_fp8w(x.data_ptr(), W8.data_ptr(), scale.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K, W8.stride(0),
+                            x.stride(0), y.stride(0), int(y.dtype == torch.float32), _ptr(norm_scale), float(eps), int(swiglu),
+                            _ptr(row_index), int(row_offset), _stream()), "csm_gemv_fp8w")
+    return y
+
+
 def lora_project(x, At, t, scale, norm_scale=None, eps=1e-5):
     """t[B, kx] = scale * x^ At (bf16), x^ = x or its RMSNorm (norm_scale): the extension operand of ``gemv_kext`` for a LoRA
     group whose At [K, kx] is read in place (training/lora.py)."""

@@ -176,10 +176,29 @@ class Model(nn.Module):
         self._fp32_source = None
         self.use_kv_cache = True                              # generate_frame: KV caches (False = prefix recompute)
         self.use_hip_graph = True                             # replay decode frames as one captured HIP graph
+        self._decode_weights = "bf16"                         # decode_weights: "bf16" | "fp8" (weight-only e4m3 decode steps)
         # which parameter groups receive weight gradients (freeze flags of trainer.prepare_optimizer / LoRA)
         self.trainable = {"backbone": True, "decoder": True, "embeddings": True, "other": True}
         if device is not None:
             self.to(device)
+
+    @property
+    def decode_weights(self) -> str:
+        """Weights the one-position decode steps stream: ``"bf16"`` (default) or ``"fp8"`` - OCP e4m3 codes with one fp32 scale per
+        output row for the layer products of both stacks (attn.qkv, attn.output_proj, mlp.w13, mlp.w2), quantised from the
+        current weights when a decode state is created; activations stay bf16, sums fp32.  Embeddings, projection and the heads
+        stay bf16, and so do training, prefill, ``DecodeState.append`` and the recompute path (``use_kv_cache = False``), which
+        ignores the mode.  Setting it drops the decode state and its captured graph.  Live (un-merged) LoRA adapters and
+        per-utterance adapter banks are refused in FP8 mode: merge first, or use bf16."""
+        return self._decode_weights
+
+    @decode_weights.setter
+    def decode_weights(self, value):
+        if value not in ("bf16", "fp8"):
+            raise ValueError(f'decode_weights must be "bf16" or "fp8" (got {value!r})')
+        if value != self._decode_weights:
+            self._decode_weights = value
+            self._decode_state = None
 
     # ------------------------------------------------------------------ layout
     def _plan(self):

@@ -229,6 +229,20 @@ int csm_gemv_bf16(const void* x, const void* W, void* y, const void* residual, i
 int csm_gemv_bf16_ex(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
                      int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index, int row_offset,
                      csm_stream_t stream);
+/* Weight-only FP8 decode (since ABI 3, additive).  csm_quantize_rows_fp8: W bf16 [N][ldw] -> W8 [N][ldw8] OCP e4m3fn codes (not
+ * fnuz) + scale fp32 [N]: per row amax = max |w|, scale = amax / 448 (a correctly rounded fp32 division; 1.0 for an all-zero row),
+ * code = e4m3fn(w / scale) rounded to nearest even and saturating at +-448 - finite weights never give a NaN code.  Rows keep W's
+ * order (interleaved gate/up rows and fused qkv rows need no special case).  K, ldw, ldw8 multiples of 8. */
+int csm_quantize_rows_fp8(const void* W, void* W8, void* scale, int N, int K, int ldw, int ldw8, csm_stream_t stream);
+/* csm_gemv_bf16_ex with the weight operand replaced by (W8, scale): y[b][n] = epilogue(scale[n] * sum_k x^[b][k] q[n][k]), bf16
+ * activations, products and sum in fp32, the scale applied once after the reduction and before the epilogue (SwiGLU: gate and
+ * up are each scaled and rounded to bf16 first).  Same fusions and the same invariants as the bf16 products: fixed reduction
+ * order, no atomics; B <= 4: row b bit-identical to the one-row launch; B = 5..16 (MFMA tiles on weights converted to bf16 in
+ * registers, exactly): a row's bits depend only on its own operands.  Needs K % 16 == 0, K <= 8192, ldw8 % 16 == 0, W8 and x
+ * 16-byte aligned. */
+int csm_gemv_fp8w(const void* x, const void* W8, const void* scale, void* y, const void* residual, int B, int N, int K, int ldw8,
+                  int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index, int row_offset,
+                  csm_stream_t stream);
 /* LoRA groups at decode time (since ABI 3, additive): t[b][0:kx] = scale * x^[b] . At (At [K][lda], a group's arena matrix),
  * rounded to bf16 once; x^ = x, or with norm_scale != NULL the RMSNorm of x exactly as csm_gemv_bf16_ex's prologue computes it.
  * B <= 4, kx a multiple of 8. */

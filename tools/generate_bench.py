@@ -9,7 +9,8 @@ the call to the first chunk on the host, total wall time and frames/s.  GEN_BATC
 utterances from one process, one line each (aggregate frames/s, seconds per frame).  GEN_LORA_BANK=q_proj,v_proj (or all): decode
 frames/s with a different LoRA adapter per utterance (16 adapters, some rows without) against the same batch without adapters
 and against the same utterances one at a time with their adapter live as model.lora, alternated in one process.
-GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
+GEN_FP8=1: decode frames/s with bf16 and with FP8 (weight-only e4m3) decode weights,
+alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in each mode.  GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
 through a Conversation (KV cache kept between turns) and statelessly (generate_stream with the accumulated Segment list - every
 turn encodes and prefills the whole history again), alternated in one process after a warm-up dialogue of each: per spoken turn the
 host time from the call to the first chunk (chunk_frames=2) and the turn's total; plus csm_attn_append alone next to the
@@ -238,6 +239,91 @@ def lora_bank_main(mods):
               f"(a) / (c) = {a / live1:.2f}x", flush=True)
 
 
+def fp8_main():
+    """GEN_FP8=1: CSM-1B random init, decode-loop frames/s (captured graph) with bf16 and with FP8 (weight-only e4m3) decode
+    weights on ONE model, alternated in one process (GEN_ROUNDS rounds, best of each) at B = GEN_BATCH_SIZES (default 1,4,16),
+    plus the bytes of layer-product weights a decode frame's steps stream in each mode.  GEN_FP8_TEACHER=1 adds the quantisation
+    loss on these RANDOM weights (teacher-forced, shared noise): relative error of codebook-0 logits, share of agreeing codes."""
+    dev = "cuda:0"
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    frames = int(os.environ.get("GEN_FRAMES", 100))
+    sizes = [int(v) for v in os.environ.get("GEN_BATCH_SIZES", "1,4,16").split(",")]
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    modes = os.environ.get("GEN_FP8_MODES", "bf16,fp8").split(",")     # (one mode alone: a profiler run of that mode)
+    res, nbytes = {}, {}
+    for _ in range(rounds):
+        for B in sizes:
+            for mode in modes:
+                model.decode_weights = mode
+                res.setdefault((mode, B), []).append(decode_fps_batch(model, B, None, frames))
+                st = model._decode_state
+                nbytes[mode] = (st.bb.weight_bytes(), st.dc.weight_bytes())
+    model.decode_weights = "bf16"
+    for mode in modes:
+        bb, dc = nbytes[mode]
+        print(f"GEN_FP8 decode weights {mode}: backbone {bb / 2**20:.1f} MiB + depth decoder {dc / 2**20:.1f} MiB per step "
+              f"(layer products; heads, embeddings and projection stay bf16 in both modes)", flush=True)
+    if len(modes) < 2:
+        for B in sizes:
+            print(f"GEN_FP8 B={B:2d}: {modes[0]} {[round(x, 1) for x in res[(modes[0], B)]]} frames/s aggregate", flush=True)
+        return
+    for B in sizes:
+        a, b = max(res[("fp8", B)]), max(res[("bf16", B)])
+        print(f"GEN_FP8 B={B:2d}: fp8 {[round(x, 1) for x in res[('fp8', B)]]} bf16 {[round(x, 1) for x in res[('bf16', B)]]} "
+              f"frames/s aggregate -> best fp8 {a:.1f} / bf16 {b:.1f} = {a / b:.3f}x", flush=True)
+    if os.environ.get("GEN_FP8_TEACHER") == "1":
+        fp8_loss(model)
+
+
+def fp8_loss(model, B=4, frames=8, prompt=40):
+    """Teacher-forced FP8 vs bf16 on the same (random) weights with shared noise: share of agreeing codes and the relative
+    error of the codebook-0 logits of every decode frame (max |diff| / max |bf16 logits|)."""
+    from csm.hip import ops
+    dev = model.device
+    K, V = model.args.audio_num_codebooks, model.args.audio_vocab_size
+    g = torch.Generator().manual_seed(0)
+    tok = torch.zeros(B, prompt, K + 1, dtype=torch.long)
+    tok[:, :, K] = torch.randint(0, model.args.text_vocab_size, (B, prompt), generator=g)
+    msk = torch.zeros(B, prompt, K + 1, dtype=torch.bool)
+    msk[:, :, K] = True
+    amask = torch.cat([torch.ones(B, K, dtype=torch.bool), torch.zeros(B, 1, dtype=torch.bool)], 1).unsqueeze(1)
+    eng = model.engine
+    body = eng._frame_tail_body
+    out = {}
+    for mode in ("bf16", "fp8"):
+        model.decode_weights = mode
+        model.setup_caches(B)
+        hs, fr = [], []
+        eng._frame_tail_body = lambda st, h, t, k: (hs.append(h.clone()), body(st, h, t, k))[1]
+        model.use_hip_graph = False
+        try:
+            t, mk, pos = tok, msk, torch.arange(prompt).unsqueeze(0).repeat(B, 1)
+            for step in range(frames):
+                gn = torch.Generator().manual_seed(100 + step)
+                noise = [torch.empty(B, V).exponential_(1, generator=gn) for _ in range(K)]
+                f = model.generate_frame(t.to(dev), mk.to(dev), pos.to(dev), 0.9, 50, noise=noise).cpu()
+                fr.append(f)
+                nxt = out["bf16"][0][step] if mode == "fp8" else f
+                t = torch.cat([nxt.long(), torch.zeros(B, 1, dtype=torch.long)], 1).unsqueeze(1)
+                mk, pos = amask, pos[:, -1:] + 1
+        finally:
+            model.use_hip_graph = True
+            del eng._frame_tail_body
+        out[mode] = (torch.stack(fr), hs)
+    model.decode_weights = "bf16"
+    agree = (out["bf16"][0] == out["fp8"][0]).float().mean().item()
+    agree0 = (out["bf16"][0][:, :, 0] == out["fp8"][0][:, :, 0]).float().mean().item()
+    rel = []
+    for hb, hf in zip(out["bf16"][1][1:], out["fp8"][1][1:]):
+        lg = [torch.empty(B, model.vocab_pad, dtype=torch.float32, device=dev) for _ in range(2)]
+        ops.gemv(hb, model.block("codebook0_head.padded"), lg[0])
+        ops.gemv(hf, model.block("codebook0_head.padded"), lg[1])
+        rel.append(((lg[0] - lg[1])[:, :V].abs().max() / lg[0][:, :V].abs().max()).item())
+    print(f"GEN_FP8 quantisation loss on RANDOM CSM-1B weights (B={B}, {frames} teacher-forced frames, shared noise): codes agree "
+          f"{agree:.1%} (codebook 0: {agree0:.1%}); codebook-0 logits of the decode frames: relative error max {max(rel):.3g}, "
+          f"mean {sum(rel) / len(rel):.3g}", flush=True)
+
+
 def stream_main():
     """GEN_STREAM=1: for each chunk size, generate() and generate_stream() alternate (GEN_ROUNDS rounds, same seed, so the
     same frames); the first chunk counts as arrived when its samples are on the host."""
@@ -426,6 +512,8 @@ def main():
         return conversation_main()
     if os.environ.get("GEN_BATCH_SWEEP") == "1":
         return sweep_main()
+    if os.environ.get("GEN_FP8") == "1":
+        return fp8_main()
     if os.environ.get("GEN_LORA_BANK"):
         return lora_bank_main(os.environ["GEN_LORA_BANK"])
     if os.environ.get("GEN_LORA"):
