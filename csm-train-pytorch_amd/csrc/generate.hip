@@ -1044,7 +1044,7 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict
     }
 }
 
-// one query position against the cache: block per (b, q-head); scores for <= 2048 keys live in LDS.
+// one query position against the cache: block per (b, q-head); the scores of all S_max <= 8192 keys live in LDS (the launcher sizes it).
 // table != NULL fuses what used to be two more launches per layer: the new position's q and k heads are rotated here
 // (torchtune RoPE on interleaved pairs, same arithmetic and bf16 rounding as rope_kernel), and the first q-head block of
 // every kv group appends the rotated k and the v of the new position to the caches.  Every block takes the new key /
@@ -1984,7 +1984,9 @@ extern "C" int csm_gemv_t_bf16(const void* x, const void* W, void* y, int B, int
 
 extern "C" int csm_kv_append(const void* qkv, void* kcache, void* vcache, const int* pos, int B, int H, int KV, int HD,
                              int S_max, int ld, hipStream_t stream) {
-    CSM_REQUIRE(qkv && kcache && vcache && pos && B > 0 && (HD & 7) == 0, "csm_kv_append: bad arguments");
+    CSM_REQUIRE(qkv && kcache && vcache && pos && B > 0 && H > 0 && KV > 0 && H % KV == 0 && (ld & 7) == 0, "csm_kv_append: bad arguments");
+    CSM_REQUIRE(HD == 64 || HD == 128, "csm_kv_append: head_dim %d unsupported", HD);            // (the shapes csm_attn_decode reads back)
+    CSM_REQUIRE(S_max >= 1 && S_max <= 8192, "csm_kv_append: S_max %d outside 1 .. 8192", S_max);
     hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)kcache, (bf16_t*)vcache, pos, H,
                        KV, HD, S_max, ld);
     CSM_CHECK_LAUNCH("csm_kv_append");
@@ -1993,9 +1995,9 @@ extern "C" int csm_kv_append(const void* qkv, void* kcache, void* vcache, const 
 
 static int attn_decode_launch(const void* qkv, void* kcache, void* vcache, void* out, const int* pos, const float* table, int B,
                               int H, int KV, int HD, int S_max, int ld, hipStream_t stream) {
-    CSM_REQUIRE(qkv && kcache && vcache && out && pos && B > 0 && H > 0 && KV > 0 && H % KV == 0, "csm_attn_decode: bad arguments");
+    CSM_REQUIRE(qkv && kcache && vcache && out && pos && B > 0 && H > 0 && KV > 0 && H % KV == 0 && (ld & 7) == 0, "csm_attn_decode: bad arguments");
     CSM_REQUIRE(HD == 64 || HD == 128, "csm_attn_decode: head_dim %d unsupported", HD);
-    CSM_REQUIRE(S_max <= 8192, "csm_attn_decode: S_max too large");
+    CSM_REQUIRE(S_max >= 1 && S_max <= 8192, "csm_attn_decode: S_max %d outside 1 .. 8192", S_max);
     const size_t lds = (size_t)(S_max + 16 + 6 * HD) * sizeof(float);
     const float scale = 1.f / sqrtf((float)HD);
     if (HD == 64)

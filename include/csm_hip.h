@@ -292,14 +292,18 @@ int csm_attn_decode_rope_at(const void* qkv, void* kcache, void* vcache, void* o
  * go out at once.  S_max <= 32, H * HD = 1024; bit-identical to csm_gemv_attn_bf16. */
 int csm_gemv_attn_at_bf16(const void* qkv, void* kcache, void* vcache, int pos, const float* rope_table, const void* W, void* y,
                           const void* residual, int N, int H, int KV, int HD, int S_max, int ldw, csm_stream_t stream);
+/* copies the (already rotated) new k and v heads of qkv[b] into row pos[b] of the caches; like csm_attn_decode, which reads them
+ * back: HD 64 or 128, H % KV == 0, 1 <= S_max <= 8192, ld % 8 == 0 - anything else returns 1 */
 int csm_kv_append(const void* qkv, void* kcache, void* vcache, const int* pos, int B, int H, int KV, int HD, int S_max, int ld,
                   csm_stream_t stream);
-/* out[b][h*HD..] = softmax(q . K[0..pos[b]]^T / sqrt(HD)) V   for the single query row in qkv[b] */
+/* out[b][h*HD..] = softmax(q . K[0..pos[b]]^T / sqrt(HD)) V   for the single query row in qkv[b].  HD 64 or 128, H % KV == 0,
+ * 1 <= S_max <= 8192 (the scores live in LDS), ld % 8 == 0 (16-byte loads from qkv + b * ld) - anything else returns 1 */
 int csm_attn_decode(const void* qkv, const void* kcache, const void* vcache, void* out, const int* pos, int B, int H, int KV,
                     int HD, int S_max, int ld, csm_stream_t stream);
 /* the same with what precedes it in a decode step fused in: q and the new k are rotated inside (table as for csm_rope,
  * position = pos[b]) and the new k / v are appended to the caches at pos[b] by the kernel itself - one launch instead of
- * csm_rope + csm_kv_append + csm_attn_decode. qkv is the UNROTATED fused projection row. */
+ * csm_rope + csm_kv_append + csm_attn_decode. qkv is the UNROTATED fused projection row.  The same shapes as csm_attn_decode
+ * (HD 64 / 128, H % KV == 0, 1 <= S_max <= 8192, ld % 8 == 0) and a non-null table; anything else returns 1. */
 int csm_attn_decode_rope(const void* qkv, void* kcache, void* vcache, void* out, const int* pos, const float* rope_table, int B,
                          int H, int KV, int HD, int S_max, int ld, csm_stream_t stream);
 /* n new positions pos0 .. pos0+n-1 of ONE sequence (batch row `row` of the caches) against what the cache already holds - a

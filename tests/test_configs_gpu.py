@@ -157,6 +157,7 @@ def test_config5_decode_kernels_at_csm1b_shapes_vs_oracle(dev):
         lg = torch.empty(B, 2112, dtype=torch.float32, device=dev)
         ops.gemv(x.to(dev), Wh.to(dev), lg)
         gclose("gemv head f32", lg, x.float() @ Wh.float().t(), 1e-4)
+    # (a spot check: tests/test_decode_attn_gpu.py is the thorough comparison of this family with a float64 reference)
     for H, KV, hd, S_max in ((32, 8, 64, 2048), (8, 2, 128, 2048), (8, 2, 128, 32)):
         B = 2
         table = O.rope_table(S_max, hd)

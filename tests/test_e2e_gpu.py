@@ -626,6 +626,7 @@ def test_decode_kernels_vs_oracle(dev):
     ops.gemv_t(x2.to(dev), Wt.to(dev), y2)
     gclose("gemv_t", y2, x2.float() @ Wt.float(), 1e-4)
     # cache attention for both head dims, ragged positions per batch row
+    # (a spot check: tests/test_decode_attn_gpu.py is the thorough comparison of this family with a float64 reference)
     for H, KV, hd in ((4, 2, 64), (2, 1, 128)):
         B, S_max = 2, 96
         qkv = torch.randn(B, (H + 2 * KV) * hd, generator=g).to(BF)
