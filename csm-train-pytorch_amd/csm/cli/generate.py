@@ -45,8 +45,10 @@ def parse_args(argv=None):
     p.add_argument("--next-speaker", type=int, action="append", default=None,
                    help="speaker ID of the corresponding --next-text (repeatable; default: the speaker of --text)")
     p.add_argument("--serve-file", type=str, default=None,
-                   help="JSON-lines file of utterances {\"text\", \"speaker\", \"adapter\"?: LoRA adapter file, \"seed\"?: int}: all are "
-                        "served as one running batch (Generator.serve) with the context of --context-*; one WAV per utterance, "
+                   help="JSON-lines file of utterances {\"text\", \"speaker\", \"adapter\"?: LoRA adapter file, \"seed\"?: int, "
+                        "\"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
+                        "--context-*; lines with the same conversation id are successive turns of one served conversation, in file "
+                        "order (KV cache kept between them; adapter and seed of its first line); one WAV per utterance, "
                         "<output stem>_<i>.wav with i = 0, 1, ... counting the file's non-empty lines")
     p.add_argument("--slots", type=int, default=16, help="--serve-file: utterances decoded at once (1..16, default 16)")
     args = p.parse_args(argv)
@@ -124,7 +126,8 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
 
 
 def read_serve_file(path):
-    """--serve-file: one JSON object per non-empty line -> [{"text", "speaker", "adapter", "seed"}]."""
+    """--serve-file: one JSON object per non-empty line -> [{"text", "speaker", "adapter", "seed"}], plus "conversation" (a
+    string) on the lines that carry that key."""
     import json
     lines = []
     with open(path) as f:
@@ -134,11 +137,13 @@ def read_serve_file(path):
             d = json.loads(raw)
             if not isinstance(d, dict) or not isinstance(d.get("text"), str):
                 raise ValueError(f"{path}:{i}: every line is a JSON object with a \"text\" string")
-            unknown = set(d) - {"text", "speaker", "adapter", "seed"}
+            unknown = set(d) - {"text", "speaker", "adapter", "seed", "conversation"}
             if unknown:
                 raise ValueError(f"{path}:{i}: unknown keys {sorted(unknown)}")
             lines.append({"text": d["text"], "speaker": int(d.get("speaker", 0)), "adapter": d.get("adapter"),
                           "seed": None if d.get("seed") is None else int(d["seed"])})
+            if d.get("conversation") is not None:
+                lines[-1]["conversation"] = str(d["conversation"])
     if not lines:
         raise ValueError(f"{path}: no utterances")
     return lines
@@ -146,8 +151,9 @@ def read_serve_file(path):
 
 def serve_to_wavs(generator, args, context, adapter=None):
     """--serve-file: every line is a request of one ``Generator.serve`` batch; adapter files are loaded once each, under their
-    path as name (--lora-adapter is the default for lines without one).  Utterance i (the i-th non-empty line, from 0) goes to
-    <output stem>_<i>.wav."""
+    path as name (--lora-adapter is the default for lines without one).  Lines with a "conversation" id are the turns of one
+    served conversation (``BatchServer.conversation``): its first line is queued with the rest, each later one when the turn
+    before it is done.  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav."""
     lines = read_serve_file(args.serve_file)
     for path in sorted({ln["adapter"] for ln in lines if ln["adapter"]}):
         generator.load_adapter(path, path)
@@ -156,14 +162,33 @@ def serve_to_wavs(generator, args, context, adapter=None):
     t0 = time.perf_counter()
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, temperature=args.temperature,
                              topk=args.topk)
-    reqs = [server.submit(ln["text"], ln["speaker"], context, adapter=ln["adapter"] or adapter, seed=ln["seed"],
-                          max_audio_length_ms=args.max_audio_length_ms) for ln in lines]
-    for req, _, done in server.run():
-        if done:
-            out = f"{stem}_{req.id}{ext or '.wav'}"
-            generator.save_wav(out, req.audio())
-            print(f"line {req.id}: {req.audio().numel() / generator.sample_rate:.2f} s -> {out} (after {time.perf_counter() - t0:.2f} s)")
-    print(f"{len(reqs)} utterances served in {time.perf_counter() - t0:.2f} s")
+    convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
+
+    def say(cid):
+        conv, todo = convs[cid]
+        i = todo.pop(0)
+        line_of[conv.say(lines[i]["text"], lines[i]["speaker"], max_audio_length_ms=args.max_audio_length_ms)] = (i, cid)
+
+    for i, ln in enumerate(lines):
+        cid = ln.get("conversation")
+        if cid is None:
+            line_of[server.submit(ln["text"], ln["speaker"], context, adapter=ln["adapter"] or adapter, seed=ln["seed"],
+                                  max_audio_length_ms=args.max_audio_length_ms)] = (i, None)
+        elif cid in convs:
+            convs[cid][1].append(i)
+        else:
+            convs[cid] = [server.conversation(context=context, adapter=ln["adapter"] or adapter, seed=ln["seed"]), [i]]
+            say(cid)
+    while server.queued or server.active:
+        for req, _, done in server.step():
+            if done:
+                i, cid = line_of[req]
+                out = f"{stem}_{i}{ext or '.wav'}"
+                generator.save_wav(out, req.audio())
+                print(f"line {i}: {req.audio().numel() / generator.sample_rate:.2f} s -> {out} (after {time.perf_counter() - t0:.2f} s)")
+                if cid is not None and convs[cid][1]:
+                    say(cid)
+    print(f"{len(lines)} utterances served in {time.perf_counter() - t0:.2f} s")
     return 0
 
 

@@ -120,9 +120,14 @@ class _Stack:
                 fuse_rope: bool = True, on_layer_start=None, append=None) -> torch.Tensor:
         """``append`` = (decode stack, batch row, pos0): the S rows are positions pos0 .. pos0+S-1 of the sequence whose earlier
         positions sit in that stack's KV caches (B = 1, ``pos`` given, nothing saved) - every layer's attention appends its K / V
-        rows to the caches and attends to them (``ops.attn_append``) instead of the from-scratch ``ops.attn_fwd``."""
+        rows to the caches and attends to them (``ops.attn_append``) instead of the from-scratch ``ops.attn_fwd``.
+        The ragged form ``append`` = (decode stack, rows, pos0s, ns) with three equally long lists of host integers stacks R <= 16
+        such segments, each against its own batch row: x holds ``sum(ns)`` rows, segment after segment, and ``pos`` their positions
+        (``ops.attn_append_rows``).  Its products are pinned to the kernel whose rows do not see each other (``pin``, ops.gemm), so a
+        segment's rows have the bits they would have in a forward of their own, whatever is stacked beside them."""
         c, dev = self.c, x.device
         M, d = x.shape
+        pin = append is not None and isinstance(append[1], (list, tuple))
         H, KV, hd, F = c.num_heads, c.num_kv_heads, c.head_dim, c.intermediate_dim
         table = self.m.rope_table(self.prefix)
         self.acts = []
@@ -142,17 +147,17 @@ class _Stack:
                 ops.linear_rope_fwd(xn, self.w(f"layers.{i}.attn.qkv"), qkv, table, S, hq + hk, hd)
             elif fused:
                 # the adapters' up-projections are extra k-steps of the same product, so the rotation still sees the sum
-                a["tx_attn_in"] = G.project(xn)
+                a["tx_attn_in"] = G.project(xn, pin=pin)
                 ops.gemm_kext(xn, self.w(f"layers.{i}.attn.qkv"), qkv, a["tx_attn_in"], G.Bx,
-                              rope=(table, S, hq + hk, hd) if rope_in_gemm else None)
+                              rope=(table, S, hq + hk, hd) if rope_in_gemm else None, pin=pin)
                 if not rope_in_gemm:
                     ops.rope(qkv, table, S, H + KV, hd, pos=pos)
             else:
-                ops.linear_fwd(xn, self.w(f"layers.{i}.attn.qkv"), qkv)
+                ops.linear_fwd(xn, self.w(f"layers.{i}.attn.qkv"), qkv, pin=pin)
                 for mod, lo_, hi_ in (("q_proj", 0, hq), ("k_proj", hq, hq + hk), ("v_proj", hq + hk, hq + 2 * hk)):
                     ad = self._lora(i, mod)
                     if ad is not None:
-                        a[f"t_{mod}"] = ad.forward(xn, qkv[:, lo_:hi_])
+                        a[f"t_{mod}"] = ad.forward(xn, qkv[:, lo_:hi_], pin=pin)
                 ops.rope(qkv, table, S, H + KV, hd, pos=pos)
             o = torch.empty(M, H * hd, dtype=BF16, device=dev)
             if append is None:
@@ -160,19 +165,23 @@ class _Stack:
                 ops.attn_fwd(qkv, o, lse, B, S, H, KV, hd)
             else:
                 assert B == 1 and pos is not None and not save
-                ds, row, pos0 = append
                 lse = None
-                ops.attn_append(qkv, ds.k[i], ds.v[i], o, row, pos0, H, KV, hd)
+                if pin:
+                    ds, rows, pos0s, ns = append
+                    ops.attn_append_rows(qkv, ds.k[i], ds.v[i], o, rows, pos0s, ns, H, KV, hd)
+                else:
+                    ds, row, pos0 = append
+                    ops.attn_append(qkv, ds.k[i], ds.v[i], o, row, pos0, H, KV, hd)
             h = torch.empty(M, d, dtype=BF16, device=dev)
             G, fused = self._group(i, "attn_out")
             if fused:
-                a["tx_attn_out"] = G.project(o)
-                ops.gemm_kext(o, self.w(f"layers.{i}.attn.output_proj.weight"), h, a["tx_attn_out"], G.Bx, R=x)
+                a["tx_attn_out"] = G.project(o, pin=pin)
+                ops.gemm_kext(o, self.w(f"layers.{i}.attn.output_proj.weight"), h, a["tx_attn_out"], G.Bx, R=x, pin=pin)
             else:
-                ops.linear_fwd(o, self.w(f"layers.{i}.attn.output_proj.weight"), h, residual=x)
+                ops.linear_fwd(o, self.w(f"layers.{i}.attn.output_proj.weight"), h, residual=x, pin=pin)
                 ad = self._lora(i, "output_proj")
                 if ad is not None:
-                    a["t_output_proj"] = ad.forward(o, h)
+                    a["t_output_proj"] = ad.forward(o, h, pin=pin)
             hn = torch.empty(M, d, dtype=BF16, device=dev)
             rstd2 = torch.empty(M, dtype=F32, device=dev)
             ops.rmsnorm_fwd(h, self.w(f"layers.{i}.mlp_norm.scale"), hn, rstd2, c.norm_eps)
@@ -181,11 +190,11 @@ class _Stack:
             ad1, ad3 = self._lora(i, "w1"), self._lora(i, "w3")
             G, fused = self._group(i, "mlp_in")
             if FUSE_SWIGLU and G is None:
-                ops.linear_swiglu_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, act)   # activation fused into the GEMM epilogue
+                ops.linear_swiglu_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, act, **ops._pin(pin))   # activation fused into the GEMM epilogue
             elif FUSE_SWIGLU and fused:
                 # adapters on w1 / w3: extra k-steps of the w13 product (Bx rows interleaved like w13), SwiGLU from the sum
-                a["tx_mlp_in"] = G.project(hn)
-                ops.gemm_kext(hn, self.w(f"layers.{i}.mlp.w13"), gu, a["tx_mlp_in"], G.Bx, swiglu_act=act)
+                a["tx_mlp_in"] = G.project(hn, pin=pin)
+                ops.gemm_kext(hn, self.w(f"layers.{i}.mlp.w13"), gu, a["tx_mlp_in"], G.Bx, swiglu_act=act, pin=pin)
             elif FUSE_SWIGLU and not any(ad is not None and ad.bias is not None for ad in (ad1, ad3)):
                 # (dropout: one mask per adapter) the adapters' (alpha/r) t B^T is written FIRST, for both at once -
                 # t13 = the adapters' projections side by side, as the group's Bx expects them - and the frozen product takes it
@@ -193,29 +202,29 @@ class _Stack:
                 rp = (ad1 or ad3).r
                 t13 = torch.zeros(M, G.kx, dtype=BF16, device=dev)
                 for j, (mod, ad) in enumerate(G.adapters.items()):
-                    a[f"t_{mod}"] = ad.project(hn, t13[:, j * rp:(j + 1) * rp])
-                ops.gemm(t13, G.Bx, gu, None, alpha=(ad1 or ad3).scaling)
-                ops.linear_swiglu_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, act, residual=gu)
+                    a[f"t_{mod}"] = ad.project(hn, t13[:, j * rp:(j + 1) * rp], pin=pin)
+                ops.gemm(t13, G.Bx, gu, None, alpha=(ad1 or ad3).scaling, **ops._pin(pin))
+                ops.linear_swiglu_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, act, residual=gu, **ops._pin(pin))
             else:
-                ops.linear_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu)
+                ops.linear_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, pin=pin)
                 if ad1 is not None or ad3 is not None:
                     gv = gu.view(M, F, 2)
                     for mod, col, ad in (("w1", 0, ad1), ("w3", 1, ad3)):
                         if ad is not None:
                             tmp = torch.zeros(M, F, dtype=BF16, device=dev)
-                            a[f"t_{mod}"] = ad.forward(hn, tmp)
+                            a[f"t_{mod}"] = ad.forward(hn, tmp, pin=pin)
                             gv[:, :, col] += tmp
                 ops.swiglu_fwd(gu, act)
             out = torch.empty(M, d, dtype=BF16, device=dev)
             G, fused = self._group(i, "mlp_out")
             if fused:
-                a["tx_mlp_out"] = G.project(act)
-                ops.gemm_kext(act, self.w(f"layers.{i}.mlp.w2.weight"), out, a["tx_mlp_out"], G.Bx, R=h)
+                a["tx_mlp_out"] = G.project(act, pin=pin)
+                ops.gemm_kext(act, self.w(f"layers.{i}.mlp.w2.weight"), out, a["tx_mlp_out"], G.Bx, R=h, pin=pin)
             else:
-                ops.linear_fwd(act, self.w(f"layers.{i}.mlp.w2.weight"), out, residual=h)
+                ops.linear_fwd(act, self.w(f"layers.{i}.mlp.w2.weight"), out, residual=h, pin=pin)
                 ad = self._lora(i, "w2")
                 if ad is not None:
-                    a["t_w2"] = ad.forward(act, out)
+                    a["t_w2"] = ad.forward(act, out, pin=pin)
             if save:
                 a.update(x=x, xn=xn, rstd1=rstd1, qkv=qkv, o=o, lse=lse, h=h, hn=hn, rstd2=rstd2, gu=gu, act=act)
                 self.acts.append(a)
@@ -899,8 +908,11 @@ class _DecodeStack:
         self.stack, self.B, self.s_max = stack, B, s_max
         H, KV, hd, F, d = c.num_heads, c.num_kv_heads, c.head_dim, c.intermediate_dim, c.embed_dim
         z = lambda *shape, dt=BF16: torch.empty(*shape, dtype=dt, device=dev)   # noqa: E731
-        self.k = [torch.zeros(B, KV, s_max, hd, dtype=BF16, device=dev) for _ in range(c.num_layers)]
-        self.v = [torch.zeros(B, KV, s_max, hd, dtype=BF16, device=dev) for _ in range(c.num_layers)]
+        # one allocation [layer, K | V, B, KV, s_max, hd]: a batch row's history in every layer is ONE strided slice of it
+        # (DecodeState.park_row / resume_row); k[i] / v[i] are the contiguous per-layer views the kernels take
+        self.kv = torch.zeros(c.num_layers, 2, B, KV, s_max, hd, dtype=BF16, device=dev)
+        self.k = [self.kv[i, 0] for i in range(c.num_layers)]
+        self.v = [self.kv[i, 1] for i in range(c.num_layers)]
         self.pos = torch.zeros(B, dtype=torch.int32, device=dev)
         self.xn, self.qkv, self.o, self.h, self.hn = z(B, d), z(B, c.qkv_dim), z(B, H * hd), z(B, d), z(B, d)
         self.gu, self.act, self.xa, self.xb, self.xf = z(B, 2 * F), z(B, F), z(B, d), z(B, d), z(B, d)
@@ -1294,6 +1306,85 @@ class DecodeState:
         self.cur = pos0 + n - 1
         return hidden[-1:].contiguous()
 
+    def append_rows(self, rows, tokens_list, masks_list):
+        """``append`` for rows of a multi-row state: feed each listed row b its new positions ([n_b, K+1] frames) after the
+        ``row_pos[b] + 1`` it holds - the next turns of conversations that share a running batch (csm/serving.py).  Segments whose
+        rows share a bank adapter (or have none) are stacked into ONE backbone forward (``_Stack.forward``, ragged ``append``:
+        the weights are walked once for all of them); rows with different adapters take one forward per adapter (``row_lora``
+        is one adapter per forward).  A row that holds nothing (``row_pos[b] == -1``) is refused: first turns go through
+        ``prefill_row``.  Returns the segments' last hidden rows [R, d] in the order of ``rows``.  A segment's bits do not depend
+        on what is stacked with it; one segment on a one-row state equals ``append``."""
+        e, m = self.e, self.e.m
+        rows = [int(b) for b in rows]
+        R = len(rows)
+        if not (1 <= R <= 16 and len(tokens_list) == R and len(masks_list) == R):
+            raise ValueError(f"append_rows takes 1..16 rows with one token and one mask tensor each (got {R} rows)")
+        if len(set(rows)) != R or any(not 0 <= b < self.B for b in rows):
+            raise ValueError(f"append_rows: rows must be distinct rows of 0..{self.B - 1}, got {rows}")
+        K1 = tokens_list[0].shape[-1]
+        tks = [t.reshape(-1, K1).to(device=m.device, dtype=torch.int64) for t in tokens_list]
+        mks = [k.reshape(-1, K1).to(device=m.device, dtype=torch.uint8) for k in masks_list]
+        held = [self.cur if self.B == 1 and self.row_pos[b] < 0 else self.row_pos[b] for b in rows]   # (prefill() keeps cur only)
+        ns, pos0s = [t.shape[0] for t in tks], [h + 1 for h in held]
+        for b, h, n in zip(rows, held, ns):
+            if h < 0:
+                raise RuntimeError(f"append_rows: row {b} holds nothing (a first turn goes through prefill_row)")
+            if n < 1:
+                raise ValueError("append_rows needs at least one position per row")
+            if h + 1 + n > m.bb.max_seq_len:
+                raise ValueError("sequence exceeds max_seq_len")
+        groups = {}                                              # adapter identity -> segment indices, in order
+        for j, b in enumerate(rows):
+            groups.setdefault(id(self.adapters[b]) if self.adapters is not None else None, []).append(j)
+        last = [None] * R
+        for idx in groups.values():
+            tk = torch.cat([tks[j] for j in idx], 0).contiguous()
+            mk = torch.cat([mks[j] for j in idx], 0).contiguous()
+            M = tk.shape[0]
+            h0 = torch.empty(M, m.bb.embed_dim, dtype=BF16, device=m.device)
+            ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
+            # (host integers only: one arange per segment)
+            pos = torch.cat([torch.arange(pos0s[j], pos0s[j] + ns[j], dtype=torch.int32, device=m.device) for j in idx])
+            seg = (self.bb, [rows[j] for j in idx], [pos0s[j] for j in idx], [ns[j] for j in idx])
+            with (row_lora(m, self.adapters[rows[idx[0]]]) if self.adapters is not None else generation_lora(m)):
+                hidden = e.backbone.forward(h0, 1, M, False, pos=pos, append=seg)
+            end = 0
+            for j in idx:
+                end += ns[j]
+                last[j] = hidden[end - 1]
+        for b, p0, n in zip(rows, pos0s, ns):
+            self.bb.pos[b] = p0 + n - 1
+            self.row_pos[b] = p0 + n - 1
+            self.cur = max(self.cur, p0 + n - 1)
+        return torch.stack(last).contiguous()
+
+    def park_row(self, b, length: int):
+        """The K / V of positions 0 .. length-1 of row ``b`` in every backbone layer, as one contiguous tensor
+        [layers, 2, KV, length, hd] (one strided copy of the stack's cache allocation) - what a conversation keeps while it holds
+        no slot.  The depth decoder's cache is per frame and needs nothing."""
+        b, length = int(b), int(length)
+        if not 0 <= b < self.B:
+            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        if not 1 <= length <= max(self.row_pos[b], self.cur if self.B == 1 else -1) + 1:
+            raise ValueError(f"park_row: {length} positions of row {b}, which holds {self.row_pos[b] + 1}")
+        return self.bb.kv[:, :, b, :, :length].contiguous()
+
+    def resume_row(self, b, parked):
+        """Copy a parked history (``park_row``, of this or another row, or of another state of the same model) into row ``b`` from
+        position 0 (one strided copy) and set the row's device position and host mirror to its last position."""
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        kv = self.bb.kv
+        length = parked.shape[3] if parked.dim() == 5 else -1
+        if parked.dim() != 5 or parked.shape[:3] != (kv.shape[0], 2, kv.shape[3]) or parked.shape[4] != kv.shape[5] or \
+                not 1 <= length <= kv.shape[4] or parked.dtype != kv.dtype:
+            raise ValueError(f"resume_row: {tuple(parked.shape)} {parked.dtype} is not a parked history of this model's backbone")
+        kv[:, :, b, :, :length].copy_(parked)
+        self.bb.pos[b] = length - 1
+        self.row_pos[b] = length - 1
+        self.cur = max(self.cur, length - 1)
+
     def truncate(self, length: int):
         """Forget every position from ``length`` on (1 <= length <= cur + 1): the device position and its host mirror move back
         to ``length - 1``.  Nothing is cleared - cache rows past the position are never read and the next step overwrites them."""
@@ -1351,15 +1442,24 @@ class DecodeState:
             if stack.lora_rows is not None:
                 stack.lora_rows[0][b:b + 1].fill_(idx)
 
-    def set_row_seed(self, b, seed):
+    def set_row_seed(self, b, seed, generator=None):
         """Row ``b``'s sampler noise comes from its own ``torch.Generator`` seeded with ``seed`` (``fill_noise``); None returns
-        the row to the whole-buffer draw from torch's global generator."""
-        if seed is None:
+        the row to the whole-buffer draw from torch's global generator.  ``generator``: an existing generator to draw from
+        instead of a fresh one - a conversation's, which travels with it from slot to slot (``new_row_generator``)."""
+        if generator is not None:
+            self.row_gen[b] = generator
+        elif seed is None:
             self.row_gen.pop(b, None)
         else:
             g = torch.Generator(device=self.noise_buf.device)
             g.manual_seed(int(seed))
             self.row_gen[b] = g
+
+    def new_row_generator(self, seed):
+        """A generator of the kind ``set_row_seed`` makes, for a caller that keeps it across rows (``set_row_seed(generator=)``)."""
+        g = torch.Generator(device=self.noise_buf.device)
+        g.manual_seed(int(seed))
+        return g
 
     def set_active(self, rows):
         """The rows that advance in the following ``serve_frame`` calls; the others idle: their position is pinned (to 0, then the

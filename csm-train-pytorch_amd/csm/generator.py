@@ -288,7 +288,9 @@ class Generator:
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
         chunk by chunk and leave at their own EOS - and ``server.run()`` iterates until all are done.  Temperature and top-k
-        belong to the server.  It takes over the model's caches like any ``generate*`` call (open streams and older servers are
+        belong to the server.  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
+        speaker)`` queues its next turn as a request, ``conv.add(Segment)`` is the other party's turn; its KV history is parked
+        between turns and resumed into any free slot, so more conversations than slots can be open.  It takes over the model's caches like any ``generate*`` call (open streams and older servers are
         invalidated) and binds the adapters loaded so far: load adapters first."""
         from .serving import BatchServer
         return BatchServer(self, slots, chunk_frames, temperature, topk)

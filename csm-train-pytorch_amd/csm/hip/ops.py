@@ -2,6 +2,7 @@
 
 PyTorch is plumbing here (device memory, streams); every arithmetic op is a hand-written gfx950 kernel.
 """
+import ctypes
 import math
 from typing import Optional
 
@@ -26,8 +27,16 @@ def _mat(t: torch.Tensor, dtype=BF16):
     return t.data_ptr(), t.shape[0], t.shape[1], t.stride(0)
 
 
-def gemm(A, B, C, R=None, transA=False, transB=False, alpha=1.0, batch=1, sA=0, sB=0, sC=0, sR=0):
-    """C[M,N] = alpha * opA(A) . opB(B)^T (+ R).  A: [M,K] (or [K,M] if transA); B: [N,K] (or [K,N] if transB)."""
+def _pin(pin):
+    """The keyword for a pinned call, nothing otherwise: ``gemm`` / ``linear_swiglu_fwd`` may be wrapped by a timer that knows
+    their positional arguments only (bench.py), and an un-pinned call must look the way it always did."""
+    return {"pin": True} if pin else {}
+
+
+def gemm(A, B, C, R=None, transA=False, transB=False, alpha=1.0, batch=1, sA=0, sB=0, sC=0, sR=0, pin=False):
+    """C[M,N] = alpha * opA(A) . opB(B)^T (+ R).  A: [M,K] (or [K,M] if transA); B: [N,K] (or [K,N] if transB).
+    ``pin`` (this call only; bf16 output, one batch): the 128x128 kernel whatever M is, so that a row's bits do not depend on the
+    other rows of the launch (``csm_gemm_bf16_pinned``)."""
     pa, a0, a1, lda = _mat(A)
     pb, b0, b1, ldb = _mat(B)
     M, K = (a1, a0) if transA else (a0, a1)
@@ -40,12 +49,17 @@ def gemm(A, B, C, R=None, transA=False, transB=False, alpha=1.0, batch=1, sA=0, 
     if R is not None:
         pr, r0, r1, ldr = _mat(R)
         assert (r0, r1) == (M, N)
+    if pin:
+        assert not out_f32 and batch == 1
+        check(lib.csm_gemm_bf16_pinned(pa, pb, pc, pr, M, N, K, lda, ldb, ldc, ldr, int(transA), int(transB), float(alpha), None, None,
+                                       0, 0, None, None, 0, 0, 0, _stream()), "csm_gemm_bf16_pinned")
+        return C
     check(lib.csm_gemm_bf16(pa, pb, pc, pr, M, N, K, lda, ldb, ldc, ldr, int(transA), int(transB), int(out_f32),
                             float(alpha), batch, sA, sB, sC, sR, _stream()), "csm_gemm_bf16")
     return C
 
 
-def linear_swiglu_fwd(x, w13, gu, act, residual=None):
+def linear_swiglu_fwd(x, w13, gu, act, residual=None, pin=False):
     """gu[M,2F] = x w13^T (+ residual) with gate/up interleaved, act[M,F] = silu(gate)*up, one GEMM launch.
     ``residual`` [M,2F] (may be ``gu`` itself) is how LoRA adapters on w1 / w3 join: their product is written first."""
     pa, M, K, lda = _mat(x)
@@ -53,6 +67,10 @@ def linear_swiglu_fwd(x, w13, gu, act, residual=None):
     assert K == Kb and gu.shape == (M, N) and act.shape == (M, N // 2) and gu.is_contiguous() and act.is_contiguous()
     pr, ldr = (None, 0) if residual is None else (residual.data_ptr(), residual.stride(0))
     assert residual is None or (residual.shape == (M, N) and residual.stride(1) == 1 and residual.dtype == BF16)
+    if pin:                                                   # (see gemm)
+        check(lib.csm_gemm_bf16_pinned(pa, pb, gu.data_ptr(), pr, M, N, K, lda, ldb, N, ldr, 0, 0, 1.0, None, None, 0, 1, None,
+                                       act.data_ptr(), N // 2, 0, 0, _stream()), "csm_gemm_bf16_pinned(swiglu fwd)")
+        return
     check(lib.csm_gemm_bf16_ex(pa, pb, gu.data_ptr(), pr, M, N, K, lda, ldb, N, ldr, 0, 0, 0, 1.0, 1, 0, 0, 0, 0, 1, None,
                                act.data_ptr(), N // 2, _stream()), "csm_gemm_bf16_ex(swiglu fwd)")
 
@@ -77,7 +95,7 @@ def linear_rope_fwd(x, w, out, table, S, n_rope_cols, head_dim):
     return out
 
 
-def gemm_kext(A, B, C, xA, xB, R=None, transB=False, rope=None, swiglu_act=None, swiglu_bwd_gu=None):
+def gemm_kext(A, B, C, xA, xB, R=None, transB=False, rope=None, swiglu_act=None, swiglu_bwd_gu=None, pin=False):
     """C[M,N] = A . opB(B)^T + xA[M,kx] . xB[N,kx]^T (+ R): a frozen projection with its LoRA adapters as extra k-steps of the
     same product.  ``rope`` = (table, S, n_rope_cols, head_dim), ``swiglu_act`` = act[M,N/2] or ``swiglu_bwd_gu`` = gate/up [M,2N]
     (then C = d(gate/up) [M,2N]) select the fused epilogues, which see the sum."""
@@ -101,26 +119,30 @@ def gemm_kext(A, B, C, xA, xB, R=None, transB=False, rope=None, swiglu_act=None,
     elif swiglu_bwd_gu is not None:      # the product is d(act) [M,N]; C = d(gate/up) [M,2N] from gate/up [M,2N]
         assert swiglu_bwd_gu.shape == (M, 2 * N) and swiglu_bwd_gu.is_contiguous() and C.is_contiguous() and R is None
         epi, aux_in, ld_aux = 2, swiglu_bwd_gu.data_ptr(), 2 * N
+    if pin:                                                   # (see gemm)
+        check(lib.csm_gemm_bf16_pinned(pa, pb, C.data_ptr(), pr, M, N, K, lda, ldb, C.stride(0), ldr, 0, int(transB), 1.0, xA.data_ptr(),
+                                       xB.data_ptr(), kx, epi, aux_in, aux_out, ld_aux, rc, hd, _stream()), "csm_gemm_bf16_pinned(kext)")
+        return C
     check(lib.csm_gemm_bf16_kext(pa, pb, C.data_ptr(), pr, M, N, K, lda, ldb, C.stride(0), ldr, 0, int(transB), xA.data_ptr(),
                                  xB.data_ptr(), kx, epi, aux_in, aux_out, ld_aux, rc, hd, _stream()), "csm_gemm_bf16_kext")
     return C
 
 
-def skinny_nt(x, wt, out, alpha=1.0):
+def skinny_nt(x, wt, out, alpha=1.0, pin=False):
     """out[M,N] = alpha * x[M,K] wt[N,K]^T for N in (32, 64): the bandwidth-shaped product of a LoRA group (falls back to the
     GEMM for other widths)."""
     pa, M, K, lda = _mat(x)
     pb, N, Kb, ldb = _mat(wt)
     assert K == Kb and out.shape == (M, N) and out.dtype == BF16 and out.stride(1) == 1
     if N not in (32, 64) or K % 128:
-        return gemm(x, wt, out, None, False, False, alpha)
+        return gemm(x, wt, out, None, False, False, alpha, **_pin(pin))
     check(lib.csm_skinny_nt_bf16(pa, pb, out.data_ptr(), M, N, K, lda, ldb, out.stride(0), float(alpha), _stream()), "csm_skinny_nt_bf16")
     return out
 
 
-def linear_fwd(x, w, out, residual=None, alpha=1.0):
+def linear_fwd(x, w, out, residual=None, alpha=1.0, pin=False):
     """out[M,N] = x[M,K] w[N,K]^T (+ residual)."""
-    return gemm(x, w, out, residual, False, False, alpha)
+    return gemm(x, w, out, residual, False, False, alpha, **_pin(pin))
 
 
 def linear_dx(dy, w, out, residual=None, alpha=1.0):
@@ -580,6 +602,29 @@ def attn_append(qkv, kcache, vcache, out, row, pos0, H, KV, HD):
         raise CsmHipError(f"csm_attn_append failed (code 1): batch row {row} outside the caches ({B} rows)")
     check(lib.csm_attn_append(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), int(row), int(pos0), n, H, KV, HD,
                               S_max, 1.0 / math.sqrt(HD), _stream()), "csm_attn_append")
+    return out
+
+
+def attn_append_rows(qkv, kcache, vcache, out, rows, pos0s, ns, H, KV, HD):
+    """``attn_append`` for R <= 16 segments in one launch: segment r is ``ns[r]`` new positions from ``pos0s[r]`` of the sequence
+    in batch row ``rows[r]`` of the caches, its q / k / v the next ``ns[r]`` rows of the stacked ``qkv`` [sum ns, ...].  ``rows``,
+    ``pos0s`` and ``ns`` are host integers: they travel in the kernel arguments.  Every row has the bits of a one-segment
+    ``attn_append`` of its segment."""
+    B, _, S_max, _ = kcache.shape
+    rows, pos0s, ns = [int(x) for x in rows], [int(x) for x in pos0s], [int(x) for x in ns]
+    R, M = len(rows), qkv.shape[0]
+    assert qkv.is_contiguous() and out.is_contiguous() and kcache.is_contiguous() and vcache.is_contiguous()
+    assert qkv.shape == (M, (H + 2 * KV) * HD) and out.shape == (M, H * HD) and vcache.shape == kcache.shape == (B, KV, S_max, HD)
+    if not (len(pos0s) == len(ns) == R):
+        raise CsmHipError(f"csm_attn_append_rows failed (code 1): {R} rows, {len(pos0s)} positions and {len(ns)} lengths")
+    for r in rows:
+        if not 0 <= r < B:
+            raise CsmHipError(f"csm_attn_append_rows failed (code 1): batch row {r} outside the caches ({B} rows)")
+    if 1 <= R <= 16 and all(n >= 1 for n in ns) and sum(ns) != M:
+        raise CsmHipError(f"csm_attn_append_rows failed (code 1): the segments hold {sum(ns)} positions, qkv has {M} rows")
+    arr = ctypes.c_int * max(R, 1)
+    check(lib.csm_attn_append_rows(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), arr(*rows), arr(*pos0s),
+                                   arr(*ns), R, H, KV, HD, S_max, 1.0 / math.sqrt(HD), _stream()), "csm_attn_append_rows")
     return out
 
 

@@ -16,15 +16,32 @@ One ``step()`` makes one chunk of ``chunk_frames`` frames for every request in a
 A request with a ``seed`` draws its sampler noise from its own generator (``DecodeState.fill_noise``), so its codes and audio do
 not depend on its slot, its neighbours or when it joined.
 
-Limitations: a slot holds one utterance, not a multi-turn conversation (``DecodeState.append`` is one-row); a join stalls the
-other rows for one whole prefill (no chunked prefill); the context audio of a request is Mimi-encoded at ``submit``, one segment
-at a time; adapters added to the Generator after ``serve()`` are unknown to the server (the state binds the bank at creation).
+Multi-turn conversations (``BatchServer.conversation`` -> ``ServedConversation``) outlive their slot.  A conversation holds a
+slot only while it speaks: at the end of the chunk in which its turn ended the K / V of its history positions are parked
+(``DecodeState.park_row``: one copy, base + kept frames - what the row sampled after EOS or after its length limit is not
+history) and the slot is free again; its next turn is admitted like any request into ANY free slot, where the parked history is
+copied back (``resume_row``) and only what the cache lacks - the last frame(s) of its own turn, the EOS frame, the other party's
+``add``ed turns, the new line's text - is fed.  All turns resumed at one chunk boundary are fed by ONE ``DecodeState.append_rows``
+(one walk over the backbone's weights; ``csm_attn_append_rows``), after the prefills of plain requests and first turns and before
+the one frame tail that gives every joiner its first frame.  So more conversations than slots can be open at once, and a turn's
+time to its first chunk depends on the new line, not on the length of the dialogue.
+An idle row's position is pinned to 0 and the frame writes a zero token's K / V at position 1 of that row: harmless for a row
+that is free, fatal for a history.  A row held by a conversation is therefore never idled: where a plain request at its length
+limit idles for the rest of the chunk, a conversation's row keeps sampling to the chunk's end and the extra frames are cut from
+the audio and from the parked length, as frames after EOS are - which is why ``say`` asks for ``chunk_frames - 1`` positions of
+headroom beyond ``max_audio_frames``.  A conversation's ``seed`` gives it one generator for its whole life, which moves only
+when the conversation samples a frame and travels with it from slot to slot.
+
+Limitations: a join stalls the other rows for one whole prefill or append (no chunked prefill); the context audio of a request
+and a conversation's ``add``ed turns are Mimi-encoded at ``submit`` / ``add``, one segment at a time; adapters added to the
+Generator after ``serve()`` are unknown to the server (the state binds the bank at creation).
 """
 from collections import deque
 from typing import Iterator, List, Optional, Tuple
 
 import torch
 
+from .conversation import OVERFLOW
 from .engine import DecodeState
 
 
@@ -41,6 +58,8 @@ class Request:
         self._tokens, self._mask, self._device = tokens, mask, device
         self._sampled = 0                        # frames sampled / handed out so far
         self._emitted = 0
+        self._conv: Optional["ServedConversation"] = None     # the conversation this is a turn of (tokens / mask: what it feeds)
+        self._base = 0                           # a turn: positions the cache holds once the feed is in
 
     def audio(self) -> torch.Tensor:
         """The audio so far (all of it once ``done``): the chunks concatenated."""
@@ -51,6 +70,121 @@ class Request:
         if not self._codes:
             return torch.zeros(self._tokens.shape[-1] - 1, 0, dtype=torch.long, device=self._device)
         return torch.cat(self._codes, 1)
+
+
+class ServedConversation:
+    """``BatchServer.conversation(...)``: one dialogue served turn by turn (see the module docstring).  ``tokens`` / ``mask`` /
+    ``cached`` mean what they mean on ``Conversation`` and the history has its layout: per turn the text frames, the audio frames,
+    one all-zero EOS frame; a spoken turn's frames are the sampled codes; the EOS frame always enters with the next feed."""
+
+    def __init__(self, server, context, adapter, seed, on_overflow):
+        if on_overflow not in OVERFLOW:
+            raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
+        self._srv, self._gen = server, server._gen
+        self.adapter, self.seed, self._on_overflow = adapter, seed, on_overflow
+        K1 = server._K + 1
+        self._tokens = torch.zeros(0, K1, dtype=torch.long, device=self._gen.device)
+        self._mask = torch.zeros(0, K1, dtype=torch.bool, device=self._gen.device)
+        self._turns: List[int] = []              # lengths of the turns that make up the history
+        self._cached = 0
+        self._parked = None                      # DecodeState.park_row of the ``cached`` leading positions, while it holds no slot
+        self._noise = None                       # its generator (made at the first admission: lives on the state's device)
+        self._open: Optional[Request] = None
+        self.closed = False
+        for seg in context:
+            self.add(seg)
+
+    @property
+    def tokens(self) -> torch.Tensor:
+        return self._tokens
+
+    @property
+    def mask(self) -> torch.Tensor:
+        return self._mask
+
+    @property
+    def cached(self) -> int:
+        return self._cached
+
+    def _idle(self, what):
+        self._srv._check()
+        if self.closed:
+            raise RuntimeError(f"{what}: this conversation was closed")
+        if self._open is not None and not self._open.done:
+            raise RuntimeError(f"{what}: this conversation's turn (request {self._open.id}) is still open - one turn at a time")
+
+    @torch.inference_mode()
+    def add(self, segment) -> None:
+        """The other party's turn: tokenised and Mimi-encoded here, once; it enters the cache with the next ``say``."""
+        self._idle("add")
+        t, m = self._gen._tokenize_segment(segment)
+        self._push(t.long(), m.bool())
+
+    def _push(self, t, m):
+        self._tokens = torch.cat([self._tokens, t.to(self._tokens.device)], 0)
+        self._mask = torch.cat([self._mask, m.to(self._mask.device)], 0)
+        self._turns.append(t.shape[0])
+
+    def _fit(self, n_new: int, max_audio_frames: int):
+        """``Conversation._fit``: the reference's length rule on history + new text; ``drop_oldest`` drops whole leading turns
+        until it holds and what is kept is prefilled again (the parked cache is dropped with them)."""
+        limit = self._srv._model.bb.max_seq_len - max_audio_frames
+        if self._tokens.shape[0] + n_new < limit:
+            return
+        drop, left = 0, self._tokens.shape[0]
+        if self._on_overflow == "drop_oldest":
+            while drop < len(self._turns) and left + n_new >= limit:
+                left -= self._turns[drop]
+                drop += 1
+        if left + n_new >= limit:
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
+        cut = self._tokens.shape[0] - left
+        self._tokens, self._mask, self._turns = self._tokens[cut:], self._mask[cut:], self._turns[drop:]
+        self._cached, self._parked = 0, None
+
+    @torch.inference_mode()
+    def say(self, text: str, speaker: int, max_audio_length_ms: float = 90_000) -> Request:
+        """Queue the next spoken turn; its audio streams through ``step()`` / ``run()`` like any request's.  The length rule
+        counts ``chunk_frames - 1`` frames beyond ``max_audio_length_ms``: a conversation's row samples to the end of its last
+        chunk (module docstring), and that must fit the cache - it raises here, not in ``step``."""
+        self._idle("say")
+        srv = self._srv
+        max_audio_frames = int(max_audio_length_ms / 80)
+        if max_audio_frames < 1:
+            raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
+        tt, tm = self._gen._tokenize_text_segment(text, speaker)
+        self._fit(tt.shape[0], max_audio_frames + srv.chunk_frames - 1)
+        feed_t = torch.cat([self._tokens[self._cached:], tt.long().to(self._tokens.device)], 0)
+        feed_m = torch.cat([self._mask[self._cached:], tm.bool().to(self._mask.device)], 0)
+        self._push(tt.long(), tm.bool())
+        req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device)
+        req._conv, req._base = self, self._tokens.shape[0]
+        srv._next_id += 1
+        srv._queue.append(req)
+        self._open = req
+        return req
+
+    def _end_turn(self, req: Request, state, b: int):
+        """The turn has ended in slot ``b`` (``BatchServer.step``): the history gets the kept frames and one EOS frame, the cache
+        its history positions only - base + the kept frames that were fed back - which are parked."""
+        K = self._srv._K
+        k = req._emitted
+        frames = torch.zeros(k + 1, K + 1, dtype=torch.long, device=self._tokens.device)
+        if k:
+            frames[:k, :K] = req.codes().t()
+        fmask = torch.zeros(k + 1, K + 1, dtype=torch.bool, device=self._mask.device)
+        fmask[:, :K] = True
+        self._tokens = torch.cat([self._tokens, frames], 0)
+        self._mask = torch.cat([self._mask, fmask], 0)
+        self._turns[-1] += k + 1
+        # positions base .. base + sampled - 2 hold the frames that were fed back (the last one sampled never was)
+        self._cached = req._base + min(req._sampled - 1, k)
+        self._parked = state.park_row(b, self._cached)
+
+    def close(self) -> None:
+        """Drop the parked cache (the history stays readable)."""
+        self._idle("close")
+        self._parked, self._cached, self.closed = None, 0, True
 
 
 class BatchServer:
@@ -114,6 +248,16 @@ class BatchServer:
         self._queue.append(req)
         return req
 
+    def conversation(self, context=(), adapter: Optional[str] = None, seed: Optional[int] = None,
+                     on_overflow: str = "error") -> ServedConversation:
+        """A multi-turn dialogue on this server: ``conv.say(text, speaker, max_audio_length_ms)`` queues its next spoken turn (a
+        ``Request``), ``conv.add(Segment)`` is the other party's turn, ``conv.close()`` drops its parked cache.  ``adapter`` and
+        ``seed`` hold for the whole conversation; ``on_overflow`` as for ``Generator.conversation``."""
+        self._check()
+        if adapter is not None and adapter not in self._bank:
+            raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})")
+        return ServedConversation(self, list(context), adapter, seed, on_overflow)
+
     @property
     def queued(self) -> int:
         return len(self._queue)
@@ -136,25 +280,44 @@ class BatchServer:
         return out
 
     def _admit(self):
-        """Queued requests into free slots: prefill each, then one frame tail for all of them.  Returns (their slots, [slots, K])."""
-        st, joined = self._state, []
+        """Queued requests into free slots: plain requests and first turns are prefilled one by one, the turns of conversations
+        with a parked cache are resumed and fed by ONE ``append_rows``, then one frame tail for all of them.  Returns (their
+        slots, [slots, K])."""
+        st, joined, resumed, hs = self._state, [], [], {}
         for b in range(self.slots):
             if not self._queue:
                 break
             if self._rows[b] is not None:
                 continue
             req = self._queue.popleft()
+            conv = req._conv
             st.set_row_adapter(b, self._bank[req.adapter] if req.adapter is not None else None)
-            st.set_row_seed(b, req.seed)
-            h = st.prefill_row(b, req._tokens, req._mask)
-            if self._last_h is None:
-                self._last_h = torch.zeros(self.slots, h.shape[-1], dtype=h.dtype, device=h.device)
-            self._last_h[b] = h
+            if conv is not None and conv.seed is not None:
+                if conv._noise is None:
+                    conv._noise = st.new_row_generator(conv.seed)
+                st.set_row_seed(b, None, generator=conv._noise)
+            else:
+                st.set_row_seed(b, req.seed)
+            if conv is not None and conv._parked is not None:
+                st.resume_row(b, conv._parked)
+                conv._parked = None
+                resumed.append(b)
+            else:
+                hs[b] = st.prefill_row(b, req._tokens, req._mask)
+            if conv is not None:
+                conv._cached = req._base
             self._codec.open(b)
             req.slot, self._rows[b] = b, req
             joined.append(b)
         if not joined:
             return joined, None
+        if resumed:
+            h = st.append_rows(resumed, [self._rows[b]._tokens for b in resumed], [self._rows[b]._mask for b in resumed])
+            hs.update({b: h[j] for j, b in enumerate(resumed)})
+        for b, h in hs.items():
+            if self._last_h is None:
+                self._last_h = torch.zeros(self.slots, h.shape[-1], dtype=h.dtype, device=h.device)
+            self._last_h[b] = h
         first = st.serve_first(self._last_h, joined, self.temperature, self.topk)
         for b in joined:
             self._tok[b, 0, :self._K] = first[b]
@@ -182,7 +345,8 @@ class BatchServer:
         frames = [first]
         held = running + joined
         for _ in range(n - 1):
-            rows = [b for b in held if self._rows[b]._sampled < self._rows[b].max_audio_frames]
+            # (a conversation's row is never idled: an idle frame would overwrite position 1 of its history - module docstring)
+            rows = [b for b in held if self._rows[b]._conv is not None or self._rows[b]._sampled < self._rows[b].max_audio_frames]
             frames.append(self._frame(rows) if rows else frames[-1])
         chunk = torch.stack(frames, 2).long()                                        # [slots, K, n]
         allz = (chunk == 0).all(dim=1).cpu()                                         # the chunk's one host look
@@ -211,6 +375,8 @@ class BatchServer:
             else:
                 part = torch.zeros(0, device=self._gen.device)
             if done[b]:
+                if req._conv is not None:
+                    req._conv._end_turn(req, self._state, b)
                 req.done, req.slot, self._rows[b] = True, None, None
                 self._state.set_row_seed(b, None)
             out.append((req, part, done[b]))

@@ -85,7 +85,7 @@ class LoRAAdapter:
             return x
         return ops.dropout_bf16(x, torch.empty(x.shape, dtype=BF16, device=x.device), self.dropout, self._draw)
 
-    def project(self, x: torch.Tensor, t: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def project(self, x: torch.Tensor, t: Optional[torch.Tensor] = None, pin: bool = False) -> torch.Tensor:
         """t = drop(x) A^T  [M, r] (draws this forward's dropout mask); ``t`` may be a column block of a wider buffer."""
         self._draw = None
         if self.dropout > 0 and self.state.training:
@@ -93,14 +93,14 @@ class LoRAAdapter:
             self._draw = (self.seed * 0x9E3779B1 + self.state.draws * 0x85EBCA77) & (2 ** 63 - 1)
         if t is None:
             t = torch.empty(x.shape[0], self.r, dtype=BF16, device=x.device)
-        ops.gemm(self._dropped(x), self.At, t, None, False, True)
+        ops.gemm(self._dropped(x), self.At, t, None, False, True, **ops._pin(pin))
         return t
 
-    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, y: torch.Tensor, pin: bool = False) -> torch.Tensor:
         """y += scaling * (drop(x) A^T) B^T (+ bias); returns t = drop(x) A^T (kept for the backward).  The second
         product accumulates into the frozen projection's output in its GEMM epilogue (C = R + alpha * acc, R = C = y)."""
-        t = self.project(x)
-        ops.gemm(t, self.B, y, y, alpha=self.scaling)
+        t = self.project(x, pin=pin)                 # (pin: ops.gemm - rows that must not see each other, engine append_rows)
+        ops.gemm(t, self.B, y, y, alpha=self.scaling, **ops._pin(pin))
         if self.bias is not None:
             ops.bias_add_bf16(y, self.bias)
         return t
@@ -136,13 +136,13 @@ class LoRAGroup:
         return all(ad.bias is None and not (ad.dropout > 0 and self.state.training) for ad in self.adapters.values())
 
     # ---- the fused path (engine): forward / backward of "frozen projection + group" -----------------------------
-    def project(self, x):
+    def project(self, x, pin=False):
         """tx = s x At  [M, KX]: the extension operand of the forward GEMM (kept for the backward)."""
         tx = torch.empty(x.shape[0], self.kx, dtype=BF16, device=x.device)
         if self.AtT is not None:
-            ops.skinny_nt(x, self.AtT, tx, alpha=self.state.scaling)
+            ops.skinny_nt(x, self.AtT, tx, alpha=self.state.scaling, pin=pin)
         else:
-            ops.gemm(x, self.At, tx, None, False, True, alpha=self.state.scaling)
+            ops.gemm(x, self.At, tx, None, False, True, alpha=self.state.scaling, **ops._pin(pin))
         return tx
 
     def backward(self, x, dy, tx):

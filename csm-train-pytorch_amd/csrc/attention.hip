@@ -712,18 +712,19 @@ extern "C" int csm_attn_bwd_rope(const void* qkv, const void* out, const void* d
 // element order inside an MFMA is a function of the key's index in its block, a row of an MFMA tile does not see the other rows,
 // and a key above a row's position enters as p = exp2(-inf) = +0 exactly: a fully masked block leaves m, l and O as they were
 // (alpha = exp2(0) = 1), so the number of blocks a tile's waves walk - which does depend on the tile's last row - cannot show.
+// The body below is one tile (16 queries of one kv head) of one segment; both entry points run it: attn_append_kernel (one
+// segment per launch) and attn_append_rows_kernel (up to 16 segments, each against its own cache row).  kc / vc are the caches of
+// the segment's batch row, qkv / out start at the segment's first row.
 template <int REP, int KS>
-__global__ __launch_bounds__(64 * REP * KS) void attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
-                                                                      bf16_t* __restrict__ vc, bf16_t* __restrict__ out, int pos0,
-                                                                      int n, int H, int KV, int S_max, float scale) {
+__device__ __forceinline__ void attn_append_tile(char* __restrict__ smem, const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
+                                                 bf16_t* __restrict__ vc, bf16_t* __restrict__ out, int pos0, int n, int H, int KV,
+                                                 int S_max, float scale, int tile, int kvh) {
     constexpr int HD = 64, NKS = 2, NDT = 4, NT = 64 * REP * KS, ST = 64 * REP;      // ST = threads that stage one split's V block
     using I = Img<HD>;
     static_assert((KS - 1) * REP * 18 * 64 * 4 <= KS * 2 * I::BYTES, "the partials reuse the V images");
-    __shared__ __attribute__((aligned(16))) char smem[KS * 2 * I::BYTES];
     const int lane = threadIdx.x & 63, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int hh = wave % REP, ks = wave / REP;
-    const int tile = gridDim.x - 1 - blockIdx.x, kvh = blockIdx.y;              // the tiles with the most keys start first
     const int h = kvh * REP + hh;
     const int ld = (H + 2 * KV) * HD;
     const int last_new = pos0 + n - 1;
@@ -909,6 +910,51 @@ __global__ __launch_bounds__(64 * REP * KS) void attn_append_kernel(const bf16_t
     }
 }
 
+template <int REP, int KS>
+__global__ __launch_bounds__(64 * REP * KS) void attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
+                                                                      bf16_t* __restrict__ vc, bf16_t* __restrict__ out, int pos0,
+                                                                      int n, int H, int KV, int S_max, float scale) {
+    __shared__ __attribute__((aligned(16))) char smem[KS * 2 * Img<64>::BYTES];
+    // the tiles with the most keys start first
+    attn_append_tile<REP, KS>(smem, qkv, kc, vc, out, pos0, n, H, KV, S_max, scale, gridDim.x - 1 - blockIdx.x, blockIdx.y);
+}
+
+// Ragged form: R <= 16 segments in one launch (the next turns of several conversations that share a running batch).  Segment r
+// is n[r] new positions from pos0[r] of the sequence in batch row row[r] of the caches; its q / k / v are rows off[r] ..
+// off[r]+n[r]-1 of the stacked qkv and it writes the same rows of out.  The table travels by value in the kernel arguments (no
+// device table, no copy).  Grid x = sum of the segments' tiles: a workgroup finds its segment by walking the table with its
+// block index - scalar work, the same for every lane.  No two segments name the same cache row (checked on the host), so the
+// one-segment kernel's rule still holds: no workgroup reads a cache row another one is writing.
+struct AppendRows {
+    int row[16];    // batch row of the caches
+    int pos0[16];   // first new position
+    int n[16];      // new positions (0 from R on)
+    int off[16];    // first row of the segment in qkv / out
+};
+
+template <int REP, int KS>
+__global__ __launch_bounds__(64 * REP * KS) void attn_append_rows_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
+                                                                           bf16_t* __restrict__ vc, bf16_t* __restrict__ out,
+                                                                           AppendRows a, int H, int KV, int S_max, float scale) {
+    __shared__ __attribute__((aligned(16))) char smem[KS * 2 * Img<64>::BYTES];
+    int t = blockIdx.x, row = 0, pos0 = 0, n = 0, off = 0, tile = 0;
+    bool found = false;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int nt = (a.n[r] + 15) >> 4;
+        if (!found && t < nt) {
+            row = a.row[r]; pos0 = a.pos0[r]; n = a.n[r]; off = a.off[r];
+            tile = nt - 1 - t;                                                  // within a segment: most keys first
+            found = true;
+        }
+        if (!found) t -= nt;
+    }
+    if (!found) return;                                                         // (the grid is exactly the tiles: not reached)
+    const size_t crow = (size_t)row * KV * S_max * 64;
+    attn_append_tile<REP, KS>(smem, qkv + (size_t)off * (H + 2 * KV) * 64, kc + crow, vc + crow, out + (size_t)off * H * 64, pos0, n,
+                              H, KV, S_max, scale, tile, blockIdx.y);
+}
+
 extern "C" int csm_attn_append(const void* qkv, void* kcache, void* vcache, void* out, int row, int pos0, int n, int H, int KV,
                                int HD, int S_max, float scale, hipStream_t stream) {
     CSM_REQUIRE(qkv && kcache && vcache && out, "csm_attn_append: null pointer");
@@ -927,5 +973,35 @@ extern "C" int csm_attn_append(const void* qkv, void* kcache, void* vcache, void
     if (rep == 4) L(4); else if (rep == 2) L(2); else L(1);
 #undef L
     CSM_CHECK_LAUNCH("csm_attn_append");
+    return 0;
+}
+
+extern "C" int csm_attn_append_rows(const void* qkv, void* kcache, void* vcache, void* out, const int* rows, const int* pos0,
+                                    const int* n, int R, int H, int KV, int HD, int S_max, float scale, hipStream_t stream) {
+    CSM_REQUIRE(qkv && kcache && vcache && out && rows && pos0 && n, "csm_attn_append_rows: null pointer");
+    CSM_REQUIRE(R >= 1 && R <= 16, "csm_attn_append_rows: %d segments (1 to 16)", R);
+    CSM_REQUIRE(H > 0 && KV > 0 && H % KV == 0 && S_max > 0, "csm_attn_append_rows: bad shape H=%d KV=%d S_max=%d", H, KV, S_max);
+    CSM_REQUIRE(HD == 64, "csm_attn_append_rows: head_dim %d unsupported (64)", HD);
+    const int rep = H / KV;
+    CSM_REQUIRE(rep == 1 || rep == 2 || rep == 4, "csm_attn_append_rows: %d query heads per kv head unsupported (1, 2 or 4)", rep);
+    AppendRows a = {};
+    long long tiles = 0, off = 0;
+    for (int r = 0; r < R; ++r) {
+        CSM_REQUIRE(rows[r] >= 0, "csm_attn_append_rows: segment %d: batch row %d", r, rows[r]);
+        CSM_REQUIRE(n[r] >= 1, "csm_attn_append_rows: segment %d: n = %d new positions (at least 1)", r, n[r]);
+        CSM_REQUIRE(pos0[r] >= 0 && (long long)pos0[r] + n[r] <= S_max,
+                    "csm_attn_append_rows: segment %d: positions %d .. %lld outside the cache (%d rows)", r, pos0[r],
+                    (long long)pos0[r] + n[r] - 1, S_max);
+        for (int q = 0; q < r; ++q)
+            CSM_REQUIRE(rows[q] != rows[r], "csm_attn_append_rows: batch row %d appears in two segments (%d and %d)", rows[r], q, r);
+        a.row[r] = rows[r]; a.pos0[r] = pos0[r]; a.n[r] = n[r]; a.off[r] = (int)off;
+        off += n[r];
+        tiles += (n[r] + 15) / 16;
+    }
+    const dim3 grid((unsigned)tiles, KV);
+#define L(REP) hipLaunchKernelGGL((attn_append_rows_kernel<REP, 2>), grid, dim3(64 * REP * 2), 0, stream, (const bf16_t*)qkv, (bf16_t*)kcache, (bf16_t*)vcache, (bf16_t*)out, a, H, KV, S_max, scale)
+    if (rep == 4) L(4); else if (rep == 2) L(2); else L(1);
+#undef L
+    CSM_CHECK_LAUNCH("csm_attn_append_rows");
     return 0;
 }

@@ -212,10 +212,10 @@ __global__ __launch_bounds__(256) void skinny_nt_kernel(const bf16_t* __restrict
 int g_gemm_variant = 2;   // 0 register staging, 1 LDS-DMA 128x128, 2 auto (256x256 where it fills the chip), 3 force 256x256
 
 template <int TA, int TB>
-int launch(const GemmArgs& g, int out_f32, int batch, hipStream_t stream) {
+int launch(const GemmArgs& g, int out_f32, int batch, hipStream_t stream, int pin = 0) {
     dim3 grid(g.tiles_m * g.tiles_n, 1, batch), block(256);
     const size_t lds = 4 * TILE_BYTES;
-    const bool glds = g_gemm_variant >= 1 && (g.K % BK) == 0 && g.M >= 8 && g.N >= 8;
+    const bool glds = (pin || g_gemm_variant >= 1) && (g.K % BK) == 0 && g.M >= 8 && g.N >= 8;
     g_last_gemm_kernel = glds ? CSM_KNAME("gemm_kernel", TA, TB, out_f32, ", true") : CSM_KNAME("gemm_kernel", TA, TB, out_f32, ", false");
     if (glds) {
         if (out_f32) hipLaunchKernelGGL((gemm_kernel<TA, TB, float, true>), grid, block, lds, stream, g);
@@ -292,7 +292,9 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* R, i
                          int ldb, int ldc, int ldr, int transA, int transB, int out_f32, float alpha, int batch,
                          long long strideA, long long strideB, long long strideC, long long strideR, int epilogue,
                          const void* aux_in, void* aux_out, int ld_aux, hipStream_t stream, int epi_p0, int epi_p1,
-                         const void* xA = nullptr, const void* xB = nullptr, int kx = 0) {
+                         const void* xA = nullptr, const void* xB = nullptr, int kx = 0, int pin = 0) {
+    // pin: this call runs the 128x128 kernel whatever M is (csm_gemm_bf16_pinned) - the auto choice below looks at M
+    const int variant = pin ? 1 : g_gemm_variant;
     CSM_REQUIRE(A && B && C, "csm_gemm_bf16: null operand");
     CSM_REQUIRE(M > 0 && N > 0 && K > 0 && batch > 0, "csm_gemm_bf16: bad shape M=%d N=%d K=%d batch=%d", M, N, K, batch);
     CSM_REQUIRE((lda & 7) == 0 && (ldb & 7) == 0, "csm_gemm_bf16: lda/ldb must be multiples of 8 (lda=%d ldb=%d)", lda, ldb);
@@ -310,10 +312,10 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* R, i
     CSM_REQUIRE(epilogue >= 0 && epilogue <= 3, "csm_gemm_bf16_ex: unknown epilogue %d", epilogue);
     // variant 4: the four-wave 256x256 kernel with the hand-scheduled K loop (gemm256w4.hip), where it applies
     // (the four-wave kernel beats the 128x128 one from 1.5 rounds of tiles on: fused q|k|v forward, 384 tiles, 97 vs 115 us)
-    if (((g_gemm_variant == 2 && g_gemm_w4 && prefer_256(M, N, K, batch, 0.70)) || (g_gemm_variant == 4 && K % 64 == 0 && M >= 8 && N >= 8)) && (kx == 0 || g_w4_kext))
+    if (((variant == 2 && g_gemm_w4 && prefer_256(M, N, K, batch, 0.70)) || (variant == 4 && K % 64 == 0 && M >= 8 && N >= 8)) && (kx == 0 || g_w4_kext))
         return csm_gemm256w4_launch(A, B, C, R, M, N, K, lda, ldb, ldc, ldr, transA, transB, out_f32, alpha, batch, strideA, strideB,
                                     strideC, strideR, epilogue, aux_in, aux_out, ld_aux, stream, epi_p0, epi_p1, xA, xB, kx);
-    if ((g_gemm_variant == 2 && prefer_256(M, N, K, batch)) || (g_gemm_variant >= 3 && K % 64 == 0 && M >= 8 && N >= 8))
+    if ((variant == 2 && prefer_256(M, N, K, batch)) || (variant >= 3 && K % 64 == 0 && M >= 8 && N >= 8))
         return csm_gemm256_launch(A, B, C, R, M, N, K, lda, ldb, ldc, ldr, transA, transB, out_f32, alpha, batch, strideA,
                                   strideB, strideC, strideR, epilogue, aux_in, aux_out, ld_aux, stream, epi_p0, epi_p1, xA, xB, kx);
     GemmArgs g;
@@ -325,10 +327,10 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* R, i
     g.alpha = alpha;
     g.epi_mode = epilogue; g.aux_in = (const bf16_t*)aux_in; g.aux_out = (bf16_t*)aux_out; g.ld_aux = ld_aux;
     g.tiles_m = (M + BM - 1) / BM; g.tiles_n = (N + BN - 1) / BN;
-    if (!transA && !transB) return launch<0, 0>(g, out_f32, batch, stream);
-    if (!transA && transB) return launch<0, 1>(g, out_f32, batch, stream);
-    if (transA && transB) return launch<1, 1>(g, out_f32, batch, stream);
-    return launch<1, 0>(g, out_f32, batch, stream);
+    if (!transA && !transB) return launch<0, 0>(g, out_f32, batch, stream, pin);
+    if (!transA && transB) return launch<0, 1>(g, out_f32, batch, stream, pin);
+    if (transA && transB) return launch<1, 1>(g, out_f32, batch, stream, pin);
+    return launch<1, 0>(g, out_f32, batch, stream, pin);
 }
 
 extern "C" int csm_gemm_bf16_ex(const void* A, const void* B, void* C, const void* R, int M, int N, int K, int lda,
@@ -371,6 +373,25 @@ extern "C" int csm_gemm_bf16_kext(const void* A, const void* B, void* C, const v
                     (N & 7) == 0 && (ldc & 7) == 0 && ((uintptr_t)C & 15) == 0 && !transA && !transB, "csm_gemm_bf16_kext: bad RoPE epilogue arguments");
     return gemm_dispatch(A, B, C, R, M, N, K, lda, ldb, ldc, ldr, transA, transB, 0, 1.f, 1, 0, 0, 0, 0, epilogue, aux_in, aux_out, ld_aux,
                          stream, epilogue == 3 ? rope_cols : 0, epilogue == 3 ? head_dim : 0, xA, xB, kx);
+}
+
+// csm_gemm_bf16 / _ex / _kext (bf16 output, one batch) with the kernel choice taken out of M's hands: always the 128x128 kernel,
+// in which an output row's bits depend on that row of A (and xA, R) and on B alone - not on M, that is not on which other rows
+// share the launch.  The auto choice moves to the 256x256 kernels once M fills the chip and those sum in another order, so a
+// caller that stacks the rows of several independent sequences into one product and promises each of them the bits it would
+// get alone (DecodeState.append_rows) pins its products here.  kx = 0: no K-extension (xA / xB ignored).  epilogue 0 .. 3 as in
+// csm_gemm_bf16_kext.
+extern "C" int csm_gemm_bf16_pinned(const void* A, const void* B, void* C, const void* R, int M, int N, int K, int lda, int ldb, int ldc,
+                                    int ldr, int transA, int transB, float alpha, const void* xA, const void* xB, int kx, int epilogue,
+                                    const void* aux_in, void* aux_out, int ld_aux, int rope_cols, int head_dim, hipStream_t stream) {
+    CSM_REQUIRE(kx >= 0 && kx % 32 == 0 && kx <= 256 && (kx == 0 || (xA && xB)), "csm_gemm_bf16_pinned: kx must be 0 or a multiple of 32 up to 256 with both operands (kx=%d)", kx);
+    CSM_REQUIRE(((uintptr_t)xA & 15) == 0 && ((uintptr_t)xB & 15) == 0, "csm_gemm_bf16_pinned: xA / xB must be 16-byte aligned");
+    CSM_REQUIRE(epilogue >= 0 && epilogue <= 3, "csm_gemm_bf16_pinned: epilogue must be 0..3");
+    if (epilogue == 3)
+        CSM_REQUIRE(aux_in && ld_aux > 0 && head_dim >= 8 && (head_dim & 7) == 0 && rope_cols >= 0 && rope_cols <= N && rope_cols % head_dim == 0 &&
+                    (N & 7) == 0 && (ldc & 7) == 0 && ((uintptr_t)C & 15) == 0 && !transA && !transB, "csm_gemm_bf16_pinned: bad RoPE epilogue arguments");
+    return gemm_dispatch(A, B, C, R, M, N, K, lda, ldb, ldc, ldr, transA, transB, 0, alpha, 1, 0, 0, 0, 0, epilogue, aux_in, aux_out, ld_aux,
+                         stream, epilogue == 3 ? rope_cols : 0, epilogue == 3 ? head_dim : 0, kx ? xA : nullptr, kx ? xB : nullptr, kx, 1);
 }
 
 // out[M][N] = alpha * X[M][K] . Wt[N][K]^T, N = 32 or 64, K a multiple of 128 - the skinny products of a LoRA group (reference

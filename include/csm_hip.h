@@ -66,6 +66,13 @@ int csm_gemm_bf16_rope(const void* A, const void* W, void* C, int M, int N, int 
 int csm_gemm_bf16_kext(const void* A, const void* B, void* C, const void* R, int M, int N, int K, int lda, int ldb, int ldc, int ldr,
                        int transA, int transB, const void* xA, const void* xB, int kx, int epilogue, const void* aux_in,
                        void* aux_out, int ld_aux, int rope_cols, int head_dim, csm_stream_t stream);
+/* csm_gemm_bf16 / _ex / _kext (bf16 output, one batch) on the 128x128 kernel whatever M is: there an output row's bits depend
+ * on that row of A (xA, R) and on B only, not on the other rows of the launch, where the automatic choice moves to the 256x256
+ * kernels (another summation order) once M fills the chip.  For callers that stack rows of independent sequences into one
+ * product and owe each the bits it gets alone (DecodeState.append_rows).  kx = 0: no K-extension; epilogue as in _kext. */
+int csm_gemm_bf16_pinned(const void* A, const void* B, void* C, const void* R, int M, int N, int K, int lda, int ldb, int ldc,
+                         int ldr, int transA, int transB, float alpha, const void* xA, const void* xB, int kx, int epilogue,
+                         const void* aux_in, void* aux_out, int ld_aux, int rope_cols, int head_dim, csm_stream_t stream);
 /* out[M][N] = alpha * X[M][K] Wt[N][K]^T for N = 32 or 64 and K % 128 == 0: the skinny products of a LoRA group (x A^T and dy B of
  * reference src/csm/mlx/components/lora.py:85-105 with the group's ranks side by side), read-once bandwidth kernel. */
 int csm_skinny_nt_bf16(const void* X, const void* Wt, void* out, int M, int N, int K, int ldx, int ldw, int ldo, float alpha,
@@ -315,6 +322,15 @@ int csm_attn_decode_rope(const void* qkv, void* kcache, void* vcache, void* out,
  * The number of batch rows of the caches is not an argument: `row` < B is the caller's to check (csm/hip/ops.py does). */
 int csm_attn_append(const void* qkv, void* kcache, void* vcache, void* out, int row, int pos0, int n, int H, int KV, int HD,
                     int S_max, float scale, csm_stream_t stream);
+/* The ragged form: R (1 .. 16) segments in ONE launch.  Segment r is n[r] >= 1 new positions from pos0[r] of the sequence in
+ * batch row rows[r] of the caches; its q / k / v are rows off[r] .. off[r]+n[r]-1 of the stacked qkv [sum n][(H+2KV)*HD], off[r] =
+ * n[0] + .. + n[r-1], and it writes the same rows of out [sum n][H*HD] and its K / V into its own cache row.  rows / pos0 / n are
+ * HOST arrays of R ints: they travel by value in the kernel arguments (no device table, no copy, no synchronisation).  The tile
+ * body is csm_attn_append's, so every output row and cache row has the bits the same segment gets from a csm_attn_append launch
+ * of its own.  Returns 1 (nothing launched) for a null pointer, R outside 1 .. 16, n[r] < 1, positions outside the cache,
+ * HD != 64, H / KV not in {1, 2, 4}, a negative row or a cache row named by two segments; rows[r] < B is the caller's to check. */
+int csm_attn_append_rows(const void* qkv, void* kcache, void* vcache, void* out, const int* rows, const int* pos0, const int* n, int R,
+                         int H, int KV, int HD, int S_max, float scale, csm_stream_t stream);
 
 /* ---- K16 (RVQ part): Mimi split residual VQ behind generator.py:117,209 ------------------------------------------ */
 int csm_rvq_encode(const float* x, const float* codebooks, long long* codes, int T, int K, int C, int D, int n_semantic,

@@ -11,7 +11,9 @@ frames/s with a different LoRA adapter per utterance (16 adapters, some rows wit
 and against the same utterances one at a time with their adapter live as model.lora, alternated in one process.
 GEN_FP8=1: decode frames/s with bf16 and with FP8 (weight-only e4m3) decode weights,
 alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in each mode.  GEN_SERVE=1: the running batch (Generator.serve): rows-codec step against single steps, the server step at
-16 rows, the join stall (serve_main).  GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
+16 rows, the join stall (serve_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
+time to the first chunk of turns 1 / 3 / 5 against stateless submits, one append_rows against one-row calls, park / resume, aggregate
+frames/s (serve_conv_main).  GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
 through a Conversation (KV cache kept between turns) and statelessly (generate_stream with the accumulated Segment list - every
 turn encodes and prefills the whole history again), alternated in one process after a warm-up dialogue of each: per spoken turn the
 host time from the call to the first chunk (chunk_frames=2) and the turn's total; plus csm_attn_append alone next to the
@@ -623,7 +625,146 @@ def serve_main():
           f"in {dt:.3f} s -> {tot / dt:.1f} frames/s aggregate (Mimi encode, prefills, streaming decode included)", flush=True)
 
 
+def serve_conv_main():
+    """GEN_SERVE_CONV=1: conversations on the running batch (BatchServer.conversation) on CSM-1B random init - 16 slots,
+    chunk_frames 4, 16 conversations of 6 turns: odd turns spoken (GEN_FRAMES frames, default 24), even turns 5 s of the other
+    party's audio (Mimi-encoded at ``add``, outside the timed steps).  All 16 turns of a round are admitted at one chunk boundary.
+    (a) host time from the step() that admits turn 1 / 3 / 5 of all 16 conversations to their first chunk on the host, next to
+        the same turns submitted statelessly (``submit`` with the accumulated segments as context, Mimi-encoded at submit) on the
+        same server in the same job; GEN_ROUNDS dialogues (default 3) after one warm-up dialogue, min / median / max;
+    (b) one append_rows over J = 1, 2, 4, 8, 16 segments of turn 5's feed length against J one-row append_rows calls;
+    (c) park_row / resume_row at the history lengths reached after turns 1, 3, 5;
+    (d) aggregate frames/s of the whole dialogue (all steps and the adds' Mimi encodes)."""
+    dev = "cuda:0"
+    NC, n = 16, 4
+    frames = int(os.environ.get("GEN_FRAMES", 24))
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    ms = 80 * frames
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=make_codec(dev))
+    srv = gen.serve(slots=NC, chunk_frames=n)
+    g = torch.Generator(device=dev).manual_seed(1)
+    heard = [torch.randn(5 * 24000, device=dev, generator=g) * 0.1 for _ in range(3)]
+    say = lambda t: (t % 4 // 2, f"turn {t + 1}: the quick brown fox jumps over the lazy dog")          # noqa: E731
+    med = lambda xs: sorted(xs)[len(xs) // 2]                                                           # noqa: E731
+    fmt = lambda xs: f"{med(xs):7.1f} [{min(xs):6.1f}..{max(xs):6.1f}]"                                 # noqa: E731
+
+    def admit_and_finish(reqs):
+        """The step that admits ``reqs`` timed to their first chunk on the host, then the rest of the turn."""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = srv.step()
+        torch.cat([a for _, a, _ in out]).cpu()
+        first = time.perf_counter() - t0
+        assert srv.last_join_rows == len(reqs) and len(out) == len(reqs)
+        while srv.active:
+            srv.step()
+        assert all(r.done and r.codes().shape[1] == frames for r in reqs), "a random-init model should not emit EOS"
+        return first * 1e3
+
+    def dialogue():
+        convs = [srv.conversation(seed=i) for i in range(NC)]
+        segs = [[] for _ in range(NC)]
+        first, cached, fed, feed = {}, {}, {}, None
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for t in range(6):
+            if t % 2 == 0:
+                spk, text = say(t)
+                reqs = [c.say(text, spk, max_audio_length_ms=ms) for c in convs]
+                feed = [(r._tokens, r._mask) for r in reqs]
+                fed[t] = feed[0][0].shape[0]
+                first[t] = admit_and_finish(reqs)
+                cached[t] = convs[0].cached
+                for i, r in enumerate(reqs):
+                    segs[i].append(Segment(spk, text, r.audio()))
+            else:
+                for i, c in enumerate(convs):
+                    seg = Segment(1 - (t - 1) % 4 // 2, f"turn {t + 1}: and what did the dog do", heard[t // 2])
+                    c.add(seg)
+                    segs[i].append(seg)
+        torch.cuda.synchronize()
+        return dict(first=first, cached=cached, fed=fed, feed=feed, total=time.perf_counter() - t0, convs=convs, segs=segs)
+
+    def stateless(segs, t):
+        spk, text = say(t)
+        reqs = [srv.submit(text, spk, segs[i][:t], seed=i, max_audio_length_ms=ms) for i in range(NC)]
+        return admit_and_finish(reqs), reqs[0]._tokens.shape[0]
+
+    d = dialogue()                                                    # warm-up: allocator, graph capture, every shape
+    for t in (0, 2, 4):
+        stateless(d["segs"], t)
+    runs, less, plen = [], {0: [], 2: [], 4: []}, {}
+    for _ in range(rounds):
+        for c in d["convs"]:
+            c.close()
+        d = dialogue()
+        runs.append(d)
+        for t in (0, 2, 4):
+            f, plen[t] = stateless(d["segs"], t)
+            less[t].append(f)
+    hist = d["convs"][0].tokens.shape[0]
+    print(f"GEN_SERVE_CONV: {NC} conversations x 6 turns on {NC} slots, chunk_frames {n}, {frames} frames per spoken turn, 5 s heard "
+          f"per even turn; {rounds} dialogues after one warm-up; history at the end {hist} positions.  ms as median [min..max]")
+    for t in (0, 2, 4):
+        fc = [r["first"][t] for r in runs]
+        print(f"(a) turn {t + 1}: step that admits all {NC} turns -> first chunk: conversation {fmt(fc)} (fed {d['fed'][t]} "
+              f"positions; {d['cached'][t]} cached after the turn) | stateless submit {fmt(less[t])} (prompt {plen[t]} positions)")
+    spread = max(max(r["first"][t] for r in runs) - min(r["first"][t] for r in runs) for t in (2, 4))
+    print(f"(a) run-to-run spread of the conversation figure (max - min over the {rounds} dialogues, worst of turns 3 and 5): {spread:.1f} ms; "
+          f"turn 5 - turn 3 (medians): {med([r['first'][4] for r in runs]) - med([r['first'][2] for r in runs]):+.1f} ms")
+    tot = [NC * 3 * frames / r["total"] for r in runs]
+    print(f"(d) aggregate over the whole dialogue ({NC * 3 * frames} frames kept; steps + adds' Mimi encodes): {med(tot):.0f} frames/s "
+          f"[{min(tot):.0f}..{max(tot):.0f}]")
+    # ---- (c) park / resume
+    st = srv._state
+    with torch.inference_mode():
+        for c in d["convs"]:
+            c.close()
+        d = dialogue()
+        parked = [c._parked for c in d["convs"]]
+        for t in (0, 2, 4):
+            L = d["cached"][t]
+            part = parked[0][:, :, :, :L].contiguous()
+            st.resume_row(0, part)
+            tp = [_timed(lambda: st.park_row(0, L), 20) * 1e3 for _ in range(rounds)]
+            tr = [_timed(lambda: st.resume_row(0, part), 20) * 1e3 for _ in range(rounds)]
+            print(f"(c) history {L:4d} positions ({part.numel() * 2 / 1e6:5.1f} MB): park_row {min(tp):.3f} ms, resume_row {min(tr):.3f} ms "
+                  f"(best of {rounds} x 20)")
+        # ---- (b) one append_rows over J segments against J one-row calls, at the end-of-dialogue history
+        base = []
+        for b in range(NC):
+            st.resume_row(b, parked[b])
+            base.append(st.row_pos[b])
+        feed = d["feed"]
+
+        def reset(J):
+            for b in range(J):
+                st.row_pos[b] = base[b]
+
+        for J in (1, 2, 4, 8, 16):
+            def together():
+                reset(J)
+                st.append_rows(list(range(J)), [feed[b][0] for b in range(J)], [feed[b][1] for b in range(J)])
+
+            def one_by_one():
+                reset(J)
+                for b in range(J):
+                    st.append_rows([b], [feed[b][0]], [feed[b][1]])
+
+            for f in (together, one_by_one):
+                _timed(f, 2)
+            best = {"rows": 1e9, "single": 1e9}
+            for _ in range(rounds):
+                best["rows"] = min(best["rows"], _timed(together, 5))
+                best["single"] = min(best["single"], _timed(one_by_one, 5))
+            print(f"(b) append_rows, {feed[0][0].shape[0]} positions per segment after {base[0] + 1} cached, J={J:2d}: one call "
+                  f"{best['rows'] * 1e3:7.2f} ms, {J} one-row calls {best['single'] * 1e3:7.2f} ms -> {best['single'] / best['rows']:.2f}x", flush=True)
+
+
 def main():
+    if os.environ.get("GEN_SERVE_CONV") == "1":
+        return serve_conv_main()
     if os.environ.get("GEN_SERVE") == "1":
         return serve_main()
     if os.environ.get("GEN_CONVERSATION") == "1":
