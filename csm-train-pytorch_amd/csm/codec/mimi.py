@@ -7,7 +7,8 @@ scale and a 250-frame window, stride-2 down / up-sampling to 12.5 Hz, split resi
 codebooks of 2048 x 256) on hand-written fp32 HIP kernels, taking the weights as a state dict with the key names of the
 Hugging Face port (``transformers.MimiModel.state_dict()``; the moshi checkpoint maps onto it 1:1).  It exposes exactly
 what ``Generator`` touches: ``encode([1,1,N]) -> [1,K,T]`` int64, ``decode([1,K,T]) -> [1,1,N]``, ``sample_rate``, and
-``decode_stream()``: a stateful decoder that turns successive chunks of frames into their audio, bit-identical to ``decode``.
+``decode_stream()``: a stateful decoder that turns successive chunks of frames into their audio, bit-identical to ``decode``,
+and ``encode_stream()``: its counterpart for the audio that is heard, bit-identical to ``encode`` on whole frames.
 """
 import math
 from typing import Dict, Optional
@@ -37,10 +38,25 @@ def decoder_conv_layers(ratios=(8, 6, 5, 4)):
     return layers
 
 
+def encoder_conv_layers(ratios=(8, 6, 5, 4)):
+    """The causal convolutions ``MimiCodec.encode_latent`` runs, in order, as (weight prefix, k, stride, input ELU, replicate):
+    the SEANet encoder (per ratio, taken in reverse, a residual block and a stride-r conv), then - after the transformer - the
+    stride-2 ``downsample``, the only one whose left padding replicates the edge (replicate True) instead of being zero."""
+    layers = [("encoder.layers.0", 7, 1, False, False)]
+    idx = 1
+    for r in reversed(tuple(ratios)):
+        layers += [(f"encoder.layers.{idx}.block.1", 3, 1, True, False),
+                   (f"encoder.layers.{idx}.block.3", 1, 1, True, False),
+                   (f"encoder.layers.{idx + 2}", 2 * r, r, True, False)]
+        idx += 3
+    layers += [(f"encoder.layers.{idx + 1}", 3, 1, True, False), ("downsample", 4, 2, False, True)]
+    return layers
+
+
 def history_len(kind: str, k: int, stride: int = 1, dilation: int = 1) -> int:
-    """Input columns a streaming layer carries between chunks: (k-1)*dil for a causal conv, ceil(k/stride)-1 for a transposed
-    conv whose overhang is cropped on the right."""
-    return (k - 1) * dilation if kind == "conv" else (k - 1) // stride
+    """Input columns a streaming layer carries between chunks: k_eff - stride = (k-1)*dil + 1 - stride for a causal conv (its
+    left padding; (k-1)*dil at stride 1), ceil(k/stride)-1 for a transposed conv whose overhang is cropped on the right."""
+    return (k - 1) * dilation + 1 - stride if kind == "conv" else (k - 1) // stride
 
 
 def ring_slot(pos: int, ring: int) -> int:
@@ -174,7 +190,10 @@ class MimiCodec:
 
     @torch.no_grad()
     def encode(self, wav: torch.Tensor) -> torch.Tensor:
-        lat = self.encode_latent(wav)
+        return self._quantize(self.encode_latent(wav)).unsqueeze(0)
+
+    def _quantize(self, lat):
+        """latent [T, hidden] -> codes [K, T] int64 (both residual VQs; every row on its own)."""
         T = lat.shape[0]
         codes = torch.empty(self.K, T, dtype=torch.int64, device=self.dev)
         q = "quantizer.semantic_residual_vector_quantizer"
@@ -183,7 +202,12 @@ class MimiCodec:
             q = "quantizer.acoustic_residual_vector_quantizer"
             na = self.K - self.n_sem
             ops.rvq_encode(self._linear(lat, self.w[f"{q}.in"]), self.cb["acoustic"][:na].contiguous(), codes[self.n_sem:], 0)
-        return codes.unsqueeze(0)
+        return codes
+
+    def encode_stream(self, max_chunk_frames: int = 32) -> "MimiEncodeStream":
+        """A stateful encoder: ``step(wav [1,1,n*1920])`` returns the codes [1,K,n] of the next n frames, and the concatenated
+        steps equal ``encode`` of all the samples, bit for bit."""
+        return MimiEncodeStream(self, max_chunk_frames)
 
     def _dequantize(self, c):
         """codes [K, T] int64 -> latent [T, hidden] (both residual VQs + their output projections)."""
@@ -225,8 +249,105 @@ class MimiCodec:
         return MimiDecodeStreamRows(self, slots, max_chunk_frames)
 
 
+class MimiEncodeStream:
+    """Streaming state of ``MimiCodec.encode``: audio goes in as it arrives, 80 ms frame by 80 ms frame, and its codes come out.
+    Every encoder op is causal - SEANet convs padded on the left by k_eff - stride, a causal windowed transformer, the stride-2
+    downsample edge-replicated on the left - and every kernel computes an output with a reduction order that does not depend on
+    the sequence length, so the concatenated codes of all ``step`` / ``feed`` calls equal ``encode(wav)[..., :whole_frames]`` bit
+    for bit, for any split.  The state is:
+      * per conv layer (``encoder_conv_layers``), the last ``history_len`` input columns in two buffers that alternate each
+        step; the stride-1 layers run csm_conv1d_stream_f32, the strided ones csm_conv1d_stream_strided_f32, and the first
+        chunk of ``downsample`` takes its history from its own first column (``edge_first``);
+      * per encoder-transformer layer, a K/V ring of ``window + 2 * max_chunk_frames - 1`` post-RoPE rows;
+      * the number of frames encoded so far, and the samples of a frame not yet complete (``feed``), on the device.
+    ``step`` makes no host synchronisation.
+    The one deviation: ``encode`` of a waveform that is not a whole number of frames pads every LAYER on the right, ``flush``
+    pads the WAVEFORM with zeros - so the codes of that last partial frame may differ from ``encode(wav)``'s; they equal
+    ``encode(zero-padded wav)``'s."""
+
+    def __init__(self, codec: MimiCodec, max_chunk_frames: int = 32):
+        if max_chunk_frames < 1:
+            raise ValueError("max_chunk_frames must be >= 1")
+        self.codec = codec
+        dev, w = codec.dev, codec.w
+        self.layers = {name: (k, stride, elu, rep) for name, k, stride, elu, rep in encoder_conv_layers(codec.ratios)}
+        self.frame = math.prod(stride for _, stride, _, _ in self.layers.values())        # samples per frame (1920)
+        self.hist = {}
+        for name, (k, stride, _, _) in self.layers.items():
+            H = history_len("conv", k, stride)
+            C_in = w[f"{name}.conv.weight"].shape[1]                                       # (every encoder conv has groups = 1)
+            self.hist[name] = [torch.zeros(C_in, H, dtype=F32, device=dev) for _ in range(2)] if H else None
+        self.ring = codec.window + 2 * max_chunk_frames - 1
+        self.kv = [tuple(torch.zeros(self.ring, codec.hidden, dtype=F32, device=dev) for _ in range(2)) for _ in range(codec.n_layers)]
+        self.reset()
+
+    def reset(self):
+        """Start a new utterance."""
+        for bufs in self.hist.values():
+            if bufs is not None:
+                bufs[0].zero_()
+        self._par = 0                      # hist[name][_par] holds the current history
+        self.pos = 0                       # frames encoded so far
+        self._rem = torch.zeros(0, dtype=F32, device=self.codec.dev)       # feed(): samples of the frame in progress
+
+    def _conv(self, x, name, res=None, edge_first=False):
+        k, stride, elu, _ = self.layers[name]
+        wt, b = self.codec.w[f"{name}.conv.weight"], self.codec.w.get(f"{name}.conv.bias")
+        bufs = self.hist[name]
+        h, h_next = (None, None) if bufs is None else (bufs[self._par], bufs[self._par ^ 1])
+        y = torch.empty(wt.shape[0], x.shape[1] // stride, dtype=F32, device=self.codec.dev)
+        if stride == 1:
+            return ops.conv1d_stream_f32(h, x, wt, b, y, h_next, 1, elu, res)
+        return ops.conv1d_stream_strided_f32(h, x, wt, b, y, h_next, stride, 1, elu, res, edge_first)
+
+    @torch.no_grad()
+    def step(self, wav: torch.Tensor) -> torch.Tensor:
+        """wav [1, 1, n * 1920], n >= 1 -> the codes of the next n frames [1, K, n] int64."""
+        cd = self.codec
+        if wav.numel() == 0 or wav.numel() % self.frame:
+            raise ValueError(f"step takes a whole number (>= 1) of {self.frame}-sample frames, got {wav.numel()} samples "
+                             "(feed() takes any length)")
+        n = wav.numel() // self.frame
+        x = wav.reshape(1, -1).to(cd.dev, F32).contiguous()
+        x = self._conv(x, "encoder.layers.0")
+        idx = 1
+        for _ in cd.ratios:
+            h = self._conv(x, f"encoder.layers.{idx}.block.1")
+            x = self._conv(h, f"encoder.layers.{idx}.block.3", res=x)
+            x = self._conv(x, f"encoder.layers.{idx + 2}")
+            idx += 3
+        x = self._conv(x, f"encoder.layers.{idx + 1}")                                           # [hidden, 2n]
+        x = cd._transformer(cd._transpose(x), "encoder_transformer", pos0=2 * self.pos, kv=self.kv)
+        x = self._conv(cd._transpose(x), "downsample", edge_first=self.pos == 0)                 # [hidden, n]
+        codes = cd._quantize(cd._transpose(x))
+        self._par ^= 1
+        self.pos += n
+        return codes.unsqueeze(0)
+
+    def _none(self):
+        return torch.zeros(1, self.codec.K, 0, dtype=torch.int64, device=self.codec.dev)
+
+    @torch.no_grad()
+    def feed(self, wav: torch.Tensor) -> torch.Tensor:
+        """Any number of samples (none included): the codes of the whole frames now available ([1, K, 0] when there is none); the
+        samples of the frame in progress wait on the device for the next call."""
+        buf = torch.cat([self._rem, wav.reshape(-1).to(self.codec.dev, F32)])
+        whole = buf.numel() // self.frame * self.frame
+        self._rem = buf[whole:].clone()
+        return self.step(buf[:whole]) if whole else self._none()
+
+    @torch.no_grad()
+    def flush(self) -> torch.Tensor:
+        """The codes of the held partial frame, zero-padded to a whole one ([1, K, 0] when nothing is held)."""
+        if not self._rem.numel():
+            return self._none()
+        pad = torch.zeros(self.frame - self._rem.numel(), dtype=F32, device=self.codec.dev)
+        buf, self._rem = torch.cat([self._rem, pad]), self._rem[:0]
+        return self.step(buf)
+
+
 class MimiDecodeStream:
-    """Streaming state of ``MimiCodec.decode``.  Every decoder op is causal (stride-1 convs with left zero padding, transposed
+    """Streaming state of ``MimiCodec.decode``. Every decoder op is causal (stride-1 convs with left zero padding, transposed
     convs cropped on the right, a causal windowed transformer), so frame t's samples depend on codes 0..t only, and every
     kernel computes an output with a reduction order that does not depend on the sequence length.  The state is:
       * per conv / transposed conv layer, the last ``history_len`` input columns ([C_in, H] fp32), in two buffers that

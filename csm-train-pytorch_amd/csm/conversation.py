@@ -5,7 +5,8 @@ A ``Conversation`` owns the token history the model has been conditioned on and 
 graph).  A turn feeds only what the cache does not hold yet - ``history[cached:]`` plus the new line's text frames - through
 ``DecodeState.append`` (``csm_attn_append``: the new positions attend to the cached ones), so the time to the first frame
 depends on the new line, not on the length of the conversation.  The frames the model speaks stay in the cache as they were
-sampled; the other party's audio is Mimi-encoded once, when it is ``add``ed.
+sampled; the other party's audio is Mimi-encoded once, when it is ``add``ed - or, with ``hear``, frame by frame while it is
+still being spoken (``HeardTurn``), which takes the encode off the path between its last sample and our first chunk.
 """
 from contextlib import contextmanager
 from typing import Iterator, List, Optional
@@ -26,6 +27,78 @@ class _Turn:
         self.fed = 0                               # samples[:fed] have been fed to the backbone (one position each)
         self.kept = 0                              # frames handed to the caller so far (stream) / kept (generate)
         self.done = False
+
+
+class HeardTurn:
+    """``conv.hear(speaker)`` on a ``Conversation`` or a ``ServedConversation``: the other party's turn, Mimi-encoded while it is
+    still being spoken (``MimiCodec.encode_stream``) so that nothing but the last partial frame is left to encode when it ends.
+    ``feed(audio)`` encodes the whole frames now available and touches neither the history nor the caches - it may be called
+    while the conversation's own turn streams, while the server steps and while other conversations speak; ``end(text)`` flushes
+    the last partial frame (zero-padded) and enters the turn exactly as ``add(Segment(speaker, text, audio))`` does - for audio
+    of a whole number of frames ``tokens`` and ``mask`` are equal to that path's; ``cancel()`` drops the turn."""
+
+    def __init__(self, conv, speaker: int, stream):
+        self._conv, self.speaker, self._stream = conv, speaker, stream
+        self._codes: List[torch.Tensor] = []
+        self._frames = 0
+        self.closed = False
+
+    def _check(self, what):
+        if self.closed:
+            raise RuntimeError(f"{what}: this heard turn was ended or cancelled")
+
+    def _take(self, codes):
+        if codes.shape[2]:
+            self._codes.append(codes[0])
+            self._frames += codes.shape[2]
+
+    @property
+    def frames(self) -> int:
+        """Frames encoded so far."""
+        return self._frames
+
+    @torch.inference_mode()
+    def feed(self, audio: torch.Tensor) -> int:
+        """The next samples of the turn, any number of them ((n,), sample_rate 24 kHz); returns ``frames``."""
+        self._check("feed")
+        self._take(self._stream.feed(audio.reshape(1, 1, -1)))
+        return self._frames
+
+    @torch.inference_mode()
+    def end(self, text: str) -> None:
+        """The turn is over and ``text`` is what was said: the history gets the text frames, the streamed codes and the all-zero
+        EOS frame; they enter the cache with the next spoken turn."""
+        self._check("end")
+        conv, gen = self._conv, self._conv._gen
+        conv._before_history("end")                                 # (raises with the turn still open: end() can be retried)
+        self._take(self._stream.flush())
+        K = gen._model.args.audio_num_codebooks
+        codes = torch.cat(self._codes, 1) if self._codes else torch.zeros(K, 0, dtype=torch.long, device=gen.device)
+        tt, tm = gen._tokenize_text_segment(text, self.speaker)
+        at, am = gen._audio_frames(codes.to(gen.device))
+        self.closed, conv._heard = True, None
+        conv._push(torch.cat([tt, at], dim=0).long(), torch.cat([tm, am], dim=0).bool())
+
+    def cancel(self) -> None:
+        """Drop the turn: nothing of it enters the history."""
+        if not self.closed:
+            self.closed, self._conv._heard = True, None
+
+
+def open_heard_turn(conv, speaker: int) -> HeardTurn:
+    """``hear`` of both conversation classes: at most one heard turn is open per conversation; its encode stream is made at the
+    first ``hear`` and started anew (``reset()``) for every later one."""
+    if conv._heard is not None:
+        raise RuntimeError("hear: this conversation already has a heard turn open - end() or cancel() it first")
+    if conv._enc is None:
+        codec = conv._gen._audio_tokenizer
+        if not callable(getattr(codec, "encode_stream", None)):
+            raise TypeError(f"{type(codec).__name__} has no encode_stream(): hearing a turn as it arrives needs a stateful encoder")
+        conv._enc = codec.encode_stream()
+    else:
+        conv._enc.reset()
+    conv._heard = HeardTurn(conv, speaker, conv._enc)
+    return conv._heard
 
 
 class Conversation:
@@ -61,6 +134,8 @@ class Conversation:
         self._state: Optional[DecodeState] = None
         self._run = 0
         self._open: Optional[_Turn] = None
+        self._heard: Optional[HeardTurn] = None    # the other party's turn being heard (hear), at most one
+        self._enc = None                           # its encode stream: made at the first hear, reused
         for seg in context:
             self.add(seg)
 
@@ -82,10 +157,22 @@ class Conversation:
     def add(self, segment) -> None:
         """The other party's turn (or any context segment): only THIS segment is tokenised and Mimi-encoded.  It enters the cache
         with the next spoken turn."""
-        self._run += 1
-        self._settle()
+        if self._heard is not None:
+            raise RuntimeError("add: a heard turn is open on this conversation - end() or cancel() it first")
+        self._before_history("add")
         t, m = self._gen._tokenize_segment(segment)
         self._push(t.long(), m.bool())
+
+    def hear(self, speaker: int) -> HeardTurn:
+        """The other party starts to speak: ``turn.feed(audio)`` Mimi-encodes the turn as it arrives, ``turn.end(text)`` enters it
+        as ``add`` would - with nothing left to encode but its last partial frame."""
+        return open_heard_turn(self, speaker)
+
+    def _before_history(self, what):
+        """What ``add`` and ``HeardTurn.end`` do before they extend the history: an open stream of this conversation is
+        invalidated and its turn settled."""
+        self._run += 1
+        self._settle()
 
     def reset(self) -> None:
         """Drop the cache (and the captured frame graph), keep the history: the next turn prefills it from position 0 with the

@@ -98,9 +98,12 @@ class Generator:
 
     def _tokenize_audio(self, audio: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference generator.py:102-130: Mimi codes [K,T] + one all-zero EOS frame into the first K columns."""
-        K1 = self._model.args.audio_num_codebooks + 1
         audio = audio.to(self.device)
-        codes = self._audio_tokenizer.encode(audio.unsqueeze(0).unsqueeze(0))[0]
+        return self._audio_frames(self._audio_tokenizer.encode(audio.unsqueeze(0).unsqueeze(0))[0])
+
+    def _audio_frames(self, codes: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Mimi codes [K,T] -> their T frames + one all-zero EOS frame (``_tokenize_audio``; ``HeardTurn.end`` for streamed codes)."""
+        K1 = self._model.args.audio_num_codebooks + 1
         eos = torch.zeros(codes.size(0), 1, dtype=codes.dtype, device=codes.device)
         codes = torch.cat([codes, eos], dim=1)
         frame = torch.zeros(codes.size(1), K1).long().to(self.device)
@@ -289,7 +292,8 @@ class Generator:
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
         chunk by chunk and leave at their own EOS - and ``server.run()`` iterates until all are done.  Temperature and top-k
         belong to the server.  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
-        speaker)`` queues its next turn as a request, ``conv.add(Segment)`` is the other party's turn; its KV history is parked
+        speaker)`` queues its next turn as a request, ``conv.add(Segment)`` (or ``conv.hear(speaker)`` -> ``feed`` / ``end``, encoded
+        while it is spoken) is the other party's turn; its KV history is parked
         between turns and resumed into any free slot, so more conversations than slots can be open.  It takes over the model's caches like any ``generate*`` call (open streams and older servers are
         invalidated) and binds the adapters loaded so far: load adapters first."""
         from .serving import BatchServer
@@ -298,7 +302,8 @@ class Generator:
     def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error"):
         """A multi-turn dialogue that keeps its KV cache between turns (csm/conversation.py): ``conv.generate(text, speaker)`` /
         ``conv.generate_stream(...)`` speak the next line with every earlier turn as context, ``conv.add(Segment)`` adds the
-        other party's turn.  ``adapter``: a bank adapter name for the whole conversation.  ``on_overflow``: ``"error"`` raises
+        other party's turn - or ``turn = conv.hear(speaker)``, ``turn.feed(audio)`` as the audio arrives and ``turn.end(text)``,
+        which Mimi-encodes the turn while it is spoken (``HeardTurn``).  ``adapter``: a bank adapter name for the whole conversation.  ``on_overflow``: ``"error"`` raises
         the reference's "Inputs too long" error when history + line + max_audio_frames reach max_seq_len, ``"drop_oldest"``
         drops whole leading turns and prefills what is left."""
         from .conversation import Conversation

@@ -101,6 +101,7 @@ _SIGS = {
     "csm_attn_window_f32": ([_p, _p, _i, _i, _i, _i, _p], _i),
     "csm_transpose_f32": ([_p, _p, _i, _i, _p], _i),
     "csm_conv1d_stream_f32": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
+    "csm_conv1d_stream_strided_f32": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_conv_transpose1d_stream_f32": ([_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_attn_window_stream_f32": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_rvq_decode": ([_p, _p, _p, _i, _i, _i, _i, _p], _i),

@@ -689,6 +689,25 @@ def conv1d_stream_f32(hist, x, w, bias, y, hist_out, dilation=1, elu_in=False, r
     return y
 
 
+def conv1d_stream_strided_f32(hist, x, w, bias, y, hist_out, stride, dilation=1, elu_in=False, residual=None, edge_first=False):
+    """One chunk of a causal conv with stride >= 1 (csm_conv1d_stream_strided_f32): x [C_in, n_in] new columns (n_in a multiple
+    of stride) after ``hist`` [C_in, H], H = (k-1)*dil + 1 - stride -> y [C_out, n_in // stride] (+ residual); the next history
+    goes to ``hist_out`` (a different buffer).  ``edge_first``: ``hist`` is not read, every history column is column 0 of x (the
+    first chunk of an edge-replicated conv).  hist / hist_out may be None when H == 0.  w: [C_out, C_in/groups, k]."""
+    C_in, n_in = x.shape
+    C_out, cin_g, k = w.shape
+    H = (k - 1) * dilation + 1 - stride
+    assert y.shape == (C_out, n_in // stride) and C_in % cin_g == 0
+    if H > 0:
+        assert hist.shape == (C_in, H) and hist_out.shape == (C_in, H)
+    check(lib.csm_conv1d_stream_strided_f32(_f32(hist, "hist") if H > 0 else None, _f32(x, "x"), _f32(w, "w"),
+                                            None if bias is None else _f32(bias, "bias"),
+                                            None if residual is None else _f32(residual, "res"), _f32(y, "y"),
+                                            _f32(hist_out, "hist_out") if H > 0 else None, C_in, C_out, n_in, k, stride, dilation,
+                                            C_in // cin_g, int(elu_in), int(edge_first), _stream()), "csm_conv1d_stream_strided_f32")
+    return y
+
+
 def conv_transpose1d_stream_f32(hist, x, w, bias, y, hist_out, pos0, stride, groups=1, elu_in=False):
     """One chunk of a causal transposed conv (csm_conv_transpose1d_stream_f32): x [C_in, n] new columns at input position
     ``pos0`` after ``hist`` [C_in, ceil(k/stride)-1] -> y [C_out, n*stride]; next history to ``hist_out``.

@@ -33,7 +33,8 @@ headroom beyond ``max_audio_frames``.  A conversation's ``seed`` gives it one ge
 when the conversation samples a frame and travels with it from slot to slot.
 
 Limitations: a join stalls the other rows for one whole prefill or append (no chunked prefill); the context audio of a request
-and a conversation's ``add``ed turns are Mimi-encoded at ``submit`` / ``add``, one segment at a time; adapters added to the
+and a conversation's ``add``ed turns are Mimi-encoded at ``submit`` / ``add``, one segment at a time (``conv.hear`` encodes a turn
+while it is being spoken instead, one encoder step per ``feed``, one conversation at a time); adapters added to the
 Generator after ``serve()`` are unknown to the server (the state binds the bank at creation).
 """
 from collections import deque
@@ -41,7 +42,7 @@ from typing import Iterator, List, Optional, Tuple
 
 import torch
 
-from .conversation import OVERFLOW
+from .conversation import OVERFLOW, HeardTurn, open_heard_turn
 from .engine import DecodeState
 
 
@@ -90,6 +91,8 @@ class ServedConversation:
         self._parked = None                      # DecodeState.park_row of the ``cached`` leading positions, while it holds no slot
         self._noise = None                       # its generator (made at the first admission: lives on the state's device)
         self._open: Optional[Request] = None
+        self._heard: Optional[HeardTurn] = None  # the other party's turn being heard (hear), at most one
+        self._enc = None                         # its encode stream: made at the first hear, reused
         self.closed = False
         for seg in context:
             self.add(seg)
@@ -116,9 +119,22 @@ class ServedConversation:
     @torch.inference_mode()
     def add(self, segment) -> None:
         """The other party's turn: tokenised and Mimi-encoded here, once; it enters the cache with the next ``say``."""
+        if self._heard is not None:
+            raise RuntimeError("add: a heard turn is open on this conversation - end() or cancel() it first")
         self._idle("add")
         t, m = self._gen._tokenize_segment(segment)
         self._push(t.long(), m.bool())
+
+    def hear(self, speaker: int) -> HeardTurn:
+        """The other party starts to speak: ``turn.feed(audio)`` Mimi-encodes the turn as it arrives - between the server's steps,
+        whoever holds the slots - and ``turn.end(text)`` enters it as ``add`` would, under ``add``'s rules (no turn of this
+        conversation still open), with nothing left to encode but its last partial frame."""
+        self._srv._check()
+        if self.closed:
+            raise RuntimeError("hear: this conversation was closed")
+        return open_heard_turn(self, speaker)
+
+    _before_history = _idle
 
     def _push(self, t, m):
         self._tokens = torch.cat([self._tokens, t.to(self._tokens.device)], 0)

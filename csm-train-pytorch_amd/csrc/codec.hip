@@ -110,6 +110,46 @@ __global__ __launch_bounds__(256) void conv1d_stream_kernel(const float* __restr
         }
 }
 
+// Streaming causal conv with stride >= 1 (the encoder's downsampling layers): the input is [hist | x] with x = n_in new
+// columns (a multiple of stride) and hist = the last H = (k-1)*dil + 1 - stride input columns before them - conv1d_kernel's
+// pad_left, zeros before the first chunk.  Output t of the chunk starts at column t*stride of [hist | x]; it goes through
+// conv1d_accum with the operands conv1d_kernel reads for the same absolute output.  edge_first (the first chunk of an
+// edge-replicated conv, pad_mode 1): hist is not read, every history column is column 0 of x.  The next history is the last
+// H columns of [hist | x]; H may exceed n_in, then it keeps H - n_in old columns.  Time is flattened onto the threads of one
+// output channel as in conv1d_kernel: the early encoder layers carry hundreds of columns per frame.
+__global__ __launch_bounds__(256) void conv1d_stream_strided_kernel(const float* __restrict__ hist, const float* __restrict__ x,
+                                                                    const float* __restrict__ w, const float* __restrict__ bias,
+                                                                    const float* __restrict__ res, float* __restrict__ y,
+                                                                    float* __restrict__ hist_out, int C_in, int C_out, int n_in, int k,
+                                                                    int stride, int dil, int groups, int elu_in, int edge_first) {
+    const int co = blockIdx.y;
+    const int H = (k - 1) * dil + 1 - stride;
+    const int n_out = n_in / stride;
+    const int cin_g = C_in / groups, cout_g = C_out / groups;
+    const int grp = co / cout_g;
+    const float* wrow = w + (size_t)co * cin_g * k;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n_out; t += gridDim.x * blockDim.x) {
+        const int base = t * stride;
+        float acc = conv1d_accum(bias ? bias[co] : 0.f, wrow, cin_g, k, elu_in, [&](int ci, int j) {
+            const int c = grp * cin_g + ci, p = base + j * dil;         // column of [hist | x]
+            const float* xr = x + (size_t)c * n_in;
+            // select the address, then load unconditionally (as conv1d_stream_kernel)
+            const float* old = edge_first ? xr : hist + (size_t)c * H + p;
+            const float* src = p < H ? old : xr + (p - H);
+            return *src;
+        });
+        if (res) acc += res[(size_t)co * n_out + t];
+        y[(size_t)co * n_out + t] = acc;
+    }
+    for (int c = blockIdx.y; c < C_in; c += gridDim.y)
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < H; i += gridDim.x * blockDim.x) {
+            const int p = n_in + i;
+            const float* xr = x + (size_t)c * n_in;
+            const float* old = edge_first ? xr : hist + (size_t)c * H + p;
+            hist_out[(size_t)c * H + i] = *(p < H ? old : xr + (p - H));
+        }
+}
+
 // ConvTranspose1d (torch weight layout [C_in][C_out/groups][k]) cropped to [crop_left, crop_left + T_out):
 // y[co][t] = bias[co] + sum_ci sum_{j : (t + crop_left - j) % stride == 0} act(x[ci][(t + crop_left - j)/stride]) w[ci][co_g][j]
 __global__ __launch_bounds__(256) void conv_transpose1d_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -674,6 +714,28 @@ extern "C" int csm_conv1d_stream_f32(const float* hist, const float* x, const fl
     hipLaunchKernelGGL(conv1d_stream_kernel, dim3(bx, C_out), dim3(256), 0, stream, hist, x, w, bias, residual, y, hist_out, C_in, C_out,
                        n, k, dilation, groups, elu_in);
     CSM_CHECK_LAUNCH("csm_conv1d_stream_f32");
+    return 0;
+}
+
+extern "C" int csm_conv1d_stream_strided_f32(const float* hist, const float* x, const float* w, const float* bias, const float* residual,
+                                             float* y, float* hist_out, int C_in, int C_out, int n_in, int k, int stride, int dilation,
+                                             int groups, int elu_in, int edge_first, hipStream_t stream) {
+    CSM_REQUIRE(x && w && y && C_in > 0 && C_out > 0 && n_in > 0 && k > 0 && stride > 0 && dilation > 0 && groups > 0 &&
+                    C_in % groups == 0 && C_out % groups == 0 && C_out <= 65535, "csm_conv1d_stream_strided_f32: bad arguments");
+    CSM_REQUIRE(n_in % stride == 0, "csm_conv1d_stream_strided_f32: n_in %d is not a multiple of stride %d", n_in, stride);
+    const long long H = (long long)(k - 1) * dilation + 1 - stride;
+    CSM_REQUIRE(H >= 0, "csm_conv1d_stream_strided_f32: stride %d exceeds the kernel's extent (k %d, dilation %d)", stride, k, dilation);
+    CSM_REQUIRE(H + n_in < (1LL << 31), "csm_conv1d_stream_strided_f32: column index overflow");
+    CSM_REQUIRE(H == 0 || (hist_out && hist != hist_out && (hist || edge_first)),
+                "csm_conv1d_stream_strided_f32: a history of %lld columns needs two distinct history buffers", H);
+    const int n_out = n_in / stride;
+    const long long work = n_out > H ? n_out : H;              // the same grid writes the outputs and the next history
+    const int bs = rows_block(work);
+    long long bx = (work + bs - 1) / bs;
+    if (bx > 4096) bx = 4096;
+    hipLaunchKernelGGL(conv1d_stream_strided_kernel, dim3((unsigned)bx, C_out), dim3(bs), 0, stream, hist, x, w, bias, residual, y,
+                       hist_out, C_in, C_out, n_in, k, stride, dilation, groups, elu_in, edge_first ? 1 : 0);
+    CSM_CHECK_LAUNCH("csm_conv1d_stream_strided_f32");
     return 0;
 }
 

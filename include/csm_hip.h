@@ -360,6 +360,14 @@ int csm_transpose_f32(const float* in, float* out, int R, int C, csm_stream_t st
  * the next history (last (k-1)*dilation columns of [hist | x]) goes to hist_out, which must not alias hist. */
 int csm_conv1d_stream_f32(const float* hist, const float* x, const float* w, const float* bias, const float* residual, float* y,
                           float* hist_out, int C_in, int C_out, int n, int k, int dilation, int groups, int elu_in, csm_stream_t stream);
+/* The same for stride >= 1 (the encoder's downsampling convs; additive since ABI 3): x = [C_in][n_in] new columns, n_in a
+ * multiple of stride (refused otherwise); hist / hist_out = [C_in][H], H = (k-1)*dilation + 1 - stride >= 0 (csm_conv1d_f32's
+ * pad_left; may exceed n_in; NULL when H == 0); y / residual = [C_out][n_in / stride], every output with the arithmetic
+ * csm_conv1d_f32 uses for the same absolute output.  edge_first != 0: hist is not read (may be NULL) and every history column is
+ * column 0 of x - pad_mode 1's left edge, for the first chunk of an edge-replicated conv. */
+int csm_conv1d_stream_strided_f32(const float* hist, const float* x, const float* w, const float* bias, const float* residual, float* y,
+                                  float* hist_out, int C_in, int C_out, int n_in, int k, int stride, int dilation, int groups,
+                                  int elu_in, int edge_first, csm_stream_t stream);
 /* transposed conv (causal: crop_left 0) for n new input columns at absolute input position pos0; hist = the previous
  * ceil(k/stride)-1 input columns; y = [C_out][n*stride]; next history to hist_out (as above). */
 int csm_conv_transpose1d_stream_f32(const float* hist, const float* x, const float* w, const float* bias, float* y, float* hist_out,

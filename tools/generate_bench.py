@@ -13,7 +13,8 @@ GEN_FP8=1: decode frames/s with bf16 and with FP8 (weight-only e4m3) decode weig
 alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in each mode.  GEN_SERVE=1: the running batch (Generator.serve): rows-codec step against single steps, the server step at
 16 rows, the join stall (serve_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
 time to the first chunk of turns 1 / 3 / 5 against stateless submits, one append_rows against one-row calls, park / resume, aggregate
-frames/s (serve_conv_main).  GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
+frames/s (serve_conv_main).  GEN_HEAR=1: a 5 s heard turn's last sample to the first chunk of the reply, with
+``add(Segment)`` against ``hear`` fed during the turn, served (16 slots) and at B = 1 (hear_main).  GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
 through a Conversation (KV cache kept between turns) and statelessly (generate_stream with the accumulated Segment list - every
 turn encodes and prefills the whole history again), alternated in one process after a warm-up dialogue of each: per spoken turn the
 host time from the call to the first chunk (chunk_frames=2) and the turn's total; plus csm_attn_append alone next to the
@@ -762,7 +763,121 @@ def serve_conv_main():
                   f"{best['rows'] * 1e3:7.2f} ms, {J} one-row calls {best['single'] * 1e3:7.2f} ms -> {best['single'] / best['rows']:.2f}x", flush=True)
 
 
+def hear_main():
+    """GEN_HEAR=1: the time from the last sample of a 5 s heard turn to the first audio chunk of the reply, on CSM-1B random init,
+    with the heard turn entered (a) by ``add(Segment)`` after its last sample - tokenise + whole-segment Mimi encode on the path -
+    and (b) by ``hear`` fed in 4-frame pieces while the turn is spoken (untimed: that happens during the turn), so that the last
+    piece (2.5 frames), ``end`` (its flush) and the reply are what is left.  Served: GEN_SERVE_CONV's setting (16 slots,
+    chunk_frames 4, all 16 conversations' heard turns end at once, reply = ``say`` + the step that admits all 16 to the chunk on
+    the host).  B = 1: GEN_CONVERSATION's setting (``generate_stream``, chunk_frames 2).  Each dialogue: a spoken turn of
+    GEN_FRAMES frames (default 24), the heard turn, the reply.  GEN_ROUNDS rounds (default 3) of (a) and (b) alternated after one
+    warm-up round of each; ms as median [min..max].  Also the per-piece ``feed`` time during the turn."""
+    dev = "cuda:0"
+    NC, n = 16, 4
+    frames = int(os.environ.get("GEN_FRAMES", 24))
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    ms = 80 * frames
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=make_codec(dev))
+    g = torch.Generator(device=dev).manual_seed(1)
+    heard = torch.randn(5 * 24000, device=dev, generator=g) * 0.1
+    piece = 4 * 1920
+    cut = heard.numel() // piece * piece                              # 60 frames arrive during the turn, 2.5 at its end
+    line, heard_text, reply = "turn 1: the quick brown fox jumps over the lazy dog", "turn 2: and what did the dog do", "turn 3: it slept"
+    med = lambda xs: sorted(xs)[len(xs) // 2]                                                           # noqa: E731
+    fmt = lambda xs: f"{med(xs):7.1f} [{min(xs):6.1f}..{max(xs):6.1f}]"                                 # noqa: E731
+    feeds = []
+
+    def during(turns):
+        """What happens while the turn is spoken: every whole 4-frame piece is fed (timed per piece, all conversations)."""
+        for lo in range(0, cut, piece):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for t in turns:
+                t.feed(heard[lo:lo + piece])
+            torch.cuda.synchronize()
+            feeds.append((time.perf_counter() - t0) * 1e3 / len(turns))
+
+    def served(form):
+        srv = gen.serve(slots=NC, chunk_frames=n)
+        convs = [srv.conversation(seed=i) for i in range(NC)]
+        for c in convs:
+            c.say(line, 0, max_audio_length_ms=ms)
+        for _ in srv.run():
+            pass
+        turns = [c.hear(1) for c in convs] if form == "hear" else None
+        if turns:
+            during(turns)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()                                      # the turn's last sample
+        for i, c in enumerate(convs):
+            if turns:
+                turns[i].feed(heard[cut:])
+                turns[i].end(heard_text)
+            else:
+                c.add(Segment(1, heard_text, heard))
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        snap = convs[0].tokens                                         # (the history with the heard turn; later pushes make new tensors)
+        for c in convs:
+            c.say(reply, 0, max_audio_length_ms=ms)
+        out = srv.step()
+        torch.cat([a for _, a, _ in out]).cpu()
+        t2 = time.perf_counter()
+        assert srv.last_join_rows == NC
+        for _ in srv.run():
+            pass
+        return (t1 - t0) * 1e3, (t2 - t0) * 1e3, snap
+
+    def single(form):
+        conv = gen.conversation()
+        for _ in conv.generate_stream(line, 0, max_audio_length_ms=ms, chunk_frames=2):
+            pass
+        turn = conv.hear(1) if form == "hear" else None
+        if turn:
+            during([turn])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if turn:
+            turn.feed(heard[cut:])
+            turn.end(heard_text)
+        else:
+            conv.add(Segment(1, heard_text, heard))
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        snap = conv.tokens
+        s = conv.generate_stream(reply, 0, max_audio_length_ms=ms, chunk_frames=2)
+        next(s).cpu()
+        t2 = time.perf_counter()
+        for _ in s:
+            pass
+        return (t1 - t0) * 1e3, (t2 - t0) * 1e3, snap
+
+    print(f"GEN_HEAR: 5 s heard turn ({heard.numel() // 1920} whole frames + {heard.numel() % 1920} samples), {frames} frames per spoken "
+          f"turn, {rounds} alternated rounds after one warm-up of each form; ms as median [min..max]")
+    for name, fn in (("served, 16 conversations at once, chunk_frames 4", served), ("B = 1 generate_stream, chunk_frames 2", single)):
+        res = {"add": [], "hear": []}
+        toks = {}
+        for r in range(rounds + 1):
+            for form in ("add", "hear"):
+                torch.manual_seed(7)
+                enter, first, toks[form] = fn(form)
+                if r:
+                    res[form].append((enter, first))
+        # (whole frames equal bit for bit; the last, partial frame is the documented deviation: layers padded against waveform padded)
+        same = bool((toks["add"][:-2] == toks["hear"][:-2]).all()) if toks["add"].shape == toks["hear"].shape else False
+        for form, what in (("add", "(a) add(Segment) + reply"), ("hear", "(b) last piece + end + reply")):
+            print(f"{name}: {what}: last sample -> first chunk on the host {fmt([f for _, f in res[form]])} ms, of which entering the "
+                  f"turn {fmt([e for e, _ in res[form]])} ms", flush=True)
+        print(f"{name}: (b) - (a) = {med([f for _, f in res['hear']]) - med([f for _, f in res['add']]):+.1f} ms (medians); histories "
+              f"{'equal up to the last partial frame' if same else 'DIFFER'}")
+    print(f"feed of one 4-frame piece during the turn (one encoder step, per conversation): {fmt(feeds)} ms; a 5 s turn makes "
+          f"{cut // piece} of them, one per 320 ms of audio")
+
+
 def main():
+    if os.environ.get("GEN_HEAR") == "1":
+        return hear_main()
     if os.environ.get("GEN_SERVE_CONV") == "1":
         return serve_conv_main()
     if os.environ.get("GEN_SERVE") == "1":

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Mimi codec on the GPU: encode / decode time for 10 s of 24 kHz audio (seeded random weights with the HF key names), then
-the streaming decoder: microseconds per ``MimiDecodeStream.step`` of n = 1, 2, 4 frames and the kernel launches per step."""
+the streaming decoder: microseconds per ``MimiDecodeStream.step`` of n = 1, 2, 4 frames and the kernel launches per step, then
+the streaming encoder: ``encode`` of 5 s next to microseconds per ``MimiEncodeStream.step`` of n = 1, 2, 4 frames."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -62,3 +63,26 @@ for n in (1, 2, 4):
     launches = counters[0].n + counters[1].n + 1          # + the latent's zero fill
     print(f"stream step n={n}: {us:.0f} us per step ({us / n:.0f} us per 80-ms frame, {n * 80e3 / us:.0f}x real time), "
           f"{launches} launches per step")
+
+wav5 = wav[:, :, :120000].cuda()
+t5, _ = t(lambda: codec.encode(wav5))
+print(f"encode 5 s: {t5*1e3:.1f} ms ({5/t5:.0f}x real time)")
+enc = codec.encode_stream()
+for n in (1, 2, 4):
+    steps = 48 // n
+    chunk = wav5[:, :, :n * 1920]
+    enc.reset()
+    for _ in range(4):
+        enc.step(chunk)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        enc.step(chunk)
+    torch.cuda.synchronize()
+    us = (time.perf_counter() - t0) / steps * 1e6
+    counters = [_Counting(mimi_mod.lib), _Counting(ops_mod.lib)]
+    mimi_mod.lib, ops_mod.lib = counters
+    enc.step(chunk)
+    mimi_mod.lib, ops_mod.lib = counters[0]._lib, counters[1]._lib
+    print(f"encode stream step n={n}: {us:.0f} us per step ({us / n:.0f} us per 80-ms frame, {n * 80e3 / us:.0f}x real time), "
+          f"{counters[0].n + counters[1].n} launches per step; 5 s in {62.5 / n * us / 1e3:.1f} ms of steps")
