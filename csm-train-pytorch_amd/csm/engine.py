@@ -781,9 +781,7 @@ class Engine:
             raise ValueError("generate_frame with caches: after the prompt, feed one position per call")
         if getattr(m, "use_hip_graph", True):
             return st.graph_frame(tokens, tokens_mask, temperature, topk, noise)
-        if st.cur + 1 >= m.bb.max_seq_len:          # the decode kernels index LDS and the KV caches with the position
-            raise ValueError("sequence exceeds max_seq_len")
-        st.cur += 1
+        st._advance()
         return self._decode_frame(st, tokens, tokens_mask, temperature, topk, noise)
 
     @torch.no_grad()
@@ -977,89 +975,74 @@ class _DecodeStack:
         table = st.m.rope_table(st.prefix)
         cur, nxt = x, self.xa
         for i in range(c.num_layers):
-            if self.lora is not None and self.lora[i]:
-                cur, nxt = self._lora_layer(i, cur, nxt, table)
-                continue
-            if self.w8 is not None:
-                cur, nxt = self._fp8_layer(i, cur, nxt, table)
-                continue
+            L = self.lora[i] if self.lora is not None else {}
             # five launches per layer (four in the depth decoder): the norms ride in the prologue of the following matrix-vector
             # product, RoPE and the cache append inside the attention kernel, SwiGLU in the epilogue of the w13 product
-            ops.gemv_ex(cur, st.w(f"layers.{i}.attn.qkv"), self.qkv, norm_scale=st.w(f"layers.{i}.sa_norm.scale"), eps=c.norm_eps)
-            if self.fuse_attn:
-                # (depth decoder: <= 32 cached positions - the attention rides in the prologue of the output projection)
+            self._product(i, "attn.qkv", L.get("attn_in"), cur, self.qkv, norm_scale=st.w(f"layers.{i}.sa_norm.scale"), eps=c.norm_eps)
+            if self.fuse_attn and "attn_out" not in L:
+                # (depth decoder: <= 32 cached positions - the attention rides in the prologue of the output projection, always
+                #  on its bf16 weight; an ``attn_out`` group takes the unfused attention and the extended product)
                 ops.gemv_attn(self.qkv, self.k[i], self.v[i], self.pos, table, st.w(f"layers.{i}.attn.output_proj.weight"), self.h, cur,
                               H, KV, hd, pos_host=self.pos_host)
             else:
                 ops.attn_decode_rope(self.qkv, self.k[i], self.v[i], self.o, self.pos, table, H, KV, hd, pos_host=self.pos_host)
-                ops.gemv(self.o, st.w(f"layers.{i}.attn.output_proj.weight"), self.h, residual=cur)
-            ops.gemv_ex(self.h, st.w(f"layers.{i}.mlp.w13"), self.act, norm_scale=st.w(f"layers.{i}.mlp_norm.scale"), eps=c.norm_eps,
-                        swiglu=True)
-            ops.gemv(self.act, st.w(f"layers.{i}.mlp.w2.weight"), nxt, residual=self.h)
+                self._product(i, "attn.output_proj.weight", L.get("attn_out"), self.o, self.h, residual=cur)
+            self._product(i, "mlp.w13", L.get("mlp_in"), self.h, self.act, norm_scale=st.w(f"layers.{i}.mlp_norm.scale"), eps=c.norm_eps,
+                          swiglu=True)
+            self._product(i, "mlp.w2.weight", L.get("mlp_out"), self.act, nxt, residual=self.h)
             cur, nxt = nxt, (self.xb if nxt is self.xa else self.xa)
         if not final_norm:
             return cur
         ops.rmsnorm_fwd(cur, st.w("norm.scale"), self.xf, None, c.norm_eps)
         return self.xf
 
-    def _fp8_layer(self, i, cur, nxt, table):
-        """``step``'s layer ``i`` on e4m3 weights: the same launches with csm_gemv_fp8w in place of csm_gemv_bf16(_ex)."""
-        st, c, q = self.stack, self.stack.c, self.w8
-        H, KV, hd = c.num_heads, c.num_kv_heads, c.head_dim
-        ops.gemv_fp8w(cur, *q[f"layers.{i}.attn.qkv"], self.qkv, norm_scale=st.w(f"layers.{i}.sa_norm.scale"), eps=c.norm_eps)
-        if self.fuse_attn:
-            ops.gemv_attn(self.qkv, self.k[i], self.v[i], self.pos, table, st.w(f"layers.{i}.attn.output_proj.weight"), self.h, cur,
-                          H, KV, hd, pos_host=self.pos_host)
-        else:
-            ops.attn_decode_rope(self.qkv, self.k[i], self.v[i], self.o, self.pos, table, H, KV, hd, pos_host=self.pos_host)
-            ops.gemv_fp8w(self.o, *q[f"layers.{i}.attn.output_proj.weight"], self.h, residual=cur)
-        ops.gemv_fp8w(self.h, *q[f"layers.{i}.mlp.w13"], self.act, norm_scale=st.w(f"layers.{i}.mlp_norm.scale"), eps=c.norm_eps,
-                      swiglu=True)
-        ops.gemv_fp8w(self.act, *q[f"layers.{i}.mlp.w2.weight"], nxt, residual=self.h)
-        return nxt, (self.xb if nxt is self.xa else self.xa)
-
-    def _lora_product(self, G, x, W, y, **kw):
-        """One product of a layer step: plain (``G`` None) or extended by a LoRA group - t = s x^ At, then the same product
-        with (t, Bx, bias) as K-extension (norm prologue, SwiGLU and residual stay fused exactly as in the plain step)."""
+    def _product(self, i, name, G, x, y, **kw):
+        """One product of a layer step, y = epilogue(x^ W^T) with layer ``i``'s weight ``name`` and the caller's fusions (norm
+        prologue, SwiGLU, residual), in the stack's mode.  With a LoRA group ``G`` on the projection: t = s x^ At, then the same
+        product with (t, Bx, bias) as K-extension - two launches, over pointer tables where each row has its own adapter (or
+        none).  Without: the e4m3 copy of the weight where ``attach_fp8`` made one (csm_gemv_fp8w), else the bf16 weight."""
+        name = f"layers.{i}.{name}"
         if G is None:
-            return ops.gemv_ex(x, W, y, **kw)
+            if self.w8 is not None and name in self.w8:
+                return ops.gemv_fp8w(x, *self.w8[name], y, **kw)
+            return ops.gemv_ex(x, self.stack.w(name), y, **kw)
+        W, norm = self.stack.w(name), dict(norm_scale=kw.get("norm_scale"), eps=kw.get("eps", 1e-5))
         if self.lora_rows is not None:
-            # per-row adapters: the same two launches over pointer tables, each row with its own adapter (or none)
             At_tab, Bx_tab, bias_tab, kx, lda, ldb = G
             ra, scale = self.lora_rows
-            ops.lora_project_rows(x, At_tab, self.lt, ra, scale, kx, lda, norm_scale=kw.get("norm_scale"), eps=kw.get("eps", 1e-5))
+            ops.lora_project_rows(x, At_tab, self.lt, ra, scale, kx, lda, **norm)
             return ops.gemv_kext_rows(x, W, y, self.lt, Bx_tab, ra, kx, ldb, bias_tab=bias_tab, **kw)
         At, Bx, bias = G
         t = self.lt[:, :At.shape[1]]
-        ops.lora_project(x, At, t, self.lora_scale, norm_scale=kw.get("norm_scale"), eps=kw.get("eps", 1e-5))
+        ops.lora_project(x, At, t, self.lora_scale, **norm)
         return ops.gemv_kext(x, W, y, t, Bx, bias=bias, **kw)
 
-    def _lora_layer(self, i, cur, nxt, table):
-        """``step``'s layer ``i`` with adapters: each group present runs its projection and the extended product in place of
-        the plain one.  An ``attn_out`` group takes the unfused attention (attn_decode_rope, then the extended product)."""
-        st, c, L = self.stack, self.stack.c, self.lora[i]
-        H, KV, hd = c.num_heads, c.num_kv_heads, c.head_dim
-        self._lora_product(L.get("attn_in"), cur, st.w(f"layers.{i}.attn.qkv"), self.qkv, norm_scale=st.w(f"layers.{i}.sa_norm.scale"),
-                           eps=c.norm_eps)
-        if self.fuse_attn and "attn_out" not in L:
-            ops.gemv_attn(self.qkv, self.k[i], self.v[i], self.pos, table, st.w(f"layers.{i}.attn.output_proj.weight"), self.h, cur,
-                          H, KV, hd, pos_host=self.pos_host)
-        else:
-            ops.attn_decode_rope(self.qkv, self.k[i], self.v[i], self.o, self.pos, table, H, KV, hd, pos_host=self.pos_host)
-            self._lora_product(L.get("attn_out"), self.o, st.w(f"layers.{i}.attn.output_proj.weight"), self.h, residual=cur)
-        self._lora_product(L.get("mlp_in"), self.h, st.w(f"layers.{i}.mlp.w13"), self.act, norm_scale=st.w(f"layers.{i}.mlp_norm.scale"),
-                           eps=c.norm_eps, swiglu=True)
-        self._lora_product(L.get("mlp_out"), self.act, st.w(f"layers.{i}.mlp.w2.weight"), nxt, residual=self.h)
-        return nxt, (self.xb if nxt is self.xa else self.xa)
-
-    def attach_lora(self, lo):
-        """Bind the active adapters of this stack: arena views of every group's At / Bx (read in place, so a captured graph
-        sees what ``load_lora_weights`` or an optimiser writes there) and the group's bias vector in the fused projection's row
-        order, built once here (the same pattern as ``DecodeState.head_t``)."""
-        st, c = self.stack, self.stack.c
+    def _group_bias(self, G):
+        """The bias vector of LoRA group ``G`` in the fused projection's row order (q | k | v stacked, w1 / w3 interleaved), built
+        once at binding (the same pattern as ``DecodeState.head_t``); None where no adapter of the group has a bias."""
+        if all(ad.bias is None for ad in G.adapters.values()):
+            return None
+        c = self.stack.c
         hq, hk, F, d = c.num_heads * c.head_dim, c.num_kv_heads * c.head_dim, c.intermediate_dim, c.embed_dim
         rows = {"q_proj": slice(0, hq), "k_proj": slice(hq, hq + hk), "v_proj": slice(hq + hk, hq + 2 * hk), "output_proj": slice(0, d),
                 "w1": slice(0, 2 * F, 2), "w3": slice(1, 2 * F, 2), "w2": slice(0, d)}
+        bias = torch.zeros(G.Bx.shape[0], dtype=BF16, device=G.Bx.device)
+        for mod, ad in G.adapters.items():
+            if ad.bias is not None:
+                bias[rows[mod]] = ad.bias
+        return bias
+
+    @staticmethod
+    def _check_kx(G):
+        """The K-extension kernels give each of a wave's 64 lanes one 8-element chunk of the extension: at most 512 columns."""
+        if G.kx > 512:
+            raise ValueError(f"generate with LoRA adapters: {G.kx} extension columns in {G.name} (the decode kernels take "
+                             "at most 512: rank x adapters per fused projection)")
+
+    def attach_lora(self, lo):
+        """Bind the active adapters of this stack: arena views of every group's At / Bx (read in place, so a captured graph
+        sees what ``load_lora_weights`` or an optimiser writes there) and the group's bias vector (``_group_bias``)."""
+        st, c = self.stack, self.stack.c
         plan, kmax = [], 0
         for i in range(c.num_layers):
             L = {}
@@ -1067,16 +1050,8 @@ class _DecodeStack:
                 G = lo.group(st.prefix, i, gname)
                 if G is None:
                     continue
-                if G.kx > 512:
-                    raise ValueError(f"generate with LoRA adapters: {G.kx} extension columns in {G.name} (the decode kernels take "
-                                     "at most 512: rank x adapters per fused projection)")
-                bias = None
-                if any(ad.bias is not None for ad in G.adapters.values()):
-                    bias = torch.zeros(G.Bx.shape[0], dtype=BF16, device=G.Bx.device)
-                    for mod, ad in G.adapters.items():
-                        if ad.bias is not None:
-                            bias[rows[mod]] = ad.bias
-                L[gname] = (G.At, G.Bx, bias)
+                self._check_kx(G)
+                L[gname] = (G.At, G.Bx, self._group_bias(G))
                 kmax = max(kmax, G.kx)
             plan.append(L)
         if kmax:
@@ -1089,12 +1064,9 @@ class _DecodeStack:
         whose rows change adapters later (``DecodeState.set_row_adapter``); the tables are then indexed by bank position.
         The adapters used are compacted to indices 0..A-1 (``row_adapter``, -1 = none); per layer and group the device tables
         hold the addresses of each adapter's At / Bx arena views (read in place: a captured graph sees later writes to the
-        adapters' weights) and of its bias in the fused projection's row order (built once here, as ``attach_lora`` does)."""
+        adapters' weights) and of its bias vector (``_group_bias``; address 0 = none)."""
         st, c = self.stack, self.stack.c
         dev = self.k[0].device
-        hq, hk, F, d = c.num_heads * c.head_dim, c.num_kv_heads * c.head_dim, c.intermediate_dim, c.embed_dim
-        rows = {"q_proj": slice(0, hq), "k_proj": slice(hq, hq + hk), "v_proj": slice(hq + hk, hq + 2 * hk), "output_proj": slice(0, d),
-                "w1": slice(0, 2 * F, 2), "w3": slice(1, 2 * F, 2), "w2": slice(0, d)}
         used, idx = list(bank or []), []
         for s in states:
             if s is None:
@@ -1122,26 +1094,13 @@ class _DecodeStack:
                        for G in Gs):
                     raise ValueError(f"per-row LoRA adapters: {st.prefix} layer {i} {gname}: the adapters do not share one layout")
                 kx = Gs[0].kx
-                if kx > 512:
-                    raise ValueError(f"generate with LoRA adapters: {kx} extension columns in {Gs[0].name} (the decode kernels take "
-                                     "at most 512: rank x adapters per fused projection)")
+                self._check_kx(Gs[0])
                 for G in Gs:
                     if G.At.data_ptr() % 16 or G.Bx.data_ptr() % 16 or G.At.stride(1) != 1 or G.Bx.stride(1) != 1:
                         raise ValueError(f"per-row LoRA adapters: {G.name} is not a 16-byte aligned row-major arena view")
-                bias_tab = None
-                if any(ad.bias is not None for G in Gs for ad in G.adapters.values()):
-                    ptrs = []
-                    for G in Gs:
-                        if any(ad.bias is not None for ad in G.adapters.values()):
-                            bias = torch.zeros(G.Bx.shape[0], dtype=BF16, device=dev)
-                            for mod, ad in G.adapters.items():
-                                if ad.bias is not None:
-                                    bias[rows[mod]] = ad.bias
-                            keep.append(bias)
-                            ptrs.append(bias.data_ptr())
-                        else:
-                            ptrs.append(0)
-                    bias_tab = table(ptrs)
+                biases = [self._group_bias(G) for G in Gs]
+                keep += [b for b in biases if b is not None]
+                bias_tab = table([0 if b is None else b.data_ptr() for b in biases]) if any(b is not None for b in biases) else None
                 L[gname] = (table([G.At.data_ptr() for G in Gs]), table([G.Bx.data_ptr() for G in Gs]), bias_tab, kx,
                             Gs[0].At.stride(0), Gs[0].Bx.stride(0))
                 kmax = max(kmax, kx)
@@ -1214,8 +1173,8 @@ class DecodeState:
         self.proj = torch.empty(B, m.dc.embed_dim, dtype=BF16, device=dev)
         self.logits = torch.empty(B, m.vocab_pad, dtype=F32, device=dev)
         self.dpos = [torch.full((B,), i, dtype=torch.int32, device=dev) for i in range(m.args.audio_num_codebooks)]
-        self.cur = -1
-        # slot lifecycle (prefill_row / set_active / serve_frame): each row's position on the host (-1 = nothing prefilled), the
+        # each row's position on the host (-1 = nothing prefilled): the one mirror of the device-side ``bb.pos`` (no sync per frame;
+        # an idle row's device position is pinned, not mirrored).  Slot lifecycle (prefill_row / set_active / serve_frame): the
         # rows that advance (host list + the device vector the idle rows' positions are pinned with), per-row noise generators
         # and the rows the next fill_noise draws for
         self.row_pos = [-1] * B
@@ -1258,6 +1217,38 @@ class DecodeState:
                     self.noise_stage = torch.empty(K, V, dtype=F32, device=self.noise_buf.device)
                 self.noise_buf[:, b].copy_(self.noise_stage.exponential_(1, generator=g))     # two launches per seeded row
 
+    @property
+    def cur(self):
+        """The last position the caches hold, over all rows (-1: nothing prefilled)."""
+        return max(self.row_pos)
+
+    def _advance(self):
+        """The rows of a decode frame (``active_rows``: all of them unless ``set_active`` chose) move one position on, on the host;
+        the device positions move inside the frame (``backbone_step``).  The decode kernels index LDS and the KV caches with the
+        position, so a row at the length limit refuses the frame and nothing moves."""
+        if any(self.row_pos[b] + 1 >= self.e.m.bb.max_seq_len for b in self.active_rows):
+            raise ValueError("sequence exceeds max_seq_len")
+        for b in self.active_rows:
+            self.row_pos[b] += 1
+
+    def _embed(self, tokens, masks, out=None):
+        """The embedded rows [M, d] of [..., K+1] tokens and masks, into ``out`` or a new tensor."""
+        m = self.e.m
+        K1 = tokens.shape[-1]
+        tk = tokens.reshape(-1, K1).to(device=m.device, dtype=torch.int64).contiguous()
+        mk = masks.reshape(-1, K1).to(device=m.device, dtype=torch.uint8).contiguous()
+        h0 = out if out is not None else torch.empty(tk.shape[0], m.bb.embed_dim, dtype=BF16, device=m.device)
+        ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
+        return h0
+
+    def _prompt_forward(self, b, tokens, masks, B, S, save, **kw):
+        """The training forward of the backbone over prompt-side positions, with the adapters generation applies to row ``b``:
+        its own bank adapter, or the model's live ones."""
+        m = self.e.m
+        h0 = self._embed(tokens, masks)
+        with (row_lora(m, self.adapters[b]) if self.adapters is not None else generation_lora(m)):
+            return self.e.backbone.forward(h0, B, S, save, **kw)
+
     def prefill(self, tokens, masks):
         e, m = self.e, self.e.m
         if self.adapters is not None:                        # (per-row adapters: every row's prefill with its own adapter)
@@ -1265,17 +1256,11 @@ class DecodeState:
         B, S, K1 = tokens.shape
         if S > m.bb.max_seq_len:
             raise ValueError("prompt longer than max_seq_len")
-        M = B * S
-        tk = tokens.reshape(M, K1).to(torch.int64).contiguous()
-        mk = masks.reshape(M, K1).to(torch.uint8).contiguous()
-        h0 = torch.empty(M, m.bb.embed_dim, dtype=BF16, device=m.device)
-        ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
-        with generation_lora(m):
-            hidden = e.backbone.forward(h0, B, S, True)
+        hidden = self._prompt_forward(0, tokens, masks, B, S, True)
         self.bb.fill_from(e.backbone.acts, B, S)
         e.backbone.acts = []
         self.bb.pos.fill_(S - 1)
-        self.cur = S - 1                       # host mirror of the device-side position (no sync per frame)
+        self.row_pos[:] = [S - 1] * B
         return hidden.view(B, S, -1)[:, -1, :].contiguous()
 
     def append(self, tokens, masks):
@@ -1284,26 +1269,20 @@ class DecodeState:
         caches (``ops.attn_append``: the rows' K / V are appended, nothing is prefilled again).  Returns the last position's hidden
         row [1, d] for ``Engine._frame_tail``, as ``prefill`` does.  Adapters apply as in ``prefill`` (live ``model.lora``, or
         the state's own bank adapter).  The captured frame graph reads the position from device memory and stays valid."""
-        e, m = self.e, self.e.m
+        m = self.e.m
         if self.B != 1:
             raise ValueError(f"append takes a one-sequence state (this one has {self.B} rows)")
         if self.cur < 0:
             raise RuntimeError("append needs a prefilled state (prefill the first turn)")
-        K1 = tokens.shape[-1]
-        tk = tokens.reshape(-1, K1).to(device=m.device, dtype=torch.int64).contiguous()
-        mk = masks.reshape(-1, K1).to(device=m.device, dtype=torch.uint8).contiguous()
-        n, pos0 = tk.shape[0], self.cur + 1
+        n, pos0 = tokens.numel() // tokens.shape[-1], self.cur + 1
         if n < 1:
             raise ValueError("append needs at least one position")
         if pos0 + n > m.bb.max_seq_len:
             raise ValueError("sequence exceeds max_seq_len")
-        h0 = torch.empty(n, m.bb.embed_dim, dtype=BF16, device=m.device)
-        ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
         pos = torch.arange(pos0, pos0 + n, dtype=torch.int32, device=m.device)
-        with (row_lora(m, self.adapters[0]) if self.adapters is not None else generation_lora(m)):
-            hidden = e.backbone.forward(h0, 1, n, False, pos=pos, append=(self.bb, 0, pos0))
+        hidden = self._prompt_forward(0, tokens, masks, 1, n, False, pos=pos, append=(self.bb, 0, pos0))
         self.bb.pos.fill_(pos0 + n - 1)
-        self.cur = pos0 + n - 1
+        self.row_pos[0] = pos0 + n - 1
         return hidden[-1:].contiguous()
 
     def append_rows(self, rows, tokens_list, masks_list):
@@ -1314,7 +1293,7 @@ class DecodeState:
         is one adapter per forward).  A row that holds nothing (``row_pos[b] == -1``) is refused: first turns go through
         ``prefill_row``.  Returns the segments' last hidden rows [R, d] in the order of ``rows``.  A segment's bits do not depend
         on what is stacked with it; one segment on a one-row state equals ``append``."""
-        e, m = self.e, self.e.m
+        m = self.e.m
         rows = [int(b) for b in rows]
         R = len(rows)
         if not (1 <= R <= 16 and len(tokens_list) == R and len(masks_list) == R):
@@ -1324,7 +1303,7 @@ class DecodeState:
         K1 = tokens_list[0].shape[-1]
         tks = [t.reshape(-1, K1).to(device=m.device, dtype=torch.int64) for t in tokens_list]
         mks = [k.reshape(-1, K1).to(device=m.device, dtype=torch.uint8) for k in masks_list]
-        held = [self.cur if self.B == 1 and self.row_pos[b] < 0 else self.row_pos[b] for b in rows]   # (prefill() keeps cur only)
+        held = [self.row_pos[b] for b in rows]
         ns, pos0s = [t.shape[0] for t in tks], [h + 1 for h in held]
         for b, h, n in zip(rows, held, ns):
             if h < 0:
@@ -1338,16 +1317,11 @@ class DecodeState:
             groups.setdefault(id(self.adapters[b]) if self.adapters is not None else None, []).append(j)
         last = [None] * R
         for idx in groups.values():
-            tk = torch.cat([tks[j] for j in idx], 0).contiguous()
-            mk = torch.cat([mks[j] for j in idx], 0).contiguous()
-            M = tk.shape[0]
-            h0 = torch.empty(M, m.bb.embed_dim, dtype=BF16, device=m.device)
-            ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
             # (host integers only: one arange per segment)
             pos = torch.cat([torch.arange(pos0s[j], pos0s[j] + ns[j], dtype=torch.int32, device=m.device) for j in idx])
             seg = (self.bb, [rows[j] for j in idx], [pos0s[j] for j in idx], [ns[j] for j in idx])
-            with (row_lora(m, self.adapters[rows[idx[0]]]) if self.adapters is not None else generation_lora(m)):
-                hidden = e.backbone.forward(h0, 1, M, False, pos=pos, append=seg)
+            hidden = self._prompt_forward(rows[idx[0]], torch.cat([tks[j] for j in idx]), torch.cat([mks[j] for j in idx]), 1,
+                                          pos.shape[0], False, pos=pos, append=seg)
             end = 0
             for j in idx:
                 end += ns[j]
@@ -1355,7 +1329,6 @@ class DecodeState:
         for b, p0, n in zip(rows, pos0s, ns):
             self.bb.pos[b] = p0 + n - 1
             self.row_pos[b] = p0 + n - 1
-            self.cur = max(self.cur, p0 + n - 1)
         return torch.stack(last).contiguous()
 
     def park_row(self, b, length: int):
@@ -1365,7 +1338,7 @@ class DecodeState:
         b, length = int(b), int(length)
         if not 0 <= b < self.B:
             raise ValueError(f"row {b} out of range (the state has {self.B})")
-        if not 1 <= length <= max(self.row_pos[b], self.cur if self.B == 1 else -1) + 1:
+        if not 1 <= length <= self.row_pos[b] + 1:
             raise ValueError(f"park_row: {length} positions of row {b}, which holds {self.row_pos[b] + 1}")
         return self.bb.kv[:, :, b, :, :length].contiguous()
 
@@ -1383,16 +1356,15 @@ class DecodeState:
         kv[:, :, b, :, :length].copy_(parked)
         self.bb.pos[b] = length - 1
         self.row_pos[b] = length - 1
-        self.cur = max(self.cur, length - 1)
 
     def truncate(self, length: int):
-        """Forget every position from ``length`` on (1 <= length <= cur + 1): the device position and its host mirror move back
-        to ``length - 1``.  Nothing is cleared - cache rows past the position are never read and the next step overwrites them."""
+        """Forget every position from ``length`` on (1 <= length <= cur + 1): every row's device position and host mirror move
+        back to ``length - 1``.  Nothing is cleared - cache rows past the position are never read and the next step overwrites them."""
         length = int(length)
         if not 1 <= length <= self.cur + 1:
             raise ValueError(f"truncate to {length} positions: the caches hold {self.cur + 1}")
         self.bb.pos.fill_(length - 1)
-        self.cur = length - 1
+        self.row_pos[:] = [length - 1] * self.B
 
     def prefill_ragged(self, tokens_list, masks_list):
         """Prompts of different lengths, one per batch row: each is prefilled on its own ([1, S_b] through the training
@@ -1410,17 +1382,11 @@ class DecodeState:
         S = tk.shape[0]
         if S > m.bb.max_seq_len:
             raise ValueError("prompt longer than max_seq_len")
-        tk = tk.to(device=m.device, dtype=torch.int64).contiguous()
-        mk = mk.to(device=m.device, dtype=torch.uint8).contiguous()
-        h0 = torch.empty(S, m.bb.embed_dim, dtype=BF16, device=m.device)
-        ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, m.args.audio_vocab_size)
-        with (row_lora(m, self.adapters[b]) if self.adapters is not None else generation_lora(m)):
-            hidden = e.backbone.forward(h0, 1, S, True)
+        hidden = self._prompt_forward(b, tk, mk, 1, S, True)
         self.bb.fill_row(e.backbone.acts, b, S)
         e.backbone.acts = []
         self.bb.pos[b] = S - 1
         self.row_pos[b] = S - 1
-        self.cur = max(self.cur, S - 1)
         return hidden[-1]
 
     # ---- slot lifecycle: rows that join, idle and leave independently (csm/serving.py) ---------------------------------------
@@ -1491,30 +1457,18 @@ class DecodeState:
         m = self.e.m
         if self.active is None:
             self.set_active(self.active_rows)
-        act = self.active_rows
-        if any(self.row_pos[b] + 1 >= m.bb.max_seq_len for b in act):
-            raise ValueError("sequence exceeds max_seq_len")
         self.bb.pos.mul_(self.active)
-        self.cur = max([self.row_pos[b] for b in act], default=1)       # graph_frame's own check and increment see the active rows
-        self.draw_rows = set(act)
+        self.draw_rows = set(self.active_rows)
         try:
             if getattr(m, "use_hip_graph", True):
-                out = self.graph_frame(tokens, masks, temperature, topk)
-            else:
-                self.cur += 1
-                out = self.e._decode_frame(self, tokens, masks, temperature, topk, None)
+                return self.graph_frame(tokens, masks, temperature, topk)
+            self._advance()
+            return self.e._decode_frame(self, tokens, masks, temperature, topk, None)
         finally:
             self.draw_rows = None
-        for b in act:
-            self.row_pos[b] += 1
-        return out
 
     def backbone_step(self, tokens, masks):
-        m = self.e.m
-        B = tokens.shape[0]
-        tk = tokens.reshape(B, -1).to(torch.int64).contiguous()
-        mk = masks.reshape(B, -1).to(torch.uint8).contiguous()
-        ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), self.h0, m.args.audio_vocab_size)
+        self._embed(tokens, masks, out=self.h0)                 # (the persistent buffer: a captured graph reads it)
         self.bb.pos.add_(1)
         return self.bb.step(self.h0)
 
@@ -1524,9 +1478,7 @@ class DecodeState:
         tokens and the frame's noise live in persistent device buffers, so the same graph serves every frame.  Re-captured
         when temperature / top-k change."""
         m = self.e.m
-        if self.cur + 1 >= m.bb.max_seq_len:
-            raise ValueError("sequence exceeds max_seq_len")
-        self.cur += 1
+        self._advance()
         key = (float(temperature), int(topk))
         if self.graph is None or self.graph_key != key:
             if self.warm < 1 or self.graph_key not in (None, key):

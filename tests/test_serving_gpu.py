@@ -183,3 +183,69 @@ def test_fp8_server_row_equals_fp8_batch(world):
         m.decode_weights = "bf16"
     b = _alone(gen, world["ctx"])
     assert not torch.equal(a.codes(), b.codes())                                      # (FP8 weights change what is said)
+
+
+def test_row_pos_is_the_one_host_mirror_of_the_device_positions(world):
+    """``DecodeState.row_pos`` follows the device position vector through every way a state is filled and advanced - also a
+    multi-row state filled by ``prefill`` - and ``cur`` is its maximum; a row at the length limit refuses its frame and moves
+    nothing, while the other rows still decode."""
+    from csm.engine import DecodeState
+    m = world["m"]
+    e = m.engine
+    amask = torch.cat([torch.ones(2, 1, K, dtype=torch.bool), torch.zeros(2, 1, 1, dtype=torch.bool)], 2).cuda()
+
+    def text_prompt(*shape, seed):
+        tk = torch.zeros(*shape, K + 1, dtype=torch.long)
+        tk[..., -1] = torch.randint(3, 200, shape, generator=torch.Generator().manual_seed(seed))
+        mk = torch.zeros(*shape, K + 1, dtype=torch.bool)
+        mk[..., -1] = True
+        return tk.cuda(), mk.cuda()
+
+    def frame_input(codes):
+        return torch.cat([codes.long(), torch.zeros(2, 1, dtype=torch.long, device="cuda")], 1).unsqueeze(1)
+
+    def mirrored(st):
+        assert st.row_pos == st.bb.pos.tolist() and st.cur == max(st.row_pos)
+
+    # frames after prefill, with the graph (eager, capture, replay) and without
+    st = DecodeState(e, 2)
+    assert st.cur == -1
+    last_h = st.prefill(*text_prompt(2, 5, seed=3))
+    mirrored(st)
+    assert st.row_pos == [4, 4]
+    out = e._frame_tail(st, last_h, TEMP, TOPK, None)
+    m._decode_state = st
+    try:
+        for graph in (True, False):
+            m.use_hip_graph = graph
+            for _ in range(3):
+                out = e.generate_frame(frame_input(out), amask, torch.ones(2, 1, dtype=torch.long), TEMP, TOPK)
+                mirrored(st)
+        assert st.row_pos == [10, 10] and st.graph is not None
+    finally:
+        m.use_hip_graph = True
+        m.reset_caches()
+    # park_row on the prefill-filled state
+    n = st.row_pos[1] + 1
+    assert st.park_row(1, n).shape[3] == n
+    with pytest.raises(ValueError, match="park_row"):
+        st.park_row(1, n + 1)
+    # rows at the length limit
+    limit = m.bb.max_seq_len
+    st = DecodeState(e, 2)
+    st.prefill_row(0, *text_prompt(limit, seed=4))
+    last = st.prefill_row(1, *text_prompt(5, seed=5))
+    mirrored(st)
+    assert st.row_pos == [limit - 1, 4]
+    out = st.serve_first(torch.stack([last, last]), [0, 1], TEMP, TOPK)
+    try:
+        for graph in (True, False):
+            m.use_hip_graph = graph
+            with pytest.raises(ValueError, match="exceeds max_seq_len"):
+                st.serve_frame(frame_input(out), amask, TEMP, TOPK)
+            assert st.row_pos == [limit - 1, 4]
+        st.set_active([1])
+        st.serve_frame(frame_input(out), amask, TEMP, TOPK)
+        assert st.row_pos == [limit - 1, 5] and int(st.bb.pos[1]) == 5
+    finally:
+        m.use_hip_graph = True
