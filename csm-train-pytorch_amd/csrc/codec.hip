@@ -636,6 +636,7 @@ extern "C" int csm_attn_window_stream_rows_f32(const float* qkv, float* kcache, 
 
 extern "C" int csm_transpose_rows_f32(const float* in, float* out, int batch, int R, int C, hipStream_t stream) {
     CSM_REQUIRE(in && out && batch > 0 && batch <= 65535 && R > 0 && C > 0, "csm_transpose_rows_f32: bad arguments");
+    CSM_REQUIRE((R + 31) / 32 <= 65535, "csm_transpose_rows_f32: %d rows exceed the grid (65535 * 32)", R);
     hipLaunchKernelGGL(transpose_f32_kernel, dim3((C + 31) / 32, (R + 31) / 32, batch), dim3(256), 0, stream, in, out, R, C);
     CSM_CHECK_LAUNCH("csm_transpose_rows_f32");
     return 0;
@@ -696,7 +697,7 @@ extern "C" int csm_rope_half_f32(float* qkv, int T, int H, int head_dim, float b
 }
 
 extern "C" int csm_attn_window_f32(const float* qkv, float* out, int T, int H, int head_dim, int window, hipStream_t stream) {
-    CSM_REQUIRE(qkv && out && T > 0 && H > 0 && window > 0 && window <= 8192, "csm_attn_window_f32: bad arguments");
+    CSM_REQUIRE(qkv && out && T > 0 && H > 0 && H <= 65535 && window > 0 && window <= 8192, "csm_attn_window_f32: bad arguments");
     CSM_REQUIRE(head_dim == 64, "csm_attn_window_f32: head_dim %d unsupported (64)", head_dim);
     hipLaunchKernelGGL((attn_f32_kernel<64>), dim3(T, H), dim3(64), (size_t)window * sizeof(float), stream, qkv, out, T, H, window);
     CSM_CHECK_LAUNCH("csm_attn_window_f32");
@@ -757,7 +758,7 @@ extern "C" int csm_conv_transpose1d_stream_f32(const float* hist, const float* x
 
 extern "C" int csm_attn_window_stream_f32(const float* qkv, float* kcache, float* vcache, float* out, int n, int pos0, int H,
                                           int head_dim, int window, int ring, hipStream_t stream) {
-    CSM_REQUIRE(qkv && kcache && vcache && out && n > 0 && pos0 >= 0 && H > 0 && window > 0 && window <= 8192 && n <= 65535,
+    CSM_REQUIRE(qkv && kcache && vcache && out && n > 0 && pos0 >= 0 && H > 0 && H <= 65535 && window > 0 && window <= 8192 && n <= 65535,
                 "csm_attn_window_stream_f32: bad arguments");
     CSM_REQUIRE(ring >= window + n - 1, "csm_attn_window_stream_f32: ring %d < window %d + n %d - 1", ring, window, n);
     CSM_REQUIRE(head_dim == 64, "csm_attn_window_stream_f32: head_dim %d unsupported (64)", head_dim);
@@ -769,6 +770,7 @@ extern "C" int csm_attn_window_stream_f32(const float* qkv, float* kcache, float
 
 extern "C" int csm_transpose_f32(const float* in, float* out, int R, int C, hipStream_t stream) {
     CSM_REQUIRE(in && out && R > 0 && C > 0, "csm_transpose_f32: bad arguments");
+    CSM_REQUIRE((R + 31) / 32 <= 65535, "csm_transpose_f32: %d rows exceed the grid (65535 * 32)", R);
     hipLaunchKernelGGL(transpose_f32_kernel, dim3((C + 31) / 32, (R + 31) / 32), dim3(256), 0, stream, in, out, R, C);
     CSM_CHECK_LAUNCH("csm_transpose_f32");
     return 0;
