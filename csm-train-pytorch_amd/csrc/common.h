@@ -91,6 +91,10 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global load (s_waitcnt vmcnt(0)),
+// which pulls prefetched weight rows and value slices - needed last - in front of it.  The compiler still counts vmcnt for their registers.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // Block-wide sum for blocks of up to 16 waves; `red` is >= 16 floats of LDS. All threads get the result.
 __device__ __forceinline__ float block_sum(float v, float* red) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;

@@ -744,7 +744,7 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
             *reinterpret_cast<float4*>(&xsh[b][lane * 8 + 512 * c + 4]) = make_float4(f[4], f[5], f[6], f[7]);
         }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // (LDS only: the weight rows stay in flight)
+    lds_barrier();                                                           // (LDS only: the weight rows stay in flight)
     csm_f2 acc[RW][NP];
 #pragma unroll
     for (int r = 0; r < RW; ++r)
@@ -928,7 +928,7 @@ __global__ __launch_bounds__(512) void gemv_mfma_kernel(const bf16_t* __restrict
                     ss = wave_sum(ss);
                     if (lane == 0) rs[b] = rsqrtf(ss / (float)K + eps);
                 }
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                lds_barrier();
             }
             if (brow) {
                 const float r = rs[c];
@@ -1326,11 +1326,6 @@ __global__ __launch_bounds__(512) void gemv_attn_kernel(const bf16_t* __restrict
 // stride 272 B: conflict-free); the rotated new key is written into the same LDS image, so that lane takes the same code path
 // instead of a divergent serial dot product.  The arithmetic is gemv_attn_kernel<1, 128>'s operation for operation (same products,
 // same order, same trees): bit-identical.  512 threads: wave w = q head w in the attention (H <= 8); S_max <= 32 (a frame's codebooks).
-// workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global load (its fence is
-// s_waitcnt vmcnt(0)), which here would pull the prefetched value slices and the weight row - needed last - in front of the first
-// barrier.  The compiler still counts vmcnt for the registers those loads fill.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <int HD>
 __global__ __launch_bounds__(512) void gemv_attn_at_kernel(const bf16_t* __restrict__ qkv, bf16_t* kc, bf16_t* vc, int p,
                                                            const float* __restrict__ table, const bf16_t* __restrict__ W,

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(const bf16_t* __restrict_
                     *reinterpret_cast<float4*>(&xsh[wv][16 * lane + 1024 * c + 4 * v]) = make_float4(xf[4 * v], xf[4 * v + 1], xf[4 * v + 2], xf[4 * v + 3]);
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // (LDS only: the weight rows stay in flight)
+        lds_barrier();                                                           // (LDS only: the weight rows stay in flight)
 #pragma unroll
         for (int c = 0; c < KC; ++c) {
             q_f2 xp[NP][16];                                                         // (row 2q, row 2q + 1) of the lane's elements
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(512) void gemv_fp8_mfma_kernel(const bf16_t* __rest
                     ss = wave_sum(ss);
                     if (lane == 0) rs[b] = rsqrtf(ss / (float)K + eps);
                 }
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                lds_barrier();
             }
             if (brow) {
                 const float r = rs[c];
