@@ -28,7 +28,8 @@ LOOP = 4096 * 256                                      # outputs one pass of a g
 # worst error is never taken below 0.5 ulp - the error of a correctly rounded float32 result - so a case whose few inputs
 # happen to evaluate exactly (rsqrt(64)) does not demand more than correct rounding could give: every allowance is >= 2 ulp.
 ALLOWANCE_SOURCE = "4 x worst ulp error of torch float32 CPU vs float64 on the case's own inputs (>= 4 x 0.5 ulp)"
-_F32 = {"expm1f": torch.expm1, "erff": torch.erf, "expf": torch.exp, "rsqrtf": torch.rsqrt, "sinf": torch.sin, "cosf": torch.cos}
+_F32 = {"expm1f": torch.expm1, "erff": torch.erf, "expf": torch.exp, "rsqrtf": torch.rsqrt, "sinf": torch.sin, "cosf": torch.cos,
+        "sqrtf": torch.sqrt, "logf": torch.log}         # the last two serve train_ops_ref.py
 measured = {}                                          # name -> worst ulp error seen so far (for the records)
 
 
