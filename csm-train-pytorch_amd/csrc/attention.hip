@@ -402,7 +402,11 @@ __global__ __launch_bounds__(256, 2) void attn_dkv_kernel(const bf16_t* __restri
         // XCD's workgroups breadth-first (w and w + run/2 share a CU), map 2 depth-first (w and w ^ 1 share a CU).
         const int run = (xcd < r8) ? q8 + 1 : q8, half = run >> 1;
         if (map == 1 && (run & 1) == 0 && half % nkblk == 0 && within >= half) kblk = nkblk - 1 - kblk;
-        if (map == 2 && (nkblk & 1) == 0 && (within & 1)) kblk = nkblk - 1 - (kblk ^ 1);
+        // (the parity is taken from nid, not from within: with nkblk even it is the key block's own parity, so the odd blocks of a
+        //  pair are permuted among themselves whichever XCD runs hold them.  `within & 1` remapped only the items of the pair that
+        //  sat at an odd place of their run: S = 384, 2 kv heads, B = 1 - 12 workgroups - ran key block 5 of the second pair
+        //  twice and block 1 never, leaving its dK / dV rows unwritten.  The same choice wherever a run starts at an even nid.)
+        if (map == 2 && (nkblk & 1) == 0 && (nid & 1)) kblk = nkblk - 1 - (kblk ^ 1);
         int pair_ = pair;
         const int base = nid - within;
         if (map == 3 && run % nkblk == 0 && base % nkblk == 0) {      // heaviest key blocks of every (b, kv-head) of the run first

@@ -163,7 +163,7 @@ def rope_table(max_seq_len: int, head_dim: int, base: float = 500_000.0, scale: 
 
 def rope(x: torch.Tensor, table: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
     """Interleaved-pair rotation.  x [B,S,H,hd]; table [P,hd/2,2]; pos [B,S] int."""
-    xs = x.float().reshape(*x.shape[:-1], -1, 2)
+    xs = (x if x.dtype == torch.float64 else x.float()).reshape(*x.shape[:-1], -1, 2)  # float64 stays float64 (the tests' references)
     t = table[pos].unsqueeze(2)  # [B,S,1,hd/2,2]
     out = torch.stack(
         [xs[..., 0] * t[..., 0] - xs[..., 1] * t[..., 1],
@@ -189,7 +189,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = 
     if causal:
         m = torch.tril(torch.ones(S, S, dtype=torch.bool))
         s = s.masked_fill(~m, float("-inf"))
-    p = torch.softmax(s.float(), dim=-1).type_as(q)
+    p = torch.softmax(s if s.dtype == torch.float64 else s.float(), dim=-1).type_as(q)  # float64 stays float64
     return (p @ v).transpose(1, 2)
 
 
