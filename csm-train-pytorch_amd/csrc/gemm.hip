@@ -310,6 +310,9 @@ static int gemm_dispatch(const void* A, const void* B, void* C, const void* R, i
     if (epilogue == 1) CSM_REQUIRE(!out_f32 && aux_out && (N & 3) == 0 && (ldc & 3) == 0 && ld_aux >= N / 2 && (ld_aux & 1) == 0, "csm_gemm_bf16_ex: bad SwiGLU-forward epilogue arguments");
     if (epilogue == 2) CSM_REQUIRE(!out_f32 && aux_in && (N & 3) == 0 && (ldc & 7) == 0 && (ld_aux & 7) == 0 && ld_aux >= 2 * N && !R && ((uintptr_t)aux_in & 15) == 0 && ((uintptr_t)C & 15) == 0, "csm_gemm_bf16_ex: bad SwiGLU-backward epilogue arguments");
     CSM_REQUIRE(epilogue >= 0 && epilogue <= 3, "csm_gemm_bf16_ex: unknown epilogue %d", epilogue);
+    // (the element-by-element store path that a residual with ldr % 4 != 0 selects adds R and stores, nothing else: it would
+    //  leave aux_out unwritten and the q / k columns unrotated)
+    if (epilogue == 1 || epilogue == 3) CSM_REQUIRE(!R || (ldr & 3) == 0, "csm_gemm_bf16: a residual under the SwiGLU-forward / RoPE epilogue needs ldr %% 4 == 0 (ldr=%d)", ldr);
     // variant 4: the four-wave 256x256 kernel with the hand-scheduled K loop (gemm256w4.hip), where it applies
     // (the four-wave kernel beats the 128x128 one from 1.5 rounds of tiles on: fused q|k|v forward, 384 tiles, 97 vs 115 us)
     if (((variant == 2 && g_gemm_w4 && prefer_256(M, N, K, batch, 0.70)) || (variant == 4 && K % 64 == 0 && M >= 8 && N >= 8)) && (kx == 0 || g_w4_kext))

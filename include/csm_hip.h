@@ -35,7 +35,7 @@ int csm_device_check(int device);
  * and torch.mm(decoder_h, audio_head[i-1]) (src/csm/models/model.py:124-126,172,184,187), their autograd
  * backward products, and the LoRA A/B products of src/csm/mlx/components/lora.py:71-105.
  * R (bf16, ldr) may alias C (accumulate).  lda/ldb multiples of 8; the contiguous dimension of A and of B a
- * multiple of 8. */
+ * multiple of 8.  Under the SwiGLU-forward and RoPE epilogues below a residual needs ldr % 4 == 0 (refused otherwise). */
 int csm_gemm_bf16(const void* A, const void* B, void* C, const void* R, int M, int N, int K, int lda, int ldb, int ldc,
                   int ldr, int transA, int transB, int out_f32, float alpha, int batch, long long strideA,
                   long long strideB, long long strideC, long long strideR, csm_stream_t stream);
