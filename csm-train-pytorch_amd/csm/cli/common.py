@@ -21,6 +21,7 @@ from ..data import SyntheticCSMDataset, collate_variable_length
 class TokenFileDataset(Dataset):
     def __init__(self, items):
         self.items = items
+        self.collate = collate_variable_length        # what get_batch collates with (--pack-sequences swaps in collate_packed)
 
     def __len__(self):
         return len(self.items)
@@ -29,7 +30,7 @@ class TokenFileDataset(Dataset):
         return self.items[i]
 
     def get_batch(self, batch_idx, batch_size):   # protocol of CSMLoRATrainer.train
-        return collate_variable_length([self.items[(batch_idx * batch_size + j) % len(self.items)] for j in range(batch_size)])
+        return self.collate([self.items[(batch_idx * batch_size + j) % len(self.items)] for j in range(batch_size)])
 
 
 def add_data_args(parser, context_turns: int = 0):
@@ -46,6 +47,9 @@ def add_data_args(parser, context_turns: int = 0):
     g.add_argument("--text-tokenizer", type=str, default=None, help="local directory of the Llama-3.2 tokenizer files")
     g.add_argument("--context-turns", type=int, default=context_turns, help="previous utterances of the same file given as context")
     g.add_argument("--ignore-padding", action="store_true", help="pad targets with -100 so padded frames leave the loss")
+    g.add_argument("--pack-sequences", action="store_true",
+                   help="pack several examples into each row of --max-seq-len positions (segment-masked attention, RoPE restarting per "
+                        "example) instead of padding to the batch maximum; implies --ignore-padding")
 
 
 def load_raw_examples(args, logger=None):

@@ -79,6 +79,14 @@ def main(argv=None):
     trainer.logger.setLevel(logging.DEBUG if args.debug else getattr(logging, args.log_level.upper(), logging.INFO))
     trainer.model.acoustic_mode = args.acoustic_mode
     train_ds, val_ds = load_datasets(args)
+    if args.pack_sequences:                        # several examples per row (data.collate_packed); implies the ignore index
+        from functools import partial
+        from ..data import collate_packed
+        from ..data.training_data import IGNORE_INDEX
+        trainer.model.target_ignore_index = IGNORE_INDEX
+        for ds in (train_ds, val_ds):
+            if ds is not None:
+                ds.collate = partial(collate_packed, max_seq_len=min(args.max_seq_len, trainer.model.bb.max_seq_len))
     trainer.prepare_optimizer()
     best = trainer.train(train_ds, val_ds, batch_size=args.batch_size, epochs=args.epochs, val_every=args.val_every,
                          save_every=args.save_every, max_grad_norm=args.max_grad_norm, resume_from=args.resume_from)

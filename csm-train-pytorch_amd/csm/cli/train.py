@@ -57,7 +57,8 @@ def main(argv=None):
         trainer.model = Model(csm_1b_args(), device=device, seed=0)
     trainer.model.acoustic_mode = args.acoustic_mode
     trainer.num_workers = args.num_workers
-    trainer.ignore_padding = args.ignore_padding
+    trainer.ignore_padding = args.ignore_padding or args.pack_sequences
+    trainer.pack_sequences, trainer.max_seq_len = args.pack_sequences, args.max_seq_len
     train_ds, val_ds = load_datasets(args)
     trainer.prepare_optimizer(freeze_backbone=args.freeze_backbone, freeze_decoder=args.freeze_decoder,
                               freeze_embeddings=args.freeze_embeddings)

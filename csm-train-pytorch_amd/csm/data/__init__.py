@@ -7,10 +7,11 @@ from .training_data import (
     LengthBucketSampler,
     create_dataloader,
     collate_variable_length,
+    collate_packed,
     load_audio,
     resample,
 )
 from .synthetic import SyntheticCSMDataset
 
 __all__ = ["TrainingExample", "CSMDataProcessor", "ContextualExampleGenerator", "CSMDataset", "LengthBucketSampler",
-           "create_dataloader", "collate_variable_length", "load_audio", "resample", "SyntheticCSMDataset"]
+           "create_dataloader", "collate_variable_length", "collate_packed", "load_audio", "resample", "SyntheticCSMDataset"]

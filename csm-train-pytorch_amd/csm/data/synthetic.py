@@ -11,6 +11,7 @@ class SyntheticCSMDataset(Dataset):
     def __init__(self, n_items: int, seq_len: int, text_vocab: int = 128256, audio_vocab: int = 2051, n_codebooks: int = 32,
                  seed: int = 1234, n_segments: int = 2):
         self.n, self.S, self.tv, self.av, self.K, self.seed, self.nseg = n_items, seq_len, text_vocab, audio_vocab, n_codebooks, seed, n_segments
+        self.collate = collate_variable_length        # what get_batch collates with (the CLIs swap in collate_packed)
 
     def __len__(self):
         return self.n
@@ -41,4 +42,4 @@ class SyntheticCSMDataset(Dataset):
     # protocol consumed by CSMLoRATrainer.train (reference training/data.py:364-388)
     def get_batch(self, batch_idx: int, batch_size: int):
         items = [self[(batch_idx * batch_size + j) % self.n] for j in range(batch_size)]
-        return collate_variable_length(items)
+        return self.collate(items)

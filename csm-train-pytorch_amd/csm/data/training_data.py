@@ -257,6 +257,56 @@ def collate_variable_length(batch: List[Dict[str, torch.Tensor]], target_pad: in
     return {"input_tokens": tokens, "input_masks": masks, "target_audio_tokens": targets}
 
 
+def collate_packed(batch: List[Dict[str, torch.Tensor]], max_seq_len: int = 2048, target_pad: int = IGNORE_INDEX) -> Dict[str, torch.Tensor]:
+    """Sequence packing: several examples share one row, each attends only to itself and has RoPE positions of its own (the
+    engine's ``segment_lengths`` path), so no position is spent on padding up to the batch maximum.
+
+    First-fit over the examples sorted by decreasing input length (ties keep the batch order: deterministic); rows are opened as
+    needed; the row length S is the longest row rounded up to a multiple of 128, capped at ``max_seq_len``.  An example longer than
+    ``max_seq_len`` raises.  Returns ``input_tokens`` [R, S, K+1], ``input_masks``, ``target_audio_tokens`` [R, S, K] and
+    ``segment_lengths`` [R, n_max] (a row's segment lengths in order, zero-padded).
+
+    Targets follow the position-indexed label convention of ``forward_loss`` (position p is labelled by ``targets[p]``, the last
+    position of a sequence by nothing), applied per segment: for example i of input length S_i with T_i target frames at row
+    offset o_i, positions o_i + p, p < min(S_i - 1, T_i), carry ``targets_i[p]`` and every other position - each segment's last one
+    and the row padding included - carries ``target_pad`` (IGNORE_INDEX: ``model.target_ignore_index`` must be set)."""
+    lens = [int(b["input_tokens"].shape[0]) for b in batch]
+    for i, n in enumerate(lens):
+        if n > max_seq_len:
+            raise ValueError(f"example {i} has {n} positions, more than max_seq_len = {max_seq_len}")
+        if n < 1:
+            raise ValueError(f"example {i} is empty")
+    rows: List[List[int]] = []
+    room: List[int] = []
+    for i in sorted(range(len(batch)), key=lambda i: -lens[i]):   # (sorted is stable: ties keep the batch order)
+        r = next((r for r in range(len(rows)) if room[r] >= lens[i]), None)
+        if r is None:
+            rows.append([])
+            room.append(max_seq_len)
+            r = len(rows) - 1
+        rows[r].append(i)
+        room[r] -= lens[i]
+    S = min(max_seq_len, -(-max(max_seq_len - x for x in room) // 128) * 128)
+    k1 = batch[0]["input_tokens"].shape[1]
+    k = batch[0]["target_audio_tokens"].shape[1]
+    R = len(rows)
+    tokens = torch.zeros(R, S, k1, dtype=torch.long)
+    masks = torch.zeros(R, S, k1, dtype=torch.bool)
+    targets = torch.full((R, S, k), target_pad, dtype=torch.long)
+    seg = torch.zeros(R, max(len(r) for r in rows), dtype=torch.long)
+    for r, members in enumerate(rows):
+        o = 0
+        for j, i in enumerate(members):
+            b, n = batch[i], lens[i]
+            t = min(n - 1, int(b["target_audio_tokens"].shape[0]))
+            tokens[r, o:o + n] = b["input_tokens"]
+            masks[r, o:o + n] = b["input_masks"]
+            targets[r, o:o + t] = b["target_audio_tokens"][:t]
+            seg[r, j] = n
+            o += n
+    return {"input_tokens": tokens, "input_masks": masks, "target_audio_tokens": targets, "segment_lengths": seg}
+
+
 class LengthBucketSampler(Sampler):
     """Batches of similar length: indices are sorted by length inside windows of ``bucket_batches`` batches, cut into
     batches, and the batches shuffled - so zero padding (and the work spent on it) stays small.  Deterministic per
@@ -294,11 +344,15 @@ class LengthBucketSampler(Sampler):
 
 
 def create_dataloader(dataset: Dataset, batch_size: int, shuffle: bool = True, num_workers: int = 2, pin_memory: bool = True,
-                      bucket_by_length: bool = False, target_pad: int = 0) -> DataLoader:
+                      bucket_by_length: bool = False, target_pad: int = 0, pack_sequences: bool = False,
+                      max_seq_len: int = 2048) -> DataLoader:
     """Reference ``create_dataloader`` (training_data.py:361-376).  ``bucket_by_length`` swaps the plain shuffle for
-    :class:`LengthBucketSampler` (needs ``dataset.lengths()``)."""
+    :class:`LengthBucketSampler` (needs ``dataset.lengths()``).  ``pack_sequences`` collates with :func:`collate_packed` into rows
+    of at most ``max_seq_len`` positions (``batch_size`` stays the number of examples drawn per step)."""
     from functools import partial
     collate = collate_variable_length if target_pad == 0 else partial(collate_variable_length, target_pad=target_pad)
+    if pack_sequences:
+        collate = partial(collate_packed, max_seq_len=max_seq_len)
     if bucket_by_length:
         sampler = LengthBucketSampler(dataset.lengths(), batch_size, shuffle=shuffle)
         return DataLoader(dataset, batch_sampler=sampler, num_workers=num_workers, pin_memory=pin_memory, collate_fn=collate)

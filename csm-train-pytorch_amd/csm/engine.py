@@ -117,8 +117,10 @@ class _Stack:
 
     # -------------------------------------------------------------------------------------------- forward
     def forward(self, x: torch.Tensor, B: int, S: int, save: bool, pos: Optional[torch.Tensor] = None,
-                fuse_rope: bool = True, on_layer_start=None, append=None) -> torch.Tensor:
-        """``append`` = (decode stack, batch row, pos0): the S rows are positions pos0 .. pos0+S-1 of the sequence whose earlier
+                fuse_rope: bool = True, on_layer_start=None, append=None, seg=None) -> torch.Tensor:
+        """``seg`` = a ``Segments`` (packed rows): attention goes through the segment-masked kernels (``ops.attn_fwd_seg``) and RoPE
+        through the un-fused path with the segment-local positions ``seg.pos``; everything else is unchanged.
+        ``append`` = (decode stack, batch row, pos0): the S rows are positions pos0 .. pos0+S-1 of the sequence whose earlier
         positions sit in that stack's KV caches (B = 1, ``pos`` given, nothing saved) - every layer's attention appends its K / V
         rows to the caches and attends to them (``ops.attn_append``) instead of the from-scratch ``ops.attn_fwd``.
         The ragged form ``append`` = (decode stack, rows, pos0s, ns) with three equally long lists of host integers stacks R <= 16
@@ -127,6 +129,9 @@ class _Stack:
         segment's rows have the bits they would have in a forward of their own, whatever is stacked beside them."""
         c, dev = self.c, x.device
         M, d = x.shape
+        if seg is not None:
+            assert pos is None and append is None
+            pos = seg.pos
         pin = append is not None and isinstance(append[1], (list, tuple))
         H, KV, hd, F = c.num_heads, c.num_kv_heads, c.head_dim, c.intermediate_dim
         table = self.m.rope_table(self.prefix)
@@ -162,7 +167,10 @@ class _Stack:
             o = torch.empty(M, H * hd, dtype=BF16, device=dev)
             if append is None:
                 lse = torch.empty(B, H, S, dtype=F32, device=dev)
-                ops.attn_fwd(qkv, o, lse, B, S, H, KV, hd)
+                if seg is not None:
+                    ops.attn_fwd_seg(qkv, o, lse, seg.seg_start, B, S, H, KV, hd)
+                else:
+                    ops.attn_fwd(qkv, o, lse, B, S, H, KV, hd)
             else:
                 assert B == 1 and pos is not None and not save
                 lse = None
@@ -238,7 +246,7 @@ class _Stack:
 
     # -------------------------------------------------------------------------------------------- backward
     def backward(self, dxf: torch.Tensor, B: int, S: int, train_base: bool, alpha: float,
-                 pos: Optional[torch.Tensor] = None, on_layer_done=None, acc: bool = True) -> torch.Tensor:
+                 pos: Optional[torch.Tensor] = None, on_layer_done=None, acc: bool = True, seg=None) -> torch.Tensor:
         """dxf = gradient w.r.t. the final-norm output.  Returns the gradient w.r.t. the stack input.
         Weight gradients are added to the gradient arena (``acc``) or overwrite what it holds (``acc=False``: the first
         backward after a lazy optimizer step, which left consumed gradients behind instead of zeros); the incoming
@@ -386,7 +394,10 @@ class _Stack:
                 if ad is not None:
                     ad.backward(a["o"], dh, a["t_output_proj"], do)
             dqkv = torch.empty(M, c.qkv_dim, dtype=BF16, device=dev)
-            if pos is None and FUSE_ROPE_BWD:     # positions = arange(S): the RoPE backward rides in the dQ / dK epilogues
+            if seg is not None:                   # packed rows: segment-masked kernels, segment-local positions
+                ops.attn_bwd_seg(a["qkv"], a["o"], do, a["lse"], dqkv, delta, seg.seg_start, seg.seg_end, B, S, H, KV, hd)
+                ops.rope(dqkv, table, S, H + KV, hd, pos=seg.pos, inverse=True)
+            elif pos is None and FUSE_ROPE_BWD:   # positions = arange(S): the RoPE backward rides in the dQ / dK epilogues
                 ops.attn_bwd(a["qkv"], a["o"], do, a["lse"], dqkv, delta, B, S, H, KV, hd, rope_table=table)
             else:
                 ops.attn_bwd(a["qkv"], a["o"], do, a["lse"], dqkv, delta, B, S, H, KV, hd)
@@ -440,6 +451,33 @@ class _Stack:
         return dx
 
 
+class Segments:
+    """The descriptor of a packed batch (several examples per row, each attending only to itself), built on the host from
+    ``segment_lengths`` [B, n_max] - per row the lengths of its segments in order, zero-padded - and copied to the device once:
+    ``seg_start`` / ``seg_end`` [B*S] int32 = the first / last position (row-local) of the position's segment, ``pos`` = the position
+    inside the segment (RoPE restarts at 0).  What a row's segments leave over is padding and becomes one more segment, so the
+    arrays are total and every attention output is finite."""
+
+    def __init__(self, segment_lengths, B: int, S: int, device):
+        L = torch.as_tensor(segment_lengths).detach().to("cpu")
+        if L.dim() != 2 or L.shape[0] != B or L.is_floating_point() or L.dtype == torch.bool:
+            raise ValueError(f"segment_lengths must be an integer tensor [B={B}, n_max], got {tuple(L.shape)} {L.dtype}")
+        L = L.to(torch.int64)
+        nz = L != 0
+        if bool((L < 0).any()) or bool((nz[:, 1:] & ~nz[:, :-1]).any()):
+            raise ValueError("segment_lengths: every length before a row's zero padding must be at least 1")
+        tot = L.sum(1)
+        if bool((tot > S).any()):
+            raise ValueError(f"segment_lengths: a row's segments sum to {int(tot.max())}, more than the {S} positions of a row")
+        full = torch.cat([L, (S - tot)[:, None]], 1)                           # the remainder of a row: one more segment
+        lens, starts = full.reshape(-1), (full.cumsum(1) - full).reshape(-1)
+        first = torch.repeat_interleave(starts, lens)                          # [B*S]: zero-length entries vanish
+        last = torch.repeat_interleave(starts + lens - 1, lens)
+        host = torch.stack([first, last, torch.arange(S).repeat(B) - first]).to(torch.int32)
+        dev_ = host.to(device, non_blocking=True)
+        self.seg_start, self.seg_end, self.pos = dev_[0], dev_[1], dev_[2]
+
+
 class Engine:
     def __init__(self, model):
         self.m = model
@@ -460,8 +498,12 @@ class Engine:
 
     # -------------------------------------------------------------------------------------------- loss forward
     def forward_loss(self, tokens: torch.Tensor, masks: torch.Tensor, targets: torch.Tensor, semantic_weight: float,
-                     acoustic_weight: float, save: bool, acoustic_rows: Optional[torch.Tensor] = None):
-        """Forward of ``compute_loss``.  Returns (total, semantic, acoustic) as 0-d fp32 GPU tensors."""
+                     acoustic_weight: float, save: bool, acoustic_rows: Optional[torch.Tensor] = None, segment_lengths=None):
+        """Forward of ``compute_loss``.  Returns (total, semantic, acoustic) as 0-d fp32 GPU tensors.
+        ``segment_lengths`` [B, n_max] (host integers, zero-padded; ``collate_packed``) marks a packed batch: every row holds several
+        examples one after the other, each attends only to itself and has RoPE positions of its own (``Segments``).  The labels
+        stay position-indexed, so a packed batch needs ``model.target_ignore_index``: each segment's last position and the row
+        padding carry it."""
         m, a = self.m, self.m.args
         dev = m.device
         B, S, K1 = tokens.shape
@@ -475,6 +517,13 @@ class Engine:
         tk = tokens.reshape(M, K1).to(device=dev, dtype=torch.int64).contiguous()
         mk = masks.reshape(M, K1).to(device=dev, dtype=torch.uint8).contiguous()
         ign = getattr(m, "target_ignore_index", None)     # None: reference behaviour, every row counts (utils.py:102-105)
+        seg = None
+        if segment_lengths is not None:
+            if ign is None:
+                raise ValueError("a packed batch (segment_lengths) has unlabelled positions by construction: set model.target_ignore_index")
+            if m.bb.head_dim != 64:
+                raise ValueError(f"packed batches need a backbone head_dim of 64 (the segment-masked attention kernels), not {m.bb.head_dim}")
+            seg = Segments(segment_lengths, B, S, dev)     # built and copied once per step; nothing is cached on the layout
         self._validate_batch(tokens, masks, targets, ign)
         tg = targets.to(device=dev, dtype=torch.int64)
 
@@ -483,7 +532,7 @@ class Engine:
         h0 = torch.empty(M, d, dtype=BF16, device=dev)
         self._need("embeddings", -1)
         ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, V)
-        hidden = self.backbone.forward(h0, B, S, save, on_layer_start=self.param_hook)
+        hidden = self.backbone.forward(h0, B, S, save, on_layer_start=self.param_hook, seg=seg)
 
         # codebook-0 head + CE over positions [0, S-1) of every sequence (reference utils.py:96-106)
         logits = torch.empty(M, Vp, dtype=F32, device=dev)
@@ -507,7 +556,7 @@ class Engine:
             ops.reduce_sum(dec["rows_loss"], ac, 1.0 / dec["n_rows"])
         total = semantic_weight * sem + acoustic_weight * ac
         if save:
-            self.saved = dict(B=B, S=S, tk=tk, mk=mk, hidden=hidden, logits=logits, t0=t0, n_sem=n_sem, dec=dec,
+            self.saved = dict(B=B, S=S, tk=tk, mk=mk, hidden=hidden, logits=logits, t0=t0, n_sem=n_sem, dec=dec, seg=seg,
                               sw=float(semantic_weight), aw=float(acoustic_weight))
         return total[0], sem[0], ac[0]
 
@@ -681,7 +730,7 @@ class Engine:
             self.grad_hook("other", -1)
 
         # ---- backbone
-        dh0 = self.backbone.backward(dhid, B, S, tr["backbone"], 1.0, on_layer_done=self.grad_hook, acc=acc["backbone"])
+        dh0 = self.backbone.backward(dhid, B, S, tr["backbone"], 1.0, on_layer_done=self.grad_hook, acc=acc["backbone"], seg=s.get("seg"))
         if train_embeddings:
             self._embedding_backward(s, dh0, dseq if (dec is not None and s["aw"] != 0.0) else None)
         if self.grad_hook is not None:

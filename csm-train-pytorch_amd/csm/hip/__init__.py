@@ -59,6 +59,8 @@ _SIGS = {
     "csm_attn_fwd": ([_p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "csm_attn_bwd": ([_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "csm_attn_bwd_rope": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "csm_attn_fwd_seg": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "csm_attn_bwd_seg": ([_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "csm_swiglu_fwd": ([_p, _p, _ll, _i, _p], _i),
     "csm_swiglu_bwd": ([_p, _p, _p, _ll, _i, _p], _i),
     "csm_embed_fwd": ([_p, _p, _p, _p, _p, _ll, _i, _i, _i, _p], _i),

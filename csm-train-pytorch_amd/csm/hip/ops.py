@@ -325,6 +325,30 @@ def attn_bwd(qkv, out, dout, lse, dqkv, delta_ws, B, S, H, KV, HD, rope_table=No
     return dqkv
 
 
+def _seg_array(t, B, S):
+    assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == B * S, "segment array: int32 [B*S] on the device"
+    return t.data_ptr()
+
+
+def attn_fwd_seg(qkv, out, lse, seg_start, B, S, H, KV, HD):
+    """attn_fwd on packed rows: key j is visible to query i iff seg_start[i] <= j <= i (int32 [B*S], row-local).  head_dim 64."""
+    assert qkv.is_contiguous() and out.is_contiguous() and qkv.shape == (B * S, (H + 2 * KV) * HD)
+    check(lib.csm_attn_fwd_seg(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), _seg_array(seg_start, B, S), B, S, H, KV, HD, _stream()),
+          "csm_attn_fwd_seg")
+    return out
+
+
+def attn_bwd_seg(qkv, out, dout, lse, dqkv, delta_ws, seg_start, seg_end, B, S, H, KV, HD):
+    """attn_bwd on packed rows (seg_end [B*S]: the last position of the position's segment); dqkv is the gradient of the rotated
+    rows - there is no fused RoPE form."""
+    assert qkv.is_contiguous() and out.is_contiguous() and dout.is_contiguous() and dqkv.is_contiguous()
+    need = lib.csm_attn_bwd_workspace_bytes(B, S, H)
+    assert delta_ws.dtype == torch.float32 and delta_ws.is_contiguous() and delta_ws.numel() * 4 >= need, f"delta_ws: {need} bytes of scratch"
+    check(lib.csm_attn_bwd_seg(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), delta_ws.data_ptr(),
+                               _seg_array(seg_start, B, S), _seg_array(seg_end, B, S), B, S, H, KV, HD, _stream()), "csm_attn_bwd_seg")
+    return dqkv
+
+
 def swiglu_fwd(gu, out):
     M, F2 = gu.shape
     check(lib.csm_swiglu_fwd(gu.data_ptr(), out.data_ptr(), M, F2 // 2, _stream()), "csm_swiglu_fwd")

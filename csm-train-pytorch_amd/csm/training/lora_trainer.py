@@ -109,7 +109,8 @@ class CSMLoRATrainer:
         if self.grad_sync is not None:
             self.grad_sync.arm(True)
         loss, _ = compute_loss(m, _to_torch(batch["input_tokens"]), _to_torch(batch["input_masks"]),
-                               _to_torch(batch["target_audio_tokens"]), self.semantic_weight, self.acoustic_weight)
+                               _to_torch(batch["target_audio_tokens"]), self.semantic_weight, self.acoustic_weight,
+                               segment_lengths=batch.get("segment_lengths"))
         m.engine.backward(1.0 / (self.grad_sync.world_size if self.grad_sync is not None else 1))
         if self.grad_sync is not None:
             self.grad_sync.finish()
@@ -182,7 +183,8 @@ class CSMLoRATrainer:
                 for i in range(n):
                     b = val_dataset.get_batch(i, batch_size)
                     loss, _ = compute_loss(self.model, _to_torch(b["input_tokens"]), _to_torch(b["input_masks"]),
-                                           _to_torch(b["target_audio_tokens"]), self.semantic_weight, self.acoustic_weight)
+                                           _to_torch(b["target_audio_tokens"]), self.semantic_weight, self.acoustic_weight,
+                                           segment_lengths=b.get("segment_lengths"))
                     total += float(loss)
         finally:
             self.model.lora.training = True

@@ -113,7 +113,7 @@ class CSMTrainer:
             self.grad_sync.note_batch(batch["input_tokens"], batch["input_masks"])
             self.grad_sync.arm(is_boundary)
         loss, details = compute_loss(m, batch["input_tokens"], batch["input_masks"], batch["target_audio_tokens"],
-                                     self.semantic_weight, self.acoustic_weight)
+                                     self.semantic_weight, self.acoustic_weight, segment_lengths=batch.get("segment_lengths"))
         scale = 1.0 / accumulation_steps
         if self.grad_sync is not None:
             scale /= self.grad_sync.world_size
@@ -134,9 +134,13 @@ class CSMTrainer:
         nw = getattr(self, "num_workers", 2)
         # ignore_padding (not in the reference): pad targets with -100 so padded frames leave the loss
         pad = 0
-        if getattr(self, "ignore_padding", False):
+        # pack_sequences (not in the reference): several examples per row of max_seq_len positions (data.collate_packed); a
+        # packed batch has unlabelled positions by construction, so it sets the ignore index as ignore_padding does
+        pack = bool(getattr(self, "pack_sequences", False))
+        if getattr(self, "ignore_padding", False) or pack:
             from ..data.training_data import IGNORE_INDEX
             pad = self.model.target_ignore_index = IGNORE_INDEX
+        packing = dict(pack_sequences=True, max_seq_len=min(getattr(self, "max_seq_len", 2048), self.model.bb.max_seq_len)) if pack else {}
         sampler = None
         rank0 = (not GradSync.active()) or torch.distributed.get_rank() == 0
         if GradSync.active():
@@ -144,13 +148,14 @@ class CSMTrainer:
             from functools import partial
             from torch.utils.data import DataLoader
             from torch.utils.data.distributed import DistributedSampler
-            from ..data import collate_variable_length
+            from ..data import collate_packed, collate_variable_length
             sampler = DistributedSampler(train_dataset, shuffle=True, drop_last=True)
+            collate = partial(collate_packed, max_seq_len=packing["max_seq_len"]) if pack else partial(collate_variable_length, target_pad=pad)
             train_loader = DataLoader(train_dataset, batch_size=batch_size, sampler=sampler, num_workers=nw,
-                                      collate_fn=partial(collate_variable_length, target_pad=pad), pin_memory=True, drop_last=True)
+                                      collate_fn=collate, pin_memory=True, drop_last=True)
         else:
-            train_loader = create_dataloader(train_dataset, batch_size=batch_size, shuffle=True, num_workers=nw, target_pad=pad)
-        val_loader = (create_dataloader(val_dataset, batch_size=batch_size, shuffle=False, num_workers=nw, target_pad=pad)
+            train_loader = create_dataloader(train_dataset, batch_size=batch_size, shuffle=True, num_workers=nw, target_pad=pad, **packing)
+        val_loader = (create_dataloader(val_dataset, batch_size=batch_size, shuffle=False, num_workers=nw, target_pad=pad, **packing)
                       if val_dataset else None)
         if self.optimizer is None:
             self.prepare_optimizer()
@@ -223,7 +228,7 @@ class CSMTrainer:
         with torch.no_grad():
             for batch in val_loader:
                 loss, _ = compute_loss(self.model, batch["input_tokens"], batch["input_masks"], batch["target_audio_tokens"],
-                                       self.semantic_weight, self.acoustic_weight)
+                                       self.semantic_weight, self.acoustic_weight, segment_lengths=batch.get("segment_lengths"))
                 total += float(loss)
                 n += 1
         self.model.train()

@@ -702,6 +702,48 @@ extern "C" int csm_attn_bwd_rope(const void* qkv, const void* out, const void* d
     return attn_bwd_impl(qkv, out, dout, lse, dqkv, delta_ws, rope_table, B, S, H, KV, HD, stream);
 }
 
+// Packed rows: several sequences share one row of S positions, key j is visible to query i iff seg_start[i] <= j <= i.
+// seg_start / seg_end [B*S] (int32, device): first / last position of the position's segment, row-local, non-decreasing along a
+// row and total (padding is a segment); built by the host and trusted here.  head_dim 64 only, second-generation kernels
+// (attention64.hip, SEG instantiations); no RoPE form - packed positions are not arange(S), the caller rotates.
+hipError_t csm_attn64_fwd_seg_launch(const void* qkv, void* out, float* lse, const int* seg_start, int B, int S, int H, int KV,
+                                     hipStream_t stream);
+hipError_t csm_attn64_dq_seg_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                    const int* seg_start, int B, int S, int H, int KV, hipStream_t stream);
+hipError_t csm_attn64_dkv_seg_launch(const void* qkv, const void* dout, const float* delta, void* dqkv, const int* seg_end, int B, int S,
+                                     int H, int KV, hipStream_t stream);
+#define CSM_CHECK_LDS(call, name)                                                                              \
+    do {                                                                                                       \
+        hipError_t e__ = (call);                                                                               \
+        if (e__ != hipSuccess) {                                                                               \
+            csm_set_error("%s: dynamic LDS request failed: %s", name, hipGetErrorString(e__));                 \
+            return 2;                                                                                          \
+        }                                                                                                      \
+    } while (0)
+
+extern "C" int csm_attn_fwd_seg(const void* qkv, void* out, float* lse, const int* seg_start, int B, int S, int H, int KV, int HD,
+                                hipStream_t stream) {
+    CSM_REQUIRE(B > 0 && S > 0 && H > 0 && KV > 0 && H % KV == 0, "csm_attn_fwd_seg: bad shape B=%d S=%d H=%d KV=%d", B, S, H, KV);
+    CSM_REQUIRE(HD == 64, "csm_attn_fwd_seg: head_dim %d unsupported (64)", HD);
+    CSM_REQUIRE(qkv && out && lse && seg_start, "csm_attn_fwd_seg: null pointer");
+    CSM_CHECK_LDS(csm_attn64_fwd_seg_launch(qkv, out, lse, seg_start, B, S, H, KV, stream), "csm_attn_fwd_seg");
+    CSM_CHECK_LAUNCH("csm_attn_fwd_seg");
+    return 0;
+}
+
+extern "C" int csm_attn_bwd_seg(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
+                                const int* seg_start, const int* seg_end, int B, int S, int H, int KV, int HD, hipStream_t stream) {
+    CSM_REQUIRE(B > 0 && S > 0 && H > 0 && KV > 0 && H % KV == 0, "csm_attn_bwd_seg: bad shape B=%d S=%d H=%d KV=%d", B, S, H, KV);
+    CSM_REQUIRE(HD == 64, "csm_attn_bwd_seg: head_dim %d unsupported (64)", HD);
+    CSM_REQUIRE(qkv && out && dout && lse && dqkv && delta_ws && seg_start && seg_end, "csm_attn_bwd_seg: null pointer");
+    g_attn_last_dkv = g_attn_last_dq = 0;            // always the compiler-scheduled kernels: the asm loops know only the causal mask
+    CSM_CHECK_LDS(csm_attn64_dq_seg_launch(qkv, out, dout, lse, delta_ws, dqkv, seg_start, B, S, H, KV, stream), "csm_attn_bwd_seg(dq)");
+    CSM_CHECK_LAUNCH("csm_attn_bwd_seg(dq)");
+    CSM_CHECK_LDS(csm_attn64_dkv_seg_launch(qkv, dout, delta_ws, dqkv, seg_end, B, S, H, KV, stream), "csm_attn_bwd_seg(dkv)");
+    CSM_CHECK_LAUNCH("csm_attn_bwd_seg(dkv)");
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Append: n new positions pos0 .. pos0+n-1 of ONE sequence against its KV cache (a conversation's next turn: the new text frames,
 // or the other party's audio, with every earlier turn already cached).  The skeleton is the forward's - swapped S^T = K Q^T, P^T

@@ -141,8 +141,20 @@ __device__ __forceinline__ void dma_tile(const bf16_t* __restrict__ P, int ld, i
 
 // ------------------------------------------------------------------------------------------------------------------
 // forward: workgroup = 128 queries of one (b, h) = 4 waves x 32 queries; key blocks of 64
+//
+// SEG (packed rows, csm_attn_fwd_seg / csm_attn_bwd_seg): key j is visible to query i iff seg_start[i] <= j <= i.  seg_start /
+// seg_end [B*S] are row-local and non-decreasing along a row, so the smallest seg_start of a run of queries is its first
+// query's and the largest its last one's.  The forward and the dQ kernel keep seg_start of the lane's query as one scalar, walk
+// key blocks seg_start[first query of the workgroup] / 64 .. last query / 64 - the ring is re-based on the first walked block
+// (kb0), its stage offsets stay compile-time - and apply the lower mask only on tiles below the wave's largest seg_start
+// (wave-uniform, like the causal mask on diagonal tiles).  A wave whose queries start later than the workgroup's first
+// walks leading tiles in which some rows see no key at all: their running maximum stays -inf and the maximum that enters
+// the exponent is held at 0 until the row has seen a key (-inf - -inf would be NaN).  Every query sees itself, so at the end
+// every maximum is finite.  SEG = false leaves the code as it was (kb0 = 0 and the tests fold away).
+template <bool SEG>
 __global__ __launch_bounds__(256, 3) void attn64_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                            float* __restrict__ lse, int S, int H, int KV, float scale) {
+                                                            float* __restrict__ lse, int S, int H, int KV, float scale,
+                                                            const int* __restrict__ seg_start) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int rep = H / KV;
     const int nqblk = (S + 127) / 128;
@@ -190,10 +202,18 @@ __global__ __launch_bounds__(256, 3) void attn64_fwd_kernel(const bf16_t* __rest
 
     int lastq = q_base + 127;
     lastq = lastq < S ? lastq : S - 1;
-    const int nkb = lastq / 64 + 1;                     // key blocks (64 keys) of the workgroup
     int lastw = qw + 31;
     lastw = lastw < S ? lastw : S - 1;
-    const int ntw = qw < S ? lastw / 32 + 1 : 0;        // key TILES (32 keys) this wave needs
+    // SEG: first walked key block (workgroup-uniform), the lane's own segment start, the wave's largest one
+    int kb0 = 0, ss = 0, ssmax = 0;
+    if constexpr (SEG) {
+        const int* sp = seg_start + (size_t)b * S;
+        kb0 = __builtin_amdgcn_readfirstlane(sp[q_base]) >> 6;
+        ss = sp[qc];
+        ssmax = __builtin_amdgcn_readfirstlane(sp[lastw]);
+    }
+    const int nkb = lastq / 64 + 1 - kb0;               // key blocks (64 keys) of the workgroup: kb0 .. kb0 + nkb - 1
+    const int ntw = qw < S ? lastw / 32 + 1 - 2 * kb0 : 0;   // key TILES (32 keys) this wave needs, counted from block kb0
 
     unsigned dma_off[2];
     dma_lane_off(ld, wave, lane, dma_off);
@@ -232,7 +252,15 @@ __global__ __launch_bounds__(256, 3) void attn64_fwd_kernel(const bf16_t* __rest
         return vmax3(x0, x3, m);
     };
     auto causal = [&](f32x16& x, int key0) {
-        if (key0 + 31 > qw) {                           // the tile crosses this wave's diagonal (wave-uniform)
+        if constexpr (SEG) {
+            if (key0 + 31 > qw || key0 < ssmax) {       // ... or it lies below the start of some query's segment (wave-uniform)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int key = key0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    if (key > qrow || key < ss) x[i] = -INFINITY;
+                }
+            }
+        } else if (key0 + 31 > qw) {                    // the tile crosses this wave's diagonal (wave-uniform)
 #pragma unroll
             for (int i = 0; i < 16; ++i)
                 if (key0 + (i & 3) + 8 * (i >> 2) + 4 * h > qrow) x[i] = -INFINITY;
@@ -245,14 +273,15 @@ __global__ __launch_bounds__(256, 3) void attn64_fwd_kernel(const bf16_t* __rest
         const bf16x4 v010 = tr_read<A>(voff[1][0]), v011 = tr_read<A>(voff[1][1]);
         const bf16x4 v100 = tr_read<A + 2048>(voff[0][0]), v101 = tr_read<A + 2048>(voff[0][1]);
         const bf16x4 v110 = tr_read<A + 2048>(voff[1][0]), v111 = tr_read<A + 2048>(voff[1][1]);
+        // (SEG: a row that has seen no key yet has m = mnew = -inf and counts as not moved; its O and l are still zero)
         if (!AB_MAX && !__all(mnew == m)) {             // rescale only when some query's running max moved
-            const float alpha = fexp2((m - mnew) * c2);
+            const float alpha = fexp2((m - (SEG && mnew == -INFINITY ? 0.f : mnew)) * c2);
 #pragma unroll
             for (int i = 0; i < 16; ++i) { o0[i] *= alpha; o1[i] *= alpha; }
             lacc[0] *= alpha;                           // every row of lacc is the same sum; only row 0 is read
             m = mnew;
         }
-        const float nb = -m * c2;
+        const float nb = -(SEG && m == -INFINITY ? 0.f : m) * c2;
         // ---- R1
         LGKM_WAIT(8);                                    // the K fragments (requested one step ago) have landed
         n = MFMA32(kf0, qf[0], zero16); SB(); EXP2(c, 0) SB();
@@ -277,8 +306,8 @@ __global__ __launch_bounds__(256, 3) void attn64_fwd_kernel(const bf16_t* __rest
     };
 #undef EXP2
 
-    issue(0, 0);
-    if (nkb > 1) { issue(1, 1); VM_WAIT(4); } else { VM_WAIT(0); }
+    issue(kb0, 0);
+    if (nkb > 1) { issue(kb0 + 1, 1); VM_WAIT(4); } else { VM_WAIT(0); }
     __builtin_amdgcn_s_barrier();
 
     // tile positions inside the ring: stage s, tile 0 / 1
@@ -294,7 +323,7 @@ __global__ __launch_bounds__(256, 3) void attn64_fwd_kernel(const bf16_t* __rest
         kf0 = row_read<4096>(koff[0]); kf1 = row_read<4096>(koff[1]); kf2 = row_read<4096>(koff[2]); kf3 = row_read<4096>(koff[3]);
         LGKM_WAIT(4);
         sa = MFMA32(k0, qf[0], zero16); sa = MFMA32(k1, qf[1], sa); sa = MFMA32(k2, qf[2], sa); sa = MFMA32(k3, qf[3], sa);
-        causal(sa, 0);
+        causal(sa, kb0 * 64);
         mnew = halves_max(rowmax(sa));
     }
     // One key block: wait for block kb+1 (issued one block ago), barrier, issue block kb+2 into the stage the barrier has
@@ -304,9 +333,9 @@ __global__ __launch_bounds__(256, 3) void attn64_fwd_kernel(const bf16_t* __rest
 #define BLOCK(KB, C0, C1, N0, N1, NNIDX)                                                                               \
     {                                                                                                                  \
         if (!AB_BAR) { VM_WAIT(0); __builtin_amdgcn_s_barrier(); }                                                     \
-        if (!AB_BAR && (KB) + 2 < nkb) issue((KB) + 2, NNIDX);                                                         \
-        if (2 * (KB) < ntw) step(C0{}, C1{}, N0{}, (KB) * 64, sa, sb);                                                 \
-        if (2 * (KB) + 1 < ntw) step(C1{}, N0{}, N1{}, (KB) * 64 + 32, sb, sa);                                        \
+        if (!AB_BAR && (KB) + 2 < nkb) issue(kb0 + (KB) + 2, NNIDX);                                                   \
+        if (2 * (KB) < ntw) step(C0{}, C1{}, N0{}, (kb0 + (KB)) * 64, sa, sb);                                         \
+        if (2 * (KB) + 1 < ntw) step(C1{}, N0{}, N1{}, (kb0 + (KB)) * 64 + 32, sb, sa);                                \
     }
     for (int kb = 0; kb < nkb; kb += 3) {
         BLOCK(kb, P00, P01, P10, P11, 2)
@@ -358,10 +387,13 @@ __device__ __forceinline__ void unrope2(const float* __restrict__ table, int p, 
 // dS = P o dP needs no subtraction), dQ^T += K^T dS^T (K^T by transposed reads of the same K image; dS^T straight from
 // the accumulators).  P = exp2(c S - lse) needs no running max.  Also computes delta = rowsum(dO o O) from the same row
 // fragments and publishes it for the dK/dV kernel, and applies the RoPE backward in the epilogue (rope != null).
+// SEG: the forward's block range and lower mask (see there); P comes from the given lse, so there is no -inf case.
+template <bool SEG>
 __global__ __launch_bounds__(256, 2) void attn64_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                            const bf16_t* __restrict__ dout, const float* __restrict__ lse,
                                                            float* __restrict__ delta, bf16_t* __restrict__ dqkv, int S, int H, int KV,
-                                                           float scale, const float* __restrict__ rope, long long nstat /* B H S */) {
+                                                           float scale, const float* __restrict__ rope, long long nstat /* B H S */,
+                                                           const int* __restrict__ seg_start) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int rep = H / KV;
     const int nqblk = (S + 127) / 128;
@@ -422,10 +454,17 @@ __global__ __launch_bounds__(256, 2) void attn64_dq_kernel(const bf16_t* __restr
 
     int lastq = q_base + 127;
     lastq = lastq < S ? lastq : S - 1;
-    const int nkb = lastq / 64 + 1;
     int lastw = qw + 31;
     lastw = lastw < S ? lastw : S - 1;
-    const int ntw = qw < S ? lastw / 32 + 1 : 0;
+    int kb0 = 0, ss = 0, ssmax = 0;
+    if constexpr (SEG) {
+        const int* sp = seg_start + (size_t)b * S;
+        kb0 = __builtin_amdgcn_readfirstlane(sp[q_base]) >> 6;
+        ss = sp[qc];
+        ssmax = __builtin_amdgcn_readfirstlane(sp[lastw]);
+    }
+    const int nkb = lastq / 64 + 1 - kb0;
+    const int ntw = qw < S ? lastw / 32 + 1 - 2 * kb0 : 0;
 
     unsigned dma_off[2];
     dma_lane_off(ld, wave, lane, dma_off);
@@ -449,7 +488,15 @@ __global__ __launch_bounds__(256, 2) void attn64_dq_kernel(const bf16_t* __restr
         const bf16x4 t010 = tr_read<A>(toff[1][0]), t011 = tr_read<A>(toff[1][1]);
         const bf16x4 t100 = tr_read<A + 2048>(toff[0][0]), t101 = tr_read<A + 2048>(toff[0][1]);
         const bf16x4 t110 = tr_read<A + 2048>(toff[1][0]), t111 = tr_read<A + 2048>(toff[1][1]);
-        if (key0 + 31 > qw) {                           // diagonal tile: exp2(-inf) = 0 kills the masked scores
+        if constexpr (SEG) {
+            if (key0 + 31 > qw || key0 < ssmax) {       // diagonal tile, or one below the start of some query's segment
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int key = key0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    if (key > qrow || key < ss) cs[i] = -INFINITY;
+                }
+            }
+        } else if (key0 + 31 > qw) {                    // diagonal tile: exp2(-inf) = 0 kills the masked scores
 #pragma unroll
             for (int i = 0; i < 16; ++i)
                 if (key0 + (i & 3) + 8 * (i >> 2) + 4 * h > qrow) cs[i] = -INFINITY;
@@ -474,8 +521,8 @@ __global__ __launch_bounds__(256, 2) void attn64_dq_kernel(const bf16_t* __restr
     };
 #undef DS2
 
-    issue(0, 0);
-    if (nkb > 1) { issue(1, 1); VM_WAIT(4); } else { VM_WAIT(0); }
+    issue(kb0, 0);
+    if (nkb > 1) { issue(kb0 + 1, 1); VM_WAIT(4); } else { VM_WAIT(0); }
     __builtin_amdgcn_s_barrier();
 
     using P00 = std::integral_constant<int, 0>;
@@ -498,9 +545,9 @@ __global__ __launch_bounds__(256, 2) void attn64_dq_kernel(const bf16_t* __restr
     {                                                                                                                  \
         VM_WAIT(0);                                                                                                    \
         __builtin_amdgcn_s_barrier();                                                                                  \
-        if ((KB) + 2 < nkb) issue((KB) + 2, NNIDX);                                                                    \
-        if (2 * (KB) < ntw) step(C0{}, N0{}, (KB) * 64, sa, da, sb, db);                                               \
-        if (2 * (KB) + 1 < ntw) step(C1{}, N1{}, (KB) * 64 + 32, sb, db, sa, da);                                      \
+        if ((KB) + 2 < nkb) issue(kb0 + (KB) + 2, NNIDX);                                                              \
+        if (2 * (KB) < ntw) step(C0{}, N0{}, (kb0 + (KB)) * 64, sa, da, sb, db);                                       \
+        if (2 * (KB) + 1 < ntw) step(C1{}, N1{}, (kb0 + (KB)) * 64 + 32, sb, db, sa, da);                              \
     }
     for (int kb = 0; kb < nkb; kb += 3) {
         BLOCK(kb, P00, P01, P10, P11, 2)
@@ -559,10 +606,13 @@ __device__ __forceinline__ f32x4 stat_read(unsigned addr) {
 constexpr int KSTAGE = 2 * TILE + 512;      // Q image + dO image + 64 x (-lse*log2e) + 64 x (-delta)
 constexpr int KNSTAGE = 4;                  // ring depth of the dK/dV kernel: 66 KiB per workgroup, two workgroups per CU
 
+// SEG: the key sits on the lane, so seg_end[key] is the per-lane scalar: query q_ is masked when q_ > seg_end[key] as well, and
+// the key block's query blocks end at seg_end[its last key] / 64 (the largest seg_end of the block) instead of the sequence end.
+template <bool SEG>
 __global__ __launch_bounds__(256, 2) void attn64_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                             const float* __restrict__ nlse2 /* -lse log2e */, const float* __restrict__ ndelta /* -delta */,
                                                             bf16_t* __restrict__ dqkv, int S, int H, int KV, float scale,
-                                                            const float* __restrict__ rope) {
+                                                            const float* __restrict__ rope, const int* __restrict__ seg_end) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int rep = H / KV;
     const int nkblk = (S + 63) / 64;
@@ -623,7 +673,15 @@ __global__ __launch_bounds__(256, 2) void attn64_dkv_kernel(const bf16_t* __rest
     const unsigned soff = sbase + 2 * TILE + (32 * qp + 4 * h) * 4;      // stats of queries 32 qp + 4h + {0..3} (+ 8k: immediate 32 k)
 
     const int nqb = (S + 63) / 64;
-    const int per_head = nqb - kblk;                     // query blocks at or below the diagonal
+    int per_head = nqb - kblk;                           // query blocks at or below the diagonal
+    int se = 0, semin = 0;                               // SEG: the lane's own segment end, the wave's smallest one
+    if constexpr (SEG) {
+        const int* sp = seg_end + (size_t)b * S;
+        const int lastk = kblk * 64 + 63 < S ? kblk * 64 + 63 : S - 1;
+        per_head = (__builtin_amdgcn_readfirstlane(sp[lastk]) >> 6) - kblk + 1;
+        se = sp[kc];
+        semin = __builtin_amdgcn_readfirstlane(sp[key0w < S ? key0w : S - 1]);
+    }
     const int niter = rep * per_head;
 
     unsigned dma_q[2], dma_o[2];
@@ -683,7 +741,15 @@ __global__ __launch_bounds__(256, 2) void attn64_dkv_kernel(const bf16_t* __rest
         const bf16x4 u110 = tr_read<A + TILE + 2048>(toff[1][0]), u111 = tr_read<A + TILE + 2048>(toff[1][1]);
         const bf16x4 w100 = tr_read<A + 2048>(toff[0][0]), w101 = tr_read<A + 2048>(toff[0][1]);
         const bf16x4 w110 = tr_read<A + 2048>(toff[1][0]), w111 = tr_read<A + 2048>(toff[1][1]);
-        if ((q0 < key0w + 32) || (q0 + 32 > S)) {       // the tile touches the diagonal or the sequence end (wave-uniform):
+        if constexpr (SEG) {
+            if ((q0 < key0w + 32) || (q0 + 31 > semin)) {   // the diagonal, or past the end of some key's segment (<= S - 1)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int q_ = q0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    if (key > q_ || q_ > se) sc[i] = -INFINITY;
+                }
+            }
+        } else if ((q0 < key0w + 32) || (q0 + 32 > S)) {    // the tile touches the diagonal or the sequence end (wave-uniform):
 #pragma unroll                                          // exp2(-inf) = 0 kills the masked scores, no branch inside the element loop
             for (int i = 0; i < 16; ++i) {
                 const int q_ = q0 + (i & 3) + 8 * (i >> 2) + 4 * h;
@@ -813,11 +879,19 @@ __global__ __launch_bounds__(256, 2) void attn64_dkv_kernel(const bf16_t* __rest
 
 }  // namespace
 
+// More than 64 KiB of dynamic LDS must be requested per kernel (each template instantiation is a kernel of its own); the
+// request is cheap, so it is made on every launch and its result is returned, not remembered in a flag.
+template <typename K>
+static hipError_t want_lds(K kernel, int lds) {
+    return lds > 65536 ? hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) : hipSuccess;
+}
+
 int csm_attn64_fwd_launch(const void* qkv, void* out, float* lse, int B, int S, int H, int KV, hipStream_t stream) {
     const float scale = 0.125f;
     const int lds = NSTAGE * STAGE;
     dim3 grid((unsigned)(((S + 127) / 128) * H * B)), block(256);
-    hipLaunchKernelGGL(attn64_fwd_kernel, grid, block, lds, stream, (const bf16_t*)qkv, (bf16_t*)out, lse, S, H, KV, scale);
+    hipLaunchKernelGGL(attn64_fwd_kernel<false>, grid, block, lds, stream, (const bf16_t*)qkv, (bf16_t*)out, lse, S, H, KV, scale,
+                       (const int*)nullptr);
     return 0;
 }
 
@@ -826,8 +900,8 @@ int csm_attn64_dq_launch(const void* qkv, const void* out, const void* dout, con
     const float scale = 0.125f;
     const int lds = NSTAGE * STAGE;
     dim3 grid((unsigned)(((S + 127) / 128) * H * B)), block(256);
-    hipLaunchKernelGGL(attn64_dq_kernel, grid, block, lds, stream, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, delta,
-                       (bf16_t*)dqkv, S, H, KV, scale, rope, (long long)B * H * S);
+    hipLaunchKernelGGL(attn64_dq_kernel<false>, grid, block, lds, stream, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
+                       delta, (bf16_t*)dqkv, S, H, KV, scale, rope, (long long)B * H * S, (const int*)nullptr);
     return 0;
 }
 
@@ -836,10 +910,41 @@ int csm_attn64_dkv_launch(const void* qkv, const void* dout, const float* lse, c
     const float scale = 0.125f;
     const int lds = KNSTAGE * KSTAGE;
     static bool done = false;        // more than 64 KiB of dynamic LDS must be requested once
-    if (!done) { (void)hipFuncSetAttribute((const void*)attn64_dkv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds); done = true; }
+    if (!done) { (void)hipFuncSetAttribute((const void*)attn64_dkv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); done = true; }
     dim3 grid((unsigned)(((S + 63) / 64) * KV * B)), block(256);
     // (delta = the dQ kernel's output: [0, BHS) = -delta, [BHS, 2 BHS) = -lse log2e)
-    hipLaunchKernelGGL(attn64_dkv_kernel, grid, block, lds, stream, (const bf16_t*)qkv, (const bf16_t*)dout, delta + (size_t)B * H * S, delta,
-                       (bf16_t*)dqkv, S, H, KV, scale, rope);
+    hipLaunchKernelGGL(attn64_dkv_kernel<false>, grid, block, lds, stream, (const bf16_t*)qkv, (const bf16_t*)dout, delta + (size_t)B * H * S,
+                       delta, (bf16_t*)dqkv, S, H, KV, scale, rope, (const int*)nullptr);
     return 0;
+}
+
+// The segment-aware instantiations (csm_attn_fwd_seg / csm_attn_bwd_seg): the same grids; the descriptor arrays are trusted.
+// Each returns the result of its LDS request (hipSuccess where none is needed); the caller checks the launch.
+hipError_t csm_attn64_fwd_seg_launch(const void* qkv, void* out, float* lse, const int* seg_start, int B, int S, int H, int KV,
+                                     hipStream_t stream) {
+    const int lds = NSTAGE * STAGE;
+    if (hipError_t e = want_lds(attn64_fwd_kernel<true>, lds)) return e;
+    dim3 grid((unsigned)(((S + 127) / 128) * H * B)), block(256);
+    hipLaunchKernelGGL(attn64_fwd_kernel<true>, grid, block, lds, stream, (const bf16_t*)qkv, (bf16_t*)out, lse, S, H, KV, 0.125f, seg_start);
+    return hipSuccess;
+}
+
+hipError_t csm_attn64_dq_seg_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                    const int* seg_start, int B, int S, int H, int KV, hipStream_t stream) {
+    const int lds = NSTAGE * STAGE;
+    if (hipError_t e = want_lds(attn64_dq_kernel<true>, lds)) return e;
+    dim3 grid((unsigned)(((S + 127) / 128) * H * B)), block(256);
+    hipLaunchKernelGGL(attn64_dq_kernel<true>, grid, block, lds, stream, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse,
+                       delta, (bf16_t*)dqkv, S, H, KV, 0.125f, (const float*)nullptr, (long long)B * H * S, seg_start);
+    return hipSuccess;
+}
+
+hipError_t csm_attn64_dkv_seg_launch(const void* qkv, const void* dout, const float* delta, void* dqkv, const int* seg_end, int B, int S,
+                                     int H, int KV, hipStream_t stream) {
+    const int lds = KNSTAGE * KSTAGE;
+    if (hipError_t e = want_lds(attn64_dkv_kernel<true>, lds)) return e;
+    dim3 grid((unsigned)(((S + 63) / 64) * KV * B)), block(256);
+    hipLaunchKernelGGL(attn64_dkv_kernel<true>, grid, block, lds, stream, (const bf16_t*)qkv, (const bf16_t*)dout, delta + (size_t)B * H * S,
+                       delta, (bf16_t*)dqkv, S, H, KV, 0.125f, (const float*)nullptr, seg_end);
+    return hipSuccess;
 }

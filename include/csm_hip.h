@@ -159,6 +159,16 @@ int csm_attn_bwd_rope(const void* qkv, const void* out, const void* dout, const 
  * (head_dim 64, S % 64 == 0, 4 query heads per kv head); a clear bit = the compiler-scheduled kernel of attention64.hip /
  * attention.hip */
 int csm_attn_last_dkv_kernel(void);
+/* Packed rows (sequence packing; additive in ABI 3): several sequences share one row of S positions and key j is visible to
+ * query i iff seg_start[i] <= j <= i.  seg_start / seg_end: int32 device arrays [B*S], the first / last position of the
+ * position's segment, row-local, non-decreasing along a row and total (a row's padding is one more segment); the host builds
+ * them and the kernels trust them.  head_dim 64 only.  There is no fused-RoPE form (packed positions are not arange(S)): rotate
+ * with csm_rope(pos) before the forward and with inverse = 1 after the backward.  The backward always takes the
+ * compiler-scheduled dQ and dK/dV kernels (csm_attn_last_dkv_kernel() answers 0 after it); delta_ws as for csm_attn_bwd.  One
+ * segment per row gives the bits of csm_attn_fwd / of csm_attn_bwd under csm_set_attn_variant(default word | 1 << 10). */
+int csm_attn_fwd_seg(const void* qkv, void* out, float* lse, const int* seg_start, int B, int S, int H, int KV, int HD, csm_stream_t stream);
+int csm_attn_bwd_seg(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws,
+                     const int* seg_start, const int* seg_end, int B, int S, int H, int KV, int HD, csm_stream_t stream);
 /* tools/probes only: a device buffer (>= grid x 4 waves x 8 rounds x 8 u64) that the asm dQ kernel fills with cycle stamps, or NULL */
 int csm_attn64_set_debug(void* device_buffer);
 
