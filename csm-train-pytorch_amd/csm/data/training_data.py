@@ -254,7 +254,11 @@ def collate_variable_length(batch: List[Dict[str, torch.Tensor]], target_pad: in
         tokens[i, :s] = b["input_tokens"]
         masks[i, :s] = b["input_masks"]
         targets[i, :t] = b["target_audio_tokens"]
-    return {"input_tokens": tokens, "input_masks": masks, "target_audio_tokens": targets}
+    out = {"input_tokens": tokens, "input_masks": masks, "target_audio_tokens": targets}
+    if any("adapter" in b for b in batch):
+        # the adapter set every example trains (multi-speaker LoRA, compute_loss(adapter_ids=...)); an example without one: -1
+        out["adapter_ids"] = torch.tensor([int(b.get("adapter", -1)) for b in batch], dtype=torch.long)
+    return out
 
 
 def collate_packed(batch: List[Dict[str, torch.Tensor]], max_seq_len: int = 2048, target_pad: int = IGNORE_INDEX) -> Dict[str, torch.Tensor]:
@@ -264,7 +268,8 @@ def collate_packed(batch: List[Dict[str, torch.Tensor]], max_seq_len: int = 2048
     First-fit over the examples sorted by decreasing input length (ties keep the batch order: deterministic); rows are opened as
     needed; the row length S is the longest row rounded up to a multiple of 128, capped at ``max_seq_len``.  An example longer than
     ``max_seq_len`` raises.  Returns ``input_tokens`` [R, S, K+1], ``input_masks``, ``target_audio_tokens`` [R, S, K] and
-    ``segment_lengths`` [R, n_max] (a row's segment lengths in order, zero-padded).
+    ``segment_lengths`` [R, n_max] (a row's segment lengths in order, zero-padded) - and, when an example carries an
+    ``"adapter"`` (its adapter set, multi-speaker LoRA), ``adapter_ids`` [R, n_max] beside it (-1 where there is no segment).
 
     Targets follow the position-indexed label convention of ``forward_loss`` (position p is labelled by ``targets[p]``, the last
     position of a sequence by nothing), applied per segment: for example i of input length S_i with T_i target frames at row
@@ -294,6 +299,8 @@ def collate_packed(batch: List[Dict[str, torch.Tensor]], max_seq_len: int = 2048
     masks = torch.zeros(R, S, k1, dtype=torch.bool)
     targets = torch.full((R, S, k), target_pad, dtype=torch.long)
     seg = torch.zeros(R, max(len(r) for r in rows), dtype=torch.long)
+    # per-segment adapter sets (multi-speaker LoRA), only when an example carries one; no segment, or no "adapter": -1
+    ads = torch.full(tuple(seg.shape), -1, dtype=torch.long) if any("adapter" in b for b in batch) else None
     for r, members in enumerate(rows):
         o = 0
         for j, i in enumerate(members):
@@ -303,8 +310,13 @@ def collate_packed(batch: List[Dict[str, torch.Tensor]], max_seq_len: int = 2048
             masks[r, o:o + n] = b["input_masks"]
             targets[r, o:o + t] = b["target_audio_tokens"][:t]
             seg[r, j] = n
+            if ads is not None:
+                ads[r, j] = int(b.get("adapter", -1))
             o += n
-    return {"input_tokens": tokens, "input_masks": masks, "target_audio_tokens": targets, "segment_lengths": seg}
+    out = {"input_tokens": tokens, "input_masks": masks, "target_audio_tokens": targets, "segment_lengths": seg}
+    if ads is not None:
+        out["adapter_ids"] = ads
+    return out
 
 
 class LengthBucketSampler(Sampler):

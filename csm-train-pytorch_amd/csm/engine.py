@@ -51,6 +51,46 @@ DECODE_POS_HOST = _os.environ.get("CSM_DECODE_POS_HOST", "1") == "1"
 LORA_FUSE = _os.environ.get("CSM_LORA_FUSE", "1") != "0"
 
 
+def _refuse_stack(lo, where: str):
+    """A stack of adapter sets (LoRAState n_adapters > 1) exists for training batches that name a set per example; every
+    single-adapter path takes one exported set."""
+    if getattr(lo, "n_adapters", 1) > 1:
+        raise ValueError(f"{where} takes one adapter set, and model.lora stacks {lo.n_adapters}: export one first "
+                         "(state = model.lora.export(a), then LoRABank.add / generate_batch(adapters=[...]) / row_lora(model, state))")
+
+
+def adapter_rows(adapter_ids, B: int, S: int, n_adapters: int, segment_lengths=None) -> torch.Tensor:
+    """``sel`` [B*S] int32 on the host: the adapter set of every position, from ``adapter_ids`` [B] (one id per example) or,
+    with ``segment_lengths`` [B, n_max], [B, n_max] (one id per segment; what a row's segments leave over is padding).
+    -1 = base model only; padding is always -1.  Ids outside [-1, n_adapters) are refused here, on the host - the kernels only
+    compare them."""
+    ids = torch.as_tensor(adapter_ids).detach().to("cpu")
+    if ids.is_floating_point() or ids.dtype == torch.bool:
+        raise ValueError(f"adapter_ids must be integers, got {ids.dtype}")
+    ids = ids.to(torch.int64)
+    if segment_lengths is None:
+        if tuple(ids.shape) != (B,):
+            raise ValueError(f"adapter_ids must have shape [B={B}] (one adapter set per example), got {tuple(ids.shape)}")
+        live = ids
+        sel = ids.repeat_interleave(S)
+    else:
+        L = torch.as_tensor(segment_lengths).detach().to("cpu").to(torch.int64)
+        if ids.dim() != 2 or tuple(ids.shape) != tuple(L.shape) or L.shape[0] != B:
+            raise ValueError(f"adapter_ids of a packed batch must have the shape of segment_lengths {tuple(L.shape)} "
+                             f"(one adapter set per segment), got {tuple(ids.shape)}")
+        if bool((L < 0).any()) or bool((L.sum(1) > S).any()):
+            raise ValueError("segment_lengths: negative, or more than a row holds")
+        live = ids[L > 0]
+        full_len = torch.cat([L, (S - L.sum(1))[:, None]], 1).reshape(-1)
+        full_ids = torch.cat([ids, torch.full((B, 1), -1, dtype=torch.int64)], 1).reshape(-1)
+        sel = torch.repeat_interleave(full_ids, full_len)
+    if live.numel() and (int(live.min()) < -1 or int(live.max()) >= n_adapters):
+        bad = live[(live < -1) | (live >= n_adapters)]
+        raise ValueError(f"adapter id {int(bad[0])} out of range: {n_adapters} adapter set(s), valid ids are -1 (base model) "
+                         f"and 0..{n_adapters - 1}")
+    return sel.to(torch.int32)
+
+
 @contextmanager
 def generation_lora(model):
     """What generation does with the adapters of ``model`` around a pass through the training forward (prefill, recompute):
@@ -62,6 +102,7 @@ def generation_lora(model):
     if lo is None:
         yield None
         return
+    _refuse_stack(lo, "generation")
     if lo.merged:
         model.lora = None
         try:
@@ -117,7 +158,7 @@ class _Stack:
 
     # -------------------------------------------------------------------------------------------- forward
     def forward(self, x: torch.Tensor, B: int, S: int, save: bool, pos: Optional[torch.Tensor] = None,
-                fuse_rope: bool = True, on_layer_start=None, append=None, seg=None) -> torch.Tensor:
+                fuse_rope: bool = True, on_layer_start=None, append=None, seg=None, sel=None) -> torch.Tensor:
         """``seg`` = a ``Segments`` (packed rows): attention goes through the segment-masked kernels (``ops.attn_fwd_seg``) and RoPE
         through the un-fused path with the segment-local positions ``seg.pos``; everything else is unchanged.
         ``append`` = (decode stack, batch row, pos0): the S rows are positions pos0 .. pos0+S-1 of the sequence whose earlier
@@ -126,7 +167,8 @@ class _Stack:
         The ragged form ``append`` = (decode stack, rows, pos0s, ns) with three equally long lists of host integers stacks R <= 16
         such segments, each against its own batch row: x holds ``sum(ns)`` rows, segment after segment, and ``pos`` their positions
         (``ops.attn_append_rows``).  Its products are pinned to the kernel whose rows do not see each other (``pin``, ops.gemm), so a
-        segment's rows have the bits they would have in a forward of their own, whatever is stacked beside them."""
+        segment's rows have the bits they would have in a forward of their own, whatever is stacked beside them.
+        ``sel`` (int32 [M] on the device): the adapter set of every row when ``model.lora`` is a stack (training/lora.py)."""
         c, dev = self.c, x.device
         M, d = x.shape
         if seg is not None:
@@ -152,7 +194,7 @@ class _Stack:
                 ops.linear_rope_fwd(xn, self.w(f"layers.{i}.attn.qkv"), qkv, table, S, hq + hk, hd)
             elif fused:
                 # the adapters' up-projections are extra k-steps of the same product, so the rotation still sees the sum
-                a["tx_attn_in"] = G.project(xn, pin=pin)
+                a["tx_attn_in"] = G.project(xn, pin=pin, sel=sel)
                 ops.gemm_kext(xn, self.w(f"layers.{i}.attn.qkv"), qkv, a["tx_attn_in"], G.Bx,
                               rope=(table, S, hq + hk, hd) if rope_in_gemm else None, pin=pin)
                 if not rope_in_gemm:
@@ -183,7 +225,7 @@ class _Stack:
             h = torch.empty(M, d, dtype=BF16, device=dev)
             G, fused = self._group(i, "attn_out")
             if fused:
-                a["tx_attn_out"] = G.project(o, pin=pin)
+                a["tx_attn_out"] = G.project(o, pin=pin, sel=sel)
                 ops.gemm_kext(o, self.w(f"layers.{i}.attn.output_proj.weight"), h, a["tx_attn_out"], G.Bx, R=x, pin=pin)
             else:
                 ops.linear_fwd(o, self.w(f"layers.{i}.attn.output_proj.weight"), h, residual=x, pin=pin)
@@ -201,7 +243,7 @@ class _Stack:
                 ops.linear_swiglu_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, act, **ops._pin(pin))   # activation fused into the GEMM epilogue
             elif FUSE_SWIGLU and fused:
                 # adapters on w1 / w3: extra k-steps of the w13 product (Bx rows interleaved like w13), SwiGLU from the sum
-                a["tx_mlp_in"] = G.project(hn, pin=pin)
+                a["tx_mlp_in"] = G.project(hn, pin=pin, sel=sel)
                 ops.gemm_kext(hn, self.w(f"layers.{i}.mlp.w13"), gu, a["tx_mlp_in"], G.Bx, swiglu_act=act, pin=pin)
             elif FUSE_SWIGLU and not any(ad is not None and ad.bias is not None for ad in (ad1, ad3)):
                 # (dropout: one mask per adapter) the adapters' (alpha/r) t B^T is written FIRST, for both at once -
@@ -226,7 +268,7 @@ class _Stack:
             out = torch.empty(M, d, dtype=BF16, device=dev)
             G, fused = self._group(i, "mlp_out")
             if fused:
-                a["tx_mlp_out"] = G.project(act, pin=pin)
+                a["tx_mlp_out"] = G.project(act, pin=pin, sel=sel)
                 ops.gemm_kext(act, self.w(f"layers.{i}.mlp.w2.weight"), out, a["tx_mlp_out"], G.Bx, R=h, pin=pin)
             else:
                 ops.linear_fwd(act, self.w(f"layers.{i}.mlp.w2.weight"), out, residual=h, pin=pin)
@@ -246,7 +288,7 @@ class _Stack:
 
     # -------------------------------------------------------------------------------------------- backward
     def backward(self, dxf: torch.Tensor, B: int, S: int, train_base: bool, alpha: float,
-                 pos: Optional[torch.Tensor] = None, on_layer_done=None, acc: bool = True, seg=None) -> torch.Tensor:
+                 pos: Optional[torch.Tensor] = None, on_layer_done=None, acc: bool = True, seg=None, sel=None) -> torch.Tensor:
         """dxf = gradient w.r.t. the final-norm output.  Returns the gradient w.r.t. the stack input.
         Weight gradients are added to the gradient arena (``acc``) or overwrite what it holds (``acc=False``: the first
         backward after a lazy optimizer step, which left consumed gradients behind instead of zeros); the incoming
@@ -331,12 +373,12 @@ class _Stack:
                 ops.linear_dx_swiglu_bwd(dx, self.w(f"layers.{i}.mlp.w2.weight"), a["gu"], dgu)   # d(act) never stored
             elif FUSE_SWIGLU and fused:
                 # d(act) = dx w2 + (s dx Bx) At^T inside one product, SwiGLU backward in its epilogue
-                dts = G.backward(a["act"], dx, a["tx_mlp_out"])
+                dts = G.backward(a["act"], dx, a["tx_mlp_out"], sel=sel)
                 ops.gemm_kext(dx, self.w(f"layers.{i}.mlp.w2.weight"), dgu, dts, G.At, transB=True, swiglu_bwd_gu=a["gu"])
             else:
                 dact = torch.empty(M, F, dtype=BF16, device=dev)
                 if fused:
-                    dts = G.backward(a["act"], dx, a["tx_mlp_out"])
+                    dts = G.backward(a["act"], dx, a["tx_mlp_out"], sel=sel)
                     ops.gemm_kext(dx, self.w(f"layers.{i}.mlp.w2.weight"), dact, dts, G.At, transB=True)
                 else:
                     ops.linear_dx(dx, self.w(f"layers.{i}.mlp.w2.weight"), dact)
@@ -355,7 +397,7 @@ class _Stack:
             G, fused = self._group(i, "mlp_in")
             fused = fused and "tx_mlp_in" in a
             if fused:
-                dts = G.backward(a["hn"], dgu, a["tx_mlp_in"])
+                dts = G.backward(a["hn"], dgu, a["tx_mlp_in"], sel=sel)
                 ops.gemm_kext(dgu, self.w(f"layers.{i}.mlp.w13"), dhn, dts, G.At, transB=True)
                 if train_base:
                     ops.linear_dw(dgu, a["hn"], self.w(f"layers.{i}.mlp.w13", True), accumulate=acc, alpha=alpha)
@@ -377,7 +419,7 @@ class _Stack:
             G, fused = self._group(i, "attn_out")
             fused = fused and "tx_attn_out" in a
             if fused:
-                dts = G.backward(a["o"], dh, a["tx_attn_out"])
+                dts = G.backward(a["o"], dh, a["tx_attn_out"], sel=sel)
                 ops.gemm_kext(dh, self.w(f"layers.{i}.attn.output_proj.weight"), do, dts, G.At, transB=True)
                 if train_base:
                     ops.linear_dw(dh, a["o"], self.w(f"layers.{i}.attn.output_proj.weight", True), accumulate=acc, alpha=alpha)
@@ -406,7 +448,7 @@ class _Stack:
             G, fused = self._group(i, "attn_in")
             fused = fused and "tx_attn_in" in a
             if fused:
-                dts = G.backward(a["xn"], dqkv, a["tx_attn_in"])
+                dts = G.backward(a["xn"], dqkv, a["tx_attn_in"], sel=sel)
                 ops.gemm_kext(dqkv, self.w(f"layers.{i}.attn.qkv"), dxn, dts, G.At, transB=True)
                 if train_base:
                     if group_dw:
@@ -498,12 +540,16 @@ class Engine:
 
     # -------------------------------------------------------------------------------------------- loss forward
     def forward_loss(self, tokens: torch.Tensor, masks: torch.Tensor, targets: torch.Tensor, semantic_weight: float,
-                     acoustic_weight: float, save: bool, acoustic_rows: Optional[torch.Tensor] = None, segment_lengths=None):
+                     acoustic_weight: float, save: bool, acoustic_rows: Optional[torch.Tensor] = None, segment_lengths=None,
+                     adapter_ids=None):
         """Forward of ``compute_loss``.  Returns (total, semantic, acoustic) as 0-d fp32 GPU tensors.
         ``segment_lengths`` [B, n_max] (host integers, zero-padded; ``collate_packed``) marks a packed batch: every row holds several
         examples one after the other, each attends only to itself and has RoPE positions of its own (``Segments``).  The labels
         stay position-indexed, so a packed batch needs ``model.target_ignore_index``: each segment's last position and the row
-        padding carry it."""
+        padding carry it.
+        ``adapter_ids`` (host integers): with a stack of adapter sets as ``model.lora`` (``LoRAState(n_adapters > 1)``), the set
+        every example runs with - [B], or [B, n_max] beside ``segment_lengths`` (one per segment); -1 = base model only.  The
+        loss stays the batch loss: the mean over the labelled rows of the whole batch, whichever sets they ran with."""
         m, a = self.m, self.m.args
         dev = m.device
         B, S, K1 = tokens.shape
@@ -526,13 +572,14 @@ class Engine:
             seg = Segments(segment_lengths, B, S, dev)     # built and copied once per step; nothing is cached on the layout
         self._validate_batch(tokens, masks, targets, ign)
         tg = targets.to(device=dev, dtype=torch.int64)
+        sel = self._adapter_sel(adapter_ids, B, S, segment_lengths)
 
         if m.lora is not None and LORA_FUSE:
             m.lora.refresh()
         h0 = torch.empty(M, d, dtype=BF16, device=dev)
         self._need("embeddings", -1)
         ops.embed_fwd(tk, mk, m.block("text_embeddings.weight"), m.block("audio_embeddings.weight"), h0, V)
-        hidden = self.backbone.forward(h0, B, S, save, on_layer_start=self.param_hook, seg=seg)
+        hidden = self.backbone.forward(h0, B, S, save, on_layer_start=self.param_hook, seg=seg, sel=sel)
 
         # codebook-0 head + CE over positions [0, S-1) of every sequence (reference utils.py:96-106)
         logits = torch.empty(M, Vp, dtype=F32, device=dev)
@@ -552,13 +599,35 @@ class Engine:
         dec = None
         if m.acoustic_mode != "off":
             rows = self._acoustic_rows(B, S, acoustic_rows, t0 if ign is not None else None)
-            dec = self._decoder_forward(hidden, rows, tg, B, S, save)
+            dec = self._decoder_forward(hidden, rows, tg, B, S, save, sel=sel)
             ops.reduce_sum(dec["rows_loss"], ac, 1.0 / dec["n_rows"])
         total = semantic_weight * sem + acoustic_weight * ac
         if save:
-            self.saved = dict(B=B, S=S, tk=tk, mk=mk, hidden=hidden, logits=logits, t0=t0, n_sem=n_sem, dec=dec, seg=seg,
+            self.saved = dict(B=B, S=S, tk=tk, mk=mk, hidden=hidden, logits=logits, t0=t0, n_sem=n_sem, dec=dec, seg=seg, sel=sel,
                               sw=float(semantic_weight), aw=float(acoustic_weight))
         return total[0], sem[0], ac[0]
+
+    def _adapter_sel(self, adapter_ids, B, S, segment_lengths):
+        """``sel`` [B*S] int32 on the device for a stack of adapter sets (``adapter_rows``; built on the host and copied once per
+        step, like ``Segments``), None without one.  A stack and ``adapter_ids`` come together or not at all."""
+        lo = self.m.lora
+        stacked = lo is not None and getattr(lo, "n_adapters", 1) > 1
+        if not stacked:
+            if adapter_ids is not None:
+                raise ValueError("adapter_ids name an adapter set per example, and model.lora is "
+                                 + ("not attached" if lo is None else "a single adapter set")
+                                 + ": attach a stack (apply_lora_to_model(..., n_adapters=A)) or drop adapter_ids")
+            return None
+        if adapter_ids is None:
+            raise ValueError(f"model.lora stacks {lo.n_adapters} adapter sets: pass adapter_ids (one per example, -1 = base model "
+                             "only), or export(a) one set and attach it alone")
+        if not (LORA_FUSE and FUSE_SWIGLU):
+            raise NotImplementedError("a stack of adapter sets trains through the K-extension path only: unset CSM_LORA_FUSE=0 / "
+                                      "CSM_FUSE_SWIGLU=0")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise NotImplementedError("a stack of adapter sets under a process group is not built (data parallel would all-reduce "
+                                      "the stack): train it in one process")
+        return adapter_rows(adapter_ids, B, S, lo.n_adapters, segment_lengths).to(self.m.device, non_blocking=True)
 
     def _validate_batch(self, tokens, masks, targets, ign):
         """Range checks of the integer inputs: the kernels index embedding tables, logits rows and gradient tables with
@@ -622,7 +691,7 @@ class Engine:
         perm = torch.randperm(allr.numel(), device=dev)[:n].sort().values
         return allr[perm].to(torch.int32).contiguous()
 
-    def _decoder_forward(self, hidden, rows, tg, B, S, save):
+    def _decoder_forward(self, hidden, rows, tg, B, S, save, sel=None):
         m, a = self.m, self.m.args
         dev = m.device
         K, V, Vp = a.audio_num_codebooks, a.audio_vocab_size, m.vocab_pad
@@ -639,7 +708,9 @@ class Engine:
         ops.decoder_input_fwd(hidden, rows, codes, m.block("audio_embeddings.weight"), seq, V)
         x0 = torch.empty(N * K, dd, dtype=BF16, device=dev)
         ops.linear_fwd(seq, m.block("projection.weight"), x0)
-        xf = self.decoder.forward(x0, N, K, save, on_layer_start=self.param_hook)   # [N*K, dd]
+        # (a stack of adapter sets: the K rows of a frame run with the set of the frame's position)
+        dsel = sel[rows.long()].repeat_interleave(K).contiguous() if sel is not None else None
+        xf = self.decoder.forward(x0, N, K, save, on_layer_start=self.param_hook, sel=dsel)   # [N*K, dd]
         logits = torch.empty(K - 1, N, Vp, dtype=F32, device=dev)
         ah = m.block("audio_head.padded")                                           # [K-1, dd, Vp]
         xf2 = xf.view(N, K * dd)
@@ -649,7 +720,7 @@ class Engine:
         ops.ce_fwd_bwd(logits.view(-1, Vp), tgt, rows_loss, None, V, 0.0)
         out = dict(rows_loss=rows_loss, n_rows=(K - 1) * N)
         if save:
-            out.update(rows=rows, codes=codes, seq=seq, xf=xf, logits=logits, tgt=tgt, N=N)
+            out.update(rows=rows, codes=codes, seq=seq, xf=xf, logits=logits, tgt=tgt, N=N, sel=dsel)
         return out
 
     # -------------------------------------------------------------------------------------------- backward
@@ -706,7 +777,7 @@ class Engine:
                          sB=N * Vp, sC=dd * Vp, sR=dd * Vp)
             del dl
             dx0 = self.decoder.backward(dxf.view(N * K, dd), N, K, tr["decoder"], 1.0, on_layer_done=self.grad_hook,
-                                        acc=acc["decoder"])
+                                        acc=acc["decoder"], sel=dec.get("sel"))
             dseq = torch.empty(N * K, d, dtype=BF16, device=dev)
             ops.linear_dx(dx0, m.block("projection.weight"), dseq)
             if train_other:
@@ -730,7 +801,8 @@ class Engine:
             self.grad_hook("other", -1)
 
         # ---- backbone
-        dh0 = self.backbone.backward(dhid, B, S, tr["backbone"], 1.0, on_layer_done=self.grad_hook, acc=acc["backbone"], seg=s.get("seg"))
+        dh0 = self.backbone.backward(dhid, B, S, tr["backbone"], 1.0, on_layer_done=self.grad_hook, acc=acc["backbone"], seg=s.get("seg"),
+                                    sel=s.get("sel"))
         if train_embeddings:
             self._embedding_backward(s, dh0, dseq if (dec is not None and s["aw"] != 0.0) else None)
         if self.grad_hook is not None:
@@ -1091,6 +1163,7 @@ class _DecodeStack:
     def attach_lora(self, lo):
         """Bind the active adapters of this stack: arena views of every group's At / Bx (read in place, so a captured graph
         sees what ``load_lora_weights`` or an optimiser writes there) and the group's bias vector (``_group_bias``)."""
+        _refuse_stack(lo, "a decode state")
         st, c = self.stack, self.stack.c
         plan, kmax = [], 0
         for i in range(c.num_layers):

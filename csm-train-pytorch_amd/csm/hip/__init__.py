@@ -34,6 +34,7 @@ _SIGS = {
     "csm_gemm_bf16_kext": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p], _i),
     "csm_gemm_bf16_pinned": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p], _i),
     "csm_skinny_nt_bf16": ([_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p], _i),
+    "csm_skinny_nt_sel_bf16": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p], _i),
     "csm_gemm_bf16_dgrad_wgrad": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i, _i, _f, _p], _i),
     "csm_gemm_bf16_two_wgrad": ([_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p], _i),
     "csm_gemm_bf16_multi_wgrad": ([_i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p], _i),

@@ -140,6 +140,19 @@ def skinny_nt(x, wt, out, alpha=1.0, pin=False):
     return out
 
 
+def skinny_nt_sel(x, wt, out, sel, blk, alpha=1.0):
+    """out[m, n] = alpha * x[m] . wt[n] where sel[m] >= 0 and n // blk == sel[m], +0 elsewhere: ``skinny_nt`` for a stack of LoRA
+    adapters whose blocks of ``blk`` columns lie side by side in ``wt`` [N, K] (``sel``: int32 [M] on the device, -1 = no
+    adapter).  There is no other route: shapes the kernel does not take are an error."""
+    pa, M, K, lda = _mat(x)
+    pb, N, Kb, ldb = _mat(wt)
+    assert K == Kb and out.shape == (M, N) and out.dtype == BF16 and out.stride(1) == 1 and out.is_cuda
+    assert sel.is_cuda and sel.dtype == torch.int32 and sel.shape == (M,) and sel.is_contiguous(), (sel.dtype, sel.shape)
+    check(lib.csm_skinny_nt_sel_bf16(pa, pb, out.data_ptr(), sel.data_ptr(), M, N, K, int(blk), lda, ldb, out.stride(0), float(alpha),
+                                     _stream()), "csm_skinny_nt_sel_bf16")
+    return out
+
+
 def linear_fwd(x, w, out, residual=None, alpha=1.0, pin=False):
     """out[M,N] = x[M,K] w[N,K]^T (+ residual)."""
     return gemm(x, w, out, residual, False, False, alpha, **_pin(pin))

@@ -47,7 +47,7 @@ class _EngineLoss(torch.autograd.Function):
 
 def compute_loss(model, input_tokens: torch.Tensor, input_masks: torch.Tensor, target_audio_tokens: torch.Tensor,
                  semantic_weight: float = 100.0, acoustic_weight: float = 1.0,
-                 acoustic_rows: Optional[torch.Tensor] = None, segment_lengths=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+                 acoustic_rows: Optional[torch.Tensor] = None, segment_lengths=None, adapter_ids=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """Loss of reference ``compute_loss`` (utils.py:56-119) on the HIP path.
 
     semantic = mean CE of codebook-0 logits at positions [0, S-1) vs ``target_audio_tokens[:, :S-1, 0]`` (no ignore
@@ -55,12 +55,14 @@ def compute_loss(model, input_tokens: torch.Tensor, input_masks: torch.Tensor, t
     ``model.acoustic_mode`` is "all" / "amortized" (teacher-forced depth-decoder CE over every / a 1/16 sample of the
     frames, the recipe the reference documents but never implemented); ``acoustic_rows`` pins the sampled rows.
     ``segment_lengths`` [B, n_max] marks a packed batch (``data.collate_packed``; ``Engine.forward_loss``).
+    ``adapter_ids`` (host integers [B], or [B, n_max] beside ``segment_lengths``; -1 = base model only): the adapter set every
+    example runs with when ``model.lora`` is a stack of sets (``LoRAState(n_adapters > 1)``).
     Returns (total, {"semantic_loss", "acoustic_loss"}).  ``total.backward()`` accumulates into ``param.grad``.
     """
     need_grad = torch.is_grad_enabled()
     total, sem, ac = model.engine.forward_loss(input_tokens, input_masks, target_audio_tokens, semantic_weight,
                                                acoustic_weight, save=need_grad, acoustic_rows=acoustic_rows,
-                                               segment_lengths=segment_lengths)
+                                               segment_lengths=segment_lengths, adapter_ids=adapter_ids)
     losses = {"semantic_loss": sem, "acoustic_loss": ac}
     if need_grad:
         if not hasattr(model, "_anchor"):

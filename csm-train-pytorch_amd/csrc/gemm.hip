@@ -203,6 +203,109 @@ __global__ __launch_bounds__(256) void skinny_nt_kernel(const bf16_t* __restrict
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The row-selected skinny product of a stack of LoRA adapters (training/lora.py, n_adapters > 1): the N columns are A blocks of
+// blk columns, one per adapter, and row m keeps only the block sel[m] names -
+//   out[m][n] = alpha * sum_k X[m][k] Wt[n][k]  if sel[m] >= 0 and n / blk == sel[m],   +0 otherwise (chosen, never multiplied:
+//   an Inf / NaN in a row that selects nothing, or beside a row's block, does not reach the output).
+// Same summation as skinny_nt_kernel - 16 rows per workgroup, a quarter of K per wave, k-steps ascending, ((q0 + q1) + q2) + q3,
+// then alpha - so a selected element has the bits csm_skinny_nt_bf16 gives it.  What differs is the loop order: the wave walks the
+// 16-column tiles and, per tile, the eight k-steps of a round (fw[8] instead of fw[8][NT]: 16 tiles of fragments do not fit the
+// register file), and it walks only the tiles that some row of its 16 selects - `tiles`, a wave-uniform mask made from the 16 sel
+// values with one load and NT ballots, so every `j` below is still a compile-time index under the unroll.  Rows of one example
+// are contiguous, so nearly every workgroup holds one adapter and does one adapter's work, whatever A is.  sel is compared, never
+// used as an index: a wild value selects nothing.
+template <int NT /* N / 16 */>
+__global__ __launch_bounds__(256) void skinny_nt_sel_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wt, bf16_t* __restrict__ out,
+                                                            const int* __restrict__ sel, int M, int K, int blk, int ldx, int ldw, int ldo, float alpha) {
+    constexpr int RS = 528;                                 // staged row, as in skinny_nt_kernel
+    constexpr int N = 16 * NT;
+    constexpr int CH = NT < 8 ? NT : 8;                     // tiles joined per pass of the reduction: 3 x 8 x 4 KiB fits the staging area
+    __shared__ __attribute__((aligned(16))) char stage[4][16 * RS];
+    static_assert(3 * CH * 64 * 4 * 4 <= 4 * 16 * RS, "reduction slabs must fit the staging area");
+    const int lane = threadIdx.x & 63, kq = threadIdx.x >> 6;
+    const int m0 = blockIdx.x * 16;
+    const int row = m0 + (lane & 15);
+    const int s = row < M ? sel[row] : -1;
+    // the columns [lo, hi) this lane's row keeps; a block that starts at or past N (or sel < 0) keeps nothing
+    const bool has = s >= 0 && s <= (N - 1) / blk;
+    const int lo = has ? s * blk : N, hi = has ? min(lo + blk, N) : N;
+    const unsigned mine = has ? (2u << ((hi - 1) >> 4)) - (1u << (lo >> 4)) : 0u;
+    unsigned tiles = 0;
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+        if (__builtin_amdgcn_ballot_w64(((mine >> j) & 1u) != 0)) tiles |= 1u << j;
+    tiles = __builtin_amdgcn_readfirstlane(tiles);
+
+    const int c = (lane >> 4) * 8;
+    const int kbeg = kq * (K >> 2), kend = kbeg + (K >> 2);
+    const bf16_t* wp = Wt + (size_t)(lane & 15) * ldw + c;
+    char* st = stage[kq];
+    f32x4 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (tiles)
+        for (int k0 = kbeg; k0 < kend; k0 += 256) {         // 256 k-values (8 k-steps of 32) per round; the last may be shorter
+            const int kn = min(256, kend - k0);             // multiple of 32
+            U4 xr[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {                   // instruction i: rows 2i, 2i+1, 32 lanes x 16 B each
+                const int r = min(m0 + 2 * i + (lane >> 5), M - 1);
+                const int kk = min((lane & 31) * 8, kn - 8);
+                xr[i] = *reinterpret_cast<const U4*>(X + (size_t)r * ldx + k0 + kk);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) *reinterpret_cast<U4*>(st + (2 * i + (lane >> 5)) * RS + (lane & 31) * 16) = xr[i];
+            bf16x8 fx[8];                                   // (wave-private staging: a wave's own LDS operations execute in order)
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                fx[u] = *reinterpret_cast<const bf16x8*>(st + (lane & 15) * RS + min(u * 64, (kn - 32) * 2) + (lane >> 4) * 16);
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+                if (tiles & (1u << j)) {
+                    bf16x8 fw[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        fw[u] = *reinterpret_cast<const bf16x8*>(wp + (size_t)(16 * j) * ldw + k0 + min(32 * u, kn - 32));
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        if (32 * u < kn) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[u], fx[u], acc[j], 0, 0, 0);
+                }
+        }
+    // lane holds out[row][16 j + 4 (lane >> 4) .. + 3]; the four K quarters of the walked tiles meet in LDS, CH tiles per pass
+    float* red = reinterpret_cast<float*>(&stage[0][0]);    // [3][CH][64][4]
+#pragma unroll
+    for (int j0 = 0; j0 < NT; j0 += CH) {
+        __syncthreads();                                    // the staging area (or the previous pass) is done with
+        if (kq > 0) {
+#pragma unroll
+            for (int jj = 0; jj < CH; ++jj)
+                if (j0 + jj < NT && (tiles & (1u << (j0 + jj)))) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) red[(((kq - 1) * CH + jj) * 64 + lane) * 4 + r] = acc[j0 + jj][r];
+                }
+        }
+        __syncthreads();
+        if (kq == 0 && row < M) {
+#pragma unroll
+            for (int jj = 0; jj < CH; ++jj)
+                if (j0 + jj < NT) {
+                    const int j = j0 + jj, col = 16 * j + 4 * (lane >> 4);   // blk % 8 == 0: the lane's four columns share a block
+                    uint2 o; o.x = 0u; o.y = 0u;
+                    if (tiles & (1u << j)) {
+                        float v[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            v[r] = (((acc[j][r] + red[((0 * CH + jj) * 64 + lane) * 4 + r]) + red[((1 * CH + jj) * 64 + lane) * 4 + r]) +
+                                    red[((2 * CH + jj) * 64 + lane) * 4 + r]) * alpha;
+                        if (col >= lo && col < hi) { o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]); }
+                    }
+                    *reinterpret_cast<uint2*>(out + (size_t)row * ldo + col) = o;
+                }
+        }
+    }
+}
+
 // symbol (as rocprofv3 prints it, argument list dropped) of the kernel the most recent GEMM entry point launched: bench.py
 // names the kernels behind its per-kind timings with it (csm_gemm_last_kernel)
 #define CSM_KNAME(base, TA, TB, f32, extra) \
@@ -409,6 +512,29 @@ extern "C" int csm_skinny_nt_bf16(const void* X, const void* Wt, void* out, int 
     if (N == 32) hipLaunchKernelGGL((skinny_nt_kernel<2>), grid, block, 0, stream, (const bf16_t*)X, (const bf16_t*)Wt, (bf16_t*)out, M, K, ldx, ldw, ldo, alpha);
     else hipLaunchKernelGGL((skinny_nt_kernel<4>), grid, block, 0, stream, (const bf16_t*)X, (const bf16_t*)Wt, (bf16_t*)out, M, K, ldx, ldw, ldo, alpha);
     CSM_CHECK_LAUNCH("csm_skinny_nt_bf16");
+    return 0;
+}
+
+// out[m][n] = alpha * X[m] . Wt[n] where sel[m] >= 0 and n / blk == sel[m], +0 elsewhere: csm_skinny_nt_bf16 for a stack of LoRA
+// adapters whose blocks of blk columns lie side by side in Wt, each row keeping its own adapter's block (skinny_nt_sel_kernel).
+extern "C" int csm_skinny_nt_sel_bf16(const void* X, const void* Wt, void* out, const int* sel, int M, int N, int K, int blk, int ldx,
+                                      int ldw, int ldo, float alpha, hipStream_t stream) {
+    CSM_REQUIRE(X && Wt && out && sel && M > 0, "csm_skinny_nt_sel_bf16: null operand");
+    CSM_REQUIRE(N >= 32 && N <= 256 && N % 32 == 0 && K >= 128 && K % 128 == 0,
+                "csm_skinny_nt_sel_bf16: N must be a multiple of 32 in [32, 256] and K a multiple of 128 (N=%d K=%d)", N, K);
+    CSM_REQUIRE(blk >= 8 && blk % 8 == 0, "csm_skinny_nt_sel_bf16: blk must be a positive multiple of 8 (blk=%d)", blk);
+    CSM_REQUIRE((ldx & 7) == 0 && (ldw & 7) == 0 && (ldo & 3) == 0 && ldx >= K && ldw >= K && ldo >= N, "csm_skinny_nt_sel_bf16: bad leading dimensions");
+    CSM_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)Wt & 15) == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)sel & 3) == 0,
+                "csm_skinny_nt_sel_bf16: operands must be 16-byte aligned (sel: 4-byte)");
+    const dim3 grid((M + 15) / 16), block(256);
+#define CSM_SEL_CASE(NT) \
+    case NT: hipLaunchKernelGGL((skinny_nt_sel_kernel<NT>), grid, block, 0, stream, (const bf16_t*)X, (const bf16_t*)Wt, (bf16_t*)out, sel, M, K, blk, \
+                                ldx, ldw, ldo, alpha); break;
+    switch (N / 16) {
+        CSM_SEL_CASE(2) CSM_SEL_CASE(4) CSM_SEL_CASE(6) CSM_SEL_CASE(8) CSM_SEL_CASE(10) CSM_SEL_CASE(12) CSM_SEL_CASE(14) CSM_SEL_CASE(16)
+    }
+#undef CSM_SEL_CASE
+    CSM_CHECK_LAUNCH("csm_skinny_nt_sel_bf16");
     return 0;
 }
 

@@ -77,6 +77,13 @@ int csm_gemm_bf16_pinned(const void* A, const void* B, void* C, const void* R, i
  * reference src/csm/mlx/components/lora.py:85-105 with the group's ranks side by side), read-once bandwidth kernel. */
 int csm_skinny_nt_bf16(const void* X, const void* Wt, void* out, int M, int N, int K, int ldx, int ldw, int ldo, float alpha,
                        csm_stream_t stream);
+/* csm_skinny_nt_bf16 for a stack of LoRA adapters trained in one batch: Wt holds the adapters' blocks of blk columns side by side
+ * (N a multiple of 32 in [32, 256], blk a multiple of 8) and row m keeps the block of its own adapter sel[m] (int32 on the device,
+ * -1 = none):  out[m][n] = alpha * sum_k X[m][k] Wt[n][k] if sel[m] >= 0 and n / blk == sel[m], +0 otherwise.  The zeros are
+ * chosen, not multiplied (Inf / NaN in X beside them does not matter); sel is compared only, never an index.  A kept element
+ * has the bits csm_skinny_nt_bf16 gives it; only the 16-column tiles some row of a 16-row tile keeps are computed. */
+int csm_skinny_nt_sel_bf16(const void* X, const void* Wt, void* out, const int* sel, int M, int N, int K, int blk, int ldx, int ldw,
+                           int ldo, float alpha, csm_stream_t stream);
 /* The two backward products of a Linear layer in one launch, their tiles interleaved over the chip:
  *   dX[M][Kin] = dY[M][Nout] W[Nout][Kin]   (dx_epilogue 0), or the SwiGLU backward of that product (dx_epilogue 2: W = w2,
  *   aux_in = gate/up [M][2 Kin], dX = d(gate/up) [M][2 Kin]);   dW[Nout][Kin] (+)= alpha_w * dY^T X[M][Kin].
