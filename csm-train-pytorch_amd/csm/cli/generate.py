@@ -51,6 +51,9 @@ def parse_args(argv=None):
                         "order (KV cache kept between them; adapter and seed of its first line); one WAV per utterance, "
                         "<output stem>_<i>.wav with i = 0, 1, ... counting the file's non-empty lines")
     p.add_argument("--slots", type=int, default=16, help="--serve-file: utterances decoded at once (1..16, default 16)")
+    p.add_argument("--hear-slots", type=int, default=0,
+                   help="--serve-file: encoder slots of the server's batched hearing (Generator.serve(hear_slots=N), 0..16; "
+                        "default 0: every conversation that hears has its own encode stream)")
     args = p.parse_args(argv)
     if args.text is None and args.serve_file is None:
         p.error("one of --text and --serve-file is required")
@@ -58,6 +61,10 @@ def parse_args(argv=None):
         p.error("--serve-file takes its lines from the file: not with --text, --next-text or --stream")
     if not 1 <= args.slots <= 16:
         p.error("--slots must be 1..16")
+    if not 0 <= args.hear_slots <= 16:
+        p.error("--hear-slots must be 0..16")
+    if args.hear_slots and args.serve_file is None:
+        p.error("--hear-slots goes with --serve-file")
     if args.next_speaker and len(args.next_speaker) != len(args.next_text or []):
         p.error("--next-speaker must be given once per --next-text (or not at all)")
     return args
@@ -161,7 +168,7 @@ def serve_to_wavs(generator, args, context, adapter=None):
     os.makedirs(os.path.dirname(stem), exist_ok=True)
     t0 = time.perf_counter()
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, temperature=args.temperature,
-                             topk=args.topk)
+                             topk=args.topk, hear_slots=args.hear_slots)
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
     def say(cid):

@@ -9,6 +9,7 @@ Hugging Face port (``transformers.MimiModel.state_dict()``; the moshi checkpoint
 what ``Generator`` touches: ``encode([1,1,N]) -> [1,K,T]`` int64, ``decode([1,K,T]) -> [1,1,N]``, ``sample_rate``, and
 ``decode_stream()``: a stateful decoder that turns successive chunks of frames into their audio, bit-identical to ``decode``,
 and ``encode_stream()``: its counterpart for the audio that is heard, bit-identical to ``encode`` on whole frames.
+``decode_stream_rows()`` / ``encode_stream_rows()`` are the two for up to 16 utterances at once, one launch per op.
 """
 import math
 from typing import Dict, Optional
@@ -62,6 +63,47 @@ def history_len(kind: str, k: int, stride: int = 1, dilation: int = 1) -> int:
 def ring_slot(pos: int, ring: int) -> int:
     """Slot of absolute transformer position ``pos`` in a K/V ring of ``ring`` rows (csm_attn_window_stream_f32)."""
     return pos % ring
+
+
+def _transformer_rows(cd: "MimiCodec", tr: str, kv, x, rows, pos0, n2):
+    """``MimiCodec._transformer`` on the stacked rows x [R*n2, hidden] of transformer ``tr``: the row-wise ops (LayerNorm, linear)
+    run over all of them, RoPE and the ring attention take row r's own first position ``pos0[r]`` and the K/V rings
+    ``kv[layer]`` ([slots, ring, hidden] each) of its slot ``rows[r]``.  Shared by the rows decoder and the rows encoder."""
+    T, D = x.shape
+    H, w = cd.heads, cd.w
+    for i in range(cd.n_layers):
+        p = f"{tr}.layers.{i}"
+        xn = torch.empty_like(x)
+        check(lib.csm_layernorm_f32(x.data_ptr(), w[f"{p}.input_layernorm.weight"].data_ptr(), w[f"{p}.input_layernorm.bias"].data_ptr(),
+                                    xn.data_ptr(), T, D, cd.eps, _s()), "csm_layernorm_f32")
+        qkv = cd._linear(xn, w[f"{p}.self_attn.qkv"])
+        ops.rope_half_rows_f32(qkv, pos0, n2, H, cd.theta)
+        o = torch.empty(T, D, dtype=F32, device=cd.dev)
+        kc, vc = kv[i]
+        ops.attn_window_stream_rows_f32(qkv, kc, vc, o, rows, pos0, n2, H, cd.window)
+        x = cd._linear(o, w[f"{p}.self_attn.o_proj.weight"], scale=w[f"{p}.self_attn_layer_scale.scale"], res=x)
+        check(lib.csm_layernorm_f32(x.data_ptr(), w[f"{p}.post_attention_layernorm.weight"].data_ptr(),
+                                    w[f"{p}.post_attention_layernorm.bias"].data_ptr(), xn.data_ptr(), T, D, cd.eps, _s()),
+              "csm_layernorm_f32")
+        h1 = cd._linear(xn, w[f"{p}.mlp.fc1.weight"], act=1)
+        x = cd._linear(h1, w[f"{p}.mlp.fc2.weight"], scale=w[f"{p}.mlp_layer_scale.scale"], res=x)
+    return x
+
+
+def peel_schedule(pending, max_chunk_frames: int):
+    """The launches that encode ``pending`` = {slot: whole frames waiting} with rows kernels that take ONE chunk size per launch:
+    a list of (n, [slots]).  While any slot has frames left, every such slot steps by n = the least of min(left,
+    max_chunk_frames) over them - so each launch carries every slot that still has work (the fullest rows), and there is one
+    launch per distinct pending count plus one per ``max_chunk_frames`` split (the fewest).  Any split gives the same bits."""
+    if max_chunk_frames < 1:
+        raise ValueError("max_chunk_frames must be >= 1")
+    left = {int(s): int(p) for s, p in dict(pending).items() if int(p) > 0}
+    out = []
+    while left:
+        n = min(min(p, max_chunk_frames) for p in left.values())
+        out.append((n, sorted(left)))
+        left = {s: p - n for s, p in left.items() if p > n}
+    return out
 
 
 class MimiCodec:
@@ -209,6 +251,12 @@ class MimiCodec:
         steps equal ``encode`` of all the samples, bit for bit."""
         return MimiEncodeStream(self, max_chunk_frames)
 
+    def encode_stream_rows(self, slots: int = 16, max_chunk_frames: int = 32) -> "MimiEncodeStreamRows":
+        """``encode_stream`` for up to ``slots`` (<= 16) utterances heard at once: ``open(slot)`` starts one, ``step(slots, wav
+        [R, n*1920])`` returns the next n frames' codes of R of them ([R, K, n]) from one launch per op; ``feed`` / ``drain`` buffer
+        and batch.  Every slot's concatenated codes equal ``encode`` of its whole frames, bit for bit."""
+        return MimiEncodeStreamRows(self, slots, max_chunk_frames)
+
     def _dequantize(self, c):
         """codes [K, T] int64 -> latent [T, hidden] (both residual VQs + their output projections)."""
         K, T = c.shape
@@ -344,6 +392,167 @@ class MimiEncodeStream:
         pad = torch.zeros(self.frame - self._rem.numel(), dtype=F32, device=self.codec.dev)
         buf, self._rem = torch.cat([self._rem, pad]), self._rem[:0]
         return self.step(buf)
+
+
+class MimiEncodeStreamRows:
+    """``MimiEncodeStream`` for up to 16 utterances heard at once: the same state with a leading slot dimension, and a ``step``
+    that encodes one chunk of R of them with ONE launch per op - csm_conv1d_stream_rows_f32 for the stride-1 convs,
+    csm_conv1d_stream_strided_rows_f32 for the strided ones, the rows transformer of ``MimiDecodeStreamRows``; LayerNorm, the
+    linears and the RVQ search are row-wise and run on the stacked rows.  An encoder step is latency-bound (a chain of dependent
+    FMAs per output), so the rows ride along.  Every row is computed with the arithmetic of the one-row kernels, so a slot's
+    concatenated codes equal ``MimiEncodeStream``'s and ``MimiCodec.encode``'s on its whole frames, bit for bit, whatever its
+    neighbours do.
+    State per slot: both history buffers of every conv layer ([slots, 2, C_in, H]), a K/V ring of
+    ``window + 2 * max_chunk_frames - 1`` rows per transformer layer, the frames encoded so far and the history parity (host),
+    and the samples not yet encoded: the remainder of the last ``drain`` on the device plus the pieces ``feed`` was given since.
+    ``step`` makes no host synchronisation: slots, parities, positions and the edge-first flags reach the kernels by value.
+    The rows kernels take one chunk size per launch; ``drain`` brings ragged slots to it with ``peel_schedule``.
+    ``flush`` pads the WAVEFORM of a partial frame with zeros, as ``MimiEncodeStream.flush`` does."""
+
+    def __init__(self, codec: MimiCodec, slots: int = 16, max_chunk_frames: int = 32):
+        if not 1 <= slots <= 16:
+            raise ValueError(f"slots must be 1..16 (the rows kernels take at most 16 rows a launch), got {slots}")
+        if max_chunk_frames < 1:
+            raise ValueError("max_chunk_frames must be >= 1")
+        self.codec, self.slots, self.max_chunk_frames = codec, slots, max_chunk_frames
+        dev, w = codec.dev, codec.w
+        self.layers = {name: (k, stride, elu, rep) for name, k, stride, elu, rep in encoder_conv_layers(codec.ratios)}
+        self.frame = math.prod(stride for _, stride, _, _ in self.layers.values())        # samples per frame (1920)
+        self.hist = {}
+        for name, (k, stride, _, _) in self.layers.items():
+            H = history_len("conv", k, stride)
+            C_in = w[f"{name}.conv.weight"].shape[1]                                       # (every encoder conv has groups = 1)
+            self.hist[name] = torch.zeros(slots, 2, C_in, H, dtype=F32, device=dev) if H else None
+        self.ring = codec.window + 2 * max_chunk_frames - 1
+        self.kv = [tuple(torch.zeros(slots, self.ring, codec.hidden, dtype=F32, device=dev) for _ in range(2))
+                   for _ in range(codec.n_layers)]
+        self.pos = [0] * slots             # frames encoded so far, per slot
+        self._par = [0] * slots            # hist[name][slot, _par[slot]] holds the slot's current history
+        self._live = [False] * slots       # open(slot) .. close(slot)
+        self._rem = [None] * slots         # device: the samples the last drain left over (less than a frame), or None
+        self._fed = [[] for _ in range(slots)]     # the pieces fed since, as given
+        self._count = [0] * slots          # samples waiting: remainder + pieces
+
+    def _slot(self, slot):
+        if not 0 <= slot < self.slots:
+            raise ValueError(f"slot {slot} out of range (0..{self.slots - 1})")
+        return int(slot)
+
+    def open(self, slot: int):
+        """Start a new utterance in ``slot`` (also after an earlier one ended there): zero histories, position 0, nothing waiting."""
+        slot = self._slot(slot)
+        for arena in self.hist.values():
+            if arena is not None:
+                arena[slot].zero_()
+        self._par[slot] = 0
+        self.pos[slot] = 0
+        self._live[slot] = True
+        self._rem[slot], self._fed[slot], self._count[slot] = None, [], 0
+
+    def close(self, slot: int):
+        """The utterance in ``slot`` is over: what still waits there is dropped and ``drain()`` no longer visits it."""
+        slot = self._slot(slot)
+        self._live[slot] = False
+        self._rem[slot], self._fed[slot], self._count[slot] = None, [], 0
+
+    @property
+    def open_slots(self):
+        return [s for s in range(self.slots) if self._live[s]]
+
+    def _conv(self, x, name, rows, res=None, edge_first=()):
+        k, stride, elu, _ = self.layers[name]
+        wt, b = self.codec.w[f"{name}.conv.weight"], self.codec.w.get(f"{name}.conv.bias")
+        y = torch.empty(x.shape[0], wt.shape[0], x.shape[2] // stride, dtype=F32, device=self.codec.dev)
+        par = [self._par[s] for s in rows]
+        if stride == 1:
+            return ops.conv1d_stream_rows_f32(self.hist[name], x, wt, b, y, rows, par, 1, elu, res)
+        return ops.conv1d_stream_strided_rows_f32(self.hist[name], x, wt, b, y, rows, par, stride, 1, elu, res, edge_first)
+
+    def _transpose(self, x):
+        y = torch.empty(x.shape[0], x.shape[2], x.shape[1], dtype=F32, device=self.codec.dev)
+        return ops.transpose_rows_f32(x, y)
+
+    @torch.no_grad()
+    def step(self, slots, wav: torch.Tensor) -> torch.Tensor:
+        """wav [R, n * 1920] - the next n frames of the utterances in ``slots`` (R distinct slot indices, in the rows' order) ->
+        their codes [R, K, n] int64."""
+        cd = self.codec
+        rows = [int(s) for s in slots]
+        R = len(rows)
+        if not 1 <= R <= self.slots or len(set(rows)) != R or any(not 0 <= s < self.slots for s in rows):
+            raise ValueError(f"step takes 1..{self.slots} distinct slots in 0..{self.slots - 1}, got {rows}")
+        if wav.dim() != 2 or wav.shape[0] != R or wav.shape[1] == 0 or wav.shape[1] % self.frame:
+            raise ValueError(f"wav must be [R = {R}, n * {self.frame}] with n >= 1, got {tuple(wav.shape)}")
+        n = wav.shape[1] // self.frame
+        if n > self.max_chunk_frames:
+            raise ValueError(f"a step takes 1..max_chunk_frames = {self.max_chunk_frames} frames per row, got {n}")
+        x = wav.reshape(R, 1, -1).to(cd.dev, F32).contiguous()
+        x = self._conv(x, "encoder.layers.0", rows)
+        idx = 1
+        for _ in cd.ratios:
+            h = self._conv(x, f"encoder.layers.{idx}.block.1", rows)
+            x = self._conv(h, f"encoder.layers.{idx}.block.3", rows, res=x)
+            x = self._conv(x, f"encoder.layers.{idx + 2}", rows)
+            idx += 3
+        x = self._conv(x, f"encoder.layers.{idx + 1}", rows)                                       # [R, hidden, 2n]
+        x = _transformer_rows(cd, "encoder_transformer", self.kv, self._transpose(x).view(R * 2 * n, cd.hidden), rows,
+                              [2 * self.pos[s] for s in rows], 2 * n)
+        x = self._conv(self._transpose(x.view(R, 2 * n, cd.hidden)), "downsample", rows,
+                       edge_first=[self.pos[s] == 0 for s in rows])                                # [R, hidden, n]
+        codes = cd._quantize(self._transpose(x).view(R * n, cd.hidden))                            # [K, R * n], row after row
+        for s in rows:
+            self._par[s] ^= 1
+            self.pos[s] += n
+        return codes.view(cd.K, R, n).permute(1, 0, 2).contiguous()
+
+    def feed(self, slot: int, wav: torch.Tensor) -> int:
+        """Any number of samples for ``slot``: they wait for the next ``drain``.  Nothing is launched, copied or synchronised -
+        the piece is held as given, so the caller must not overwrite it before that drain.  Returns ``pending(slot)``."""
+        slot = self._slot(slot)
+        if not self._live[slot]:
+            raise ValueError(f"feed: slot {slot} is not open")
+        if wav.numel():
+            self._fed[slot].append(wav.detach().reshape(-1))
+            self._count[slot] += wav.numel()
+        return self._count[slot] // self.frame
+
+    def pending(self, slot: int) -> int:
+        """Whole frames waiting in ``slot``."""
+        return self._count[self._slot(slot)] // self.frame
+
+    @torch.no_grad()
+    def drain(self, slots=None, flush=()):
+        """Encode every whole frame waiting in ``slots`` (default: all open slots) -> {slot: codes [K, m] int64}, m >= 0.
+        Slots named in ``flush`` (a subset of ``slots``) first have their partial frame zero-padded to a whole one.  The launches
+        follow ``peel_schedule``."""
+        cd = self.codec
+        todo = self.open_slots if slots is None else [self._slot(s) for s in slots]
+        flush = {self._slot(s) for s in flush}
+        if len(set(todo)) != len(todo) or any(not self._live[s] for s in todo) or not flush <= set(todo):
+            raise ValueError(f"drain takes distinct open slots and flushes only slots it drains, got {todo} / flush {sorted(flush)}")
+        bufs = {}
+        for s in todo:
+            parts = ([self._rem[s]] if self._rem[s] is not None else []) + [p.to(cd.dev, F32) for p in self._fed[s]]
+            tail = self._count[s] % self.frame
+            if s in flush and tail:
+                parts.append(torch.zeros(self.frame - tail, dtype=F32, device=cd.dev))
+                self._count[s] += self.frame - tail
+            if parts:
+                bufs[s] = parts[0] if len(parts) == 1 else torch.cat(parts)
+            self._fed[s] = []
+        out = {s: [] for s in todo}
+        at = dict.fromkeys(todo, 0)
+        for n, group in peel_schedule({s: self._count[s] // self.frame for s in todo}, self.max_chunk_frames):
+            m = n * self.frame
+            codes = self.step(group, torch.stack([bufs[s][at[s]:at[s] + m] for s in group]))
+            for r, s in enumerate(group):
+                out[s].append(codes[r])
+                at[s] += m
+        for s in todo:
+            self._count[s] -= at[s]
+            self._rem[s] = bufs[s][at[s]:].clone() if self._count[s] else None
+        none = torch.zeros(cd.K, 0, dtype=torch.int64, device=cd.dev)
+        return {s: torch.cat(c, 1) if c else none for s, c in out.items()}
 
 
 class MimiDecodeStream:
@@ -486,29 +695,8 @@ class MimiDecodeStreamRows:
         return ops.transpose_rows_f32(x, y)
 
     def _transformer(self, x, rows, n2):
-        """``MimiCodec._transformer`` on the stacked rows x [R*n2, hidden]: the row-wise ops (LayerNorm, linear) run over all of
-        them, RoPE and the ring attention take each row's own position 2 * frames-so-far."""
-        cd = self.codec
-        T, D = x.shape
-        H, w, tr = cd.heads, cd.w, "decoder_transformer"
-        pos0 = [2 * self.pos[s] for s in rows]
-        for i in range(cd.n_layers):
-            p = f"{tr}.layers.{i}"
-            xn = torch.empty_like(x)
-            check(lib.csm_layernorm_f32(x.data_ptr(), w[f"{p}.input_layernorm.weight"].data_ptr(), w[f"{p}.input_layernorm.bias"].data_ptr(),
-                                        xn.data_ptr(), T, D, cd.eps, _s()), "csm_layernorm_f32")
-            qkv = cd._linear(xn, w[f"{p}.self_attn.qkv"])
-            ops.rope_half_rows_f32(qkv, pos0, n2, H, cd.theta)
-            o = torch.empty(T, D, dtype=F32, device=cd.dev)
-            kc, vc = self.kv[i]
-            ops.attn_window_stream_rows_f32(qkv, kc, vc, o, rows, pos0, n2, H, cd.window)
-            x = cd._linear(o, w[f"{p}.self_attn.o_proj.weight"], scale=w[f"{p}.self_attn_layer_scale.scale"], res=x)
-            check(lib.csm_layernorm_f32(x.data_ptr(), w[f"{p}.post_attention_layernorm.weight"].data_ptr(),
-                                        w[f"{p}.post_attention_layernorm.bias"].data_ptr(), xn.data_ptr(), T, D, cd.eps, _s()),
-                  "csm_layernorm_f32")
-            h1 = cd._linear(xn, w[f"{p}.mlp.fc1.weight"], act=1)
-            x = cd._linear(h1, w[f"{p}.mlp.fc2.weight"], scale=w[f"{p}.mlp_layer_scale.scale"], res=x)
-        return x
+        """The decoder transformer on the stacked rows x [R*n2, hidden], each row at position 2 * frames-so-far."""
+        return _transformer_rows(self.codec, "decoder_transformer", self.kv, x, rows, [2 * self.pos[s] for s in rows], n2)
 
     @torch.no_grad()
     def step(self, slots, codes: torch.Tensor) -> torch.Tensor:

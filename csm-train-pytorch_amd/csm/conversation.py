@@ -57,6 +57,12 @@ class HeardTurn:
         """Frames encoded so far."""
         return self._frames
 
+    @property
+    def pending(self) -> int:
+        """Whole frames fed but not encoded yet: always 0 here - ``feed`` encodes them at once.  (On a server with
+        ``hear_slots`` they wait for ``hear_step``: ``SlotHeardTurn`` in csm/serving.py.)"""
+        return 0
+
     @torch.inference_mode()
     def feed(self, audio: torch.Tensor) -> int:
         """The next samples of the turn, any number of them ((n,), sample_rate 24 kHz); returns ``frames``."""
@@ -72,9 +78,13 @@ class HeardTurn:
         conv, gen = self._conv, self._conv._gen
         conv._before_history("end")                                 # (raises with the turn still open: end() can be retried)
         self._take(self._stream.flush())
+        self._enter(*gen._tokenize_text_segment(text, self.speaker))
+
+    def _enter(self, tt, tm) -> None:
+        """The turn enters the history: the text frames ``tt`` / ``tm``, the codes taken so far, the EOS frame."""
+        conv, gen = self._conv, self._conv._gen
         K = gen._model.args.audio_num_codebooks
         codes = torch.cat(self._codes, 1) if self._codes else torch.zeros(K, 0, dtype=torch.long, device=gen.device)
-        tt, tm = gen._tokenize_text_segment(text, self.speaker)
         at, am = gen._audio_frames(codes.to(gen.device))
         self.closed, conv._heard = True, None
         conv._push(torch.cat([tt, at], dim=0).long(), torch.cat([tm, am], dim=0).bool())

@@ -286,7 +286,7 @@ class Generator:
                 out.append(self._audio_tokenizer.decode(codes_all[b:b + 1, :, :n]).squeeze(0).squeeze(0))
         return out
 
-    def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50):
+    def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0):
         """A running batch (csm/serving.py): ``server.submit(text, speaker, context, adapter=None, seed=None,
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
@@ -295,9 +295,12 @@ class Generator:
         speaker)`` queues its next turn as a request, ``conv.add(Segment)`` (or ``conv.hear(speaker)`` -> ``feed`` / ``end``, encoded
         while it is spoken) is the other party's turn; its KV history is parked
         between turns and resumed into any free slot, so more conversations than slots can be open.  It takes over the model's caches like any ``generate*`` call (open streams and older servers are
-        invalidated) and binds the adapters loaded so far: load adapters first."""
+        invalidated) and binds the adapters loaded so far: load adapters first.
+        ``hear_slots`` (0..16): 0, the default, gives every conversation that hears its own encode stream, one encoder step per
+        ``feed``; N >= 1 gives the server one rows encoder of N slots - ``feed`` only buffers, ``server.hear_step()`` (called by
+        ``step()``) encodes all open heard turns in one batched step, ``server.end_heard([(turn, text), ...])`` ends several."""
         from .serving import BatchServer
-        return BatchServer(self, slots, chunk_frames, temperature, topk)
+        return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots)
 
     def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error"):
         """A multi-turn dialogue that keeps its KV cache between turns (csm/conversation.py): ``conv.generate(text, speaker)`` /

@@ -109,6 +109,7 @@ _SIGS = {
     "csm_attn_window_stream_f32": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_rvq_decode": ([_p, _p, _p, _i, _i, _i, _i, _p], _i),
     "csm_conv1d_stream_rows_f32": ([_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),
+    "csm_conv1d_stream_strided_rows_f32": ([_p, _p, _p, _p, _p, _p, _i, _p, _p, C.c_uint, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_conv_transpose1d_stream_rows_f32": ([_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_rope_half_rows_f32": ([_p, _i, _p, _i, _i, _i, _f, _p], _i),
     "csm_attn_window_stream_rows_f32": ([_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),

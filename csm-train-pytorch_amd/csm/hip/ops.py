@@ -799,6 +799,29 @@ def conv1d_stream_rows_f32(arena, x, w, bias, y, slots, parity, dilation=1, elu_
     return y
 
 
+def conv1d_stream_strided_rows_f32(arena, x, w, bias, y, slots, parity, stride, dilation=1, elu_in=False, residual=None,
+                                   edge_first=()):
+    """``conv1d_stream_strided_f32`` for R rows in one launch (csm_conv1d_stream_strided_rows_f32): x [R, C_in, n_in] ->
+    y [R, C_out, n_in // stride] (+ residual of that shape).  ``arena`` [n_slots, 2, C_in, H], H = (k-1)*dil + 1 - stride (None
+    when H == 0), read and written as by ``conv1d_stream_rows_f32``.  ``edge_first``: one flag per row (or empty = none); a
+    flagged row does not read its history, every history column is column 0 of its x."""
+    R, C_in, n_in = x.shape
+    C_out, cin_g, k = w.shape
+    H = (k - 1) * dilation + 1 - stride
+    assert y.shape == (R, C_out, n_in // stride) and C_in % cin_g == 0 and len(slots) == len(parity) == R
+    assert len(edge_first) in (0, R)
+    n_slots = arena.shape[0] if H > 0 else max(slots) + 1
+    if H > 0:
+        assert arena.shape[1:] == (2, C_in, H)
+    mask = sum(1 << r for r, e in enumerate(edge_first) if e)
+    check(lib.csm_conv1d_stream_strided_rows_f32(_f32(arena, "arena") if H > 0 else None, _f32(x, "x"), _f32(w, "w"),
+                                                 None if bias is None else _f32(bias, "bias"),
+                                                 None if residual is None else _f32(residual, "res"), _f32(y, "y"), R, _ints(slots),
+                                                 _ints(parity), mask, n_slots, C_in, C_out, n_in, k, stride, dilation, C_in // cin_g,
+                                                 int(elu_in), _stream()), "csm_conv1d_stream_strided_rows_f32")
+    return y
+
+
 def conv_transpose1d_stream_rows_f32(arena, x, w, bias, y, slots, parity, pos0, stride, groups=1, elu_in=False):
     """``conv_transpose1d_stream_f32`` for R rows in one launch: x [R, C_in, n] at input positions ``pos0[r]`` ->
     y [R, C_out, n*stride]; ``arena`` [n_slots, 2, C_in, ceil(k/stride)-1] as for ``conv1d_stream_rows_f32``."""

@@ -32,9 +32,16 @@ the audio and from the parked length, as frames after EOS are - which is why ``s
 headroom beyond ``max_audio_frames``.  A conversation's ``seed`` gives it one generator for its whole life, which moves only
 when the conversation samples a frame and travels with it from slot to slot.
 
+Hearing (``conv.hear`` -> ``turn.feed`` / ``turn.end``) Mimi-encodes the other party's turn while it is spoken.  By default
+every conversation owns a ``MimiEncodeStream`` and every ``feed`` is one encoder step for that conversation.  With
+``serve(hear_slots=N)`` (1..16) the server owns ONE ``MimiEncodeStreamRows`` of N slots instead: ``hear`` takes a free encoder
+slot, ``feed`` only buffers, and ``hear_step()`` - which ``step()`` calls first - encodes what waits in every open heard turn
+with one batched ``drain``: N listeners cost one encoder step per chunk (plus one per distinct backlog, ``peel_schedule``).
+``turn.end`` drains and flushes its own slot; ``end_heard`` does it for turns that end together with one drain for all.
+
 Limitations: a join stalls the other rows for one whole prefill or append (no chunked prefill); the context audio of a request
-and a conversation's ``add``ed turns are Mimi-encoded at ``submit`` / ``add``, one segment at a time (``conv.hear`` encodes a turn
-while it is being spoken instead, one encoder step per ``feed``, one conversation at a time); adapters added to the
+and a conversation's ``add``ed turns are Mimi-encoded at ``submit`` / ``add``, one segment at a time (only ``conv.hear`` encodes
+while the turn is being spoken - and only with ``hear_slots`` batched over the conversations); adapters added to the
 Generator after ``serve()`` are unknown to the server (the state binds the bank at creation).
 """
 from collections import deque
@@ -71,6 +78,35 @@ class Request:
         if not self._codes:
             return torch.zeros(self._tokens.shape[-1] - 1, 0, dtype=torch.long, device=self._device)
         return torch.cat(self._codes, 1)
+
+
+class SlotHeardTurn(HeardTurn):
+    """``conv.hear(speaker)`` on a server with ``hear_slots``: the turn holds one slot of the server's ``MimiEncodeStreamRows``
+    from ``hear`` to ``end`` / ``cancel`` / ``conv.close()``.  ``feed`` only buffers (nothing is launched; the piece is held as
+    given until the next ``hear_step``, so do not overwrite it before); ``frames`` counts the frames encoded so far,
+    ``pending`` the whole frames that wait for the next ``hear_step``."""
+
+    def __init__(self, conv, speaker: int, server, slot: int):
+        super().__init__(conv, speaker, server._hear)
+        self._srv, self.slot = server, slot
+
+    @property
+    def pending(self) -> int:
+        return 0 if self.closed else self._stream.pending(self.slot)
+
+    def feed(self, audio: torch.Tensor) -> int:
+        self._check("feed")
+        self._srv._check()
+        self._stream.feed(self.slot, audio.reshape(-1))
+        return self._frames
+
+    def end(self, text: str) -> None:
+        self._srv.end_heard([(self, text)])
+
+    def cancel(self) -> None:
+        if not self.closed:
+            self._srv._free_heard(self)
+            super().cancel()
 
 
 class ServedConversation:
@@ -128,10 +164,13 @@ class ServedConversation:
     def hear(self, speaker: int) -> HeardTurn:
         """The other party starts to speak: ``turn.feed(audio)`` Mimi-encodes the turn as it arrives - between the server's steps,
         whoever holds the slots - and ``turn.end(text)`` enters it as ``add`` would, under ``add``'s rules (no turn of this
-        conversation still open), with nothing left to encode but its last partial frame."""
+        conversation still open), with nothing left to encode but its last partial frame.  On a server with ``hear_slots`` the
+        turn takes one of its encoder slots (``SlotHeardTurn``; RuntimeError when none is free)."""
         self._srv._check()
         if self.closed:
             raise RuntimeError("hear: this conversation was closed")
+        if self._srv.hear_slots:
+            return self._srv._open_heard(self, speaker)
         return open_heard_turn(self, speaker)
 
     _before_history = _idle
@@ -198,8 +237,10 @@ class ServedConversation:
         self._parked = state.park_row(b, self._cached)
 
     def close(self) -> None:
-        """Drop the parked cache (the history stays readable)."""
+        """Drop the parked cache (the history stays readable); a heard turn that holds an encoder slot is cancelled."""
         self._idle("close")
+        if isinstance(self._heard, SlotHeardTurn):
+            self._heard.cancel()
         self._parked, self._cached, self.closed = None, 0, True
 
 
@@ -207,16 +248,20 @@ class BatchServer:
     """``Generator.serve``: see the module docstring.  Temperature and top-k belong to the server - they are the key of the
     captured frame graph."""
 
-    def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50):
+    def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0):
         if int(slots) != slots or not 1 <= slots <= 16:
             raise ValueError(f"slots must be an integer in 1..16, got {slots!r}")
+        if int(hear_slots) != hear_slots or not 0 <= hear_slots <= 16:
+            raise ValueError(f"hear_slots must be an integer in 0..16 (0: one encode stream per conversation), got {hear_slots!r}")
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
         codec = gen._audio_tokenizer
         if not callable(getattr(codec, "decode_stream_rows", None)):
             raise TypeError(f"{type(codec).__name__} has no decode_stream_rows(): serving needs a batched stateful decoder")
+        if hear_slots and not callable(getattr(codec, "encode_stream_rows", None)):
+            raise TypeError(f"{type(codec).__name__} has no encode_stream_rows(): hear_slots needs a batched stateful encoder")
         self._gen, self._model = gen, gen._model
-        self.slots, self.chunk_frames = int(slots), int(chunk_frames)
+        self.slots, self.chunk_frames, self.hear_slots = int(slots), int(chunk_frames), int(hear_slots)
         self.temperature, self.topk = float(temperature), int(topk)
         gen._run += 1                                    # takes over the model's caches, as generate_batch does
         self._run = gen._run
@@ -226,6 +271,10 @@ class BatchServer:
         with torch.inference_mode():
             self._state = DecodeState(self._model.engine, self.slots, bank=list(self._bank.values()))
             self._codec = codec.decode_stream_rows(slots=self.slots, max_chunk_frames=self.chunk_frames)
+        # heard turns: one rows encoder for all conversations (None: each conversation makes its own MimiEncodeStream).  Made
+        # outside inference mode: ``conv.hear`` opens its slot (an in-place zero fill of the state) from ordinary caller code
+        self._hear = codec.encode_stream_rows(slots=self.hear_slots) if self.hear_slots else None
+        self._hearing: List[Optional[SlotHeardTurn]] = [None] * self.hear_slots     # encoder slot -> the turn that holds it
         self._model._decode_state = self._state
         K = self._model.args.audio_num_codebooks
         dev = gen.device
@@ -282,6 +331,62 @@ class BatchServer:
     def active(self) -> List[Request]:
         """The requests that hold a slot, in slot order."""
         return [r for r in self._rows if r is not None]
+
+    # ------------------------------------------------------------------------------------------------------------- hearing
+    def _open_heard(self, conv, speaker: int) -> SlotHeardTurn:
+        if conv._heard is not None:
+            raise RuntimeError("hear: this conversation already has a heard turn open - end() or cancel() it first")
+        free = [s for s, t in enumerate(self._hearing) if t is None]
+        if not free:
+            raise RuntimeError(f"hear: all hear_slots = {self.hear_slots} encoder slots are taken - end() or cancel() a heard turn, "
+                               "or serve with more")
+        self._hear.open(free[0])
+        conv._heard = self._hearing[free[0]] = SlotHeardTurn(conv, speaker, self, free[0])
+        return conv._heard
+
+    def _free_heard(self, turn: SlotHeardTurn):
+        self._hear.close(turn.slot)
+        self._hearing[turn.slot] = None
+
+    @torch.inference_mode()
+    def hear_step(self) -> int:
+        """Encode what waits in every open heard turn: ONE ``drain`` over all of them (nothing is launched when nothing waits).
+        ``step()`` calls it first.  Returns the number of frames encoded."""
+        self._check()
+        turns = [t for t in self._hearing if t is not None and t.pending]
+        if not turns:
+            return 0
+        codes = self._hear.drain([t.slot for t in turns])
+        for t in turns:
+            t._take(codes[t.slot].unsqueeze(0))
+        return sum(codes[t.slot].shape[1] for t in turns)
+
+    @torch.inference_mode()
+    def end_heard(self, ended) -> None:
+        """``ended`` = [(turn, text), ...]: heard turns of this server that end together.  Each enters its conversation as
+        ``turn.end(text)`` would - under ``add``'s rules - but what is left to encode, the zero-padded last partial frames
+        included, goes through ONE batched drain.  All turns are checked (and their texts tokenised) before anything is
+        encoded or entered: when one is refused the call raises and none has changed."""
+        self._check()
+        ended = list(ended)
+        texts = []
+        for i, (turn, text) in enumerate(ended):
+            if not isinstance(turn, SlotHeardTurn) or turn._srv is not self:
+                raise ValueError("end_heard: not a heard turn of this server (turns of hear_slots = 0 servers and of Generator."
+                                 "conversation() end through turn.end())")
+            if any(turn is t for t, _ in ended[:i]):
+                raise ValueError("end_heard: a turn is named twice")
+            turn._check("end")
+            turn._conv._before_history("end")                       # (a ServedConversation's only checks: nothing to undo)
+            texts.append(self._gen._tokenize_text_segment(text, turn.speaker))
+        if not ended:
+            return
+        slots = [turn.slot for turn, _ in ended]
+        codes = self._hear.drain(slots, flush=slots)
+        for (turn, _), (tt, tm) in zip(ended, texts):
+            turn._take(codes[turn.slot].unsqueeze(0))
+            self._free_heard(turn)
+            turn._enter(tt, tm)
 
     # ---------------------------------------------------------------------------------------------------------------- step
     def _frame(self, rows):
@@ -345,6 +450,8 @@ class BatchServer:
         """One chunk: ``(request, audio_chunk, done)`` for every request that held a slot in it (a request's last chunk may be
         shorter than ``chunk_frames * 1920`` samples, or empty when its first frame of the chunk was EOS)."""
         self._check()
+        if self.hear_slots:
+            self.hear_step()
         n, K = self.chunk_frames, self._K
         running = [b for b in range(self.slots) if self._rows[b] is not None]
         first = self._frame(running) if running else None

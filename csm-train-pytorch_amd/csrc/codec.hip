@@ -401,7 +401,8 @@ __global__ __launch_bounds__(256) void transpose_f32_kernel(const float* __restr
         if (c0 + i < Cn && r0 + tx < R) out[(size_t)(c0 + i) * R + r0 + tx] = tile[tx][i];
 }
 
-// ---- rows forms of the streaming ops: R <= 16 utterances, each with its own state slot, decoded by one launch -------------
+// ---- rows forms of the streaming ops: R <= 16 utterances, each with its own state slot, decoded or encoded by one launch ---
+// (the decoder's: stride-1 conv, transposed conv, RoPE, ring attention, transpose; the encoder's adds the strided conv)
 // A streaming step is a chain of dependent FMAs per output with nothing to overlap, and a 4-frame chunk fills 8 lanes of a
 // wave in the wide early layers; the rows of a batch are the missing parallelism.  The launches below flatten (row, time)
 // onto the threads of one output channel - the weights stay wave-uniform - and every output goes through conv1d_accum /
@@ -446,6 +447,51 @@ __global__ __launch_bounds__(256) void conv1d_stream_rows_kernel(float* __restri
             float* hist_out = arena + ((size_t)rows.slot[r] * 2 + (rows.par[r] ^ 1)) * hsz;
             const int p = n + i;
             hist_out[(size_t)c * H + i] = p < H ? hist[(size_t)c * H + p] : x[((size_t)r * C_in + c) * n + p - H];
+        }
+}
+
+// conv1d_stream_strided_kernel for R rows: x [R][C_in][n_in], y / res [R][C_out][n_in / stride], hist arena [slots][2][C_in][H]
+// with H = (k-1)*dil + 1 - stride.  Bit r of edge_mask = row r is the first chunk of an edge-replicated conv: its history is not
+// read, every history column is column 0 of its x.  The flag differs between the lanes of a wave, so it only selects an address;
+// the load stays unconditional.  H == 0: NULL arena, never dereferenced - as above.
+__global__ __launch_bounds__(256) void conv1d_stream_strided_rows_kernel(float* __restrict__ arena, const float* __restrict__ x,
+                                                                         const float* __restrict__ w, const float* __restrict__ bias,
+                                                                         const float* __restrict__ res, float* __restrict__ y,
+                                                                         StreamRows rows, unsigned edge_mask, int R, int C_in, int C_out,
+                                                                         int n_in, int k, int stride, int dil, int groups, int elu_in) {
+    const int co = blockIdx.y;
+    const int H = (k - 1) * dil + 1 - stride;
+    const int n_out = n_in / stride;
+    const int cin_g = C_in / groups, cout_g = C_out / groups;
+    const int grp = co / cout_g;
+    const float* wrow = w + (size_t)co * cin_g * k;
+    const size_t hsz = (size_t)C_in * H;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < R * n_out; g += gridDim.x * blockDim.x) {
+        const int r = g / n_out, t = g - r * n_out;
+        const int base = t * stride;
+        const bool edge = (edge_mask >> r) & 1u;
+        const float* hist = arena + ((size_t)rows.slot[r] * 2 + rows.par[r]) * hsz;
+        const float* xrow = x + (size_t)r * C_in * n_in;
+        float acc = conv1d_accum(bias ? bias[co] : 0.f, wrow, cin_g, k, elu_in, [&](int ci, int j) {
+            const int c = grp * cin_g + ci, p = base + j * dil;         // column of [hist | x]
+            const float* xr = xrow + (size_t)c * n_in;
+            const float* old = edge ? xr : hist + (size_t)c * H + p;
+            const float* src = p < H ? old : xr + (p - H);
+            return *src;
+        });
+        const size_t o = ((size_t)r * C_out + co) * n_out + t;
+        if (res) acc += res[o];
+        y[o] = acc;
+    }
+    for (int c = blockIdx.y; c < C_in; c += gridDim.y)
+        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < R * H; g += gridDim.x * blockDim.x) {
+            const int r = g / H, i = g - r * H;
+            const float* hist = arena + ((size_t)rows.slot[r] * 2 + rows.par[r]) * hsz;
+            float* hist_out = arena + ((size_t)rows.slot[r] * 2 + (rows.par[r] ^ 1)) * hsz;
+            const int p = n_in + i;
+            const float* xr = x + ((size_t)r * C_in + c) * n_in;
+            const float* old = ((edge_mask >> r) & 1u) ? xr : hist + (size_t)c * H + p;
+            hist_out[(size_t)c * H + i] = *(p < H ? old : xr + (p - H));
         }
 }
 
@@ -575,6 +621,36 @@ extern "C" int csm_conv1d_stream_rows_f32(float* hist_arena, const float* x, con
     hipLaunchKernelGGL(conv1d_stream_rows_kernel, dim3(bx, C_out), dim3(bs), 0, stream, hist_arena, x, w, bias, residual, y, rows, R, C_in,
                        C_out, n, k, dilation, groups, elu_in);
     CSM_CHECK_LAUNCH("csm_conv1d_stream_rows_f32");
+    return 0;
+}
+
+extern "C" int csm_conv1d_stream_strided_rows_f32(float* hist_arena, const float* x, const float* w, const float* bias,
+                                                  const float* residual, float* y, int R, const int* slots, const int* parity,
+                                                  unsigned edge_first_mask, int n_slots, int C_in, int C_out, int n_in, int k, int stride,
+                                                  int dilation, int groups, int elu_in, hipStream_t stream) {
+    CSM_REQUIRE(x && w && y && C_in > 0 && C_out > 0 && n_in > 0 && k > 0 && stride > 0 && dilation > 0 && groups > 0 &&
+                    C_in % groups == 0 && C_out % groups == 0 && C_out <= 65535, "csm_conv1d_stream_strided_rows_f32: bad arguments");
+    CSM_REQUIRE(n_in % stride == 0, "csm_conv1d_stream_strided_rows_f32: n_in %d is not a multiple of stride %d", n_in, stride);
+    const long long H = (long long)(k - 1) * dilation + 1 - stride;
+    CSM_REQUIRE(H >= 0, "csm_conv1d_stream_strided_rows_f32: stride %d exceeds the kernel's extent (k %d, dilation %d)", stride, k,
+                dilation);
+    CSM_REQUIRE(H == 0 || (hist_arena && parity),
+                "csm_conv1d_stream_strided_rows_f32: a history of %lld columns needs the history arena and the rows' parities", H);
+    StreamRows rows;
+    CSM_REQUIRE(stream_rows_arg(rows, R, slots, parity, nullptr, n_slots),
+                "csm_conv1d_stream_strided_rows_f32: 1..16 rows with distinct slots in [0, %d) and parities 0 / 1", n_slots);
+    CSM_REQUIRE((edge_first_mask >> R) == 0,"csm_conv1d_stream_strided_rows_f32: edge-first mask 0x%x names a row >= R = %d",
+                edge_first_mask, R);
+    const int n_out = n_in / stride;
+    CSM_REQUIRE(H + n_in < (1LL << 31) && 16 * H < (1LL << 31) && 16LL * n_out < (1LL << 31),
+                "csm_conv1d_stream_strided_rows_f32: column index overflow");
+    const long long work = (long long)R * (n_out > H ? n_out : H);   // the same grid writes the outputs and the next histories
+    const int bs = rows_block(work);
+    long long bx = (work + bs - 1) / bs;
+    if (bx > 4096) bx = 4096;                                        // 16 rows x 32 frames x 1920 columns = 3840 blocks of 256
+    hipLaunchKernelGGL(conv1d_stream_strided_rows_kernel, dim3((unsigned)bx, C_out), dim3(bs), 0, stream, hist_arena, x, w, bias, residual,
+                       y, rows, edge_first_mask, R, C_in, C_out, n_in, k, stride, dilation, groups, elu_in);
+    CSM_CHECK_LAUNCH("csm_conv1d_stream_strided_rows_f32");
     return 0;
 }
 

@@ -404,6 +404,16 @@ int csm_attn_window_stream_f32(const float* qkv, float* kcache, float* vcache, f
 int csm_conv1d_stream_rows_f32(float* hist_arena, const float* x, const float* w, const float* bias, const float* residual, float* y,
                                int R, const int* slots, const int* parity, int n_slots, int C_in, int C_out, int n, int k,
                                int dilation, int groups, int elu_in, csm_stream_t stream);
+/* csm_conv1d_stream_strided_f32 for R rows with the same n_in (the encoder's downsampling convs; additive since ABI 3):
+ * x = [R][C_in][n_in], y / residual = [R][C_out][n_in / stride], hist_arena = [n_slots][2][C_in][H], H = (k-1)*dilation + 1 - stride
+ * (may exceed n_in; NULL when H == 0).  Bit r of edge_first_mask: row r is the first chunk of an edge-replicated conv - its
+ * history is not read, every history column is column 0 of that row's x.  Refused, with nothing launched: R outside 1..16, a slot
+ * out of range or named twice, a parity other than 0 / 1, a mask bit at or above R, n_in not a multiple of stride, H < 0, H > 0
+ * with a NULL arena. */
+int csm_conv1d_stream_strided_rows_f32(float* hist_arena, const float* x, const float* w, const float* bias, const float* residual,
+                                       float* y, int R, const int* slots, const int* parity, unsigned edge_first_mask, int n_slots,
+                                       int C_in, int C_out, int n_in, int k, int stride, int dilation, int groups, int elu_in,
+                                       csm_stream_t stream);
 /* pos0[r]: absolute input position of row r's first new column */
 int csm_conv_transpose1d_stream_rows_f32(float* hist_arena, const float* x, const float* w, const float* bias, float* y, int R,
                                          const int* slots, const int* parity, const int* pos0, int n_slots, int C_in, int C_out,

@@ -14,7 +14,9 @@ alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in ea
 16 rows, the join stall (serve_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
 time to the first chunk of turns 1 / 3 / 5 against stateless submits, one append_rows against one-row calls, park / resume, aggregate
 frames/s (serve_conv_main).  GEN_HEAR=1: a 5 s heard turn's last sample to the first chunk of the reply, with
-``add(Segment)`` against ``hear`` fed during the turn, served (16 slots) and at B = 1 (hear_main).  GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
+``add(Segment)`` against ``hear`` fed during the turn, served (16 slots) and at B = 1 (hear_main), then the batched hearing of
+``serve(hear_slots=16)`` against ``hear_slots=0``: the hearing cost per 4-frame chunk of 16 listeners and the last sample to
+the first chunk when all 16 end together, ``end_heard`` against 16 ``end`` calls (hear_rows_main; GEN_HEAR=rows: that leg alone).  GEN_CONVERSATION=1: a scripted dialogue of 8 turns (odd turns spoken with 63 frames, even turns the other party's 5 s of audio)
 through a Conversation (KV cache kept between turns) and statelessly (generate_stream with the accumulated Segment list - every
 turn encodes and prefills the whole history again), alternated in one process after a warm-up dialogue of each: per spoken turn the
 host time from the call to the first chunk (chunk_frames=2) and the turn's total; plus csm_attn_append alone next to the
@@ -875,9 +877,99 @@ def hear_main():
           f"{cut // piece} of them, one per 320 ms of audio")
 
 
+def hear_rows_main():
+    """GEN_HEAR=1 (after hear_main) or GEN_HEAR=rows (alone): 16 conversations on the 16-slot server (CSM-1B random init,
+    chunk_frames 4) each hear a 5 s turn in 4-frame pieces, with (a) ``hear_slots=0`` - one MimiEncodeStream per conversation, one
+    encoder step per ``feed`` - and (b) ``hear_slots=16`` - ``feed`` buffers, one ``hear_step`` per chunk encodes all 16.
+    Reported: the hearing cost of one chunk (16 feeds, plus ``hear_step`` for (b); nobody speaks meanwhile), and the time from
+    the last sample (a 2.5-frame piece) to the first chunk of the 16 replies on the host when all 16 turns end together: (a) 16
+    ``end`` calls, (b1) 16 ``end`` calls on the rows encoder (16 one-row drains), (b2) one ``end_heard``.  GEN_ROUNDS rounds
+    (default 3) alternated after one warm-up round of each form; ms as median [min..max]."""
+    dev = "cuda:0"
+    NC, n = 16, 4
+    frames = int(os.environ.get("GEN_FRAMES", 24))
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    ms = 80 * frames
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=make_codec(dev))
+    g = torch.Generator(device=dev).manual_seed(1)
+    heard = [torch.randn(5 * 24000, device=dev, generator=g) * 0.1 for _ in range(NC)]
+    piece = n * 1920
+    cut = heard[0].numel() // piece * piece
+    line, heard_text, reply = "turn 1: the quick brown fox jumps over the lazy dog", "turn 2: and what did the dog do", "turn 3: it slept"
+    med = lambda xs: sorted(xs)[len(xs) // 2]                                                           # noqa: E731
+    fmt = lambda xs: f"{med(xs):7.1f} [{min(xs):6.1f}..{max(xs):6.1f}]"                                 # noqa: E731
+
+    def dialogue(form):
+        hs = 0 if form == "a" else NC
+        srv = gen.serve(slots=NC, chunk_frames=n, hear_slots=hs)
+        convs = [srv.conversation(seed=i) for i in range(NC)]
+        for c in convs:
+            c.say(line, 0, max_audio_length_ms=ms)
+        for _ in srv.run():
+            pass
+        turns = [c.hear(1) for c in convs]
+        chunks = []
+        for lo in range(0, cut, piece):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i, t in enumerate(turns):
+                t.feed(heard[i][lo:lo + piece])
+            srv.hear_step()
+            torch.cuda.synchronize()
+            chunks.append((time.perf_counter() - t0) * 1e3)
+        assert all(t.frames == cut // 1920 for t in turns)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()                                      # the turns' last sample
+        for i, t in enumerate(turns):
+            t.feed(heard[i][cut:])
+        if form == "b2":
+            srv.end_heard([(t, heard_text) for t in turns])
+        else:
+            for t in turns:
+                t.end(heard_text)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        snap = [c.tokens for c in convs]
+        for c in convs:
+            c.say(reply, 0, max_audio_length_ms=ms)
+        out = srv.step()
+        torch.cat([a for _, a, _ in out]).cpu()
+        t2 = time.perf_counter()
+        assert srv.last_join_rows == NC
+        for _ in srv.run():
+            pass
+        return chunks, (t1 - t0) * 1e3, (t2 - t0) * 1e3, snap
+
+    forms = (("a", "(a) hear_slots=0, 16 end calls"), ("b1", "(b1) hear_slots=16, 16 end calls"), ("b2", "(b2) hear_slots=16, one end_heard"))
+    res = {f: {"chunk": [], "enter": [], "first": []} for f, _ in forms}
+    toks = {}
+    print(f"GEN_HEAR rows: {NC} conversations hear 5 s ({cut // piece} pieces of {n} frames + 2.5 frames at the end) on {NC} slots, "
+          f"chunk_frames {n}, {rounds} alternated rounds after one warm-up of each form; ms as median [min..max]")
+    for r in range(rounds + 1):
+        for f, _ in forms:
+            torch.manual_seed(7)
+            chunks, enter, first, toks[f] = dialogue(f)
+            if r:
+                res[f]["chunk"] += chunks[1:]                         # (the first piece of a turn warms the encoder's buffers)
+                res[f]["enter"].append(enter)
+                res[f]["first"].append(first)
+    same = all(torch.equal(x, y) for f in ("b1", "b2") for x, y in zip(toks["a"], toks[f]))
+    for f, what in forms:
+        print(f"{what}: hearing cost per chunk ({NC} listeners) {fmt(res[f]['chunk'])} ms; last sample -> first chunk on the host "
+              f"{fmt(res[f]['first'])} ms, of which entering the 16 turns {fmt(res[f]['enter'])} ms", flush=True)
+    a, b = med(res["a"]["chunk"]), med(res["b2"]["chunk"])
+    print(f"per chunk: {a:.1f} -> {b:.1f} ms ({a / b:.2f}x); last sample -> first chunk: {med(res['a']['first']):.1f} -> "
+          f"{med(res['b2']['first']):.1f} ms with end_heard ({med(res['b1']['first']):.1f} ms with 16 end calls on the rows encoder); "
+          f"histories {'equal' if same else 'DIFFER'}")
+
+
 def main():
+    if os.environ.get("GEN_HEAR") == "rows":
+        return hear_rows_main()
     if os.environ.get("GEN_HEAR") == "1":
-        return hear_main()
+        hear_main()
+        return hear_rows_main()
     if os.environ.get("GEN_SERVE_CONV") == "1":
         return serve_conv_main()
     if os.environ.get("GEN_SERVE") == "1":
