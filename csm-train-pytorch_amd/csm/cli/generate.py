@@ -46,9 +46,11 @@ def parse_args(argv=None):
                    help="speaker ID of the corresponding --next-text (repeatable; default: the speaker of --text)")
     p.add_argument("--serve-file", type=str, default=None,
                    help="JSON-lines file of utterances {\"text\", \"speaker\", \"adapter\"?: LoRA adapter file, \"seed\"?: int, "
-                        "\"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
+                        "\"temperature\"?: float, \"topk\"?: int, \"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
                         "--context-*; lines with the same conversation id are successive turns of one served conversation, in file "
-                        "order (KV cache kept between them; adapter and seed of its first line); one WAV per utterance, "
+                        "order (KV cache kept between them; adapter and seed of its first line); a line's temperature / topk hold for "
+                        "that utterance or turn (default: --temperature / --topk; a file that names one is served with "
+                        "row_sampling=True); one WAV per utterance, "
                         "<output stem>_<i>.wav with i = 0, 1, ... counting the file's non-empty lines")
     p.add_argument("--slots", type=int, default=16, help="--serve-file: utterances decoded at once (1..16, default 16)")
     p.add_argument("--hear-slots", type=int, default=0,
@@ -134,7 +136,7 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
 
 def read_serve_file(path):
     """--serve-file: one JSON object per non-empty line -> [{"text", "speaker", "adapter", "seed"}], plus "conversation" (a
-    string) on the lines that carry that key."""
+    string), "temperature" (a float) and "topk" (an int) on the lines that carry those keys."""
     import json
     lines = []
     with open(path) as f:
@@ -144,23 +146,42 @@ def read_serve_file(path):
             d = json.loads(raw)
             if not isinstance(d, dict) or not isinstance(d.get("text"), str):
                 raise ValueError(f"{path}:{i}: every line is a JSON object with a \"text\" string")
-            unknown = set(d) - {"text", "speaker", "adapter", "seed", "conversation"}
+            unknown = set(d) - {"text", "speaker", "adapter", "seed", "conversation", "temperature", "topk"}
             if unknown:
                 raise ValueError(f"{path}:{i}: unknown keys {sorted(unknown)}")
             lines.append({"text": d["text"], "speaker": int(d.get("speaker", 0)), "adapter": d.get("adapter"),
                           "seed": None if d.get("seed") is None else int(d["seed"])})
             if d.get("conversation") is not None:
                 lines[-1]["conversation"] = str(d["conversation"])
+            if d.get("temperature") is not None:
+                if isinstance(d["temperature"], bool) or not isinstance(d["temperature"], (int, float)):
+                    raise ValueError(f"{path}:{i}: \"temperature\" is a number, got {d['temperature']!r}")
+                lines[-1]["temperature"] = float(d["temperature"])
+            if d.get("topk") is not None:
+                if isinstance(d["topk"], bool) or not isinstance(d["topk"], int):
+                    raise ValueError(f"{path}:{i}: \"topk\" is an integer, got {d['topk']!r}")
+                lines[-1]["topk"] = d["topk"]
     if not lines:
         raise ValueError(f"{path}: no utterances")
     return lines
+
+
+def line_sampling(line):
+    """The sampling keywords of one --serve-file line for ``submit`` / ``say``: only what the line carries."""
+    return {k: line[k] for k in ("temperature", "topk") if k in line}
+
+
+def serve_sampling(lines):
+    """``Generator.serve`` keywords for these lines: ``row_sampling=True`` as soon as one of them carries a parameter."""
+    return {"row_sampling": True} if any(line_sampling(ln) for ln in lines) else {}
 
 
 def serve_to_wavs(generator, args, context, adapter=None):
     """--serve-file: every line is a request of one ``Generator.serve`` batch; adapter files are loaded once each, under their
     path as name (--lora-adapter is the default for lines without one).  Lines with a "conversation" id are the turns of one
     served conversation (``BatchServer.conversation``): its first line is queued with the rest, each later one when the turn
-    before it is done.  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav."""
+    before it is done.  A line's "temperature" / "topk" are that utterance's or that turn's; if any line has one, the server is
+    made with ``row_sampling=True`` (--temperature / --topk are then the other lines' values).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav."""
     lines = read_serve_file(args.serve_file)
     for path in sorted({ln["adapter"] for ln in lines if ln["adapter"]}):
         generator.load_adapter(path, path)
@@ -168,19 +189,20 @@ def serve_to_wavs(generator, args, context, adapter=None):
     os.makedirs(os.path.dirname(stem), exist_ok=True)
     t0 = time.perf_counter()
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, temperature=args.temperature,
-                             topk=args.topk, hear_slots=args.hear_slots)
+                             topk=args.topk, hear_slots=args.hear_slots, **serve_sampling(lines))
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
     def say(cid):
         conv, todo = convs[cid]
         i = todo.pop(0)
-        line_of[conv.say(lines[i]["text"], lines[i]["speaker"], max_audio_length_ms=args.max_audio_length_ms)] = (i, cid)
+        line_of[conv.say(lines[i]["text"], lines[i]["speaker"], max_audio_length_ms=args.max_audio_length_ms,
+                         **line_sampling(lines[i]))] = (i, cid)
 
     for i, ln in enumerate(lines):
         cid = ln.get("conversation")
         if cid is None:
             line_of[server.submit(ln["text"], ln["speaker"], context, adapter=ln["adapter"] or adapter, seed=ln["seed"],
-                                  max_audio_length_ms=args.max_audio_length_ms)] = (i, None)
+                                  max_audio_length_ms=args.max_audio_length_ms, **line_sampling(ln))] = (i, None)
         elif cid in convs:
             convs[cid][1].append(i)
         else:

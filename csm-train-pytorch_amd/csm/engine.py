@@ -12,6 +12,8 @@ With 288 GB of HBM nothing is recomputed.
 """
 from __future__ import annotations
 
+import math
+import numbers
 from contextlib import contextmanager
 from typing import Dict, List, Optional
 
@@ -876,6 +878,8 @@ class Engine:
         ``model.use_kv_cache = False`` selects the cache-free prefix-recompute path (same arithmetic, kept as a check).
         ``adapters`` (read on the first call of a generation, ignored later): a LoRAState or None per batch row - per-utterance
         adapters from a bank (csm/lora_bank.py).
+        ``temperature`` / ``topk``: two numbers - or, with caches, a sequence of B values for either one (a parameter pair per
+        row, ``DecodeState.sampling_args``), or None for both (the pairs ``DecodeState.set_row_sampling`` wrote).
         """
         m, a = self.m, self.m.args
         self._need()
@@ -895,6 +899,7 @@ class Engine:
                                "same batch size (call it with input_pos starting at 0 first)")
         if first:
             st = m._decode_state = DecodeState(self, Bn, adapters)
+        temperature, topk = st.sampling_args(temperature, topk)
         if first:
             last_h = st.prefill(tokens, tokens_mask)
             return self._frame_tail(st, last_h, temperature, topk, noise)
@@ -909,10 +914,12 @@ class Engine:
     def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None, adapters=None):
         """Batched generation (up to 16 utterances): prefill B prompts of different lengths and sample the
         first frame of each; later frames go through ``generate_frame`` with ``[B, 1, K+1]`` tokens and a non-zero
-        ``input_pos``, exactly as for one utterance."""
+        ``input_pos``, exactly as for one utterance.  ``temperature`` / ``topk``: two numbers, or a sequence of B values for
+        either one - row b then samples with its own pair (``DecodeState.sampling_args``); give the same to ``generate_frame``."""
         m = self.m
         self._need()
         st = m._decode_state = DecodeState(self, len(tokens_list), adapters)
+        temperature, topk = st.sampling_args(temperature, topk)
         last_h = st.prefill_ragged(tokens_list, masks_list)
         return self._frame_tail(st, last_h, temperature, topk, noise)
 
@@ -938,8 +945,18 @@ class Engine:
 
         qall = st.noise_buf          # all Exp(1) draws of the frame (the reference draws them one codebook at a time, model.py:79-82)
 
-        def draw(lg, i):
-            return sample_topk(lg[:, :V], topk, temperature, qall[i])
+        if temperature is None and topk is None:
+            # each row's own pair, read by the sampler from the state's row buffers (written outside the graph: set_row_sampling)
+            from .models.model import sample_topk_rows
+            row_t, row_k = st.row_sampling_buffers()
+
+            def draw(lg, i):
+                return sample_topk_rows(lg[:, :V], row_k, row_t, qall[i])
+        elif temperature is None or topk is None:
+            raise ValueError("temperature and topk are both numbers, or both None (each row's own pair: set_row_sampling)")
+        else:
+            def draw(lg, i):
+                return sample_topk(lg[:, :V], topk, temperature, qall[i])
 
         ops.gemv(last_h, m.block("codebook0_head.padded"), st.logits)
         samples = [draw(st.logits, 0)]
@@ -958,6 +975,9 @@ class Engine:
     @torch.no_grad()
     def _generate_frame_recompute(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None):
         """Reference model.py:140-195.  The KV state is the token history (prefix recompute)."""
+        if not (_is_number(temperature) and _is_number(topk)):
+            raise ValueError("the recompute path (use_kv_cache = False) samples every row with one temperature and one topk: "
+                             "per-row sampling parameters need the KV-cache path")
         ads = getattr(self.m, "_gen_adapters", None)
         if ads is not None:
             # (the cache-free check path runs ONE adapter set for the whole batch: the training forward has no per-row adapters)
@@ -1255,6 +1275,39 @@ def _prime_graph_rng(device):
     _graph_rng_primed = g
 
 
+def _is_number(x):
+    """One value for all rows: a real number, or a 0-d tensor / array of one (what ``float()`` / ``int()`` take)."""
+    return (isinstance(x, numbers.Real) and not isinstance(x, bool)) or getattr(x, "ndim", None) == 0
+
+
+def _as_list(x):
+    """A sequence of per-row values (list / tuple / 1-D tensor or array) as a list; None for anything else."""
+    if isinstance(x, (str, bytes)) or x is None:
+        return None
+    if hasattr(x, "tolist"):
+        x = x.tolist()
+    return list(x) if isinstance(x, (list, tuple)) else None
+
+
+def check_sampling(temperature, topk, vocab):
+    """The rule for one row's sampling parameters: ``temperature`` a finite number > 0, ``topk`` an integer in 1..vocab (the
+    audio vocabulary).  Returns (float, int); raises ValueError with the offending value."""
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        t = float("nan")
+    if isinstance(temperature, bool) or not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+    try:
+        k = int(topk)
+        whole = not isinstance(topk, bool) and k == topk
+    except (TypeError, ValueError, OverflowError):
+        k, whole = 0, False
+    if not whole or not 1 <= k <= int(vocab):
+        raise ValueError(f"topk must be an integer in 1..{int(vocab)} (the audio vocabulary), got {topk!r}")
+    return t, k
+
+
 class DecodeState:
     """Everything ``generate_frame`` keeps between calls: the two stacks' caches and small persistent buffers."""
 
@@ -1304,6 +1357,8 @@ class DecodeState:
         self.active = None
         self.row_gen, self.draw_rows, self.noise_stage = {}, None, None
         self.graph, self.graph_key, self.warm = None, None, 0
+        # per-row sampling parameters (set_row_sampling): two device vectors the rows sampler reads + their host mirror
+        self.row_temperature, self.row_topk, self.row_sampling = None, None, None
         # the frame's Exp(1) draws [K, B, V]: a PERSISTENT buffer, refilled before every frame outside the captured graph -
         # so a replayed frame can be given the same noise as an eager one (parity tests) or fresh draws (generation)
         self.noise_buf = torch.empty(m.args.audio_num_codebooks, B, m.args.audio_vocab_size, dtype=F32, device=dev)
@@ -1530,6 +1585,49 @@ class DecodeState:
             if stack.lora_rows is not None:
                 stack.lora_rows[0][b:b + 1].fill_(idx)
 
+    def set_row_sampling(self, b, temperature, topk):
+        """Row ``b`` samples with ``temperature`` / ``topk`` from its next frame on, in every frame body called with
+        ``temperature=None, topk=None``: one float and one int written to ``row_temperature[b]`` / ``row_topk[b]`` on the device,
+        which the rows sampler reads (``csm_sample_topk_rows``) - outside the captured graph, so a change never recaptures.  The
+        two buffers are made by the first call, with every row at that call's values (a row that is never set still samples
+        with a valid pair: the kernel runs on all B rows).  ``row_sampling`` is the host mirror, [(temperature, topk)] * B."""
+        temperature, topk = check_sampling(temperature, topk, self.e.m.args.audio_vocab_size)
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        if self.row_sampling is None:
+            dev = self.noise_buf.device
+            self.row_temperature = torch.full((self.B,), temperature, dtype=F32, device=dev)
+            self.row_topk = torch.full((self.B,), topk, dtype=torch.int32, device=dev)
+            self.row_sampling = [(temperature, topk)] * self.B
+        elif self.row_sampling[b] != (temperature, topk):
+            self.row_temperature[b:b + 1].fill_(temperature)
+            self.row_topk[b:b + 1].fill_(topk)
+            self.row_sampling[b] = (temperature, topk)
+
+    def row_sampling_buffers(self):
+        """(row_temperature, row_topk) for a frame body called with None, None."""
+        if self.row_sampling is None:
+            raise RuntimeError("temperature = topk = None samples each row with its own pair: call set_row_sampling first")
+        return self.row_temperature, self.row_topk
+
+    def sampling_args(self, temperature, topk):
+        """What ``Engine.generate_frame`` / ``generate_first_frames`` hand to the frame bodies: two numbers (or None, None) pass
+        through; a sequence of B values for either one is written to the rows (``set_row_sampling``; the other, if a number,
+        holds for every row) and (None, None) comes back."""
+        if (temperature is None and topk is None) or (_is_number(temperature) and _is_number(topk)):
+            return temperature, topk
+        ts = [temperature] * self.B if _is_number(temperature) else _as_list(temperature)
+        ks = [topk] * self.B if _is_number(topk) else _as_list(topk)
+        if ts is None or ks is None or len(ts) != self.B or len(ks) != self.B:
+            raise ValueError(f"temperature and topk are numbers or sequences of one value per row ({self.B} rows): got "
+                             f"temperature={temperature!r}, topk={topk!r}")
+        for t, k in zip(ts, ks):                       # (all of them before any is written)
+            check_sampling(t, k, self.e.m.args.audio_vocab_size)
+        for b, (t, k) in enumerate(zip(ts, ks)):
+            self.set_row_sampling(b, t, k)
+        return None, None
+
     def set_row_seed(self, b, seed, generator=None):
         """Row ``b``'s sampler noise comes from its own ``torch.Generator`` seeded with ``seed`` (``fill_noise``); None returns
         the row to the whole-buffer draw from torch's global generator.  ``generator``: an existing generator to draw from
@@ -1565,7 +1663,8 @@ class DecodeState:
     def serve_first(self, last_h, rows, temperature, topk):
         """The first frame of the rows just prefilled (``last_h`` [B, d]: their ``prefill_row`` results in their rows, anything in
         the others) - ``Engine._frame_tail`` over the whole batch, with per-row noise drawn for ``rows`` only.  [B, K]; the other
-        rows' output is meaningless."""
+        rows' output is meaningless.  ``temperature`` / ``topk``, here and in ``serve_frame``: two numbers, or None, None for each
+        row's own pair (``set_row_sampling``)."""
         self.draw_rows = set(rows)
         try:
             return self.e._frame_tail(self, last_h, temperature, topk, None)
@@ -1598,10 +1697,11 @@ class DecodeState:
         """Replay one decode frame (~1.8 k kernel launches) as a single HIP graph.  The first decode frame runs eagerly
         (warm-up: lazy function attributes, allocator), the second is captured, later ones are replays; positions, input
         tokens and the frame's noise live in persistent device buffers, so the same graph serves every frame.  Re-captured
-        when temperature / top-k change."""
+        when temperature / top-k change; with ``None, None`` the key is (None, None) and the sampler reads each row's pair from
+        the row buffers (``set_row_sampling``), so a change of any row's parameters replays the same graph."""
         m = self.e.m
         self._advance()
-        key = (float(temperature), int(topk))
+        key = (None, None) if temperature is None and topk is None else (float(temperature), int(topk))
         if self.graph is None or self.graph_key != key:
             if self.warm < 1 or self.graph_key not in (None, key):
                 self.warm, self.graph, self.graph_key = 1, None, None

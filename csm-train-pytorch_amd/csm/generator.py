@@ -235,10 +235,14 @@ class Generator:
         each row's codes are those of a one-utterance run; 5..16 rows go through the MFMA decode products, whose rows are
         the same bits for any batch size in 5..16 (not those of 1..4).  Live (un-merged) LoRA adapters: at most 4.
         ``adapters``: one bank adapter name or None per utterance (``add_adapter`` / ``load_adapter``), 1..16 rows; with it, a
-        live ``model.lora`` must be absent or merged."""
+        live ``model.lora`` must be absent or merged.
+        ``temperature`` / ``topk``: a number for all utterances, or a sequence of one value per utterance for either one -
+        each row then samples with its own pair (the rows sampler, ``DecodeState.set_row_sampling``) and has the codes it
+        has in a batch of the same size run with its pair for everybody; two numbers are the one-pair path."""
         B = len(texts)
         if not (1 <= B <= 16 and len(speakers) == B and len(contexts) == B):
             raise ValueError("generate_batch takes 1..16 utterances with one speaker id and one context list each")
+        temperature, topk = self._batch_sampling(temperature, topk, B)
         if adapters is not None and len(adapters) != B:
             raise ValueError(f"generate_batch: {len(adapters)} adapter names for {B} utterances (one name or None each)")
         ads = self._resolve_adapters(list(adapters)) if adapters is not None else None
@@ -286,12 +290,34 @@ class Generator:
                 out.append(self._audio_tokenizer.decode(codes_all[b:b + 1, :, :n]).squeeze(0).squeeze(0))
         return out
 
-    def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0):
+    def _batch_sampling(self, temperature, topk, B):
+        """``generate_batch``'s temperature / topk: numbers pass through; a sequence must have one valid value per utterance
+        (checked here, before the caches are taken over) and comes back as a list."""
+        from .engine import _as_list, _is_number, check_sampling
+        if _is_number(temperature) and _is_number(topk):
+            return temperature, topk
+        out = []
+        for name, v in (("temperature", temperature), ("topk", topk)):
+            if not _is_number(v):
+                seq = _as_list(v)
+                if seq is None or len(seq) != B:
+                    raise ValueError(f"generate_batch: {name} is a number or a sequence of one value per utterance ({B}), got {v!r}")
+                v = seq
+            out.append(v)
+        vocab = self._model.args.audio_vocab_size
+        for b in range(B):
+            check_sampling(out[0] if _is_number(out[0]) else out[0][b], out[1] if _is_number(out[1]) else out[1][b], vocab)
+        return out[0], out[1]
+
+    def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
+              row_sampling: bool = False):
         """A running batch (csm/serving.py): ``server.submit(text, speaker, context, adapter=None, seed=None,
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
         chunk by chunk and leave at their own EOS - and ``server.run()`` iterates until all are done.  Temperature and top-k
-        belong to the server.  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
+        belong to the server - unless ``row_sampling=True``: then they are the requests' defaults, ``submit`` / ``conversation``
+        / ``say`` take ``temperature=`` and ``topk=`` of their own (say > conversation > server), each slot samples with its
+        request's pair through the rows sampler, and one captured frame serves every mix (a change never recaptures).  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
         speaker)`` queues its next turn as a request, ``conv.add(Segment)`` (or ``conv.hear(speaker)`` -> ``feed`` / ``end``, encoded
         while it is spoken) is the other party's turn; its KV history is parked
         between turns and resumed into any free slot, so more conversations than slots can be open.  It takes over the model's caches like any ``generate*`` call (open streams and older servers are
@@ -300,7 +326,7 @@ class Generator:
         ``feed``; N >= 1 gives the server one rows encoder of N slots - ``feed`` only buffers, ``server.hear_step()`` (called by
         ``step()``) encodes all open heard turns in one batched step, ``server.end_heard([(turn, text), ...])`` ends several."""
         from .serving import BatchServer
-        return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots)
+        return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling)
 
     def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error"):
         """A multi-turn dialogue that keeps its KV cache between turns (csm/conversation.py): ``conv.generate(text, speaker)`` /

@@ -687,6 +687,18 @@ def sample_topk(logits_f32, q_f32, out_i32, topk, temperature, V=None):
     return out_i32
 
 
+def sample_topk_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, V=None):
+    """``sample_topk`` with row r's parameters read from ``topk_i32[r]`` / ``temperature_f32[r]`` on the device."""
+    rows = logits_f32.shape[0]
+    V = V or logits_f32.shape[1]
+    assert q_f32.is_contiguous() and q_f32.shape == (rows, V)
+    assert topk_i32.dtype == torch.int32 and topk_i32.is_contiguous() and topk_i32.numel() == rows
+    assert temperature_f32.dtype == torch.float32 and temperature_f32.is_contiguous() and temperature_f32.numel() == rows
+    check(lib.csm_sample_topk_rows(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0),
+                                   topk_i32.data_ptr(), temperature_f32.data_ptr(), _stream()), "csm_sample_topk_rows")
+    return out_i32
+
+
 def rvq_encode(x_f32, codebooks_f32, codes_i64, n_semantic=1):
     T, D = x_f32.shape
     K, Cn, D2 = codebooks_f32.shape

@@ -123,6 +123,23 @@ def sample_topk(logits: torch.Tensor, topk: int, temperature: float, q: Optional
     return out.reshape(*lead, 1)
 
 
+def sample_topk_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, q: Optional[torch.Tensor] = None):
+    """``sample_topk`` for [B, V] logits with one parameter pair per row: ``topk`` int32 [B] and ``temperature`` float32 [B] on the
+    logits' device, read by the kernel (``csm_sample_topk_rows``) - row b is ``sample_topk(logits[b], topk[b], temperature[b],
+    q[b])`` bit for bit.  Returns int32 [B, 1]."""
+    lg2 = logits.float()
+    if lg2.dim() != 2:
+        raise ValueError(f"sample_topk_rows takes [B, V] logits, got {tuple(logits.shape)}")
+    if lg2.stride(1) != 1:
+        lg2 = lg2.contiguous()
+    if q is None:
+        q = torch.empty(lg2.shape, dtype=torch.float32, device=lg2.device).exponential_(1)
+    q = q.reshape(lg2.shape).float().contiguous()
+    out = torch.empty(lg2.shape[0], dtype=torch.int32, device=lg2.device)
+    ops.sample_topk_rows(lg2, q, out, topk, temperature, V=lg2.shape[1])
+    return out.reshape(-1, 1)
+
+
 @dataclass
 class ModelArgs:
     """Arguments for the CSM model (reference model.py:99-107)."""
@@ -449,6 +466,7 @@ class Model(nn.Module):
                        topk: int, noise: Optional[List[torch.Tensor]] = None, adapters=None) -> torch.Tensor:
         """Reference model.py:140-195: one frame of K codes, [B, K] int32.  ``noise`` (K tensors [B, V_a] of Exp(1)
         draws) pins the sampler for parity tests.  ``adapters``: a LoRAState or None per batch row (csm/lora_bank.py), read
-        on a generation's first call."""
+        on a generation's first call.  ``temperature`` / ``topk``: two numbers, a sequence of B values for either one, or None for
+        both - one pair per row through the rows sampler (``Engine.generate_frame``)."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
         return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise, adapters)

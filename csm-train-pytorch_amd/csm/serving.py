@@ -16,6 +16,14 @@ One ``step()`` makes one chunk of ``chunk_frames`` frames for every request in a
 A request with a ``seed`` draws its sampler noise from its own generator (``DecodeState.fill_noise``), so its codes and audio do
 not depend on its slot, its neighbours or when it joined.
 
+Sampling parameters.  By default temperature and top-k belong to the server: they reach the sampler as launch scalars and are the
+key of the captured frame graph.  With ``serve(row_sampling=True)`` they belong to the request: ``submit`` / ``conversation`` /
+``say`` take ``temperature`` and ``topk`` (say > conversation > server's), the slot gets them at admission
+(``DecodeState.set_row_sampling``: two small device writes outside the graph) and every draw of every frame goes through the rows
+sampler (``csm_sample_topk_rows``), which reads ``row_topk[b]`` / ``row_temperature[b]`` from device memory.  One captured frame
+then serves every mix of parameters - a greedy row (``topk=1``) next to a 0.9 / 50 one - and a change never recaptures.  A row's
+codes are those of a default server made with that row's pair (the same bits).  A free row keeps the pair of its last request.
+
 Multi-turn conversations (``BatchServer.conversation`` -> ``ServedConversation``) outlive their slot.  A conversation holds a
 slot only while it speaks: at the end of the chunk in which its turn ended the K / V of its history positions are parked
 (``DecodeState.park_row``: one copy, base + kept frames - what the row sampled after EOS or after its length limit is not
@@ -50,14 +58,15 @@ from typing import Iterator, List, Optional, Tuple
 import torch
 
 from .conversation import OVERFLOW, HeardTurn, open_heard_turn
-from .engine import DecodeState
+from .engine import DecodeState, check_sampling
 
 
 class Request:
     """One utterance of a ``BatchServer``: its audio arrives in ``chunks`` while it holds a slot; ``done`` once it has ended."""
 
-    def __init__(self, rid, text, speaker, adapter, seed, max_audio_frames, tokens, mask, device):
+    def __init__(self, rid, text, speaker, adapter, seed, max_audio_frames, tokens, mask, device, temperature=None, topk=None):
         self.id, self.text, self.speaker, self.adapter, self.seed = rid, text, speaker, adapter, seed
+        self.temperature, self.topk = temperature, topk      # resolved: what it is sampled with
         self.max_audio_frames = max_audio_frames
         self.slot: Optional[int] = None          # the slot it holds (None while queued and after it ended)
         self.done = False
@@ -114,11 +123,12 @@ class ServedConversation:
     ``cached`` mean what they mean on ``Conversation`` and the history has its layout: per turn the text frames, the audio frames,
     one all-zero EOS frame; a spoken turn's frames are the sampled codes; the EOS frame always enters with the next feed."""
 
-    def __init__(self, server, context, adapter, seed, on_overflow):
+    def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None):
         if on_overflow not in OVERFLOW:
             raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
         self._srv, self._gen = server, server._gen
         self.adapter, self.seed, self._on_overflow = adapter, seed, on_overflow
+        self.temperature, self.topk = server._sampling("conversation", temperature, topk)      # its turns' defaults, resolved
         K1 = server._K + 1
         self._tokens = torch.zeros(0, K1, dtype=torch.long, device=self._gen.device)
         self._mask = torch.zeros(0, K1, dtype=torch.bool, device=self._gen.device)
@@ -198,12 +208,15 @@ class ServedConversation:
         self._cached, self._parked = 0, None
 
     @torch.inference_mode()
-    def say(self, text: str, speaker: int, max_audio_length_ms: float = 90_000) -> Request:
+    def say(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: Optional[float] = None,
+            topk: Optional[int] = None) -> Request:
         """Queue the next spoken turn; its audio streams through ``step()`` / ``run()`` like any request's.  The length rule
         counts ``chunk_frames - 1`` frames beyond ``max_audio_length_ms``: a conversation's row samples to the end of its last
-        chunk (module docstring), and that must fit the cache - it raises here, not in ``step``."""
+        chunk (module docstring), and that must fit the cache - it raises here, not in ``step``.  ``temperature`` / ``topk``
+        (``row_sampling`` servers): this turn's, over the conversation's."""
         self._idle("say")
         srv = self._srv
+        temperature, topk = srv._sampling("say", temperature, topk, (self.temperature, self.topk))
         max_audio_frames = int(max_audio_length_ms / 80)
         if max_audio_frames < 1:
             raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
@@ -212,7 +225,8 @@ class ServedConversation:
         feed_t = torch.cat([self._tokens[self._cached:], tt.long().to(self._tokens.device)], 0)
         feed_m = torch.cat([self._mask[self._cached:], tm.bool().to(self._mask.device)], 0)
         self._push(tt.long(), tm.bool())
-        req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device)
+        req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device,
+                      temperature, topk)
         req._conv, req._base = self, self._tokens.shape[0]
         srv._next_id += 1
         srv._queue.append(req)
@@ -245,10 +259,12 @@ class ServedConversation:
 
 
 class BatchServer:
-    """``Generator.serve``: see the module docstring.  Temperature and top-k belong to the server - they are the key of the
-    captured frame graph."""
+    """``Generator.serve``: see the module docstring.  Without ``row_sampling`` temperature and top-k belong to the server - they
+    are launch scalars of the sampler and the key of the captured frame graph.  With it they are the defaults of the requests,
+    which may bring their own: the rows sampler reads each slot's pair from device memory and the graph's key is (None, None)."""
 
-    def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0):
+    def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
+                 row_sampling: bool = False):
         if int(slots) != slots or not 1 <= slots <= 16:
             raise ValueError(f"slots must be an integer in 1..16, got {slots!r}")
         if int(hear_slots) != hear_slots or not 0 <= hear_slots <= 16:
@@ -263,6 +279,9 @@ class BatchServer:
         self._gen, self._model = gen, gen._model
         self.slots, self.chunk_frames, self.hear_slots = int(slots), int(chunk_frames), int(hear_slots)
         self.temperature, self.topk = float(temperature), int(topk)
+        self.row_sampling = bool(row_sampling)
+        if self.row_sampling:                            # (the requests' defaults: held to the requests' rule, before anything is taken over)
+            self.temperature, self.topk = check_sampling(temperature, topk, gen._model.args.audio_vocab_size)
         gen._run += 1                                    # takes over the model's caches, as generate_batch does
         self._run = gen._run
         self._model.reset_caches()
@@ -276,6 +295,9 @@ class BatchServer:
         self._hear = codec.encode_stream_rows(slots=self.hear_slots) if self.hear_slots else None
         self._hearing: List[Optional[SlotHeardTurn]] = [None] * self.hear_slots     # encoder slot -> the turn that holds it
         self._model._decode_state = self._state
+        if self.row_sampling:
+            for b in range(self.slots):                  # every row starts with a valid pair: the sampler runs on all of them
+                self._state.set_row_sampling(b, self.temperature, self.topk)
         K = self._model.args.audio_num_codebooks
         dev = gen.device
         self._K = K
@@ -294,11 +316,29 @@ class BatchServer:
             raise RuntimeError("this server was invalidated: a later generate / generate_batch / generate_stream / serve call on "
                                "the same Generator took over the model's caches")
 
+    def _sampling(self, what, temperature, topk, default=None):
+        """A request's (temperature, topk), resolved against ``default`` (the server's pair if None) and held to
+        ``DecodeState.set_row_sampling``'s rule - at the call, so a bad request raises before it queues."""
+        dt, dk = default if default is not None else (self.temperature, self.topk)
+        if temperature is None and topk is None:
+            return dt, dk
+        if not self.row_sampling:
+            raise ValueError(f"{what}: temperature / topk per request need a server made with serve(row_sampling=True) (this "
+                             f"server samples every row with temperature={self.temperature}, topk={self.topk})")
+        return check_sampling(dt if temperature is None else temperature, dk if topk is None else topk,
+                              self._model.args.audio_vocab_size)
+
+    def _sample_args(self):
+        """What ``serve_first`` / ``serve_frame`` get: the server's two numbers, or None, None (each row's own pair)."""
+        return (None, None) if self.row_sampling else (self.temperature, self.topk)
+
     def submit(self, text: str, speaker: int, context, adapter: Optional[str] = None, seed: Optional[int] = None,
-               max_audio_length_ms: float = 90_000) -> Request:
+               max_audio_length_ms: float = 90_000, temperature: Optional[float] = None, topk: Optional[int] = None) -> Request:
         """Queue one utterance; it takes a slot at the next chunk boundary that has a free one.  The prompt is tokenised here, so
-        the reference's length rule ("Inputs too long ...") and an unknown adapter name raise here."""
+        the reference's length rule ("Inputs too long ...") and an unknown adapter name raise here.  ``temperature`` / ``topk``
+        (``row_sampling`` servers): this request's, over the server's."""
         self._check()
+        temperature, topk = self._sampling("submit", temperature, topk)
         if adapter is not None and adapter not in self._bank:
             known = self._gen._bank is not None and adapter in self._gen._bank.entries
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})" +
@@ -308,20 +348,23 @@ class BatchServer:
             raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
         with torch.inference_mode():
             tokens, mask, _ = self._gen._prompt(text, speaker, list(context), max_audio_frames)
-        req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device)
+        req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device,
+                      temperature, topk)
         self._next_id += 1
         self._queue.append(req)
         return req
 
     def conversation(self, context=(), adapter: Optional[str] = None, seed: Optional[int] = None,
-                     on_overflow: str = "error") -> ServedConversation:
+                     on_overflow: str = "error", temperature: Optional[float] = None,
+                     topk: Optional[int] = None) -> ServedConversation:
         """A multi-turn dialogue on this server: ``conv.say(text, speaker, max_audio_length_ms)`` queues its next spoken turn (a
         ``Request``), ``conv.add(Segment)`` is the other party's turn, ``conv.close()`` drops its parked cache.  ``adapter`` and
-        ``seed`` hold for the whole conversation; ``on_overflow`` as for ``Generator.conversation``."""
+        ``seed`` hold for the whole conversation; ``on_overflow`` as for ``Generator.conversation``.  ``temperature`` / ``topk``
+        (``row_sampling`` servers): the defaults of its turns, over the server's; ``say`` may name a turn's own."""
         self._check()
         if adapter is not None and adapter not in self._bank:
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})")
-        return ServedConversation(self, list(context), adapter, seed, on_overflow)
+        return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk)
 
     @property
     def queued(self) -> int:
@@ -394,7 +437,7 @@ class BatchServer:
         st = self._state
         st.set_active(rows)
         live = st.active.view(self.slots, 1, 1)
-        out = st.serve_frame(self._tok * live, self._mask, self.temperature, self.topk)
+        out = st.serve_frame(self._tok * live, self._mask, *self._sample_args())
         self._tok[:, 0, :self._K] = torch.where(live[:, 0].bool(), out.long(), self._tok[:, 0, :self._K])
         for b in rows:
             self._rows[b]._sampled += 1
@@ -413,6 +456,8 @@ class BatchServer:
             req = self._queue.popleft()
             conv = req._conv
             st.set_row_adapter(b, self._bank[req.adapter] if req.adapter is not None else None)
+            if self.row_sampling:
+                st.set_row_sampling(b, req.temperature, req.topk)
             if conv is not None and conv.seed is not None:
                 if conv._noise is None:
                     conv._noise = st.new_row_generator(conv.seed)
@@ -439,7 +484,7 @@ class BatchServer:
             if self._last_h is None:
                 self._last_h = torch.zeros(self.slots, h.shape[-1], dtype=h.dtype, device=h.device)
             self._last_h[b] = h
-        first = st.serve_first(self._last_h, joined, self.temperature, self.topk)
+        first = st.serve_first(self._last_h, joined, *self._sample_args())
         for b in joined:
             self._tok[b, 0, :self._K] = first[b]
             self._rows[b]._sampled = 1

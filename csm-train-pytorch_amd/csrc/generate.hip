@@ -69,13 +69,36 @@ __device__ __forceinline__ int dpp_row_shr_add(int v, int ctrl_n) {   // v + (v 
         default: return v + __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
     }
 }
-template <int NPT>
+// Where a row's two parameters come from (the kernel's last template parameter).  SampleScalars: the launch scalars of
+// csm_sample_topk, one pair for every row, validated by the entry point - the kernel argument layout (int, float) and the code
+// are those of the kernel before there were two forms.  SampleRows (csm_sample_topk_rows): row r samples with topk[r] /
+// temperature[r], read from device memory - so a captured frame serves every mix of parameters (csm/serving.py,
+// row_sampling).  The two are loaded once per workgroup (two scalar loads of block-uniform addresses, issued among the Exp(1)
+// row's and the logits' loads and before the first wait on any of them, so all are in flight together; the division is their
+// first use).  The host cannot see them, so they are made safe here: top-k into [1, V]; a temperature that is not a finite
+// positive number (zero, negative, NaN, inf) counts as 1.  The one-wave / block-wide choice stays block-uniform: a workgroup
+// is one row.
+struct SampleScalars {
+    int topk;
+    float temperature;
+    __device__ __forceinline__ int k(int, int) const { return topk; }
+    __device__ __forceinline__ float t(int) const { return temperature; }
+};
+struct SampleRows {
+    const int* topk;
+    const float* temperature;
+    __device__ __forceinline__ int k(int row, int V) const { const int v = topk[row]; return v < 1 ? 1 : (v > V ? V : v); }
+    __device__ __forceinline__ float t(int row) const { const float v = temperature[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
+};
+template <int NPT, class Params>
 __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restrict__ logits, const float* __restrict__ q,
-                                                          int* __restrict__ out, int V, int ldl, int topk, float temperature) {
+                                                          int* __restrict__ out, int V, int ldl, const Params prm) {
     __shared__ ValIdx red[4];
     __shared__ float fred[16];
     __shared__ __attribute__((aligned(16))) uint32_t hist[4][256];
     const int row = blockIdx.x;
+    const int topk = prm.k(row, V);
+    const float temperature = prm.t(row);
     const float* x = logits + (size_t)row * ldl;
     const float* qq = q + (size_t)row * V;
     const int lane = threadIdx.x & 63;
@@ -293,9 +316,21 @@ extern "C" int csm_sample_topk(const float* logits, const float* q, int* out, in
     CSM_REQUIRE(logits && q && out && rows > 0 && V > 0 && ldl >= V, "csm_sample_topk: bad arguments");
     CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "csm_sample_topk: V=%d exceeds %d", V, 256 * SMP_PER_THREAD);
     CSM_REQUIRE(topk > 0 && topk <= V && temperature > 0.f, "csm_sample_topk: bad topk=%d / temperature=%f", topk, temperature);
-    if (V <= 256 * 9) hipLaunchKernelGGL(sample_topk_kernel<9>, dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, topk, temperature);
-    else hipLaunchKernelGGL(sample_topk_kernel<SMP_PER_THREAD>, dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, topk, temperature);
+    const SampleScalars prm = {topk, temperature};
+    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleScalars>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleScalars>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
     CSM_CHECK_LAUNCH("csm_sample_topk");
+    return 0;
+}
+
+extern "C" int csm_sample_topk_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
+                                    const float* temperature, hipStream_t stream) {
+    CSM_REQUIRE(logits && q && out && topk && temperature && rows > 0 && V > 0 && ldl >= V, "csm_sample_topk_rows: bad arguments");
+    CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "csm_sample_topk_rows: V=%d exceeds %d", V, 256 * SMP_PER_THREAD);
+    const SampleRows prm = {topk, temperature};
+    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleRows>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleRows>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    CSM_CHECK_LAUNCH("csm_sample_topk_rows");
     return 0;
 }
 

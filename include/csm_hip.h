@@ -233,6 +233,13 @@ int csm_set_adamw_blocks(int blocks); /* tuning switch */
 /* ---- K14: sample_topk + _multinomial_sample_one_no_sync (model.py:79-96), Exp(1) noise q supplied ---------------- */
 int csm_sample_topk(const float* logits, const float* q, int* out, int rows, int V, int ldl, int topk, float temperature,
                     csm_stream_t stream);
+/* Per-row parameters (additive, ABI 3): `topk` / `temperature` are DEVICE arrays of `rows` entries; row r is sampled exactly as
+ * csm_sample_topk samples it with the scalars topk[r], temperature[r] (same bits).  The values cannot be checked on the host, so
+ * the kernel bounds them: topk[r] is clamped into [1, V], a temperature[r] that is not a finite positive number counts as 1.0 -
+ * with finite logits the written index is always in [0, V).  A captured graph that holds this launch serves every mix of
+ * parameters: write the two arrays between replays. */
+int csm_sample_topk_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
+                         const float* temperature, csm_stream_t stream);
 
 /* ---- K15: batch-1 decode of Model.generate_frame (model.py:161-195) against KV caches ------------------------------ *
  * y[b][n] = sum_k x[b][k] W[n][k] (+ residual[b][n]), B <= 16 (weight-streaming matrix-vector product).  B <= 4: VALU kernels,

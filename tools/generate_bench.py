@@ -11,7 +11,8 @@ frames/s with a different LoRA adapter per utterance (16 adapters, some rows wit
 and against the same utterances one at a time with their adapter live as model.lora, alternated in one process.
 GEN_FP8=1: decode frames/s with bf16 and with FP8 (weight-only e4m3) decode weights,
 alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in each mode.  GEN_SERVE=1: the running batch (Generator.serve): rows-codec step against single steps, the server step at
-16 rows, the join stall (serve_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
+16 rows, the join stall (serve_main).  GEN_SERVE_SAMPLING=1: the rows sampler against the scalar one and the 16-row
+server step with row_sampling off / on (serve_sampling_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
 time to the first chunk of turns 1 / 3 / 5 against stateless submits, one append_rows against one-row calls, park / resume, aggregate
 frames/s (serve_conv_main).  GEN_HEAR=1: a 5 s heard turn's last sample to the first chunk of the reply, with
 ``add(Segment)`` against ``hear`` fed during the turn, served (16 slots) and at B = 1 (hear_main), then the batched hearing of
@@ -628,6 +629,73 @@ def serve_main():
           f"in {dt:.3f} s -> {tot / dt:.1f} frames/s aggregate (Mimi encode, prefills, streaming decode included)", flush=True)
 
 
+def serve_sampling_main():
+    """GEN_SERVE_SAMPLING=1: per-request sampling parameters (Generator.serve(row_sampling=True)).  (a) the sampler alone, 16 rows,
+    V = 2051 in the model's padded logits buffer: csm_sample_topk at (50, 0.9) against csm_sample_topk_rows with that pair in every
+    row and with a mixed list (five rows in the block-wide form) - 200 back-to-back launches between two synchronisations,
+    alternated, median (min .. max) of GEN_ROUNDS repeats (default 5).  (b) the steady 16-row server step of GEN_SERVE's setting
+    (CSM-1B random init, 16 slots, chunk_frames 4, 5 s of context each, per-row seeds): row_sampling off (the one-pair path - the
+    yardstick), on with the server's pair in every row, on with a mixed list (four rows above topk 64); each leg is a fresh
+    server, the three alternated GEN_ROUNDS times (default 3), per leg the median of 20 steps and the spread of the repeats'
+    medians."""
+    dev = "cuda:0"
+    n = 4
+    topk = [1, 2, 12, 50, 64, 65, 200, 2051, 50, 50, 64, 65, 1, 7, 300, 33]
+    temp = [0.9, 0.5, 0.8, 0.9, 1.0, 1.3, 0.7, 1.0, 0.25, 2.0, 0.9, 0.9, 1.5, 0.6, 1.1, 0.95]
+    # ---- (a) the sampler alone
+    V, ld = 2051, 2112
+    g = torch.Generator(device=dev).manual_seed(0)
+    lg = torch.randn(16, ld, device=dev, generator=g) * 2
+    q = torch.empty(16, V, device=dev).exponential_(1, generator=g)
+    out = torch.empty(16, dtype=torch.int32, device=dev)
+    k_eq, t_eq = torch.full((16,), 50, dtype=torch.int32, device=dev), torch.full((16,), 0.9, dtype=torch.float32, device=dev)
+    k_mix, t_mix = torch.tensor(topk, dtype=torch.int32, device=dev), torch.tensor(temp, dtype=torch.float32, device=dev)
+    legs = {"scalar (50, 0.9)": lambda: ops.sample_topk(lg, q, out, 50, 0.9, V=V),
+            "rows, (50, 0.9) in every row": lambda: ops.sample_topk_rows(lg, q, out, k_eq, t_eq, V=V),
+            "rows, mixed": lambda: ops.sample_topk_rows(lg, q, out, k_mix, t_mix, V=V)}
+    rounds = int(os.environ.get("GEN_ROUNDS", 5))
+    res = {name: [] for name in legs}
+    for f in legs.values():
+        _timed(f, 20)
+    for _ in range(rounds):
+        for name, f in legs.items():
+            res[name].append(_timed(f, 200))
+    for name, v in res.items():
+        v.sort()
+        print(f"GEN_SERVE_SAMPLING (a) sampler, 16 rows, V={V}: {name}: median {v[len(v) // 2] * 1e6:.2f} us per launch "
+              f"(min {v[0] * 1e6:.2f}, max {v[-1] * 1e6:.2f}; {rounds} x 200 back-to-back launches)", flush=True)
+    # ---- (b) the server step
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    codec = make_codec(dev)
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=codec)
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+    topk_b = list(topk)
+    topk_b[11] = 50                                                          # four rows above 64: 65, 200, 2051, 300
+    modes = {"off": None, "on, equal": [(0.9, 50)] * 16, "on, mixed": list(zip(temp, topk_b))}
+    meds = {name: [] for name in modes}
+    for _ in range(rounds):
+        for name, pairs in modes.items():
+            srv = gen.serve(slots=16, chunk_frames=n, row_sampling=pairs is not None)
+            for i in range(16):
+                kw = {} if pairs is None else dict(temperature=pairs[i][0], topk=pairs[i][1])
+                srv.submit(f"utterance number {i}: {text}", i, ctx, seed=i, max_audio_length_ms=80 * 400, **kw)
+            _timed(srv.step, 1)                                              # 16 prefills + the first chunk
+            _timed(srv.step, 2)                                              # eager warm-up frame, graph capture
+            steps = sorted(_timed(srv.step, 1) for _ in range(20))
+            meds[name].append(steps[len(steps) // 2])
+    for name, v in meds.items():
+        print(f"GEN_SERVE_SAMPLING (b) server step, 16 rows x {n} frames, row_sampling {name}: medians of 20 steps "
+              f"{[round(x * 1e3, 2) for x in v]} ms -> median {sorted(v)[len(v) // 2] * 1e3:.2f} ms, spread of the repeats "
+              f"{(max(v) - min(v)) * 1e3:.2f} ms", flush=True)
+    off = sorted(meds["off"])[rounds // 2]
+    for name in ("on, equal", "on, mixed"):
+        on = sorted(meds[name])[rounds // 2]
+        print(f"GEN_SERVE_SAMPLING (b) row_sampling {name} - off: {(on - off) * 1e3:+.2f} ms per step = {(on - off) * 1e6 / n:+.1f} us per "
+              f"frame (off's own repeats span {(max(meds['off']) - min(meds['off'])) * 1e3:.2f} ms)", flush=True)
+
+
 def serve_conv_main():
     """GEN_SERVE_CONV=1: conversations on the running batch (BatchServer.conversation) on CSM-1B random init - 16 slots,
     chunk_frames 4, 16 conversations of 6 turns: odd turns spoken (GEN_FRAMES frames, default 24), even turns 5 s of the other
@@ -970,6 +1038,8 @@ def main():
     if os.environ.get("GEN_HEAR") == "1":
         hear_main()
         return hear_rows_main()
+    if os.environ.get("GEN_SERVE_SAMPLING") == "1":
+        return serve_sampling_main()
     if os.environ.get("GEN_SERVE_CONV") == "1":
         return serve_conv_main()
     if os.environ.get("GEN_SERVE") == "1":
