@@ -30,6 +30,11 @@ def parse_args(argv=None):
     p.add_argument("--max-audio-length-ms", type=int, default=10000)
     p.add_argument("--temperature", type=float, default=0.9)
     p.add_argument("--topk", type=int, default=50)
+    p.add_argument("--top-p", type=float, default=1.0,
+                   help="nucleus cut in (0, 1], applied inside the sampler to what --topk kept: the largest values whose probability "
+                        "reaches it stay (1.0: off)")
+    p.add_argument("--min-p", type=float, default=0.0,
+                   help="min-p cut in [0, 1], applied before --top-p: tokens below min-p times the largest probability go (0.0: off)")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--mimi-weights", type=str, required=True, help="local Mimi weights (transformers.MimiModel state dict)")
     p.add_argument("--text-tokenizer", type=str, required=True, help="local directory of the Llama-3.2 tokenizer files")
@@ -46,11 +51,12 @@ def parse_args(argv=None):
                    help="speaker ID of the corresponding --next-text (repeatable; default: the speaker of --text)")
     p.add_argument("--serve-file", type=str, default=None,
                    help="JSON-lines file of utterances {\"text\", \"speaker\", \"adapter\"?: LoRA adapter file, \"seed\"?: int, "
-                        "\"temperature\"?: float, \"topk\"?: int, \"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
+                        "\"temperature\"?: float, \"topk\"?: int, \"top_p\"?: float, \"min_p\"?: float, \"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
                         "--context-*; lines with the same conversation id are successive turns of one served conversation, in file "
                         "order (KV cache kept between them; adapter and seed of its first line); a line's temperature / topk hold for "
                         "that utterance or turn (default: --temperature / --topk; a file that names one is served with "
-                        "row_sampling=True); one WAV per utterance, "
+                        "row_sampling=True); likewise a line's top_p / min_p (default: --top-p / --min-p; a file that names one, or "
+                        "a --top-p / --min-p that is not 1.0 / 0.0, is served with row_filters=True); one WAV per utterance, "
                         "<output stem>_<i>.wav with i = 0, 1, ... counting the file's non-empty lines")
     p.add_argument("--slots", type=int, default=16, help="--serve-file: utterances decoded at once (1..16, default 16)")
     p.add_argument("--hear-slots", type=int, default=0,
@@ -104,7 +110,7 @@ def main(argv=None):
     if args.stream:
         return stream_to_wav(generator, args, speaker_id, context, adapter)
     audio = generator.generate(text=args.text, speaker=speaker_id, context=context, max_audio_length_ms=args.max_audio_length_ms,
-                               temperature=args.temperature, topk=args.topk, adapter=adapter)
+                               temperature=args.temperature, topk=args.topk, adapter=adapter, top_p=args.top_p, min_p=args.min_p)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     generator.save_wav(args.output, audio)
     print(f"Audio saved to {args.output} ({audio.numel() / generator.sample_rate:.2f} s at {generator.sample_rate} Hz)")
@@ -123,7 +129,8 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
         w.setframerate(int(generator.sample_rate))
         for chunk in generator.generate_stream(text=args.text, speaker=speaker_id, context=context,
                                                max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature,
-                                               topk=args.topk, chunk_frames=args.chunk_frames, adapter=adapter):
+                                               topk=args.topk, chunk_frames=args.chunk_frames, adapter=adapter,
+                                               top_p=args.top_p, min_p=args.min_p):
             pcm = (chunk.detach().float().cpu().clamp(-1, 1) * 32767.0).to(torch.int16).numpy().tobytes()
             if n == 0:
                 print(f"first chunk after {time.perf_counter() - t0:.3f} s")
@@ -136,7 +143,7 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
 
 def read_serve_file(path):
     """--serve-file: one JSON object per non-empty line -> [{"text", "speaker", "adapter", "seed"}], plus "conversation" (a
-    string), "temperature" (a float) and "topk" (an int) on the lines that carry those keys."""
+    string), "temperature" (a float), "topk" (an int), "top_p" and "min_p" (floats) on the lines that carry those keys."""
     import json
     lines = []
     with open(path) as f:
@@ -146,7 +153,7 @@ def read_serve_file(path):
             d = json.loads(raw)
             if not isinstance(d, dict) or not isinstance(d.get("text"), str):
                 raise ValueError(f"{path}:{i}: every line is a JSON object with a \"text\" string")
-            unknown = set(d) - {"text", "speaker", "adapter", "seed", "conversation", "temperature", "topk"}
+            unknown = set(d) - {"text", "speaker", "adapter", "seed", "conversation", "temperature", "topk", "top_p", "min_p"}
             if unknown:
                 raise ValueError(f"{path}:{i}: unknown keys {sorted(unknown)}")
             lines.append({"text": d["text"], "speaker": int(d.get("speaker", 0)), "adapter": d.get("adapter"),
@@ -161,6 +168,11 @@ def read_serve_file(path):
                 if isinstance(d["topk"], bool) or not isinstance(d["topk"], int):
                     raise ValueError(f"{path}:{i}: \"topk\" is an integer, got {d['topk']!r}")
                 lines[-1]["topk"] = d["topk"]
+            for k in ("top_p", "min_p"):
+                if d.get(k) is not None:
+                    if isinstance(d[k], bool) or not isinstance(d[k], (int, float)):
+                        raise ValueError(f"{path}:{i}: \"{k}\" is a number, got {d[k]!r}")
+                    lines[-1][k] = float(d[k])
     if not lines:
         raise ValueError(f"{path}: no utterances")
     return lines
@@ -176,12 +188,27 @@ def serve_sampling(lines):
     return {"row_sampling": True} if any(line_sampling(ln) for ln in lines) else {}
 
 
+def line_filters(line):
+    """The filter keywords of one --serve-file line for ``submit`` / ``say``: only what the line carries."""
+    return {k: line[k] for k in ("top_p", "min_p") if k in line}
+
+
+def serve_filters(lines, top_p=1.0, min_p=0.0):
+    """``Generator.serve`` keywords for these lines and the command line's --top-p / --min-p: ``row_filters=True`` (with
+    ``row_sampling=True``, which it needs, and the two as the server's defaults) as soon as a line names a filter or the
+    command line's are not 1.0 / 0.0; nothing otherwise - the server is then the one it is without filters."""
+    if any(line_filters(ln) for ln in lines) or (top_p, min_p) != (1.0, 0.0):
+        return {"row_sampling": True, "row_filters": True, "top_p": top_p, "min_p": min_p}
+    return {}
+
+
 def serve_to_wavs(generator, args, context, adapter=None):
     """--serve-file: every line is a request of one ``Generator.serve`` batch; adapter files are loaded once each, under their
     path as name (--lora-adapter is the default for lines without one).  Lines with a "conversation" id are the turns of one
     served conversation (``BatchServer.conversation``): its first line is queued with the rest, each later one when the turn
     before it is done.  A line's "temperature" / "topk" are that utterance's or that turn's; if any line has one, the server is
-    made with ``row_sampling=True`` (--temperature / --topk are then the other lines' values).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav."""
+    made with ``row_sampling=True`` (--temperature / --topk are then the other lines' values); "top_p" / "min_p" likewise, with
+    ``row_filters=True`` (``serve_filters``).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav."""
     lines = read_serve_file(args.serve_file)
     for path in sorted({ln["adapter"] for ln in lines if ln["adapter"]}):
         generator.load_adapter(path, path)
@@ -189,20 +216,22 @@ def serve_to_wavs(generator, args, context, adapter=None):
     os.makedirs(os.path.dirname(stem), exist_ok=True)
     t0 = time.perf_counter()
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, temperature=args.temperature,
-                             topk=args.topk, hear_slots=args.hear_slots, **serve_sampling(lines))
+                             topk=args.topk, hear_slots=args.hear_slots,
+                             **{**serve_sampling(lines), **serve_filters(lines, args.top_p, args.min_p)})
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
     def say(cid):
         conv, todo = convs[cid]
         i = todo.pop(0)
         line_of[conv.say(lines[i]["text"], lines[i]["speaker"], max_audio_length_ms=args.max_audio_length_ms,
-                         **line_sampling(lines[i]))] = (i, cid)
+                         **line_sampling(lines[i]), **line_filters(lines[i]))] = (i, cid)
 
     for i, ln in enumerate(lines):
         cid = ln.get("conversation")
         if cid is None:
             line_of[server.submit(ln["text"], ln["speaker"], context, adapter=ln["adapter"] or adapter, seed=ln["seed"],
-                                  max_audio_length_ms=args.max_audio_length_ms, **line_sampling(ln))] = (i, None)
+                                  max_audio_length_ms=args.max_audio_length_ms, **line_sampling(ln),
+                                  **line_filters(ln))] = (i, None)
         elif cid in convs:
             convs[cid][1].append(i)
         else:
@@ -232,7 +261,8 @@ def converse_to_wav(generator, args, speaker_id, context, adapter=None):
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     lines = [(args.text, speaker_id)] + list(zip(args.next_text, args.next_speaker or [speaker_id] * len(args.next_text)))
     conv = generator.conversation(context=context, adapter=adapter)
-    kw = dict(max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature, topk=args.topk)
+    kw = dict(max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature, topk=args.topk, top_p=args.top_p,
+              min_p=args.min_p)
     t0 = time.perf_counter()
     n = 0
     with wave.open(args.output, "wb") as w:

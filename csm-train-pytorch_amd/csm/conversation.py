@@ -224,7 +224,7 @@ class Conversation:
         finally:
             m._decode_state = prev
 
-    def _begin(self, text, speaker, max_audio_frames, temperature, topk) -> _Turn:
+    def _begin(self, text, speaker, max_audio_frames, temperature, topk, filters={}) -> _Turn:
         """Feed what the cache lacks plus the new line's text frames, sample the first frame."""
         m, e = self._m, self._m.engine
         if not getattr(m, "use_kv_cache", True):
@@ -244,17 +244,19 @@ class Conversation:
         self._push(tt.long(), tm.bool())
         self._cached = self._tokens.shape[0]
         turn = self._open = _Turn(self._cached, tt.shape[0])
+        if filters:                                                  # (the rows path of this conversation's state)
+            temperature, topk = st.sampling_args(temperature, topk, **filters)
         turn.samples.append(e._frame_tail(st, last_h, temperature, topk, None))
         return turn
 
-    def _next_frame(self, turn: _Turn, temperature, topk):
+    def _next_frame(self, turn: _Turn, temperature, topk, filters={}):
         """Feed the last sampled frame, sample the next one (``Model.generate_frame`` on this conversation's state)."""
         K = self._m.args.audio_num_codebooks
         dev = self._gen.device
         tokens = torch.cat([turn.samples[-1].long(), torch.zeros(1, 1, dtype=torch.long, device=dev)], dim=1).unsqueeze(1)
         mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(dev)
         with self._installed():
-            s = self._m.generate_frame(tokens, mask, torch.ones(1, 1, dtype=torch.long), temperature, topk)
+            s = self._m.generate_frame(tokens, mask, torch.ones(1, 1, dtype=torch.long), temperature, topk, **filters)
         turn.fed += 1
         turn.samples.append(s)
 
@@ -285,8 +287,11 @@ class Conversation:
 
     @torch.inference_mode()
     def generate(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
-                 eos_check_every: int = 8) -> torch.Tensor:
-        """Speak ``text`` as ``speaker`` with the whole history as context; arguments and EOS handling as ``Generator.generate``."""
+                 eos_check_every: int = 8, top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
+        """Speak ``text`` as ``speaker`` with the whole history as context; arguments (``top_p`` / ``min_p`` included: this turn's)
+        and EOS handling as ``Generator.generate``."""
+        from .generator import filter_kwargs
+        filters = filter_kwargs(top_p, min_p)
         self._run += 1
         self._settle()
         max_audio_frames = int(max_audio_length_ms / 80)
@@ -295,9 +300,9 @@ class Conversation:
         try:
             for i in range(max_audio_frames):
                 if turn is None:
-                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk)
+                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk, filters)
                 else:
-                    self._next_frame(turn, temperature, topk)
+                    self._next_frame(turn, temperature, topk, filters)
                 n = len(turn.samples)
                 if n - checked >= step or i == max_audio_frames - 1:
                     hit = (torch.cat(turn.samples[checked:], 0) == 0).all(dim=1).nonzero()          # one host look per chunk
@@ -314,9 +319,11 @@ class Conversation:
         return self._gen._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
 
     def generate_stream(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9,
-                        topk: int = 50, chunk_frames: int = 4) -> Iterator[torch.Tensor]:
+                        topk: int = 50, chunk_frames: int = 4, top_p: float = 1.0, min_p: float = 0.0) -> Iterator[torch.Tensor]:
         """``generate`` handing the audio out chunk by chunk, as ``Generator.generate_stream`` does; under the same seed the
         chunks concatenate to ``generate``'s audio.  A later call on THIS conversation invalidates the stream."""
+        from .generator import filter_kwargs
+        filters = filter_kwargs(top_p, min_p)
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
         codec = self._gen._audio_tokenizer
@@ -325,10 +332,10 @@ class Conversation:
                             "(decoding chunks independently would be wrong at the chunk edges)")
         self._run += 1
         self._settle()
-        return self._stream(self._run, text, speaker, max_audio_length_ms, temperature, topk, int(chunk_frames))
+        return self._stream(self._run, text, speaker, max_audio_length_ms, temperature, topk, int(chunk_frames), filters)
 
     @torch.inference_mode()
-    def _stream(self, run, text, speaker, max_audio_length_ms, temperature, topk, chunk_frames):
+    def _stream(self, run, text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, filters={}):
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later call on the same Conversation took its turn")
@@ -340,9 +347,9 @@ class Conversation:
         try:
             for i in range(max_audio_frames):
                 if turn is None:
-                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk)
+                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk, filters)
                 else:
-                    self._next_frame(turn, temperature, topk)
+                    self._next_frame(turn, temperature, topk, filters)
                 if len(turn.samples) - done == chunk_frames or i == max_audio_frames - 1:
                     codes = torch.stack(turn.samples[done:]).permute(1, 2, 0).long()               # [1, K, n]
                     hit = (codes[0] == 0).all(dim=0).nonzero()                                     # the chunk's one host look

@@ -869,7 +869,8 @@ class Engine:
         return self.backbone.forward(h0, B, S, False).view(B, S, -1)
 
     @torch.no_grad()
-    def generate_frame(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None, adapters=None):
+    def generate_frame(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None, adapters=None, top_p=None,
+                       min_p=None):
         """Reference model.py:140-195: backbone position(s) -> c0 -> 31 depth-decoder steps, against KV caches.
 
         The prompt (``input_pos`` starting at 0) is prefilled with the training forward kernels and its post-RoPE K/V
@@ -880,12 +881,16 @@ class Engine:
         adapters from a bank (csm/lora_bank.py).
         ``temperature`` / ``topk``: two numbers - or, with caches, a sequence of B values for either one (a parameter pair per
         row, ``DecodeState.sampling_args``), or None for both (the pairs ``DecodeState.set_row_sampling`` wrote).
+        ``top_p`` / ``min_p`` (with caches; None: not named): a number or B values for either one - the rows then sample through
+        the filtered rows sampler (``DecodeState.set_row_filters``); give the same to every call of the generation.
         """
         m, a = self.m, self.m.args
         self._need()
         if int(input_pos[0, 0]) == 0:
             m._gen_adapters = list(adapters) if adapters is not None and any(x is not None for x in adapters) else None
         if not getattr(m, "use_kv_cache", True):
+            if top_p is not None or min_p is not None:
+                raise ValueError("the recompute path (use_kv_cache = False) has no top_p / min_p: the filters need the KV-cache path")
             return self._generate_frame_recompute(tokens, tokens_mask, input_pos, temperature, topk, noise)
         dev = m.device
         K, V, Vp = a.audio_num_codebooks, a.audio_vocab_size, m.vocab_pad
@@ -899,7 +904,7 @@ class Engine:
                                "same batch size (call it with input_pos starting at 0 first)")
         if first:
             st = m._decode_state = DecodeState(self, Bn, adapters)
-        temperature, topk = st.sampling_args(temperature, topk)
+        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p)
         if first:
             last_h = st.prefill(tokens, tokens_mask)
             return self._frame_tail(st, last_h, temperature, topk, noise)
@@ -911,15 +916,17 @@ class Engine:
         return self._decode_frame(st, tokens, tokens_mask, temperature, topk, noise)
 
     @torch.no_grad()
-    def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None, adapters=None):
+    def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None, adapters=None, top_p=None,
+                              min_p=None):
         """Batched generation (up to 16 utterances): prefill B prompts of different lengths and sample the
         first frame of each; later frames go through ``generate_frame`` with ``[B, 1, K+1]`` tokens and a non-zero
         ``input_pos``, exactly as for one utterance.  ``temperature`` / ``topk``: two numbers, or a sequence of B values for
-        either one - row b then samples with its own pair (``DecodeState.sampling_args``); give the same to ``generate_frame``."""
+        either one - row b then samples with its own pair (``DecodeState.sampling_args``); give the same to ``generate_frame``.
+        ``top_p`` / ``min_p``: as for ``generate_frame``."""
         m = self.m
         self._need()
         st = m._decode_state = DecodeState(self, len(tokens_list), adapters)
-        temperature, topk = st.sampling_args(temperature, topk)
+        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p)
         last_h = st.prefill_ragged(tokens_list, masks_list)
         return self._frame_tail(st, last_h, temperature, topk, noise)
 
@@ -947,11 +954,17 @@ class Engine:
 
         if temperature is None and topk is None:
             # each row's own pair, read by the sampler from the state's row buffers (written outside the graph: set_row_sampling)
-            from .models.model import sample_topk_rows
+            from .models.model import sample_filtered_rows, sample_topk_rows
             row_t, row_k = st.row_sampling_buffers()
+            if st.row_filters is not None:
+                # ... and its own top-p / min-p (set_row_filters): the filtered rows sampler; a (1, 0) row is the rows sampler's
+                row_p, row_m = st.row_filter_buffers()
 
-            def draw(lg, i):
-                return sample_topk_rows(lg[:, :V], row_k, row_t, qall[i])
+                def draw(lg, i):
+                    return sample_filtered_rows(lg[:, :V], row_k, row_t, row_p, row_m, qall[i])
+            else:
+                def draw(lg, i):
+                    return sample_topk_rows(lg[:, :V], row_k, row_t, qall[i])
         elif temperature is None or topk is None:
             raise ValueError("temperature and topk are both numbers, or both None (each row's own pair: set_row_sampling)")
         else:
@@ -1308,6 +1321,22 @@ def check_sampling(temperature, topk, vocab):
     return t, k
 
 
+def check_filters(top_p, min_p):
+    """The rule for one row's sampling filters: ``top_p`` a number in (0, 1] (1: no nucleus cut), ``min_p`` a number in [0, 1]
+    (0: no min-p cut).  Returns (float, float); raises ValueError with the offending value."""
+    out = []
+    for name, v, ok, rule in (("top_p", top_p, lambda f: 0.0 < f <= 1.0, "in (0, 1]"),
+                              ("min_p", min_p, lambda f: 0.0 <= f <= 1.0, "in [0, 1]")):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            f = float("nan")
+        if isinstance(v, (bool, str, bytes)) or not ok(f):
+            raise ValueError(f"{name} must be a number {rule}, got {v!r}")
+        out.append(f)
+    return out[0], out[1]
+
+
 class DecodeState:
     """Everything ``generate_frame`` keeps between calls: the two stacks' caches and small persistent buffers."""
 
@@ -1359,6 +1388,8 @@ class DecodeState:
         self.graph, self.graph_key, self.warm = None, None, 0
         # per-row sampling parameters (set_row_sampling): two device vectors the rows sampler reads + their host mirror
         self.row_temperature, self.row_topk, self.row_sampling = None, None, None
+        # ... and per-row filters (set_row_filters): top-p / min-p vectors for the filtered rows sampler + their host mirror
+        self.row_top_p, self.row_min_p, self.row_filters = None, None, None
         # the frame's Exp(1) draws [K, B, V]: a PERSISTENT buffer, refilled before every frame outside the captured graph -
         # so a replayed frame can be given the same noise as an eager one (parity tests) or fresh draws (generation)
         self.noise_buf = torch.empty(m.args.audio_num_codebooks, B, m.args.audio_vocab_size, dtype=F32, device=dev)
@@ -1611,10 +1642,53 @@ class DecodeState:
             raise RuntimeError("temperature = topk = None samples each row with its own pair: call set_row_sampling first")
         return self.row_temperature, self.row_topk
 
-    def sampling_args(self, temperature, topk):
+    def set_row_filters(self, b, top_p, min_p):
+        """Row ``b`` samples with the nucleus ``top_p`` and the min-p threshold ``min_p`` from its next frame on, in every frame
+        body called with ``temperature=None, topk=None``: two floats written to ``row_top_p[b]`` / ``row_min_p[b]`` on the device,
+        which the filtered rows sampler reads (``csm_sample_filtered_rows``) - outside the captured graph, so a change never
+        recaptures.  The two buffers are made by the first call, with every row at that call's values; once they exist the frame
+        bodies draw through the filtered sampler (make them before the first capture).  ``row_filters`` is the host mirror,
+        [(top_p, min_p)] * B."""
+        top_p, min_p = check_filters(top_p, min_p)
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        if self.row_filters is None:
+            dev = self.noise_buf.device
+            self.row_top_p = torch.full((self.B,), top_p, dtype=F32, device=dev)
+            self.row_min_p = torch.full((self.B,), min_p, dtype=F32, device=dev)
+            self.row_filters = [(top_p, min_p)] * self.B
+        elif self.row_filters[b] != (top_p, min_p):
+            self.row_top_p[b:b + 1].fill_(top_p)
+            self.row_min_p[b:b + 1].fill_(min_p)
+            self.row_filters[b] = (top_p, min_p)
+
+    def row_filter_buffers(self):
+        """(row_top_p, row_min_p) for a frame body called with None, None."""
+        if self.row_filters is None:
+            raise RuntimeError("no row filters: call set_row_filters first")
+        return self.row_top_p, self.row_min_p
+
+    def sampling_args(self, temperature, topk, top_p=None, min_p=None):
         """What ``Engine.generate_frame`` / ``generate_first_frames`` hand to the frame bodies: two numbers (or None, None) pass
         through; a sequence of B values for either one is written to the rows (``set_row_sampling``; the other, if a number,
-        holds for every row) and (None, None) comes back."""
+        holds for every row) and (None, None) comes back.  ``top_p`` / ``min_p`` (None: not named - nothing changes): numbers or
+        one value per row, written to the rows' filters (``set_row_filters``) - they live in the rows path, so the pair goes to
+        the rows too and (None, None) comes back."""
+        if top_p is not None or min_p is not None:
+            ps = [1.0 if top_p is None else top_p] * self.B if top_p is None or _is_number(top_p) else _as_list(top_p)
+            ms = [0.0 if min_p is None else min_p] * self.B if min_p is None or _is_number(min_p) else _as_list(min_p)
+            if ps is None or ms is None or len(ps) != self.B or len(ms) != self.B:
+                raise ValueError(f"top_p and min_p are numbers or sequences of one value per row ({self.B} rows): got "
+                                 f"top_p={top_p!r}, min_p={min_p!r}")
+            for p_, m_ in zip(ps, ms):                     # (all of them before any is written)
+                check_filters(p_, m_)
+            if _is_number(temperature) and _is_number(topk):
+                temperature, topk = [temperature] * self.B, [topk] * self.B
+            temperature, topk = self.sampling_args(temperature, topk)
+            for b, (p_, m_) in enumerate(zip(ps, ms)):
+                self.set_row_filters(b, p_, m_)
+            return temperature, topk
         if (temperature is None and topk is None) or (_is_number(temperature) and _is_number(topk)):
             return temperature, topk
         ts = [temperature] * self.B if _is_number(temperature) else _as_list(temperature)
@@ -1698,10 +1772,14 @@ class DecodeState:
         (warm-up: lazy function attributes, allocator), the second is captured, later ones are replays; positions, input
         tokens and the frame's noise live in persistent device buffers, so the same graph serves every frame.  Re-captured
         when temperature / top-k change; with ``None, None`` the key is (None, None) and the sampler reads each row's pair from
-        the row buffers (``set_row_sampling``), so a change of any row's parameters replays the same graph."""
+        the row buffers (``set_row_sampling``), so a change of any row's parameters replays the same graph; once the state has
+        row filters (``set_row_filters``) it is (None, None, "filters") - the frame holds the filtered rows sampler, and a change
+        of any row's top-p / min-p replays it too."""
         m = self.e.m
         self._advance()
         key = (None, None) if temperature is None and topk is None else (float(temperature), int(topk))
+        if key == (None, None) and self.row_filters is not None:
+            key = (None, None, "filters")                # (the frame draws through the filtered rows sampler: another graph)
         if self.graph is None or self.graph_key != key:
             if self.warm < 1 or self.graph_key not in (None, key):
                 self.warm, self.graph, self.graph_key = 1, None, None

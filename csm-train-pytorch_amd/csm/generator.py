@@ -41,6 +41,27 @@ def load_llama3_tokenizer(path: str = "meta-llama/Llama-3.2-1B"):
     return tokenizer
 
 
+def filter_kwargs(top_p, min_p, B=None):
+    """The ``top_p`` / ``min_p`` keywords of a frame call: {} at the defaults (1.0 / 0.0 - the call is then today's, untouched),
+    else both, held to ``check_filters`` here (before any cache is taken over).  ``B``: either one may be a sequence of B values."""
+    from .engine import _as_list, _is_number, check_filters
+    if _is_number(top_p) and _is_number(min_p):
+        top_p, min_p = check_filters(top_p, min_p)
+        return {} if (top_p, min_p) == (1.0, 0.0) else {"top_p": top_p, "min_p": min_p}
+    out = {}
+    for name, v in (("top_p", top_p), ("min_p", min_p)):
+        if not _is_number(v):
+            seq = None if B is None else _as_list(v)
+            if seq is None or len(seq) != B:
+                raise ValueError(f"{name} is a number" + (f" or a sequence of one value per utterance ({B})" if B else "") +
+                                 f", got {v!r}")
+            v = seq
+        out[name] = v
+    for b in range(B):
+        check_filters(*[v if _is_number(v) else v[b] for v in (out["top_p"], out["min_p"])])
+    return out
+
+
 class Generator:
     """Speech generator using the CSM model (reference generator.py:48)."""
 
@@ -119,12 +140,17 @@ class Generator:
 
     @torch.inference_mode()
     def generate(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
-                 temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8, adapter: Optional[str] = None) -> torch.Tensor:
+                 temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8, adapter: Optional[str] = None,
+                 top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
         """Reference generator.py:147-218.  ``adapter``: the name of a bank adapter (``add_adapter`` / ``load_adapter``) to
         speak with, or None.  The reference tests every frame for EOS on the host (one device sync per
         frame, generator.py:196-199); here the all-zero test runs on the device and the host looks at it once per
         ``eos_check_every`` frames, so the frame graphs are enqueued back to back.  The audio returned is the same: frames
-        sampled past the EOS frame are dropped."""
+        sampled past the EOS frame are dropped.
+        ``top_p`` (in (0, 1]) / ``min_p`` (in [0, 1]): a nucleus and a min-p cut applied inside the sampler to what top-k kept -
+        first p_i >= min_p * p_max, then the smallest set of the largest values whose probability reaches top_p.  At 1.0 / 0.0
+        (the defaults) the call is what it is without them; otherwise it samples through the filtered rows sampler."""
+        filters = filter_kwargs(top_p, min_p)
         ads = self._resolve_adapters([adapter])
         self._run += 1
         self._model.reset_caches()
@@ -137,7 +163,7 @@ class Generator:
         checked = 0                                   # frames [0, checked) are known not to be EOS
         step = max(1, int(eos_check_every))
         for i in range(max_audio_frames):
-            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads)
+            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads, **filters)
             samples.append(sample)
             if len(samples) - checked >= step or i == max_audio_frames - 1:
                 eos = (torch.cat(samples[checked:], 0) == 0).all(dim=1)                 # one host look per chunk
@@ -174,14 +200,15 @@ class Generator:
 
     def generate_stream(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                         temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4,
-                        adapter: Optional[str] = None) -> Iterator[torch.Tensor]:
+                        adapter: Optional[str] = None, top_p: float = 1.0, min_p: float = 0.0) -> Iterator[torch.Tensor]:
         """``generate`` that hands the audio out while it is being made: an iterator of 1-D device tensors of
         ``chunk_frames * 1920`` samples (the last one may be shorter), decoded by the audio tokenizer's stateful
         ``decode_stream()``.  The frames are sampled by the same ``generate_frame`` calls in the same order as ``generate``,
         so under the same torch seed the concatenated chunks equal ``generate``'s audio.  The host looks for EOS once per
         chunk; frames from EOS on are never decoded.  A later ``generate`` / ``generate_batch`` / ``generate_stream`` on this
         Generator invalidates the stream (its next ``next()`` raises ``RuntimeError``); abandoning it is harmless.
-        ``adapter``: as for ``generate``."""
+        ``adapter``, ``top_p``, ``min_p``: as for ``generate``."""
+        filters = filter_kwargs(top_p, min_p)
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
         if not callable(getattr(self._audio_tokenizer, "decode_stream", None)):
@@ -189,10 +216,11 @@ class Generator:
                             "(decoding chunks independently would be wrong at the chunk edges)")
         ads = self._resolve_adapters([adapter])
         self._run += 1
-        return self._stream(self._run, text, speaker, context, max_audio_length_ms, temperature, topk, int(chunk_frames), ads)
+        return self._stream(self._run, text, speaker, context, max_audio_length_ms, temperature, topk, int(chunk_frames), ads,
+                            filters)
 
     @torch.inference_mode()
-    def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames, ads=None):
+    def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames, ads=None, filters={}):
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later generate / generate_batch / generate_stream call on "
@@ -208,7 +236,7 @@ class Generator:
         pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
         pending = []
         for i in range(max_audio_frames):
-            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads)
+            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads, **filters)
             pending.append(sample)
             if len(pending) == chunk_frames or i == max_audio_frames - 1:
                 codes = torch.stack(pending).permute(1, 2, 0).long()                       # [1, K, n]
@@ -227,7 +255,8 @@ class Generator:
     @torch.inference_mode()
     def generate_batch(self, texts: List[str], speakers: List[int], contexts: List[List[Segment]],
                        max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
-                       eos_check_every: int = 8, adapters: Optional[List[Optional[str]]] = None) -> List[torch.Tensor]:
+                       eos_check_every: int = 8, adapters: Optional[List[Optional[str]]] = None, top_p=1.0,
+                       min_p=0.0) -> List[torch.Tensor]:
         """``generate`` for up to 16 utterances at once (not in the reference, whose loop is single-utterance): the prompts
         (different lengths) are prefilled one by one into their rows of the KV caches, then every decode frame advances all
         rows together - the decode kernels share each weight load between the batch rows, so B utterances cost about as
@@ -238,11 +267,14 @@ class Generator:
         live ``model.lora`` must be absent or merged.
         ``temperature`` / ``topk``: a number for all utterances, or a sequence of one value per utterance for either one -
         each row then samples with its own pair (the rows sampler, ``DecodeState.set_row_sampling``) and has the codes it
-        has in a batch of the same size run with its pair for everybody; two numbers are the one-pair path."""
+        has in a batch of the same size run with its pair for everybody; two numbers are the one-pair path.
+        ``top_p`` / ``min_p``: a number or one value per utterance for either one (``generate``); at 1.0 / 0.0 the call is what it
+        is without them, otherwise every row samples through the filtered rows sampler with its own four parameters."""
         B = len(texts)
         if not (1 <= B <= 16 and len(speakers) == B and len(contexts) == B):
             raise ValueError("generate_batch takes 1..16 utterances with one speaker id and one context list each")
         temperature, topk = self._batch_sampling(temperature, topk, B)
+        filters = filter_kwargs(top_p, min_p, B)
         if adapters is not None and len(adapters) != B:
             raise ValueError(f"generate_batch: {len(adapters)} adapter names for {B} utterances (one name or None each)")
         ads = self._resolve_adapters(list(adapters)) if adapters is not None else None
@@ -264,7 +296,7 @@ class Generator:
             msks.append(torch.cat(m_, 0).bool().to(self.device))
             if toks[-1].size(0) >= self._model.bb.max_seq_len - max_audio_frames:
                 raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {self._model.bb.max_seq_len - max_audio_frames}")
-        frames = [self._model.engine.generate_first_frames(toks, msks, temperature, topk, adapters=ads)]          # [B, K] each
+        frames = [self._model.engine.generate_first_frames(toks, msks, temperature, topk, adapters=ads, **filters)]          # [B, K] each
         mask = torch.cat([torch.ones(B, K, dtype=torch.bool), torch.zeros(B, 1, dtype=torch.bool)], 1).unsqueeze(1).to(self.device)
         pad = torch.zeros(B, 1, dtype=torch.long, device=self.device)
         pos = torch.ones(B, 1, dtype=torch.long, device=self.device)       # only "not the prompt" matters: positions live on the device
@@ -279,7 +311,7 @@ class Generator:
                 if all(e is not None for e in eos_at) or i == max_audio_frames:
                     break
             tokens = torch.cat([frames[-1].long(), pad], dim=1).unsqueeze(1)
-            frames.append(self._model.generate_frame(tokens, mask, pos, temperature, topk))
+            frames.append(self._model.generate_frame(tokens, mask, pos, temperature, topk, **filters))
         out = []
         codes_all = torch.stack(frames, 2).long()                                                    # [B, K, T]
         for b in range(B):
@@ -310,14 +342,17 @@ class Generator:
         return out[0], out[1]
 
     def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
-              row_sampling: bool = False):
+              row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0):
         """A running batch (csm/serving.py): ``server.submit(text, speaker, context, adapter=None, seed=None,
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
         chunk by chunk and leave at their own EOS - and ``server.run()`` iterates until all are done.  Temperature and top-k
         belong to the server - unless ``row_sampling=True``: then they are the requests' defaults, ``submit`` / ``conversation``
         / ``say`` take ``temperature=`` and ``topk=`` of their own (say > conversation > server), each slot samples with its
-        request's pair through the rows sampler, and one captured frame serves every mix (a change never recaptures).  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
+        request's pair through the rows sampler, and one captured frame serves every mix (a change never recaptures).  With
+        ``row_filters=True`` as well (it needs ``row_sampling``), ``top_p`` / ``min_p`` are the requests' default nucleus and min-p
+        cuts and ``submit`` / ``conversation`` / ``say`` take their own (``top_p=``, ``min_p=``); every draw then goes through the
+        filtered rows sampler, and a request at 1.0 / 0.0 has the codes it has without ``row_filters``.  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
         speaker)`` queues its next turn as a request, ``conv.add(Segment)`` (or ``conv.hear(speaker)`` -> ``feed`` / ``end``, encoded
         while it is spoken) is the other party's turn; its KV history is parked
         between turns and resumed into any free slot, so more conversations than slots can be open.  It takes over the model's caches like any ``generate*`` call (open streams and older servers are
@@ -326,7 +361,7 @@ class Generator:
         ``feed``; N >= 1 gives the server one rows encoder of N slots - ``feed`` only buffers, ``server.hear_step()`` (called by
         ``step()``) encodes all open heard turns in one batched step, ``server.end_heard([(turn, text), ...])`` ends several."""
         from .serving import BatchServer
-        return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling)
+        return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p)
 
     def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error"):
         """A multi-turn dialogue that keeps its KV cache between turns (csm/conversation.py): ``conv.generate(text, speaker)`` /

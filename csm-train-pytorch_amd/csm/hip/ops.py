@@ -699,6 +699,21 @@ def sample_topk_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, V=No
     return out_i32
 
 
+def sample_filtered_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, top_p_f32, min_p_f32, V=None):
+    """``sample_topk_rows`` with row r's nucleus and min-p thresholds read from ``top_p_f32[r]`` / ``min_p_f32[r]`` on the device
+    (``csm_sample_filtered_rows``; a row with 1.0 / 0.0 is ``sample_topk_rows``' row)."""
+    rows = logits_f32.shape[0]
+    V = V or logits_f32.shape[1]
+    assert q_f32.is_contiguous() and q_f32.shape == (rows, V)
+    assert topk_i32.dtype == torch.int32 and topk_i32.is_contiguous() and topk_i32.numel() == rows
+    for a in (temperature_f32, top_p_f32, min_p_f32):
+        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == rows
+    check(lib.csm_sample_filtered_rows(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0),
+                                       topk_i32.data_ptr(), temperature_f32.data_ptr(), top_p_f32.data_ptr(),
+                                       min_p_f32.data_ptr(), _stream()), "csm_sample_filtered_rows")
+    return out_i32
+
+
 def rvq_encode(x_f32, codebooks_f32, codes_i64, n_semantic=1):
     T, D = x_f32.shape
     K, Cn, D2 = codebooks_f32.shape

@@ -140,6 +140,25 @@ def sample_topk_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torc
     return out.reshape(-1, 1)
 
 
+def sample_filtered_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor,
+                         min_p: torch.Tensor, q: Optional[torch.Tensor] = None):
+    """``sample_topk_rows`` with a nucleus (``top_p`` float32 [B], in (0, 1]) and a min-p threshold (``min_p`` float32 [B], in
+    [0, 1]) per row, applied inside the kernel (``csm_sample_filtered_rows``) to the values top-k kept: first min-p (drop
+    p_i < min_p * p_max), then the nucleus over what is left (a token stays while the probability of the strictly larger values
+    is below top_p).  Row b with 1.0 / 0.0 is ``sample_topk_rows``' row b, bit for bit.  Returns int32 [B, 1]."""
+    lg2 = logits.float()
+    if lg2.dim() != 2:
+        raise ValueError(f"sample_filtered_rows takes [B, V] logits, got {tuple(logits.shape)}")
+    if lg2.stride(1) != 1:
+        lg2 = lg2.contiguous()
+    if q is None:
+        q = torch.empty(lg2.shape, dtype=torch.float32, device=lg2.device).exponential_(1)
+    q = q.reshape(lg2.shape).float().contiguous()
+    out = torch.empty(lg2.shape[0], dtype=torch.int32, device=lg2.device)
+    ops.sample_filtered_rows(lg2, q, out, topk, temperature, top_p, min_p, V=lg2.shape[1])
+    return out.reshape(-1, 1)
+
+
 @dataclass
 class ModelArgs:
     """Arguments for the CSM model (reference model.py:99-107)."""
@@ -463,10 +482,12 @@ class Model(nn.Module):
 
     @torch.no_grad()
     def generate_frame(self, tokens: torch.Tensor, tokens_mask: torch.Tensor, input_pos: torch.Tensor, temperature: float,
-                       topk: int, noise: Optional[List[torch.Tensor]] = None, adapters=None) -> torch.Tensor:
+                       topk: int, noise: Optional[List[torch.Tensor]] = None, adapters=None, top_p=None,
+                       min_p=None) -> torch.Tensor:
         """Reference model.py:140-195: one frame of K codes, [B, K] int32.  ``noise`` (K tensors [B, V_a] of Exp(1)
         draws) pins the sampler for parity tests.  ``adapters``: a LoRAState or None per batch row (csm/lora_bank.py), read
         on a generation's first call.  ``temperature`` / ``topk``: two numbers, a sequence of B values for either one, or None for
-        both - one pair per row through the rows sampler (``Engine.generate_frame``)."""
+        both - one pair per row through the rows sampler (``Engine.generate_frame``).  ``top_p`` / ``min_p``: None (not named), or
+        a number / B values for either one - the filtered rows sampler (``sample_filtered_rows``)."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
-        return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise, adapters)
+        return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise, adapters, top_p, min_p)

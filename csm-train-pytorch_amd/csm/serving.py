@@ -24,6 +24,13 @@ sampler (``csm_sample_topk_rows``), which reads ``row_topk[b]`` / ``row_temperat
 then serves every mix of parameters - a greedy row (``topk=1``) next to a 0.9 / 50 one - and a change never recaptures.  A row's
 codes are those of a default server made with that row's pair (the same bits).  A free row keeps the pair of its last request.
 
+Filters.  ``serve(row_sampling=True, row_filters=True, top_p=1.0, min_p=0.0)`` adds a nucleus (top-p) and a min-p cut per request,
+resolved and checked like the pair (``submit`` / ``conversation`` / ``say`` take ``top_p`` and ``min_p``; say > conversation >
+server's) and written at admission (``DecodeState.set_row_filters``).  The server makes the two filter buffers before its first
+capture, so every draw goes through the filtered rows sampler (``csm_sample_filtered_rows``): min-p, then the nucleus, inside the
+sampler's one launch, on what top-k kept.  A row at (1.0, 0.0) skips both and has the codes of a ``row_sampling`` server; a change
+of any row's four parameters replays the same captured frame.  Without ``row_filters`` nothing here is touched.
+
 Multi-turn conversations (``BatchServer.conversation`` -> ``ServedConversation``) outlive their slot.  A conversation holds a
 slot only while it speaks: at the end of the chunk in which its turn ended the K / V of its history positions are parked
 (``DecodeState.park_row``: one copy, base + kept frames - what the row sampled after EOS or after its length limit is not
@@ -58,15 +65,17 @@ from typing import Iterator, List, Optional, Tuple
 import torch
 
 from .conversation import OVERFLOW, HeardTurn, open_heard_turn
-from .engine import DecodeState, check_sampling
+from .engine import DecodeState, check_filters, check_sampling
 
 
 class Request:
     """One utterance of a ``BatchServer``: its audio arrives in ``chunks`` while it holds a slot; ``done`` once it has ended."""
 
-    def __init__(self, rid, text, speaker, adapter, seed, max_audio_frames, tokens, mask, device, temperature=None, topk=None):
+    def __init__(self, rid, text, speaker, adapter, seed, max_audio_frames, tokens, mask, device, temperature=None, topk=None,
+                 top_p=1.0, min_p=0.0):
         self.id, self.text, self.speaker, self.adapter, self.seed = rid, text, speaker, adapter, seed
         self.temperature, self.topk = temperature, topk      # resolved: what it is sampled with
+        self.top_p, self.min_p = top_p, min_p                # (likewise; 1.0 / 0.0 on a server without row_filters)
         self.max_audio_frames = max_audio_frames
         self.slot: Optional[int] = None          # the slot it holds (None while queued and after it ended)
         self.done = False
@@ -123,12 +132,13 @@ class ServedConversation:
     ``cached`` mean what they mean on ``Conversation`` and the history has its layout: per turn the text frames, the audio frames,
     one all-zero EOS frame; a spoken turn's frames are the sampled codes; the EOS frame always enters with the next feed."""
 
-    def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None):
+    def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None, top_p=None, min_p=None):
         if on_overflow not in OVERFLOW:
             raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
         self._srv, self._gen = server, server._gen
         self.adapter, self.seed, self._on_overflow = adapter, seed, on_overflow
         self.temperature, self.topk = server._sampling("conversation", temperature, topk)      # its turns' defaults, resolved
+        self.top_p, self.min_p = server._filters("conversation", top_p, min_p)
         K1 = server._K + 1
         self._tokens = torch.zeros(0, K1, dtype=torch.long, device=self._gen.device)
         self._mask = torch.zeros(0, K1, dtype=torch.bool, device=self._gen.device)
@@ -209,14 +219,15 @@ class ServedConversation:
 
     @torch.inference_mode()
     def say(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: Optional[float] = None,
-            topk: Optional[int] = None) -> Request:
+            topk: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None) -> Request:
         """Queue the next spoken turn; its audio streams through ``step()`` / ``run()`` like any request's.  The length rule
         counts ``chunk_frames - 1`` frames beyond ``max_audio_length_ms``: a conversation's row samples to the end of its last
         chunk (module docstring), and that must fit the cache - it raises here, not in ``step``.  ``temperature`` / ``topk``
-        (``row_sampling`` servers): this turn's, over the conversation's."""
+        (``row_sampling`` servers) and ``top_p`` / ``min_p`` (``row_filters`` servers): this turn's, over the conversation's."""
         self._idle("say")
         srv = self._srv
         temperature, topk = srv._sampling("say", temperature, topk, (self.temperature, self.topk))
+        top_p, min_p = srv._filters("say", top_p, min_p, (self.top_p, self.min_p))
         max_audio_frames = int(max_audio_length_ms / 80)
         if max_audio_frames < 1:
             raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
@@ -226,7 +237,7 @@ class ServedConversation:
         feed_m = torch.cat([self._mask[self._cached:], tm.bool().to(self._mask.device)], 0)
         self._push(tt.long(), tm.bool())
         req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device,
-                      temperature, topk)
+                      temperature, topk, top_p, min_p)
         req._conv, req._base = self, self._tokens.shape[0]
         srv._next_id += 1
         srv._queue.append(req)
@@ -261,10 +272,16 @@ class ServedConversation:
 class BatchServer:
     """``Generator.serve``: see the module docstring.  Without ``row_sampling`` temperature and top-k belong to the server - they
     are launch scalars of the sampler and the key of the captured frame graph.  With it they are the defaults of the requests,
-    which may bring their own: the rows sampler reads each slot's pair from device memory and the graph's key is (None, None)."""
+    which may bring their own: the rows sampler reads each slot's pair from device memory and the graph's key is (None, None).
+    ``row_filters`` (needs ``row_sampling``): ``top_p`` / ``min_p`` are the requests' default filters and requests may bring their
+    own; every draw goes through the filtered rows sampler."""
 
     def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
-                 row_sampling: bool = False):
+                 row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0):
+        if row_filters and not row_sampling:
+            raise ValueError("serve(row_filters=True) needs row_sampling=True: top-p / min-p live in the rows sampler")
+        if not row_filters and not (top_p == 1.0 and min_p == 0.0):
+            raise ValueError(f"top_p={top_p!r} / min_p={min_p!r} need a server made with serve(row_filters=True) (and row_sampling=True)")
         if int(slots) != slots or not 1 <= slots <= 16:
             raise ValueError(f"slots must be an integer in 1..16, got {slots!r}")
         if int(hear_slots) != hear_slots or not 0 <= hear_slots <= 16:
@@ -282,6 +299,8 @@ class BatchServer:
         self.row_sampling = bool(row_sampling)
         if self.row_sampling:                            # (the requests' defaults: held to the requests' rule, before anything is taken over)
             self.temperature, self.topk = check_sampling(temperature, topk, gen._model.args.audio_vocab_size)
+        self.row_filters = bool(row_filters)
+        self.top_p, self.min_p = check_filters(top_p, min_p) if self.row_filters else (1.0, 0.0)
         gen._run += 1                                    # takes over the model's caches, as generate_batch does
         self._run = gen._run
         self._model.reset_caches()
@@ -298,6 +317,9 @@ class BatchServer:
         if self.row_sampling:
             for b in range(self.slots):                  # every row starts with a valid pair: the sampler runs on all of them
                 self._state.set_row_sampling(b, self.temperature, self.topk)
+        if self.row_filters:
+            for b in range(self.slots):                  # (before the first capture: the frame holds the filtered sampler)
+                self._state.set_row_filters(b, self.top_p, self.min_p)
         K = self._model.args.audio_num_codebooks
         dev = gen.device
         self._K = K
@@ -328,17 +350,30 @@ class BatchServer:
         return check_sampling(dt if temperature is None else temperature, dk if topk is None else topk,
                               self._model.args.audio_vocab_size)
 
+    def _filters(self, what, top_p, min_p, default=None):
+        """A request's (top_p, min_p), resolved against ``default`` (the server's if None) and held to ``check_filters`` - at the
+        call, so a bad request raises before it queues."""
+        dp, dm = default if default is not None else (self.top_p, self.min_p)
+        if top_p is None and min_p is None:
+            return dp, dm
+        if not self.row_filters:
+            raise ValueError(f"{what}: top_p / min_p per request need a server made with serve(row_filters=True) (with "
+                             f"row_sampling=True; this server samples without filters)")
+        return check_filters(dp if top_p is None else top_p, dm if min_p is None else min_p)
+
     def _sample_args(self):
         """What ``serve_first`` / ``serve_frame`` get: the server's two numbers, or None, None (each row's own pair)."""
         return (None, None) if self.row_sampling else (self.temperature, self.topk)
 
     def submit(self, text: str, speaker: int, context, adapter: Optional[str] = None, seed: Optional[int] = None,
-               max_audio_length_ms: float = 90_000, temperature: Optional[float] = None, topk: Optional[int] = None) -> Request:
+               max_audio_length_ms: float = 90_000, temperature: Optional[float] = None, topk: Optional[int] = None,
+               top_p: Optional[float] = None, min_p: Optional[float] = None) -> Request:
         """Queue one utterance; it takes a slot at the next chunk boundary that has a free one.  The prompt is tokenised here, so
         the reference's length rule ("Inputs too long ...") and an unknown adapter name raise here.  ``temperature`` / ``topk``
-        (``row_sampling`` servers): this request's, over the server's."""
+        (``row_sampling`` servers) and ``top_p`` / ``min_p`` (``row_filters`` servers): this request's, over the server's."""
         self._check()
         temperature, topk = self._sampling("submit", temperature, topk)
+        top_p, min_p = self._filters("submit", top_p, min_p)
         if adapter is not None and adapter not in self._bank:
             known = self._gen._bank is not None and adapter in self._gen._bank.entries
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})" +
@@ -349,22 +384,24 @@ class BatchServer:
         with torch.inference_mode():
             tokens, mask, _ = self._gen._prompt(text, speaker, list(context), max_audio_frames)
         req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device,
-                      temperature, topk)
+                      temperature, topk, top_p, min_p)
         self._next_id += 1
         self._queue.append(req)
         return req
 
     def conversation(self, context=(), adapter: Optional[str] = None, seed: Optional[int] = None,
                      on_overflow: str = "error", temperature: Optional[float] = None,
-                     topk: Optional[int] = None) -> ServedConversation:
+                     topk: Optional[int] = None, top_p: Optional[float] = None,
+                     min_p: Optional[float] = None) -> ServedConversation:
         """A multi-turn dialogue on this server: ``conv.say(text, speaker, max_audio_length_ms)`` queues its next spoken turn (a
         ``Request``), ``conv.add(Segment)`` is the other party's turn, ``conv.close()`` drops its parked cache.  ``adapter`` and
         ``seed`` hold for the whole conversation; ``on_overflow`` as for ``Generator.conversation``.  ``temperature`` / ``topk``
-        (``row_sampling`` servers): the defaults of its turns, over the server's; ``say`` may name a turn's own."""
+        (``row_sampling`` servers) and ``top_p`` / ``min_p`` (``row_filters`` servers): the defaults of its turns, over the
+        server's; ``say`` may name a turn's own."""
         self._check()
         if adapter is not None and adapter not in self._bank:
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})")
-        return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk)
+        return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk, top_p, min_p)
 
     @property
     def queued(self) -> int:
@@ -458,6 +495,8 @@ class BatchServer:
             st.set_row_adapter(b, self._bank[req.adapter] if req.adapter is not None else None)
             if self.row_sampling:
                 st.set_row_sampling(b, req.temperature, req.topk)
+            if self.row_filters:
+                st.set_row_filters(b, req.top_p, req.min_p)
             if conv is not None and conv.seed is not None:
                 if conv._noise is None:
                     conv._noise = st.new_row_generator(conv.seed)

@@ -79,17 +79,61 @@ __device__ __forceinline__ int dpp_row_shr_add(int v, int ctrl_n) {   // v + (v 
 // positive number (zero, negative, NaN, inf) counts as 1.  The one-wave / block-wide choice stays block-uniform: a workgroup
 // is one row.
 struct SampleScalars {
+    static constexpr bool FILTERS = false;
     int topk;
     float temperature;
     __device__ __forceinline__ int k(int, int) const { return topk; }
     __device__ __forceinline__ float t(int) const { return temperature; }
 };
 struct SampleRows {
+    static constexpr bool FILTERS = false;
     const int* topk;
     const float* temperature;
     __device__ __forceinline__ int k(int row, int V) const { const int v = topk[row]; return v < 1 ? 1 : (v > V ? V : v); }
     __device__ __forceinline__ float t(int row) const { const float v = temperature[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
 };
+// SampleFiltered (csm_sample_filtered_rows): SampleRows plus a nucleus (top-p) and a min-p threshold per row, two more
+// block-uniform loads issued with the other two.  With v = x / temperature, e_i = exp(v_i - max v) and K today's kept set:
+//   M = { i in K : e_i >= min_p };  N = { i in M : sum over j in M with v_j > v_i of e_j  <  top_p * sum over M of e_j };
+// the finish (log_softmax -> softmax -> argmax p / q) then runs over N with today's expressions.  Every rule is a threshold on
+// the value - equal values stay or go together and no index enters - so N is never empty (nothing lies above the largest).
+// A top_p outside (0, 1] counts as 1, a min_p outside [0, 1] as 0 (NaN is outside both).  A row with (1, 0) skips all of it
+// (block-uniform) and is the SampleRows kernel.  Mass is summed as 64-bit fixed point, e_i * 2^40 truncated: integer sums do
+// not depend on their order, so neither the butterfly nor the LDS atomics below can change a kept set from run to run.
+//  * at most 64 kept values (the common case after top-k): wave 0 has them compacted, one per lane; every lane walks the
+//    others' (value, mass) pairs with readlane and adds up the mass strictly above its own value.
+//  * more: a second 8-bit radix select over the same integer keys, with the mass instead of a count added into 64-bit LDS
+//    histograms (ds_add_u64); the wanted mass tau = ceil(top_p * S) plays the part of k.  The digit's bin is the first from the
+//    top whose inclusive mass reaches tau: the bins above it are kept whole, the ones below dropped whole, and tau minus the mass
+//    above (exact in integers) is wanted inside it.  Four passes give the last kept key; rows that min-p drops get key 0, which
+//    no threshold keeps.  The set is then counted again and takes whichever finish fits it.
+// Error: |kernel's sum P_j - exact| <= 2 (V 2^-40 + (2 + dbar) 2^-24), dbar the P-weighted mean of
+// max v - v_j; |kernel's e_i / exact - 1| <= (2 + max v - v_i) 2^-24.
+struct SampleFiltered {
+    static constexpr bool FILTERS = true;
+    const int* topk;
+    const float* temperature;
+    const float* top_p;
+    const float* min_p;
+    __device__ __forceinline__ int k(int row, int V) const { const int v = topk[row]; return v < 1 ? 1 : (v > V ? V : v); }
+    __device__ __forceinline__ float t(int row) const { const float v = temperature[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
+    __device__ __forceinline__ float p(int row) const { const float v = top_p[row]; return (v > 0.f && v <= 1.f) ? v : 1.f; }
+    __device__ __forceinline__ float m(int row) const { const float v = min_p[row]; return (v >= 0.f && v <= 1.f) ? v : 0.f; }
+};
+constexpr float SMP_MASS_ONE = 1099511627776.f;                          // 2^40: the fixed-point image of e = 1
+__device__ __forceinline__ unsigned long long smp_mass(float e) { return (unsigned long long)(e * SMP_MASS_ONE); }   // (exact product, truncated)
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned long long smp_tau(unsigned long long S, float top_p) {   // smallest integer >= top_p * S (S < 2^53: exact)
+    return (unsigned long long)ceil((double)S * (double)top_p);
+}
 template <int NPT, class Params>
 __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restrict__ logits, const float* __restrict__ q,
                                                           int* __restrict__ out, int V, int ldl, const Params prm) {
@@ -99,6 +143,8 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
     const int row = blockIdx.x;
     const int topk = prm.k(row, V);
     const float temperature = prm.t(row);
+    float top_p = 1.f, min_p = 0.f;
+    if constexpr (Params::FILTERS) { top_p = prm.p(row); min_p = prm.m(row); }
     const float* x = logits + (size_t)row * ldl;
     const float* qq = q + (size_t)row * V;
     const int lane = threadIdx.x & 63;
@@ -192,8 +238,95 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
     if (lane == 63) wtot[threadIdx.x >> 6] = pre;
     __syncthreads();
     const int w_ = threadIdx.x >> 6;
-    const int before = (w_ > 0 ? wtot[0] : 0) + (w_ > 1 ? wtot[1] : 0) + (w_ > 2 ? wtot[2] : 0);
-    const int total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    int before = (w_ > 0 ? wtot[0] : 0) + (w_ > 1 ? wtot[1] : 0) + (w_ > 2 ? wtot[2] : 0);
+    int total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    bool wave_filters = false;                              // steps 2 and 3 still to be done, by the one-wave finish
+    if constexpr (Params::FILTERS) {
+        wave_filters = top_p < 1.f || min_p > 0.f;          // (block-uniform; false: the SampleRows kernel from here on)
+        if (wave_filters && total > 64) {
+            // ---- more than 64 kept values: min-p and the nucleus block-wide, on the keys in registers
+            __shared__ __attribute__((aligned(16))) unsigned long long mhist[4][256];
+            __shared__ unsigned long long sred[4];
+            wave_filters = false;
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) mhist[ps][threadIdx.x] = 0ull;
+            const float gtop = block_max(tmax, fred);
+            if (prefix == 0u) prefix = 1u;                  // (no value has key 0: the same set, and key 0 now means dropped)
+            unsigned long long sm = 0ull;
+#pragma unroll
+            for (int j = 0; j < NPT; ++j) {
+                const int c = threadIdx.x + 256 * j;
+                if (c < V && key[j] >= prefix) {
+                    const float e = expf(val[j] - gtop);
+                    if (e >= min_p) sm += smp_mass(e);
+                    else key[j] = 0u;                       // dropped by min-p: below every threshold (prefix >= 1)
+                }
+            }
+            if (top_p < 1.f) {                              // (block-uniform)
+                sm = wave_sum_u64(sm);
+                if (lane == 0) sred[w_] = sm;
+                __syncthreads();                            // the wave sums, and the zeroed histograms
+                unsigned long long trem = smp_tau(sred[0] + sred[1] + sred[2] + sred[3], top_p);   // mass still wanted
+                uint32_t mprefix = 0u;
+#pragma unroll 1
+                for (int ps = 0; ps < 4; ++ps) {
+                    const int shift = 24 - 8 * ps;
+#pragma unroll
+                    for (int j = 0; j < NPT; ++j) {
+                        const int c = threadIdx.x + 256 * j;
+                        const bool in = c < V && key[j] >= prefix && (ps == 0 || (key[j] >> (shift + 8)) == (mprefix >> (shift + 8)));
+                        if (in) atomicAdd(&mhist[ps][(key[j] >> shift) & 255u], smp_mass(expf(val[j] - gtop)));
+                    }
+                    __syncthreads();
+                    // lane l owns bins 252 - 4l .. 255 - 4l, as in the count select; the scan runs from the top bin down
+                    const ulonglong2 hlo = *reinterpret_cast<const ulonglong2*>(&mhist[ps][252 - 4 * lane]);
+                    const ulonglong2 hhi = *reinterpret_cast<const ulonglong2*>(&mhist[ps][254 - 4 * lane]);
+                    const unsigned long long b3 = hhi.y, b2 = hhi.x, b1 = hlo.y, b0 = hlo.x;
+                    const unsigned long long mn = b3 + b2 + b1 + b0;
+                    unsigned long long pr = mn;             // -> mass in my bins and every bin above them
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const unsigned long long y = __shfl_up(pr, o, 64);
+                        if (lane >= o) pr += y;
+                    }
+                    unsigned long long above = pr - mn;
+                    int digit;
+                    if (above + b3 >= trem) digit = 255 - 4 * lane;
+                    else {
+                        above += b3;
+                        if (above + b2 >= trem) digit = 254 - 4 * lane;
+                        else {
+                            above += b2;
+                            if (above + b1 >= trem) digit = 253 - 4 * lane;
+                            else { above += b1; digit = 252 - 4 * lane; }
+                        }
+                    }
+                    const unsigned long long cross = __ballot(pr >= trem);
+                    const int L = cross ? __ffsll((long long)cross) - 1 : 63;          // (never empty: the matching mass is >= trem)
+                    digit = __builtin_amdgcn_readlane(digit, L);
+                    above = readlane_u64(above, L);
+                    mprefix |= (uint32_t)digit << shift;
+                    trem -= above;
+                }
+                prefix = mprefix;                           // the last kept key (>= the top-k threshold: its bin held mass)
+            }
+            // the kept set changed: count it again for the compaction
+            mine = 0;
+#pragma unroll
+            for (int j = 0; j < NPT; ++j) mine += (threadIdx.x + 256 * j < V && key[j] >= prefix) ? 1 : 0;
+            pre = mine;
+            pre = dpp_row_shr_add(pre, 1); pre = dpp_row_shr_add(pre, 2); pre = dpp_row_shr_add(pre, 4); pre = dpp_row_shr_add(pre, 8);
+            {
+                const int t0 = __builtin_amdgcn_readlane(pre, 15), t1 = __builtin_amdgcn_readlane(pre, 31), t2 = __builtin_amdgcn_readlane(pre, 47);
+                pre += (lane >= 16 ? t0 : 0) + (lane >= 32 ? t1 : 0) + (lane >= 48 ? t2 : 0);
+            }
+            __syncthreads();                                // every wave has read the first count
+            if (lane == 63) wtot[w_] = pre;
+            __syncthreads();
+            before = (w_ > 0 ? wtot[0] : 0) + (w_ > 1 ? wtot[1] : 0) + (w_ > 2 ? wtot[2] : 0);
+            total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+        }
+    }
     if (total <= 64) {                                      // (block-uniform)
         int at = before + pre - mine;
 #pragma unroll
@@ -203,9 +336,28 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
         }
         __syncthreads();
         if (threadIdx.x < 64) {
-            const bool on = lane < total;
-            const float v = on ? cval[lane] : -INFINITY;
+            bool on = lane < total;
+            float v = on ? cval[lane] : -INFINITY;
             const float top = wave_max(v);
+            if constexpr (Params::FILTERS) {
+                if (wave_filters) {                         // steps 2 and 3 on the compacted values, one per lane
+                    const float e = on ? expf(v - top) : 0.f;
+                    on = on && e >= min_p;
+                    const unsigned long long ms = on ? smp_mass(e) : 0ull;
+                    if (top_p < 1.f) {
+                        const unsigned long long tau = smp_tau(wave_sum_u64(ms), top_p);
+                        unsigned long long above = 0ull;    // mass of the values strictly larger than mine
+#pragma unroll 1
+                        for (int j = 0; j < total; ++j) {
+                            const float vj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), j));
+                            const unsigned long long mj = readlane_u64(ms, j);
+                            above += vj > v ? mj : 0ull;
+                        }
+                        on = on && above < tau;
+                    }
+                    v = on ? v : -INFINITY;
+                }
+            }
             const float e1 = on ? expf(v - top) : 0.f;
             const float logsum = logf(wave_sum(e1));
             const float ymax = (top - top) - logsum;
@@ -331,6 +483,18 @@ extern "C" int csm_sample_topk_rows(const float* logits, const float* q, int* ou
     if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleRows>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
     else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleRows>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
     CSM_CHECK_LAUNCH("csm_sample_topk_rows");
+    return 0;
+}
+
+extern "C" int csm_sample_filtered_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
+                                        const float* temperature, const float* top_p, const float* min_p, hipStream_t stream) {
+    CSM_REQUIRE(logits && q && out && topk && temperature && top_p && min_p && rows > 0 && V > 0 && ldl >= V,
+                "csm_sample_filtered_rows: bad arguments");
+    CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "csm_sample_filtered_rows: V=%d exceeds %d", V, 256 * SMP_PER_THREAD);
+    const SampleFiltered prm = {topk, temperature, top_p, min_p};
+    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleFiltered>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleFiltered>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    CSM_CHECK_LAUNCH("csm_sample_filtered_rows");
     return 0;
 }
 

@@ -240,6 +240,18 @@ int csm_sample_topk(const float* logits, const float* q, int* out, int rows, int
  * parameters: write the two arrays between replays. */
 int csm_sample_topk_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
                          const float* temperature, csm_stream_t stream);
+/* Per-row nucleus (top-p) and min-p filters (additive, ABI 3): csm_sample_topk_rows with two more DEVICE arrays of `rows` floats.
+ * With v = logits / temperature[r], e_i = exp(v_i - max v) and K the set csm_sample_topk_rows keeps (v_i >= the topk[r]-th
+ * largest, ties included):  M = { i in K : e_i >= min_p[r] }  (p_i >= min_p * p_max);
+ * N = { i in M : sum over j in M with v_j > v_i of e_j  <  top_p[r] * sum over M of e_j }  - a token stays while the mass of
+ * the strictly larger values is below top_p, so the token that crosses top_p is kept, equal values stay or go together and no
+ * index enters; the largest value always stays.  log_softmax -> softmax -> argmax p / q then run over N.  A row with
+ * top_p = 1 and min_p = 0 writes the index csm_sample_topk_rows writes, for every input.  The kernel bounds what it reads: a
+ * top_p[r] outside (0, 1] counts as 1, a min_p[r] outside [0, 1] as 0 (NaN is outside both), topk / temperature as above - with
+ * finite logits the written index is always in [0, V).  Mass is summed in 64-bit fixed point (quantum 2^-40): the kept set does
+ * not depend on the order of summation and a launch gives the same bits every time (error bound: DESIGN.md section 6). */
+int csm_sample_filtered_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
+                             const float* temperature, const float* top_p, const float* min_p, csm_stream_t stream);
 
 /* ---- K15: batch-1 decode of Model.generate_frame (model.py:161-195) against KV caches ------------------------------ *
  * y[b][n] = sum_k x[b][k] W[n][k] (+ residual[b][n]), B <= 16 (weight-streaming matrix-vector product).  B <= 4: VALU kernels,

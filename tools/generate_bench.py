@@ -12,7 +12,8 @@ and against the same utterances one at a time with their adapter live as model.l
 GEN_FP8=1: decode frames/s with bf16 and with FP8 (weight-only e4m3) decode weights,
 alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in each mode.  GEN_SERVE=1: the running batch (Generator.serve): rows-codec step against single steps, the server step at
 16 rows, the join stall (serve_main).  GEN_SERVE_SAMPLING=1: the rows sampler against the scalar one and the 16-row
-server step with row_sampling off / on (serve_sampling_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
+server step with row_sampling off / on (serve_sampling_main); GEN_SERVE_SAMPLING=filters: the filtered rows sampler (top-p / min-p)
+in four forms and the server step with row_filters off / on (serve_filters_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
 time to the first chunk of turns 1 / 3 / 5 against stateless submits, one append_rows against one-row calls, park / resume, aggregate
 frames/s (serve_conv_main).  GEN_HEAR=1: a 5 s heard turn's last sample to the first chunk of the reply, with
 ``add(Segment)`` against ``hear`` fed during the turn, served (16 slots) and at B = 1 (hear_main), then the batched hearing of
@@ -696,6 +697,88 @@ def serve_sampling_main():
               f"frame (off's own repeats span {(max(meds['off']) - min(meds['off'])) * 1e3:.2f} ms)", flush=True)
 
 
+def serve_filters_main():
+    """GEN_SERVE_SAMPLING=filters: per-request top-p / min-p (Generator.serve(row_sampling=True, row_filters=True)), in the shape of
+    GEN_SERVE_SAMPLING=1.  (a) the sampler alone, 16 rows, V = 2051 in the model's padded logits buffer, four forms: csm_sample_topk
+    at (50, 0.9); csm_sample_topk_rows with that pair in every row; csm_sample_filtered_rows with that pair and (1, 0) in every row
+    (filters off: the block-uniform skip); csm_sample_filtered_rows with mixed values - (50, 0.9) rows with top-p 0.9 / min-p 0.05
+    (the one-wave filter) next to pure-nucleus rows, topk = V with top-p 0.9 (the block-wide filter: a second radix select) - and,
+    shown separately, 16 pure-nucleus rows and 16 one-wave-filter rows.  200 back-to-back launches between two synchronisations,
+    alternated, median (min .. max) of GEN_ROUNDS repeats (default 5).  (b) the steady 16-row server step of GEN_SERVE's setting:
+    row_sampling on without row_filters (the yardstick), row_filters on with (1, 0) everywhere, on with mixed values (four
+    pure-nucleus rows); each leg a fresh server, alternated GEN_ROUNDS times (default 3), per leg the median of 20 steps."""
+    dev = "cuda:0"
+    n = 4
+    V, ld = 2051, 2112
+    g = torch.Generator(device=dev).manual_seed(0)
+    lg = torch.randn(16, ld, device=dev, generator=g) * 2
+    q = torch.empty(16, V, device=dev).exponential_(1, generator=g)
+    out = torch.empty(16, dtype=torch.int32, device=dev)
+
+    def f32(v):
+        return torch.tensor(v, dtype=torch.float32, device=dev)
+
+    def i32(v):
+        return torch.tensor(v, dtype=torch.int32, device=dev)
+    k_eq, t_eq = i32([50] * 16), f32([0.9] * 16)
+    p_off, m_off = f32([1.0] * 16), f32([0.0] * 16)
+    nucleus = [b % 4 == 3 for b in range(16)]                                # four pure-nucleus rows among twelve top-k 50 rows
+    k_mix = i32([V if x else 50 for x in nucleus])
+    p_mix, m_mix = f32([0.9] * 16), f32([0.0 if x else 0.05 for x in nucleus])
+    k_all, m_all = i32([V] * 16), f32([0.05] * 16)
+    legs = {"scalar (50, 0.9)": lambda: ops.sample_topk(lg, q, out, 50, 0.9, V=V),
+            "rows, (50, 0.9) in every row": lambda: ops.sample_topk_rows(lg, q, out, k_eq, t_eq, V=V),
+            "filtered, (50, 0.9) and filters off (1, 0) in every row": lambda: ops.sample_filtered_rows(lg, q, out, k_eq, t_eq, p_off, m_off, V=V),
+            "filtered, mixed (12 rows top-k 50 + top-p 0.9 + min-p 0.05, 4 rows pure nucleus 0.9)":
+                lambda: ops.sample_filtered_rows(lg, q, out, k_mix, t_eq, p_mix, m_mix, V=V),
+            "filtered, one-wave filter in every row (top-k 50, top-p 0.9, min-p 0.05)":
+                lambda: ops.sample_filtered_rows(lg, q, out, k_eq, t_eq, p_mix, m_all, V=V),
+            "filtered, pure nucleus in every row (topk = V, top-p 0.9)":
+                lambda: ops.sample_filtered_rows(lg, q, out, k_all, t_eq, p_mix, m_off, V=V)}
+    rounds = int(os.environ.get("GEN_ROUNDS", 5))
+    res = {name: [] for name in legs}
+    for f in legs.values():
+        _timed(f, 20)
+    for _ in range(rounds):
+        for name, f in legs.items():
+            res[name].append(_timed(f, 200))
+    for name, v in res.items():
+        v.sort()
+        print(f"GEN_SERVE_SAMPLING=filters (a) sampler, 16 rows, V={V}: {name}: median {v[len(v) // 2] * 1e6:.2f} us per launch "
+              f"(min {v[0] * 1e6:.2f}, max {v[-1] * 1e6:.2f}; {rounds} x 200 back-to-back launches)", flush=True)
+    if os.environ.get("GEN_SERVE_PARTS", "ab") == "a":
+        return
+    # ---- (b) the server step
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    codec = make_codec(dev)
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=codec)
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+    mixed = [dict(topk=V, top_p=0.9) if x else dict(top_p=0.9, min_p=0.05) for x in nucleus]
+    modes = {"off (row_sampling only)": None, "on, (1, 0) everywhere": [{}] * 16, "on, mixed": mixed}
+    meds = {name: [] for name in modes}
+    for _ in range(rounds):
+        for name, kws in modes.items():
+            srv = gen.serve(slots=16, chunk_frames=n, row_sampling=True, row_filters=kws is not None)
+            for i in range(16):
+                srv.submit(f"utterance number {i}: {text}", i, ctx, seed=i, max_audio_length_ms=80 * 400, **(kws[i] if kws else {}))
+            _timed(srv.step, 1)                                              # 16 prefills + the first chunk
+            _timed(srv.step, 2)                                              # eager warm-up frame, graph capture
+            steps = sorted(_timed(srv.step, 1) for _ in range(20))
+            meds[name].append(steps[len(steps) // 2])
+    for name, v in meds.items():
+        print(f"GEN_SERVE_SAMPLING=filters (b) server step, 16 rows x {n} frames, row_filters {name}: medians of 20 steps "
+              f"{[round(x * 1e3, 2) for x in v]} ms -> median {sorted(v)[len(v) // 2] * 1e3:.2f} ms, spread of the repeats "
+              f"{(max(v) - min(v)) * 1e3:.2f} ms", flush=True)
+    off = sorted(meds["off (row_sampling only)"])[rounds // 2]
+    for name in ("on, (1, 0) everywhere", "on, mixed"):
+        on = sorted(meds[name])[rounds // 2]
+        print(f"GEN_SERVE_SAMPLING=filters (b) row_filters {name} - off: {(on - off) * 1e3:+.2f} ms per step = {(on - off) * 1e6 / n:+.1f} "
+              f"us per frame (off's own repeats span {(max(meds['off (row_sampling only)']) - min(meds['off (row_sampling only)'])) * 1e3:.2f} ms)",
+              flush=True)
+
+
 def serve_conv_main():
     """GEN_SERVE_CONV=1: conversations on the running batch (BatchServer.conversation) on CSM-1B random init - 16 slots,
     chunk_frames 4, 16 conversations of 6 turns: odd turns spoken (GEN_FRAMES frames, default 24), even turns 5 s of the other
@@ -1040,6 +1123,8 @@ def main():
         return hear_rows_main()
     if os.environ.get("GEN_SERVE_SAMPLING") == "1":
         return serve_sampling_main()
+    if os.environ.get("GEN_SERVE_SAMPLING") == "filters":
+        return serve_filters_main()
     if os.environ.get("GEN_SERVE_CONV") == "1":
         return serve_conv_main()
     if os.environ.get("GEN_SERVE") == "1":
