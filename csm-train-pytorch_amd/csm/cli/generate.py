@@ -49,6 +49,13 @@ def parse_args(argv=None):
                    help="a further line, spoken after --text in the same conversation with the KV cache kept (repeatable)")
     p.add_argument("--next-speaker", type=int, action="append", default=None,
                    help="speaker ID of the corresponding --next-text (repeatable; default: the speaker of --text)")
+    p.add_argument("--on-overflow", type=str, choices=["error", "drop_oldest", "shift"], default="error",
+                   help="--next-text / --serve-file conversations, when history + line + max audio reach the model's length: error "
+                        "(default), drop_oldest (drop the oldest turns, prefill the rest again) or shift (drop them and slide the "
+                        "KV cache: nothing is prefilled again)")
+    p.add_argument("--keep-turns", type=int, default=0,
+                   help="with --on-overflow drop_oldest / shift: leading turns (the voice prompt of --context-*) that are never "
+                        "dropped (default 0)")
     p.add_argument("--serve-file", type=str, default=None,
                    help="JSON-lines file of utterances {\"text\", \"speaker\", \"adapter\"?: LoRA adapter file, \"seed\"?: int, "
                         "\"temperature\"?: float, \"topk\"?: int, \"top_p\"?: float, \"min_p\"?: float, \"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
@@ -73,6 +80,8 @@ def parse_args(argv=None):
         p.error("--hear-slots must be 0..16")
     if args.hear_slots and args.serve_file is None:
         p.error("--hear-slots goes with --serve-file")
+    if args.keep_turns < 0:
+        p.error("--keep-turns must be >= 0")
     if args.next_speaker and len(args.next_speaker) != len(args.next_text or []):
         p.error("--next-speaker must be given once per --next-text (or not at all)")
     return args
@@ -235,7 +244,8 @@ def serve_to_wavs(generator, args, context, adapter=None):
         elif cid in convs:
             convs[cid][1].append(i)
         else:
-            convs[cid] = [server.conversation(context=context, adapter=ln["adapter"] or adapter, seed=ln["seed"]), [i]]
+            convs[cid] = [server.conversation(context=context, adapter=ln["adapter"] or adapter, seed=ln["seed"],
+                                              on_overflow=args.on_overflow, keep_turns=args.keep_turns), [i]]
             say(cid)
     while server.queued or server.active:
         for req, _, done in server.step():
@@ -260,7 +270,7 @@ def converse_to_wav(generator, args, speaker_id, context, adapter=None):
     converts them."""
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     lines = [(args.text, speaker_id)] + list(zip(args.next_text, args.next_speaker or [speaker_id] * len(args.next_text)))
-    conv = generator.conversation(context=context, adapter=adapter)
+    conv = generator.conversation(context=context, adapter=adapter, on_overflow=args.on_overflow, keep_turns=args.keep_turns)
     kw = dict(max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature, topk=args.topk, top_p=args.top_p,
               min_p=args.min_p)
     t0 = time.perf_counter()

@@ -15,7 +15,38 @@ import torch
 
 from .engine import DecodeState
 
-OVERFLOW = ("error", "drop_oldest")
+OVERFLOW = ("error", "drop_oldest", "shift")
+
+
+def check_keep_turns(keep_turns) -> int:
+    """``keep_turns`` of both conversation classes: an integer >= 0 (bool is refused: it is not a count)."""
+    if isinstance(keep_turns, bool) or not isinstance(keep_turns, int) or keep_turns < 0:
+        raise ValueError(f"keep_turns must be an integer >= 0, got {keep_turns!r}")
+    return keep_turns
+
+
+def fit_history(conv, n_new: int, limit: int):
+    """``_fit`` of both conversation classes, the part they share.  The reference's length rule (generator.py:168-170) on history
+    + new text: ``drop_oldest`` and ``shift`` drop whole turns, the oldest first AFTER the ``keep_turns`` leading ones (the
+    voice prompt), until it holds.  Raises the reference's error - with nothing changed - when it cannot.  Returns None when
+    nothing had to go; else (head, gone): positions ``head .. head+gone-1`` of the OLD history were cut out of ``_tokens`` /
+    ``_mask`` / ``_turns``; what becomes of the cache is the caller's."""
+    L = conv._tokens.shape[0]
+    if L + n_new < limit:
+        return None
+    first = min(conv._keep_turns, len(conv._turns))
+    drop, left = first, L
+    if conv._on_overflow != "error":
+        while drop < len(conv._turns) and left + n_new >= limit:
+            left -= conv._turns[drop]
+            drop += 1
+    if left + n_new >= limit:
+        raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
+    head, gone = sum(conv._turns[:first]), L - left
+    conv._tokens = torch.cat([conv._tokens[:head], conv._tokens[head + gone:]], 0) if head else conv._tokens[gone:]
+    conv._mask = torch.cat([conv._mask[:head], conv._mask[head + gone:]], 0) if head else conv._mask[gone:]
+    conv._turns = conv._turns[:first] + conv._turns[drop:]
+    return head, gone
 
 
 class _Turn:
@@ -130,9 +161,10 @@ class Conversation:
     ``reset()`` - the history is kept and prefilled again by the next turn.
     """
 
-    def __init__(self, gen, context=(), adapter: Optional[str] = None, on_overflow: str = "error"):
+    def __init__(self, gen, context=(), adapter: Optional[str] = None, on_overflow: str = "error", keep_turns: int = 0):
         if on_overflow not in OVERFLOW:
             raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
+        self._keep_turns = check_keep_turns(keep_turns)
         self._gen, self._m = gen, gen._model
         self._ads = gen._resolve_adapters([adapter])
         self._on_overflow = on_overflow
@@ -197,21 +229,20 @@ class Conversation:
         self._turns.append(t.shape[0])
 
     def _fit(self, n_new: int, max_audio_frames: int):
-        """The reference's length rule (generator.py:168-170) on history + new text; ``drop_oldest`` drops whole leading turns
-        until it holds - cached keys are rotated for their positions and cannot slide, so what is kept is prefilled again."""
-        limit = self._m.bb.max_seq_len - max_audio_frames
-        if self._tokens.shape[0] + n_new < limit:
+        """The reference's length rule on history + new text (``fit_history``).  Under ``drop_oldest`` what is kept is prefilled
+        again.  Under ``shift`` the cache slides instead: ONE ``DecodeState.shift_row`` takes the cut's cached positions out and
+        rotates the keys behind them back (cut positions that were only pending just leave the pending tokens), so the turn is
+        fed by ``append`` like any other - unless nothing cached is left, which is ``drop_oldest``."""
+        cut = fit_history(self, n_new, self._m.bb.max_seq_len - max_audio_frames)
+        if cut is None:
             return
-        drop, left = 0, self._tokens.shape[0]
-        if self._on_overflow == "drop_oldest":
-            while drop < len(self._turns) and left + n_new >= limit:
-                left -= self._turns[drop]
-                drop += 1
-        if left + n_new >= limit:
-            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
-        cut = self._tokens.shape[0] - left
-        self._tokens, self._mask, self._turns = self._tokens[cut:], self._mask[cut:], self._turns[drop:]
-        self._cached = 0
+        head, gone = cut
+        out = min(self._cached, head + gone) - head                # cached positions among the cut ones
+        if self._on_overflow != "shift" or self._cached - max(out, 0) < 1:
+            self._cached = 0
+        elif out > 0:
+            self._state.shift_row(0, head, out)
+            self._cached -= out
 
     # ---- a spoken turn -----------------------------------------------------------------------------------------------------
     @contextmanager

@@ -1565,6 +1565,28 @@ class DecodeState:
         self.bb.pos[b] = length - 1
         self.row_pos[b] = length - 1
 
+    def shift_parked(self, parked, keep: int, drop: int):
+        """A parked history (``park_row``) without its positions ``keep .. keep+drop-1``: a new tensor of ``length - drop``
+        positions whose keys behind the gap are rotated back by ``drop`` positions (``ops.kv_shift``, one launch) - the context
+        shift that lets a conversation forget turns without prefilling the kept ones again.  Touches nothing of the state."""
+        kv = self.bb.kv
+        if parked.dim() != 5 or parked.shape[:3] != (kv.shape[0], 2, kv.shape[3]) or parked.shape[4] != kv.shape[5] or \
+                parked.dtype != kv.dtype:
+            raise ValueError(f"shift_parked: {tuple(parked.shape)} {parked.dtype} is not a parked history of this model's backbone")
+        keep, drop, length = int(keep), int(drop), parked.shape[3]
+        if not (drop >= 1 and keep >= 0 and keep + drop <= length and length - drop >= 1):
+            raise ValueError(f"shift_parked: keep {keep} + drop {drop} of {length} positions (at least one is dropped and one is left)")
+        return ops.kv_shift(parked.contiguous(), self.e.m.rope_table("backbone"), keep, drop)
+
+    def shift_row(self, b, keep: int, drop: int):
+        """Row ``b`` forgets its positions ``keep .. keep+drop-1``: ``park_row`` of all it holds, ``shift_parked``, ``resume_row``
+        (which sets the device position and the host mirror to the new last position).  The other rows, the depth decoder's
+        caches and the captured frame graph are not touched."""
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        self.resume_row(b, self.shift_parked(self.park_row(b, self.row_pos[b] + 1), keep, drop))
+
     def truncate(self, length: int):
         """Forget every position from ``length`` on (1 <= length <= cur + 1): every row's device position and host mirror move
         back to ``length - 1``.  Nothing is cleared - cache rows past the position are never read and the next step overwrites them."""

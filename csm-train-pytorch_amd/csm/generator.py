@@ -363,15 +363,18 @@ class Generator:
         from .serving import BatchServer
         return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p)
 
-    def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error"):
+    def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error",
+                     keep_turns: int = 0):
         """A multi-turn dialogue that keeps its KV cache between turns (csm/conversation.py): ``conv.generate(text, speaker)`` /
         ``conv.generate_stream(...)`` speak the next line with every earlier turn as context, ``conv.add(Segment)`` adds the
         other party's turn - or ``turn = conv.hear(speaker)``, ``turn.feed(audio)`` as the audio arrives and ``turn.end(text)``,
         which Mimi-encodes the turn while it is spoken (``HeardTurn``).  ``adapter``: a bank adapter name for the whole conversation.  ``on_overflow``: ``"error"`` raises
         the reference's "Inputs too long" error when history + line + max_audio_frames reach max_seq_len, ``"drop_oldest"``
-        drops whole leading turns and prefills what is left."""
+        drops whole turns - the oldest first, after the ``keep_turns`` leading ones (the voice prompt), which always stay - and
+        prefills what is left; ``"shift"`` drops the same turns but keeps the cache: the kept keys are rotated back to their new
+        positions (``DecodeState.shift_row``), nothing is prefilled again and the turn is appended as any other."""
         from .conversation import Conversation
-        return Conversation(self, context or [], adapter, on_overflow)
+        return Conversation(self, context or [], adapter, on_overflow, keep_turns)
 
     def save_wav(self, path: str, audio: torch.Tensor):
         """16-bit PCM writer (torchaudio is not available in this image)."""

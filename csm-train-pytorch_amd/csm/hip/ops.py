@@ -671,6 +671,20 @@ def kv_append(qkv, kcache, vcache, pos_i32, H, KV, HD):
                             qkv.stride(0), _stream()), "csm_kv_append")
 
 
+def kv_shift(parked, table, keep, drop):
+    """The context shift of a parked history ([layers, 2, KV, len, HD] bf16, ``DecodeState.park_row``): a NEW tensor
+    [layers, 2, KV, len - drop, HD] without positions ``keep .. keep+drop-1`` - the head and every V copied, the keys behind the
+    gap rotated back by ``drop`` positions (csm_kv_shift; row ``drop`` of ``table``, sine negated).  ``parked`` is not touched."""
+    assert parked.dim() == 5 and parked.shape[1] == 2 and parked.dtype == BF16 and parked.is_contiguous()
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] * 2 == parked.shape[4]
+    layers, _, KV, length, HD = parked.shape
+    keep, drop = int(keep), int(drop)
+    out = torch.empty(layers, 2, KV, max(length - drop, 0), HD, dtype=BF16, device=parked.device)
+    check(lib.csm_kv_shift(parked.data_ptr(), out.data_ptr(), table.data_ptr(), table.shape[0], layers, KV, HD, length, keep, drop,
+                           _stream()), "csm_kv_shift")
+    return out
+
+
 def attn_decode(qkv, kcache, vcache, out, pos_i32, H, KV, HD):
     B, _, S_max, _ = kcache.shape
     check(lib.csm_attn_decode(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), pos_i32.data_ptr(), B, H, KV,

@@ -64,7 +64,7 @@ from typing import Iterator, List, Optional, Tuple
 
 import torch
 
-from .conversation import OVERFLOW, HeardTurn, open_heard_turn
+from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, open_heard_turn
 from .engine import DecodeState, check_filters, check_sampling
 
 
@@ -132,9 +132,11 @@ class ServedConversation:
     ``cached`` mean what they mean on ``Conversation`` and the history has its layout: per turn the text frames, the audio frames,
     one all-zero EOS frame; a spoken turn's frames are the sampled codes; the EOS frame always enters with the next feed."""
 
-    def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None, top_p=None, min_p=None):
+    def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None, top_p=None, min_p=None,
+                 keep_turns: int = 0):
         if on_overflow not in OVERFLOW:
             raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
+        self._keep_turns = check_keep_turns(keep_turns)
         self._srv, self._gen = server, server._gen
         self.adapter, self.seed, self._on_overflow = adapter, seed, on_overflow
         self.temperature, self.topk = server._sampling("conversation", temperature, topk)      # its turns' defaults, resolved
@@ -201,21 +203,20 @@ class ServedConversation:
         self._turns.append(t.shape[0])
 
     def _fit(self, n_new: int, max_audio_frames: int):
-        """``Conversation._fit``: the reference's length rule on history + new text; ``drop_oldest`` drops whole leading turns
-        until it holds and what is kept is prefilled again (the parked cache is dropped with them)."""
-        limit = self._srv._model.bb.max_seq_len - max_audio_frames
-        if self._tokens.shape[0] + n_new < limit:
+        """``Conversation._fit``: the reference's length rule on history + new text (``fit_history``).  Under ``drop_oldest`` the
+        parked cache is dropped and what is kept is prefilled again; under ``shift`` ONE ``DecodeState.shift_parked`` takes the
+        cut's cached positions out of the parked cache, so the turn is resumed and fed by the stacked ``append_rows`` like any
+        other - unless nothing cached is left, which is ``drop_oldest``."""
+        cut = fit_history(self, n_new, self._srv._model.bb.max_seq_len - max_audio_frames)
+        if cut is None:
             return
-        drop, left = 0, self._tokens.shape[0]
-        if self._on_overflow == "drop_oldest":
-            while drop < len(self._turns) and left + n_new >= limit:
-                left -= self._turns[drop]
-                drop += 1
-        if left + n_new >= limit:
-            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
-        cut = self._tokens.shape[0] - left
-        self._tokens, self._mask, self._turns = self._tokens[cut:], self._mask[cut:], self._turns[drop:]
-        self._cached, self._parked = 0, None
+        head, gone = cut
+        out = min(self._cached, head + gone) - head                # cached (= parked) positions among the cut ones
+        if self._on_overflow != "shift" or self._parked is None or self._cached - max(out, 0) < 1:
+            self._cached, self._parked = 0, None
+        elif out > 0:
+            self._parked = self._srv._state.shift_parked(self._parked, head, out)
+            self._cached -= out
 
     @torch.inference_mode()
     def say(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: Optional[float] = None,
@@ -392,16 +393,17 @@ class BatchServer:
     def conversation(self, context=(), adapter: Optional[str] = None, seed: Optional[int] = None,
                      on_overflow: str = "error", temperature: Optional[float] = None,
                      topk: Optional[int] = None, top_p: Optional[float] = None,
-                     min_p: Optional[float] = None) -> ServedConversation:
+                     min_p: Optional[float] = None, keep_turns: int = 0) -> ServedConversation:
         """A multi-turn dialogue on this server: ``conv.say(text, speaker, max_audio_length_ms)`` queues its next spoken turn (a
         ``Request``), ``conv.add(Segment)`` is the other party's turn, ``conv.close()`` drops its parked cache.  ``adapter`` and
-        ``seed`` hold for the whole conversation; ``on_overflow`` as for ``Generator.conversation``.  ``temperature`` / ``topk``
+        ``seed`` hold for the whole conversation; ``on_overflow`` / ``keep_turns`` as for ``Generator.conversation`` (``"shift"``
+        slides the parked cache at ``say``).  ``temperature`` / ``topk``
         (``row_sampling`` servers) and ``top_p`` / ``min_p`` (``row_filters`` servers): the defaults of its turns, over the
         server's; ``say`` may name a turn's own."""
         self._check()
         if adapter is not None and adapter not in self._bank:
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})")
-        return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk, top_p, min_p)
+        return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk, top_p, min_p, keep_turns)
 
     @property
     def queued(self) -> int:

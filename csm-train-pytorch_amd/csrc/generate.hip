@@ -1249,6 +1249,39 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict
     }
 }
 
+// A parked history [planes = layers * 2 * KV][len][HD] (K planes before V planes per layer) without its positions keep ..
+// keep+drop-1: the head is copied, the tail moves `drop` positions down and its KEYS are rotated back by drop positions -
+// row `drop` of the RoPE table with the sine negated (rope(k, p + d) -> rope(k, p): a context shift).  Out of place: a thread
+// owns one 16-byte vector (4 interleaved pairs) of one position and walks the planes, so the table row is read once.
+template <int HD>
+__global__ __launch_bounds__(256) void kv_shift_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst,
+                                                       const float* __restrict__ trow, int planes, int KV, int len, int keep,
+                                                       int drop) {
+    constexpr int VPR = HD / 8;                                    // 16-byte vectors per position
+    const int nl = len - drop;
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= (long long)nl * VPR) return;
+    const int p = (int)(v / VPR), d8 = (int)(v - (long long)p * VPR);
+    const bool tail = p >= keep;
+    float c[4] = {1.f, 1.f, 1.f, 1.f}, sn[4] = {0.f, 0.f, 0.f, 0.f};
+    if (tail) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { c[j] = trow[(d8 * 4 + j) * 2]; sn[j] = trow[(d8 * 4 + j) * 2 + 1]; }
+    }
+    const size_t so = (size_t)(tail ? p + drop : p) * HD + d8 * 8, dof = (size_t)p * HD + d8 * 8;
+    for (int hp = blockIdx.y; hp < planes; hp += gridDim.y) {      // hp = (layer * 2 + plane) * KV + kv head
+        U4 u = *reinterpret_cast<const U4*>(src + (size_t)hp * len * HD + so);
+        if (tail && ((hp / KV) & 1) == 0) {                        // a key of the tail
+            float f[8];
+            unpack8(u, f);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rope_rot(f[2 * j], f[2 * j + 1], c[j], -sn[j]);
+            u = pack8(f);
+        }
+        *reinterpret_cast<U4*>(dst + (size_t)hp * nl * HD + dof) = u;
+    }
+}
+
 // one query position against the cache: block per (b, q-head); the scores of all S_max <= 8192 keys live in LDS (the launcher sizes it).
 // table != NULL fuses what used to be two more launches per layer: the new position's q and k heads are rotated here
 // (torchtune RoPE on interleaved pairs, same arithmetic and bf16 rounding as rope_kernel), and the first q-head block of
@@ -2190,6 +2223,30 @@ extern "C" int csm_kv_append(const void* qkv, void* kcache, void* vcache, const 
     hipLaunchKernelGGL(kv_append_kernel, dim3(B), dim3(256), 0, stream, (const bf16_t*)qkv, (bf16_t*)kcache, (bf16_t*)vcache, pos, H,
                        KV, HD, S_max, ld);
     CSM_CHECK_LAUNCH("csm_kv_append");
+    return 0;
+}
+
+extern "C" int csm_kv_shift(const void* src, void* dst, const float* rope_table, int table_rows, int layers, int KV, int HD, int len,
+                            int keep, int drop, hipStream_t stream) {
+    CSM_REQUIRE(src && dst && rope_table, "csm_kv_shift: null pointer");
+    CSM_REQUIRE(HD == 64 || HD == 128, "csm_kv_shift: head_dim %d unsupported", HD);
+    CSM_REQUIRE(layers >= 1 && KV >= 1 && (long long)layers * 2 * KV <= 0x7fffffffLL, "csm_kv_shift: %d layers x %d kv heads", layers, KV);
+    CSM_REQUIRE(drop >= 1 && keep >= 0 && (long long)keep + drop <= len && len - drop >= 1,
+                "csm_kv_shift: keep %d + drop %d of %d positions (needs drop >= 1, keep >= 0, keep + drop <= len, len - drop >= 1)", keep,
+                drop, len);
+    CSM_REQUIRE(drop < table_rows, "csm_kv_shift: drop %d outside the RoPE table (%d rows)", drop, table_rows);
+    const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
+    CSM_REQUIRE((s0 & 15) == 0 && (d0 & 15) == 0, "csm_kv_shift: src and dst must be 16-byte aligned");
+    const int planes = layers * 2 * KV, nl = len - drop;
+    const size_t sbytes = (size_t)planes * len * HD * sizeof(bf16_t), dbytes = (size_t)planes * nl * HD * sizeof(bf16_t);
+    CSM_REQUIRE(s0 + sbytes <= d0 || d0 + dbytes <= s0, "csm_kv_shift: dst overlaps src (the shift is out of place)");
+    const float* trow = rope_table + (size_t)drop * HD;             // row `drop`: HD / 2 (cos, sin) pairs
+    const dim3 grid((unsigned)(((long long)nl * (HD / 8) + 255) / 256), (unsigned)(planes < 65535 ? planes : 65535));
+    if (HD == 64)
+        hipLaunchKernelGGL((kv_shift_kernel<64>), grid, dim3(256), 0, stream, (const bf16_t*)src, (bf16_t*)dst, trow, planes, KV, len, keep, drop);
+    else
+        hipLaunchKernelGGL((kv_shift_kernel<128>), grid, dim3(256), 0, stream, (const bf16_t*)src, (bf16_t*)dst, trow, planes, KV, len, keep, drop);
+    CSM_CHECK_LAUNCH("csm_kv_shift");
     return 0;
 }
 

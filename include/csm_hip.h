@@ -339,6 +339,15 @@ int csm_gemv_attn_at_bf16(const void* qkv, void* kcache, void* vcache, int pos, 
  * back: HD 64 or 128, H % KV == 0, 1 <= S_max <= 8192, ld % 8 == 0 - anything else returns 1 */
 int csm_kv_append(const void* qkv, void* kcache, void* vcache, const int* pos, int B, int H, int KV, int HD, int S_max, int ld,
                   csm_stream_t stream);
+/* Context shift of a parked history (what DecodeState.park_row returns): src bf16 [layers][2][KV][len][HD], K plane before V
+ * plane, -> dst bf16 [layers][2][KV][len - drop][HD] without positions keep .. keep+drop-1.  Positions p < keep and every V are
+ * copied bit for bit; a K at p >= keep is src's K at p + drop with each interleaved pair rotated by -drop positions: (c, s) of
+ * row `drop` of the table csm_rope reads, the sine negated, fp32 with one rounding to bf16 - the key rope(k, p + drop) becomes
+ * rope(k, p).  Out of place: dst must not overlap src.  len / keep / drop are host integers.  Returns 1 (nothing launched) for
+ * a null pointer, HD other than 64 / 128, layers or KV < 1, drop < 1, keep < 0, keep + drop > len, len - drop < 1,
+ * drop >= table_rows, src or dst not 16-byte aligned, overlapping ranges. */
+int csm_kv_shift(const void* src, void* dst, const float* rope_table, int table_rows, int layers, int KV, int HD, int len, int keep,
+                 int drop, csm_stream_t stream);
 /* out[b][h*HD..] = softmax(q . K[0..pos[b]]^T / sqrt(HD)) V   for the single query row in qkv[b].  HD 64 or 128, H % KV == 0,
  * 1 <= S_max <= 8192 (the scores live in LDS), ld % 8 == 0 (16-byte loads from qkv + b * ld) - anything else returns 1 */
 int csm_attn_decode(const void* qkv, const void* kcache, const void* vcache, void* out, const int* pos, int B, int H, int KV,

@@ -22,7 +22,10 @@ the first chunk when all 16 end together, ``end_heard`` against 16 ``end`` calls
 through a Conversation (KV cache kept between turns) and statelessly (generate_stream with the accumulated Segment list - every
 turn encodes and prefills the whole history again), alternated in one process after a warm-up dialogue of each: per spoken turn the
 host time from the call to the first chunk (chunk_frames=2) and the turn's total; plus csm_attn_append alone next to the
-csm_attn_fwd launch that would recompute the whole sequence."""
+csm_attn_fwd launch that would recompute the whole sequence.  GEN_OVERFLOW=1: a conversation past the length limit
+(max_audio_length_ms = 90 000: 923 positions) - time to the first chunk of the overflowing turn under on_overflow="drop_oldest"
+(the kept history is prefilled again) and "shift" (the KV cache slides: csm_kv_shift) next to an in-limit turn, at B = 1 and for
+16 conversations that overflow at one boundary of the 16-slot server, plus csm_kv_shift alone (overflow_main)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -1115,7 +1118,142 @@ def hear_rows_main():
           f"histories {'equal' if same else 'DIFFER'}")
 
 
+def overflow_main():
+    """GEN_OVERFLOW=1: CSM-1B random init.  Every conversation: a 5 s voice prompt (kept: keep_turns=1) and six 5 s turns of the
+    other party, spoken turn 1 (GEN_FRAMES frames, default 24; prefills everything), a 5 s turn, spoken turn 2 (in the limit: the
+    baseline, fed by append), a 5 s turn, spoken turn 3 with max_audio_length_ms = 90 000 - the length rule (923 positions, 920
+    served) drops the two oldest turns after the voice prompt.  The 5 s turns are tokenised and Mimi-encoded once, outside the
+    timed part.  GEN_ROUNDS rounds (default 3) of drop_oldest and shift alternated after one warm-up round of each; ms as median
+    [min..max]; a first chunk counts as arrived when its samples are on the host.
+    (a) B = 1 (Generator.conversation, generate_stream, chunk_frames 2): the call -> first chunk of turns 2 and 3;
+    (b) GEN_SERVE_CONV's setting (16 slots, chunk_frames 4): the step that admits all 16 turns -> first chunk, turns 2 and 3;
+    (c) csm_kv_shift alone at len 900 / drop 200 / keep 100 in CSM-1B geometry, and shift_row (park + shift + resume)."""
+    dev = "cuda:0"
+    NC, n = 16, 4
+    frames = int(os.environ.get("GEN_FRAMES", 24))
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    ms, long_ms = 80 * frames, 90_000
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=make_codec(dev))
+    g = torch.Generator(device=dev).manual_seed(1)
+    with torch.inference_mode():
+        heard = [gen._tokenize_segment(Segment(t % 2, f"turn {t}: and what did the dog do", torch.randn(5 * 24000, device=dev, generator=g) * 0.1))
+                 for t in range(9)]
+    text = "the quick brown fox jumps over the lazy dog"
+    med = lambda xs: sorted(xs)[len(xs) // 2]                                                           # noqa: E731
+    fmt = lambda xs: f"{med(xs):7.1f} [{min(xs):6.1f}..{max(xs):6.1f}]"                                 # noqa: E731
+    MODES = ("drop_oldest", "shift")
+
+    def push(conv, segs):
+        for t, m in segs:
+            conv._push(t.long(), m.bool())                           # (what add() does after its tokenise + Mimi encode)
+
+    def first_chunk(stream, whole):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        it = stream()
+        next(it).cpu()
+        first = time.perf_counter() - t0
+        if whole:
+            for _ in it:
+                pass
+        else:
+            it.close()                                               # abandoned after the first chunk: the turn is settled
+        return first * 1e3
+
+    def solo(mode):
+        torch.manual_seed(0)
+        conv = gen.conversation(on_overflow=mode, keep_turns=1)
+        push(conv, heard[:7])
+        say = lambda ms_, whole: first_chunk(lambda: conv.generate_stream(text, 0, max_audio_length_ms=ms_, chunk_frames=2), whole)  # noqa: E731
+        say(ms, True)
+        push(conv, heard[7:8])
+        fed2 = conv.tokens.shape[0] - conv.cached
+        t2 = say(ms, True)
+        push(conv, heard[8:9])
+        before, cached = conv.tokens.shape[0], conv.cached
+        t3 = say(long_ms, False)
+        return dict(t2=t2, t3=t3, fed2=fed2, before=before, cached=cached, after=conv.tokens.shape[0], turns=len(conv._turns))
+
+    def served(mode):
+        srv = gen.serve(slots=NC, chunk_frames=n)
+
+        def admit(reqs, finish):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = srv.step()
+            torch.cat([a for _, a, _ in out]).cpu()
+            first = time.perf_counter() - t0
+            assert srv.last_join_rows == NC and len(out) == NC
+            while finish and srv.active:
+                srv.step()
+            return first * 1e3
+        convs = [srv.conversation(seed=i, on_overflow=mode, keep_turns=1) for i in range(NC)]
+        for c in convs:
+            push(c, heard[:7])
+        admit([c.say(text, 0, max_audio_length_ms=ms) for c in convs], True)
+        for c in convs:
+            push(c, heard[7:8])
+        t2 = admit([c.say(text, 0, max_audio_length_ms=ms) for c in convs], True)
+        for c in convs:
+            push(c, heard[8:9])
+        before, cached = convs[0].tokens.shape[0], convs[0].cached
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        reqs = [c.say(text, 0, max_audio_length_ms=long_ms) for c in convs]       # _fit runs here: 16 shift_parked under "shift"
+        torch.cuda.synchronize()
+        t_say = (time.perf_counter() - t0) * 1e3
+        fed3 = reqs[0]._tokens.shape[0]
+        t3 = admit(reqs, False)                                                    # (the 90 s turns are not played out)
+        return dict(t2=t2, t3=t3, say=t_say, fed3=fed3, before=before, cached=cached, kept=convs[0].cached)
+
+    for name, leg in (("(a) B = 1, chunk_frames 2", solo), ("(b) 16 conversations on 16 slots, chunk_frames 4", served)):
+        for mode in MODES:
+            leg(mode)                                                # warm-up round of each: allocator, graph capture, shapes
+        res = {m: [] for m in MODES}
+        for _ in range(rounds):
+            for mode in MODES:
+                res[mode].append(leg(mode))
+        r = res["shift"][0]
+        print(f"GEN_OVERFLOW {name}: history {r['before']} positions ({r['cached']} cached) before turn 3, {frames} frames per in-limit turn; "
+              f"{rounds} alternated rounds after one warm-up of each; ms as median [min..max]")
+        for mode in MODES:
+            v = res[mode]
+            line = f"  {mode:11s}: in-limit turn 2 -> first chunk {fmt([x['t2'] for x in v])} | overflowing turn 3 -> first chunk {fmt([x['t3'] for x in v])}"
+            if "say" in v[0]:
+                line += f" (fed {v[0]['fed3']} positions per row, history {v[0]['kept']} positions once fed; the 16 say() calls before it {fmt([x['say'] for x in v])})"
+            else:
+                line += f" (turn 2 fed {v[0]['fed2']} + text; history {v[0]['after']} positions in {v[0]['turns']} turns after turn 3's first chunk)"
+            print(line, flush=True)
+    # ---- (c) the kernel alone, CSM-1B geometry
+    with torch.inference_mode():
+        L, keep, drop = 900, 100, 200
+        c = model.bb
+        parked = torch.randn(c.num_layers, 2, c.num_kv_heads, L, c.head_dim, device=dev).to(torch.bfloat16)
+        table = model.rope_table("backbone")
+        _timed(lambda: ops.kv_shift(parked, table, keep, drop), 20)
+        tk = sorted(_timed(lambda: ops.kv_shift(parked, table, keep, drop), 100) * 1e3 for _ in range(max(rounds, 5)))
+        moved = parked.numel() * 2 * (2 * L - drop) / L
+        print(f"GEN_OVERFLOW (c) csm_kv_shift len {L} keep {keep} drop {drop}, {c.num_layers} layers x {c.num_kv_heads} kv heads x {c.head_dim}: "
+              f"median {med(tk) * 1e3:.1f} us [{tk[0] * 1e3:.1f}..{tk[-1] * 1e3:.1f}] per call (output allocation included), "
+              f"{moved / 1e6:.1f} MB read + written -> {moved / med(tk) / 1e6:.0f} GB/s")
+        from csm.engine import DecodeState
+        st = DecodeState(model.engine, 1)
+        st.resume_row(0, parked)
+
+        def row():
+            st.resume_row(0, parked)
+            st.shift_row(0, keep, drop)
+        _timed(row, 5)
+        both = sorted(_timed(row, 20) * 1e3 for _ in range(max(rounds, 5)))
+        res_only = sorted(_timed(lambda: st.resume_row(0, parked), 20) * 1e3 for _ in range(max(rounds, 5)))
+        print(f"GEN_OVERFLOW (c) shift_row (park_row + csm_kv_shift + resume_row) at the same sizes: median {med(both) - med(res_only):.3f} ms "
+              f"(resume_row of {L} positions alone {med(res_only):.3f} ms, taken off)")
+
+
 def main():
+    if os.environ.get("GEN_OVERFLOW") == "1":
+        return overflow_main()
     if os.environ.get("GEN_HEAR") == "rows":
         return hear_rows_main()
     if os.environ.get("GEN_HEAR") == "1":
