@@ -69,7 +69,12 @@ def parse_args(argv=None):
     p.add_argument("--hear-slots", type=int, default=0,
                    help="--serve-file: encoder slots of the server's batched hearing (Generator.serve(hear_slots=N), 0..16; "
                         "default 0: every conversation that hears has its own encode stream)")
+    p.add_argument("--output-sample-rate", type=int, default=None, metavar="HZ",
+                   help="sample rate of the WAV(s) written (default: the codec's 24000); another rate is resampled on the device, "
+                        "chunk by chunk with --stream and on the server (all modes)")
     args = p.parse_args(argv)
+    if args.output_sample_rate is not None and args.output_sample_rate < 1:
+        p.error("--output-sample-rate must be >= 1")
     if args.text is None and args.serve_file is None:
         p.error("one of --text and --serve-file is required")
     if args.serve_file is not None and (args.text is not None or args.next_text or args.stream):
@@ -85,6 +90,16 @@ def parse_args(argv=None):
     if args.next_speaker and len(args.next_speaker) != len(args.next_text or []):
         p.error("--next-speaker must be given once per --next-text (or not at all)")
     return args
+
+
+def out_rate_kw(args):
+    """The ``output_sample_rate`` keyword of the generate / serve calls: nothing without --output-sample-rate."""
+    return {} if args.output_sample_rate is None else {"output_sample_rate": args.output_sample_rate}
+
+
+def out_rate(generator, args) -> int:
+    """The rate of what is written: --output-sample-rate, or the generator's."""
+    return int(generator.sample_rate if args.output_sample_rate is None else args.output_sample_rate)
 
 
 def build_context(args, sample_rate):
@@ -119,10 +134,11 @@ def main(argv=None):
     if args.stream:
         return stream_to_wav(generator, args, speaker_id, context, adapter)
     audio = generator.generate(text=args.text, speaker=speaker_id, context=context, max_audio_length_ms=args.max_audio_length_ms,
-                               temperature=args.temperature, topk=args.topk, adapter=adapter, top_p=args.top_p, min_p=args.min_p)
+                               temperature=args.temperature, topk=args.topk, adapter=adapter, top_p=args.top_p, min_p=args.min_p,
+                               **out_rate_kw(args))
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
-    generator.save_wav(args.output, audio)
-    print(f"Audio saved to {args.output} ({audio.numel() / generator.sample_rate:.2f} s at {generator.sample_rate} Hz)")
+    generator.save_wav(args.output, audio, **({} if args.output_sample_rate is None else {"sample_rate": args.output_sample_rate}))
+    print(f"Audio saved to {args.output} ({audio.numel() / out_rate(generator, args):.2f} s at {out_rate(generator, args)} Hz)")
     return 0
 
 
@@ -135,17 +151,17 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
     with wave.open(args.output, "wb") as w:
         w.setnchannels(1)
         w.setsampwidth(2)
-        w.setframerate(int(generator.sample_rate))
+        w.setframerate(out_rate(generator, args))
         for chunk in generator.generate_stream(text=args.text, speaker=speaker_id, context=context,
                                                max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature,
                                                topk=args.topk, chunk_frames=args.chunk_frames, adapter=adapter,
-                                               top_p=args.top_p, min_p=args.min_p):
+                                               top_p=args.top_p, min_p=args.min_p, **out_rate_kw(args)):
             pcm = (chunk.detach().float().cpu().clamp(-1, 1) * 32767.0).to(torch.int16).numpy().tobytes()
             if n == 0:
                 print(f"first chunk after {time.perf_counter() - t0:.3f} s")
             w.writeframes(pcm)
             n += chunk.numel()
-    print(f"Audio saved to {args.output} ({n / generator.sample_rate:.2f} s at {generator.sample_rate} Hz, streamed in "
+    print(f"Audio saved to {args.output} ({n / out_rate(generator, args):.2f} s at {out_rate(generator, args)} Hz, streamed in "
           f"{time.perf_counter() - t0:.2f} s)")
     return 0
 
@@ -226,7 +242,7 @@ def serve_to_wavs(generator, args, context, adapter=None):
     t0 = time.perf_counter()
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, temperature=args.temperature,
                              topk=args.topk, hear_slots=args.hear_slots,
-                             **{**serve_sampling(lines), **serve_filters(lines, args.top_p, args.min_p)})
+                             **{**serve_sampling(lines), **serve_filters(lines, args.top_p, args.min_p), **out_rate_kw(args)})
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
     def say(cid):
@@ -252,8 +268,8 @@ def serve_to_wavs(generator, args, context, adapter=None):
             if done:
                 i, cid = line_of[req]
                 out = f"{stem}_{i}{ext or '.wav'}"
-                generator.save_wav(out, req.audio())
-                print(f"line {i}: {req.audio().numel() / generator.sample_rate:.2f} s -> {out} (after {time.perf_counter() - t0:.2f} s)")
+                generator.save_wav(out, req.audio(), **({} if args.output_sample_rate is None else {"sample_rate": req.sample_rate}))
+                print(f"line {i}: {req.audio().numel() / out_rate(generator, args):.2f} s -> {out} (after {time.perf_counter() - t0:.2f} s)")
                 if cid is not None and convs[cid][1]:
                     say(cid)
     print(f"{len(lines)} utterances served in {time.perf_counter() - t0:.2f} s")
@@ -272,13 +288,13 @@ def converse_to_wav(generator, args, speaker_id, context, adapter=None):
     lines = [(args.text, speaker_id)] + list(zip(args.next_text, args.next_speaker or [speaker_id] * len(args.next_text)))
     conv = generator.conversation(context=context, adapter=adapter, on_overflow=args.on_overflow, keep_turns=args.keep_turns)
     kw = dict(max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature, topk=args.topk, top_p=args.top_p,
-              min_p=args.min_p)
+              min_p=args.min_p, **out_rate_kw(args))
     t0 = time.perf_counter()
     n = 0
     with wave.open(args.output, "wb") as w:
         w.setnchannels(1)
         w.setsampwidth(2)
-        w.setframerate(int(generator.sample_rate))
+        w.setframerate(out_rate(generator, args))
         for i, (text, spk) in enumerate(lines):
             t1 = time.perf_counter()
             if args.stream:
@@ -293,8 +309,8 @@ def converse_to_wav(generator, args, speaker_id, context, adapter=None):
                 audio = conv.generate(text, spk, **kw)
                 w.writeframes(_pcm(audio))
                 n += audio.numel()
-                print(f"turn {i + 1}: {audio.numel() / generator.sample_rate:.2f} s of audio in {time.perf_counter() - t1:.2f} s")
-    print(f"Audio saved to {args.output} ({n / generator.sample_rate:.2f} s at {generator.sample_rate} Hz, {len(lines)} turns in "
+                print(f"turn {i + 1}: {audio.numel() / out_rate(generator, args):.2f} s of audio in {time.perf_counter() - t1:.2f} s")
+    print(f"Audio saved to {args.output} ({n / out_rate(generator, args):.2f} s at {out_rate(generator, args)} Hz, {len(lines)} turns in "
           f"{time.perf_counter() - t0:.2f} s)")
     return 0
 

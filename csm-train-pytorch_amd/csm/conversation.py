@@ -68,8 +68,9 @@ class HeardTurn:
     the last partial frame (zero-padded) and enters the turn exactly as ``add(Segment(speaker, text, audio))`` does - for audio
     of a whole number of frames ``tokens`` and ``mask`` are equal to that path's; ``cancel()`` drops the turn."""
 
-    def __init__(self, conv, speaker: int, stream):
+    def __init__(self, conv, speaker: int, stream, resampler=None):
         self._conv, self.speaker, self._stream = conv, speaker, stream
+        self._rs = resampler                       # ``hear(sample_rate=)``: a ResampleStream in front of the encode stream
         self._codes: List[torch.Tensor] = []
         self._frames = 0
         self.closed = False
@@ -96,8 +97,11 @@ class HeardTurn:
 
     @torch.inference_mode()
     def feed(self, audio: torch.Tensor) -> int:
-        """The next samples of the turn, any number of them ((n,), sample_rate 24 kHz); returns ``frames``."""
+        """The next samples of the turn, any number of them ((n,), at the ``sample_rate`` given to ``hear`` - the codec's 24 kHz
+        by default); returns ``frames``."""
         self._check("feed")
+        if self._rs is not None:
+            audio = self._rs.feed(audio)
         self._take(self._stream.feed(audio.reshape(1, 1, -1)))
         return self._frames
 
@@ -108,6 +112,8 @@ class HeardTurn:
         self._check("end")
         conv, gen = self._conv, self._conv._gen
         conv._before_history("end")                                 # (raises with the turn still open: end() can be retried)
+        if self._rs is not None:                                    # the samples the resampler still owes, then the encoder's flush
+            self._take(self._stream.feed(self._rs.flush().reshape(1, 1, -1)))
         self._take(self._stream.flush())
         self._enter(*gen._tokenize_text_segment(text, self.speaker))
 
@@ -126,9 +132,17 @@ class HeardTurn:
             self.closed, self._conv._heard = True, None
 
 
-def open_heard_turn(conv, speaker: int) -> HeardTurn:
+def hear_resampler(gen, sample_rate):
+    """``hear(sample_rate=)``: None for None or the codec's own rate, else the ``Resampler`` from that rate to the codec's."""
+    from .codec.resample import rate_resampler
+    return rate_resampler("sample_rate", sample_rate, gen.sample_rate, gen.device, to_native=True)
+
+
+def open_heard_turn(conv, speaker: int, sample_rate=None) -> HeardTurn:
     """``hear`` of both conversation classes: at most one heard turn is open per conversation; its encode stream is made at the
-    first ``hear`` and started anew (``reset()``) for every later one."""
+    first ``hear`` and started anew (``reset()``) for every later one.  ``sample_rate``: the rate of what ``feed`` will get; one
+    other than the codec's puts a ``ResampleStream`` (one per rate, kept like the encode stream) in front of the encoder."""
+    rs = hear_resampler(conv._gen, sample_rate)
     if conv._heard is not None:
         raise RuntimeError("hear: this conversation already has a heard turn open - end() or cancel() it first")
     if conv._enc is None:
@@ -138,7 +152,14 @@ def open_heard_turn(conv, speaker: int) -> HeardTurn:
         conv._enc = codec.encode_stream()
     else:
         conv._enc.reset()
-    conv._heard = HeardTurn(conv, speaker, conv._enc)
+    stream = None
+    if rs is not None:
+        stream = conv._hear_rs.get(rs.orig_sr)
+        if stream is None:
+            stream = conv._hear_rs[rs.orig_sr] = rs.stream()
+        else:
+            stream.reset()
+    conv._heard = HeardTurn(conv, speaker, conv._enc, stream)
     return conv._heard
 
 
@@ -178,6 +199,7 @@ class Conversation:
         self._open: Optional[_Turn] = None
         self._heard: Optional[HeardTurn] = None    # the other party's turn being heard (hear), at most one
         self._enc = None                           # its encode stream: made at the first hear, reused
+        self._hear_rs = {}                         # hear(sample_rate=): input rate -> its ResampleStream, made once, reused
         for seg in context:
             self.add(seg)
 
@@ -205,10 +227,12 @@ class Conversation:
         t, m = self._gen._tokenize_segment(segment)
         self._push(t.long(), m.bool())
 
-    def hear(self, speaker: int) -> HeardTurn:
+    def hear(self, speaker: int, sample_rate: Optional[int] = None) -> HeardTurn:
         """The other party starts to speak: ``turn.feed(audio)`` Mimi-encodes the turn as it arrives, ``turn.end(text)`` enters it
-        as ``add`` would - with nothing left to encode but its last partial frame."""
-        return open_heard_turn(self, speaker)
+        as ``add`` would - with nothing left to encode but its last partial frame.  ``sample_rate``: the rate of the samples
+        ``feed`` will get (None: the codec's 24 kHz); another rate is resampled on the device as it arrives, and the turn enters
+        as ``add`` of ``ops.resample(whole, sample_rate, 24000)`` would."""
+        return open_heard_turn(self, speaker, sample_rate)
 
     def _before_history(self, what):
         """What ``add`` and ``HeardTurn.end`` do before they extend the history: an open stream of this conversation is
@@ -318,11 +342,13 @@ class Conversation:
 
     @torch.inference_mode()
     def generate(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
-                 eos_check_every: int = 8, top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
-        """Speak ``text`` as ``speaker`` with the whole history as context; arguments (``top_p`` / ``min_p`` included: this turn's)
-        and EOS handling as ``Generator.generate``."""
+                 eos_check_every: int = 8, top_p: float = 1.0, min_p: float = 0.0,
+                 output_sample_rate: Optional[int] = None) -> torch.Tensor:
+        """Speak ``text`` as ``speaker`` with the whole history as context; arguments (``top_p`` / ``min_p`` and
+        ``output_sample_rate`` included: this turn's) and EOS handling as ``Generator.generate``."""
         from .generator import filter_kwargs
         filters = filter_kwargs(top_p, min_p)
+        out_rs = self._gen._out_resampler(output_sample_rate)
         self._run += 1
         self._settle()
         max_audio_frames = int(max_audio_length_ms / 80)
@@ -347,14 +373,17 @@ class Conversation:
         if not samples:
             return torch.zeros(0, device=self._gen.device)
         codes = torch.stack(samples).permute(1, 2, 0).long()
-        return self._gen._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
+        audio = self._gen._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
+        return audio if out_rs is None else out_rs(audio)
 
     def generate_stream(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9,
-                        topk: int = 50, chunk_frames: int = 4, top_p: float = 1.0, min_p: float = 0.0) -> Iterator[torch.Tensor]:
+                        topk: int = 50, chunk_frames: int = 4, top_p: float = 1.0, min_p: float = 0.0,
+                        output_sample_rate: Optional[int] = None) -> Iterator[torch.Tensor]:
         """``generate`` handing the audio out chunk by chunk, as ``Generator.generate_stream`` does; under the same seed the
         chunks concatenate to ``generate``'s audio.  A later call on THIS conversation invalidates the stream."""
         from .generator import filter_kwargs
         filters = filter_kwargs(top_p, min_p)
+        out_rs = self._gen._out_resampler(output_sample_rate)
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
         codec = self._gen._audio_tokenizer
@@ -363,10 +392,10 @@ class Conversation:
                             "(decoding chunks independently would be wrong at the chunk edges)")
         self._run += 1
         self._settle()
-        return self._stream(self._run, text, speaker, max_audio_length_ms, temperature, topk, int(chunk_frames), filters)
+        return self._stream(self._run, text, speaker, max_audio_length_ms, temperature, topk, int(chunk_frames), filters, out_rs)
 
     @torch.inference_mode()
-    def _stream(self, run, text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, filters={}):
+    def _stream(self, run, text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, filters={}, out_rs=None):
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later call on the same Conversation took its turn")
@@ -374,6 +403,7 @@ class Conversation:
         check()
         max_audio_frames = int(max_audio_length_ms / 80)
         decoder = self._gen._audio_tokenizer.decode_stream()
+        out = out_rs.stream() if out_rs is not None else None
         turn, done = None, 0
         try:
             for i in range(max_audio_frames):
@@ -388,10 +418,13 @@ class Conversation:
                     turn.kept = done + n
                     done = len(turn.samples)
                     if n:
-                        yield decoder.step(codes[:, :, :n]).reshape(-1)
+                        chunk = decoder.step(codes[:, :, :n]).reshape(-1)
+                        yield chunk if out is None else out.feed(chunk)
                         check()
                     if hit.numel():
-                        return
+                        break
+            if out is not None and out.pos:                            # the samples the resampler still owes (its lag)
+                yield out.flush()
         finally:
             if turn is not None and self._open is turn:
                 self._settle()

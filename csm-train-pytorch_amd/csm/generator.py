@@ -107,6 +107,12 @@ class Generator:
             raise ValueError(f"unknown LoRA adapter {next(n for n in names if n is not None)!r} (none loaded)")
         return self._bank.resolve(names)
 
+    def _out_resampler(self, output_sample_rate):
+        """``output_sample_rate=`` of the generate / serve calls: None for None or the codec's own rate (the call is then today's,
+        untouched), else the device ``Resampler`` from the codec's rate to it.  A bad rate raises here, before anything runs."""
+        from .codec.resample import rate_resampler
+        return rate_resampler("output_sample_rate", output_sample_rate, self.sample_rate, self.device, to_native=False)
+
     def _tokenize_text_segment(self, text: str, speaker: int) -> Tuple[torch.Tensor, torch.Tensor]:
         """Reference generator.py:77-100: ``f"[{speaker}]{text}"`` ids into the last column."""
         K1 = self._model.args.audio_num_codebooks + 1
@@ -141,7 +147,7 @@ class Generator:
     @torch.inference_mode()
     def generate(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                  temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8, adapter: Optional[str] = None,
-                 top_p: float = 1.0, min_p: float = 0.0) -> torch.Tensor:
+                 top_p: float = 1.0, min_p: float = 0.0, output_sample_rate: Optional[int] = None) -> torch.Tensor:
         """Reference generator.py:147-218.  ``adapter``: the name of a bank adapter (``add_adapter`` / ``load_adapter``) to
         speak with, or None.  The reference tests every frame for EOS on the host (one device sync per
         frame, generator.py:196-199); here the all-zero test runs on the device and the host looks at it once per
@@ -149,8 +155,11 @@ class Generator:
         sampled past the EOS frame are dropped.
         ``top_p`` (in (0, 1]) / ``min_p`` (in [0, 1]): a nucleus and a min-p cut applied inside the sampler to what top-k kept -
         first p_i >= min_p * p_max, then the smallest set of the largest values whose probability reaches top_p.  At 1.0 / 0.0
-        (the defaults) the call is what it is without them; otherwise it samples through the filtered rows sampler."""
+        (the defaults) the call is what it is without them; otherwise it samples through the filtered rows sampler.
+        ``output_sample_rate``: the rate of the audio returned (None: the codec's 24 kHz); another rate is resampled on the
+        device (``csm.codec.resample``) - the codes are the same."""
         filters = filter_kwargs(top_p, min_p)
+        out_rs = self._out_resampler(output_sample_rate)
         ads = self._resolve_adapters([adapter])
         self._run += 1
         self._model.reset_caches()
@@ -178,7 +187,8 @@ class Generator:
         if not samples:
             return torch.zeros(0, device=self.device)
         codes = torch.stack(samples).permute(1, 2, 0).long()
-        return self._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
+        audio = self._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
+        return audio if out_rs is None else out_rs(audio)
 
     def _prompt(self, text: str, speaker: int, context: List[Segment], max_audio_frames: int):
         """Prompt frames of ``generate`` / ``generate_stream``: (tokens [1,S,K+1], mask [1,S,K+1], positions [1,S])."""
@@ -200,15 +210,19 @@ class Generator:
 
     def generate_stream(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                         temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4,
-                        adapter: Optional[str] = None, top_p: float = 1.0, min_p: float = 0.0) -> Iterator[torch.Tensor]:
+                        adapter: Optional[str] = None, top_p: float = 1.0, min_p: float = 0.0,
+                        output_sample_rate: Optional[int] = None) -> Iterator[torch.Tensor]:
         """``generate`` that hands the audio out while it is being made: an iterator of 1-D device tensors of
         ``chunk_frames * 1920`` samples (the last one may be shorter), decoded by the audio tokenizer's stateful
         ``decode_stream()``.  The frames are sampled by the same ``generate_frame`` calls in the same order as ``generate``,
         so under the same torch seed the concatenated chunks equal ``generate``'s audio.  The host looks for EOS once per
         chunk; frames from EOS on are never decoded.  A later ``generate`` / ``generate_batch`` / ``generate_stream`` on this
         Generator invalidates the stream (its next ``next()`` raises ``RuntimeError``); abandoning it is harmless.
-        ``adapter``, ``top_p``, ``min_p``: as for ``generate``."""
+        ``adapter``, ``top_p``, ``min_p``: as for ``generate``.  ``output_sample_rate``: the chunks go through a stateful
+        ``ResampleStream`` - they concatenate to ``generate(..., output_sample_rate=)``'s audio bit for bit; the stream lags by
+        the filter's half-width, and what it still owes comes as one last short chunk."""
         filters = filter_kwargs(top_p, min_p)
+        out_rs = self._out_resampler(output_sample_rate)
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
         if not callable(getattr(self._audio_tokenizer, "decode_stream", None)):
@@ -217,10 +231,11 @@ class Generator:
         ads = self._resolve_adapters([adapter])
         self._run += 1
         return self._stream(self._run, text, speaker, context, max_audio_length_ms, temperature, topk, int(chunk_frames), ads,
-                            filters)
+                            filters, out_rs)
 
     @torch.inference_mode()
-    def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames, ads=None, filters={}):
+    def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames, ads=None, filters={},
+                out_rs=None):
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later generate / generate_batch / generate_stream call on "
@@ -231,6 +246,7 @@ class Generator:
         max_audio_frames = int(max_audio_length_ms / 80)
         curr_tokens, curr_mask, curr_pos = self._prompt(text, speaker, context, max_audio_frames)
         decoder = self._audio_tokenizer.decode_stream()
+        out = out_rs.stream() if out_rs is not None else None
         K = self._model.args.audio_num_codebooks
         audio_mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(self.device)
         pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
@@ -243,20 +259,23 @@ class Generator:
                 hit = (codes[0] == 0).all(dim=0).nonzero()                                  # the chunk's one host look
                 n = int(hit[0]) if hit.numel() else codes.shape[2]
                 if n:
-                    yield decoder.step(codes[:, :, :n]).reshape(-1)
+                    chunk = decoder.step(codes[:, :, :n]).reshape(-1)
+                    yield chunk if out is None else out.feed(chunk)
                     check()
                 if hit.numel():
-                    return
+                    break
                 pending = []
             curr_tokens = torch.cat([sample.long(), pad], dim=1).unsqueeze(1)
             curr_mask = audio_mask
             curr_pos = curr_pos[:, -1:] + 1
+        if out is not None and out.pos:                                # the samples the resampler still owes (its lag)
+            yield out.flush()
 
     @torch.inference_mode()
     def generate_batch(self, texts: List[str], speakers: List[int], contexts: List[List[Segment]],
                        max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
                        eos_check_every: int = 8, adapters: Optional[List[Optional[str]]] = None, top_p=1.0,
-                       min_p=0.0) -> List[torch.Tensor]:
+                       min_p=0.0, output_sample_rate: Optional[int] = None) -> List[torch.Tensor]:
         """``generate`` for up to 16 utterances at once (not in the reference, whose loop is single-utterance): the prompts
         (different lengths) are prefilled one by one into their rows of the KV caches, then every decode frame advances all
         rows together - the decode kernels share each weight load between the batch rows, so B utterances cost about as
@@ -269,7 +288,9 @@ class Generator:
         each row then samples with its own pair (the rows sampler, ``DecodeState.set_row_sampling``) and has the codes it
         has in a batch of the same size run with its pair for everybody; two numbers are the one-pair path.
         ``top_p`` / ``min_p``: a number or one value per utterance for either one (``generate``); at 1.0 / 0.0 the call is what it
-        is without them, otherwise every row samples through the filtered rows sampler with its own four parameters."""
+        is without them, otherwise every row samples through the filtered rows sampler with its own four parameters.
+        ``output_sample_rate``: as for ``generate``, for every utterance."""
+        out_rs = self._out_resampler(output_sample_rate)
         B = len(texts)
         if not (1 <= B <= 16 and len(speakers) == B and len(contexts) == B):
             raise ValueError("generate_batch takes 1..16 utterances with one speaker id and one context list each")
@@ -319,7 +340,8 @@ class Generator:
             if n == 0:
                 out.append(torch.zeros(0, device=self.device))
             else:
-                out.append(self._audio_tokenizer.decode(codes_all[b:b + 1, :, :n]).squeeze(0).squeeze(0))
+                audio = self._audio_tokenizer.decode(codes_all[b:b + 1, :, :n]).squeeze(0).squeeze(0)
+                out.append(audio if out_rs is None else out_rs(audio))
         return out
 
     def _batch_sampling(self, temperature, topk, B):
@@ -342,7 +364,8 @@ class Generator:
         return out[0], out[1]
 
     def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
-              row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0):
+              row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
+              output_sample_rate: Optional[int] = None):
         """A running batch (csm/serving.py): ``server.submit(text, speaker, context, adapter=None, seed=None,
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
@@ -359,9 +382,12 @@ class Generator:
         invalidated) and binds the adapters loaded so far: load adapters first.
         ``hear_slots`` (0..16): 0, the default, gives every conversation that hears its own encode stream, one encoder step per
         ``feed``; N >= 1 gives the server one rows encoder of N slots - ``feed`` only buffers, ``server.hear_step()`` (called by
-        ``step()``) encodes all open heard turns in one batched step, ``server.end_heard([(turn, text), ...])`` ends several."""
+        ``step()``) encodes all open heard turns in one batched step, ``server.end_heard([(turn, text), ...])`` ends several.
+        ``output_sample_rate``: the rate of every chunk and of ``Request.audio()`` (None: the codec's 24 kHz); the server then keeps
+        one rows resampler over its slots - one more launch per ``step()``.  ``conv.hear(speaker, sample_rate=)`` is the input side."""
         from .serving import BatchServer
-        return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p)
+        return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p,
+                           output_sample_rate)
 
     def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error",
                      keep_turns: int = 0):
@@ -376,14 +402,15 @@ class Generator:
         from .conversation import Conversation
         return Conversation(self, context or [], adapter, on_overflow, keep_turns)
 
-    def save_wav(self, path: str, audio: torch.Tensor):
-        """16-bit PCM writer (torchaudio is not available in this image)."""
+    def save_wav(self, path: str, audio: torch.Tensor, sample_rate: Optional[int] = None):
+        """16-bit PCM writer (torchaudio is not available in this image).  ``sample_rate``: the rate ``audio`` is at (None: the
+        codec's) - what a call with ``output_sample_rate=`` returned is written with that rate in the header."""
         import wave
         pcm = (audio.detach().float().cpu().clamp(-1, 1) * 32767.0).to(torch.int16).numpy().tobytes()
         with wave.open(path, "wb") as w:
             w.setnchannels(1)
             w.setsampwidth(2)
-            w.setframerate(int(self.sample_rate))
+            w.setframerate(int(self.sample_rate if sample_rate is None else sample_rate))
             w.writeframes(pcm)
 
 

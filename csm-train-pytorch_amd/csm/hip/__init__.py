@@ -117,6 +117,9 @@ _SIGS = {
     "csm_rope_half_rows_f32": ([_p, _i, _p, _i, _i, _i, _f, _p], _i),
     "csm_attn_window_stream_rows_f32": ([_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_transpose_rows_f32": ([_p, _p, _i, _i, _i, _p], _i),
+    "csm_resample_f32": ([_p, _p, _p, _i, _ll, _i, _i, _i, _p], _i),
+    "csm_resample_stream_rows_f32": ([_p, _p, _p, _p, _ll, _i, _p, _p, _p, _p, C.c_uint, _i, _i, _i, _i, _i, _p], _i),
+    "csm_resample_stream_f32": ([_p, _i, _p, _i, _ll, _i, _p, _p, _ll, _i, _i, _i, _i, _p], _i),
 }
 
 for _name, (_args, _res) in _SIGS.items():

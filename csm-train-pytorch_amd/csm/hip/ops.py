@@ -910,3 +910,49 @@ def transpose_rows_f32(x, y):
     assert y.shape == (b, Cn, R)
     check(lib.csm_transpose_rows_f32(_f32(x, "x"), _f32(y, "y"), b, R, Cn, _stream()), "csm_transpose_rows_f32")
     return y
+
+
+def resample_f32(x, taps, y, o, n, width):
+    """One-shot band-limited resampling (csm_resample_f32): x [R, N] -> y [R, ceil(n*N/o)] with the polyphase table ``taps``
+    [n, 2*width + o] of the reduced rate pair o / n (``csm.codec.resample.design``)."""
+    R, N = x.shape
+    assert taps.shape == (n, 2 * width + o) and y.shape == (R, -(-n * N // o))
+    check(lib.csm_resample_f32(_f32(x, "x") if N else None, _f32(taps, "taps"), _f32(y, "y") if N else None, R, N, o, n, width,
+                               _stream()), "csm_resample_f32")
+    return y
+
+
+def resample_stream_rows_f32(arena, xs, taps, y, slots, parity, pos, final, max_in, o, n, width):
+    """R streams in one launch (csm_resample_stream_rows_f32): row r feeds the 1-D fp32 tensor ``xs[r]`` (None or empty: nothing
+    new - only with its ``final`` flag) to the stream of slot ``slots[r]`` that has seen ``pos[r]`` samples; ``arena``
+    [n_slots, 2, T - 1] holds the carries, ``y`` [R, ldy] receives each row's new outputs from column 0.  Slots, parities,
+    lengths, positions and the rows' device pointers travel by value."""
+    R = len(slots)
+    T = 2 * width + o
+    assert len(xs) == len(parity) == len(pos) == R and arena.shape[1:] == (2, T - 1) and taps.shape == (n, T)
+    assert len(final) in (0, R) and y.dim() == 2 and y.shape[0] == R
+    n_in = [0 if x is None else x.numel() for x in xs]
+    ptrs = (ctypes.c_void_p * R)(*[_f32(x, "x") if k else None for x, k in zip(xs, n_in)])
+    mask = sum(1 << r for r, f in enumerate(final) if f)
+    check(lib.csm_resample_stream_rows_f32(_f32(arena, "arena"), ptrs, _f32(taps, "taps"), _f32(y, "y") if y.numel() else None,
+                                           y.shape[1], R, _ints(slots), _ints(parity), _ints(n_in),
+                                           (ctypes.c_longlong * R)(*[int(p) for p in pos]), mask, arena.shape[0], int(max_in), o, n,
+                                           width, _stream()), "csm_resample_stream_rows_f32")
+    return y
+
+
+def resample_stream_f32(carry, parity, x, pos, final, taps, y, max_in, o, n, width):
+    """One stream (csm_resample_stream_f32): ``carry`` [2, T - 1], ``x`` the next samples (None: a flush), ``y`` [>= outputs]."""
+    T = 2 * width + o
+    assert carry.shape == (2, T - 1) and taps.shape == (n, T) and y.dim() == 1
+    k = 0 if x is None else x.numel()
+    check(lib.csm_resample_stream_f32(_f32(carry, "carry"), int(parity), _f32(x, "x") if k else None, k, int(pos), int(bool(final)),
+                                      _f32(taps, "taps"), _f32(y, "y") if y.numel() else None, y.numel(), int(max_in), o, n, width,
+                                      _stream()), "csm_resample_stream_f32")
+    return y
+
+
+def resample(x, orig_sr, new_sr):
+    """``csm.data.resample`` on the device: x [..., N] fp32 -> [..., ceil(N * new_sr / orig_sr)] (``csm.codec.resample``)."""
+    from ..codec.resample import get_resampler
+    return get_resampler(orig_sr, new_sr, x.device)(x)

@@ -54,6 +54,15 @@ slot, ``feed`` only buffers, and ``hear_step()`` - which ``step()`` calls first 
 with one batched ``drain``: N listeners cost one encoder step per chunk (plus one per distinct backlog, ``peel_schedule``).
 ``turn.end`` drains and flushes its own slot; ``end_heard`` does it for turns that end together with one drain for all.
 
+Other sample rates (csm/codec/resample.py).  ``conv.hear(speaker, sample_rate=16000)`` takes the turn's samples at that rate:
+without ``hear_slots`` the turn owns a ``ResampleStream`` in front of its encode stream; with them ``feed`` buffers the raw
+samples and ``hear_step`` first resamples every row that has new ones - ONE rows launch per distinct input rate among them
+(``ResampleStreamRows`` over the encoder slots) - and hands the 24 kHz samples to the encoder's ``feed``; ``end_heard`` ends the
+resampler streams (their ``final`` step) before the encoder's flush.  ``serve(output_sample_rate=48000)`` makes every chunk and
+``Request.audio()`` 48 kHz: one table, one rows stream over the decode slots, one rows launch per ``step()`` on the rows that
+produced audio - a row that ends in that step ends its stream there (``final``), so its last chunk carries the resampler's lag.
+Histories are codes and do not change.
+
 Limitations: a join stalls the other rows for one whole prefill or append (no chunked prefill); the context audio of a request
 and a conversation's ``add``ed turns are Mimi-encoded at ``submit`` / ``add``, one segment at a time (only ``conv.hear`` encodes
 while the turn is being spoken - and only with ``hear_slots`` batched over the conversations); adapters added to the
@@ -64,7 +73,7 @@ from typing import Iterator, List, Optional, Tuple
 
 import torch
 
-from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, open_heard_turn
+from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, hear_resampler, open_heard_turn
 from .engine import DecodeState, check_filters, check_sampling
 
 
@@ -85,6 +94,7 @@ class Request:
         self._sampled = 0                        # frames sampled / handed out so far
         self._emitted = 0
         self._conv: Optional["ServedConversation"] = None     # the conversation this is a turn of (tokens / mask: what it feeds)
+        self.sample_rate: Optional[int] = None   # the rate of ``chunks`` / ``audio()`` (the server's; set when it queues)
         self._base = 0                           # a turn: positions the cache holds once the feed is in
 
     def audio(self) -> torch.Tensor:
@@ -104,19 +114,43 @@ class SlotHeardTurn(HeardTurn):
     given until the next ``hear_step``, so do not overwrite it before); ``frames`` counts the frames encoded so far,
     ``pending`` the whole frames that wait for the next ``hear_step``."""
 
-    def __init__(self, conv, speaker: int, server, slot: int):
+    def __init__(self, conv, speaker: int, server, slot: int, rows=None):
         super().__init__(conv, speaker, server._hear)
         self._srv, self.slot = server, slot
+        self._rows = rows                        # ``hear(sample_rate=)``: the server's ResampleStreamRows of that rate (or None)
+        self._raw: List[torch.Tensor] = []       # samples at that rate fed since the last hear_step, as given
+        self._raw_n = 0
 
     @property
     def pending(self) -> int:
-        return 0 if self.closed else self._stream.pending(self.slot)
+        if self.closed:
+            return 0
+        if self._rows is None:
+            return self._stream.pending(self.slot)
+        from .codec.resample import step_outputs
+        rs = self._rows.rs                       # what the waiting raw samples will give the encoder, in whole frames
+        more = step_outputs(self._rows.pos[self.slot], self._raw_n, False, rs.o, rs.n, rs.width)
+        return (self._stream._count[self.slot] + more) // self._stream.frame
 
     def feed(self, audio: torch.Tensor) -> int:
         self._check("feed")
         self._srv._check()
-        self._stream.feed(self.slot, audio.reshape(-1))
+        if self._rows is None:
+            self._stream.feed(self.slot, audio.reshape(-1))
+        elif audio.numel():
+            self._raw.append(audio.detach().reshape(-1))
+            self._raw_n += audio.numel()
         return self._frames
+
+    def _take_raw(self, limit: int):
+        """Up to ``limit`` of the waiting raw samples as one tensor (None when nothing waits)."""
+        if not self._raw_n:
+            return None
+        dev = self._rows.rs.device
+        buf = self._raw[0].to(dev, torch.float32) if len(self._raw) == 1 else torch.cat([p.to(dev, torch.float32) for p in self._raw])
+        head, rest = buf[:limit], buf[limit:]
+        self._raw, self._raw_n = ([rest], rest.numel()) if rest.numel() else ([], 0)
+        return head
 
     def end(self, text: str) -> None:
         self._srv.end_heard([(self, text)])
@@ -151,6 +185,7 @@ class ServedConversation:
         self._open: Optional[Request] = None
         self._heard: Optional[HeardTurn] = None  # the other party's turn being heard (hear), at most one
         self._enc = None                         # its encode stream: made at the first hear, reused
+        self._hear_rs = {}                       # hear(sample_rate=) without hear_slots: input rate -> its ResampleStream
         self.closed = False
         for seg in context:
             self.add(seg)
@@ -183,17 +218,18 @@ class ServedConversation:
         t, m = self._gen._tokenize_segment(segment)
         self._push(t.long(), m.bool())
 
-    def hear(self, speaker: int) -> HeardTurn:
+    def hear(self, speaker: int, sample_rate: Optional[int] = None) -> HeardTurn:
         """The other party starts to speak: ``turn.feed(audio)`` Mimi-encodes the turn as it arrives - between the server's steps,
         whoever holds the slots - and ``turn.end(text)`` enters it as ``add`` would, under ``add``'s rules (no turn of this
         conversation still open), with nothing left to encode but its last partial frame.  On a server with ``hear_slots`` the
-        turn takes one of its encoder slots (``SlotHeardTurn``; RuntimeError when none is free)."""
+        turn takes one of its encoder slots (``SlotHeardTurn``; RuntimeError when none is free).  ``sample_rate``: the rate of
+        the samples ``feed`` will get (None: the codec's 24 kHz), resampled on the device - module docstring."""
         self._srv._check()
         if self.closed:
             raise RuntimeError("hear: this conversation was closed")
         if self._srv.hear_slots:
-            return self._srv._open_heard(self, speaker)
-        return open_heard_turn(self, speaker)
+            return self._srv._open_heard(self, speaker, sample_rate)
+        return open_heard_turn(self, speaker, sample_rate)
 
     _before_history = _idle
 
@@ -239,7 +275,7 @@ class ServedConversation:
         self._push(tt.long(), tm.bool())
         req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device,
                       temperature, topk, top_p, min_p)
-        req._conv, req._base = self, self._tokens.shape[0]
+        req._conv, req._base, req.sample_rate = self, self._tokens.shape[0], srv.sample_rate
         srv._next_id += 1
         srv._queue.append(req)
         self._open = req
@@ -278,7 +314,9 @@ class BatchServer:
     own; every draw goes through the filtered rows sampler."""
 
     def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
-                 row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0):
+                 row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
+                 output_sample_rate: Optional[int] = None):
+        out_rs = gen._out_resampler(output_sample_rate)      # (a bad rate raises here, before anything is taken over)
         if row_filters and not row_sampling:
             raise ValueError("serve(row_filters=True) needs row_sampling=True: top-p / min-p live in the rows sampler")
         if not row_filters and not (top_p == 1.0 and min_p == 0.0):
@@ -314,6 +352,12 @@ class BatchServer:
         # outside inference mode: ``conv.hear`` opens its slot (an in-place zero fill of the state) from ordinary caller code
         self._hear = codec.encode_stream_rows(slots=self.hear_slots) if self.hear_slots else None
         self._hearing: List[Optional[SlotHeardTurn]] = [None] * self.hear_slots     # encoder slot -> the turn that holds it
+        self._hear_rs = {}                               # input rate -> ResampleStreamRows over the encoder slots (hear(sample_rate=))
+        # speaking at another rate: one rows resampler over the decode slots, a step takes at most one chunk per row
+        self.sample_rate = int(gen.sample_rate) if out_rs is None else out_rs.new_sr
+        self._out = None
+        if out_rs is not None:
+            self._out = out_rs.stream_rows(self.slots, self.chunk_frames * (int(gen.sample_rate) * 80 // 1000))     # (80 ms frames)
         self._model._decode_state = self._state
         if self.row_sampling:
             for b in range(self.slots):                  # every row starts with a valid pair: the sampler runs on all of them
@@ -386,6 +430,7 @@ class BatchServer:
             tokens, mask, _ = self._gen._prompt(text, speaker, list(context), max_audio_frames)
         req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device,
                       temperature, topk, top_p, min_p)
+        req.sample_rate = self.sample_rate
         self._next_id += 1
         self._queue.append(req)
         return req
@@ -415,27 +460,55 @@ class BatchServer:
         return [r for r in self._rows if r is not None]
 
     # ------------------------------------------------------------------------------------------------------------- hearing
-    def _open_heard(self, conv, speaker: int) -> SlotHeardTurn:
+    def _open_heard(self, conv, speaker: int, sample_rate=None) -> SlotHeardTurn:
+        rs = hear_resampler(self._gen, sample_rate)
         if conv._heard is not None:
             raise RuntimeError("hear: this conversation already has a heard turn open - end() or cancel() it first")
         free = [s for s, t in enumerate(self._hearing) if t is None]
         if not free:
             raise RuntimeError(f"hear: all hear_slots = {self.hear_slots} encoder slots are taken - end() or cancel() a heard turn, "
                                "or serve with more")
+        rows = None
+        if rs is not None:                               # one rows stream per input rate, over the encoder slots; a step takes <= 1 s
+            rows = self._hear_rs.get(rs.orig_sr)
+            if rows is None:
+                rows = self._hear_rs[rs.orig_sr] = rs.stream_rows(self.hear_slots)
+            rows.open(free[0])
         self._hear.open(free[0])
-        conv._heard = self._hearing[free[0]] = SlotHeardTurn(conv, speaker, self, free[0])
+        conv._heard = self._hearing[free[0]] = SlotHeardTurn(conv, speaker, self, free[0], rows)
         return conv._heard
 
     def _free_heard(self, turn: SlotHeardTurn):
         self._hear.close(turn.slot)
+        if turn._rows is not None:
+            turn._rows.close(turn.slot)
         self._hearing[turn.slot] = None
+
+    def _resample_heard(self, turns, final=False):
+        """The raw samples waiting in ``turns`` go through their rates' rows resamplers - one launch per distinct rate (more only
+        for a backlog beyond a launch's ``max_in``) - and on to the encoder's ``feed``.  ``final``: the turns end - every one of
+        them with a rate ends its resampler stream, with or without new samples."""
+        by_rate = {}
+        for t in turns:
+            if t._rows is not None and (t._raw_n or final):
+                by_rate.setdefault(t._rows.rs.orig_sr, []).append(t)
+        for group in by_rate.values():
+            rows = group[0]._rows
+            while group:
+                xs = [t._take_raw(rows.max_in) for t in group]
+                last = [t for t in group if not t._raw_n]                # (nothing left behind: the turn's part is done)
+                ys = rows.step([t.slot for t in group], xs, final=[t.slot for t in last] if final else ())
+                for t, y in zip(group, ys):
+                    self._hear.feed(t.slot, y)
+                group = [t for t in group if t._raw_n]
 
     @torch.inference_mode()
     def hear_step(self) -> int:
         """Encode what waits in every open heard turn: ONE ``drain`` over all of them (nothing is launched when nothing waits).
         ``step()`` calls it first.  Returns the number of frames encoded."""
         self._check()
-        turns = [t for t in self._hearing if t is not None and t.pending]
+        self._resample_heard([t for t in self._hearing if t is not None])
+        turns = [t for t in self._hearing if t is not None and self._hear.pending(t.slot)]
         if not turns:
             return 0
         codes = self._hear.drain([t.slot for t in turns])
@@ -464,6 +537,7 @@ class BatchServer:
         if not ended:
             return
         slots = [turn.slot for turn, _ in ended]
+        self._resample_heard([turn for turn, _ in ended], final=True)
         codes = self._hear.drain(slots, flush=slots)
         for (turn, _), (tt, tm) in zip(ended, texts):
             turn._take(codes[turn.slot].unsqueeze(0))
@@ -514,6 +588,8 @@ class BatchServer:
             if conv is not None:
                 conv._cached = req._base
             self._codec.open(b)
+            if self._out is not None:
+                self._out.open(b)
             req.slot, self._rows[b] = b, req
             joined.append(b)
         if not joined:
@@ -573,11 +649,23 @@ class BatchServer:
             # (its output for those frames is cut below; the frames before them do not depend on it - the decoder is causal)
             live = torch.tensor([[j < keep[b] for j in range(n)] for b in heard], device=chunk.device)
             audio = self._codec.step(heard, chunk[heard] * live[:, None, :])
+        spoken = {}
+        if self._out is not None:
+            # ONE rows launch: the rows that produced audio, plus a row that ended on an empty chunk and is still owed its lag;
+            # a row that ends in this step ends its resampler stream with it
+            rows = [b for b in sorted(held) if keep[b] > 0 or (done[b] and self._out.pos[b] > 0)]
+            if rows:
+                xs = [audio[heard.index(b), :keep[b] * (audio.shape[1] // n)] if keep[b] > 0 else None for b in rows]
+                spoken = dict(zip(rows, self._out.step(rows, xs, final=[b for b in rows if done[b]])))
         out = []
         for b in sorted(held):
             req = self._rows[b]
-            if keep[b] > 0:
-                part = audio[heard.index(b), :keep[b] * (audio.shape[1] // n)].clone()
+            if b in spoken and keep[b] == 0:                         # (only the lag: no frames, no codes)
+                part = spoken[b].clone()
+                if part.numel():
+                    req.chunks.append(part)
+            elif keep[b] > 0:
+                part = (spoken[b] if b in spoken else audio[heard.index(b), :keep[b] * (audio.shape[1] // n)]).clone()
                 req.chunks.append(part)
                 req._codes.append(chunk[b, :, :keep[b]].clone())
                 req._emitted += keep[b]

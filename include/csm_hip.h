@@ -455,6 +455,36 @@ int csm_attn_window_stream_rows_f32(const float* qkv, float* kcache, float* vcac
 /* out[b][c][r] = in[b][r][c] for b < batch */
 int csm_transpose_rows_f32(const float* in, float* out, int batch, int R, int C, csm_stream_t stream);
 
+/* Band-limited sample-rate conversion (csrc/resample.hip), additive since ABI 3: the windowed-sinc polyphase interpolation of
+ * csm.data.resample.  A rate pair is given reduced - o / n = sr_in / sr_out in lowest terms - with its filter half-width `width`
+ * in input samples; T = 2 * width + o taps per phase; taps = [n][T] fp32 on the device, built by the host.
+ *     y[j] = sum_{t = 0 .. T-1} taps[j mod n][t] * xbar[(j div n) * o - width + t],   xbar = x inside [0, N), 0 outside,
+ * summed in fp32 by one fmaf chain in ascending t - in every form below, so the forms agree bit for bit.
+ * Refused for every form: o == n (equal rates), o / n not in lowest terms, T > 2048, n * T > 4 Mi table entries (16 MB).  Tables
+ * of up to 14336 padded floats (56 KB) are staged in LDS, larger ones are read from global memory.
+ * One-shot: x [R][N] -> y [R][M], M = ceil(n * N / o); N == 0 launches nothing. */
+int csm_resample_f32(const float* x, const float* taps, float* y, int R, long long N, int o, int n, int width, csm_stream_t stream);
+/* R = 1..16 streams in ONE launch.  `x` (R device pointers), `slots`, `parity`, `n_in` and `pos` are HOST arrays of R entries,
+ * handed to the kernel by value: no device buffer, no copy, no synchronisation, nothing read back.  Row r continues the stream of
+ * slot slots[r] (all distinct, in [0, n_slots)) with its next n_in[r] samples x[r][0 .. n_in[r]); pos[r] is the number of samples
+ * the stream had before this call (the caller's integer mirror).  carry_arena = [n_slots][2][T - 1]: buffer parity[r] of the slot
+ * holds the stream's last T - 1 samples (all zeros for a new stream: the caller zeroes the slot when it opens it) and the next
+ * carry goes to buffer parity[r] ^ 1 (the caller flips its per-slot parity after the step).
+ * After N' samples the output blocks q < max(0, floor((N' - width - o) / o) + 1) are computable (n outputs each); the call writes
+ * the outputs of the blocks that became computable to y[r][0 ..) (y = [R][ldy]) - the caller knows how many from the same
+ * integers.  Bit r of
+ * final_mask: row r's stream ends with this call - the samples past its end are zeros and it emits every remaining j < M of its
+ * total length.  Every output has the bits csm_resample_f32 gives it for the same absolute j, however the input was cut.
+ * Refused, with nothing launched: R outside 1..16, a slot out of range or named twice, a parity other than 0 / 1, a mask bit at
+ * or above R, n_in[r] above max_in (the capacity the stream was made with) or below 1 (0 is allowed with the row's final bit: a
+ * flush with nothing new), a row that would emit more than ldy outputs, a negative position. */
+int csm_resample_stream_rows_f32(float* carry_arena, const float* const* x, const float* taps, float* y, long long ldy, int R,
+                                 const int* slots, const int* parity, const int* n_in, const long long* pos, unsigned final_mask,
+                                 int n_slots, int max_in, int o, int n, int width, csm_stream_t stream);
+/* The same for one stream: carry = [2][T - 1]; csm_resample_stream_rows_f32 with R = 1, slot 0 of 1. */
+int csm_resample_stream_f32(float* carry, int parity, const float* x, int n_in, long long pos, int final, const float* taps, float* y,
+                            long long ldy, int max_in, int o, int n, int width, csm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

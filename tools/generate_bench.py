@@ -22,7 +22,8 @@ the first chunk when all 16 end together, ``end_heard`` against 16 ``end`` calls
 through a Conversation (KV cache kept between turns) and statelessly (generate_stream with the accumulated Segment list - every
 turn encodes and prefills the whole history again), alternated in one process after a warm-up dialogue of each: per spoken turn the
 host time from the call to the first chunk (chunk_frames=2) and the turn's total; plus csm_attn_append alone next to the
-csm_attn_fwd launch that would recompute the whole sequence.  GEN_OVERFLOW=1: a conversation past the length limit
+csm_attn_fwd launch that would recompute the whole sequence.  GEN_RESAMPLE=1: the 16-slot server step with output_sample_rate=48000 and the 16-listener hear_step at 16 kHz input, each
+against the same step without the resampler (resample_main).  GEN_OVERFLOW=1: a conversation past the length limit
 (max_audio_length_ms = 90 000: 923 positions) - time to the first chunk of the overflowing turn under on_overflow="drop_oldest"
 (the kept history is prefilled again) and "shift" (the KV cache slides: csm_kv_shift) next to an in-limit turn, at B = 1 and for
 16 conversations that overflow at one boundary of the 16-slot server, plus csm_kv_shift alone (overflow_main)."""
@@ -1251,7 +1252,69 @@ def overflow_main():
               f"(resume_row of {L} positions alone {med(res_only):.3f} ms, taken off)")
 
 
+def resample_main():
+    """GEN_RESAMPLE=1: the device resampler on the serving paths, CSM-1B random init, 16 slots, chunk_frames 4.  (a) the steady
+    16-row server step of GEN_SERVE's setting with ``output_sample_rate=48000`` (one rows resampler launch per step) against the
+    same step without it; (b) the 16-listener ``hear_step`` (16 feeds of one 320 ms chunk + the step; nobody speaks) with
+    ``hear(sample_rate=16000)`` against 24 kHz input.  Each leg is a fresh server, the two alternated GEN_ROUNDS times (default 3),
+    per repeat the median of 20 steps / 12 chunks; the difference is reported next to the base's own repeat-to-repeat spread."""
+    dev = "cuda:0"
+    n, NC = 4, 16
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=make_codec(dev))
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+    med = lambda xs: sorted(xs)[len(xs) // 2]                                                           # noqa: E731
+
+    def report(what, unit, res, base, other):
+        for name, v in res.items():
+            print(f"GEN_RESAMPLE {what}, {name}: medians {[round(x * 1e3, 3) for x in v]} ms -> median {med(v) * 1e3:.3f} ms, spread of "
+                  f"the repeats {(max(v) - min(v)) * 1e3:.3f} ms", flush=True)
+        d = med(res[other]) - med(res[base])
+        print(f"GEN_RESAMPLE {what}: {other} - {base}: {d * 1e3:+.3f} ms per {unit} ({base}'s own repeats span "
+              f"{(max(res[base]) - min(res[base])) * 1e3:.3f} ms)", flush=True)
+
+    # ---- (a) speaking: the server step
+    res = {"24 kHz out (off)": [], "48 kHz out": []}
+    for _ in range(rounds):
+        for name, rate in (("24 kHz out (off)", None), ("48 kHz out", 48000)):
+            srv = gen.serve(slots=NC, chunk_frames=n, output_sample_rate=rate)
+            reqs = [srv.submit(f"utterance number {i}: {text}", i, ctx, seed=i, max_audio_length_ms=80 * 400) for i in range(NC)]
+            _timed(srv.step, 1)                                              # 16 prefills + the first chunk
+            _timed(srv.step, 2)                                              # eager warm-up frame, graph capture
+            steps = sorted(_timed(srv.step, 1) for _ in range(20))
+            res[name].append(steps[len(steps) // 2])
+            assert reqs[0].sample_rate == (rate or 24000) and reqs[0].chunks[-1].numel() in (n * 1920, 2 * n * 1920)
+    report(f"(a) server step, {NC} rows x {n} frames", "step", res, "24 kHz out (off)", "48 kHz out")
+    # ---- (b) hearing: 16 listeners, one 320 ms chunk each per hear_step
+    res = {"24 kHz in (off)": [], "16 kHz in": []}
+    g = torch.Generator(device=dev).manual_seed(1)
+    for _ in range(rounds):
+        for name, rate in (("24 kHz in (off)", None), ("16 kHz in", 16000)):
+            piece = n * 1920 * (rate or 24000) // 24000
+            heard = [torch.randn(14 * piece, device=dev, generator=g) * 0.1 for _ in range(NC)]
+            srv = gen.serve(slots=NC, chunk_frames=n, hear_slots=NC)
+            turns = [srv.conversation().hear(1, sample_rate=rate) for _ in range(NC)]
+            chunks = []
+            for c in range(14):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i, t in enumerate(turns):
+                    t.feed(heard[i][c * piece:(c + 1) * piece])
+                srv.hear_step()
+                torch.cuda.synchronize()
+                chunks.append(time.perf_counter() - t0)
+            assert all(t.frames >= 13 * n for t in turns)
+            res[name].append(med(chunks[2:]))                                # (the first pieces warm the encoder's buffers)
+            for t in turns:
+                t.cancel()
+    report(f"(b) hear_step, {NC} listeners x {n} frames", "chunk", res, "24 kHz in (off)", "16 kHz in")
+
+
 def main():
+    if os.environ.get("GEN_RESAMPLE") == "1":
+        return resample_main()
     if os.environ.get("GEN_OVERFLOW") == "1":
         return overflow_main()
     if os.environ.get("GEN_HEAR") == "rows":

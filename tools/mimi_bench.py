@@ -2,12 +2,52 @@
 """Mimi codec on the GPU: encode / decode time for 10 s of 24 kHz audio (seeded random weights with the HF key names), then
 the streaming decoder: microseconds per ``MimiDecodeStream.step`` of n = 1, 2, 4 frames and the kernel launches per step, then
 the streaming encoder: ``encode`` of 5 s next to microseconds per ``MimiEncodeStream.step`` of n = 1, 2, 4 frames, then the rows
-encoder: one ``MimiEncodeStreamRows.step`` of R = 1 / 4 / 16 rows at n = 4 against R consecutive ``MimiEncodeStream.step`` calls.
-MIMI_BENCH=rows runs the rows leg alone."""
+encoder: one ``MimiEncodeStreamRows.step`` of R = 1 / 4 / 16 rows at n = 4 against R consecutive ``MimiEncodeStream.step`` calls,
+then the device resampler: one ``ResampleStreamRows.step`` of R = 1 / 4 / 16 rows for a 320 ms chunk against R one-row launches.
+MIMI_BENCH=rows runs the rows leg alone, MIMI_BENCH=resample the resampler leg alone (no codec is built)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
 import torch
+
+
+def resample_leg():
+    """One rows launch at R = 1 / 4 / 16 for a 320 ms chunk against R one-row launches (``ResampleStream.feed``), alternated
+    three times in this job: 200 back-to-back steps between two synchronisations, median and spread of the repeats."""
+    from csm.codec.resample import Resampler
+    for (a, b), n_in in (((24000, 48000), 7680), ((16000, 24000), 5120), ((44100, 24000), 14112)):
+        rs = Resampler(a, b, device="cuda")
+        for R in (1, 4, 16):
+            g = torch.Generator().manual_seed(R)
+            xs = [(torch.randn(n_in, generator=g) * 0.1).cuda() for _ in range(R)]
+            rows, singles = rs.stream_rows(16, n_in), [rs.stream(n_in) for _ in range(R)]
+            slots = list(range(R))
+            for s_ in slots:
+                rows.open(s_)
+            legs = {"rows": lambda: rows.step(slots, xs), "single": lambda: [singles[r].feed(xs[r]) for r in range(R)]}
+            res = {"rows": [], "single": []}
+            for _ in range(3):
+                for name, fn in legs.items():
+                    for _ in range(20):
+                        out = fn()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(200):
+                        out = fn()
+                    torch.cuda.synchronize()
+                    res[name].append((time.perf_counter() - t0) / 200 * 1e6)
+                    if name == "rows": got = out
+            same = all(torch.equal(got[r], out[r]) for r in range(R))        # both ran 660 steps from position 0 on the same audio
+            med = {k: sorted(v)[1] for k, v in res.items()}
+            print(f"resample {a} -> {b} rows step R={R:2d} n_in={n_in}: {med['rows']:.1f} us per step (repeats "
+                  f"{[round(v, 1) for v in res['rows']]}), 1 launch; {R} one-row launches {med['single']:.1f} us (repeats "
+                  f"{[round(v, 1) for v in res['single']]}) -> {med['single'] / med['rows']:.2f}x; outputs "
+                  f"{'equal' if same else 'DIFFER'}", flush=True)
+
+
+if os.environ.get("MIMI_BENCH") == "resample":
+    resample_leg()
+    sys.exit(0)
 from transformers import MimiConfig, MimiModel
 from csm.codec import MimiCodec
 
@@ -124,3 +164,5 @@ for R in (1, 4, 16):
     print(f"encode rows step R={R:2d} n={n}: {best['rows']:.0f} us per step, {counters[0].n + counters[1].n} launches; {R} single "
           f"steps {best['single']:.0f} us -> {best['single'] / best['rows']:.2f}x ({best['rows'] / best['single'] * R:.2f} single steps "
           f"for {R} rows); codes {'equal' if same else 'DIFFER'}", flush=True)
+
+resample_leg()
