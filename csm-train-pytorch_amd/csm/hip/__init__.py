@@ -76,6 +76,8 @@ _SIGS = {
     "csm_clip_coef": ([_p, _i, _f, _p, _p], _i),
     "csm_adamw_step": ([_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _f, _i, _p, _f, _i, _p], _i),
     "csm_adamw_step_split": ([_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _f, _i, _p, _f, _i, _p], _i),
+    "csm_adamw_step_live": ([_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _f, _i, _p, _f, _i, _p, _p], _i),
+    "csm_adamw_step_split_live": ([_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _f, _i, _p, _f, _i, _p, _p], _i),
     "csm_set_adamw_blocks": ([_i], _i),
     "csm_gemv_bf16": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_gemv_bf16_kext": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _i, _p, _p, _i, _i, _i, _p, _p], _i),

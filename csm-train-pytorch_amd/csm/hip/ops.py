@@ -434,19 +434,38 @@ def clip_coef(partials, max_norm, norm_and_coef):
     check(lib.csm_clip_coef(partials.data_ptr(), partials.numel(), float(max_norm), norm_and_coef.data_ptr(), _stream()), "csm_clip_coef")
 
 
-def adamw_step(master, m, v, param, grad, lr, beta1, beta2, eps, wd, step, norm_and_coef=None, grad_mul=1.0, zero_grad=False):
+ADAMW_BLOCK = 2048                     # elements per ``block_live`` flag of the flagged AdamW entries
+
+
+def _live_ptr(block_live, n):
+    assert block_live.dtype == torch.uint8 and block_live.is_contiguous() and block_live.numel() == -(-n // ADAMW_BLOCK)
+    return block_live.data_ptr()
+
+
+def adamw_step(master, m, v, param, grad, lr, beta1, beta2, eps, wd, step, norm_and_coef=None, grad_mul=1.0, zero_grad=False, *,
+               block_live=None):
+    """``block_live`` (uint8, one per 2048 elements, 0 = "m and v of this block are all-zero bits"): blocks that are not live and
+    get an all-zero gradient only have their weights decayed; same bits out as without it (csm_adamw_step_live)."""
     n = master.numel()
     assert master.dtype == torch.float32 and param.dtype == BF16 and grad.dtype == BF16 and param.numel() == n == grad.numel()
-    check(lib.csm_adamw_step(master.data_ptr(), m.data_ptr(), v.data_ptr(), param.data_ptr(), grad.data_ptr(), n, lr, beta1,
-                             beta2, eps, wd, int(step), _ptr(norm_and_coef), float(grad_mul), int(zero_grad), _stream()), "csm_adamw_step")
+    args = (master.data_ptr(), m.data_ptr(), v.data_ptr(), param.data_ptr(), grad.data_ptr(), n, lr, beta1, beta2, eps, wd, int(step),
+            _ptr(norm_and_coef), float(grad_mul), int(zero_grad))
+    if block_live is None:
+        check(lib.csm_adamw_step(*args, _stream()), "csm_adamw_step")
+    else:
+        check(lib.csm_adamw_step_live(*args, _live_ptr(block_live, n), _stream()), "csm_adamw_step_live")
 
 
-def adamw_step_split(master_lo, m, v, param, grad, lr, beta1, beta2, eps, wd, step, norm_and_coef=None, grad_mul=1.0, zero_grad=False):
+def adamw_step_split(master_lo, m, v, param, grad, lr, beta1, beta2, eps, wd, step, norm_and_coef=None, grad_mul=1.0, zero_grad=False, *,
+                     block_live=None):
     n = master_lo.numel()
     assert master_lo.dtype == torch.int16 and param.dtype == BF16 and grad.dtype == BF16 and param.numel() == n == grad.numel()
-    check(lib.csm_adamw_step_split(master_lo.data_ptr(), m.data_ptr(), v.data_ptr(), param.data_ptr(), grad.data_ptr(), n, lr, beta1,
-                                   beta2, eps, wd, int(step), _ptr(norm_and_coef), float(grad_mul), int(zero_grad), _stream()),
-          "csm_adamw_step_split")
+    args = (master_lo.data_ptr(), m.data_ptr(), v.data_ptr(), param.data_ptr(), grad.data_ptr(), n, lr, beta1, beta2, eps, wd, int(step),
+            _ptr(norm_and_coef), float(grad_mul), int(zero_grad))
+    if block_live is None:
+        check(lib.csm_adamw_step_split(*args, _stream()), "csm_adamw_step_split")
+    else:
+        check(lib.csm_adamw_step_split_live(*args, _live_ptr(block_live, n), _stream()), "csm_adamw_step_split_live")
 
 
 def gemv(x, W, y, residual=None):

@@ -10,6 +10,12 @@ Master weights are fp32 but not stored as such: the bf16 working copy IS the upp
 half-up) and a 16-bit ``lo`` tensor holds the lower half, master = ((hi - (lo >> 15)) << 16) | lo exactly - 26 instead of
 28 bytes of HBM traffic per parameter and step and 2 bytes less state (``CSM_ADAMW_SPLIT=0`` restores the plain fp32
 master for A/B).  ``state_dict`` / ``named_master`` still speak fp32 masters, so checkpoints keep their format.
+
+The ``embeddings`` group is mostly rows that never get a gradient (text tokens the data never uses): their m, v and gradient
+are zero on every step and their whole update is the weight decay.  ``FusedAdamW`` keeps one flag byte per 2048 elements of that
+group ("this block has had a gradient"), and the kernel moves only the weights of a block that is not live and whose gradient
+is all-zero bits: 10 instead of 26 bytes per parameter, the same bits out (``CSM_ADAMW_DEAD_BLOCKS=0`` runs the un-flagged
+kernel for A/B).
 """
 import os
 from typing import Dict, List, Optional
@@ -20,6 +26,7 @@ from ..hip import ops
 
 F32 = torch.float32
 SPLIT_MASTER = os.environ.get("CSM_ADAMW_SPLIT", "1") == "1"
+FLAGGED_GROUPS = ("embeddings",)        # the groups whose rows mostly never see a gradient
 
 
 def split_master(master: torch.Tensor, param_out: torch.Tensor) -> torch.Tensor:
@@ -71,8 +78,23 @@ def _span_end(v: torch.Tensor, so: int) -> int:
     return so + sum((sz - 1) * st for sz, st in zip(v.size(), v.stride())) + 1
 
 
+def live_blocks(m: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """One uint8 per ``ops.ADAMW_BLOCK`` elements (the last block may be partial): any bit set in ``m`` or ``v`` (-0 counts)."""
+    bits, B = m.view(torch.int32) | v.view(torch.int32), ops.ADAMW_BLOCK
+    full = bits.numel() // B * B
+    live = [bits[:full].view(-1, B).any(dim=1)]
+    if full < bits.numel():
+        live.append(bits[full:].any().reshape(1))
+    return torch.cat(live).to(torch.uint8)
+
+
 class FusedAdamW:
+    """``state[name]["live"]`` (the groups of ``FLAGGED_GROUPS`` only) holds the kernel's block flags: 0 promises that every bit of
+    ``m`` and ``v`` in that block is zero.  The kernel keeps them while it is the only writer of the moments.  Whoever else writes
+    ``state[name]["m"]`` or ``["v"]`` (``load_state_dict`` does) must call ``moments_rewritten()`` afterwards, or a block with
+    moments could be taken for a dead one.  The flags are derived state and are never saved."""
     sharded = False
+    dead_blocks = True
 
     def __init__(self, model, group_lrs: Dict[str, float], weight_decay: float = 0.01, betas=(0.9, 0.999),
                  eps: float = 1e-8, lora_lr: Optional[float] = None, lora_weight_decay: float = 0.0):
@@ -82,6 +104,7 @@ class FusedAdamW:
         self.state: Dict[str, Dict[str, torch.Tensor]] = {}
         self.step_count = 0
         self._coef: Optional[torch.Tensor] = None
+        self.dead_blocks = os.environ.get("CSM_ADAMW_DEAD_BLOCKS", "1") == "1"      # 0: the un-flagged kernels everywhere (A/B)
         model.ensure_grads()
         for name, lr in group_lrs.items():
             if lr is None or not model.trainable.get(name, False):
@@ -101,6 +124,8 @@ class FusedAdamW:
                 del master
             else:
                 self.state[g["name"]] = dict(master=master, m=torch.zeros_like(master), v=torch.zeros_like(master))
+            if self.dead_blocks and g["name"] in FLAGGED_GROUPS:          # zero moments: no block is live yet
+                self.state[g["name"]]["live"] = torch.zeros(-(-g["numel"] // ops.ADAMW_BLOCK), dtype=torch.uint8, device=g["param"].device)
         self._partials = torch.empty(max(1, len(self.param_groups)) * ops.sumsq_blocks(), dtype=F32, device=model.device)
         self._norm_coef = torch.ones(2, dtype=F32, device=model.device)
         # the model tells its optimisers when somebody rewrites the working weights behind their back (params_rewritten)
@@ -111,6 +136,13 @@ class FusedAdamW:
 
     def _seed_master(self, g, from_fp32_source: bool = False) -> torch.Tensor:
         return seed_master(self.model, g["offset"], g["numel"], g["param"], from_fp32_source and g["name"] != "lora")
+
+    def moments_rewritten(self):
+        """Rebuild the block flags of the flagged groups from the moments as they are now: call after writing ``m`` or ``v``."""
+        for name in FLAGGED_GROUPS:
+            if self.dead_blocks and name in self.state:
+                st = self.state[name]
+                st["live"] = live_blocks(st["m"], st["v"])
 
     def named_master(self):
         """(reference parameter name, fp32 master view) for every trainable base parameter."""
@@ -201,10 +233,10 @@ class FusedAdamW:
             zero = bool(zero_grad) if zero_grad != "lazy" else (name == "embeddings" or name not in gs)
             if "lo" in st:
                 ops.adamw_step_split(st["lo"], st["m"], st["v"], g["param"], g["grad"], g["lr"], b1, b2, self.eps,
-                                     g["weight_decay"], self.step_count, self._coef, zero_grad=zero)
+                                     g["weight_decay"], self.step_count, self._coef, zero_grad=zero, block_live=st.get("live"))
             else:
                 ops.adamw_step(st["master"], st["m"], st["v"], g["param"], g["grad"], g["lr"], b1, b2, self.eps,
-                               g["weight_decay"], self.step_count, self._coef, zero_grad=zero)
+                               g["weight_decay"], self.step_count, self._coef, zero_grad=zero, block_live=st.get("live"))
             if name in gs:
                 if zero:
                     gs[name] = "zero"
@@ -231,6 +263,7 @@ class FusedAdamW:
                 "groups": [{k: g[k] for k in ("name", "lr", "weight_decay", "offset", "numel")} for g in self.param_groups],
                 # (fp32 masters whatever the in-memory form: the checkpoint format does not depend on CSM_ADAMW_SPLIT)
                 "state": {n: {"master": self.master(n).cpu(), "m": st["m"].cpu(), "v": st["v"].cpu()} for n, st in self.state.items()}}
+        # (the block flags are not saved: load_state_dict derives them from the moments)
 
     def load_state_dict(self, sd):
         """Groups are matched by NAME (backbone / decoder / embeddings / other / lora), never by position: resuming with
@@ -251,6 +284,7 @@ class FusedAdamW:
                     self.set_master(n, v)
                 else:
                     self.state[n][k].copy_(v)
+        self.moments_rewritten()
         for g in self.param_groups:
             saved = saved_by_name[g["name"]]
             g["lr"], g["weight_decay"] = saved["lr"], saved["weight_decay"]

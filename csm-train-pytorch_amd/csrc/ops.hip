@@ -606,17 +606,29 @@ __global__ __launch_bounds__(1024) void clip_coef_kernel(const float* __restrict
     }
 }
 
-// One element of torch.optim.AdamW (decoupled decay, bias-corrected, eps outside the sqrt ratio).  Floating-point contraction
-// is off so that every kernel that inlines this rounds exactly the same way (csm_adamw_step and csm_adamw_step_split are
-// bit-identical in master / m / v).
-__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, float lr, float beta1, float beta2, float eps,
-                                            float wd, float bc1, float bc2_sqrt) {
+// One element of torch.optim.AdamW (decoupled decay, bias-corrected, eps outside the sqrt ratio), in two parts.  Floating-point
+// contraction is off so that every kernel that inlines them rounds exactly the same way (csm_adamw_step and csm_adamw_step_split
+// are bit-identical in master / m / v).  adam_decay alone is the whole update of an element whose m, v and gradient are zero.
+__device__ __forceinline__ float adam_decay(float p, float lr, float wd) {
 #pragma clang fp contract(off)
-    p = p * (1.f - lr * wd);
+    return p * (1.f - lr * wd);
+}
+
+// m and v move on; -> what the decayed weight loses
+__device__ __forceinline__ float adam_moments(float& m, float& v, float g, float lr, float beta1, float beta2, float eps, float bc1,
+                                              float bc2_sqrt) {
+#pragma clang fp contract(off)
     m = beta1 * m + (1.f - beta1) * g;
     v = beta2 * v + ((1.f - beta2) * g) * g;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = p - (lr / bc1) * (m / denom);
+    return (lr / bc1) * (m / denom);
+}
+
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, float lr, float beta1, float beta2, float eps,
+                                            float wd, float bc1, float bc2_sqrt) {
+#pragma clang fp contract(off)
+    p = adam_decay(p, lr, wd);
+    p = p - adam_moments(m, v, g, lr, beta1, beta2, eps, bc1, bc2_sqrt);
 }
 
 // A NEGATIVE clip coefficient on the device (norm_and_coef[1] < 0) means "this optimiser step does not happen": weights and
@@ -627,6 +639,37 @@ __device__ __forceinline__ void adamw_skipped(bf16_t* __restrict__ grad, long lo
     if (!zero_grad) return;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long long)gridDim.x * blockDim.x)
         *reinterpret_cast<U4*>(grad + i * 8) = (U4){0u, 0u, 0u, 0u};
+}
+
+// the scalars of one AdamW launch
+struct AdamArgs {
+    float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, coef;
+    int zero_grad;
+};
+
+// One 8-element vector of the plain form: the loop body of adamw_kernel and of the live blocks of adamw_live_kernel.
+__device__ __forceinline__ void adamw_vec(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
+                                          bf16_t* __restrict__ param, bf16_t* __restrict__ grad, long long i, const AdamArgs& a) {
+    float g[8];
+    unpack8(*reinterpret_cast<const U4*>(grad + i * 8), g);
+    float4 p0 = *reinterpret_cast<const float4*>(master + i * 8), p1 = *reinterpret_cast<const float4*>(master + i * 8 + 4);
+    float4 m0 = *reinterpret_cast<const float4*>(m + i * 8), m1 = *reinterpret_cast<const float4*>(m + i * 8 + 4);
+    float4 v0 = *reinterpret_cast<const float4*>(v + i * 8), v1 = *reinterpret_cast<const float4*>(v + i * 8 + 4);
+    float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+    float mm[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+    float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        adam_update(p[j], mm[j], vv[j], g[j] * a.coef, a.lr, a.beta1, a.beta2, a.eps, a.wd, a.bc1, a.bc2_sqrt);
+    }
+    *reinterpret_cast<float4*>(master + i * 8) = make_float4(p[0], p[1], p[2], p[3]);
+    *reinterpret_cast<float4*>(master + i * 8 + 4) = make_float4(p[4], p[5], p[6], p[7]);
+    *reinterpret_cast<float4*>(m + i * 8) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+    *reinterpret_cast<float4*>(m + i * 8 + 4) = make_float4(mm[4], mm[5], mm[6], mm[7]);
+    *reinterpret_cast<float4*>(v + i * 8) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+    *reinterpret_cast<float4*>(v + i * 8 + 4) = make_float4(vv[4], vv[5], vv[6], vv[7]);
+    *reinterpret_cast<U4*>(param + i * 8) = pack8(p);
+    if (a.zero_grad) *reinterpret_cast<U4*>(grad + i * 8) = (U4){0u, 0u, 0u, 0u};
 }
 
 // torch.optim.AdamW over one contiguous parameter range: fp32 master / m / v, bf16 gradient (times the device-side
@@ -640,28 +683,44 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, 
     const float coef = (coef_ptr ? coef_ptr[1] : 1.f) * gmul;
     const long long nvec = n >> 3;
     if (coef_ptr && coef_ptr[1] < 0.f) { adamw_skipped(grad, nvec, zero_grad); return; }
+    const AdamArgs a = {lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, coef, zero_grad};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long long)gridDim.x * blockDim.x) {
-        float g[8];
-        unpack8(*reinterpret_cast<const U4*>(grad + i * 8), g);
-        float4 p0 = *reinterpret_cast<const float4*>(master + i * 8), p1 = *reinterpret_cast<const float4*>(master + i * 8 + 4);
-        float4 m0 = *reinterpret_cast<const float4*>(m + i * 8), m1 = *reinterpret_cast<const float4*>(m + i * 8 + 4);
-        float4 v0 = *reinterpret_cast<const float4*>(v + i * 8), v1 = *reinterpret_cast<const float4*>(v + i * 8 + 4);
-        float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
-        float mm[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-        float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            adam_update(p[j], mm[j], vv[j], g[j] * coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
-        }
-        *reinterpret_cast<float4*>(master + i * 8) = make_float4(p[0], p[1], p[2], p[3]);
-        *reinterpret_cast<float4*>(master + i * 8 + 4) = make_float4(p[4], p[5], p[6], p[7]);
-        *reinterpret_cast<float4*>(m + i * 8) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        *reinterpret_cast<float4*>(m + i * 8 + 4) = make_float4(mm[4], mm[5], mm[6], mm[7]);
-        *reinterpret_cast<float4*>(v + i * 8) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        *reinterpret_cast<float4*>(v + i * 8 + 4) = make_float4(vv[4], vv[5], vv[6], vv[7]);
-        *reinterpret_cast<U4*>(param + i * 8) = pack8(p);
-        if (zero_grad) *reinterpret_cast<U4*>(grad + i * 8) = (U4){0u, 0u, 0u, 0u};
+        adamw_vec(master, m, v, param, grad, i, a);
     }
+}
+
+// One 8-element vector of the split form (below): the loop body of adamw_split_kernel and of adamw_split_live_kernel's live blocks.
+__device__ __forceinline__ void adamw_split_vec(uint16_t* __restrict__ lo, float* __restrict__ m, float* __restrict__ v,
+                                                bf16_t* __restrict__ param, bf16_t* __restrict__ grad, long long i, const AdamArgs& a) {
+    float g[8];
+    unpack8(*reinterpret_cast<const U4*>(grad + i * 8), g);
+    const U4 hw = *reinterpret_cast<const U4*>(param + i * 8), lw = *reinterpret_cast<const U4*>(lo + i * 8);
+    float4 m0 = *reinterpret_cast<const float4*>(m + i * 8), m1 = *reinterpret_cast<const float4*>(m + i * 8 + 4);
+    float4 v0 = *reinterpret_cast<const float4*>(v + i * 8), v1 = *reinterpret_cast<const float4*>(v + i * 8 + 4);
+    const uint32_t hww[4] = {hw.x, hw.y, hw.z, hw.w}, lww[4] = {lw.x, lw.y, lw.z, lw.w};
+    float p[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint32_t h16 = (hww[j >> 1] >> ((j & 1) * 16)) & 0xffffu, l16 = (lww[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+        p[j] = __uint_as_float(((h16 - (l16 >> 15)) << 16) | l16);
+    }
+    float mm[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+    float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+    uint32_t ho[4] = {0u, 0u, 0u, 0u}, lout[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        adam_update(p[j], mm[j], vv[j], g[j] * a.coef, a.lr, a.beta1, a.beta2, a.eps, a.wd, a.bc1, a.bc2_sqrt);
+        const uint32_t bits = __float_as_uint(p[j]);
+        ho[j >> 1] |= (((bits + 0x8000u) >> 16) & 0xffffu) << ((j & 1) * 16);
+        lout[j >> 1] |= (bits & 0xffffu) << ((j & 1) * 16);
+    }
+    *reinterpret_cast<float4*>(m + i * 8) = make_float4(mm[0], mm[1], mm[2], mm[3]);
+    *reinterpret_cast<float4*>(m + i * 8 + 4) = make_float4(mm[4], mm[5], mm[6], mm[7]);
+    *reinterpret_cast<float4*>(v + i * 8) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+    *reinterpret_cast<float4*>(v + i * 8 + 4) = make_float4(vv[4], vv[5], vv[6], vv[7]);
+    *reinterpret_cast<U4*>(param + i * 8) = (U4){ho[0], ho[1], ho[2], ho[3]};
+    *reinterpret_cast<U4*>(lo + i * 8) = (U4){lout[0], lout[1], lout[2], lout[3]};
+    if (a.zero_grad) *reinterpret_cast<U4*>(grad + i * 8) = (U4){0u, 0u, 0u, 0u};
 }
 
 // The same update with the fp32 master weight held as TWO 16-bit halves: the bf16 working copy IS the upper half (rounded
@@ -676,36 +735,104 @@ __global__ __launch_bounds__(256) void adamw_split_kernel(uint16_t* __restrict__
     const float coef = (coef_ptr ? coef_ptr[1] : 1.f) * gmul;
     const long long nvec = n >> 3;
     if (coef_ptr && coef_ptr[1] < 0.f) { adamw_skipped(grad, nvec, zero_grad); return; }
+    const AdamArgs a = {lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, coef, zero_grad};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long long)gridDim.x * blockDim.x) {
-        float g[8];
-        unpack8(*reinterpret_cast<const U4*>(grad + i * 8), g);
-        const U4 hw = *reinterpret_cast<const U4*>(param + i * 8), lw = *reinterpret_cast<const U4*>(lo + i * 8);
-        float4 m0 = *reinterpret_cast<const float4*>(m + i * 8), m1 = *reinterpret_cast<const float4*>(m + i * 8 + 4);
-        float4 v0 = *reinterpret_cast<const float4*>(v + i * 8), v1 = *reinterpret_cast<const float4*>(v + i * 8 + 4);
-        const uint32_t hww[4] = {hw.x, hw.y, hw.z, hw.w}, lww[4] = {lw.x, lw.y, lw.z, lw.w};
-        float p[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint32_t h16 = (hww[j >> 1] >> ((j & 1) * 16)) & 0xffffu, l16 = (lww[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
-            p[j] = __uint_as_float(((h16 - (l16 >> 15)) << 16) | l16);
+        adamw_split_vec(lo, m, v, param, grad, i, a);
+    }
+}
+
+// ---- the flagged forms: blocks of 2048 elements that never had a gradient move 10 instead of 28 (26) B/param ---------------
+// block_live[b] == 0 promises that every bit of m and v in block b of the range is zero.  If the block's gradient is all-zero
+// bits too, every element's update is the same one: m' and v' stay zero and the weight loses adam_moments(0, 0, 0 * coef).
+// adam_dead_exact asks whether those three are all-zero bits under this launch's scalars (they are for any sane ones; eps = 0
+// or a non-finite coefficient are among those that are not): then adam_decay is the element's whole update, bit for bit, and
+// m, v and the gradient need neither be read (m, v) nor written.  A gradient of -0 is a set bit: it takes the full path.
+__device__ __forceinline__ bool adam_dead_exact(const AdamArgs& a) {
+    float m = 0.f, v = 0.f;
+    const float t = adam_moments(m, v, 0.f * a.coef, a.lr, a.beta1, a.beta2, a.eps, a.bc1, a.bc2_sqrt);
+    return (__float_as_uint(m) | __float_as_uint(v) | __float_as_uint(t)) == 0u;
+}
+
+// One workgroup per 2048-element block and loop step (the last block may be partial; block_live has one byte per block, counted
+// from the start of the range).  A live block runs adamw_vec as the un-flagged kernel does.  A block not yet live loads what both
+// outcomes need, votes on "any gradient bit set", and either decays the weights or marks itself live and runs adamw_vec.
+__global__ __launch_bounds__(256) void adamw_live_kernel(float* __restrict__ master, float* __restrict__ m, float* __restrict__ v,
+                                                         bf16_t* __restrict__ param, bf16_t* __restrict__ grad, long long n,
+                                                         float lr, float beta1, float beta2, float eps, float wd, float bc1,
+                                                         float bc2_sqrt, const float* __restrict__ coef_ptr, float gmul,
+                                                         int zero_grad, uint8_t* block_live) {
+    const AdamArgs a = {lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, (coef_ptr ? coef_ptr[1] : 1.f) * gmul, zero_grad};
+    const long long nvec = n >> 3, nblk = (nvec + 255) >> 8;
+    if (coef_ptr && coef_ptr[1] < 0.f) { adamw_skipped(grad, nvec, zero_grad); return; }
+    const bool dead_exact = adam_dead_exact(a);
+    for (long long b = blockIdx.x; b < nblk; b += gridDim.x) {
+        const long long i = b * 256 + threadIdx.x;
+        const bool in = i < nvec;
+        const bool live = block_live[b] != 0;                 // uniform: every branch below that holds a barrier is too
+        U4 gw = {0u, 0u, 0u, 0u};
+        float4 p0 = {0.f, 0.f, 0.f, 0.f}, p1 = p0;
+        if (in) {
+            gw = *reinterpret_cast<const U4*>(grad + i * 8);
+            p0 = *reinterpret_cast<const float4*>(master + i * 8), p1 = *reinterpret_cast<const float4*>(master + i * 8 + 4);
         }
-        float mm[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-        float vv[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        uint32_t ho[4] = {0u, 0u, 0u, 0u}, lout[4] = {0u, 0u, 0u, 0u};
+        if (!live) {
+            const bool any = __syncthreads_or((gw.x | gw.y | gw.z | gw.w) != 0u) != 0;
+            if (!any && dead_exact) {
+                if (in) {
+                    float p[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            adam_update(p[j], mm[j], vv[j], g[j] * coef, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
-            const uint32_t bits = __float_as_uint(p[j]);
-            ho[j >> 1] |= (((bits + 0x8000u) >> 16) & 0xffffu) << ((j & 1) * 16);
-            lout[j >> 1] |= (bits & 0xffffu) << ((j & 1) * 16);
+                    for (int j = 0; j < 8; ++j) p[j] = adam_decay(p[j], lr, wd);
+                    *reinterpret_cast<float4*>(master + i * 8) = make_float4(p[0], p[1], p[2], p[3]);
+                    *reinterpret_cast<float4*>(master + i * 8 + 4) = make_float4(p[4], p[5], p[6], p[7]);
+                    *reinterpret_cast<U4*>(param + i * 8) = pack8(p);
+                }
+                continue;
+            }
+            if (threadIdx.x == 0) block_live[b] = 1;
         }
-        *reinterpret_cast<float4*>(m + i * 8) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        *reinterpret_cast<float4*>(m + i * 8 + 4) = make_float4(mm[4], mm[5], mm[6], mm[7]);
-        *reinterpret_cast<float4*>(v + i * 8) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-        *reinterpret_cast<float4*>(v + i * 8 + 4) = make_float4(vv[4], vv[5], vv[6], vv[7]);
-        *reinterpret_cast<U4*>(param + i * 8) = (U4){ho[0], ho[1], ho[2], ho[3]};
-        *reinterpret_cast<U4*>(lo + i * 8) = (U4){lout[0], lout[1], lout[2], lout[3]};
-        if (zero_grad) *reinterpret_cast<U4*>(grad + i * 8) = (U4){0u, 0u, 0u, 0u};
+        if (in) adamw_vec(master, m, v, param, grad, i, a);
+    }
+}
+
+__global__ __launch_bounds__(256) void adamw_split_live_kernel(uint16_t* __restrict__ lo, float* __restrict__ m, float* __restrict__ v,
+                                                               bf16_t* __restrict__ param, bf16_t* __restrict__ grad, long long n,
+                                                               float lr, float beta1, float beta2, float eps, float wd, float bc1,
+                                                               float bc2_sqrt, const float* __restrict__ coef_ptr, float gmul,
+                                                               int zero_grad, uint8_t* block_live) {
+    const AdamArgs a = {lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, (coef_ptr ? coef_ptr[1] : 1.f) * gmul, zero_grad};
+    const long long nvec = n >> 3, nblk = (nvec + 255) >> 8;
+    if (coef_ptr && coef_ptr[1] < 0.f) { adamw_skipped(grad, nvec, zero_grad); return; }
+    const bool dead_exact = adam_dead_exact(a);
+    for (long long b = blockIdx.x; b < nblk; b += gridDim.x) {
+        const long long i = b * 256 + threadIdx.x;
+        const bool in = i < nvec;
+        const bool live = block_live[b] != 0;
+        U4 gw = {0u, 0u, 0u, 0u}, hw = gw, lw = gw;
+        if (in) {
+            gw = *reinterpret_cast<const U4*>(grad + i * 8);
+            hw = *reinterpret_cast<const U4*>(param + i * 8), lw = *reinterpret_cast<const U4*>(lo + i * 8);
+        }
+        if (!live) {
+            const bool any = __syncthreads_or((gw.x | gw.y | gw.z | gw.w) != 0u) != 0;
+            if (!any && dead_exact) {
+                if (in) {
+                    const uint32_t hww[4] = {hw.x, hw.y, hw.z, hw.w}, lww[4] = {lw.x, lw.y, lw.z, lw.w};
+                    uint32_t ho[4] = {0u, 0u, 0u, 0u}, lout[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const uint32_t h16 = (hww[j >> 1] >> ((j & 1) * 16)) & 0xffffu, l16 = (lww[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+                        const uint32_t bits = __float_as_uint(adam_decay(__uint_as_float(((h16 - (l16 >> 15)) << 16) | l16), lr, wd));
+                        ho[j >> 1] |= (((bits + 0x8000u) >> 16) & 0xffffu) << ((j & 1) * 16);
+                        lout[j >> 1] |= (bits & 0xffffu) << ((j & 1) * 16);
+                    }
+                    *reinterpret_cast<U4*>(param + i * 8) = (U4){ho[0], ho[1], ho[2], ho[3]};
+                    *reinterpret_cast<U4*>(lo + i * 8) = (U4){lout[0], lout[1], lout[2], lout[3]};
+                }
+                continue;
+            }
+            if (threadIdx.x == 0) block_live[b] = 1;
+        }
+        if (in) adamw_split_vec(lo, m, v, param, grad, i, a);
     }
 }
 
@@ -957,5 +1084,38 @@ extern "C" int csm_adamw_step_split(void* master_lo, float* m, float* v, void* p
     hipLaunchKernelGGL(adamw_split_kernel, dim3(grid_for(n >> 3, 256, g_adamw_blocks)), dim3(256), 0, stream, (uint16_t*)master_lo, m, v,
                        (bf16_t*)param, (bf16_t*)grad, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, norm_and_coef, grad_mul, zero_grad);
     CSM_CHECK_LAUNCH("csm_adamw_step_split");
+    return 0;
+}
+
+// The two entries above with one flag byte per 2048-element block of the range (ceil(n / 2048) bytes, the last block may be
+// partial).  block_live[b] == 0 promises that m and v of block b are all-zero bits; such a block whose gradient is all-zero
+// bits as well only has its weights decayed (10 instead of 28 / 26 B/param), any other is marked live and updated in full.
+// Every output bit equals the un-flagged entry's.  A skipped step (norm_and_coef[1] < 0) leaves the flags alone.
+extern "C" int csm_adamw_step_live(float* master, float* m, float* v, void* param, void* grad, long long n, float lr,
+                                   float beta1, float beta2, float eps, float weight_decay, int step,
+                                   const float* norm_and_coef, float grad_mul, int zero_grad, void* block_live, hipStream_t stream) {
+    CSM_REQUIRE(master && m && v && param && grad && block_live && n > 0 && step > 0, "csm_adamw_step_live: bad arguments");
+    CSM_REQUIRE((n & 7) == 0, "csm_adamw_step_live: n must be a multiple of 8 (pad the arena)");
+    const float bc1 = 1.f - powf(beta1, (float)step);
+    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(adamw_live_kernel, dim3(grid_for(n >> 3, 256, g_adamw_blocks)), dim3(256), 0, stream, master, m, v, (bf16_t*)param,
+                       (bf16_t*)grad, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, norm_and_coef, grad_mul, zero_grad,
+                       (uint8_t*)block_live);
+    CSM_CHECK_LAUNCH("csm_adamw_step_live");
+    return 0;
+}
+
+extern "C" int csm_adamw_step_split_live(void* master_lo, float* m, float* v, void* param, void* grad, long long n, float lr,
+                                         float beta1, float beta2, float eps, float weight_decay, int step,
+                                         const float* norm_and_coef, float grad_mul, int zero_grad, void* block_live,
+                                         hipStream_t stream) {
+    CSM_REQUIRE(master_lo && m && v && param && grad && block_live && n > 0 && step >= 1, "csm_adamw_step_split_live: bad arguments");
+    CSM_REQUIRE((n & 7) == 0, "csm_adamw_step_split_live: n must be a multiple of 8 (pad the arena)");
+    const float bc1 = 1.f - powf(beta1, (float)step);
+    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+    hipLaunchKernelGGL(adamw_split_live_kernel, dim3(grid_for(n >> 3, 256, g_adamw_blocks)), dim3(256), 0, stream, (uint16_t*)master_lo,
+                       m, v, (bf16_t*)param, (bf16_t*)grad, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, norm_and_coef, grad_mul,
+                       zero_grad, (uint8_t*)block_live);
+    CSM_CHECK_LAUNCH("csm_adamw_step_split_live");
     return 0;
 }

@@ -227,6 +227,16 @@ int csm_adamw_step(float* master, float* m, float* v, void* param, void* grad, l
 int csm_adamw_step_split(void* master_lo, float* m, float* v, void* param, void* grad, long long n, float lr, float beta1,
                          float beta2, float eps, float weight_decay, int step, const float* norm_and_coef, float grad_mul,
                          int zero_grad, csm_stream_t stream);
+/* both with one flag byte per 2048-element block of the range, counted from its start (ceil(n / 2048) bytes): block_live[b] == 0
+ * promises that m and v of block b are all-zero bits.  Such a block whose gradient is all-zero bits too only has its weights
+ * decayed - m, v and the gradient are neither read (m, v) nor written, 10 B/param; any other block is marked live (a -0 gradient
+ * counts) and updated in full.  Every output bit equals the un-flagged call's; a skipped step leaves the flags alone. */
+int csm_adamw_step_live(float* master, float* m, float* v, void* param, void* grad, long long n, float lr, float beta1,
+                        float beta2, float eps, float weight_decay, int step, const float* norm_and_coef, float grad_mul,
+                        int zero_grad, void* block_live, csm_stream_t stream);
+int csm_adamw_step_split_live(void* master_lo, float* m, float* v, void* param, void* grad, long long n, float lr, float beta1,
+                              float beta2, float eps, float weight_decay, int step, const float* norm_and_coef, float grad_mul,
+                              int zero_grad, void* block_live, csm_stream_t stream);
 
 int csm_set_adamw_blocks(int blocks); /* tuning switch */
 
