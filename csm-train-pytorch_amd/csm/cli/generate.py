@@ -35,6 +35,16 @@ def parse_args(argv=None):
                         "reaches it stay (1.0: off)")
     p.add_argument("--min-p", type=float, default=0.0,
                    help="min-p cut in [0, 1], applied before --top-p: tokens below min-p times the largest probability go (0.0: off)")
+    p.add_argument("--repetition-penalty", type=float, default=1.0, metavar="R",
+                   help="repetition penalty in (0, 100], applied inside the sampler before the temperature: the logit x of every code "
+                        "the utterance drew for the same codebook in its last --repetition-window frames becomes x / R (x > 0) or "
+                        "x * R (1.0: off)")
+    p.add_argument("--repetition-window", type=int, default=64, metavar="W",
+                   help="frames the repetition penalty looks back, 0..64 (default 64; a turn's window covers that turn only)")
+    p.add_argument("--acoustic-temperature", type=float, default=None, metavar="T",
+                   help="temperature of codebooks 1..K-1 (the acoustic ones; codebook 0 keeps --temperature)")
+    p.add_argument("--acoustic-topk", type=int, default=None, metavar="K",
+                   help="top-k of codebooks 1..K-1 (codebook 0 keeps --topk)")
     p.add_argument("--device", type=str, default="cuda")
     p.add_argument("--mimi-weights", type=str, required=True, help="local Mimi weights (transformers.MimiModel state dict)")
     p.add_argument("--text-tokenizer", type=str, required=True, help="local directory of the Llama-3.2 tokenizer files")
@@ -58,13 +68,16 @@ def parse_args(argv=None):
                         "dropped (default 0)")
     p.add_argument("--serve-file", type=str, default=None,
                    help="JSON-lines file of utterances {\"text\", \"speaker\", \"adapter\"?: LoRA adapter file, \"seed\"?: int, "
-                        "\"temperature\"?: float, \"topk\"?: int, \"top_p\"?: float, \"min_p\"?: float, \"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
+                        "\"temperature\"?: float, \"topk\"?: int, \"top_p\"?: float, \"min_p\"?: float, \"repetition_penalty\"?: float, "
+                        "\"repetition_window\"?: int, \"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
                         "--context-*; lines with the same conversation id are successive turns of one served conversation, in file "
                         "order (KV cache kept between them; adapter and seed of its first line); a line's temperature / topk hold for "
                         "that utterance or turn (default: --temperature / --topk; a file that names one is served with "
                         "row_sampling=True); likewise a line's top_p / min_p (default: --top-p / --min-p; a file that names one, or "
-                        "a --top-p / --min-p that is not 1.0 / 0.0, is served with row_filters=True); one WAV per utterance, "
-                        "<output stem>_<i>.wav with i = 0, 1, ... counting the file's non-empty lines")
+                        "a --top-p / --min-p that is not 1.0 / 0.0, is served with row_filters=True); a line's repetition_penalty / "
+                        "repetition_window, and a list of one number per codebook for any of the four keys before them (a file or a "
+                        "command line that uses any of these, --acoustic-* included, is served with row_processors=True); one WAV "
+                        "per utterance, <output stem>_<i>.wav with i = 0, 1, ... counting the file's non-empty lines")
     p.add_argument("--slots", type=int, default=16, help="--serve-file: utterances decoded at once (1..16, default 16)")
     p.add_argument("--hear-slots", type=int, default=0,
                    help="--serve-file: encoder slots of the server's batched hearing (Generator.serve(hear_slots=N), 0..16; "
@@ -90,6 +103,29 @@ def parse_args(argv=None):
     if args.next_speaker and len(args.next_speaker) != len(args.next_text or []):
         p.error("--next-speaker must be given once per --next-text (or not at all)")
     return args
+
+
+def sampling_kw(args, codebooks):
+    """The sampling keywords of the generate calls from the command line: --temperature / --topk / --top-p / --min-p, with
+    --acoustic-temperature / --acoustic-topk expanded to one value per codebook (codebook 0 keeps the plain flag's), and
+    --repetition-penalty / --repetition-window only where they are not 1.0 / 64 - without the new flags, the call it was.
+    ``codebooks``: the model's K, or a callable that gives it (called only if an --acoustic-* flag needs it)."""
+    kw = dict(temperature=args.temperature, topk=args.topk, top_p=args.top_p, min_p=args.min_p)
+    if callable(codebooks) and (args.acoustic_temperature is not None or args.acoustic_topk is not None):
+        codebooks = codebooks()
+    if args.acoustic_temperature is not None:
+        kw["temperature"] = [args.temperature] + [args.acoustic_temperature] * (codebooks - 1)
+    if args.acoustic_topk is not None:
+        kw["topk"] = [args.topk] + [args.acoustic_topk] * (codebooks - 1)
+    if (args.repetition_penalty, args.repetition_window) != (1.0, 64):
+        kw.update(repetition_penalty=args.repetition_penalty, repetition_window=args.repetition_window)
+    return kw
+
+
+def uses_processors(args):
+    """Whether the command line names what only the processed sampler has."""
+    return (args.acoustic_temperature is not None or args.acoustic_topk is not None
+            or (args.repetition_penalty, args.repetition_window) != (1.0, 64))
 
 
 def out_rate_kw(args):
@@ -134,8 +170,7 @@ def main(argv=None):
     if args.stream:
         return stream_to_wav(generator, args, speaker_id, context, adapter)
     audio = generator.generate(text=args.text, speaker=speaker_id, context=context, max_audio_length_ms=args.max_audio_length_ms,
-                               temperature=args.temperature, topk=args.topk, adapter=adapter, top_p=args.top_p, min_p=args.min_p,
-                               **out_rate_kw(args))
+                               adapter=adapter, **sampling_kw(args, lambda: generator._model.args.audio_num_codebooks), **out_rate_kw(args))
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     generator.save_wav(args.output, audio, **({} if args.output_sample_rate is None else {"sample_rate": args.output_sample_rate}))
     print(f"Audio saved to {args.output} ({audio.numel() / out_rate(generator, args):.2f} s at {out_rate(generator, args)} Hz)")
@@ -153,9 +188,9 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
         w.setsampwidth(2)
         w.setframerate(out_rate(generator, args))
         for chunk in generator.generate_stream(text=args.text, speaker=speaker_id, context=context,
-                                               max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature,
-                                               topk=args.topk, chunk_frames=args.chunk_frames, adapter=adapter,
-                                               top_p=args.top_p, min_p=args.min_p, **out_rate_kw(args)):
+                                               max_audio_length_ms=args.max_audio_length_ms, chunk_frames=args.chunk_frames,
+                                               adapter=adapter, **sampling_kw(args, lambda: generator._model.args.audio_num_codebooks),
+                                               **out_rate_kw(args)):
             pcm = (chunk.detach().float().cpu().clamp(-1, 1) * 32767.0).to(torch.int16).numpy().tobytes()
             if n == 0:
                 print(f"first chunk after {time.perf_counter() - t0:.3f} s")
@@ -166,11 +201,24 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
     return 0
 
 
-def read_serve_file(path):
+def read_serve_file(path, codebooks=None):
     """--serve-file: one JSON object per non-empty line -> [{"text", "speaker", "adapter", "seed"}], plus "conversation" (a
-    string), "temperature" (a float), "topk" (an int), "top_p" and "min_p" (floats) on the lines that carry those keys."""
+    string), "temperature" (a float), "topk" (an int), "top_p" and "min_p" (floats), "repetition_penalty" (a float) and
+    "repetition_window" (an int) on the lines that carry those keys.  With ``codebooks`` (the model's K, or a callable that gives
+    it: called at the first list) the first four may also be a list of K numbers, one per codebook; a list of another length is
+    refused here."""
     import json
     lines = []
+
+    def per_codebook(i, key, value, integer):
+        nonlocal codebooks
+        kind = "integers" if integer else "numbers"
+        if callable(codebooks):
+            codebooks = codebooks()
+        if codebooks is None or len(value) != codebooks or not all(
+                not isinstance(v, bool) and isinstance(v, int if integer else (int, float)) for v in value):
+            raise ValueError(f"{path}:{i}: \"{key}\" is a list of one value per codebook ({codebooks} {kind}), got {value!r}")
+        return [v if integer else float(v) for v in value]
     with open(path) as f:
         for i, raw in enumerate(f, 1):
             if not raw.strip():
@@ -178,13 +226,25 @@ def read_serve_file(path):
             d = json.loads(raw)
             if not isinstance(d, dict) or not isinstance(d.get("text"), str):
                 raise ValueError(f"{path}:{i}: every line is a JSON object with a \"text\" string")
-            unknown = set(d) - {"text", "speaker", "adapter", "seed", "conversation", "temperature", "topk", "top_p", "min_p"}
+            unknown = set(d) - {"text", "speaker", "adapter", "seed", "conversation", "temperature", "topk", "top_p", "min_p",
+                                "repetition_penalty", "repetition_window"}
             if unknown:
                 raise ValueError(f"{path}:{i}: unknown keys {sorted(unknown)}")
             lines.append({"text": d["text"], "speaker": int(d.get("speaker", 0)), "adapter": d.get("adapter"),
                           "seed": None if d.get("seed") is None else int(d["seed"])})
             if d.get("conversation") is not None:
                 lines[-1]["conversation"] = str(d["conversation"])
+            for k in ("temperature", "topk", "top_p", "min_p"):
+                if isinstance(d.get(k), list):
+                    lines[-1][k] = per_codebook(i, k, d.pop(k), k == "topk")
+            if d.get("repetition_penalty") is not None:
+                if isinstance(d["repetition_penalty"], bool) or not isinstance(d["repetition_penalty"], (int, float)):
+                    raise ValueError(f"{path}:{i}: \"repetition_penalty\" is a number, got {d['repetition_penalty']!r}")
+                lines[-1]["repetition_penalty"] = float(d["repetition_penalty"])
+            if d.get("repetition_window") is not None:
+                if isinstance(d["repetition_window"], bool) or not isinstance(d["repetition_window"], int):
+                    raise ValueError(f"{path}:{i}: \"repetition_window\" is an integer, got {d['repetition_window']!r}")
+                lines[-1]["repetition_window"] = d["repetition_window"]
             if d.get("temperature") is not None:
                 if isinstance(d["temperature"], bool) or not isinstance(d["temperature"], (int, float)):
                     raise ValueError(f"{path}:{i}: \"temperature\" is a number, got {d['temperature']!r}")
@@ -227,36 +287,59 @@ def serve_filters(lines, top_p=1.0, min_p=0.0):
     return {}
 
 
+def line_processors(line):
+    """The repetition keywords of one --serve-file line for ``submit`` / ``say``: only what the line carries."""
+    return {k: line[k] for k in ("repetition_penalty", "repetition_window") if k in line}
+
+
+def serve_processors(lines, args=None, codebooks=None):
+    """``Generator.serve`` keywords for these lines and the command line: ``row_processors=True`` (with ``row_sampling=True``, which it
+    needs, and the command line's values - --acoustic-* expanded - as the server's defaults) as soon as a line names a repetition
+    penalty, a window or a list per codebook, or the command line uses --repetition-* / --acoustic-*; nothing otherwise."""
+    named = any(line_processors(ln) or any(isinstance(ln.get(k), list) for k in ("temperature", "topk", "top_p", "min_p"))
+                for ln in lines)
+    if not named and (args is None or not uses_processors(args)):
+        return {}
+    kw = {"row_sampling": True, "row_processors": True}
+    if args is not None:
+        kw.update(sampling_kw(args, codebooks))
+    return kw
+
+
 def serve_to_wavs(generator, args, context, adapter=None):
     """--serve-file: every line is a request of one ``Generator.serve`` batch; adapter files are loaded once each, under their
     path as name (--lora-adapter is the default for lines without one).  Lines with a "conversation" id are the turns of one
     served conversation (``BatchServer.conversation``): its first line is queued with the rest, each later one when the turn
     before it is done.  A line's "temperature" / "topk" are that utterance's or that turn's; if any line has one, the server is
     made with ``row_sampling=True`` (--temperature / --topk are then the other lines' values); "top_p" / "min_p" likewise, with
-    ``row_filters=True`` (``serve_filters``).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav."""
-    lines = read_serve_file(args.serve_file)
+    ``row_filters=True`` (``serve_filters``); "repetition_penalty" / "repetition_window", a list per codebook or the command
+    line's --repetition-* / --acoustic-* make it ``row_processors=True`` (``serve_processors``).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav."""
+    def K():
+        return generator._model.args.audio_num_codebooks
+    lines = read_serve_file(args.serve_file, K)
     for path in sorted({ln["adapter"] for ln in lines if ln["adapter"]}):
         generator.load_adapter(path, path)
     stem, ext = os.path.splitext(os.path.abspath(args.output))
     os.makedirs(os.path.dirname(stem), exist_ok=True)
     t0 = time.perf_counter()
-    server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, temperature=args.temperature,
-                             topk=args.topk, hear_slots=args.hear_slots,
-                             **{**serve_sampling(lines), **serve_filters(lines, args.top_p, args.min_p), **out_rate_kw(args)})
+    server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, hear_slots=args.hear_slots,
+                             **{"temperature": args.temperature, "topk": args.topk, **serve_sampling(lines),
+                                **serve_filters(lines, args.top_p, args.min_p), **serve_processors(lines, args, K),
+                                **out_rate_kw(args)})
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
     def say(cid):
         conv, todo = convs[cid]
         i = todo.pop(0)
         line_of[conv.say(lines[i]["text"], lines[i]["speaker"], max_audio_length_ms=args.max_audio_length_ms,
-                         **line_sampling(lines[i]), **line_filters(lines[i]))] = (i, cid)
+                         **line_sampling(lines[i]), **line_filters(lines[i]), **line_processors(lines[i]))] = (i, cid)
 
     for i, ln in enumerate(lines):
         cid = ln.get("conversation")
         if cid is None:
             line_of[server.submit(ln["text"], ln["speaker"], context, adapter=ln["adapter"] or adapter, seed=ln["seed"],
                                   max_audio_length_ms=args.max_audio_length_ms, **line_sampling(ln),
-                                  **line_filters(ln))] = (i, None)
+                                  **line_filters(ln), **line_processors(ln))] = (i, None)
         elif cid in convs:
             convs[cid][1].append(i)
         else:
@@ -287,8 +370,8 @@ def converse_to_wav(generator, args, speaker_id, context, adapter=None):
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     lines = [(args.text, speaker_id)] + list(zip(args.next_text, args.next_speaker or [speaker_id] * len(args.next_text)))
     conv = generator.conversation(context=context, adapter=adapter, on_overflow=args.on_overflow, keep_turns=args.keep_turns)
-    kw = dict(max_audio_length_ms=args.max_audio_length_ms, temperature=args.temperature, topk=args.topk, top_p=args.top_p,
-              min_p=args.min_p, **out_rate_kw(args))
+    kw = dict(max_audio_length_ms=args.max_audio_length_ms, **sampling_kw(args, lambda: generator._model.args.audio_num_codebooks),
+              **out_rate_kw(args))
     t0 = time.perf_counter()
     n = 0
     with wave.open(args.output, "wb") as w:

@@ -870,7 +870,7 @@ class Engine:
 
     @torch.no_grad()
     def generate_frame(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None, adapters=None, top_p=None,
-                       min_p=None):
+                       min_p=None, repetition_penalty=None, repetition_window=None):
         """Reference model.py:140-195: backbone position(s) -> c0 -> 31 depth-decoder steps, against KV caches.
 
         The prompt (``input_pos`` starting at 0) is prefilled with the training forward kernels and its post-RoPE K/V
@@ -883,12 +883,17 @@ class Engine:
         row, ``DecodeState.sampling_args``), or None for both (the pairs ``DecodeState.set_row_sampling`` wrote).
         ``top_p`` / ``min_p`` (with caches; None: not named): a number or B values for either one - the rows then sample through
         the filtered rows sampler (``DecodeState.set_row_filters``); give the same to every call of the generation.
+        ``repetition_penalty`` / ``repetition_window`` (with caches; None: not named), or an entry per row that is K numbers in
+        any of the six: the processed rows sampler (``DecodeState.sampling_args``); likewise the same to every call.
         """
         m, a = self.m, self.m.args
         self._need()
         if int(input_pos[0, 0]) == 0:
             m._gen_adapters = list(adapters) if adapters is not None and any(x is not None for x in adapters) else None
         if not getattr(m, "use_kv_cache", True):
+            if names_processors(temperature, topk, repetition_penalty=repetition_penalty, repetition_window=repetition_window):
+                raise ValueError("the recompute path (use_kv_cache = False) has no repetition penalty and no per-codebook "
+                                 "parameters: they need the KV-cache path")
             if top_p is not None or min_p is not None:
                 raise ValueError("the recompute path (use_kv_cache = False) has no top_p / min_p: the filters need the KV-cache path")
             return self._generate_frame_recompute(tokens, tokens_mask, input_pos, temperature, topk, noise)
@@ -904,7 +909,8 @@ class Engine:
                                "same batch size (call it with input_pos starting at 0 first)")
         if first:
             st = m._decode_state = DecodeState(self, Bn, adapters)
-        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p)
+        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        st.set_live(range(Bn))
         if first:
             last_h = st.prefill(tokens, tokens_mask)
             return self._frame_tail(st, last_h, temperature, topk, noise)
@@ -917,16 +923,17 @@ class Engine:
 
     @torch.no_grad()
     def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None, adapters=None, top_p=None,
-                              min_p=None):
+                              min_p=None, repetition_penalty=None, repetition_window=None):
         """Batched generation (up to 16 utterances): prefill B prompts of different lengths and sample the
         first frame of each; later frames go through ``generate_frame`` with ``[B, 1, K+1]`` tokens and a non-zero
         ``input_pos``, exactly as for one utterance.  ``temperature`` / ``topk``: two numbers, or a sequence of B values for
         either one - row b then samples with its own pair (``DecodeState.sampling_args``); give the same to ``generate_frame``.
-        ``top_p`` / ``min_p``: as for ``generate_frame``."""
+        ``top_p`` / ``min_p`` / ``repetition_penalty`` / ``repetition_window``: as for ``generate_frame``."""
         m = self.m
         self._need()
         st = m._decode_state = DecodeState(self, len(tokens_list), adapters)
-        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p)
+        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        st.set_live(range(st.B))
         last_h = st.prefill_ragged(tokens_list, masks_list)
         return self._frame_tail(st, last_h, temperature, topk, noise)
 
@@ -954,15 +961,25 @@ class Engine:
 
         if temperature is None and topk is None:
             # each row's own pair, read by the sampler from the state's row buffers (written outside the graph: set_row_sampling)
-            from .models.model import sample_filtered_rows, sample_topk_rows
-            row_t, row_k = st.row_sampling_buffers()
-            if st.row_filters is not None:
+            from .models.model import sample_filtered_rows, sample_processed_rows, sample_topk_rows
+            if st.row_processors is not None:
+                # ... each row's own six parameters per codebook (set_row_processors): the processed rows sampler, which also keeps
+                # the rows' rings of sampled codes; the last codebook's draw counts the frame
+                pt, pk, pp, pm, pr, pw = st.proc
+
+                def draw(lg, i):
+                    return sample_processed_rows(lg[:, :V], pk[i], pt[i], pp[i], pm[i], pr[i], pw[i], st.code_hist[:, i],
+                                                 st.hist_frame, st.hist_live, advance=(i == K - 1), q=qall[i])
+            elif st.row_filters is not None:
                 # ... and its own top-p / min-p (set_row_filters): the filtered rows sampler; a (1, 0) row is the rows sampler's
+                row_t, row_k = st.row_sampling_buffers()
                 row_p, row_m = st.row_filter_buffers()
 
                 def draw(lg, i):
                     return sample_filtered_rows(lg[:, :V], row_k, row_t, row_p, row_m, qall[i])
             else:
+                row_t, row_k = st.row_sampling_buffers()
+
                 def draw(lg, i):
                     return sample_topk_rows(lg[:, :V], row_k, row_t, qall[i])
         elif temperature is None or topk is None:
@@ -1337,6 +1354,68 @@ def check_filters(top_p, min_p):
     return out[0], out[1]
 
 
+HIST_FRAMES = 64        # SMP_HIST of csrc/generate.hip: the frames a row's ring of sampled codes holds, per codebook
+
+
+def check_processors(repetition_penalty, repetition_window):
+    """The rule for one row's repetition penalty: ``repetition_penalty`` a finite number with 0 < r <= 100 (1: off; above 1 a
+    code of the window becomes less likely, below 1 more), ``repetition_window`` an integer in 0..64 (the most recent frames
+    looked at; 0: off).  Returns (float, int); raises ValueError with the offending value."""
+    try:
+        r = float(repetition_penalty)
+    except (TypeError, ValueError):
+        r = float("nan")
+    if isinstance(repetition_penalty, (bool, str, bytes)) or not (math.isfinite(r) and 0.0 < r <= 100.0):
+        raise ValueError(f"repetition_penalty must be a finite number with 0 < r <= 100, got {repetition_penalty!r}")
+    try:
+        w = int(repetition_window)
+        whole = not isinstance(repetition_window, (bool, str, bytes)) and w == repetition_window
+    except (TypeError, ValueError, OverflowError):
+        w, whole = 0, False
+    if not whole or not 0 <= w <= HIST_FRAMES:
+        raise ValueError(f"repetition_window must be an integer in 0..{HIST_FRAMES} (frames), got {repetition_window!r}")
+    return r, w
+
+
+PROCESSOR_NAMES = ("temperature", "topk", "top_p", "min_p", "repetition_penalty", "repetition_window")
+
+
+def per_codebook(name, value, K):
+    """``value`` - a number (every codebook) or a sequence of K numbers (one per codebook) - as a list of K entries."""
+    if _is_number(value):
+        return [value] * K
+    vs = _as_list(value)
+    if vs is None or len(vs) != K or not all(_is_number(v) for v in vs):
+        raise ValueError(f"{name} is a number or a sequence of one number per codebook ({K} codebooks), got {value!r}")
+    return vs
+
+
+def check_row_processors(K, vocab, temperature, topk, top_p, min_p, repetition_penalty, repetition_window):
+    """One row's six sampling parameters, each a number or K numbers, held to ``check_sampling`` / ``check_filters`` /
+    ``check_processors`` codebook by codebook.  Returns six tuples of K values (floats; ints for topk and the window)."""
+    cols = [per_codebook(n, v, K) for n, v in zip(PROCESSOR_NAMES, (temperature, topk, top_p, min_p, repetition_penalty,
+                                                                     repetition_window))]
+    out = [[] for _ in cols]
+    for i in range(K):
+        vals = (check_sampling(cols[0][i], cols[1][i], vocab) + check_filters(cols[2][i], cols[3][i])
+                + check_processors(cols[4][i], cols[5][i]))
+        for o, v in zip(out, vals):
+            o.append(v)
+    return tuple(tuple(o) for o in out)
+
+
+def names_processors(*values, repetition_penalty=None, repetition_window=None):
+    """Whether a call names what only the processed sampler has: a penalty, a window, or a per-codebook sequence among
+    ``values`` (each a number, None, a flat sequence of numbers - per row, today's meaning - or a sequence holding sequences)."""
+    if repetition_penalty is not None or repetition_window is not None:
+        return True
+    for v in values:
+        vs = _as_list(v)
+        if vs is not None and any(_as_list(x) is not None for x in vs):
+            return True
+    return False
+
+
 class DecodeState:
     """Everything ``generate_frame`` keeps between calls: the two stacks' caches and small persistent buffers."""
 
@@ -1390,6 +1469,10 @@ class DecodeState:
         self.row_temperature, self.row_topk, self.row_sampling = None, None, None
         # ... and per-row filters (set_row_filters): top-p / min-p vectors for the filtered rows sampler + their host mirror
         self.row_top_p, self.row_min_p, self.row_filters = None, None, None
+        # ... and per-row, per-codebook processors (set_row_processors): six [K, B] buffers + each row's ring of sampled codes, its
+        # frame counter and the live flags for the processed rows sampler + the host mirrors
+        self.proc, self.row_processors = None, None
+        self.code_hist, self.hist_frame, self.hist_live, self.live_rows = None, None, None, None
         # the frame's Exp(1) draws [K, B, V]: a PERSISTENT buffer, refilled before every frame outside the captured graph -
         # so a replayed frame can be given the same noise as an eager one (parity tests) or fresh draws (generation)
         self.noise_buf = torch.empty(m.args.audio_num_codebooks, B, m.args.audio_vocab_size, dtype=F32, device=dev)
@@ -1691,12 +1774,86 @@ class DecodeState:
             raise RuntimeError("no row filters: call set_row_filters first")
         return self.row_top_p, self.row_min_p
 
-    def sampling_args(self, temperature, topk, top_p=None, min_p=None):
+    def set_row_processors(self, b, temperature, topk, top_p, min_p, repetition_penalty, repetition_window):
+        """Row ``b`` samples with these six parameters from its next frame on, each a number (every codebook) or K numbers (one per
+        codebook), in every frame body called with ``temperature=None, topk=None``.  They sit in six device buffers of shape
+        [K, B] (``proc``, codebook-major: codebook i's draw reads row i of each), column b written here - outside the captured
+        graph, so a change never recaptures - with one small copy per buffer that changed.  The first call makes the buffers, with
+        every row at that call's values, and the history the processed rows sampler (``csm_sample_processed_rows``) keeps:
+        ``code_hist`` int32 [B, K, 64] (slot f % 64 of [b, i]: the code row b drew for codebook i in frame f of its utterance),
+        ``hist_frame`` int32 [B] (f; ``reset_row_history``) and ``hist_live`` int32 [B] (the rows that write their ring and
+        count the frame).  Once they exist the frame bodies draw through that sampler (make them before the first capture).
+        ``row_processors`` is the host mirror: per row, six tuples of K values."""
+        a = self.e.m.args
+        K = a.audio_num_codebooks
+        vals = check_row_processors(K, a.audio_vocab_size, temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        dtypes = (F32, torch.int32, F32, F32, F32, torch.int32)
+        if self.row_processors is None:
+            dev = self.noise_buf.device
+            self.proc = tuple(torch.tensor(v, dtype=dt).view(K, 1).repeat(1, self.B).to(dev) for v, dt in zip(vals, dtypes))
+            self.code_hist = torch.zeros(self.B, K, HIST_FRAMES, dtype=torch.int32, device=dev)
+            self.hist_frame = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.hist_live = torch.ones(self.B, dtype=torch.int32, device=dev)
+            self.live_rows = list(range(self.B))
+            self.row_processors = [vals] * self.B
+        elif self.row_processors[b] != vals:
+            for buf, new, old, dt in zip(self.proc, vals, self.row_processors[b], dtypes):
+                if new != old:
+                    buf[:, b].copy_(torch.tensor(new, dtype=dt))
+            self.row_processors[b] = vals
+
+    def reset_row_history(self, b):
+        """Row ``b`` starts an utterance: its frame counter returns to 0.  The ring is left as it is - the sampler looks at
+        min(window, frame) entries, so what an earlier utterance left there is never read."""
+        if self.row_processors is None:
+            raise RuntimeError("no row processors: call set_row_processors first")
+        self.hist_frame[int(b):int(b) + 1].zero_()
+
+    def set_live(self, rows):
+        """The rows whose draws count in the next frame tail (the processed sampler writes their ring and advances their frame);
+        the others' rings and counters stay as they are, whatever their rows of the batch hold.  Nothing without processors."""
+        if self.row_processors is None:
+            return
+        rows = sorted(int(b) for b in rows)
+        if rows != self.live_rows:
+            self.hist_live.copy_(torch.tensor([1 if b in rows else 0 for b in range(self.B)], dtype=torch.int32))
+            self.live_rows = rows
+
+    def sampling_args(self, temperature, topk, top_p=None, min_p=None, repetition_penalty=None, repetition_window=None):
         """What ``Engine.generate_frame`` / ``generate_first_frames`` hand to the frame bodies: two numbers (or None, None) pass
         through; a sequence of B values for either one is written to the rows (``set_row_sampling``; the other, if a number,
         holds for every row) and (None, None) comes back.  ``top_p`` / ``min_p`` (None: not named - nothing changes): numbers or
         one value per row, written to the rows' filters (``set_row_filters``) - they live in the rows path, so the pair goes to
-        the rows too and (None, None) comes back."""
+        the rows too and (None, None) comes back.  ``repetition_penalty`` / ``repetition_window`` (None: not named), or an entry
+        per row that is itself a sequence of K numbers (one per codebook) in any of the six: all six go to the rows' processors
+        (``set_row_processors``; a number holds for every row and codebook, an entry per row is a number or K numbers) and
+        (None, None) comes back."""
+        plain = (temperature is None and topk is None) or (_is_number(temperature) and _is_number(topk))
+        if names_processors(temperature, topk, top_p, min_p, repetition_penalty=repetition_penalty,
+                            repetition_window=repetition_window) or (
+                self.row_processors is not None and not (plain and top_p is None and min_p is None)):
+            # (a state that has processors draws every rows frame through them: rows' pairs and filters go there too)
+            if temperature is None or topk is None:
+                raise ValueError("per-codebook parameters and the repetition penalty need temperature and topk named")
+            six = (temperature, topk, 1.0 if top_p is None else top_p, 0.0 if min_p is None else min_p,
+                   1.0 if repetition_penalty is None else repetition_penalty,
+                   HIST_FRAMES if repetition_window is None else repetition_window)
+            rows = []
+            for name, v in zip(PROCESSOR_NAMES, six):
+                vs = [v] * self.B if _is_number(v) else _as_list(v)
+                if vs is None or len(vs) != self.B:
+                    raise ValueError(f"{name} is a number or a sequence of one entry per row ({self.B} rows; an entry is a number "
+                                     f"or one number per codebook), got {v!r}")
+                rows.append(vs)
+            a = self.e.m.args
+            for b in range(self.B):                        # (all of them before any is written)
+                check_row_processors(a.audio_num_codebooks, a.audio_vocab_size, *[vs[b] for vs in rows])
+            for b in range(self.B):
+                self.set_row_processors(b, *[vs[b] for vs in rows])
+            return None, None
         if top_p is not None or min_p is not None:
             ps = [1.0 if top_p is None else top_p] * self.B if top_p is None or _is_number(top_p) else _as_list(top_p)
             ms = [0.0 if min_p is None else min_p] * self.B if min_p is None or _is_number(min_p) else _as_list(min_p)
@@ -1762,6 +1919,7 @@ class DecodeState:
         rows' output is meaningless.  ``temperature`` / ``topk``, here and in ``serve_frame``: two numbers, or None, None for each
         row's own pair (``set_row_sampling``)."""
         self.draw_rows = set(rows)
+        self.set_live(rows)                              # (the other rows are mid-utterance: this tail must not count for them)
         try:
             return self.e._frame_tail(self, last_h, temperature, topk, None)
         finally:
@@ -1775,6 +1933,7 @@ class DecodeState:
         if self.active is None:
             self.set_active(self.active_rows)
         self.bb.pos.mul_(self.active)
+        self.set_live(self.active_rows)
         self.draw_rows = set(self.active_rows)
         try:
             if getattr(m, "use_hip_graph", True):
@@ -1796,12 +1955,14 @@ class DecodeState:
         when temperature / top-k change; with ``None, None`` the key is (None, None) and the sampler reads each row's pair from
         the row buffers (``set_row_sampling``), so a change of any row's parameters replays the same graph; once the state has
         row filters (``set_row_filters``) it is (None, None, "filters") - the frame holds the filtered rows sampler, and a change
-        of any row's top-p / min-p replays it too."""
+        of any row's top-p / min-p replays it too; with row processors (``set_row_processors``) it is (None, None, "processors")."""
         m = self.e.m
         self._advance()
         key = (None, None) if temperature is None and topk is None else (float(temperature), int(topk))
         if key == (None, None) and self.row_filters is not None:
             key = (None, None, "filters")                # (the frame draws through the filtered rows sampler: another graph)
+        if key[:2] == (None, None) and self.row_processors is not None:
+            key = (None, None, "processors")             # (... through the processed rows sampler)
         if self.graph is None or self.graph_key != key:
             if self.warm < 1 or self.graph_key not in (None, key):
                 self.warm, self.graph, self.graph_key = 1, None, None

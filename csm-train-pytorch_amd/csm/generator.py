@@ -62,6 +62,39 @@ def filter_kwargs(top_p, min_p, B=None):
     return out
 
 
+def sampling_kwargs(gen, temperature, topk, top_p, min_p, repetition_penalty=1.0, repetition_window=64, B=None):
+    """(temperature, topk, keywords) of the frame calls of a generation on the Generator ``gen``.  Nothing new named -
+    ``repetition_penalty`` 1.0, ``repetition_window`` 64 and no per-codebook sequence: what the call has always made of them (``filter_kwargs``;
+    ``Generator._batch_sampling`` with ``B``), untouched.  Otherwise every one of the six goes to the rows' processors
+    (``DecodeState.sampling_args``): one entry per row, each a number or K numbers (one per codebook), checked here, before
+    any cache is taken over.  Without ``B`` (one utterance) a value is a number or K numbers; with ``B`` a number or a sequence
+    of B entries, each a number or K numbers - a flat sequence of B numbers keeps its meaning, one value per utterance."""
+    from .engine import PROCESSOR_NAMES, _as_list, _is_number, check_row_processors
+    six = (temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+    if B is None:
+        new = not all(_is_number(v) for v in six)
+    else:
+        new = not all(_is_number(v) for v in six[4:]) or any(
+            _as_list(v) is not None and any(_as_list(x) is not None for x in _as_list(v)) for v in six[:4])
+    new = new or not (repetition_penalty == 1.0 and repetition_window == 64)
+    if not new:
+        if B is not None:
+            temperature, topk = gen._batch_sampling(temperature, topk, B)
+        return temperature, topk, filter_kwargs(top_p, min_p, B)
+    n = 1 if B is None else B
+    rows = []
+    for name, v in zip(PROCESSOR_NAMES, six):
+        vs = [v] * n if _is_number(v) or B is None else _as_list(v)
+        if vs is None or len(vs) != n:
+            raise ValueError(f"{name} is a number or a sequence of one entry per utterance ({n}; an entry is a number or one "
+                             f"number per codebook), got {v!r}")
+        rows.append(vs)
+    a = gen._model.args
+    for b in range(n):
+        check_row_processors(a.audio_num_codebooks, a.audio_vocab_size, *[vs[b] for vs in rows])
+    return rows[0], rows[1], dict(zip(PROCESSOR_NAMES[2:], rows[2:]))
+
+
 class Generator:
     """Speech generator using the CSM model (reference generator.py:48)."""
 
@@ -147,7 +180,8 @@ class Generator:
     @torch.inference_mode()
     def generate(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                  temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8, adapter: Optional[str] = None,
-                 top_p: float = 1.0, min_p: float = 0.0, output_sample_rate: Optional[int] = None) -> torch.Tensor:
+                 top_p: float = 1.0, min_p: float = 0.0, output_sample_rate: Optional[int] = None,
+                 repetition_penalty=1.0, repetition_window=64) -> torch.Tensor:
         """Reference generator.py:147-218.  ``adapter``: the name of a bank adapter (``add_adapter`` / ``load_adapter``) to
         speak with, or None.  The reference tests every frame for EOS on the host (one device sync per
         frame, generator.py:196-199); here the all-zero test runs on the device and the host looks at it once per
@@ -157,8 +191,14 @@ class Generator:
         first p_i >= min_p * p_max, then the smallest set of the largest values whose probability reaches top_p.  At 1.0 / 0.0
         (the defaults) the call is what it is without them; otherwise it samples through the filtered rows sampler.
         ``output_sample_rate``: the rate of the audio returned (None: the codec's 24 kHz); another rate is resampled on the
-        device (``csm.codec.resample``) - the codes are the same."""
-        filters = filter_kwargs(top_p, min_p)
+        device (``csm.codec.resample``) - the codes are the same.
+        ``repetition_penalty`` r (0 < r <= 100) / ``repetition_window`` (0..64 frames): inside the sampler, the logit x of every
+        code the utterance drew for this codebook in its last ``repetition_window`` frames becomes x / r (x > 0) or x * r before
+        the temperature.  ``temperature`` / ``topk`` / ``top_p`` / ``min_p`` and these two may each be a sequence of K numbers, one
+        per codebook (codebook 0 is the semantic one).  At 1.0 / 64 with plain numbers the call is what it is without them;
+        otherwise it samples through the processed rows sampler (``DecodeState.set_row_processors``)."""
+        temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
+                                                     repetition_window)
         out_rs = self._out_resampler(output_sample_rate)
         ads = self._resolve_adapters([adapter])
         self._run += 1
@@ -211,17 +251,20 @@ class Generator:
     def generate_stream(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                         temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4,
                         adapter: Optional[str] = None, top_p: float = 1.0, min_p: float = 0.0,
-                        output_sample_rate: Optional[int] = None) -> Iterator[torch.Tensor]:
+                        output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
+                        repetition_window=64) -> Iterator[torch.Tensor]:
         """``generate`` that hands the audio out while it is being made: an iterator of 1-D device tensors of
         ``chunk_frames * 1920`` samples (the last one may be shorter), decoded by the audio tokenizer's stateful
         ``decode_stream()``.  The frames are sampled by the same ``generate_frame`` calls in the same order as ``generate``,
         so under the same torch seed the concatenated chunks equal ``generate``'s audio.  The host looks for EOS once per
         chunk; frames from EOS on are never decoded.  A later ``generate`` / ``generate_batch`` / ``generate_stream`` on this
         Generator invalidates the stream (its next ``next()`` raises ``RuntimeError``); abandoning it is harmless.
-        ``adapter``, ``top_p``, ``min_p``: as for ``generate``.  ``output_sample_rate``: the chunks go through a stateful
+        ``adapter``, ``top_p``, ``min_p``, ``repetition_penalty``, ``repetition_window`` and per-codebook sequences: as for
+        ``generate``.  ``output_sample_rate``: the chunks go through a stateful
         ``ResampleStream`` - they concatenate to ``generate(..., output_sample_rate=)``'s audio bit for bit; the stream lags by
         the filter's half-width, and what it still owes comes as one last short chunk."""
-        filters = filter_kwargs(top_p, min_p)
+        temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
+                                                     repetition_window)
         out_rs = self._out_resampler(output_sample_rate)
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
@@ -275,7 +318,8 @@ class Generator:
     def generate_batch(self, texts: List[str], speakers: List[int], contexts: List[List[Segment]],
                        max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
                        eos_check_every: int = 8, adapters: Optional[List[Optional[str]]] = None, top_p=1.0,
-                       min_p=0.0, output_sample_rate: Optional[int] = None) -> List[torch.Tensor]:
+                       min_p=0.0, output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
+                       repetition_window=64) -> List[torch.Tensor]:
         """``generate`` for up to 16 utterances at once (not in the reference, whose loop is single-utterance): the prompts
         (different lengths) are prefilled one by one into their rows of the KV caches, then every decode frame advances all
         rows together - the decode kernels share each weight load between the batch rows, so B utterances cost about as
@@ -289,13 +333,16 @@ class Generator:
         has in a batch of the same size run with its pair for everybody; two numbers are the one-pair path.
         ``top_p`` / ``min_p``: a number or one value per utterance for either one (``generate``); at 1.0 / 0.0 the call is what it
         is without them, otherwise every row samples through the filtered rows sampler with its own four parameters.
+        ``repetition_penalty`` / ``repetition_window`` (``generate``): a number or one value per utterance; with them, or with an
+        entry per utterance that is a sequence of K numbers (one per codebook) in any of the six, every row samples through the
+        processed rows sampler with its own parameters.  A flat sequence of B numbers is one value per utterance, as before.
         ``output_sample_rate``: as for ``generate``, for every utterance."""
         out_rs = self._out_resampler(output_sample_rate)
         B = len(texts)
         if not (1 <= B <= 16 and len(speakers) == B and len(contexts) == B):
             raise ValueError("generate_batch takes 1..16 utterances with one speaker id and one context list each")
-        temperature, topk = self._batch_sampling(temperature, topk, B)
-        filters = filter_kwargs(top_p, min_p, B)
+        temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
+                                                     repetition_window, B)
         if adapters is not None and len(adapters) != B:
             raise ValueError(f"generate_batch: {len(adapters)} adapter names for {B} utterances (one name or None each)")
         ads = self._resolve_adapters(list(adapters)) if adapters is not None else None
@@ -365,7 +412,8 @@ class Generator:
 
     def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
               row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
-              output_sample_rate: Optional[int] = None):
+              output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
+              repetition_window=64):
         """A running batch (csm/serving.py): ``server.submit(text, speaker, context, adapter=None, seed=None,
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
@@ -375,7 +423,12 @@ class Generator:
         request's pair through the rows sampler, and one captured frame serves every mix (a change never recaptures).  With
         ``row_filters=True`` as well (it needs ``row_sampling``), ``top_p`` / ``min_p`` are the requests' default nucleus and min-p
         cuts and ``submit`` / ``conversation`` / ``say`` take their own (``top_p=``, ``min_p=``); every draw then goes through the
-        filtered rows sampler, and a request at 1.0 / 0.0 has the codes it has without ``row_filters``.  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
+        filtered rows sampler, and a request at 1.0 / 0.0 has the codes it has without ``row_filters``.  With
+        ``row_processors=True`` (it needs ``row_sampling`` and includes ``row_filters``), ``repetition_penalty`` / ``repetition_window``
+        are the requests' default windowed repetition penalty (``generate``), ``submit`` / ``conversation`` / ``say`` take their own,
+        and each of the six parameters may be a sequence of K numbers, one per codebook; every draw then goes through the
+        processed rows sampler, which remembers each slot's last 64 frames, and a request at penalty 1 has the codes it has with
+        ``row_filters``.  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
         speaker)`` queues its next turn as a request, ``conv.add(Segment)`` (or ``conv.hear(speaker)`` -> ``feed`` / ``end``, encoded
         while it is spoken) is the other party's turn; its KV history is parked
         between turns and resumed into any free slot, so more conversations than slots can be open.  It takes over the model's caches like any ``generate*`` call (open streams and older servers are
@@ -387,7 +440,7 @@ class Generator:
         one rows resampler over its slots - one more launch per ``step()``.  ``conv.hear(speaker, sample_rate=)`` is the input side."""
         from .serving import BatchServer
         return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p,
-                           output_sample_rate)
+                           output_sample_rate, row_processors, repetition_penalty, repetition_window)
 
     def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error",
                      keep_turns: int = 0):

@@ -747,6 +747,31 @@ def sample_filtered_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, 
     return out_i32
 
 
+def sample_processed_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, top_p_f32, min_p_f32, penalty_f32, window_i32,
+                          hist_i32, frame_i32, live_i32, advance=False, V=None):
+    """``sample_filtered_rows`` with a windowed repetition penalty per row and the row's memory of what it drew
+    (``csm_sample_processed_rows``).  ``hist_i32`` [rows, 64] (any row stride >= 64): row r's ring, slot f % 64 the code of frame
+    f; ``frame_i32[r]``: f; the ids of the last min(window_i32[r], f, 64) frames are penalised by ``penalty_f32[r]`` before the
+    draw.  A row with ``live_i32[r]`` != 0 then stores its winner to slot f % 64 and, with ``advance``, f + 1 to ``frame_i32[r]``.
+    A row with penalty 1 or window 0 is ``sample_filtered_rows``' row."""
+    rows = logits_f32.shape[0]
+    V = V or logits_f32.shape[1]
+    assert q_f32.is_contiguous() and q_f32.shape == (rows, V)
+    for a in (topk_i32, window_i32, frame_i32, live_i32):
+        assert a.dtype == torch.int32 and a.is_contiguous() and a.numel() == rows
+    for a in (temperature_f32, top_p_f32, min_p_f32, penalty_f32):
+        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == rows
+    assert hist_i32.dtype == torch.int32 and hist_i32.dim() == 2 and hist_i32.shape == (rows, 64) and hist_i32.stride(1) == 1
+    assert rows == 1 or hist_i32.stride(0) >= 64
+    ldh = hist_i32.stride(0) if rows > 1 else 64
+    check(lib.csm_sample_processed_rows(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0),
+                                        topk_i32.data_ptr(), temperature_f32.data_ptr(), top_p_f32.data_ptr(),
+                                        min_p_f32.data_ptr(), penalty_f32.data_ptr(), window_i32.data_ptr(), hist_i32.data_ptr(),
+                                        ldh, frame_i32.data_ptr(), live_i32.data_ptr(), 1 if advance else 0, _stream()),
+          "csm_sample_processed_rows")
+    return out_i32
+
+
 def rvq_encode(x_f32, codebooks_f32, codes_i64, n_semantic=1):
     T, D = x_f32.shape
     K, Cn, D2 = codebooks_f32.shape

@@ -159,6 +159,29 @@ def sample_filtered_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: 
     return out.reshape(-1, 1)
 
 
+def sample_processed_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor,
+                          min_p: torch.Tensor, penalty: torch.Tensor, window: torch.Tensor, hist: torch.Tensor,
+                          frame: torch.Tensor, live: torch.Tensor, advance: bool = False, q: Optional[torch.Tensor] = None):
+    """``sample_filtered_rows`` with a windowed repetition penalty (``penalty`` float32 [B], ``window`` int32 [B], frames) on the
+    codes the row drew before, kept by the kernel (``csm_sample_processed_rows``) in ``hist`` int32 [B, 64] (a view with any row
+    stride: slot f % 64 of row b is the code of frame f of its utterance) with f = ``frame[b]`` (int32 [B]).  The distinct ids of
+    the last n = min(window, f, 64) frames get x = x / r (x > 0) or x * r on the raw logit, then the draw is
+    ``sample_filtered_rows``'; row b with r = 1 or n = 0 is that row bit for bit.  A row with ``live[b]`` != 0 then stores its
+    winner to slot f % 64 and, with ``advance``, f + 1 to ``frame[b]``.  Returns int32 [B, 1]."""
+    lg2 = logits.float()
+    if lg2.dim() != 2:
+        raise ValueError(f"sample_processed_rows takes [B, V] logits, got {tuple(logits.shape)}")
+    if lg2.stride(1) != 1:
+        lg2 = lg2.contiguous()
+    if q is None:
+        q = torch.empty(lg2.shape, dtype=torch.float32, device=lg2.device).exponential_(1)
+    q = q.reshape(lg2.shape).float().contiguous()
+    out = torch.empty(lg2.shape[0], dtype=torch.int32, device=lg2.device)
+    ops.sample_processed_rows(lg2, q, out, topk, temperature, top_p, min_p, penalty, window, hist, frame, live, advance=advance,
+                              V=lg2.shape[1])
+    return out.reshape(-1, 1)
+
+
 @dataclass
 class ModelArgs:
     """Arguments for the CSM model (reference model.py:99-107)."""
@@ -483,11 +506,12 @@ class Model(nn.Module):
     @torch.no_grad()
     def generate_frame(self, tokens: torch.Tensor, tokens_mask: torch.Tensor, input_pos: torch.Tensor, temperature: float,
                        topk: int, noise: Optional[List[torch.Tensor]] = None, adapters=None, top_p=None,
-                       min_p=None) -> torch.Tensor:
+                       min_p=None, repetition_penalty=None, repetition_window=None) -> torch.Tensor:
         """Reference model.py:140-195: one frame of K codes, [B, K] int32.  ``noise`` (K tensors [B, V_a] of Exp(1)
         draws) pins the sampler for parity tests.  ``adapters``: a LoRAState or None per batch row (csm/lora_bank.py), read
         on a generation's first call.  ``temperature`` / ``topk``: two numbers, a sequence of B values for either one, or None for
         both - one pair per row through the rows sampler (``Engine.generate_frame``).  ``top_p`` / ``min_p``: None (not named), or
         a number / B values for either one - the filtered rows sampler (``sample_filtered_rows``)."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
-        return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise, adapters, top_p, min_p)
+        return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise, adapters, top_p, min_p,
+                                          repetition_penalty, repetition_window)

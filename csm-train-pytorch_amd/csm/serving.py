@@ -31,6 +31,17 @@ capture, so every draw goes through the filtered rows sampler (``csm_sample_filt
 sampler's one launch, on what top-k kept.  A row at (1.0, 0.0) skips both and has the codes of a ``row_sampling`` server; a change
 of any row's four parameters replays the same captured frame.  Without ``row_filters`` nothing here is touched.
 
+Processors.  ``serve(row_sampling=True, row_processors=True, repetition_penalty=1.0, repetition_window=64)`` includes the filters and
+adds a windowed repetition penalty per request (``repetition_penalty`` / ``repetition_window``, resolved and checked like the others)
+and parameters per codebook: each of the six is a number or a sequence of K numbers.  They are written at admission
+(``DecodeState.set_row_processors``: six [K, B] buffers, column b) and every draw goes through the processed rows sampler
+(``csm_sample_processed_rows``), which keeps each slot's last 64 codes per codebook in a ring on the device and penalises the
+logits of the codes of the last ``repetition_window`` frames before the draw.  Every joining row starts at frame 0
+(``reset_row_history``), resumed conversation turns included - a turn's window covers that turn's frames only, nothing is parked
+with the conversation - and only the rows a frame is for count it: the joined rows in the first-frame tail, the active rows in a
+decode frame.  So a request has the same codes in any slot, whoever joins beside it; at penalty 1 they are the codes of a
+``row_filters`` server; a change of any of a row's parameters replays the same captured frame.
+
 Multi-turn conversations (``BatchServer.conversation`` -> ``ServedConversation``) outlive their slot.  A conversation holds a
 slot only while it speaks: at the end of the chunk in which its turn ended the K / V of its history positions are parked
 (``DecodeState.park_row``: one copy, base + kept frames - what the row sampled after EOS or after its length limit is not
@@ -74,17 +85,24 @@ from typing import Iterator, List, Optional, Tuple
 import torch
 
 from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, hear_resampler, open_heard_turn
-from .engine import DecodeState, check_filters, check_sampling
+from .engine import HIST_FRAMES, DecodeState, _as_list, check_filters, check_row_processors, check_sampling
+
+
+def _collapsed(six):
+    """``check_row_processors``' six tuples of K values, each as one number where every codebook has the same."""
+    return tuple(v[0] if all(x == v[0] for x in v) else v for v in six)
 
 
 class Request:
     """One utterance of a ``BatchServer``: its audio arrives in ``chunks`` while it holds a slot; ``done`` once it has ended."""
 
     def __init__(self, rid, text, speaker, adapter, seed, max_audio_frames, tokens, mask, device, temperature=None, topk=None,
-                 top_p=1.0, min_p=0.0):
+                 top_p=1.0, min_p=0.0, repetition_penalty=1.0, repetition_window=HIST_FRAMES):
         self.id, self.text, self.speaker, self.adapter, self.seed = rid, text, speaker, adapter, seed
         self.temperature, self.topk = temperature, topk      # resolved: what it is sampled with
         self.top_p, self.min_p = top_p, min_p                # (likewise; 1.0 / 0.0 on a server without row_filters)
+        # (likewise; 1.0 / 64 without row_processors.  With them each of the six is a number, or a tuple of K: one per codebook)
+        self.repetition_penalty, self.repetition_window = repetition_penalty, repetition_window
         self.max_audio_frames = max_audio_frames
         self.slot: Optional[int] = None          # the slot it holds (None while queued and after it ended)
         self.done = False
@@ -167,14 +185,15 @@ class ServedConversation:
     one all-zero EOS frame; a spoken turn's frames are the sampled codes; the EOS frame always enters with the next feed."""
 
     def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None, top_p=None, min_p=None,
-                 keep_turns: int = 0):
+                 keep_turns: int = 0, repetition_penalty=None, repetition_window=None):
         if on_overflow not in OVERFLOW:
             raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
         self._keep_turns = check_keep_turns(keep_turns)
         self._srv, self._gen = server, server._gen
         self.adapter, self.seed, self._on_overflow = adapter, seed, on_overflow
-        self.temperature, self.topk = server._sampling("conversation", temperature, topk)      # its turns' defaults, resolved
-        self.top_p, self.min_p = server._filters("conversation", top_p, min_p)
+        # its turns' defaults, resolved
+        (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window) = server._resolve(
+            "conversation", temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
         K1 = server._K + 1
         self._tokens = torch.zeros(0, K1, dtype=torch.long, device=self._gen.device)
         self._mask = torch.zeros(0, K1, dtype=torch.bool, device=self._gen.device)
@@ -256,15 +275,18 @@ class ServedConversation:
 
     @torch.inference_mode()
     def say(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: Optional[float] = None,
-            topk: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None) -> Request:
+            topk: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
+            repetition_penalty=None, repetition_window=None) -> Request:
         """Queue the next spoken turn; its audio streams through ``step()`` / ``run()`` like any request's.  The length rule
         counts ``chunk_frames - 1`` frames beyond ``max_audio_length_ms``: a conversation's row samples to the end of its last
         chunk (module docstring), and that must fit the cache - it raises here, not in ``step``.  ``temperature`` / ``topk``
-        (``row_sampling`` servers) and ``top_p`` / ``min_p`` (``row_filters`` servers): this turn's, over the conversation's."""
+        (``row_sampling`` servers), ``top_p`` / ``min_p`` (``row_filters`` servers) and ``repetition_penalty`` / ``repetition_window`` /
+        a sequence of K values for any of the six (``row_processors`` servers): this turn's, over the conversation's.  The
+        window looks at this turn's frames only."""
         self._idle("say")
         srv = self._srv
-        temperature, topk = srv._sampling("say", temperature, topk, (self.temperature, self.topk))
-        top_p, min_p = srv._filters("say", top_p, min_p, (self.top_p, self.min_p))
+        six = srv._resolve("say", temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
+                           (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window))
         max_audio_frames = int(max_audio_length_ms / 80)
         if max_audio_frames < 1:
             raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
@@ -274,7 +296,7 @@ class ServedConversation:
         feed_m = torch.cat([self._mask[self._cached:], tm.bool().to(self._mask.device)], 0)
         self._push(tt.long(), tm.bool())
         req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device,
-                      temperature, topk, top_p, min_p)
+                      *six)
         req._conv, req._base, req.sample_rate = self, self._tokens.shape[0], srv.sample_rate
         srv._next_id += 1
         srv._queue.append(req)
@@ -311,12 +333,24 @@ class BatchServer:
     are launch scalars of the sampler and the key of the captured frame graph.  With it they are the defaults of the requests,
     which may bring their own: the rows sampler reads each slot's pair from device memory and the graph's key is (None, None).
     ``row_filters`` (needs ``row_sampling``): ``top_p`` / ``min_p`` are the requests' default filters and requests may bring their
-    own; every draw goes through the filtered rows sampler."""
+    own; every draw goes through the filtered rows sampler.  ``row_processors`` (needs ``row_sampling``; includes what
+    ``row_filters`` gives): ``repetition_penalty`` / ``repetition_window`` join the requests' defaults, each of the six may be a
+    sequence of K values (one per codebook), and every draw goes through the processed rows sampler, which remembers each slot's
+    last 64 frames (``DecodeState.set_row_processors``)."""
 
     def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
                  row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
-                 output_sample_rate: Optional[int] = None):
+                 output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
+                 repetition_window=HIST_FRAMES):
         out_rs = gen._out_resampler(output_sample_rate)      # (a bad rate raises here, before anything is taken over)
+        if row_processors and not row_sampling:
+            raise ValueError("serve(row_processors=True) needs row_sampling=True: the repetition penalty and per-codebook "
+                             "parameters live in the rows sampler")
+        if not row_processors and (not (repetition_penalty == 1.0 and repetition_window == HIST_FRAMES)
+                                   or any(_as_list(v) is not None for v in (temperature, topk, top_p, min_p))):
+            raise ValueError(f"repetition_penalty={repetition_penalty!r} / repetition_window={repetition_window!r} and a sequence of "
+                             "values per codebook need a server made with serve(row_processors=True) (and row_sampling=True)")
+        row_filters = bool(row_filters or row_processors)
         if row_filters and not row_sampling:
             raise ValueError("serve(row_filters=True) needs row_sampling=True: top-p / min-p live in the rows sampler")
         if not row_filters and not (top_p == 1.0 and min_p == 0.0):
@@ -334,12 +368,18 @@ class BatchServer:
             raise TypeError(f"{type(codec).__name__} has no encode_stream_rows(): hear_slots needs a batched stateful encoder")
         self._gen, self._model = gen, gen._model
         self.slots, self.chunk_frames, self.hear_slots = int(slots), int(chunk_frames), int(hear_slots)
-        self.temperature, self.topk = float(temperature), int(topk)
-        self.row_sampling = bool(row_sampling)
-        if self.row_sampling:                            # (the requests' defaults: held to the requests' rule, before anything is taken over)
-            self.temperature, self.topk = check_sampling(temperature, topk, gen._model.args.audio_vocab_size)
-        self.row_filters = bool(row_filters)
-        self.top_p, self.min_p = check_filters(top_p, min_p) if self.row_filters else (1.0, 0.0)
+        self.row_sampling, self.row_filters, self.row_processors = bool(row_sampling), bool(row_filters), bool(row_processors)
+        self._K = gen._model.args.audio_num_codebooks
+        self.repetition_penalty, self.repetition_window = 1.0, HIST_FRAMES
+        if self.row_processors:                          # (the requests' defaults: held to the requests' rule, before anything is taken over)
+            (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window) = _collapsed(
+                check_row_processors(self._K, gen._model.args.audio_vocab_size, temperature, topk, top_p, min_p, repetition_penalty,
+                                     repetition_window))
+        else:
+            self.temperature, self.topk = float(temperature), int(topk)
+            if self.row_sampling:
+                self.temperature, self.topk = check_sampling(temperature, topk, gen._model.args.audio_vocab_size)
+            self.top_p, self.min_p = check_filters(top_p, min_p) if self.row_filters else (1.0, 0.0)
         gen._run += 1                                    # takes over the model's caches, as generate_batch does
         self._run = gen._run
         self._model.reset_caches()
@@ -359,15 +399,17 @@ class BatchServer:
         if out_rs is not None:
             self._out = out_rs.stream_rows(self.slots, self.chunk_frames * (int(gen.sample_rate) * 80 // 1000))     # (80 ms frames)
         self._model._decode_state = self._state
-        if self.row_sampling:
+        if self.row_processors:
+            for b in range(self.slots):                  # (before the first capture: the frame holds the processed sampler)
+                self._state.set_row_processors(b, *self._defaults())
+        elif self.row_sampling:
             for b in range(self.slots):                  # every row starts with a valid pair: the sampler runs on all of them
                 self._state.set_row_sampling(b, self.temperature, self.topk)
-        if self.row_filters:
+        if self.row_filters and not self.row_processors:
             for b in range(self.slots):                  # (before the first capture: the frame holds the filtered sampler)
                 self._state.set_row_filters(b, self.top_p, self.min_p)
-        K = self._model.args.audio_num_codebooks
+        K = self._K
         dev = gen.device
-        self._K = K
         self._tok = torch.zeros(self.slots, 1, K + 1, dtype=torch.long, device=dev)      # each row's last sampled frame
         self._mask = torch.cat([torch.ones(self.slots, 1, K, dtype=torch.bool), torch.zeros(self.slots, 1, 1, dtype=torch.bool)],
                                2).to(dev)
@@ -406,19 +448,44 @@ class BatchServer:
                              f"row_sampling=True; this server samples without filters)")
         return check_filters(dp if top_p is None else top_p, dm if min_p is None else min_p)
 
+    def _defaults(self):
+        return (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window)
+
+    def _resolve(self, what, temperature, topk, top_p, min_p, repetition_penalty, repetition_window, default=None):
+        """A request's six sampling parameters (None: not named), resolved against ``default`` (the server's if None) and held to
+        the rows' rules - at the call, so a bad request raises before it queues.  On a ``row_processors`` server each is a number
+        or K numbers (one per codebook) and comes back as a number, or as a tuple of K where the codebooks differ; on any other
+        server a penalty, a window or a sequence is refused and the last two come back as 1.0 / 64."""
+        d = default if default is not None else self._defaults()
+        if not self.row_processors:
+            if repetition_penalty is not None or repetition_window is not None or any(
+                    _as_list(v) is not None for v in (temperature, topk, top_p, min_p)):
+                raise ValueError(f"{what}: repetition_penalty / repetition_window and a sequence of values per codebook need a "
+                                 "server made with serve(row_processors=True) (with row_sampling=True)")
+            return (self._sampling(what, temperature, topk, d[:2]) + self._filters(what, top_p, min_p, d[2:4])
+                    + (1.0, HIST_FRAMES))
+        named = (temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        try:
+            return _collapsed(check_row_processors(self._K, self._model.args.audio_vocab_size,
+                                                   *[dv if v is None else v for v, dv in zip(named, d)]))
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+
     def _sample_args(self):
         """What ``serve_first`` / ``serve_frame`` get: the server's two numbers, or None, None (each row's own pair)."""
         return (None, None) if self.row_sampling else (self.temperature, self.topk)
 
     def submit(self, text: str, speaker: int, context, adapter: Optional[str] = None, seed: Optional[int] = None,
                max_audio_length_ms: float = 90_000, temperature: Optional[float] = None, topk: Optional[int] = None,
-               top_p: Optional[float] = None, min_p: Optional[float] = None) -> Request:
+               top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty=None,
+               repetition_window=None) -> Request:
         """Queue one utterance; it takes a slot at the next chunk boundary that has a free one.  The prompt is tokenised here, so
         the reference's length rule ("Inputs too long ...") and an unknown adapter name raise here.  ``temperature`` / ``topk``
-        (``row_sampling`` servers) and ``top_p`` / ``min_p`` (``row_filters`` servers): this request's, over the server's."""
+        (``row_sampling`` servers), ``top_p`` / ``min_p`` (``row_filters`` servers) and ``repetition_penalty`` / ``repetition_window`` /
+        a sequence of K values, one per codebook, for any of the six (``row_processors`` servers): this request's, over the
+        server's."""
         self._check()
-        temperature, topk = self._sampling("submit", temperature, topk)
-        top_p, min_p = self._filters("submit", top_p, min_p)
+        six = self._resolve("submit", temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
         if adapter is not None and adapter not in self._bank:
             known = self._gen._bank is not None and adapter in self._gen._bank.entries
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})" +
@@ -429,7 +496,7 @@ class BatchServer:
         with torch.inference_mode():
             tokens, mask, _ = self._gen._prompt(text, speaker, list(context), max_audio_frames)
         req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device,
-                      temperature, topk, top_p, min_p)
+                      *six)
         req.sample_rate = self.sample_rate
         self._next_id += 1
         self._queue.append(req)
@@ -438,17 +505,20 @@ class BatchServer:
     def conversation(self, context=(), adapter: Optional[str] = None, seed: Optional[int] = None,
                      on_overflow: str = "error", temperature: Optional[float] = None,
                      topk: Optional[int] = None, top_p: Optional[float] = None,
-                     min_p: Optional[float] = None, keep_turns: int = 0) -> ServedConversation:
+                     min_p: Optional[float] = None, keep_turns: int = 0, repetition_penalty=None,
+                     repetition_window=None) -> ServedConversation:
         """A multi-turn dialogue on this server: ``conv.say(text, speaker, max_audio_length_ms)`` queues its next spoken turn (a
         ``Request``), ``conv.add(Segment)`` is the other party's turn, ``conv.close()`` drops its parked cache.  ``adapter`` and
         ``seed`` hold for the whole conversation; ``on_overflow`` / ``keep_turns`` as for ``Generator.conversation`` (``"shift"``
         slides the parked cache at ``say``).  ``temperature`` / ``topk``
-        (``row_sampling`` servers) and ``top_p`` / ``min_p`` (``row_filters`` servers): the defaults of its turns, over the
+        (``row_sampling`` servers), ``top_p`` / ``min_p`` (``row_filters`` servers) and ``repetition_penalty`` /
+        ``repetition_window`` / per-codebook sequences (``row_processors`` servers): the defaults of its turns, over the
         server's; ``say`` may name a turn's own."""
         self._check()
         if adapter is not None and adapter not in self._bank:
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})")
-        return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk, top_p, min_p, keep_turns)
+        return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk, top_p, min_p, keep_turns,
+                                  repetition_penalty, repetition_window)
 
     @property
     def queued(self) -> int:
@@ -569,9 +639,14 @@ class BatchServer:
             req = self._queue.popleft()
             conv = req._conv
             st.set_row_adapter(b, self._bank[req.adapter] if req.adapter is not None else None)
-            if self.row_sampling:
+            if self.row_processors:
+                # (every joining row, resumed turns included: a turn's window covers its own frames)
+                st.set_row_processors(b, req.temperature, req.topk, req.top_p, req.min_p, req.repetition_penalty,
+                                      req.repetition_window)
+                st.reset_row_history(b)
+            elif self.row_sampling:
                 st.set_row_sampling(b, req.temperature, req.topk)
-            if self.row_filters:
+            if self.row_filters and not self.row_processors:
                 st.set_row_filters(b, req.top_p, req.min_p)
             if conv is not None and conv.seed is not None:
                 if conv._noise is None:

@@ -79,14 +79,14 @@ __device__ __forceinline__ int dpp_row_shr_add(int v, int ctrl_n) {   // v + (v 
 // positive number (zero, negative, NaN, inf) counts as 1.  The one-wave / block-wide choice stays block-uniform: a workgroup
 // is one row.
 struct SampleScalars {
-    static constexpr bool FILTERS = false;
+    static constexpr bool FILTERS = false, PENALTY = false;
     int topk;
     float temperature;
     __device__ __forceinline__ int k(int, int) const { return topk; }
     __device__ __forceinline__ float t(int) const { return temperature; }
 };
 struct SampleRows {
-    static constexpr bool FILTERS = false;
+    static constexpr bool FILTERS = false, PENALTY = false;
     const int* topk;
     const float* temperature;
     __device__ __forceinline__ int k(int row, int V) const { const int v = topk[row]; return v < 1 ? 1 : (v > V ? V : v); }
@@ -110,7 +110,7 @@ struct SampleRows {
 // Error: |kernel's sum P_j - exact| <= 2 (V 2^-40 + (2 + dbar) 2^-24), dbar the P-weighted mean of
 // max v - v_j; |kernel's e_i / exact - 1| <= (2 + max v - v_i) 2^-24.
 struct SampleFiltered {
-    static constexpr bool FILTERS = true;
+    static constexpr bool FILTERS = true, PENALTY = false;
     const int* topk;
     const float* temperature;
     const float* top_p;
@@ -119,6 +119,48 @@ struct SampleFiltered {
     __device__ __forceinline__ float t(int row) const { const float v = temperature[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
     __device__ __forceinline__ float p(int row) const { const float v = top_p[row]; return (v > 0.f && v <= 1.f) ? v : 1.f; }
     __device__ __forceinline__ float m(int row) const { const float v = min_p[row]; return (v >= 0.f && v <= 1.f) ? v : 0.f; }
+};
+// SampleProcessed (csm_sample_processed_rows): SampleFiltered plus a windowed repetition penalty and the row's memory of what it
+// drew.  A row keeps, per codebook, a ring of SMP_HIST codes: slot f % SMP_HIST holds the code of frame f of its utterance.  With
+// f = frame[row] and n = min(window[row], f, SMP_HIST), the distinct ids of ring[(f - 1 - j) % SMP_HIST], j < n, that lie in
+// [0, V) get x = x > 0 ? x / r : x * r - ONE correctly rounded fp32 operation on the raw logit, before the division by the
+// temperature; an id seen twice is penalised once, ids outside [0, V) are ignored (so a ring nobody initialised is harmless).
+// A penalty that is not a finite positive number counts as 1, the window is clamped to [0, SMP_HIST].  r = 1 or n = 0 skips all
+// of it (block-uniform) and is the SampleFiltered kernel.  How: wave 0 loads the ring, one slot per lane, and builds a V-bit
+// membership bitmap in LDS (it zeroes the 72 / 128 words, then every lane whose slot the window reaches ORs its bit in: one ds_or;
+// a readlane walk over the entries cost 80 ns per entry, 5 us at n = 64) while the other waves zero the histograms; one more
+// barrier publishes it, and every thread tests its own bits before it forms x / temperature.  The
+// ring, the penalty, the window, the frame and the live flag are loads of block-uniform or per-lane addresses issued with the
+// logits' and the Exp(1) row's, so all are in flight together.  A live row then stores its winner to ring[f % SMP_HIST] (after
+// every read of the ring: the reads sit before the first barrier, the store after the last; with n = SMP_HIST it overwrites the
+// oldest entry read) and, with `advance`, f + 1 to frame[row] - plain vector stores by the thread that writes `out`.  Only this
+// row's block touches the row's ring and counter.
+constexpr int SMP_HIST = 64;
+struct SampleProcessed {
+    static constexpr bool FILTERS = true, PENALTY = true;
+    const int* topk;
+    const float* temperature;
+    const float* top_p;
+    const float* min_p;
+    const float* penalty;
+    const int* window;
+    int* hist;
+    int ldh;
+    int* frame;
+    const int* live;
+    int advance;
+    __device__ __forceinline__ int k(int row, int V) const { const int v = topk[row]; return v < 1 ? 1 : (v > V ? V : v); }
+    __device__ __forceinline__ float t(int row) const { const float v = temperature[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
+    __device__ __forceinline__ float p(int row) const { const float v = top_p[row]; return (v > 0.f && v <= 1.f) ? v : 1.f; }
+    __device__ __forceinline__ float m(int row) const { const float v = min_p[row]; return (v >= 0.f && v <= 1.f) ? v : 0.f; }
+    __device__ __forceinline__ float r(int row) const { const float v = penalty[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
+    __device__ __forceinline__ int w(int row) const { const int v = window[row]; return v < 0 ? 0 : (v > SMP_HIST ? SMP_HIST : v); }
+    __device__ __forceinline__ void wrote(int row, int f, int winner) const {   // (one thread, after the draw)
+        if (live[row]) {
+            hist[(size_t)row * ldh + (f & (SMP_HIST - 1))] = winner;
+            if (advance) frame[row] = f + 1;
+        }
+    }
 };
 constexpr float SMP_MASS_ONE = 1099511627776.f;                          // 2^40: the fixed-point image of e = 1
 __device__ __forceinline__ unsigned long long smp_mass(float e) { return (unsigned long long)(e * SMP_MASS_ONE); }   // (exact product, truncated)
@@ -150,6 +192,17 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
     const int lane = threadIdx.x & 63;
     STAMP_DECL;
     STAMP(0);
+    float rep = 1.f;
+    int pframe = 0, pn = 0, recent = -1;
+    if constexpr (Params::PENALTY) {
+        // (wave 0's lane l takes slot l of the ring, whatever the frame is: the load depends on no other load)
+        if (threadIdx.x < SMP_HIST) recent = prm.hist[(size_t)row * prm.ldh + threadIdx.x];
+        rep = prm.r(row);
+        pframe = prm.frame[row];
+        const int w = prm.w(row);
+        pn = __builtin_amdgcn_readfirstlane(pframe < w ? (pframe < 0 ? 0 : pframe) : w);        // min(window, frame, SMP_HIST)
+    }
+    const bool pen_on = Params::PENALTY && rep != 1.f && pn > 0;         // (block-uniform)
     float qv[NPT], val[NPT];
 #pragma unroll
     for (int j = 0; j < NPT; ++j) {
@@ -163,6 +216,28 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
     }
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) hist[ps][threadIdx.x] = 0u;
+    if constexpr (Params::PENALTY) {
+        constexpr int PEN_WORDS = 256 * NPT / 32;           // the membership bitmap: one bit per id (72 or 128 words)
+        __shared__ uint32_t pbits[PEN_WORDS];
+        if (pen_on) {
+            if (threadIdx.x < 64) {                         // wave 0: lane l zeroes words l, l + 64, then sets its slot's bit
+                pbits[lane] = 0u;
+                if (lane + 64 < PEN_WORDS) pbits[lane + 64] = 0u;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // (one wave: its LDS operations complete in order)
+                __builtin_amdgcn_wave_barrier();
+                // V <= 256 * NPT: the word lies inside pbits.  An OR does not depend on the order of the lanes: the same bitmap
+                // every run, and an id that is in the window twice sets one bit
+                const int age = (pframe - 1 - lane) & (SMP_HIST - 1);      // slot `lane` holds the code of frame f - 1 - age
+                if (age < pn && (unsigned)recent < (unsigned)V) atomicOr(&pbits[recent >> 5], 1u << (recent & 31));
+            }
+            __syncthreads();                                // the bitmap (block-uniform branch)
+#pragma unroll
+            for (int j = 0; j < NPT; ++j) {                 // thread's id c = threadIdx.x + 256 j: word 8 j + threadIdx.x / 32
+                const bool hit = (pbits[8 * j + (threadIdx.x >> 5)] >> (threadIdx.x & 31)) & 1u;
+                if (hit) val[j] = val[j] > 0.f ? val[j] / rep : val[j] * rep;
+            }
+        }
+    }
     uint32_t key[NPT];
     float tmax = -INFINITY;
 #pragma unroll
@@ -368,7 +443,10 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
 #define CSM_ARG_STEP(o) { ValIdx y; y.v = lane_xor<o>(best.v); y.i = lane_xor<o>(best.i); best = vi_max(best, y); }
             CSM_ARG_STEP(32) CSM_ARG_STEP(16) CSM_ARG_STEP(8) CSM_ARG_STEP(4) CSM_ARG_STEP(2) CSM_ARG_STEP(1)
 #undef CSM_ARG_STEP
-            if (lane == 0) out[row] = best.i;
+            if (lane == 0) {
+                out[row] = best.i;
+                if constexpr (Params::PENALTY) prm.wrote(row, pframe, best.i);
+            }
         }
         STAMP(6);
         STAMP_FLUSH(300);
@@ -405,7 +483,10 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
     }
     STAMP(5);
     best = block_arg<true>(best, red);
-    if (threadIdx.x == 0) out[row] = best.i;
+    if (threadIdx.x == 0) {
+        out[row] = best.i;
+        if constexpr (Params::PENALTY) prm.wrote(row, pframe, best.i);
+    }
     STAMP(6);
     STAMP_FLUSH(300);
 }
@@ -495,6 +576,21 @@ extern "C" int csm_sample_filtered_rows(const float* logits, const float* q, int
     if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleFiltered>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
     else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleFiltered>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
     CSM_CHECK_LAUNCH("csm_sample_filtered_rows");
+    return 0;
+}
+
+extern "C" int csm_sample_processed_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
+                                         const float* temperature, const float* top_p, const float* min_p, const float* penalty,
+                                         const int* window, int* hist, int ldh, int* frame, const int* live, int advance,
+                                         hipStream_t stream) {
+    CSM_REQUIRE(logits && q && out && topk && temperature && top_p && min_p && penalty && window && hist && frame && live &&
+                rows > 0 && V > 0 && ldl >= V, "csm_sample_processed_rows: bad arguments");
+    CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "csm_sample_processed_rows: V=%d exceeds %d", V, 256 * SMP_PER_THREAD);
+    CSM_REQUIRE(ldh >= SMP_HIST, "csm_sample_processed_rows: ldh=%d is below the ring's %d", ldh, SMP_HIST);
+    const SampleProcessed prm = {topk, temperature, top_p, min_p, penalty, window, hist, ldh, frame, live, advance};
+    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleProcessed>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleProcessed>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    CSM_CHECK_LAUNCH("csm_sample_processed_rows");
     return 0;
 }
 

@@ -262,6 +262,23 @@ int csm_sample_topk_rows(const float* logits, const float* q, int* out, int rows
  * not depend on the order of summation and a launch gives the same bits every time (error bound: DESIGN.md section 6). */
 int csm_sample_filtered_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
                              const float* temperature, const float* top_p, const float* min_p, csm_stream_t stream);
+/* A windowed repetition penalty and the row's memory of its draws (additive, ABI 3): csm_sample_filtered_rows with, all in DEVICE
+ * memory and indexed by row, penalty[r] (float), window[r] (int, frames), the row's ring hist + r * ldh (CSM_SAMPLE_HIST ints,
+ * ldh >= CSM_SAMPLE_HIST: slot f % CSM_SAMPLE_HIST holds the code the row drew in frame f of its utterance), frame[r] (f, the
+ * frame being sampled) and live[r].  With n = min(window[r], f, CSM_SAMPLE_HIST) and T the distinct ids among
+ * ring[(f - 1 - j) % CSM_SAMPLE_HIST], j < n, that lie in [0, V):  x_t = x_t > 0 ? x_t / penalty : x_t * penalty  for t in T -
+ * one correctly rounded fp32 operation on the raw logit, before the division by the temperature; then the draw of
+ * csm_sample_filtered_rows.  A row with penalty 1 or n = 0 writes the index csm_sample_filtered_rows writes.  Afterwards a row
+ * with live[r] != 0 stores its winner to ring[f % CSM_SAMPLE_HIST] (every read of the ring comes first) and, with `advance`
+ * nonzero, f + 1 to frame[r]; a row with live[r] = 0 writes `out` only.  Made safe in the kernel: a penalty that is not a finite
+ * positive number counts as 1, the window is clamped to [0, CSM_SAMPLE_HIST], ring ids outside [0, V) are ignored (an
+ * uninitialised ring is harmless), any f addresses a slot inside the ring.  One launch may use a (hist, frame) pair for one
+ * call at a time: only row r's workgroup touches row r's ring and counter. */
+#define CSM_SAMPLE_HIST 64
+int csm_sample_processed_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
+                              const float* temperature, const float* top_p, const float* min_p, const float* penalty,
+                              const int* window, int* hist, int ldh, int* frame, const int* live, int advance,
+                              csm_stream_t stream);
 
 /* ---- K15: batch-1 decode of Model.generate_frame (model.py:161-195) against KV caches ------------------------------ *
  * y[b][n] = sum_k x[b][k] W[n][k] (+ residual[b][n]), B <= 16 (weight-streaming matrix-vector product).  B <= 4: VALU kernels,

@@ -12,7 +12,8 @@ and against the same utterances one at a time with their adapter live as model.l
 GEN_FP8=1: decode frames/s with bf16 and with FP8 (weight-only e4m3) decode weights,
 alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in each mode.  GEN_SERVE=1: the running batch (Generator.serve): rows-codec step against single steps, the server step at
 16 rows, the join stall (serve_main).  GEN_SERVE_SAMPLING=1: the rows sampler against the scalar one and the 16-row
-server step with row_sampling off / on (serve_sampling_main); GEN_SERVE_SAMPLING=filters: the filtered rows sampler (top-p / min-p)
+server step with row_sampling off / on (serve_sampling_main); GEN_SERVE_SAMPLING=processors: the processed rows sampler (repetition penalty, per-codebook
+parameters; serve_processors_main); GEN_SERVE_SAMPLING=filters: the filtered rows sampler (top-p / min-p)
 in four forms and the server step with row_filters off / on (serve_filters_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
 time to the first chunk of turns 1 / 3 / 5 against stateless submits, one append_rows against one-row calls, park / resume, aggregate
 frames/s (serve_conv_main).  GEN_HEAR=1: a 5 s heard turn's last sample to the first chunk of the reply, with
@@ -783,6 +784,93 @@ def serve_filters_main():
               flush=True)
 
 
+def serve_processors_main():
+    """GEN_SERVE_SAMPLING=processors: a windowed repetition penalty and per-codebook parameters per request
+    (Generator.serve(row_sampling=True, row_processors=True)), in the shape of GEN_SERVE_SAMPLING=filters.  (a) the sampler alone, 16
+    rows, V = 2051 in the model's padded logits buffer, (50, 0.9) with top-p 0.9 / min-p 0.05 in every row (the one-wave filter):
+    csm_sample_filtered_rows; csm_sample_processed_rows with penalty 1 (the block-uniform skip), with penalty 1.3 at window 16 and
+    at window 64 (rings of random ids, frame 200, every row live).  200 back-to-back launches between two synchronisations,
+    alternated, median (min .. max) of GEN_ROUNDS repeats (default 5).  (b) the steady 16-row server step of GEN_SERVE's setting:
+    row_filters on (the yardstick: the code before the processors), row_processors on at identity (penalty 1 everywhere), on with a
+    mixed load (penalties 1.0 .. 2.0 at windows 0 .. 64, an acoustic temperature / top-k of their own in half of the rows); each
+    leg a fresh server, alternated GEN_ROUNDS times (default 3), per leg the median of 20 steps."""
+    dev = "cuda:0"
+    n = 4
+    V, ld = 2051, 2112
+    g = torch.Generator(device=dev).manual_seed(0)
+    lg = torch.randn(16, ld, device=dev, generator=g) * 2
+    q = torch.empty(16, V, device=dev).exponential_(1, generator=g)
+    out = torch.empty(16, dtype=torch.int32, device=dev)
+
+    def f32(v):
+        return torch.tensor(v, dtype=torch.float32, device=dev)
+
+    def i32(v):
+        return torch.tensor(v, dtype=torch.int32, device=dev)
+    k, t, p, m = i32([50] * 16), f32([0.9] * 16), f32([0.9] * 16), f32([0.05] * 16)
+    hist = torch.randint(0, V, (16, 64), device=dev, generator=g).to(torch.int32)
+    frame, live = i32([200] * 16), i32([1] * 16)
+    r_off, r_on, w16, w64 = f32([1.0] * 16), f32([1.3] * 16), i32([16] * 16), i32([64] * 16)
+
+    def processed(r, w):
+        return lambda: ops.sample_processed_rows(lg, q, out, k, t, p, m, r, w, hist, frame, live, advance=False, V=V)
+    legs = {"filtered (csm_sample_filtered_rows)": lambda: ops.sample_filtered_rows(lg, q, out, k, t, p, m, V=V),
+            "processed, penalty 1": processed(r_off, w64),
+            "processed, penalty 1.3 at window 16": processed(r_on, w16),
+            "processed, penalty 1.3 at window 64": processed(r_on, w64)}
+    rounds = int(os.environ.get("GEN_ROUNDS", 5))
+    res = {name: [] for name in legs}
+    for f in legs.values():
+        _timed(f, 20)
+    for _ in range(rounds):
+        for name, f in legs.items():
+            res[name].append(_timed(f, 200))
+    for name, v in res.items():
+        v.sort()
+        print(f"GEN_SERVE_SAMPLING=processors (a) sampler, 16 rows, V={V}: {name}: median {v[len(v) // 2] * 1e6:.2f} us per launch "
+              f"(min {v[0] * 1e6:.2f}, max {v[-1] * 1e6:.2f}; {rounds} x 200 back-to-back launches)", flush=True)
+    if os.environ.get("GEN_SERVE_PARTS", "ab") == "a":
+        return
+    # ---- (b) the server step
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    codec = make_codec(dev)
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=codec)
+    K = model.args.audio_num_codebooks
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+    pens = [(1.0, 64), (1.3, 16), (2.0, 64), (1.1, 0), (1.5, 33), (1.3, 64), (1.2, 8), (1.7, 64)]
+    mixed = []
+    for b in range(16):
+        kw = dict(top_p=0.9, min_p=0.05, repetition_penalty=pens[b % 8][0], repetition_window=pens[b % 8][1])
+        if b % 2:
+            kw.update(temperature=[0.9] + [0.7] * (K - 1), topk=[50] + [30] * (K - 1))
+        mixed.append(kw)
+    base = "row_filters (the yardstick)"
+    modes = {base: (dict(row_filters=True), [{}] * 16), "row_processors, identity": (dict(row_processors=True), [{}] * 16),
+             "row_processors, mixed": (dict(row_processors=True), mixed)}
+    meds = {name: [] for name in modes}
+    for _ in range(rounds):
+        for name, (flags, kws) in modes.items():
+            srv = gen.serve(slots=16, chunk_frames=n, row_sampling=True, **flags)
+            for i in range(16):
+                srv.submit(f"utterance number {i}: {text}", i, ctx, seed=i, max_audio_length_ms=80 * 400, **kws[i])
+            _timed(srv.step, 1)                                              # 16 prefills + the first chunk
+            _timed(srv.step, 2)                                              # eager warm-up frame, graph capture
+            steps = sorted(_timed(srv.step, 1) for _ in range(20))
+            meds[name].append(steps[len(steps) // 2])
+    for name, v in meds.items():
+        print(f"GEN_SERVE_SAMPLING=processors (b) server step, 16 rows x {n} frames, {name}: medians of 20 steps "
+              f"{[round(x * 1e3, 2) for x in v]} ms -> median {sorted(v)[len(v) // 2] * 1e3:.2f} ms, spread of the repeats "
+              f"{(max(v) - min(v)) * 1e3:.2f} ms", flush=True)
+    off = sorted(meds[base])[rounds // 2]
+    for name in ("row_processors, identity", "row_processors, mixed"):
+        on = sorted(meds[name])[rounds // 2]
+        print(f"GEN_SERVE_SAMPLING=processors (b) {name} - row_filters: {(on - off) * 1e3:+.2f} ms per step = "
+              f"{(on - off) * 1e6 / n:+.1f} us per frame (row_filters' own repeats span {(max(meds[base]) - min(meds[base])) * 1e3:.2f} ms)",
+              flush=True)
+
+
 def serve_conv_main():
     """GEN_SERVE_CONV=1: conversations on the running batch (BatchServer.conversation) on CSM-1B random init - 16 slots,
     chunk_frames 4, 16 conversations of 6 turns: odd turns spoken (GEN_FRAMES frames, default 24), even turns 5 s of the other
@@ -1326,6 +1414,8 @@ def main():
         return serve_sampling_main()
     if os.environ.get("GEN_SERVE_SAMPLING") == "filters":
         return serve_filters_main()
+    if os.environ.get("GEN_SERVE_SAMPLING") == "processors":
+        return serve_processors_main()
     if os.environ.get("GEN_SERVE_CONV") == "1":
         return serve_conv_main()
     if os.environ.get("GEN_SERVE") == "1":
