@@ -80,6 +80,7 @@ _SIGS = {
     "csm_adamw_step_split_live": ([_p, _p, _p, _p, _p, _ll, _f, _f, _f, _f, _f, _i, _p, _f, _i, _p, _p], _i),
     "csm_set_adamw_blocks": ([_i], _i),
     "csm_gemv_bf16": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
+    "csm_gemv_last_kernel": ([], C.c_char_p),
     "csm_gemv_bf16_kext": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _i, _p, _p, _i, _i, _i, _p, _p], _i),
     "csm_lora_project_bf16": ([_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _f, _p], _i),
     "csm_lora_project_rows_bf16": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _p], _i),

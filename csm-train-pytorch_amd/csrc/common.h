@@ -167,3 +167,8 @@ extern "C" void csm_set_error(const char* fmt, ...);
             return 1;                                                                 \
         }                                                                             \
     } while (0)
+
+// What the decode product launchers (generate.hip, quant.hip) record per launch for csm_gemv_last_kernel (generate.hip): a format
+// that takes (first template argument, output type name, further arguments) and the values - the name is put together on request.
+struct CsmGemvLast { const char* fmt; const char* t; int a[6]; };
+extern CsmGemvLast g_last_gemv;

@@ -2130,6 +2130,22 @@ extern "C" int csm_decode_stamps(unsigned long long* host, int max_records) {
 //  that launch streams 32 MB and is bound by its loads, not by the per-wave normalisation: one pair per wave stays the default)
 // (g_gemv_mfma_small: B = 2..4 through gemv_mfma_kernel as well - A/B measurement only, off by default: it gives up the B <= 4
 //  products' bit-equality with the one-row kernels)
+// the decode product kernel the library launched last, with its template arguments (host bookkeeping only: the kernel-level tests
+// assert with it which kernel took a case); written by the launchers below and by csm_gemv_fp8w (quant.hip)
+// (a launcher only stores the arguments - a few host stores per launch; the name is put together when it is asked for)
+CsmGemvLast g_last_gemv = {nullptr, "", {0, 0, 0, 0, 0, 0}};
+extern "C" const char* csm_gemv_last_kernel(void) {
+    static char name[128];
+    const CsmGemvLast& l = g_last_gemv;
+    name[0] = 0;
+    if (l.fmt) (void)snprintf(name, sizeof(name), l.fmt, l.a[0], l.t, l.a[1], l.a[2], l.a[3], l.a[4], l.a[5]);
+    return name;
+}
+// fmt takes (int, type name, int...) in this order: the first template argument, the output type, the rest
+static inline void gemv_note(const char* fmt, int a0, const char* t, int a1 = 0, int a2 = 0, int a3 = 0, int a4 = 0, int a5 = 0) {
+    g_last_gemv.fmt = fmt; g_last_gemv.t = t;
+    g_last_gemv.a[0] = a0; g_last_gemv.a[1] = a1; g_last_gemv.a[2] = a2; g_last_gemv.a[3] = a3; g_last_gemv.a[4] = a4; g_last_gemv.a[5] = a5;
+}
 static int g_gemv_reg = 1, g_gemv_nt = 1, g_gemv_rpw = 1, g_gemv_regn = 1, g_gemv_mfma_small = 0;   // csm_set_decode_tuning (A/B: tools/probes)
 extern "C" int csm_set_decode_tuning(int key, int value) {
     if (key == 0) g_gemv_reg = value; else if (key == 1) g_gemv_nt = value; else if (key == 2) g_gemv_rpw = value;
@@ -2153,6 +2169,8 @@ static int gemv_mfma_launch(const void* x, const void* W, void* y, const void* r
     else { if (nt) LMS(bf16_t, false, true); else LMS(bf16_t, false, false); }
 #undef LMS
 #undef LM
+    gemv_note("gemv_mfma_kernel<%d, %s, %d, %d, ext%d>", spw <= 1 ? 1 : (spw <= 2 ? 2 : (spw <= 4 ? 4 : 8)),
+              (out_f32 && !swiglu) ? "float" : "bf16", swiglu ? 1 : 0, nt ? 1 : 0, ExtKind<Ext...>::v);
     CSM_CHECK_LAUNCH("csm_gemv_bf16");
     return 0;
 }
@@ -2195,6 +2213,11 @@ static int gemv_launch(const void* x, const void* W, void* y, const void* residu
         else { if (nt) LK(bf16_t, false, true); else LK(bf16_t, false, false); }
 #undef LK
 #undef LR
+        {
+            const bool rpw = swiglu && K == 1024 && !nt && g_gemv_rpw > 1 && no >= 2048;
+            gemv_note("gemv_reg_kernel<%d, %s, %d, %d, %d, ext%d>", K / 512, (out_f32 && !swiglu) ? "float" : "bf16", swiglu ? 1 : 0,
+                      nt ? 1 : 0, rpw ? (g_gemv_rpw == 2 ? 2 : 4) : 1, ExtKind<Ext...>::v);
+        }
         CSM_CHECK_LAUNCH("csm_gemv_bf16");
         return 0;
     }
@@ -2213,6 +2236,9 @@ static int gemv_launch(const void* x, const void* W, void* y, const void* residu
 #undef LNK
 #undef LNB
 #undef LN
+        gemv_note(B == 2 ? "gemv_regn_kernel<%d, 2, %s, %d, %d, %d, ext%d>" : B == 3 ? "gemv_regn_kernel<%d, 3, %s, %d, %d, %d, ext%d>"
+                                                                                      : "gemv_regn_kernel<%d, 4, %s, %d, %d, %d, ext%d>",
+                  K / 512, (out_f32 && !swiglu) ? "float" : "bf16", swiglu ? 1 : 0, (nt && K != 1024) ? 1 : 0, K == 1024 ? 2 : 4, ExtKind<Ext...>::v);
         CSM_CHECK_LAUNCH("csm_gemv_bf16");
         return 0;
     }
@@ -2223,6 +2249,7 @@ static int gemv_launch(const void* x, const void* W, void* y, const void* residu
     else if (out_f32) { if (B == 1) L(1, float, false); else if (B == 2) L(2, float, false); else if (B == 3) L(3, float, false); else L(4, float, false); }
     else { if (B == 1) L(1, bf16_t, false); else if (B == 2) L(2, bf16_t, false); else if (B == 3) L(3, bf16_t, false); else L(4, bf16_t, false); }
 #undef L
+    gemv_note("gemv_kernel<%d, %s, %d, ext%d>", B, (out_f32 && !swiglu) ? "float" : "bf16", swiglu ? 1 : 0, ExtKind<Ext...>::v);
     CSM_CHECK_LAUNCH("csm_gemv_bf16");
     return 0;
 }
@@ -2283,6 +2310,7 @@ extern "C" int csm_lora_project_rows_bf16(const void* x, const void* const* At, 
 #define L(NB) hipLaunchKernelGGL((lora_project_rows_kernel<NB>), grid, dim3(512), 0, stream, (const bf16_t*)x, (const bf16_t* const*)At, (bf16_t*)t, row_adapter, scale, n_adapters, B, K, ldx, lda, ldt, (const bf16_t*)norm_scale, eps)
     if (nb == 1) L(1); else if (nb == 2) L(2); else if (nb == 3) L(3); else L(4);
 #undef L
+    gemv_note("lora_project_rows_kernel<%d>%.0s", nb, "");
     CSM_CHECK_LAUNCH("csm_lora_project_rows_bf16");
     return 0;
 }
@@ -2295,6 +2323,7 @@ extern "C" int csm_lora_project_bf16(const void* x, const void* At, void* t, int
 #define L(NB) hipLaunchKernelGGL((lora_project_kernel<NB>), dim3(kx / 8), dim3(512), 0, stream, (const bf16_t*)x, (const bf16_t*)At, (bf16_t*)t, K, ldx, lda, ldt, (const bf16_t*)norm_scale, eps, scale)
     if (B == 1) L(1); else if (B == 2) L(2); else if (B == 3) L(3); else L(4);
 #undef L
+    gemv_note("lora_project_kernel<%d>%.0s", B, "");
     CSM_CHECK_LAUNCH("csm_lora_project_bf16");
     return 0;
 }
@@ -2307,6 +2336,7 @@ extern "C" int csm_gemv_t_bf16(const void* x, const void* W, void* y, int B, int
     if (out_f32) { if (B == 1) L(1, float); else if (B == 2) L(2, float); else if (B == 3) L(3, float); else L(4, float); }
     else { if (B == 1) L(1, bf16_t); else if (B == 2) L(2, bf16_t); else if (B == 3) L(3, bf16_t); else L(4, bf16_t); }
 #undef L
+    gemv_note("gemv_t_kernel<%d, %s>", B, out_f32 ? "float" : "bf16");
     CSM_CHECK_LAUNCH("csm_gemv_t_bf16");
     return 0;
 }

@@ -419,6 +419,8 @@ extern "C" int csm_gemv_fp8w(const void* x, const void* W8, const void* scale, v
         else { if (nt) LMS(bf16_t, false, true); else LMS(bf16_t, false, false); }
 #undef LMS
 #undef LM
+        g_last_gemv = {"gemv_fp8_mfma_kernel<%d, %s, %d, %d>", (out_f32 && !swiglu) ? "float" : "bf16",
+                       {spw <= 1 ? 1 : (spw <= 2 ? 2 : (spw <= 4 ? 4 : 8)), swiglu ? 1 : 0, nt ? 1 : 0, 0, 0, 0}};
         CSM_CHECK_LAUNCH("csm_gemv_fp8w");
         return 0;
     }
@@ -437,6 +439,9 @@ extern "C" int csm_gemv_fp8w(const void* x, const void* W8, const void* scale, v
 #undef LNB
 #undef LN
 #undef ARGS
+    g_last_gemv = {B == 1 ? "gemv_fp8_kernel<%d, 1, %s, %d, %d>" : B == 2 ? "gemv_fp8_kernel<%d, 2, %s, %d, %d>"
+                   : B == 3 ? "gemv_fp8_kernel<%d, 3, %s, %d, %d>" : "gemv_fp8_kernel<%d, 4, %s, %d, %d>",
+                   (out_f32 && !swiglu) ? "float" : "bf16", {kc, swiglu ? 1 : 0, (nt && kc != 1) ? 1 : 0, 0, 0, 0}};
     CSM_CHECK_LAUNCH("csm_gemv_fp8w");
     return 0;
 }

@@ -290,8 +290,23 @@ int csm_sample_processed_rows(const float* logits, const float* q, int* out, int
  * key 3 = two to four batch rows: K = 1024 / 2048 products keep every row of x in registers (default 1; 0 = the LDS kernel),
  * key 4 = two to four batch rows through the B = 5..16 MFMA kernel (default 0; A/B measurement only) */
 int csm_set_decode_tuning(int key, int value);
+/* Layout and alignment of the decode products (every csm_gemv_* entry point below):
+ *  - residual [B][ldy] shares ldy with y: the kernels read residual[b * ldy + n] (and may be y itself);
+ *  - the SwiGLU form writes y [B][N / 2] with the same ldy (W and ext_B hold the N gate / up rows interleaved);
+ *  - the bf16 entry points read x, W and norm_scale rows in 16-byte loads: x (the table under row_index), W and norm_scale must be
+ *    16-byte aligned, ldx and ldw multiples of 8.  csm_gemv_bf16 / _ex / _kext / _kext_rows check the leading dimensions only -
+ *    the alignment of the three bases is the caller's duty (csm_gemv_fp8w refuses a misaligned x, W8 or norm_scale).
+ *    csm_gemv_t_bf16 reads W [K][ldw] in 16-byte loads (W 16-byte aligned, ldw a multiple of 8, ldw >= N rounded up to 8) and x
+ *    element by element. */
 int csm_gemv_bf16(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
                   int out_f32, csm_stream_t stream);
+/* The decode product kernel launched last by csm_gemv_bf16 / _ex / _kext / _kext_rows, csm_gemv_fp8w, csm_lora_project_bf16 /
+ * _rows_bf16 or csm_gemv_t_bf16, with its template arguments, e.g. "gemv_reg_kernel<4, bf16, 0, 1, 1, ext0>" (host bookkeeping
+ * for tests and probes, like csm_gemm_last_kernel; "" before the first launch; not thread-safe).  gemv_reg_kernel<KCH, T, SWIGLU,
+ * NT, RPW, ext>, gemv_regn_kernel<KCH, NB, T, SWIGLU, NT, SC, ext>, gemv_kernel<NB, T, SWIGLU, ext>, gemv_mfma_kernel<SEG, T,
+ * SWIGLU, NT, ext>, gemv_fp8_kernel<KC, NB, T, SWIGLU, NT>, gemv_fp8_mfma_kernel<SEG, T, SWIGLU, NT>, lora_project_kernel<NB>,
+ * lora_project_rows_kernel<NB>, gemv_t_kernel<NB, T>; ext0 = no K-extension, ext1 = csm_gemv_bf16_kext, ext2 = _kext_rows. */
+const char* csm_gemv_last_kernel(void);
 /* csm_gemv_bf16 with the neighbouring element-wise steps of a decode layer fused in: norm_scale != NULL applies torchtune
  * RMSNorm (eps) to x first; swiglu = 1 reads W as interleaved gate/up rows (N = 2F) and writes y[b][F] = silu(g) * u;
  * row_index != NULL takes batch row b of x from row (row_index[b] + row_offset) of the table x (embedding lookup of a
