@@ -12,14 +12,14 @@ With 288 GB of HBM nothing is recomputed.
 """
 from __future__ import annotations
 
-import math
-import numbers
 from contextlib import contextmanager
 from typing import Dict, List, Optional
 
 import torch
 
 from .hip import ops
+from .sampling import (RowSampler, _is_number, check_filters, check_processors, check_row_processors,  # noqa: F401
+                       check_sampling, names_processors)
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -959,34 +959,14 @@ class Engine:
 
         qall = st.noise_buf          # all Exp(1) draws of the frame (the reference draws them one codebook at a time, model.py:79-82)
 
-        if temperature is None and topk is None:
-            # each row's own pair, read by the sampler from the state's row buffers (written outside the graph: set_row_sampling)
-            from .models.model import sample_filtered_rows, sample_processed_rows, sample_topk_rows
-            if st.row_processors is not None:
-                # ... each row's own six parameters per codebook (set_row_processors): the processed rows sampler, which also keeps
-                # the rows' rings of sampled codes; the last codebook's draw counts the frame
-                pt, pk, pp, pm, pr, pw = st.proc
-
-                def draw(lg, i):
-                    return sample_processed_rows(lg[:, :V], pk[i], pt[i], pp[i], pm[i], pr[i], pw[i], st.code_hist[:, i],
-                                                 st.hist_frame, st.hist_live, advance=(i == K - 1), q=qall[i])
-            elif st.row_filters is not None:
-                # ... and its own top-p / min-p (set_row_filters): the filtered rows sampler; a (1, 0) row is the rows sampler's
-                row_t, row_k = st.row_sampling_buffers()
-                row_p, row_m = st.row_filter_buffers()
-
-                def draw(lg, i):
-                    return sample_filtered_rows(lg[:, :V], row_k, row_t, row_p, row_m, qall[i])
-            else:
-                row_t, row_k = st.row_sampling_buffers()
-
-                def draw(lg, i):
-                    return sample_topk_rows(lg[:, :V], row_k, row_t, qall[i])
-        elif temperature is None or topk is None:
+        if (temperature is None) != (topk is None):
             raise ValueError("temperature and topk are both numbers, or both None (each row's own pair: set_row_sampling)")
-        else:
-            def draw(lg, i):
-                return sample_topk(lg[:, :V], topk, temperature, qall[i])
+
+        def draw(lg, i):
+            if temperature is None:
+                # each row's own parameters, read by the sampler from the state's buffers (written outside the graph)
+                return st.sampler.draw(lg[:, :V], i, qall[i])
+            return sample_topk(lg[:, :V], topk, temperature, qall[i])
 
         ops.gemv(last_h, m.block("codebook0_head.padded"), st.logits)
         samples = [draw(st.logits, 0)]
@@ -1305,117 +1285,6 @@ def _prime_graph_rng(device):
     _graph_rng_primed = g
 
 
-def _is_number(x):
-    """One value for all rows: a real number, or a 0-d tensor / array of one (what ``float()`` / ``int()`` take)."""
-    return (isinstance(x, numbers.Real) and not isinstance(x, bool)) or getattr(x, "ndim", None) == 0
-
-
-def _as_list(x):
-    """A sequence of per-row values (list / tuple / 1-D tensor or array) as a list; None for anything else."""
-    if isinstance(x, (str, bytes)) or x is None:
-        return None
-    if hasattr(x, "tolist"):
-        x = x.tolist()
-    return list(x) if isinstance(x, (list, tuple)) else None
-
-
-def check_sampling(temperature, topk, vocab):
-    """The rule for one row's sampling parameters: ``temperature`` a finite number > 0, ``topk`` an integer in 1..vocab (the
-    audio vocabulary).  Returns (float, int); raises ValueError with the offending value."""
-    try:
-        t = float(temperature)
-    except (TypeError, ValueError):
-        t = float("nan")
-    if isinstance(temperature, bool) or not (math.isfinite(t) and t > 0.0):
-        raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
-    try:
-        k = int(topk)
-        whole = not isinstance(topk, bool) and k == topk
-    except (TypeError, ValueError, OverflowError):
-        k, whole = 0, False
-    if not whole or not 1 <= k <= int(vocab):
-        raise ValueError(f"topk must be an integer in 1..{int(vocab)} (the audio vocabulary), got {topk!r}")
-    return t, k
-
-
-def check_filters(top_p, min_p):
-    """The rule for one row's sampling filters: ``top_p`` a number in (0, 1] (1: no nucleus cut), ``min_p`` a number in [0, 1]
-    (0: no min-p cut).  Returns (float, float); raises ValueError with the offending value."""
-    out = []
-    for name, v, ok, rule in (("top_p", top_p, lambda f: 0.0 < f <= 1.0, "in (0, 1]"),
-                              ("min_p", min_p, lambda f: 0.0 <= f <= 1.0, "in [0, 1]")):
-        try:
-            f = float(v)
-        except (TypeError, ValueError):
-            f = float("nan")
-        if isinstance(v, (bool, str, bytes)) or not ok(f):
-            raise ValueError(f"{name} must be a number {rule}, got {v!r}")
-        out.append(f)
-    return out[0], out[1]
-
-
-HIST_FRAMES = 64        # SMP_HIST of csrc/generate.hip: the frames a row's ring of sampled codes holds, per codebook
-
-
-def check_processors(repetition_penalty, repetition_window):
-    """The rule for one row's repetition penalty: ``repetition_penalty`` a finite number with 0 < r <= 100 (1: off; above 1 a
-    code of the window becomes less likely, below 1 more), ``repetition_window`` an integer in 0..64 (the most recent frames
-    looked at; 0: off).  Returns (float, int); raises ValueError with the offending value."""
-    try:
-        r = float(repetition_penalty)
-    except (TypeError, ValueError):
-        r = float("nan")
-    if isinstance(repetition_penalty, (bool, str, bytes)) or not (math.isfinite(r) and 0.0 < r <= 100.0):
-        raise ValueError(f"repetition_penalty must be a finite number with 0 < r <= 100, got {repetition_penalty!r}")
-    try:
-        w = int(repetition_window)
-        whole = not isinstance(repetition_window, (bool, str, bytes)) and w == repetition_window
-    except (TypeError, ValueError, OverflowError):
-        w, whole = 0, False
-    if not whole or not 0 <= w <= HIST_FRAMES:
-        raise ValueError(f"repetition_window must be an integer in 0..{HIST_FRAMES} (frames), got {repetition_window!r}")
-    return r, w
-
-
-PROCESSOR_NAMES = ("temperature", "topk", "top_p", "min_p", "repetition_penalty", "repetition_window")
-
-
-def per_codebook(name, value, K):
-    """``value`` - a number (every codebook) or a sequence of K numbers (one per codebook) - as a list of K entries."""
-    if _is_number(value):
-        return [value] * K
-    vs = _as_list(value)
-    if vs is None or len(vs) != K or not all(_is_number(v) for v in vs):
-        raise ValueError(f"{name} is a number or a sequence of one number per codebook ({K} codebooks), got {value!r}")
-    return vs
-
-
-def check_row_processors(K, vocab, temperature, topk, top_p, min_p, repetition_penalty, repetition_window):
-    """One row's six sampling parameters, each a number or K numbers, held to ``check_sampling`` / ``check_filters`` /
-    ``check_processors`` codebook by codebook.  Returns six tuples of K values (floats; ints for topk and the window)."""
-    cols = [per_codebook(n, v, K) for n, v in zip(PROCESSOR_NAMES, (temperature, topk, top_p, min_p, repetition_penalty,
-                                                                     repetition_window))]
-    out = [[] for _ in cols]
-    for i in range(K):
-        vals = (check_sampling(cols[0][i], cols[1][i], vocab) + check_filters(cols[2][i], cols[3][i])
-                + check_processors(cols[4][i], cols[5][i]))
-        for o, v in zip(out, vals):
-            o.append(v)
-    return tuple(tuple(o) for o in out)
-
-
-def names_processors(*values, repetition_penalty=None, repetition_window=None):
-    """Whether a call names what only the processed sampler has: a penalty, a window, or a per-codebook sequence among
-    ``values`` (each a number, None, a flat sequence of numbers - per row, today's meaning - or a sequence holding sequences)."""
-    if repetition_penalty is not None or repetition_window is not None:
-        return True
-    for v in values:
-        vs = _as_list(v)
-        if vs is not None and any(_as_list(x) is not None for x in vs):
-            return True
-    return False
-
-
 class DecodeState:
     """Everything ``generate_frame`` keeps between calls: the two stacks' caches and small persistent buffers."""
 
@@ -1465,14 +1334,8 @@ class DecodeState:
         self.active = None
         self.row_gen, self.draw_rows, self.noise_stage = {}, None, None
         self.graph, self.graph_key, self.warm = None, None, 0
-        # per-row sampling parameters (set_row_sampling): two device vectors the rows sampler reads + their host mirror
-        self.row_temperature, self.row_topk, self.row_sampling = None, None, None
-        # ... and per-row filters (set_row_filters): top-p / min-p vectors for the filtered rows sampler + their host mirror
-        self.row_top_p, self.row_min_p, self.row_filters = None, None, None
-        # ... and per-row, per-codebook processors (set_row_processors): six [K, B] buffers + each row's ring of sampled codes, its
-        # frame counter and the live flags for the processed rows sampler + the host mirrors
-        self.proc, self.row_processors = None, None
-        self.code_hist, self.hist_frame, self.hist_live, self.live_rows = None, None, None, None
+        # per-row sampling parameters (set_row_sampling / set_row_filters / set_row_processors): one state with a level
+        self.sampler = RowSampler(B, m.args.audio_num_codebooks, m.args.audio_vocab_size, dev)
         # the frame's Exp(1) draws [K, B, V]: a PERSISTENT buffer, refilled before every frame outside the captured graph -
         # so a replayed frame can be given the same noise as an eager one (parity tests) or fresh draws (generation)
         self.noise_buf = torch.empty(m.args.audio_num_codebooks, B, m.args.audio_vocab_size, dtype=F32, device=dev)
@@ -1721,165 +1584,41 @@ class DecodeState:
             if stack.lora_rows is not None:
                 stack.lora_rows[0][b:b + 1].fill_(idx)
 
+    # ---- per-row sampling: thin names over ``self.sampler`` (csm/sampling.py: the levels, the buffers, the one writer) ----------
     def set_row_sampling(self, b, temperature, topk):
         """Row ``b`` samples with ``temperature`` / ``topk`` from its next frame on, in every frame body called with
-        ``temperature=None, topk=None``: one float and one int written to ``row_temperature[b]`` / ``row_topk[b]`` on the device,
-        which the rows sampler reads (``csm_sample_topk_rows``) - outside the captured graph, so a change never recaptures.  The
-        two buffers are made by the first call, with every row at that call's values (a row that is never set still samples
-        with a valid pair: the kernel runs on all B rows).  ``row_sampling`` is the host mirror, [(temperature, topk)] * B."""
-        temperature, topk = check_sampling(temperature, topk, self.e.m.args.audio_vocab_size)
-        b = int(b)
-        if not 0 <= b < self.B:
-            raise ValueError(f"row {b} out of range (the state has {self.B})")
-        if self.row_sampling is None:
-            dev = self.noise_buf.device
-            self.row_temperature = torch.full((self.B,), temperature, dtype=F32, device=dev)
-            self.row_topk = torch.full((self.B,), topk, dtype=torch.int32, device=dev)
-            self.row_sampling = [(temperature, topk)] * self.B
-        elif self.row_sampling[b] != (temperature, topk):
-            self.row_temperature[b:b + 1].fill_(temperature)
-            self.row_topk[b:b + 1].fill_(topk)
-            self.row_sampling[b] = (temperature, topk)
-
-    def row_sampling_buffers(self):
-        """(row_temperature, row_topk) for a frame body called with None, None."""
-        if self.row_sampling is None:
-            raise RuntimeError("temperature = topk = None samples each row with its own pair: call set_row_sampling first")
-        return self.row_temperature, self.row_topk
+        ``temperature=None, topk=None`` (level 1: the rows sampler).  The first call gives its pair to every row."""
+        self.sampler.write(b, 1, temperature, topk)
 
     def set_row_filters(self, b, top_p, min_p):
-        """Row ``b`` samples with the nucleus ``top_p`` and the min-p threshold ``min_p`` from its next frame on, in every frame
-        body called with ``temperature=None, topk=None``: two floats written to ``row_top_p[b]`` / ``row_min_p[b]`` on the device,
-        which the filtered rows sampler reads (``csm_sample_filtered_rows``) - outside the captured graph, so a change never
-        recaptures.  The two buffers are made by the first call, with every row at that call's values; once they exist the frame
-        bodies draw through the filtered sampler (make them before the first capture).  ``row_filters`` is the host mirror,
-        [(top_p, min_p)] * B."""
-        top_p, min_p = check_filters(top_p, min_p)
-        b = int(b)
-        if not 0 <= b < self.B:
-            raise ValueError(f"row {b} out of range (the state has {self.B})")
-        if self.row_filters is None:
-            dev = self.noise_buf.device
-            self.row_top_p = torch.full((self.B,), top_p, dtype=F32, device=dev)
-            self.row_min_p = torch.full((self.B,), min_p, dtype=F32, device=dev)
-            self.row_filters = [(top_p, min_p)] * self.B
-        elif self.row_filters[b] != (top_p, min_p):
-            self.row_top_p[b:b + 1].fill_(top_p)
-            self.row_min_p[b:b + 1].fill_(min_p)
-            self.row_filters[b] = (top_p, min_p)
-
-    def row_filter_buffers(self):
-        """(row_top_p, row_min_p) for a frame body called with None, None."""
-        if self.row_filters is None:
-            raise RuntimeError("no row filters: call set_row_filters first")
-        return self.row_top_p, self.row_min_p
+        """... and with the nucleus ``top_p`` and the min-p threshold ``min_p`` (level 2: the filtered rows sampler; after
+        ``set_row_sampling``).  The call that raises the level gives its two to every row: make it before the first capture."""
+        self.sampler.write(b, 2, top_p, min_p)
 
     def set_row_processors(self, b, temperature, topk, top_p, min_p, repetition_penalty, repetition_window):
-        """Row ``b`` samples with these six parameters from its next frame on, each a number (every codebook) or K numbers (one per
-        codebook), in every frame body called with ``temperature=None, topk=None``.  They sit in six device buffers of shape
-        [K, B] (``proc``, codebook-major: codebook i's draw reads row i of each), column b written here - outside the captured
-        graph, so a change never recaptures - with one small copy per buffer that changed.  The first call makes the buffers, with
-        every row at that call's values, and the history the processed rows sampler (``csm_sample_processed_rows``) keeps:
-        ``code_hist`` int32 [B, K, 64] (slot f % 64 of [b, i]: the code row b drew for codebook i in frame f of its utterance),
-        ``hist_frame`` int32 [B] (f; ``reset_row_history``) and ``hist_live`` int32 [B] (the rows that write their ring and
-        count the frame).  Once they exist the frame bodies draw through that sampler (make them before the first capture).
-        ``row_processors`` is the host mirror: per row, six tuples of K values."""
-        a = self.e.m.args
-        K = a.audio_num_codebooks
-        vals = check_row_processors(K, a.audio_vocab_size, temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
-        b = int(b)
-        if not 0 <= b < self.B:
-            raise ValueError(f"row {b} out of range (the state has {self.B})")
-        dtypes = (F32, torch.int32, F32, F32, F32, torch.int32)
-        if self.row_processors is None:
-            dev = self.noise_buf.device
-            self.proc = tuple(torch.tensor(v, dtype=dt).view(K, 1).repeat(1, self.B).to(dev) for v, dt in zip(vals, dtypes))
-            self.code_hist = torch.zeros(self.B, K, HIST_FRAMES, dtype=torch.int32, device=dev)
-            self.hist_frame = torch.zeros(self.B, dtype=torch.int32, device=dev)
-            self.hist_live = torch.ones(self.B, dtype=torch.int32, device=dev)
-            self.live_rows = list(range(self.B))
-            self.row_processors = [vals] * self.B
-        elif self.row_processors[b] != vals:
-            for buf, new, old, dt in zip(self.proc, vals, self.row_processors[b], dtypes):
-                if new != old:
-                    buf[:, b].copy_(torch.tensor(new, dtype=dt))
-            self.row_processors[b] = vals
+        """... with these six, each a number (every codebook) or K numbers (one per codebook) (level 3: the processed rows
+        sampler, which keeps the rows' rings of sampled codes).  The call that raises the level gives its six to every row."""
+        self.sampler.write(b, 3, temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
 
     def reset_row_history(self, b):
         """Row ``b`` starts an utterance: its frame counter returns to 0.  The ring is left as it is - the sampler looks at
         min(window, frame) entries, so what an earlier utterance left there is never read."""
-        if self.row_processors is None:
-            raise RuntimeError("no row processors: call set_row_processors first")
-        self.hist_frame[int(b):int(b) + 1].zero_()
+        self.sampler.reset_history(b)
 
     def set_live(self, rows):
         """The rows whose draws count in the next frame tail (the processed sampler writes their ring and advances their frame);
-        the others' rings and counters stay as they are, whatever their rows of the batch hold.  Nothing without processors."""
-        if self.row_processors is None:
-            return
-        rows = sorted(int(b) for b in rows)
-        if rows != self.live_rows:
-            self.hist_live.copy_(torch.tensor([1 if b in rows else 0 for b in range(self.B)], dtype=torch.int32))
-            self.live_rows = rows
+        the others' rings and counters stay as they are, whatever their rows of the batch hold.  Nothing below level 3."""
+        self.sampler.set_live(rows)
 
     def sampling_args(self, temperature, topk, top_p=None, min_p=None, repetition_penalty=None, repetition_window=None):
-        """What ``Engine.generate_frame`` / ``generate_first_frames`` hand to the frame bodies: two numbers (or None, None) pass
-        through; a sequence of B values for either one is written to the rows (``set_row_sampling``; the other, if a number,
-        holds for every row) and (None, None) comes back.  ``top_p`` / ``min_p`` (None: not named - nothing changes): numbers or
-        one value per row, written to the rows' filters (``set_row_filters``) - they live in the rows path, so the pair goes to
-        the rows too and (None, None) comes back.  ``repetition_penalty`` / ``repetition_window`` (None: not named), or an entry
-        per row that is itself a sequence of K numbers (one per codebook) in any of the six: all six go to the rows' processors
-        (``set_row_processors``; a number holds for every row and codebook, an entry per row is a number or K numbers) and
-        (None, None) comes back."""
-        plain = (temperature is None and topk is None) or (_is_number(temperature) and _is_number(topk))
-        if names_processors(temperature, topk, top_p, min_p, repetition_penalty=repetition_penalty,
-                            repetition_window=repetition_window) or (
-                self.row_processors is not None and not (plain and top_p is None and min_p is None)):
-            # (a state that has processors draws every rows frame through them: rows' pairs and filters go there too)
-            if temperature is None or topk is None:
-                raise ValueError("per-codebook parameters and the repetition penalty need temperature and topk named")
-            six = (temperature, topk, 1.0 if top_p is None else top_p, 0.0 if min_p is None else min_p,
-                   1.0 if repetition_penalty is None else repetition_penalty,
-                   HIST_FRAMES if repetition_window is None else repetition_window)
-            rows = []
-            for name, v in zip(PROCESSOR_NAMES, six):
-                vs = [v] * self.B if _is_number(v) else _as_list(v)
-                if vs is None or len(vs) != self.B:
-                    raise ValueError(f"{name} is a number or a sequence of one entry per row ({self.B} rows; an entry is a number "
-                                     f"or one number per codebook), got {v!r}")
-                rows.append(vs)
-            a = self.e.m.args
-            for b in range(self.B):                        # (all of them before any is written)
-                check_row_processors(a.audio_num_codebooks, a.audio_vocab_size, *[vs[b] for vs in rows])
-            for b in range(self.B):
-                self.set_row_processors(b, *[vs[b] for vs in rows])
-            return None, None
-        if top_p is not None or min_p is not None:
-            ps = [1.0 if top_p is None else top_p] * self.B if top_p is None or _is_number(top_p) else _as_list(top_p)
-            ms = [0.0 if min_p is None else min_p] * self.B if min_p is None or _is_number(min_p) else _as_list(min_p)
-            if ps is None or ms is None or len(ps) != self.B or len(ms) != self.B:
-                raise ValueError(f"top_p and min_p are numbers or sequences of one value per row ({self.B} rows): got "
-                                 f"top_p={top_p!r}, min_p={min_p!r}")
-            for p_, m_ in zip(ps, ms):                     # (all of them before any is written)
-                check_filters(p_, m_)
-            if _is_number(temperature) and _is_number(topk):
-                temperature, topk = [temperature] * self.B, [topk] * self.B
-            temperature, topk = self.sampling_args(temperature, topk)
-            for b, (p_, m_) in enumerate(zip(ps, ms)):
-                self.set_row_filters(b, p_, m_)
-            return temperature, topk
-        if (temperature is None and topk is None) or (_is_number(temperature) and _is_number(topk)):
-            return temperature, topk
-        ts = [temperature] * self.B if _is_number(temperature) else _as_list(temperature)
-        ks = [topk] * self.B if _is_number(topk) else _as_list(topk)
-        if ts is None or ks is None or len(ts) != self.B or len(ks) != self.B:
-            raise ValueError(f"temperature and topk are numbers or sequences of one value per row ({self.B} rows): got "
-                             f"temperature={temperature!r}, topk={topk!r}")
-        for t, k in zip(ts, ks):                       # (all of them before any is written)
-            check_sampling(t, k, self.e.m.args.audio_vocab_size)
-        for b, (t, k) in enumerate(zip(ts, ks)):
-            self.set_row_sampling(b, t, k)
-        return None, None
+        """What ``Engine.generate_frame`` / ``generate_first_frames`` hand to the frame bodies: two numbers (or None, None) with
+        nothing else named pass through; anything else (``sampling.normalise``: a value per row, ``top_p`` / ``min_p``, a penalty,
+        a window, values per codebook) is written to the rows at the level it needs and (None, None) comes back."""
+        return self.sampler.args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+
+    row_sampling = property(lambda self: self.sampler.row_sampling, doc="[(temperature, topk)] * B at levels 1 and 2, else None")
+    row_filters = property(lambda self: self.sampler.row_filters, doc="[(top_p, min_p)] * B at level 2, else None")
+    row_processors = property(lambda self: self.sampler.row_processors, doc="six K-tuples per row at level 3, else None")
 
     def set_row_seed(self, b, seed, generator=None):
         """Row ``b``'s sampler noise comes from its own ``torch.Generator`` seeded with ``seed`` (``fill_noise``); None returns
@@ -1958,11 +1697,7 @@ class DecodeState:
         of any row's top-p / min-p replays it too; with row processors (``set_row_processors``) it is (None, None, "processors")."""
         m = self.e.m
         self._advance()
-        key = (None, None) if temperature is None and topk is None else (float(temperature), int(topk))
-        if key == (None, None) and self.row_filters is not None:
-            key = (None, None, "filters")                # (the frame draws through the filtered rows sampler: another graph)
-        if key[:2] == (None, None) and self.row_processors is not None:
-            key = (None, None, "processors")             # (... through the processed rows sampler)
+        key = self.sampler.graph_key(temperature, topk)
         if self.graph is None or self.graph_key != key:
             if self.warm < 1 or self.graph_key not in (None, key):
                 self.warm, self.graph, self.graph_key = 1, None, None

@@ -15,6 +15,7 @@ from typing import Iterator, List, Optional, Tuple
 import torch
 
 from .models.model import Model, ModelArgs
+from .sampling import PROCESSOR_NAMES, _as_list, _is_number, check_filters, names_processors, normalise, per_codebook
 
 
 @dataclass
@@ -41,57 +42,42 @@ def load_llama3_tokenizer(path: str = "meta-llama/Llama-3.2-1B"):
     return tokenizer
 
 
+def _untouched(v):
+    """A value as the frame calls take it: a number as it is, a sequence as a list."""
+    return v if _is_number(v) else _as_list(v)
+
+
 def filter_kwargs(top_p, min_p, B=None):
     """The ``top_p`` / ``min_p`` keywords of a frame call: {} at the defaults (1.0 / 0.0 - the call is then today's, untouched),
     else both, held to ``check_filters`` here (before any cache is taken over).  ``B``: either one may be a sequence of B values."""
-    from .engine import _as_list, _is_number, check_filters
     if _is_number(top_p) and _is_number(min_p):
         top_p, min_p = check_filters(top_p, min_p)
         return {} if (top_p, min_p) == (1.0, 0.0) else {"top_p": top_p, "min_p": min_p}
-    out = {}
-    for name, v in (("top_p", top_p), ("min_p", min_p)):
-        if not _is_number(v):
-            seq = None if B is None else _as_list(v)
-            if seq is None or len(seq) != B:
-                raise ValueError(f"{name} is a number" + (f" or a sequence of one value per utterance ({B})" if B else "") +
-                                 f", got {v!r}")
-            v = seq
-        out[name] = v
-    for b in range(B):
-        check_filters(*[v if _is_number(v) else v[b] for v in (out["top_p"], out["min_p"])])
-    return out
+    if B is None:
+        raise ValueError(f"top_p and min_p are numbers, got top_p={top_p!r}, min_p={min_p!r}")
+    normalise(B, 1, 1, None, None, top_p, min_p, unit="utterance")
+    return {"top_p": _untouched(top_p), "min_p": _untouched(min_p)}
 
 
 def sampling_kwargs(gen, temperature, topk, top_p, min_p, repetition_penalty=1.0, repetition_window=64, B=None):
     """(temperature, topk, keywords) of the frame calls of a generation on the Generator ``gen``.  Nothing new named -
     ``repetition_penalty`` 1.0, ``repetition_window`` 64 and no per-codebook sequence: what the call has always made of them (``filter_kwargs``;
     ``Generator._batch_sampling`` with ``B``), untouched.  Otherwise every one of the six goes to the rows' processors
-    (``DecodeState.sampling_args``): one entry per row, each a number or K numbers (one per codebook), checked here, before
-    any cache is taken over.  Without ``B`` (one utterance) a value is a number or K numbers; with ``B`` a number or a sequence
-    of B entries, each a number or K numbers - a flat sequence of B numbers keeps its meaning, one value per utterance."""
-    from .engine import PROCESSOR_NAMES, _as_list, _is_number, check_row_processors
-    six = (temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+    (``DecodeState.sampling_args``): one entry per row, each a number or K numbers (one per codebook), checked here
+    (``sampling.normalise``, the check the state makes), before any cache is taken over.  Without ``B`` (one utterance) a value is
+    a number or K numbers - the one entry of a batch of one; with ``B`` a number or a sequence of B entries, each a number or K
+    numbers - a flat sequence of B numbers keeps its meaning, one value per utterance."""
+    six = [temperature, topk, top_p, min_p, repetition_penalty, repetition_window]
     if B is None:
-        new = not all(_is_number(v) for v in six)
-    else:
-        new = not all(_is_number(v) for v in six[4:]) or any(
-            _as_list(v) is not None and any(_as_list(x) is not None for x in _as_list(v)) for v in six[:4])
-    new = new or not (repetition_penalty == 1.0 and repetition_window == 64)
-    if not new:
+        six = [v if _is_number(v) else [per_codebook(name, v, gen._model.args.audio_num_codebooks)]
+               for name, v in zip(PROCESSOR_NAMES, six)]
+    if not names_processors(*six[:4]) and all(_is_number(v) for v in six[4:]) and six[4] == 1.0 and six[5] == 64:
         if B is not None:
             temperature, topk = gen._batch_sampling(temperature, topk, B)
         return temperature, topk, filter_kwargs(top_p, min_p, B)
-    n = 1 if B is None else B
-    rows = []
-    for name, v in zip(PROCESSOR_NAMES, six):
-        vs = [v] * n if _is_number(v) or B is None else _as_list(v)
-        if vs is None or len(vs) != n:
-            raise ValueError(f"{name} is a number or a sequence of one entry per utterance ({n}; an entry is a number or one "
-                             f"number per codebook), got {v!r}")
-        rows.append(vs)
-    a = gen._model.args
-    for b in range(n):
-        check_row_processors(a.audio_num_codebooks, a.audio_vocab_size, *[vs[b] for vs in rows])
+    a, n = gen._model.args, 1 if B is None else B
+    normalise(n, a.audio_num_codebooks, a.audio_vocab_size, *six, unit="utterance")
+    rows = [[v] * n if _is_number(v) else _as_list(v) for v in six]
     return rows[0], rows[1], dict(zip(PROCESSOR_NAMES[2:], rows[2:]))
 
 
@@ -394,21 +380,9 @@ class Generator:
     def _batch_sampling(self, temperature, topk, B):
         """``generate_batch``'s temperature / topk: numbers pass through; a sequence must have one valid value per utterance
         (checked here, before the caches are taken over) and comes back as a list."""
-        from .engine import _as_list, _is_number, check_sampling
-        if _is_number(temperature) and _is_number(topk):
-            return temperature, topk
-        out = []
-        for name, v in (("temperature", temperature), ("topk", topk)):
-            if not _is_number(v):
-                seq = _as_list(v)
-                if seq is None or len(seq) != B:
-                    raise ValueError(f"generate_batch: {name} is a number or a sequence of one value per utterance ({B}), got {v!r}")
-                v = seq
-            out.append(v)
-        vocab = self._model.args.audio_vocab_size
-        for b in range(B):
-            check_sampling(out[0] if _is_number(out[0]) else out[0][b], out[1] if _is_number(out[1]) else out[1][b], vocab)
-        return out[0], out[1]
+        if not (_is_number(temperature) and _is_number(topk)):
+            normalise(B, 1, self._model.args.audio_vocab_size, temperature, topk, unit="utterance")
+        return _untouched(temperature), _untouched(topk)
 
     def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
               row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,

@@ -104,38 +104,38 @@ def llama3_rope_table(max_seq_len: int, head_dim: int, base: float, scale: float
     return torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1).contiguous()
 
 
-def sample_topk(logits: torch.Tensor, topk: int, temperature: float, q: Optional[torch.Tensor] = None):
-    """Reference ``sample_topk`` (model.py:85-96) on the GPU: returns int32 [..., 1].
-
-    The Exp(1) draw of ``_multinomial_sample_one_no_sync`` comes from torch's generator (or ``q`` when given, which is
-    how parity tests pin the result); threshold / softmax / argmax run in one HIP kernel.
-    """
+def _sample_operands(logits, q, rows_form=None):
+    """What the four samplers hand to their kernel: the logits as fp32 [rows, V] with unit column stride, the Exp(1) draws
+    (``q``, or fresh ones from torch's generator) shaped like them and the int32 [rows] output.  ``rows_form``: the name of a
+    sampler that takes [B, V] logits only."""
     lg = logits.float()
-    lead = lg.shape[:-1]
+    if rows_form is not None and lg.dim() != 2:
+        raise ValueError(f"{rows_form} takes [B, V] logits, got {tuple(logits.shape)}")
     lg2 = lg.reshape(-1, lg.shape[-1])
     if lg2.stride(1) != 1:
         lg2 = lg2.contiguous()
     if q is None:
         q = torch.empty(lg2.shape, dtype=torch.float32, device=lg2.device).exponential_(1)
     q = q.reshape(lg2.shape).float().contiguous()
-    out = torch.empty(lg2.shape[0], dtype=torch.int32, device=lg2.device)
+    return lg2, q, torch.empty(lg2.shape[0], dtype=torch.int32, device=lg2.device)
+
+
+def sample_topk(logits: torch.Tensor, topk: int, temperature: float, q: Optional[torch.Tensor] = None):
+    """Reference ``sample_topk`` (model.py:85-96) on the GPU: returns int32 [..., 1].
+
+    The Exp(1) draw of ``_multinomial_sample_one_no_sync`` comes from torch's generator (or ``q`` when given, which is
+    how parity tests pin the result); threshold / softmax / argmax run in one HIP kernel.
+    """
+    lg2, q, out = _sample_operands(logits, q)
     ops.sample_topk(lg2, q, out, topk, temperature, V=lg2.shape[1])
-    return out.reshape(*lead, 1)
+    return out.reshape(*logits.shape[:-1], 1)
 
 
 def sample_topk_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, q: Optional[torch.Tensor] = None):
     """``sample_topk`` for [B, V] logits with one parameter pair per row: ``topk`` int32 [B] and ``temperature`` float32 [B] on the
     logits' device, read by the kernel (``csm_sample_topk_rows``) - row b is ``sample_topk(logits[b], topk[b], temperature[b],
     q[b])`` bit for bit.  Returns int32 [B, 1]."""
-    lg2 = logits.float()
-    if lg2.dim() != 2:
-        raise ValueError(f"sample_topk_rows takes [B, V] logits, got {tuple(logits.shape)}")
-    if lg2.stride(1) != 1:
-        lg2 = lg2.contiguous()
-    if q is None:
-        q = torch.empty(lg2.shape, dtype=torch.float32, device=lg2.device).exponential_(1)
-    q = q.reshape(lg2.shape).float().contiguous()
-    out = torch.empty(lg2.shape[0], dtype=torch.int32, device=lg2.device)
+    lg2, q, out = _sample_operands(logits, q, "sample_topk_rows")
     ops.sample_topk_rows(lg2, q, out, topk, temperature, V=lg2.shape[1])
     return out.reshape(-1, 1)
 
@@ -146,15 +146,7 @@ def sample_filtered_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: 
     [0, 1]) per row, applied inside the kernel (``csm_sample_filtered_rows``) to the values top-k kept: first min-p (drop
     p_i < min_p * p_max), then the nucleus over what is left (a token stays while the probability of the strictly larger values
     is below top_p).  Row b with 1.0 / 0.0 is ``sample_topk_rows``' row b, bit for bit.  Returns int32 [B, 1]."""
-    lg2 = logits.float()
-    if lg2.dim() != 2:
-        raise ValueError(f"sample_filtered_rows takes [B, V] logits, got {tuple(logits.shape)}")
-    if lg2.stride(1) != 1:
-        lg2 = lg2.contiguous()
-    if q is None:
-        q = torch.empty(lg2.shape, dtype=torch.float32, device=lg2.device).exponential_(1)
-    q = q.reshape(lg2.shape).float().contiguous()
-    out = torch.empty(lg2.shape[0], dtype=torch.int32, device=lg2.device)
+    lg2, q, out = _sample_operands(logits, q, "sample_filtered_rows")
     ops.sample_filtered_rows(lg2, q, out, topk, temperature, top_p, min_p, V=lg2.shape[1])
     return out.reshape(-1, 1)
 
@@ -168,15 +160,7 @@ def sample_processed_rows(logits: torch.Tensor, topk: torch.Tensor, temperature:
     the last n = min(window, f, 64) frames get x = x / r (x > 0) or x * r on the raw logit, then the draw is
     ``sample_filtered_rows``'; row b with r = 1 or n = 0 is that row bit for bit.  A row with ``live[b]`` != 0 then stores its
     winner to slot f % 64 and, with ``advance``, f + 1 to ``frame[b]``.  Returns int32 [B, 1]."""
-    lg2 = logits.float()
-    if lg2.dim() != 2:
-        raise ValueError(f"sample_processed_rows takes [B, V] logits, got {tuple(logits.shape)}")
-    if lg2.stride(1) != 1:
-        lg2 = lg2.contiguous()
-    if q is None:
-        q = torch.empty(lg2.shape, dtype=torch.float32, device=lg2.device).exponential_(1)
-    q = q.reshape(lg2.shape).float().contiguous()
-    out = torch.empty(lg2.shape[0], dtype=torch.int32, device=lg2.device)
+    lg2, q, out = _sample_operands(logits, q, "sample_processed_rows")
     ops.sample_processed_rows(lg2, q, out, topk, temperature, top_p, min_p, penalty, window, hist, frame, live, advance=advance,
                               V=lg2.shape[1])
     return out.reshape(-1, 1)

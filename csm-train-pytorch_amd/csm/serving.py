@@ -20,13 +20,13 @@ Sampling parameters.  By default temperature and top-k belong to the server: the
 key of the captured frame graph.  With ``serve(row_sampling=True)`` they belong to the request: ``submit`` / ``conversation`` /
 ``say`` take ``temperature`` and ``topk`` (say > conversation > server's), the slot gets them at admission
 (``DecodeState.set_row_sampling``: two small device writes outside the graph) and every draw of every frame goes through the rows
-sampler (``csm_sample_topk_rows``), which reads ``row_topk[b]`` / ``row_temperature[b]`` from device memory.  One captured frame
+sampler (``csm_sample_topk_rows``), which reads ``topk[b]`` / ``temperature[b]`` from device memory.  One captured frame
 then serves every mix of parameters - a greedy row (``topk=1``) next to a 0.9 / 50 one - and a change never recaptures.  A row's
 codes are those of a default server made with that row's pair (the same bits).  A free row keeps the pair of its last request.
 
 Filters.  ``serve(row_sampling=True, row_filters=True, top_p=1.0, min_p=0.0)`` adds a nucleus (top-p) and a min-p cut per request,
 resolved and checked like the pair (``submit`` / ``conversation`` / ``say`` take ``top_p`` and ``min_p``; say > conversation >
-server's) and written at admission (``DecodeState.set_row_filters``).  The server makes the two filter buffers before its first
+server's) and written at admission (``DecodeState.set_row_filters``).  The server raises its state to that level before its first
 capture, so every draw goes through the filtered rows sampler (``csm_sample_filtered_rows``): min-p, then the nucleus, inside the
 sampler's one launch, on what top-k kept.  A row at (1.0, 0.0) skips both and has the codes of a ``row_sampling`` server; a change
 of any row's four parameters replays the same captured frame.  Without ``row_filters`` nothing here is touched.
@@ -85,7 +85,8 @@ from typing import Iterator, List, Optional, Tuple
 import torch
 
 from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, hear_resampler, open_heard_turn
-from .engine import HIST_FRAMES, DecodeState, _as_list, check_filters, check_row_processors, check_sampling
+from .engine import DecodeState
+from .sampling import HIST_FRAMES, _as_list, check_filters, check_row_processors, check_sampling
 
 
 def _collapsed(six):

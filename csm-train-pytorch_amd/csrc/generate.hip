@@ -109,14 +109,10 @@ struct SampleRows {
 //    no threshold keeps.  The set is then counted again and takes whichever finish fits it.
 // Error: |kernel's sum P_j - exact| <= 2 (V 2^-40 + (2 + dbar) 2^-24), dbar the P-weighted mean of
 // max v - v_j; |kernel's e_i / exact - 1| <= (2 + max v - v_i) 2^-24.
-struct SampleFiltered {
+struct SampleFiltered : SampleRows {
     static constexpr bool FILTERS = true, PENALTY = false;
-    const int* topk;
-    const float* temperature;
     const float* top_p;
     const float* min_p;
-    __device__ __forceinline__ int k(int row, int V) const { const int v = topk[row]; return v < 1 ? 1 : (v > V ? V : v); }
-    __device__ __forceinline__ float t(int row) const { const float v = temperature[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
     __device__ __forceinline__ float p(int row) const { const float v = top_p[row]; return (v > 0.f && v <= 1.f) ? v : 1.f; }
     __device__ __forceinline__ float m(int row) const { const float v = min_p[row]; return (v >= 0.f && v <= 1.f) ? v : 0.f; }
 };
@@ -136,12 +132,8 @@ struct SampleFiltered {
 // oldest entry read) and, with `advance`, f + 1 to frame[row] - plain vector stores by the thread that writes `out`.  Only this
 // row's block touches the row's ring and counter.
 constexpr int SMP_HIST = 64;
-struct SampleProcessed {
+struct SampleProcessed : SampleFiltered {
     static constexpr bool FILTERS = true, PENALTY = true;
-    const int* topk;
-    const float* temperature;
-    const float* top_p;
-    const float* min_p;
     const float* penalty;
     const int* window;
     int* hist;
@@ -149,10 +141,6 @@ struct SampleProcessed {
     int* frame;
     const int* live;
     int advance;
-    __device__ __forceinline__ int k(int row, int V) const { const int v = topk[row]; return v < 1 ? 1 : (v > V ? V : v); }
-    __device__ __forceinline__ float t(int row) const { const float v = temperature[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
-    __device__ __forceinline__ float p(int row) const { const float v = top_p[row]; return (v > 0.f && v <= 1.f) ? v : 1.f; }
-    __device__ __forceinline__ float m(int row) const { const float v = min_p[row]; return (v >= 0.f && v <= 1.f) ? v : 0.f; }
     __device__ __forceinline__ float r(int row) const { const float v = penalty[row]; return (v > 0.f && v < INFINITY) ? v : 1.f; }
     __device__ __forceinline__ int w(int row) const { const int v = window[row]; return v < 0 ? 0 : (v > SMP_HIST ? SMP_HIST : v); }
     __device__ __forceinline__ void wrote(int row, int f, int winner) const {   // (one thread, after the draw)
@@ -544,39 +532,36 @@ __global__ __launch_bounds__(256) void rvq_decode_kernel(const long long* __rest
 
 }  // namespace
 
+// The four samplers' launch: the kernel with 9 values per thread where the row fits, else SMP_PER_THREAD; one workgroup per row.
+template <class Params>
+static int sample_launch(const char* name, const float* logits, const float* q, int* out, int rows, int V, int ldl,
+                         hipStream_t stream, const Params& prm) {
+    CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "%s: V=%d exceeds %d", name, V, 256 * SMP_PER_THREAD);
+    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, Params>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, Params>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
+    CSM_CHECK_LAUNCH(name);
+    return 0;
+}
+
 extern "C" int csm_sample_topk(const float* logits, const float* q, int* out, int rows, int V, int ldl, int topk,
                                float temperature, hipStream_t stream) {
     CSM_REQUIRE(logits && q && out && rows > 0 && V > 0 && ldl >= V, "csm_sample_topk: bad arguments");
-    CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "csm_sample_topk: V=%d exceeds %d", V, 256 * SMP_PER_THREAD);
     CSM_REQUIRE(topk > 0 && topk <= V && temperature > 0.f, "csm_sample_topk: bad topk=%d / temperature=%f", topk, temperature);
-    const SampleScalars prm = {topk, temperature};
-    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleScalars>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
-    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleScalars>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
-    CSM_CHECK_LAUNCH("csm_sample_topk");
-    return 0;
+    return sample_launch("csm_sample_topk", logits, q, out, rows, V, ldl, stream, SampleScalars{topk, temperature});
 }
 
 extern "C" int csm_sample_topk_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
                                     const float* temperature, hipStream_t stream) {
     CSM_REQUIRE(logits && q && out && topk && temperature && rows > 0 && V > 0 && ldl >= V, "csm_sample_topk_rows: bad arguments");
-    CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "csm_sample_topk_rows: V=%d exceeds %d", V, 256 * SMP_PER_THREAD);
-    const SampleRows prm = {topk, temperature};
-    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleRows>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
-    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleRows>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
-    CSM_CHECK_LAUNCH("csm_sample_topk_rows");
-    return 0;
+    return sample_launch("csm_sample_topk_rows", logits, q, out, rows, V, ldl, stream, SampleRows{topk, temperature});
 }
 
 extern "C" int csm_sample_filtered_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
                                         const float* temperature, const float* top_p, const float* min_p, hipStream_t stream) {
     CSM_REQUIRE(logits && q && out && topk && temperature && top_p && min_p && rows > 0 && V > 0 && ldl >= V,
                 "csm_sample_filtered_rows: bad arguments");
-    CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "csm_sample_filtered_rows: V=%d exceeds %d", V, 256 * SMP_PER_THREAD);
-    const SampleFiltered prm = {topk, temperature, top_p, min_p};
-    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleFiltered>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
-    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleFiltered>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
-    CSM_CHECK_LAUNCH("csm_sample_filtered_rows");
-    return 0;
+    return sample_launch("csm_sample_filtered_rows", logits, q, out, rows, V, ldl, stream,
+                         SampleFiltered{topk, temperature, top_p, min_p});
 }
 
 extern "C" int csm_sample_processed_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
@@ -585,13 +570,9 @@ extern "C" int csm_sample_processed_rows(const float* logits, const float* q, in
                                          hipStream_t stream) {
     CSM_REQUIRE(logits && q && out && topk && temperature && top_p && min_p && penalty && window && hist && frame && live &&
                 rows > 0 && V > 0 && ldl >= V, "csm_sample_processed_rows: bad arguments");
-    CSM_REQUIRE(V <= 256 * SMP_PER_THREAD, "csm_sample_processed_rows: V=%d exceeds %d", V, 256 * SMP_PER_THREAD);
     CSM_REQUIRE(ldh >= SMP_HIST, "csm_sample_processed_rows: ldh=%d is below the ring's %d", ldh, SMP_HIST);
-    const SampleProcessed prm = {topk, temperature, top_p, min_p, penalty, window, hist, ldh, frame, live, advance};
-    if (V <= 256 * 9) hipLaunchKernelGGL((sample_topk_kernel<9, SampleProcessed>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
-    else hipLaunchKernelGGL((sample_topk_kernel<SMP_PER_THREAD, SampleProcessed>), dim3(rows), dim3(256), 0, stream, logits, q, out, V, ldl, prm);
-    CSM_CHECK_LAUNCH("csm_sample_processed_rows");
-    return 0;
+    return sample_launch("csm_sample_processed_rows", logits, q, out, rows, V, ldl, stream,
+                         SampleProcessed{topk, temperature, top_p, min_p, penalty, window, hist, ldh, frame, live, advance});
 }
 
 extern "C" int csm_rvq_encode(const float* x, const float* codebooks, long long* codes, int T, int K, int C, int D,

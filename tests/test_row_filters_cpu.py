@@ -65,7 +65,7 @@ def test_entry_point_declared_exported_and_wired():
     assert len(hip.lib.csm_sample_filtered_rows.argtypes) == 11
     assert hip.lib.csm_abi_version() == 3                                  # additive: the ABI number stays
     assert callable(ops.sample_filtered_rows) and callable(model.sample_filtered_rows)
-    assert callable(DecodeState.set_row_filters) and callable(DecodeState.row_filter_buffers)
+    assert callable(DecodeState.set_row_filters) and isinstance(DecodeState.row_filters, property)
 
 
 def test_check_filters_rule():

@@ -65,8 +65,9 @@ def test_four_parameters_follow_the_request(world, four):
     st = srv._state
     assert b.slot not in (None, 0) and len(srv.active) >= 8 and srv.queued > 0
     assert st.row_filters[b.slot] == (four[2], four[3]) and len(set(st.row_filters)) >= 5
-    assert torch.equal(st.row_top_p.cpu(), torch.tensor([p for p, _ in st.row_filters]))
-    assert torch.equal(st.row_min_p.cpu(), torch.tensor([m_ for _, m_ in st.row_filters]))
+    row_p, row_m = st.sampler.params[2:4]                                               # [K, B]: every codebook's row of the buffers
+    assert torch.equal(row_p.cpu(), torch.tensor([p for p, _ in st.row_filters]).expand(K, -1))
+    assert torch.equal(row_m.cpu(), torch.tensor([m_ for _, m_ in st.row_filters]).expand(K, -1))
     _finish(srv)
     assert b.done and all(o.done for o in others) and (b.temperature, b.topk, b.top_p, b.min_p) == four
     _same(b, a)
@@ -163,11 +164,12 @@ def test_a_change_of_parameters_replays_the_same_graph_and_bad_values_leave_the_
     from csm.engine import DecodeState
     s3 = DecodeState(m.engine, 3)
     with pytest.raises(RuntimeError, match="set_row_filters first"):
-        s3.row_filter_buffers()
+        s3.sampler.need(2)
     assert s3.sampling_args(0.8, 5, top_p=[0.9, 1.0, 0.5]) == (None, None)
     assert s3.row_filters == [(0.9, 0.0), (1.0, 0.0), (0.5, 0.0)] and s3.row_sampling == [(0.8, 5)] * 3
     s3.set_row_filters(1, 0.25, 0.5)
-    assert s3.row_top_p.tolist() == [pytest.approx(0.9), 0.25, 0.5] and s3.row_min_p.tolist() == [0.0, 0.5, 0.0]
+    row_p, row_m = s3.sampler.params[2:4]
+    assert row_p.tolist() == [[pytest.approx(0.9), 0.25, 0.5]] * K and row_m.tolist() == [[0.0, 0.5, 0.0]] * K
     with pytest.raises(ValueError, match="one value per row"):
         s3.sampling_args(0.8, 5, top_p=[0.9, 1.0])
     with pytest.raises(ValueError, match="top_p must be"):

@@ -24,7 +24,7 @@ def _probe(srv, ctx, **kw):
 
 
 def _mirrors_equal_buffers(st):
-    for j, buf in enumerate(st.proc):
+    for j, buf in enumerate(st.sampler.params):
         want = torch.tensor([st.row_processors[b][j] for b in range(st.B)], dtype=buf.dtype).t()
         assert buf.shape == (K, st.B) and torch.equal(buf.cpu(), want), j
 
@@ -47,7 +47,7 @@ def test_penalty_one_is_the_row_filters_server(world):
     assert srv_f._state.row_processors is None and srv_f._state.graph_key == (None, None, "filters")
     st = srv_p._state
     assert st.row_processors is not None and st.graph_key == (None, None, "processors")
-    assert st.code_hist.shape == (16, K, 64) and st.hist_frame.shape == (16,) and st.hist_live.shape == (16,)
+    assert st.sampler.code_hist.shape == (16, K, 64) and st.sampler.hist_frame.shape == (16,) and st.sampler.hist_live.shape == (16,)
     assert all(r.repetition_penalty == 1.0 and r.repetition_window == 64 for r in got)
     for a, b in zip(got, want):
         _same(a, b)
@@ -88,7 +88,7 @@ def test_a_request_has_its_codes_in_any_slot_among_any_neighbours(world):
     assert len(set(st.row_processors)) >= 5
     srv.step()                                                                          # ... and join while the probe is mid-utterance
     assert srv.queued < waiting and b.slot is not None and not b.done
-    assert int(st.hist_frame[b.slot]) == b._sampled                                     # (their first-frame tail did not count for it)
+    assert int(st.sampler.hist_frame[b.slot]) == b._sampled                                     # (their first-frame tail did not count for it)
     _mirrors_equal_buffers(st)
     _finish(srv)
     assert b.done and all(o.done for o in others)
@@ -106,14 +106,14 @@ def test_ring_holds_the_last_64_frames_and_a_new_request_never_sees_them(world):
     _finish(srv)
     codes = long.codes()
     assert long.done and codes.shape == (K, F) and long._sampled == F
-    assert int(st.hist_frame[0]) == F and st.hist_frame[1:].tolist() == [0, 0, 0]
-    ring = st.code_hist[0].cpu().long()                                                 # [K, 64]
+    assert int(st.sampler.hist_frame[0]) == F and st.sampler.hist_frame[1:].tolist() == [0, 0, 0]
+    ring = st.sampler.code_hist[0].cpu().long()                                                 # [K, 64]
     for f in range(F - 64, F):
         assert torch.equal(ring[:, f % 64], codes[:, f].cpu()), f
-    assert not bool(st.code_hist[1:].any())                                             # (idle rows wrote nothing)
+    assert not bool(st.sampler.code_hist[1:].any())                                             # (idle rows wrote nothing)
     second = _probe(srv, ctx, repetition_penalty=1.5, repetition_window=64)             # into slot 0, over the stale ring
     srv.step()
-    assert second.slot == 0 and int(st.hist_frame[0]) == second._sampled == 4
+    assert second.slot == 0 and int(st.sampler.hist_frame[0]) == second._sampled == 4
     _finish(srv)
     fresh_srv = gen.serve(slots=4, chunk_frames=4, **PROC)
     fresh = _probe(fresh_srv, ctx, repetition_penalty=1.5, repetition_window=64)
@@ -141,7 +141,7 @@ def test_a_conversation_turn_has_its_codes_in_any_slot_and_its_window_is_its_own
         t2 = conv.say("and the second", 1, max_audio_length_ms=9 * 80)
         srv.step()
         slot = t2.slot
-        assert int(srv._state.hist_frame[slot]) == t2._sampled == 4                     # the turn's own frames only
+        assert int(srv._state.sampler.hist_frame[slot]) == t2._sampled == 4                     # the turn's own frames only
         _finish(srv)
         assert t1.done and t2.done and all(b.done for b in blockers)
         return t1, t2, slot
@@ -225,7 +225,7 @@ def test_generate_batch_rows_are_their_one_utterance_runs(world):
     assert st.graph_key in (None, (None, None, "processors"))
     assert st.row_processors[0][0] == tuple(temp) and st.row_processors[0][4] == (1.4,) * K
     assert st.row_processors[1] == ((0.9,) * K, (50,) * K, (1.0,) * K, (0.0,) * K, (1.0,) * K, (64,) * K)
-    assert st.hist_frame.tolist() == [6, 6] and st.hist_live.tolist() == [1, 1]
+    assert st.sampler.hist_frame.tolist() == [6, 6] and st.sampler.hist_live.tolist() == [1, 1]
     noise(11)
     base = gen.generate_batch(texts, speakers, [[], []], max_audio_length_ms=6 * 80, temperature=[0.8, 0.9], topk=50)
     assert gen._model._decode_state.row_processors is None
@@ -250,12 +250,12 @@ def test_defaults_are_todays_generate_and_the_new_arguments_reach_every_entry_po
     want = run(gen.generate)
     got = run(gen.generate, repetition_penalty=1.0, repetition_window=64)
     st = gen._model._decode_state
-    assert st.row_processors is None and st.row_sampling is None and st.code_hist is None and torch.equal(got, want)
+    assert st.row_processors is None and st.row_sampling is None and st.sampler.code_hist is None and torch.equal(got, want)
     assert st.graph_key in (None, (0.8, 20))
     pen = run(gen.generate, repetition_penalty=3.0, repetition_window=48)
     st = gen._model._decode_state
-    assert st.row_processors[0][4:] == ((3.0,) * K, (48,) * K) and int(st.hist_frame[0]) == 12 and pen.numel() > 0
-    assert bool(st.code_hist[0, :, :12].any()) and not bool(st.code_hist[0, :, 12:].any())      # the ring took the twelve frames
+    assert st.row_processors[0][4:] == ((3.0,) * K, (48,) * K) and int(st.sampler.hist_frame[0]) == 12 and pen.numel() > 0
+    assert bool(st.sampler.code_hist[0, :, :12].any()) and not bool(st.sampler.code_hist[0, :, 12:].any())      # the ring took the twelve frames
     assert torch.equal(run(gen.generate_stream, repetition_penalty=3.0, repetition_window=48), pen)
     assert torch.equal(run(gen.generate_stream, repetition_penalty=1.0), want)
     torch.manual_seed(5)
@@ -268,7 +268,7 @@ def test_defaults_are_todays_generate_and_the_new_arguments_reach_every_entry_po
     assert conv._state.row_processors[0][4] == (3.0,) * K and c1.numel() > 0
     torch.manual_seed(6)
     conv.generate("and again", 1, max_audio_length_ms=5 * 80, temperature=0.8, topk=20, repetition_penalty=3.0, repetition_window=48)
-    assert int(conv._state.hist_frame[0]) == 5                               # the second turn counted from 0
+    assert int(conv._state.sampler.hist_frame[0]) == 5                               # the second turn counted from 0
     conv2 = gen.conversation(context=ctx)
     torch.manual_seed(5)
     c2 = conv2.generate("say it plainly", 1, max_audio_length_ms=12 * 80, temperature=0.8, topk=20)
@@ -326,12 +326,12 @@ def test_refusals(world):
         s3.reset_row_history(0)
     assert s3.sampling_args(0.8, 5) == (0.8, 5) and s3.row_processors is None
     assert s3.sampling_args(0.8, 5, repetition_penalty=[1.3, 1.0, 2.0]) == (None, None)
-    assert [p[4][0] for p in s3.row_processors] == [1.3, 1.0, 2.0] and s3.proc[4].shape == (K, 3)
+    assert [p[4][0] for p in s3.row_processors] == [1.3, 1.0, 2.0] and s3.sampler.params[4].shape == (K, 3)
     with pytest.raises(ValueError, match="one entry per row"):
         s3.sampling_args(0.8, 5, repetition_penalty=[1.3, 1.0])
     with pytest.raises(ValueError, match="repetition_window must be"):
         s3.sampling_args(0.8, 5, repetition_window=[1, 2, 65])
     assert [p[5][0] for p in s3.row_processors] == [64, 64, 64]             # (all checked before any is written)
     s3.set_row_processors(1, 0.8, 5, 1.0, 0.0, [1.0 + 0.01 * i for i in range(K)], 7)
-    assert s3.proc[4][:, 1].cpu().tolist() == pytest.approx([1.0 + 0.01 * i for i in range(K)])
-    assert s3.proc[4][:, 0].cpu().tolist() == pytest.approx([1.3] * K) and s3.proc[5][:, 1].tolist() == [7] * K
+    assert s3.sampler.params[4][:, 1].cpu().tolist() == pytest.approx([1.0 + 0.01 * i for i in range(K)])
+    assert s3.sampler.params[4][:, 0].cpu().tolist() == pytest.approx([1.3] * K) and s3.sampler.params[5][:, 1].tolist() == [7] * K

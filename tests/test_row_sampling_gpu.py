@@ -121,8 +121,9 @@ def test_parameters_follow_the_request(world, pair):
     srv.step()
     assert b.slot not in (None, 0) and srv.last_join_rows == 4 and len(srv.active) >= 8 and srv.queued > 0     # (it joined 12 others)
     assert srv._state.row_sampling[b.slot] == pair and len(set(srv._state.row_sampling)) >= 6
-    assert srv._state.row_topk.tolist() == [k for _, k in srv._state.row_sampling]
-    assert torch.equal(srv._state.row_temperature.cpu(), torch.tensor([t for t, _ in srv._state.row_sampling]))
+    row_t, row_k = srv._state.sampler.params[:2]                                        # [K, B]: every codebook's row of the buffers
+    assert row_k.tolist() == [[k for _, k in srv._state.row_sampling]] * K
+    assert torch.equal(row_t.cpu(), torch.tensor([t for t, _ in srv._state.row_sampling]).expand(K, -1))
     _finish(srv)
     assert b.done and all(o.done for o in others) and (b.temperature, b.topk) == pair
     _same(b, a)
@@ -198,7 +199,8 @@ def test_engine_frames_take_one_pair_per_row(world):
     st = DecodeState(e, 3)
     assert st.sampling_args(0.8, [5, 6, 7]) == (None, None) and st.row_sampling == [(0.8, 5), (0.8, 6), (0.8, 7)]
     st.set_row_sampling(1, 1.25, 2051)
-    assert st.row_topk.tolist() == [5, 2051, 7] and st.row_temperature.tolist() == [pytest.approx(0.8), 1.25, pytest.approx(0.8)]
+    row_t, row_k = st.sampler.params[:2]                                    # [K, B]: every codebook's row of the buffers
+    assert row_k.tolist() == [[5, 2051, 7]] * K and row_t.tolist() == [[pytest.approx(0.8), 1.25, pytest.approx(0.8)]] * K
     assert st.sampling_args(0.9, 50) == (0.9, 50) and st.sampling_args(None, None) == (None, None)
     for t, k in ((0.0, 5), (float("nan"), 5), (float("inf"), 5), (-1.0, 5), (0.9, 0), (0.9, 2052), (0.9, 2.5)):
         with pytest.raises(ValueError, match="temperature must be|topk must be"):
@@ -207,7 +209,7 @@ def test_engine_frames_take_one_pair_per_row(world):
         st.sampling_args([0.9, 0.8], 5)
     assert st.row_sampling == [(0.8, 5), (1.25, 2051), (0.8, 7)]
     with pytest.raises(RuntimeError, match="set_row_sampling first"):
-        DecodeState(e, 2).row_sampling_buffers()
+        DecodeState(e, 2).sampler.draw(None, 0, None)                      # (what a frame body called with None, None does)
     m.use_kv_cache = False
     try:
         with pytest.raises(ValueError, match="per-row sampling parameters need the KV-cache path"):
