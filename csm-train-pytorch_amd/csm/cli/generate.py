@@ -54,7 +54,10 @@ def parse_args(argv=None):
                    help="LoRA adapter file written by csm-finetune-lora (.safetensors with its _metadata.json), applied without merging")
     p.add_argument("--decode-weights", type=str, choices=["bf16", "fp8"], default="bf16",
                    help="weights streamed by the decode steps: bf16 (default) or fp8 (weight-only e4m3, one scale per output row; "
-                        "not with --lora-adapter)")
+                        "not with --lora-adapter or --serve-file lines that name an adapter, unless --fp8-adapters)")
+    p.add_argument("--fp8-adapters", action="store_true",
+                   help="with --decode-weights fp8: run --lora-adapter and the adapters of --serve-file lines un-merged on the FP8 "
+                        "base (Model.fp8_adapters; the adapters were trained against the bf16 base - check the voices)")
     p.add_argument("--next-text", type=str, action="append", default=None,
                    help="a further line, spoken after --text in the same conversation with the KV cache kept (repeatable)")
     p.add_argument("--next-speaker", type=int, action="append", default=None,
@@ -100,6 +103,8 @@ def parse_args(argv=None):
         p.error("--hear-slots goes with --serve-file")
     if args.keep_turns < 0:
         p.error("--keep-turns must be >= 0")
+    if args.fp8_adapters and args.decode_weights != "fp8":
+        p.error("--fp8-adapters goes with --decode-weights fp8")
     if args.next_speaker and len(args.next_speaker) != len(args.next_text or []):
         p.error("--next-speaker must be given once per --next-text (or not at all)")
     return args
@@ -157,6 +162,8 @@ def main(argv=None):
     args = parse_args(argv)
     speaker_id = VOICE_PRESETS[args.voice] if args.voice else args.speaker
     extra = {} if args.decode_weights == "bf16" else {"decode_weights": args.decode_weights}     # (the default needs no word)
+    if args.fp8_adapters:
+        extra["fp8_adapters"] = True
     generator = load_csm_1b(args.model_path, args.device, mimi_weights=args.mimi_weights, tokenizer_path=args.text_tokenizer, **extra)
     context = build_context(args, generator.sample_rate)
     adapter = None

@@ -1151,7 +1151,10 @@ class _DecodeStack:
         """One product of a layer step, y = epilogue(x^ W^T) with layer ``i``'s weight ``name`` and the caller's fusions (norm
         prologue, SwiGLU, residual), in the stack's mode.  With a LoRA group ``G`` on the projection: t = s x^ At, then the same
         product with (t, Bx, bias) as K-extension - two launches, over pointer tables where each row has its own adapter (or
-        none).  Without: the e4m3 copy of the weight where ``attach_fp8`` made one (csm_gemv_fp8w), else the bf16 weight."""
+        none).  Without: the e4m3 copy of the weight where ``attach_fp8`` made one (csm_gemv_fp8w), else the bf16 weight.
+        Per-row adapters on a weight that has an e4m3 copy (``model.fp8_adapters``): the same t, then csm_gemv_fp8w_kext_rows -
+        the extension joins the SCALED base sum; a weight without a copy (the depth decoder's output projection while
+        ``fuse_attn`` keeps it bf16, met here only under an ``attn_out`` group) keeps the bf16 extended product."""
         name = f"layers.{i}.{name}"
         if G is None:
             if self.w8 is not None and name in self.w8:
@@ -1162,6 +1165,8 @@ class _DecodeStack:
             At_tab, Bx_tab, bias_tab, kx, lda, ldb = G
             ra, scale = self.lora_rows
             ops.lora_project_rows(x, At_tab, self.lt, ra, scale, kx, lda, **norm)
+            if self.w8 is not None and name in self.w8:
+                return ops.gemv_fp8w_kext_rows(x, *self.w8[name], y, self.lt, Bx_tab, ra, kx, ldb, bias_tab=bias_tab, **kw)
             return ops.gemv_kext_rows(x, W, y, self.lt, Bx_tab, ra, kx, ldb, bias_tab=bias_tab, **kw)
         At, Bx, bias = G
         t = self.lt[:, :At.shape[1]]
@@ -1313,10 +1318,17 @@ class DecodeState:
             raise ValueError(f"generate with live (un-merged) LoRA adapters takes at most 4 sequences at a time (got {B}): "
                              "merge them first (merge_lora_weights) or decode at most 4 utterances")
         self.decode_weights = getattr(m, "decode_weights", "bf16")
-        if self.decode_weights == "fp8" and (self.adapters is not None or (m.lora is not None and not m.lora.merged)):
+        fp8_adapters = bool(getattr(m, "fp8_adapters", False))
+        if self.decode_weights == "fp8" and m.lora is not None and not m.lora.merged and self.adapters is None and fp8_adapters:
+            raise ValueError('decode_weights = "fp8" with live (un-merged) LoRA adapters as model.lora: the FP8 K-extension kernels '
+                             'take per-utterance adapters only - merge the adapters first (merge_lora_weights), pass them per '
+                             'utterance or through the bank instead (generate(adapter=), load_adapter), or set '
+                             'model.decode_weights = "bf16"')
+        if self.decode_weights == "fp8" and not fp8_adapters and (self.adapters is not None or (m.lora is not None and not m.lora.merged)):
             raise ValueError('decode_weights = "fp8" with live (un-merged) LoRA adapters or a per-utterance adapter bank: the '
                              'K-extension decode kernels are bf16-only - merge the adapters first (merge_lora_weights) or set '
-                             'model.decode_weights = "bf16"')
+                             'model.decode_weights = "bf16".  Per-utterance adapters and banks run on the quantised base with '
+                             'model.fp8_adapters = True (an opt-in: the adapters were trained against the bf16 base)')
         self.e, self.B = engine, B
         dev = m.device
         self.bb = _DecodeStack(engine.backbone, B, m.bb.max_seq_len)

@@ -442,9 +442,12 @@ class Generator:
 
 
 def load_csm_1b(ckpt_path: str = "ckpt.pt", device: str = "cuda", text_tokenizer=None, audio_tokenizer=None,
-                mimi_weights: str = None, tokenizer_path: str = None, decode_weights: str = "bf16") -> Generator:
+                mimi_weights: str = None, tokenizer_path: str = None, decode_weights: str = "bf16",
+                fp8_adapters: bool = False) -> Generator:
     """Reference generator.py:221-244.  ``mimi_weights`` / ``tokenizer_path`` name local files for the two tokenizers the
-    reference pulls from the hub.  ``decode_weights``: "bf16" or "fp8" (``Model.decode_weights``: weight-only e4m3 decode)."""
+    reference pulls from the hub.  ``decode_weights``: "bf16" or "fp8" (``Model.decode_weights``: weight-only e4m3 decode).
+    ``fp8_adapters``: with "fp8", let per-utterance adapters and the bank run un-merged on the quantised base
+    (``Model.fp8_adapters``: an opt-in - the adapters were trained against the bf16 base)."""
     if audio_tokenizer is None and mimi_weights:
         from .codec import load_mimi
         audio_tokenizer = load_mimi(mimi_weights, device=device)
@@ -455,4 +458,5 @@ def load_csm_1b(ckpt_path: str = "ckpt.pt", device: str = "cuda", text_tokenizer
     model = Model(args, device=device)
     model.load_state_dict(torch.load(ckpt_path, map_location="cpu", weights_only=False))
     model.decode_weights = decode_weights
+    model.fp8_adapters = fp8_adapters
     return Generator(model, text_tokenizer=text_tokenizer, audio_tokenizer=audio_tokenizer)

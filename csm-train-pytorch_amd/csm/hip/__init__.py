@@ -89,6 +89,7 @@ _SIGS = {
     "csm_gemv_bf16_ex": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _i, _p], _i),
     "csm_quantize_rows_fp8": ([_p, _p, _p, _i, _i, _i, _i, _p], _i),
     "csm_gemv_fp8w": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _i, _p], _i),
+    "csm_gemv_fp8w_kext_rows": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _f, _i, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "csm_attn_decode_rope": ([_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_gemv_attn_bf16": ([_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_gemv_attn_at_bf16": ([_p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),

@@ -528,6 +528,31 @@ def gemv_fp8w(x, W8, scale, y, residual=None, norm_scale=None, eps=1e-5, swiglu=
     return y
 
 
+def gemv_fp8w_kext_rows(x, W8, scale, y, ext_t, Bx_tab, row_adapter, kx, ldb, residual=None, norm_scale=None, eps=1e-5, swiglu=False,
+                        row_index=None, row_offset=0, bias_tab=None):
+    """``gemv_fp8w`` with row b extended by its own adapter a = row_adapter[b] (the bank of ``gemv_kext_rows`` on the quantised
+    base): y = epilogue(scale[n] * x^ q^T + ext_t[b] Bx[a]^T + bias[a]) - the scale on the base sum only, the extension added in
+    fp32 after it.  Tables as for ``gemv_kext_rows``.  B = 1..16: B <= 4 row b is the bits of the one-row launch with adapter a;
+    5..16 a row's bits depend on its own operands only; a row without adapter is the plain ``gemv_fp8w`` at the same B."""
+    B = y.shape[0]
+    K = x.shape[1]
+    N = W8.shape[0]
+    A = Bx_tab.numel()
+    assert W8.dtype == torch.uint8 and scale.dtype == torch.float32 and scale.numel() == N and scale.is_contiguous() and x.dtype == BF16
+    assert W8.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W8.stride(1) == 1 and y.stride(1) == 1
+    assert row_index is not None or x.shape[0] == B
+    assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
+    assert ext_t.shape[0] == B and ext_t.shape[1] >= kx and ext_t.stride(1) == 1 and ext_t.dtype == BF16
+    assert Bx_tab.dtype == torch.int64 and Bx_tab.is_contiguous() and Bx_tab.is_cuda
+    assert bias_tab is None or (bias_tab.dtype == torch.int64 and bias_tab.numel() == A and bias_tab.is_contiguous() and bias_tab.is_cuda)
+    assert row_adapter.dtype == torch.int32 and row_adapter.numel() == B and row_adapter.is_contiguous() and row_adapter.is_cuda
+    check(lib.csm_gemv_fp8w_kext_rows(x.data_ptr(), W8.data_ptr(), scale.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K,
+                                      W8.stride(0), x.stride(0), y.stride(0), int(y.dtype == torch.float32), _ptr(norm_scale),
+                                      float(eps), int(swiglu), _ptr(row_index), int(row_offset), ext_t.data_ptr(), Bx_tab.data_ptr(),
+                                      _ptr(bias_tab), row_adapter.data_ptr(), A, int(kx), ext_t.stride(0), int(ldb), _stream()),
+          "csm_gemv_fp8w_kext_rows")
+    return y
+
 def lora_project(x, At, t, scale, norm_scale=None, eps=1e-5):
     """t[B, kx] = scale * x^ At (bf16), x^ = x or its RMSNorm (norm_scale): the extension operand of ``gemv_kext`` for a LoRA
     group whose At [K, kx] is read in place (training/lora.py)."""

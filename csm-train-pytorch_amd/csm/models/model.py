@@ -220,6 +220,7 @@ class Model(nn.Module):
         self.use_kv_cache = True                              # generate_frame: KV caches (False = prefix recompute)
         self.use_hip_graph = True                             # replay decode frames as one captured HIP graph
         self._decode_weights = "bf16"                         # decode_weights: "bf16" | "fp8" (weight-only e4m3 decode steps)
+        self._fp8_adapters = False                            # fp8_adapters: per-utterance adapters / banks on the FP8 base (opt-in)
         # which parameter groups receive weight gradients (freeze flags of trainer.prepare_optimizer / LoRA)
         self.trainable = {"backbone": True, "decoder": True, "embeddings": True, "other": True}
         if device is not None:
@@ -232,7 +233,8 @@ class Model(nn.Module):
         current weights when a decode state is created; activations stay bf16, sums fp32.  Embeddings, projection and the heads
         stay bf16, and so do training, prefill, ``DecodeState.append`` and the recompute path (``use_kv_cache = False``), which
         ignores the mode.  Setting it drops the decode state and its captured graph.  Live (un-merged) LoRA adapters and
-        per-utterance adapter banks are refused in FP8 mode: merge first, or use bf16."""
+        per-utterance adapter banks are refused in FP8 mode: merge first, or use bf16 - or opt in to per-utterance adapters on
+        the quantised base with ``fp8_adapters``."""
         return self._decode_weights
 
     @decode_weights.setter
@@ -241,6 +243,25 @@ class Model(nn.Module):
             raise ValueError(f'decode_weights must be "bf16" or "fp8" (got {value!r})')
         if value != self._decode_weights:
             self._decode_weights = value
+            self._decode_state = None
+
+    @property
+    def fp8_adapters(self) -> bool:
+        """Opt-in (default ``False``): with ``decode_weights = "fp8"``, per-utterance LoRA adapters and adapter banks
+        (``generate(adapter=)``, ``generate_batch(adapters=)``, ``serve()`` / ``submit(adapter=)``, conversations with an adapter)
+        ride on the FP8 layer products as un-merged K-extensions (csm_gemv_fp8w_kext_rows) instead of being refused.  Caveat: the
+        adapters were trained against the bf16 base and are applied here on a quantised base - the extension itself is exact
+        bf16 arithmetic and is never scaled, but the base activations it reads and adds to carry the FP8 quantisation error, which
+        no adapter was trained to see; judge the voices' quality on your own data before serving this way.  Live adapters attached
+        as ``model.lora`` stay refused in FP8 mode either way (merge them, or put them into the bank).  Ignored in bf16 mode.
+        Setting it drops the decode state and its captured graph."""
+        return self._fp8_adapters
+
+    @fp8_adapters.setter
+    def fp8_adapters(self, value):
+        value = bool(value)
+        if value != self._fp8_adapters:
+            self._fp8_adapters = value
             self._decode_state = None
 
     # ------------------------------------------------------------------ layout

@@ -1,6 +1,7 @@
 // Generation-side kernels for gfx950: top-k / temperature sampler with injected Exp(1) noise, and the Mimi
 // split residual vector quantiser (nearest-codeword encode, codebook-sum decode).
 #include "common.h"
+#include "gemv_ext.h"
 #include <math.h>
 
 namespace {
@@ -603,56 +604,8 @@ extern "C" int csm_rvq_decode(const long long* codes, const float* codebooks, fl
 // between waves) and reduce with wave shuffles.
 namespace {
 
-// K-extension of a decode product (a LoRA group, training/lora.py): output row n also takes sum_j t[b][j] Bx[n][j] (+ bias[n])
-// - the group's adapters as extra k-steps of the frozen projection, before the residual / SwiGLU / fp32-output epilogue, as
-// csm_gemm_bf16_kext does in training.  The kernels below take it as a trailing argument PACK: the plain instantiations have an
-// empty pack, so their signature and code are what they were.  Lane l owns the extension's 8-element chunk l (kx <= 512), loaded
-// beside the weights; its products are added to the lane's partial sum AFTER the main k-loop (the main partial sums keep their
-// order: Bx = 0 leaves every bit of the plain product) by explicit fused multiply-adds in ascending j - the same operations in
-// every kernel, so a B-row launch stays bit-equal per row to the one-row launch.
-struct GemvExt {
-    const bf16_t* t;      // [B][ldt]  s x^ At, bf16 (csm_lora_project_bf16)
-    const bf16_t* Bx;     // [N][ldb]  rows in the fused projection's order (w13: gate / up interleaved)
-    const bf16_t* bias;   // [N] or NULL
-    int kx, ldt, ldb;
-};
-__device__ __forceinline__ const GemvExt& ext_arg(const GemvExt& e) { return e; }
-// The per-row ("gathered") form (csm_gemv_bf16_kext_rows: a bank of adapters, one per batch row): row b takes its extension from
-// adapter a = row_adapter[b] - Bx[a], bias[a] (the table itself or an entry may be NULL) - with the same operations in the same
-// order as GemvExt, so row b is bit-identical to a one-row GemvExt launch with adapter a.  a = -1 (or out of range): no extension
-// at all, the plain product's bits.  t is [B][ldt] as for GemvExt (csm_lora_project_rows_bf16 leaves each row's own adapter's t).
-struct GemvExtRows {
-    const bf16_t* t;                  // [B][ldt]
-    const bf16_t* const* Bx;          // [nad] -> [N][ldb]
-    const bf16_t* const* bias;        // [nad] -> [N] or NULL; NULL: no adapter has a bias
-    const int* row_adapter;           // [B], -1 = none
-    int nad, kx, ldt, ldb;
-};
-__device__ __forceinline__ const GemvExtRows& ext_rows_arg(const GemvExtRows& e) { return e; }
-// 0: the plain products (empty pack), 1: GemvExt, 2: GemvExtRows
-template <typename... E> struct ExtKind { static constexpr int v = 0; };
-template <> struct ExtKind<GemvExt> { static constexpr int v = 1; };
-template <> struct ExtKind<GemvExtRows> { static constexpr int v = 2; };
-__device__ __forceinline__ int ext_row_adapter(const GemvExtRows& e, int b) {      // (wave-uniform) the row's adapter or -1
-    const int a = e.row_adapter[b];
-    return a < e.nad ? a : -1;
-}
-__device__ __forceinline__ float ext_row_bias(const GemvExtRows& e, int a, int n) {
-    const bf16_t* bb = e.bias ? e.bias[a] : nullptr;
-    return bb ? bf2f(bb[n]) : 0.f;
-}
-__device__ __forceinline__ U4 ext_load(const bf16_t* row, int lane, int kx) {
-    U4 z = {0u, 0u, 0u, 0u};
-    return lane < (kx >> 3) ? *reinterpret_cast<const U4*>(row + lane * 8) : z;
-}
-__device__ __forceinline__ float ext_fma(float acc, const U4& b, const U4& t) {
-    float bf[8], tf[8];
-    unpack8(b, bf);
-    unpack8(t, tf);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc = __builtin_fmaf(bf[j], tf[j], acc);
-    return acc;
-}
+// (the K-extension of these products - GemvExt, GemvExtRows, ExtKind, ext_load / ext_fma / ext_dot - is gemv_ext.h: quant.hip's
+//  FP8 families take the same packs)
 
 // y[b][n] = sum_k x[b][k] * W[n][k] (+ R[b][n]);  one wave per output row, NB <= 4 batch rows share every weight load.
 // Two optional fusions remove the tiny kernels that otherwise sit between the matrix-vector products of a decode step:
@@ -1140,11 +1093,6 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
 // extension sum_j t[b][j] Bx[a_b][n][j] to the wave-ordered sum, one fmaf per j in ascending j (then the adapter's bias), before
 // the rounding / SwiGLU / residual epilogue.  It reads only row b's operands, so a row keeps its bits for any B in 5..16, any
 // position and any batch-mates and their adapters; a row without adapter takes no extension: the plain product's bits.
-__device__ __forceinline__ float ext_dot(float v, const bf16_t* __restrict__ bx, const bf16_t* __restrict__ t, int kx) {
-    for (int j = 0; j < kx; j += 8)
-        v = ext_fma(v, *reinterpret_cast<const U4*>(bx + j), *reinterpret_cast<const U4*>(t + j));
-    return v;
-}
 template <int SEG, typename OutT, bool SWIGLU, bool NT, typename... Ext>
 __global__ __launch_bounds__(512) void gemv_mfma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, OutT* __restrict__ y,
                                                         const bf16_t* __restrict__ R, int B, int N, int K, int ldw, int ldx, int ldy,

@@ -5,7 +5,30 @@
 // the quantiser's.  The kernels mirror the bf16 families of generate.hip (gemv_reg_kernel / gemv_regn_kernel / gemv_mfma_kernel)
 // with the weight operand replaced: weights global -> VGPRs in 16-byte loads (16 weights each), no LDS for them, fixed
 // reduction order, no atomics.
+//
+// Per-row K-extension (csm_gemv_fp8w_kext_rows: an un-merged LoRA adapter per batch row on the quantised base; the packs and the
+// extension's operations are gemv_ext.h's, shared with the bf16 families).  Row b with adapter a = row_adapter[b]:
+//     y[b][n] = epilogue(scale[n] * sum_k x^[b][k] q[n][k]  +  sum_j t[b][j] Bx[a][n][j]  +  bias[a][n])
+//   1. base = scale[n] * (the row sum), formed exactly as csm_gemv_fp8w forms it: same products, same order, ONE scaling of the
+//      finished sum.  The scale belongs to the quantised weights alone - t and Bx are bf16 numbers that never saw the quantiser -
+//      so the extension is NOT scaled.
+//   2. ext = sum_j t[b][j] Bx[a][n][j] in fp32, a fixed order, starting from zero (VALU) or accumulated onto base (MFMA):
+//        B <= 4 (gemv_fp8_kernel):       lane l owns extension chunk l (ext_load), ext_fma from 0 over its 8 elements in ascending
+//                                        j, then a SECOND butterfly of the kernel's own shape (wave_sum; under SwiGLU the same
+//                                        permlane32_swap pairing: gate partials to lanes 0-31, up partials to lanes 32-63, one
+//                                        butterfly for both); v = base + ext.  The base butterfly is untouched: the lane partials
+//                                        of the main loop are never mixed with extension terms.
+//        B = 5..16 (gemv_fp8_mfma_kernel): the epilogue thread of output (n, b) runs ext_dot ONTO base, one fmaf per j in
+//                                        ascending j, as gemv_mfma_kernel does onto its un-scaled sum.
+//   3. v += bias[a][n] (0 where the table or the adapter's entry is NULL), then the existing epilogue: SwiGLU rounds gate and up to
+//      bf16 after extension and bias; residual; bf16 or fp32 store.
+// A row with a = -1 or a >= n_adapters skips 2 and 3 altogether (a wave-uniform branch, not an addition of zero): the bits of
+// csm_gemv_fp8w at the same B.  Every step reads row b's operands only and the VALU steps are the same operations for every NB,
+// so the plain kernels' two promises carry over: B <= 4, row b of a B-row launch is the one-row launch's bits; B = 5..16, a row's
+// bits do not depend on B, its position or its batch-mates and their adapters.  No atomics.  The plain instantiations have an
+// empty pack: their signature, code and bits are what they were.
 #include "common.h"
+#include "gemv_ext.h"
 #include <math.h>
 
 // Every multiply-add below is written out (__builtin_fmaf / elementwise_fma): nothing is left to the compiler's contraction, which
@@ -124,12 +147,14 @@ __device__ __forceinline__ void xhat16(const U4 (&xr)[2], const bf16_t* __restri
 // elements in ascending k and then the same butterfly: row b of a B-row launch is bit-identical to the one-row launch.
 // Fusions as csm_gemv_bf16_ex: norm_w (RMSNorm prologue), SWIGLU (interleaved gate / up rows, each scaled and rounded to bf16
 // first), R (residual), fp32 output, row_index (x gathered from a table), NT (non-temporal weight loads).
-template <int KC, int NB, typename OutT, bool SWIGLU, bool NT>
+template <int KC, int NB, typename OutT, bool SWIGLU, bool NT, typename... Ext>
 __global__ __launch_bounds__(256) void gemv_fp8_kernel(const bf16_t* __restrict__ x, const uint8_t* __restrict__ W8,
                                                        const float* __restrict__ scale, OutT* __restrict__ y,
                                                        const bf16_t* __restrict__ R, int N, int K, int ldw8, int ldx, int ldy,
                                                        const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
-                                                       int row_offset) {
+                                                       int row_offset, Ext... ext) {
+    constexpr int EK = ExtKind<Ext...>::v;
+    static_assert(EK != 1, "gemv_fp8_kernel takes the per-row extension only");
     constexpr int RW = SWIGLU ? 2 : 1;
     constexpr int NP = (NB + 1) / 2;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -152,6 +177,30 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(const bf16_t* __restrict_
                 }
             }
     }
+    // GemvExtRows: row b's adapter (wave-uniform), its chunk of t and of the adapter's Bx rows, the adapter's bias.  Requested
+    // beside the weights where the registers allow it (KC <= 2), after the main loop otherwise (K = 8192: a long loop, the
+    // latency is small against it).
+    [[maybe_unused]] int ea[NB];
+    [[maybe_unused]] U4 et[NB], eb[RW][NB];
+    [[maybe_unused]] float ebias[RW][NB];
+    [[maybe_unused]] auto ext_fetch = [&]() {
+        if constexpr (EK == 2) {
+            const GemvExtRows& e = ext_rows_arg(ext...);
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                ea[b] = __builtin_amdgcn_readfirstlane(ext_row_adapter(e, b));
+                if (ea[b] >= 0) {
+                    et[b] = ext_load(e.t + (size_t)b * e.ldt, lane, e.kx);
+#pragma unroll
+                    for (int r = 0; r < RW; ++r) {
+                        eb[r][b] = ext_load(e.Bx[ea[b]] + (size_t)(nn * RW + r) * e.ldb, lane, e.kx);
+                        ebias[r][b] = ext_row_bias(e, ea[b], nn * RW + r);
+                    }
+                }
+            }
+        }
+    };
+    if constexpr (EK == 2 && KC <= 2) ext_fetch();
     q_f2 acc[RW][NP];
 #pragma unroll
     for (int r = 0; r < RW; ++r)
@@ -219,6 +268,7 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(const bf16_t* __restrict_
             if constexpr (KC > 2) __builtin_amdgcn_sched_barrier(0);
         }
     }
+    if constexpr (EK == 2 && KC > 2) ext_fetch();
     float sc[RW];
 #pragma unroll
     for (int r = 0; r < RW; ++r) sc[r] = scale[nn * RW + r];
@@ -226,18 +276,39 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(const bf16_t* __restrict_
     for (int b = 0; b < NB; ++b) {
         const float a0 = (b & 1) ? acc[0][b >> 1].y : acc[0][b >> 1].x;
         float v;
+        [[maybe_unused]] bool ron = false;                       // (wave-uniform) the row has an adapter
+        if constexpr (EK == 2) ron = ea[b] >= 0;
         if constexpr (SWIGLU) {
             // both row sums in one butterfly (gemv_reg_kernel): gate partials to lanes 0-31, up partials to lanes 32-63
             const float a1 = (b & 1) ? acc[1][b >> 1].y : acc[1][b >> 1].x;
             auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
             float t = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
             t += lane_xor<16>(t); t += lane_xor<8>(t); t += lane_xor<4>(t); t += lane_xor<2>(t); t += lane_xor<1>(t);
-            const float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0)) * sc[0];
-            const float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32)) * sc[1];
+            float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0)) * sc[0];
+            float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32)) * sc[1];
+            if constexpr (EK == 2) {
+                if (ron) {
+                    // the extension's own butterfly, the same pairing: lane partials from zero, gate to lanes 0-31, up to 32-63
+                    const float e0 = ext_fma(0.f, eb[0][b], et[b]), e1 = ext_fma(0.f, eb[1][b], et[b]);
+                    auto se = __builtin_amdgcn_permlane32_swap(__float_as_uint(e0), __float_as_uint(e1), false, false);
+                    float te = __uint_as_float(se[0]) + __uint_as_float(se[1]);
+                    te += lane_xor<16>(te); te += lane_xor<8>(te); te += lane_xor<4>(te); te += lane_xor<2>(te); te += lane_xor<1>(te);
+                    gs += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(te), 0));
+                    us += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(te), 32));
+                    gs += ebias[0][b];
+                    us += ebias[1][b];
+                }
+            }
             const float g = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
             v = silu(g) * u;
         } else {
             v = wave_sum(a0) * sc[0];
+            if constexpr (EK == 2) {
+                if (ron) {
+                    v += wave_sum(ext_fma(0.f, eb[0][b], et[b]));
+                    v += ebias[0][b];
+                }
+            }
         }
         if (lane == 0 && live) {
             if (R) v += bf2f(R[(size_t)b * ldy + n]);
@@ -260,12 +331,16 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(const bf16_t* __restrict_
 // both modes hold exactly the two modes' sampled codes then drift apart inside a frame ('FP8 weights').
 // An output column sees only its own batch row's operands in an order fixed by K: the same bits for any B in 5..16, any
 // position, any batch-mates.
-template <int SEG, typename OutT, bool SWIGLU, bool NT>
+// Trailing pack (empty, or one GemvExtRows): the epilogue thread of output (n, b) takes the scaled sum, then - where row b has an
+// adapter - ext_dot onto it (one fmaf per j, ascending j) and the adapter's bias, before the rounding / SwiGLU / residual.
+template <int SEG, typename OutT, bool SWIGLU, bool NT, typename... Ext>
 __global__ __launch_bounds__(512) void gemv_fp8_mfma_kernel(const bf16_t* __restrict__ x, const uint8_t* __restrict__ W8,
                                                             const float* __restrict__ scale, OutT* __restrict__ y,
                                                             const bf16_t* __restrict__ R, int B, int N, int K, int ldw8, int ldx,
                                                             int ldy, const bf16_t* __restrict__ norm_w, float eps,
-                                                            const int* __restrict__ row_index, int row_offset) {
+                                                            const int* __restrict__ row_index, int row_offset, Ext... ext) {
+    constexpr int EK = ExtKind<Ext...>::v;
+    static_assert(EK != 1, "gemv_fp8_mfma_kernel takes the per-row extension only");
     constexpr int NW = 8;
     __shared__ float rs[16];
     __shared__ float part[NW][16][17];                        // [wave][weight row of the tile][batch row] (+1: no bank conflicts)
@@ -361,6 +436,16 @@ __global__ __launch_bounds__(512) void gemv_fp8_mfma_kernel(const bf16_t* __rest
             for (int w = 1; w < NW; ++w) { gs += part[w][2 * i][b]; us += part[w][2 * i + 1][b]; }
             gs *= scale[n0 + 2 * i];
             us *= scale[n0 + 2 * i + 1];
+            if constexpr (EK == 2) {
+                const GemvExtRows& e = ext_rows_arg(ext...);
+                const int a = ext_row_adapter(e, b);
+                if (a >= 0) {
+                    gs = ext_dot(gs, e.Bx[a] + (size_t)(n0 + 2 * i) * e.ldb, e.t + (size_t)b * e.ldt, e.kx);
+                    us = ext_dot(us, e.Bx[a] + (size_t)(n0 + 2 * i + 1) * e.ldb, e.t + (size_t)b * e.ldt, e.kx);
+                    gs += ext_row_bias(e, a, n0 + 2 * i);
+                    us += ext_row_bias(e, a, n0 + 2 * i + 1);
+                }
+            }
             const float gg = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
             float v = silu(gg) * u;
             const int n = (n0 >> 1) + i;
@@ -375,6 +460,11 @@ __global__ __launch_bounds__(512) void gemv_fp8_mfma_kernel(const bf16_t* __rest
 #pragma unroll
             for (int w = 1; w < NW; ++w) v += part[w][rr][b];
             v *= scale[n];
+            if constexpr (EK == 2) {
+                const GemvExtRows& e = ext_rows_arg(ext...);
+                const int a = ext_row_adapter(e, b);
+                if (a >= 0) v = ext_dot(v, e.Bx[a] + (size_t)n * e.ldb, e.t + (size_t)b * e.ldt, e.kx) + ext_row_bias(e, a, n);
+            }
             if (R) v += bf2f(R[(size_t)b * ldy + n]);
             if constexpr (sizeof(OutT) == 2) y[(size_t)b * ldy + n] = f2bf(v);
             else y[(size_t)b * ldy + n] = v;
@@ -396,9 +486,12 @@ extern "C" int csm_quantize_rows_fp8(const void* W, void* W8, void* scale, int N
     return 0;
 }
 
-extern "C" int csm_gemv_fp8w(const void* x, const void* W8, const void* scale, void* y, const void* residual, int B, int N, int K,
-                             int ldw8, int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu,
-                             const int* row_index, int row_offset, hipStream_t stream) {
+// ext: empty (csm_gemv_fp8w) or one GemvExtRows (csm_gemv_fp8w_kext_rows): the same checks and dispatch, the kernels' trailing pack
+template <typename... Ext>
+static int gemv_fp8_launch(const void* x, const void* W8, const void* scale, void* y, const void* residual, int B, int N, int K,
+                           int ldw8, int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu,
+                           const int* row_index, int row_offset, hipStream_t stream, Ext... ext) {
+    constexpr bool EXT = ExtKind<Ext...>::v != 0;
     CSM_REQUIRE(x && W8 && scale && y && B >= 1 && B <= 16 && N > 0 && K > 0,
                 "csm_gemv_fp8w: bad arguments (B=%d N=%d K=%d: needs 1 <= B <= 16)", B, N, K);
     CSM_REQUIRE((K & 15) == 0 && K <= 8192, "csm_gemv_fp8w: needs K %% 16 == 0 and K <= 8192 (K=%d): a 16-byte load carries 16 weights", K);
@@ -412,14 +505,15 @@ extern "C" int csm_gemv_fp8w(const void* x, const void* W8, const void* scale, v
     if (B > 4) {
         const int grid = (N + 15) / 16;
         const int spw = ((K + 63) / 64 + 7) / 8;                // 64-k steps per wave
-#define LM(SEG, T, SW, NT_) hipLaunchKernelGGL((gemv_fp8_mfma_kernel<SEG, T, SW, NT_>), dim3(grid), dim3(512), 0, stream, ARGS(T), B, N, K, ldw8, ldx, ldy, (const bf16_t*)norm_scale, eps, row_index, row_offset)
+#define LM(SEG, T, SW, NT_) hipLaunchKernelGGL((gemv_fp8_mfma_kernel<SEG, T, SW, NT_, Ext...>), dim3(grid), dim3(512), 0, stream, ARGS(T), B, N, K, ldw8, ldx, ldy, (const bf16_t*)norm_scale, eps, row_index, row_offset, ext...)
 #define LMS(T, SW, NT_) do { if (spw <= 1) LM(1, T, SW, NT_); else if (spw <= 2) LM(2, T, SW, NT_); else if (spw <= 4) LM(4, T, SW, NT_); else LM(8, T, SW, NT_); } while (0)
         if (swiglu) { if (nt) LMS(bf16_t, true, true); else LMS(bf16_t, true, false); }
         else if (out_f32) { if (nt) LMS(float, false, true); else LMS(float, false, false); }
         else { if (nt) LMS(bf16_t, false, true); else LMS(bf16_t, false, false); }
 #undef LMS
 #undef LM
-        g_last_gemv = {"gemv_fp8_mfma_kernel<%d, %s, %d, %d>", (out_f32 && !swiglu) ? "float" : "bf16",
+        g_last_gemv = {EXT ? "gemv_fp8_mfma_kernel<%d, %s, %d, %d, ext2>" : "gemv_fp8_mfma_kernel<%d, %s, %d, %d>",
+                       (out_f32 && !swiglu) ? "float" : "bf16",
                        {spw <= 1 ? 1 : (spw <= 2 ? 2 : (spw <= 4 ? 4 : 8)), swiglu ? 1 : 0, nt ? 1 : 0, 0, 0, 0}};
         CSM_CHECK_LAUNCH("csm_gemv_fp8w");
         return 0;
@@ -428,9 +522,9 @@ extern "C" int csm_gemv_fp8w(const void* x, const void* W8, const void* scale, v
     const int grid = (no + 3) / 4;
     const int kc = K <= 1024 ? 1 : (K <= 2048 ? 2 : 8);
     const size_t lds = B == 1 ? 0 : (size_t)B * kc * 1024 * sizeof(float);
-#define LN(KC, NB, T, SW, NT_) do { auto kf = gemv_fp8_kernel<KC, NB, T, SW, NT_>;                                                      \
+#define LN(KC, NB, T, SW, NT_) do { auto kf = gemv_fp8_kernel<KC, NB, T, SW, NT_, Ext...>;                                              \
         if (lds > 65536) { static bool done_ = false; if (!done_) { (void)hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); done_ = true; } } \
-        hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, stream, ARGS(T), N, K, ldw8, ldx, ldy, (const bf16_t*)norm_scale, eps, row_index, row_offset); } while (0)
+        hipLaunchKernelGGL(kf, dim3(grid), dim3(256), lds, stream, ARGS(T), N, K, ldw8, ldx, ldy, (const bf16_t*)norm_scale, eps, row_index, row_offset, ext...); } while (0)
 #define LNB(KC, T, SW, NT_) do { if (B == 1) LN(KC, 1, T, SW, NT_); else if (B == 2) LN(KC, 2, T, SW, NT_); else if (B == 3) LN(KC, 3, T, SW, NT_); else LN(KC, 4, T, SW, NT_); } while (0)
 #define LNK(T, SW) do { if (kc == 1) LNB(1, T, SW, false); else if (kc == 2) { if (nt) LNB(2, T, SW, true); else LNB(2, T, SW, false); } \
                         else { if (nt) LNB(8, T, SW, true); else LNB(8, T, SW, false); } } while (0)
@@ -439,9 +533,37 @@ extern "C" int csm_gemv_fp8w(const void* x, const void* W8, const void* scale, v
 #undef LNB
 #undef LN
 #undef ARGS
-    g_last_gemv = {B == 1 ? "gemv_fp8_kernel<%d, 1, %s, %d, %d>" : B == 2 ? "gemv_fp8_kernel<%d, 2, %s, %d, %d>"
-                   : B == 3 ? "gemv_fp8_kernel<%d, 3, %s, %d, %d>" : "gemv_fp8_kernel<%d, 4, %s, %d, %d>",
-                   (out_f32 && !swiglu) ? "float" : "bf16", {kc, swiglu ? 1 : 0, (nt && kc != 1) ? 1 : 0, 0, 0, 0}};
+    if (EXT)
+        g_last_gemv = {B == 1 ? "gemv_fp8_kernel<%d, 1, %s, %d, %d, ext2>" : B == 2 ? "gemv_fp8_kernel<%d, 2, %s, %d, %d, ext2>"
+                       : B == 3 ? "gemv_fp8_kernel<%d, 3, %s, %d, %d, ext2>" : "gemv_fp8_kernel<%d, 4, %s, %d, %d, ext2>",
+                       (out_f32 && !swiglu) ? "float" : "bf16", {kc, swiglu ? 1 : 0, (nt && kc != 1) ? 1 : 0, 0, 0, 0}};
+    else
+        g_last_gemv = {B == 1 ? "gemv_fp8_kernel<%d, 1, %s, %d, %d>" : B == 2 ? "gemv_fp8_kernel<%d, 2, %s, %d, %d>"
+                       : B == 3 ? "gemv_fp8_kernel<%d, 3, %s, %d, %d>" : "gemv_fp8_kernel<%d, 4, %s, %d, %d>",
+                       (out_f32 && !swiglu) ? "float" : "bf16", {kc, swiglu ? 1 : 0, (nt && kc != 1) ? 1 : 0, 0, 0, 0}};
     CSM_CHECK_LAUNCH("csm_gemv_fp8w");
     return 0;
+}
+
+extern "C" int csm_gemv_fp8w(const void* x, const void* W8, const void* scale, void* y, const void* residual, int B, int N, int K,
+                             int ldw8, int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu,
+                             const int* row_index, int row_offset, hipStream_t stream) {
+    return gemv_fp8_launch(x, W8, scale, y, residual, B, N, K, ldw8, ldx, ldy, out_f32, norm_scale, eps, swiglu, row_index, row_offset, stream);
+}
+
+// csm_gemv_fp8w with one adapter per batch row (GemvExtRows, as csm_gemv_bf16_kext_rows takes it): B = 1..16.
+extern "C" int csm_gemv_fp8w_kext_rows(const void* x, const void* W8, const void* scale, void* y, const void* residual, int B, int N,
+                                       int K, int ldw8, int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu,
+                                       const int* row_index, int row_offset, const void* ext_t, const void* const* ext_B,
+                                       const void* const* bias, const int* row_adapter, int n_adapters, int kx, int ld_ext_t,
+                                       int ld_ext_B, hipStream_t stream) {
+    CSM_REQUIRE(B >= 1 && B <= 16, "csm_gemv_fp8w_kext_rows: B=%d: the per-row K-extension takes 1 to 16 batch rows", B);
+    CSM_REQUIRE(ext_t && ext_B && row_adapter && n_adapters >= 1 && kx > 0 && kx <= 512 && (kx & 7) == 0 && ld_ext_t >= kx &&
+                ld_ext_B >= kx && (ld_ext_t & 7) == 0 && (ld_ext_B & 7) == 0 && ((uintptr_t)ext_t & 15) == 0,
+                "csm_gemv_fp8w_kext_rows: bad extension (adapters=%d kx=%d ld_t=%d ld_B=%d: needs kx <= 512, multiples of 8, "
+                "16-byte aligned rows)", n_adapters, kx, ld_ext_t, ld_ext_B);
+    GemvExtRows e;
+    e.t = (const bf16_t*)ext_t; e.Bx = (const bf16_t* const*)ext_B; e.bias = (const bf16_t* const*)bias;
+    e.row_adapter = row_adapter; e.nad = n_adapters; e.kx = kx; e.ldt = ld_ext_t; e.ldb = ld_ext_B;
+    return gemv_fp8_launch(x, W8, scale, y, residual, B, N, K, ldw8, ldx, ldy, out_f32, norm_scale, eps, swiglu, row_index, row_offset, stream, e);
 }

@@ -304,7 +304,8 @@ int csm_gemv_bf16(const void* x, const void* W, void* y, const void* residual, i
  * _rows_bf16 or csm_gemv_t_bf16, with its template arguments, e.g. "gemv_reg_kernel<4, bf16, 0, 1, 1, ext0>" (host bookkeeping
  * for tests and probes, like csm_gemm_last_kernel; "" before the first launch; not thread-safe).  gemv_reg_kernel<KCH, T, SWIGLU,
  * NT, RPW, ext>, gemv_regn_kernel<KCH, NB, T, SWIGLU, NT, SC, ext>, gemv_kernel<NB, T, SWIGLU, ext>, gemv_mfma_kernel<SEG, T,
- * SWIGLU, NT, ext>, gemv_fp8_kernel<KC, NB, T, SWIGLU, NT>, gemv_fp8_mfma_kernel<SEG, T, SWIGLU, NT>, lora_project_kernel<NB>,
+ * SWIGLU, NT, ext>, gemv_fp8_kernel<KC, NB, T, SWIGLU, NT>, gemv_fp8_mfma_kernel<SEG, T, SWIGLU, NT> (csm_gemv_fp8w_kext_rows:
+ * the same two with a trailing ", ext2"), lora_project_kernel<NB>,
  * lora_project_rows_kernel<NB>, gemv_t_kernel<NB, T>; ext0 = no K-extension, ext1 = csm_gemv_bf16_kext, ext2 = _kext_rows. */
 const char* csm_gemv_last_kernel(void);
 /* csm_gemv_bf16 with the neighbouring element-wise steps of a decode layer fused in: norm_scale != NULL applies torchtune
@@ -358,6 +359,21 @@ int csm_gemv_bf16_kext_rows(const void* x, const void* W, void* y, const void* r
                             int ldy, int out_f32, const void* norm_scale, float eps, int swiglu, const int* row_index, int row_offset,
                             const void* ext_t, const void* const* ext_B, const void* const* bias, const int* row_adapter,
                             int n_adapters, int kx, int ld_ext_t, int ld_ext_B, csm_stream_t stream);
+/* csm_gemv_fp8w_kext_rows (since ABI 3, additive): csm_gemv_fp8w with row b extended by its own adapter a = row_adapter[b], the
+ * bank of csm_gemv_bf16_kext_rows on the quantised base:  y[b][n] = epilogue(scale[n] * sum_k x^[b][k] q[n][k] + sum_j ext_t[b][j]
+ * ext_B[a][n][j] + bias[a][n]).  The scaled base sum is csm_gemv_fp8w's, operation for operation; the extension (never scaled: t
+ * and ext_B are bf16 numbers the quantiser never saw) is summed in fp32 in a fixed order and added to it, then the adapter's bias,
+ * then the epilogue (SwiGLU: gate and up rounded to bf16 after extension and bias).  B <= 4: row b bit-identical to the one-row
+ * launch on that row with adapter a.  B = 5..16: a row's bits depend only on its own operands (any B in 5..16, any position, any
+ * batch-mates and their adapters).  A row with a = -1 or a >= n_adapters takes no extension: bit-identical to csm_gemv_fp8w at
+ * the same B.  Tables as for csm_gemv_bf16_kext_rows; kx <= 512 and a multiple of 8, extension rows 16-byte aligned; everything
+ * csm_gemv_fp8w requires of K, ldw8 and alignment.  csm_gemv_last_kernel() names these launches with a trailing ext2, e.g.
+ * "gemv_fp8_kernel<2, 4, bf16, 0, 1, ext2>"; csm_gemv_fp8w's launches keep their names without it. */
+int csm_gemv_fp8w_kext_rows(const void* x, const void* W8, const void* scale, void* y, const void* residual, int B, int N, int K,
+                            int ldw8, int ldx, int ldy, int out_f32, const void* norm_scale, float eps, int swiglu,
+                            const int* row_index, int row_offset, const void* ext_t, const void* const* ext_B,
+                            const void* const* bias, const int* row_adapter, int n_adapters, int kx, int ld_ext_t, int ld_ext_B,
+                            csm_stream_t stream);
 /* y[b][n] = sum_k x[b][k] W[k][n]  (K-major weights: audio_head[i] = [decoder_dim][vocab]) */
 int csm_gemv_t_bf16(const void* x, const void* W, void* y, int B, int N, int K, int ldw, int ldx, int ldy, int out_f32,
                     csm_stream_t stream);

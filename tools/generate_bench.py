@@ -9,7 +9,8 @@ the call to the first chunk on the host, total wall time and frames/s.  GEN_BATC
 utterances from one process, one line each (aggregate frames/s, seconds per frame).  GEN_LORA_BANK=q_proj,v_proj (or all): decode
 frames/s with a different LoRA adapter per utterance (16 adapters, some rows without) against the same batch without adapters
 and against the same utterances one at a time with their adapter live as model.lora, alternated in one process.
-GEN_FP8=1: decode frames/s with bf16 and with FP8 (weight-only e4m3) decode weights,
+GEN_FP8=1 together with GEN_LORA_BANK=...: bf16 + bank, FP8 + bank (model.fp8_adapters), FP8 and bf16 without adapters, alternated
+on one model at B = 4 / 8 / 16 (decode loop only).  GEN_FP8=1: decode frames/s with bf16 and with FP8 (weight-only e4m3) decode weights,
 alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in each mode.  GEN_SERVE=1: the running batch (Generator.serve): rows-codec step against single steps, the server step at
 16 rows, the join stall (serve_main).  GEN_SERVE_SAMPLING=1: the rows sampler against the scalar one and the 16-row
 server step with row_sampling off / on (serve_sampling_main); GEN_SERVE_SAMPLING=processors: the processed rows sampler (repetition penalty, per-codebook
@@ -208,23 +209,29 @@ def decode_fps_batch(model, B, adapters=None, frames=50, prompt=40):
     return B * frames / (time.time() - t0)
 
 
-def lora_bank_main(mods):
-    """GEN_LORA_BANK=q_proj,v_proj (or all): CSM-1B random init, 16 random r = 8 adapters with non-zero B.  For B = 4, 8, 16
-    (GEN_BANK_SIZES): (a) one adapter per utterance - distinct adapters, every fourth row without; (b) the same batch without
-    adapters; (c) the utterances one at a time, each with its adapter live as model.lora (today's only option; its aggregate
-    frames/s is the one-utterance rate whatever B).  Alternated in one process, GEN_ROUNDS rounds, best of each."""
+def _random_bank(model, mods, dev, n=16):
+    """``n`` random r = 8 adapters of ``model`` with non-zero B (lora_bank_main's)."""
     from csm.training.lora import LoRAState
-    dev = "cuda:0"
-    mods = ["q_proj", "k_proj", "v_proj", "output_proj", "w1", "w2", "w3"] if mods == "all" else mods.split(",")
-    model = Model(csm_1b_args(), device=dev, seed=0)
     bank = []
-    for s in range(16):
+    for s in range(n):
         st = LoRAState(model, 8, 16.0, 0.0, mods, None, False, seed=s, grad=False)
         with torch.no_grad():
             gb = torch.Generator(device=dev).manual_seed(100 + s)
             for ad in st.adapters.values():
                 ad.B[:, :8].copy_((torch.randn(ad.B.shape[0], 8, generator=gb, device=dev) * 0.02).to(torch.bfloat16))
         bank.append(st)
+    return bank
+
+
+def lora_bank_main(mods):
+    """GEN_LORA_BANK=q_proj,v_proj (or all): CSM-1B random init, 16 random r = 8 adapters with non-zero B.  For B = 4, 8, 16
+    (GEN_BANK_SIZES): (a) one adapter per utterance - distinct adapters, every fourth row without; (b) the same batch without
+    adapters; (c) the utterances one at a time, each with its adapter live as model.lora (today's only option; its aggregate
+    frames/s is the one-utterance rate whatever B).  Alternated in one process, GEN_ROUNDS rounds, best of each."""
+    dev = "cuda:0"
+    mods = ["q_proj", "k_proj", "v_proj", "output_proj", "w1", "w2", "w3"] if mods == "all" else mods.split(",")
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    bank = _random_bank(model, mods, dev)
     frames = int(os.environ.get("GEN_FRAMES", 50))
     sizes = [int(v) for v in os.environ.get("GEN_BANK_SIZES", "4,8,16").split(",")]
     rounds = int(os.environ.get("GEN_ROUNDS", 2))
@@ -250,6 +257,39 @@ def lora_bank_main(mods):
         print(f"GEN_LORA_BANK B={B:2d}: (a) per-row adapters {[round(x, 1) for x in res[('bank', B)]]} (b) no adapters "
               f"{[round(x, 1) for x in res[('none', B)]]} frames/s aggregate -> best (a) {a:.1f} / (b) {b:.1f} = {a / b:.3f}x; "
               f"(a) / (c) = {a / live1:.2f}x", flush=True)
+
+
+def fp8_bank_main(mods):
+    """GEN_FP8=1 GEN_LORA_BANK=q_proj,v_proj (or all): CSM-1B random init, 16 random r = 8 adapters (GEN_LORA_BANK's bank and
+    rows: distinct adapters, every fourth row without).  Decode-loop frames/s (captured graph) of four legs on ONE model,
+    alternated in one process - bf16 + bank, FP8 + bank (model.fp8_adapters), FP8 without adapters, bf16 without adapters - at
+    B = GEN_BANK_SIZES (default 4,8,16), GEN_ROUNDS alternated repeats (default 3), best of each."""
+    dev = "cuda:0"
+    mods = ["q_proj", "k_proj", "v_proj", "output_proj", "w1", "w2", "w3"] if mods == "all" else mods.split(",")
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    bank = _random_bank(model, mods, dev)
+    model.fp8_adapters = True
+    frames = int(os.environ.get("GEN_FRAMES", 50))
+    sizes = [int(v) for v in os.environ.get("GEN_BANK_SIZES", "4,8,16").split(",")]
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    legs = (("bf16+bank", "bf16", True), ("fp8+bank", "fp8", True), ("fp8", "fp8", False), ("bf16", "bf16", False))
+    res = {}
+    for _ in range(rounds):
+        for B in sizes:
+            rows = [None if b % 4 == 3 else bank[b] for b in range(B)]
+            for name, mode, banked in legs:
+                model.decode_weights = mode
+                res.setdefault((name, B), []).append(decode_fps_batch(model, B, rows if banked else None, frames))
+                st = model._decode_state
+                assert (st.bb.w8 is not None) == (mode == "fp8") and (st.bb.lora_rows is not None) == banked
+    model.decode_weights = "bf16"
+    print(f"GEN_FP8 + GEN_LORA_BANK {','.join(mods)} r=8, 16 adapters, {frames} frames, {rounds} alternated repeats (best of each)", flush=True)
+    for B in sizes:
+        best = {name: max(res[(name, B)]) for name, _, _ in legs}
+        print(f"GEN_FP8_BANK B={B:2d}: " + " ".join(f"{name} {[round(x, 1) for x in res[(name, B)]]}" for name, _, _ in legs) +
+              f" frames/s aggregate -> best fp8+bank {best['fp8+bank']:.1f} / bf16+bank {best['bf16+bank']:.1f} = "
+              f"{best['fp8+bank'] / best['bf16+bank']:.3f}x; fp8+bank / fp8 = {best['fp8+bank'] / best['fp8']:.3f}x; "
+              f"bf16+bank / bf16 = {best['bf16+bank'] / best['bf16']:.3f}x; fp8 / bf16 = {best['fp8'] / best['bf16']:.3f}x", flush=True)
 
 
 def fp8_main():
@@ -1424,6 +1464,8 @@ def main():
         return conversation_main()
     if os.environ.get("GEN_BATCH_SWEEP") == "1":
         return sweep_main()
+    if os.environ.get("GEN_FP8") == "1" and os.environ.get("GEN_LORA_BANK"):
+        return fp8_bank_main(os.environ["GEN_LORA_BANK"])
     if os.environ.get("GEN_FP8") == "1":
         return fp8_main()
     if os.environ.get("GEN_LORA_BANK"):
