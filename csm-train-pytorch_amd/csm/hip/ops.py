@@ -479,16 +479,35 @@ def gemv(x, W, y, residual=None):
     return y
 
 
-def gemv_ex(x, W, y, residual=None, norm_scale=None, eps=1e-5, swiglu=False, row_index=None, row_offset=0):
-    """gemv with an RMSNorm prologue on x (norm_scale), the SwiGLU pairing of interleaved gate/up rows (y is [B, N/2]) and /
-    or x gathered from a table: batch row b = x[row_index[b] + row_offset] (row_index int32 [B] on the device).  B <= 16 as
-    for ``gemv`` (every fusion on both kernel families)."""
+def _gemv_dims(x, W, y, swiglu, row_index):
+    """(B, N, K) of an extended or fused decode product, after the asserts its wrappers share: the shapes (y is [B, N/2] under
+    SwiGLU), unit inner strides and the ``row_index`` gather."""
     B = y.shape[0]
     K = x.shape[1]
     N = W.shape[0]
     assert W.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W.stride(1) == 1 and y.stride(1) == 1
     assert row_index is not None or x.shape[0] == B
     assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
+    return B, N, K
+
+
+def _ext_rows_args(B, ext_t, Bx_tab, bias_tab, row_adapter, kx, ldb):
+    """The trailing arguments of the ``*_kext_rows`` entry points (extension operand, adapter tables, stream), after the
+    asserts on them."""
+    A = Bx_tab.numel()
+    assert ext_t.shape[0] == B and ext_t.shape[1] >= kx and ext_t.stride(1) == 1 and ext_t.dtype == BF16
+    assert Bx_tab.dtype == torch.int64 and Bx_tab.is_contiguous() and Bx_tab.is_cuda
+    assert bias_tab is None or (bias_tab.dtype == torch.int64 and bias_tab.numel() == A and bias_tab.is_contiguous() and bias_tab.is_cuda)
+    assert row_adapter.dtype == torch.int32 and row_adapter.numel() == B and row_adapter.is_contiguous() and row_adapter.is_cuda
+    return (ext_t.data_ptr(), Bx_tab.data_ptr(), _ptr(bias_tab), row_adapter.data_ptr(), A, int(kx), ext_t.stride(0), int(ldb),
+            _stream())
+
+
+def gemv_ex(x, W, y, residual=None, norm_scale=None, eps=1e-5, swiglu=False, row_index=None, row_offset=0):
+    """gemv with an RMSNorm prologue on x (norm_scale), the SwiGLU pairing of interleaved gate/up rows (y is [B, N/2]) and /
+    or x gathered from a table: batch row b = x[row_index[b] + row_offset] (row_index int32 [B] on the device).  B <= 16 as
+    for ``gemv`` (every fusion on both kernel families)."""
+    B, N, K = _gemv_dims(x, W, y, swiglu, row_index)
     check(lib.csm_gemv_bf16_ex(x.data_ptr(), W.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K, W.stride(0), x.stride(0),
                                y.stride(0), int(y.dtype == torch.float32), _ptr(norm_scale), float(eps), int(swiglu),
                                _ptr(row_index), int(row_offset), _stream()), "csm_gemv_bf16_ex")
@@ -515,13 +534,8 @@ def gemv_fp8w(x, W8, scale, y, residual=None, norm_scale=None, eps=1e-5, swiglu=
     """``gemv_ex`` with e4m3 weights and one fp32 scale per output row (``quantize_rows_fp8``): y[b][n] = epilogue(scale[n] *
     sum_k x^[b][k] q[n][k]), bf16 activations, fp32 products and sum, the scale applied once after the reduction.  Same fusions,
     same B <= 16 and the same bit-level invariants as the bf16 products; K % 16 == 0, 16-byte aligned weight rows."""
-    B = y.shape[0]
-    K = x.shape[1]
-    N = W8.shape[0]
+    B, N, K = _gemv_dims(x, W8, y, swiglu, row_index)
     assert W8.dtype == torch.uint8 and scale.dtype == torch.float32 and scale.numel() == N and scale.is_contiguous() and x.dtype == BF16
-    assert W8.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W8.stride(1) == 1 and y.stride(1) == 1
-    assert row_index is not None or x.shape[0] == B
-    assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
     check(lib.csm_gemv_fp8w(x.data_ptr(), W8.data_ptr(), scale.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K, W8.stride(0),
                             x.stride(0), y.stride(0), int(y.dtype == torch.float32), _ptr(norm_scale), float(eps), int(swiglu),
                             _ptr(row_index), int(row_offset), _stream()), "csm_gemv_fp8w")
@@ -534,23 +548,12 @@ def gemv_fp8w_kext_rows(x, W8, scale, y, ext_t, Bx_tab, row_adapter, kx, ldb, re
     base): y = epilogue(scale[n] * x^ q^T + ext_t[b] Bx[a]^T + bias[a]) - the scale on the base sum only, the extension added in
     fp32 after it.  Tables as for ``gemv_kext_rows``.  B = 1..16: B <= 4 row b is the bits of the one-row launch with adapter a;
     5..16 a row's bits depend on its own operands only; a row without adapter is the plain ``gemv_fp8w`` at the same B."""
-    B = y.shape[0]
-    K = x.shape[1]
-    N = W8.shape[0]
-    A = Bx_tab.numel()
+    B, N, K = _gemv_dims(x, W8, y, swiglu, row_index)
     assert W8.dtype == torch.uint8 and scale.dtype == torch.float32 and scale.numel() == N and scale.is_contiguous() and x.dtype == BF16
-    assert W8.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W8.stride(1) == 1 and y.stride(1) == 1
-    assert row_index is not None or x.shape[0] == B
-    assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
-    assert ext_t.shape[0] == B and ext_t.shape[1] >= kx and ext_t.stride(1) == 1 and ext_t.dtype == BF16
-    assert Bx_tab.dtype == torch.int64 and Bx_tab.is_contiguous() and Bx_tab.is_cuda
-    assert bias_tab is None or (bias_tab.dtype == torch.int64 and bias_tab.numel() == A and bias_tab.is_contiguous() and bias_tab.is_cuda)
-    assert row_adapter.dtype == torch.int32 and row_adapter.numel() == B and row_adapter.is_contiguous() and row_adapter.is_cuda
     check(lib.csm_gemv_fp8w_kext_rows(x.data_ptr(), W8.data_ptr(), scale.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K,
                                       W8.stride(0), x.stride(0), y.stride(0), int(y.dtype == torch.float32), _ptr(norm_scale),
-                                      float(eps), int(swiglu), _ptr(row_index), int(row_offset), ext_t.data_ptr(), Bx_tab.data_ptr(),
-                                      _ptr(bias_tab), row_adapter.data_ptr(), A, int(kx), ext_t.stride(0), int(ldb), _stream()),
-          "csm_gemv_fp8w_kext_rows")
+                                      float(eps), int(swiglu), _ptr(row_index), int(row_offset),
+                                      *_ext_rows_args(B, ext_t, Bx_tab, bias_tab, row_adapter, kx, ldb)), "csm_gemv_fp8w_kext_rows")
     return y
 
 def lora_project(x, At, t, scale, norm_scale=None, eps=1e-5):
@@ -569,13 +572,8 @@ def gemv_kext(x, W, y, ext_t, ext_B, residual=None, norm_scale=None, eps=1e-5, s
               bias=None):
     """``gemv_ex`` with a LoRA group as K-extension: y = epilogue(x^ W^T + ext_t ext_B^T + bias).  ext_t [B, kx] from
     ``lora_project``; ext_B [N, kx] and bias [N] in W's row order."""
-    B = y.shape[0]
-    K = x.shape[1]
-    N = W.shape[0]
+    B, N, K = _gemv_dims(x, W, y, swiglu, row_index)
     kx = ext_B.shape[1]
-    assert W.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W.stride(1) == 1 and y.stride(1) == 1
-    assert row_index is not None or x.shape[0] == B
-    assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
     assert ext_t.shape == (B, kx) and ext_B.shape[0] == N and ext_t.stride(1) == 1 and ext_B.stride(1) == 1
     assert bias is None or (bias.shape == (N,) and bias.is_contiguous() and bias.dtype == BF16)
     check(lib.csm_gemv_bf16_kext(x.data_ptr(), W.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K, W.stride(0), x.stride(0),
@@ -608,22 +606,11 @@ def gemv_kext_rows(x, W, y, ext_t, Bx_tab, row_adapter, kx, ldb, residual=None, 
     ``Bx_tab`` / ``bias_tab`` int64 [A]: device addresses of each adapter's Bx [N, ldb] (W's row order) and bias [N] (0 = none;
     ``bias_tab`` None = no adapter has one).  B = 1..16: B <= 4 row b is the bits of a one-row ``gemv_kext`` with adapter a; 5..16
     a row's bits depend on its own operands only; a row without adapter is the plain ``gemv_ex`` at the same B."""
-    B = y.shape[0]
-    K = x.shape[1]
-    N = W.shape[0]
-    A = Bx_tab.numel()
-    assert W.shape[1] == K and y.shape == (B, N // 2 if swiglu else N) and x.stride(1) == 1 and W.stride(1) == 1 and y.stride(1) == 1
-    assert row_index is not None or x.shape[0] == B
-    assert row_index is None or (row_index.dtype == torch.int32 and row_index.numel() == B and row_index.is_contiguous())
-    assert ext_t.shape[0] == B and ext_t.shape[1] >= kx and ext_t.stride(1) == 1 and ext_t.dtype == BF16
-    assert Bx_tab.dtype == torch.int64 and Bx_tab.is_contiguous() and Bx_tab.is_cuda
-    assert bias_tab is None or (bias_tab.dtype == torch.int64 and bias_tab.numel() == A and bias_tab.is_contiguous() and bias_tab.is_cuda)
-    assert row_adapter.dtype == torch.int32 and row_adapter.numel() == B and row_adapter.is_contiguous() and row_adapter.is_cuda
+    B, N, K = _gemv_dims(x, W, y, swiglu, row_index)
     check(lib.csm_gemv_bf16_kext_rows(x.data_ptr(), W.data_ptr(), y.data_ptr(), _ptr(residual), B, N, K, W.stride(0), x.stride(0),
                                       y.stride(0), int(y.dtype == torch.float32), _ptr(norm_scale), float(eps), int(swiglu),
-                                      _ptr(row_index), int(row_offset), ext_t.data_ptr(), Bx_tab.data_ptr(), _ptr(bias_tab),
-                                      row_adapter.data_ptr(), A, int(kx), ext_t.stride(0), int(ldb), _stream()),
-          "csm_gemv_bf16_kext_rows")
+                                      _ptr(row_index), int(row_offset),
+                                      *_ext_rows_args(B, ext_t, Bx_tab, bias_tab, row_adapter, kx, ldb)), "csm_gemv_bf16_kext_rows")
     return y
 
 

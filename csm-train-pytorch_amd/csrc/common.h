@@ -85,6 +85,17 @@ __device__ __forceinline__ float wave_sum(float v) {       // the butterfly of `
     return v;
 }
 
+// Two wave sums in ONE butterfly (a SwiGLU pair's gate and up partials in the decode products): v_permlane32_swap(a0, a1) leaves
+// the a0 partials in lanes 0-31 and the a1 partials in lanes 32-63, each already added to its xor-32 partner; xor 16 .. 1 then
+// stay inside the halves.  s0 / s1 are wave_sum(a0) / wave_sum(a1) bit for bit, for the price of one.
+__device__ __forceinline__ void wave_sum2(float a0, float a1, float& s0, float& s1) {
+    auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
+    float t = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+    t += lane_xor<16>(t); t += lane_xor<8>(t); t += lane_xor<4>(t); t += lane_xor<2>(t); t += lane_xor<1>(t);
+    s0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
+    s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+}
+
 __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, lane_xor<32>(v)); v = fmaxf(v, lane_xor<16>(v)); v = fmaxf(v, lane_xor<8>(v));
     v = fmaxf(v, lane_xor<4>(v)); v = fmaxf(v, lane_xor<2>(v)); v = fmaxf(v, lane_xor<1>(v));

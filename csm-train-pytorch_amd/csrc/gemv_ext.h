@@ -63,4 +63,18 @@ __device__ __forceinline__ float ext_dot(float v, const bf16_t* __restrict__ bx,
     return v;
 }
 
+// host: the checks of a per-row extension's arguments, shared by the *_kext_rows entry points (`entry`: the caller's name, for the
+// message); fills e
+static inline int ext_rows_check(const char* entry, GemvExtRows& e, int B, const void* ext_t, const void* const* ext_B,
+                                 const void* const* bias, const int* row_adapter, int n_adapters, int kx, int ld_ext_t, int ld_ext_B) {
+    CSM_REQUIRE(B >= 1 && B <= 16, "%s: B=%d: the per-row K-extension takes 1 to 16 batch rows", entry, B);
+    CSM_REQUIRE(ext_t && ext_B && row_adapter && n_adapters >= 1 && kx > 0 && kx <= 512 && (kx & 7) == 0 && ld_ext_t >= kx &&
+                ld_ext_B >= kx && (ld_ext_t & 7) == 0 && (ld_ext_B & 7) == 0 && ((uintptr_t)ext_t & 15) == 0,
+                "%s: bad extension (adapters=%d kx=%d ld_t=%d ld_B=%d: needs kx <= 512, multiples of 8, 16-byte aligned rows)",
+                entry, n_adapters, kx, ld_ext_t, ld_ext_B);
+    e.t = (const bf16_t*)ext_t; e.Bx = (const bf16_t* const*)ext_B; e.bias = (const bf16_t* const*)bias;
+    e.row_adapter = row_adapter; e.nad = n_adapters; e.kx = kx; e.ldt = ld_ext_t; e.ldb = ld_ext_B;
+    return 0;
+}
+
 }  // namespace

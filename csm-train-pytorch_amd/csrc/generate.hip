@@ -2,6 +2,7 @@
 // split residual vector quantiser (nearest-codeword encode, codebook-sum decode).
 #include "common.h"
 #include "gemv_ext.h"
+#include "gemv_mfma.h"
 #include <math.h>
 
 namespace {
@@ -605,7 +606,8 @@ extern "C" int csm_rvq_decode(const long long* codes, const float* codebooks, fl
 namespace {
 
 // (the K-extension of these products - GemvExt, GemvExtRows, ExtKind, ext_load / ext_fma / ext_dot - is gemv_ext.h: quant.hip's
-//  FP8 families take the same packs)
+//  FP8 families take the same packs; the B = 5..16 product, gemv_mfma_kernel and its launcher, is gemv_mfma.h: one kernel for both
+//  weight formats)
 
 // y[b][n] = sum_k x[b][k] * W[n][k] (+ R[b][n]);  one wave per output row, NB <= 4 batch rows share every weight load.
 // Two optional fusions remove the tiny kernels that otherwise sit between the matrix-vector products of a decode step:
@@ -874,12 +876,8 @@ __global__ __launch_bounds__(256) void gemv_reg_kernel(const bf16_t* __restrict_
     for (int o = 0; o < RPW; ++o) {
         float v;
         if constexpr (SWIGLU) {
-            // both row sums in one butterfly: gate partials to lanes 0-31, up partials to lanes 32-63, then xor 16 .. 1 inside the halves
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[o][0]), __float_as_uint(acc[o][1]), false, false);
-            float t = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-            t += lane_xor<16>(t); t += lane_xor<8>(t); t += lane_xor<4>(t); t += lane_xor<2>(t); t += lane_xor<1>(t);
-            float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
-            float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+            float gs, us;
+            wave_sum2(acc[o][0], acc[o][1], gs, us);             // both row sums in one butterfly
             if constexpr (EXT) { gs += bias[o][0]; us += bias[o][1]; }
             if constexpr (EK == 2) { if (ron) { gs += bias[o][0]; us += bias[o][1]; } }
             const float g = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
@@ -1051,11 +1049,8 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
             float a1 = (b & 1) ? acc[1][b >> 1].y : acc[1][b >> 1].x;
             if constexpr (EXT) a1 = ext_fma(a1, eb[1], et);
             if constexpr (EK == 2) { if (ron) a1 = ext_fma(a1, eb[1], et); }
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
-            float t = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-            t += lane_xor<16>(t); t += lane_xor<8>(t); t += lane_xor<4>(t); t += lane_xor<2>(t); t += lane_xor<1>(t);
-            float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0));
-            float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32));
+            float gs, us;
+            wave_sum2(a0, a1, gs, us);
             if constexpr (EXT) { gs += bias[0]; us += bias[1]; }
             if constexpr (EK == 2) { if (ron) { gs += rb[0]; us += rb[1]; } }
             const float g = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
@@ -1073,161 +1068,8 @@ __global__ __launch_bounds__(256) void gemv_regn_kernel(const bf16_t* __restrict
     }
 }
 
-// Five to sixteen batch rows (generate_batch at B > 4): the product as MFMA tiles, D[n][b] = sum_k W[n][k] x^[b][k] with
-// v_mfma_f32_16x16x32_bf16, A = 16 weight rows, B = x^ transposed with the batch rows padded to 16 by zeros (never stored).
-// A workgroup owns one tile of 16 weight rows (8 gate/up pairs under SWIGLU) and its eight waves split K: wave w takes the
-// 64-k steps s = w, w + 8, w + 16, ...  In a step lane l (column c = l & 15, k group g = l >> 4) loads 32 contiguous bytes of
-// weight row n0 + c at k = 64 s + 16 g - two loads, so the four lanes of a row fetch its whole 128-byte line - and uses the first
-// and the second 16 bytes as the fragments of two MFMAs.  The fragment's k order is thereby permuted (element j of group g is
-// k = 16 g + j, resp. 16 g + 8 + j): the B fragment is loaded with the same permutation, x^[c][64 s + 16 g ..], straight from
-// global memory (x is a few KB, L2 resident).  No LDS copy of x: every element of x^ is multiplied by exactly one wave of the
-// workgroup, so staging it would add a round trip and a barrier and save nothing.  Weights go global -> VGPRs, a segment of
-// SEG steps in flight per lane before the first MFMA waits for them (non-temporal under the g_gemv_nt policy).
-// RMSNorm prologue: the workgroup's waves compute rstd of the batch rows with gemv_kernel's order (lane-strided 8-element
-// chunks, wave_sum) behind one barrier that keeps the weight loads in flight; x^ = bf16(x rstd w) as gemv_regn_kernel rounds it.
-// The eight partial tiles meet in LDS and are summed in wave order 0..7 (no atomics).  Every output column sees only its own
-// batch row's operands in an order fixed by K, so a row's result is the same bits for any B in 5..16, any position of the row in
-// the batch and any contents of the other rows (tests/test_generate_wide_batch_gpu.py).  It is not bit-equal to the B <= 4
-// kernels, which sum in another order.
-// Trailing pack (empty: the plain product, or one GemvExtRows): the epilogue thread of output (n, b) adds row b's own adapter's
-// extension sum_j t[b][j] Bx[a_b][n][j] to the wave-ordered sum, one fmaf per j in ascending j (then the adapter's bias), before
-// the rounding / SwiGLU / residual epilogue.  It reads only row b's operands, so a row keeps its bits for any B in 5..16, any
-// position and any batch-mates and their adapters; a row without adapter takes no extension: the plain product's bits.
-template <int SEG, typename OutT, bool SWIGLU, bool NT, typename... Ext>
-__global__ __launch_bounds__(512) void gemv_mfma_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, OutT* __restrict__ y,
-                                                        const bf16_t* __restrict__ R, int B, int N, int K, int ldw, int ldx, int ldy,
-                                                        const bf16_t* __restrict__ norm_w, float eps, const int* __restrict__ row_index,
-                                                        int row_offset, Ext... ext) {
-    constexpr int EK = ExtKind<Ext...>::v;
-    static_assert(EK != 1, "gemv_mfma_kernel takes the per-row extension only");
-    constexpr int NW = 8;
-    __shared__ float rs[16];
-    __shared__ float part[NW][16][17];                        // [wave][weight row of the tile][batch row] (+1: no bank conflicts)
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int g = lane >> 4, c = lane & 15;
-    const int n0 = blockIdx.x * 16;
-    const int S = (K + 63) >> 6;                              // 64-k steps; with K % 64 == 32 the last one has groups 0, 1 only
-    const bf16_t* wrow = W + (size_t)min(n0 + c, N - 1) * ldw + 16 * g;       // (rows past N re-read row N-1, never stored)
-    const bool brow = c < B;
-    const size_t xr = brow ? (row_index ? (size_t)(row_index[c] + row_offset) : (size_t)c) : (size_t)0;
-    const bf16_t* xrow = x + xr * ldx + 16 * g;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int nseg = (S + NW * SEG - 1) / (NW * SEG);
-    for (int sg = 0; sg < nseg; ++sg) {
-        U4 wq[SEG][2], xq[SEG][2];
-        const U4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < SEG; ++i) {
-            const int s = (sg * SEG + i) * NW + wv;
-            const int k = 64 * s + 16 * g;
-            wq[i][0] = z; wq[i][1] = z;
-            if (s < S && k < K) {
-                const U4* p = reinterpret_cast<const U4*>(wrow + 64 * s);
-                wq[i][0] = NT ? __builtin_nontemporal_load(p) : p[0];
-                wq[i][1] = NT ? __builtin_nontemporal_load(p + 1) : p[1];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SEG; ++i) {
-            const int s = (sg * SEG + i) * NW + wv;
-            const int k = 64 * s + 16 * g;
-            xq[i][0] = z; xq[i][1] = z;
-            if (brow && s < S && k < K) {
-                const U4* p = reinterpret_cast<const U4*>(xrow + 64 * s);
-                xq[i][0] = p[0]; xq[i][1] = p[1];
-            }
-        }
-        if (norm_w) {
-            if (sg == 0) {
-                // rstd of batch rows wv, wv + 8 (gemv_kernel's summation order); one barrier, LDS only: the weights stay in flight
-                for (int b = wv; b < B; b += NW) {
-                    const bf16_t* xb = x + (row_index ? (size_t)(row_index[b] + row_offset) : (size_t)b) * ldx;
-                    float ss = 0.f;
-                    for (int q = lane; q < (K >> 3); q += 64) {
-                        float f[8];
-                        unpack8(*reinterpret_cast<const U4*>(xb + q * 8), f);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) ss += f[j] * f[j];
-                    }
-                    ss = wave_sum(ss);
-                    if (lane == 0) rs[b] = rsqrtf(ss / (float)K + eps);
-                }
-                lds_barrier();
-            }
-            if (brow) {
-                const float r = rs[c];
-#pragma unroll
-                for (int i = 0; i < SEG; ++i) {
-                    const int s = (sg * SEG + i) * NW + wv;
-                    const int k = 64 * s + 16 * g;
-                    if (s < S && k < K) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            float f[8], w8[8];
-                            unpack8(xq[i][h], f);
-                            unpack8(*reinterpret_cast<const U4*>(norm_w + k + 8 * h), w8);
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) f[j] = f[j] * r * w8[j];
-                            xq[i][h] = pack8(f);                      // the bf16 rounding of gemv_regn_kernel's x^
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SEG; ++i) {
-            const int s = (sg * SEG + i) * NW + wv;
-            if (s < S) {                                              // (wave-uniform)
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wq[i][0]), __builtin_bit_cast(bf16x8, xq[i][0]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wq[i][1]), __builtin_bit_cast(bf16x8, xq[i][1]), acc, 0, 0, 0);
-            }
-        }
-    }
-    // lane holds D[weight row 4 g + r][batch row c]; the eight K slices are added in wave order
-#pragma unroll
-    for (int r = 0; r < 4; ++r) part[wv][4 * g + r][c] = acc[r];
-    __syncthreads();
-    const int t = threadIdx.x;
-    if constexpr (SWIGLU) {
-        const int i = t & 7, b = t >> 3;                      // output n0 / 2 + i of batch row b: gate row 2 i, up row 2 i + 1
-        if (b < B && n0 + 2 * i < N) {
-            float gs = part[0][2 * i][b], us = part[0][2 * i + 1][b];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) { gs += part[w][2 * i][b]; us += part[w][2 * i + 1][b]; }
-            if constexpr (EK == 2) {
-                const GemvExtRows& e = ext_rows_arg(ext...);
-                const int a = ext_row_adapter(e, b);
-                if (a >= 0) {
-                    gs = ext_dot(gs, e.Bx[a] + (size_t)(n0 + 2 * i) * e.ldb, e.t + (size_t)b * e.ldt, e.kx);
-                    us = ext_dot(us, e.Bx[a] + (size_t)(n0 + 2 * i + 1) * e.ldb, e.t + (size_t)b * e.ldt, e.kx);
-                    gs += ext_row_bias(e, a, n0 + 2 * i);
-                    us += ext_row_bias(e, a, n0 + 2 * i + 1);
-                }
-            }
-            const float gg = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
-            float v = silu(gg) * u;
-            const int n = (n0 >> 1) + i;
-            if (R) v += bf2f(R[(size_t)b * ldy + n]);
-            y[(size_t)b * ldy + n] = f2bf(v);
-        }
-    } else {
-        const int rr = t & 15, b = t >> 4;
-        const int n = n0 + rr;
-        if (b < B && n < N) {
-            float v = part[0][rr][b];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) v += part[w][rr][b];
-            if constexpr (EK == 2) {
-                const GemvExtRows& e = ext_rows_arg(ext...);
-                const int a = ext_row_adapter(e, b);
-                if (a >= 0) v = ext_dot(v, e.Bx[a] + (size_t)n * e.ldb, e.t + (size_t)b * e.ldt, e.kx) + ext_row_bias(e, a, n);
-            }
-            if (R) v += bf2f(R[(size_t)b * ldy + n]);
-            if constexpr (sizeof(OutT) == 2) y[(size_t)b * ldy + n] = f2bf(v);
-            else y[(size_t)b * ldy + n] = v;
-        }
-    }
-}
+// Five to sixteen batch rows (generate_batch at B > 4): gemv_mfma_kernel<WeightBf16, ...> of gemv_mfma.h - the MFMA product that the
+// FP8 decode (quant.hip) instantiates with its own weight format.
 
 // y[b][n] = sum_k x[b][k] * W[k][n]  (weights stored K-major, e.g. audio_head[i] = [d'][V]): a thread owns 8 columns.
 template <int NB, typename OutT>
@@ -2081,28 +1923,6 @@ extern "C" int csm_set_decode_tuning(int key, int value) {
     else if (key == 3) g_gemv_regn = value; else if (key == 4) g_gemv_mfma_small = value; else return 1;
     return 0;
 }
-// B = 5..16 (or 2..4 under g_gemv_mfma_small): gemv_mfma_kernel, one workgroup per 16 weight rows; SEG = 64-k steps per wave
-// and segment, sized so that K <= 2048 runs as one segment (K = 8192: two of eight steps)
-template <typename... Ext>
-static int gemv_mfma_launch(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx,
-                            int ldy, int out_f32, const void* norm_w, float eps, int swiglu, const int* row_index, int row_offset,
-                            hipStream_t stream, Ext... ext) {
-    CSM_REQUIRE((K & 31) == 0, "csm_gemv_bf16: B=%d needs K %% 32 == 0 (K=%d)", B, K);
-    const int grid = (N + 15) / 16;
-    const int spw = ((K + 63) / 64 + 7) / 8;                  // 64-k steps per wave
-    const bool nt = g_gemv_nt && (K == 2048 || (K == 8192 && N == 2048));
-#define LM(SEG, T, SW, NT_) hipLaunchKernelGGL((gemv_mfma_kernel<SEG, T, SW, NT_, Ext...>), dim3(grid), dim3(512), 0, stream, (const bf16_t*)x, (const bf16_t*)W, (T*)y, (const bf16_t*)residual, B, N, K, ldw, ldx, ldy, (const bf16_t*)norm_w, eps, row_index, row_offset, ext...)
-#define LMS(T, SW, NT_) do { if (spw <= 1) LM(1, T, SW, NT_); else if (spw <= 2) LM(2, T, SW, NT_); else if (spw <= 4) LM(4, T, SW, NT_); else LM(8, T, SW, NT_); } while (0)
-    if (swiglu) { if (nt) LMS(bf16_t, true, true); else LMS(bf16_t, true, false); }
-    else if (out_f32) { if (nt) LMS(float, false, true); else LMS(float, false, false); }
-    else { if (nt) LMS(bf16_t, false, true); else LMS(bf16_t, false, false); }
-#undef LMS
-#undef LM
-    gemv_note("gemv_mfma_kernel<%d, %s, %d, %d, ext%d>", spw <= 1 ? 1 : (spw <= 2 ? 2 : (spw <= 4 ? 4 : 8)),
-              (out_f32 && !swiglu) ? "float" : "bf16", swiglu ? 1 : 0, nt ? 1 : 0, ExtKind<Ext...>::v);
-    CSM_CHECK_LAUNCH("csm_gemv_bf16");
-    return 0;
-}
 // ext: empty (the plain products) or one GemvExt (csm_gemv_bf16_kext): the same dispatch, the kernels' trailing pack
 template <typename... Ext>
 static int gemv_launch(const void* x, const void* W, void* y, const void* residual, int B, int N, int K, int ldw, int ldx, int ldy,
@@ -2112,9 +1932,11 @@ static int gemv_launch(const void* x, const void* W, void* y, const void* residu
                 "csm_gemv_bf16: bad arguments (B=%d N=%d K=%d: needs 1 <= B <= 16)", B, N, K);
     CSM_REQUIRE(!swiglu || ((N & 1) == 0 && !out_f32), "csm_gemv_bf16_ex: the SwiGLU form needs an even N and bf16 output");
     if constexpr (ExtKind<Ext...>::v != 1) {             // (the plain products and the per-row extension dispatch alike)
-        if (B > 4 || (B >= 2 && g_gemv_mfma_small && (K & 31) == 0))
-            return gemv_mfma_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_w, eps, swiglu, row_index, row_offset, stream,
-                                    ext...);
+        if (B > 4 || (B >= 2 && g_gemv_mfma_small && (K & 31) == 0)) {   // gemv_mfma.h
+            const bool nt = g_gemv_nt && (K == 2048 || (K == 8192 && N == 2048));
+            return gemv_mfma_launch<WeightBf16>({(const bf16_t*)W}, x, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_w, eps, swiglu, row_index,
+                                                row_offset, nt, stream, ext...);
+        }
     } else {
         CSM_REQUIRE(B <= 4, "csm_gemv_bf16_kext: B=%d: the K-extension (live LoRA adapters) takes at most 4 batch rows", B);
     }
@@ -2216,14 +2038,8 @@ extern "C" int csm_gemv_bf16_kext_rows(const void* x, const void* W, void* y, co
                                        const int* row_index, int row_offset, const void* ext_t, const void* const* ext_B,
                                        const void* const* bias, const int* row_adapter, int n_adapters, int kx, int ld_ext_t,
                                        int ld_ext_B, hipStream_t stream) {
-    CSM_REQUIRE(B >= 1 && B <= 16, "csm_gemv_bf16_kext_rows: B=%d: the per-row K-extension takes 1 to 16 batch rows", B);
-    CSM_REQUIRE(ext_t && ext_B && row_adapter && n_adapters >= 1 && kx > 0 && kx <= 512 && (kx & 7) == 0 && ld_ext_t >= kx &&
-                ld_ext_B >= kx && (ld_ext_t & 7) == 0 && (ld_ext_B & 7) == 0 && ((uintptr_t)ext_t & 15) == 0,
-                "csm_gemv_bf16_kext_rows: bad extension (adapters=%d kx=%d ld_t=%d ld_B=%d: needs kx <= 512, multiples of 8, "
-                "16-byte aligned rows)", n_adapters, kx, ld_ext_t, ld_ext_B);
     GemvExtRows e;
-    e.t = (const bf16_t*)ext_t; e.Bx = (const bf16_t* const*)ext_B; e.bias = (const bf16_t* const*)bias;
-    e.row_adapter = row_adapter; e.nad = n_adapters; e.kx = kx; e.ldt = ld_ext_t; e.ldb = ld_ext_B;
+    if (const int rc = ext_rows_check("csm_gemv_bf16_kext_rows", e, B, ext_t, ext_B, bias, row_adapter, n_adapters, kx, ld_ext_t, ld_ext_B)) return rc;
     return gemv_launch(x, W, y, residual, B, N, K, ldw, ldx, ldy, out_f32, norm_scale, eps, swiglu, row_index, row_offset, stream, e);
 }
 

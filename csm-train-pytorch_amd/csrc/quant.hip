@@ -2,9 +2,9 @@
 // output row - csm_quantize_rows_fp8 makes them, csm_gemv_fp8w multiplies with them.  Activations stay bf16, products and sums
 // are fp32, the scale is applied ONCE to the finished row sum:  y[b][n] = epilogue(scale[n] * sum_k x^[b][k] q[n][k]).
 // e4m3 -> fp32 / bf16 is exact (v_cvt_pk_f32_fp8; a value has four significant bits), so the only rounding the mode adds is
-// the quantiser's.  The kernels mirror the bf16 families of generate.hip (gemv_reg_kernel / gemv_regn_kernel / gemv_mfma_kernel)
+// the quantiser's.  B <= 4: gemv_fp8_kernel below mirrors the bf16 families of generate.hip (gemv_reg_kernel / gemv_regn_kernel)
 // with the weight operand replaced: weights global -> VGPRs in 16-byte loads (16 weights each), no LDS for them, fixed
-// reduction order, no atomics.
+// reduction order, no atomics.  B = 5..16 is no mirror: gemv_mfma.h's one kernel, instantiated with the e4m3 weight format.
 //
 // Per-row K-extension (csm_gemv_fp8w_kext_rows: an un-merged LoRA adapter per batch row on the quantised base; the packs and the
 // extension's operations are gemv_ext.h's, shared with the bf16 families).  Row b with adapter a = row_adapter[b]:
@@ -18,8 +18,8 @@
 //                                        permlane32_swap pairing: gate partials to lanes 0-31, up partials to lanes 32-63, one
 //                                        butterfly for both); v = base + ext.  The base butterfly is untouched: the lane partials
 //                                        of the main loop are never mixed with extension terms.
-//        B = 5..16 (gemv_fp8_mfma_kernel): the epilogue thread of output (n, b) runs ext_dot ONTO base, one fmaf per j in
-//                                        ascending j, as gemv_mfma_kernel does onto its un-scaled sum.
+//        B = 5..16 (gemv_mfma_kernel):   the epilogue thread of output (n, b) runs ext_dot ONTO base, one fmaf per j in
+//                                        ascending j, as the bf16 instantiation does onto its un-scaled sum.
 //   3. v += bias[a][n] (0 where the table or the adapter's entry is NULL), then the existing epilogue: SwiGLU rounds gate and up to
 //      bf16 after extension and bias; residual; bf16 or fp32 store.
 // A row with a = -1 or a >= n_adapters skips 2 and 3 altogether (a wave-uniform branch, not an addition of zero): the bits of
@@ -29,6 +29,7 @@
 // empty pack: their signature, code and bits are what they were.
 #include "common.h"
 #include "gemv_ext.h"
+#include "gemv_mfma.h"
 #include <math.h>
 
 // Every multiply-add below is written out (__builtin_fmaf / elementwise_fma): nothing is left to the compiler's contraction, which
@@ -37,9 +38,7 @@
 
 namespace {
 
-typedef float q_f2 __attribute__((ext_vector_type(2)));
-
-// 16 e4m3 bytes -> 16 fp32 (exact), in byte order
+// 16 e4m3 bytes -> 16 fp32 (exact), in byte order  (q_f2 and cvt8_bf16, the MFMA fragment's conversion: gemv_mfma.h)
 __device__ __forceinline__ void cvt16(const U4& q, float* f) {
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
@@ -47,17 +46,6 @@ __device__ __forceinline__ void cvt16(const U4& q, float* f) {
         const q_f2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[w], true);
         f[4 * w] = lo[0]; f[4 * w + 1] = lo[1]; f[4 * w + 2] = hi[0]; f[4 * w + 3] = hi[1];
     }
-}
-// two e4m3 words (8 bytes) -> one bf16x8 MFMA fragment (exact: the fp32 image's low 16 bits are zero)
-__device__ __forceinline__ bf16x8 cvt8_bf16(uint32_t a, uint32_t b) {
-    const q_f2 a0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a, false), a1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)a, true);
-    const q_f2 b0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, false), b1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b, true);
-    U4 u;
-    u.x = (__float_as_uint(a0[0]) >> 16) | (__float_as_uint(a0[1]) & 0xffff0000u);
-    u.y = (__float_as_uint(a1[0]) >> 16) | (__float_as_uint(a1[1]) & 0xffff0000u);
-    u.z = (__float_as_uint(b0[0]) >> 16) | (__float_as_uint(b0[1]) & 0xffff0000u);
-    u.w = (__float_as_uint(b1[0]) >> 16) | (__float_as_uint(b1[1]) & 0xffff0000u);
-    return __builtin_bit_cast(bf16x8, u);
 }
 
 // ------------------------------------------------------------------------------------------------------------- quantiser
@@ -281,20 +269,17 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(const bf16_t* __restrict_
         if constexpr (SWIGLU) {
             // both row sums in one butterfly (gemv_reg_kernel): gate partials to lanes 0-31, up partials to lanes 32-63
             const float a1 = (b & 1) ? acc[1][b >> 1].y : acc[1][b >> 1].x;
-            auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(a0), __float_as_uint(a1), false, false);
-            float t = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-            t += lane_xor<16>(t); t += lane_xor<8>(t); t += lane_xor<4>(t); t += lane_xor<2>(t); t += lane_xor<1>(t);
-            float gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 0)) * sc[0];
-            float us = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t), 32)) * sc[1];
+            float gs, us;
+            wave_sum2(a0, a1, gs, us);
+            gs *= sc[0];
+            us *= sc[1];
             if constexpr (EK == 2) {
                 if (ron) {
                     // the extension's own butterfly, the same pairing: lane partials from zero, gate to lanes 0-31, up to 32-63
-                    const float e0 = ext_fma(0.f, eb[0][b], et[b]), e1 = ext_fma(0.f, eb[1][b], et[b]);
-                    auto se = __builtin_amdgcn_permlane32_swap(__float_as_uint(e0), __float_as_uint(e1), false, false);
-                    float te = __uint_as_float(se[0]) + __uint_as_float(se[1]);
-                    te += lane_xor<16>(te); te += lane_xor<8>(te); te += lane_xor<4>(te); te += lane_xor<2>(te); te += lane_xor<1>(te);
-                    gs += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(te), 0));
-                    us += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(te), 32));
+                    float ge, ue;
+                    wave_sum2(ext_fma(0.f, eb[0][b], et[b]), ext_fma(0.f, eb[1][b], et[b]), ge, ue);
+                    gs += ge;
+                    us += ue;
                     gs += ebias[0][b];
                     us += ebias[1][b];
                 }
@@ -319,158 +304,15 @@ __global__ __launch_bounds__(256) void gemv_fp8_kernel(const bf16_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------- five to sixteen batch rows
-// The mirror of gemv_mfma_kernel: D[n][b] = sum_k q[n][k] x^[b][k] as v_mfma_f32_16x16x32_bf16 tiles, the e4m3 weight fragments
-// converted to bf16 in registers (exact); a workgroup owns 16 weight rows and its eight waves split K.  The reduction is
-// gemv_mfma_kernel's, element for element: 64-k steps, wave w takes steps w, w + 8, ..., lane l (row c = l & 15, k group
-// g = l >> 4) holds k = 64 s + 16 g .. + 15 - here ONE 16-byte load - whose bytes 0-7 and 8-15 are the fragments of the step's two
-// MFMAs, x^ loaded with the same permutation straight from global memory; the eight partial tiles meet in LDS and are summed in
-// wave order, then scaled by scale[n].  So the product differs from the bf16 product on the dequantised weights by the scale's
-// place only, and not at all where the scale is a power of two (scaling by it commutes with every rounding): FP8 mode and bf16
-// mode then decode the same bits.  The other layout - 128-k steps, 32 bytes per lane, a whole 128-byte line per row as the bf16
-// kernel fetches - was built first and measured 7-21 % faster per product than bf16; it sums in another order, and on weights
-// both modes hold exactly the two modes' sampled codes then drift apart inside a frame ('FP8 weights').
-// An output column sees only its own batch row's operands in an order fixed by K: the same bits for any B in 5..16, any
-// position, any batch-mates.
-// Trailing pack (empty, or one GemvExtRows): the epilogue thread of output (n, b) takes the scaled sum, then - where row b has an
-// adapter - ext_dot onto it (one fmaf per j, ascending j) and the adapter's bias, before the rounding / SwiGLU / residual.
-template <int SEG, typename OutT, bool SWIGLU, bool NT, typename... Ext>
-__global__ __launch_bounds__(512) void gemv_fp8_mfma_kernel(const bf16_t* __restrict__ x, const uint8_t* __restrict__ W8,
-                                                            const float* __restrict__ scale, OutT* __restrict__ y,
-                                                            const bf16_t* __restrict__ R, int B, int N, int K, int ldw8, int ldx,
-                                                            int ldy, const bf16_t* __restrict__ norm_w, float eps,
-                                                            const int* __restrict__ row_index, int row_offset, Ext... ext) {
-    constexpr int EK = ExtKind<Ext...>::v;
-    static_assert(EK != 1, "gemv_fp8_mfma_kernel takes the per-row extension only");
-    constexpr int NW = 8;
-    __shared__ float rs[16];
-    __shared__ float part[NW][16][17];                        // [wave][weight row of the tile][batch row] (+1: no bank conflicts)
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int g = lane >> 4, c = lane & 15;
-    const int n0 = blockIdx.x * 16;
-    const int S = (K + 63) >> 6;                              // 64-k steps (the last one may be partial: K % 16 == 0)
-    const uint8_t* wrow = W8 + (size_t)min(n0 + c, N - 1) * ldw8 + 16 * g;    // (rows past N re-read row N-1, never stored)
-    const bool brow = c < B;
-    const size_t xr = brow ? (row_index ? (size_t)(row_index[c] + row_offset) : (size_t)c) : (size_t)0;
-    const bf16_t* xrow = x + xr * ldx + 16 * g;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int nseg = (S + NW * SEG - 1) / (NW * SEG);
-    for (int sg = 0; sg < nseg; ++sg) {
-        U4 wq[SEG], xq[SEG][2];
-        const U4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < SEG; ++i) {
-            const int s = (sg * SEG + i) * NW + wv;
-            const int k = 64 * s + 16 * g;
-            wq[i] = z;
-            if (s < S && k < K) {
-                const U4* p = reinterpret_cast<const U4*>(wrow + 64 * s);
-                wq[i] = NT ? __builtin_nontemporal_load(p) : *p;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SEG; ++i) {
-            const int s = (sg * SEG + i) * NW + wv;
-            const int k = 64 * s + 16 * g;
-            xq[i][0] = z; xq[i][1] = z;
-            if (brow && s < S && k < K) {
-                const U4* p = reinterpret_cast<const U4*>(xrow + 64 * s);
-                xq[i][0] = p[0]; xq[i][1] = p[1];
-            }
-        }
-        if (norm_w) {
-            if (sg == 0) {
-                // rstd of batch rows wv, wv + 8 (gemv_mfma_kernel's order); one barrier, LDS only: the weights stay in flight
-                for (int b = wv; b < B; b += NW) {
-                    const bf16_t* xb = x + (row_index ? (size_t)(row_index[b] + row_offset) : (size_t)b) * ldx;
-                    float ss = 0.f;
-                    for (int q = lane; q < (K >> 3); q += 64) {
-                        float f[8];
-                        unpack8(*reinterpret_cast<const U4*>(xb + q * 8), f);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) ss = __builtin_fmaf(f[j], f[j], ss);
-                    }
-                    ss = wave_sum(ss);
-                    if (lane == 0) rs[b] = rsqrtf(ss / (float)K + eps);
-                }
-                lds_barrier();
-            }
-            if (brow) {
-                const float r = rs[c];
-#pragma unroll
-                for (int i = 0; i < SEG; ++i) {
-                    const int s = (sg * SEG + i) * NW + wv;
-                    const int k = 64 * s + 16 * g;
-                    if (s < S && k < K) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            float f[8], w8[8];
-                            unpack8(xq[i][h], f);
-                            unpack8(*reinterpret_cast<const U4*>(norm_w + k + 8 * h), w8);
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) f[j] = f[j] * r * w8[j];
-                            xq[i][h] = pack8(f);                      // the bf16 rounding of the B <= 4 kernels' x^
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SEG; ++i) {
-            const int s = (sg * SEG + i) * NW + wv;
-            if (s < S) {                                              // (wave-uniform)
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8_bf16(wq[i].x, wq[i].y), __builtin_bit_cast(bf16x8, xq[i][0]), acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(cvt8_bf16(wq[i].z, wq[i].w), __builtin_bit_cast(bf16x8, xq[i][1]), acc, 0, 0, 0);
-            }
-        }
-    }
-    // lane holds D[weight row 4 g + r][batch row c]; the eight K slices are added in wave order
-#pragma unroll
-    for (int r = 0; r < 4; ++r) part[wv][4 * g + r][c] = acc[r];
-    __syncthreads();
-    const int t = threadIdx.x;
-    if constexpr (SWIGLU) {
-        const int i = t & 7, b = t >> 3;                      // output n0 / 2 + i of batch row b: gate row 2 i, up row 2 i + 1
-        if (b < B && n0 + 2 * i < N) {
-            float gs = part[0][2 * i][b], us = part[0][2 * i + 1][b];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) { gs += part[w][2 * i][b]; us += part[w][2 * i + 1][b]; }
-            gs *= scale[n0 + 2 * i];
-            us *= scale[n0 + 2 * i + 1];
-            if constexpr (EK == 2) {
-                const GemvExtRows& e = ext_rows_arg(ext...);
-                const int a = ext_row_adapter(e, b);
-                if (a >= 0) {
-                    gs = ext_dot(gs, e.Bx[a] + (size_t)(n0 + 2 * i) * e.ldb, e.t + (size_t)b * e.ldt, e.kx);
-                    us = ext_dot(us, e.Bx[a] + (size_t)(n0 + 2 * i + 1) * e.ldb, e.t + (size_t)b * e.ldt, e.kx);
-                    gs += ext_row_bias(e, a, n0 + 2 * i);
-                    us += ext_row_bias(e, a, n0 + 2 * i + 1);
-                }
-            }
-            const float gg = bf2f(f2bf(gs)), u = bf2f(f2bf(us));
-            float v = silu(gg) * u;
-            const int n = (n0 >> 1) + i;
-            if (R) v += bf2f(R[(size_t)b * ldy + n]);
-            y[(size_t)b * ldy + n] = f2bf(v);
-        }
-    } else {
-        const int rr = t & 15, b = t >> 4;
-        const int n = n0 + rr;
-        if (b < B && n < N) {
-            float v = part[0][rr][b];
-#pragma unroll
-            for (int w = 1; w < NW; ++w) v += part[w][rr][b];
-            v *= scale[n];
-            if constexpr (EK == 2) {
-                const GemvExtRows& e = ext_rows_arg(ext...);
-                const int a = ext_row_adapter(e, b);
-                if (a >= 0) v = ext_dot(v, e.Bx[a] + (size_t)n * e.ldb, e.t + (size_t)b * e.ldt, e.kx) + ext_row_bias(e, a, n);
-            }
-            if (R) v += bf2f(R[(size_t)b * ldy + n]);
-            if constexpr (sizeof(OutT) == 2) y[(size_t)b * ldy + n] = f2bf(v);
-            else y[(size_t)b * ldy + n] = v;
-        }
-    }
-}
+// gemv_mfma_kernel<WeightFp8, ...> of gemv_mfma.h: the bf16 product's kernel with the weight fragments converted from e4m3 in
+// registers and the finished row sum scaled by scale[n].  FP8-specific is only the layout that makes this possible: a lane's 16
+// weights of a 64-k step are ONE 16-byte load, whose bytes 0-7 and 8-15 are the fragments of the step's two MFMAs - the k
+// ownership of the bf16 weights' two loads, element for element.  So the product differs from the bf16 product on the dequantised
+// weights by the scale's place only, and not at all where the scale is a power of two (scaling by it commutes with every
+// rounding): FP8 mode and bf16 mode then decode the same bits.  The other layout - 128-k steps, 32 bytes per lane, a whole 128-byte
+// line per row as the bf16 kernel fetches - was built first and measured 7-21 % faster per product than bf16; it sums in another
+// order, and on weights both modes hold exactly the two modes' sampled codes then drift apart inside a frame ('FP8
+// weights').
 
 }  // namespace
 
@@ -501,23 +343,10 @@ static int gemv_fp8_launch(const void* x, const void* W8, const void* scale, voi
     CSM_REQUIRE(!norm_scale || ((uintptr_t)norm_scale & 15) == 0, "csm_gemv_fp8w: norm_scale must be 16-byte aligned");
     CSM_REQUIRE(!swiglu || ((N & 1) == 0 && !out_f32), "csm_gemv_fp8w: the SwiGLU form needs an even N and bf16 output");
     const bool nt = K == 2048 || (K == 8192 && N == 2048);   // the 2048-wide stack: streamed once per frame, non-temporal
+    if (B > 4)                                                // gemv_mfma.h
+        return gemv_mfma_launch<WeightFp8>({(const uint8_t*)W8, (const float*)scale}, x, y, residual, B, N, K, ldw8, ldx, ldy, out_f32, norm_scale,
+                                           eps, swiglu, row_index, row_offset, nt, stream, ext...);
 #define ARGS(T) (const bf16_t*)x, (const uint8_t*)W8, (const float*)scale, (T*)y, (const bf16_t*)residual
-    if (B > 4) {
-        const int grid = (N + 15) / 16;
-        const int spw = ((K + 63) / 64 + 7) / 8;                // 64-k steps per wave
-#define LM(SEG, T, SW, NT_) hipLaunchKernelGGL((gemv_fp8_mfma_kernel<SEG, T, SW, NT_, Ext...>), dim3(grid), dim3(512), 0, stream, ARGS(T), B, N, K, ldw8, ldx, ldy, (const bf16_t*)norm_scale, eps, row_index, row_offset, ext...)
-#define LMS(T, SW, NT_) do { if (spw <= 1) LM(1, T, SW, NT_); else if (spw <= 2) LM(2, T, SW, NT_); else if (spw <= 4) LM(4, T, SW, NT_); else LM(8, T, SW, NT_); } while (0)
-        if (swiglu) { if (nt) LMS(bf16_t, true, true); else LMS(bf16_t, true, false); }
-        else if (out_f32) { if (nt) LMS(float, false, true); else LMS(float, false, false); }
-        else { if (nt) LMS(bf16_t, false, true); else LMS(bf16_t, false, false); }
-#undef LMS
-#undef LM
-        g_last_gemv = {EXT ? "gemv_fp8_mfma_kernel<%d, %s, %d, %d, ext2>" : "gemv_fp8_mfma_kernel<%d, %s, %d, %d>",
-                       (out_f32 && !swiglu) ? "float" : "bf16",
-                       {spw <= 1 ? 1 : (spw <= 2 ? 2 : (spw <= 4 ? 4 : 8)), swiglu ? 1 : 0, nt ? 1 : 0, 0, 0, 0}};
-        CSM_CHECK_LAUNCH("csm_gemv_fp8w");
-        return 0;
-    }
     const int no = swiglu ? N / 2 : N;
     const int grid = (no + 3) / 4;
     const int kc = K <= 1024 ? 1 : (K <= 2048 ? 2 : 8);
@@ -557,13 +386,7 @@ extern "C" int csm_gemv_fp8w_kext_rows(const void* x, const void* W8, const void
                                        const int* row_index, int row_offset, const void* ext_t, const void* const* ext_B,
                                        const void* const* bias, const int* row_adapter, int n_adapters, int kx, int ld_ext_t,
                                        int ld_ext_B, hipStream_t stream) {
-    CSM_REQUIRE(B >= 1 && B <= 16, "csm_gemv_fp8w_kext_rows: B=%d: the per-row K-extension takes 1 to 16 batch rows", B);
-    CSM_REQUIRE(ext_t && ext_B && row_adapter && n_adapters >= 1 && kx > 0 && kx <= 512 && (kx & 7) == 0 && ld_ext_t >= kx &&
-                ld_ext_B >= kx && (ld_ext_t & 7) == 0 && (ld_ext_B & 7) == 0 && ((uintptr_t)ext_t & 15) == 0,
-                "csm_gemv_fp8w_kext_rows: bad extension (adapters=%d kx=%d ld_t=%d ld_B=%d: needs kx <= 512, multiples of 8, "
-                "16-byte aligned rows)", n_adapters, kx, ld_ext_t, ld_ext_B);
     GemvExtRows e;
-    e.t = (const bf16_t*)ext_t; e.Bx = (const bf16_t* const*)ext_B; e.bias = (const bf16_t* const*)bias;
-    e.row_adapter = row_adapter; e.nad = n_adapters; e.kx = kx; e.ldt = ld_ext_t; e.ldb = ld_ext_B;
+    if (const int rc = ext_rows_check("csm_gemv_fp8w_kext_rows", e, B, ext_t, ext_B, bias, row_adapter, n_adapters, kx, ld_ext_t, ld_ext_B)) return rc;
     return gemv_fp8_launch(x, W8, scale, y, residual, B, N, K, ldw8, ldx, ldy, out_f32, norm_scale, eps, swiglu, row_index, row_offset, stream, e);
 }

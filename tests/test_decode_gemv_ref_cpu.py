@@ -241,14 +241,17 @@ def test_dispatch_restatement_matches_the_source():
     import os
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "csm-train-pytorch_amd", "csrc")
     gen, q = open(os.path.join(root, "generate.hip")).read(), open(os.path.join(root, "quant.hip")).read()
+    mfma = open(os.path.join(root, "gemv_mfma.h")).read()          # the B = 5..16 launcher both files call
     for text in ("if (B == 1 && g_gemv_reg && (K == 1024 || K == 2048 || K == 8192))",
                  "if (B >= 2 && g_gemv_reg && g_gemv_regn && (K == 1024 || K == 2048 || (K == 8192 && !swiglu && !out_f32)))",
                  "if (B > 4 || (B >= 2 && g_gemv_mfma_small && (K & 31) == 0))",
                  "const bool nt = g_gemv_nt && (K == 2048 || (K == 8192 && N == 2048));",
-                 "if (swiglu && K == 1024 && !nt && g_gemv_rpw > 1 && no >= 2048)",
-                 "const int spw = ((K + 63) / 64 + 7) / 8;"):
+                 "if (swiglu && K == 1024 && !nt && g_gemv_rpw > 1 && no >= 2048)"):
         assert text in gen, text
-    for text in ("const int kc = K <= 1024 ? 1 : (K <= 2048 ? 2 : 8);", "const bool nt = K == 2048 || (K == 8192 && N == 2048);"):
+    for text in ("const int spw = ((K + 63) / 64 + 7) / 8;", "const int seg = spw <= 1 ? 1 : (spw <= 2 ? 2 : (spw <= 4 ? 4 : 8));"):
+        assert text in mfma, text
+    for text in ("const int kc = K <= 1024 ? 1 : (K <= 2048 ? 2 : 8);", "const bool nt = K == 2048 || (K == 8192 && N == 2048);",
+                 "if (B > 4)"):
         assert text in q, text
     from csm import hip
     assert hip._SIGS["csm_gemv_last_kernel"] == ([], hip.C.c_char_p) and hasattr(hip.lib, "csm_gemv_last_kernel")

@@ -1,6 +1,7 @@
 """Weight-only FP8 decode (Model.decode_weights = "fp8") on the GPU: the HIP quantiser against its torch restatement bit for
-bit, the FP8 decode products (csm_gemv_fp8w) against fp32 on the DEQUANTISED weights and their batch invariance, and the engine
-and public surface in FP8 mode.
+bit, the FP8 decode products (csm_gemv_fp8w) against fp32 on the DEQUANTISED weights and their batch invariance, the B = 5..16
+product against the bf16 product bit for bit where every row scale is a power of two, and the engine and public surface in FP8
+mode.
 
 Quantisation loss is not asserted anywhere here: the engine comparison runs on grid-snapped weights (csm.quant.
 snap_rows_to_fp8_grid), which FP8 mode represents exactly, so FP8 and bf16 decode hold the same numbers and differ by summation
@@ -179,6 +180,86 @@ def test_fp8_abi_limits(dev):
     with pytest.raises(Exception, match="K <= 8192"):
         ops.gemv_fp8w(torch.zeros(1, 16384, dtype=BF, device=dev), torch.zeros(16, 16384, dtype=torch.uint8, device=dev),
                       torch.ones(16, device=dev), torch.empty(1, 16, dtype=BF, device=dev))
+
+
+def _seg(K):
+    spw = ((K + 63) // 64 + 7) // 8                             # 64-k steps per wave -> the launcher's SEG
+    return 1 if spw <= 1 else 2 if spw <= 2 else 4 if spw <= 4 else 8
+
+
+# (24, 96): a partial 16-row tile, K % 64 == 32, idle waves; (48, 1056): 17 steps, SEG 4 with a ragged last segment;
+# (32, 8192): SEG 8, two segments
+@pytest.mark.parametrize("B", [5, 16])
+@pytest.mark.parametrize("N,K", [(24, 96), (48, 1056), (32, 8192)], ids=["24x96", "48x1056", "32x8192"])
+def test_fp8_mfma_product_is_the_bf16_mfma_product_on_power_of_two_scales(dev, N, K, B):
+    """B = 5..16 is ONE kernel for both weight formats (csrc/gemv_mfma.h).  With every row scale a power of two, scaling the
+    finished sum commutes with every rounding, so the FP8 product must be the bf16 product on the dequantised weights in the raw
+    output bits - every form, the per-row K-extension included.  Codes are random bytes without the two NaN codes, scale[n] = 2^e,
+    e in [-8, 0]; the bf16 weight q * scale is exact (an e4m3 value has four significant bits)."""
+    from csm.hip import lib, ops
+    g = torch.Generator().manual_seed(N * 31 + K + B)
+    codes = torch.randint(0, 256, (N, K), generator=g, dtype=torch.int32)
+    codes = torch.where((codes & 0x7F) == 0x7F, torch.full_like(codes, 0x38), codes).to(torch.uint8)
+    sc = torch.exp2(-torch.randint(0, 9, (N,), generator=g).float())
+    Wd = dequantize_rows_fp8(codes, sc)
+    W = Wd.to(BF)
+    assert torch.equal(W.float(), Wd) and bool(torch.isfinite(Wd).all())
+    W8 = torch.zeros(N, (K + 15) // 16 * 16, dtype=torch.uint8, device=dev)[:, :K].copy_(codes)
+    W, sc = W.to(dev), sc.to(dev)
+    w = (1 + 0.1 * torch.randn(K, generator=g)).to(BF).to(dev)
+    x = torch.randn(B, K, generator=g).to(BF).to(dev)
+    # under the norm prologue the two formats round the sum of squares differently (bf16: each square rounded, then added; FP8:
+    # fused), so with general x their rstd - and the product - need NOT agree, and that is not asserted.  Here x is drawn from
+    # {+-0.5, +-1, +-2}: the squares are 0.25, 1, 4 and every partial sum is a multiple of 0.25 of at most 2^15 - exact in fp32
+    # in any order, fused or not - so rstd is the same number in both and equality must hold.
+    xn = (torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (B, K), generator=g)]
+          * (1 - 2 * torch.randint(0, 2, (B, K), generator=g)).float()).to(BF).to(dev)
+    R = torch.randn(B, N, generator=g).to(BF).to(dev)
+    Rh = torch.randn(B, N // 2, generator=g).to(BF).to(dev)
+    table = torch.randn(64, K, generator=g).to(BF).to(dev)
+    idx = torch.randint(0, 50, (B,), generator=g).to(torch.int32).to(dev)
+    kx = 16
+    t = torch.randn(B, kx, generator=g).to(BF).to(dev)
+    Bx = [(torch.randn(N, kx, generator=g) * 0.05).to(BF).to(dev) for _ in range(2)]
+    bias0 = torch.randn(N, generator=g).to(BF).to(dev)
+    Bx_tab = torch.tensor([b.data_ptr() for b in Bx], dtype=torch.int64).to(dev)
+    bias_tab = torch.tensor([bias0.data_ptr(), 0], dtype=torch.int64).to(dev)          # adapter 1 has no bias
+    row_adapter = torch.tensor([(0, -1, 1)[b % 3] for b in range(B)], dtype=torch.int32).to(dev)   # every third row: no adapter
+    ext = dict(ext_t=t, Bx_tab=Bx_tab, row_adapter=row_adapter, kx=kx, ldb=kx, bias_tab=bias_tab)
+    # name: (x, output dtype, SwiGLU, arguments both products take, per-row extension)
+    forms_ = {
+        "bf16": (x, BF, False, {}, False),
+        "f32": (x, torch.float32, False, {}, False),
+        "swiglu": (x, BF, True, dict(swiglu=True), False),
+        "residual": (x, BF, False, dict(residual=R), False),
+        "gather": (table, BF, False, dict(row_index=idx, row_offset=7), False),
+        "ext_rows": (x, BF, False, dict(residual=R), True),
+        "ext_rows+swiglu": (x, BF, True, dict(swiglu=True), True),
+        "norm": (xn, BF, False, dict(norm_scale=w, eps=1e-5), False),
+        "norm+f32": (xn, torch.float32, False, dict(norm_scale=w, eps=1e-5), False),
+        "norm+swiglu+residual": (xn, BF, True, dict(norm_scale=w, eps=1e-5, swiglu=True, residual=Rh), False),
+        "norm+ext_rows": (xn, BF, False, dict(norm_scale=w, eps=1e-5), True),
+    }
+    seg = _seg(K)
+    for name, (xin, dt, sw, kw, rows) in forms_.items():
+        y8 = torch.empty(B, N // 2 if sw else N, dtype=dt, device=dev)
+        yb = torch.empty_like(y8)
+        if rows:
+            ops.gemv_fp8w_kext_rows(xin, W8, sc, y8, **ext, **kw)
+        else:
+            ops.gemv_fp8w(xin, W8, sc, y8, **kw)
+        k8 = lib.csm_gemv_last_kernel().decode()
+        if rows:
+            ops.gemv_kext_rows(xin, W, yb, **ext, **kw)
+        else:
+            ops.gemv_ex(xin, W, yb, **kw)
+        kb = lib.csm_gemv_last_kernel().decode()
+        assert k8.startswith(f"gemv_fp8_mfma_kernel<{seg}, ") and k8.endswith(", ext2>") == rows, f"{name}: {k8}"
+        assert kb.startswith(f"gemv_mfma_kernel<{seg}, ") and kb.endswith(f", ext{2 if rows else 0}>"), f"{name}: {kb}"
+        bits = torch.int16 if dt == BF else torch.int32
+        a, b = y8.view(bits), yb.view(bits)
+        assert torch.equal(a, b), f"{N}x{K} B={B} {name}: {int((a != b).sum())} of {a.numel()} outputs differ in their bits"
+        assert bool(torch.isfinite(y8.float()).all()), f"{N}x{K} B={B} {name}: non-finite output"
 
 
 # ------------------------------------------------------------------------------------------------------------ engine level
