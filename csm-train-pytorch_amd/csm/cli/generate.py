@@ -81,6 +81,10 @@ def parse_args(argv=None):
                         "repetition_window, and a list of one number per codebook for any of the four keys before them (a file or a "
                         "command line that uses any of these, --acoustic-* included, is served with row_processors=True); one WAV "
                         "per utterance, <output stem>_<i>.wav with i = 0, 1, ... counting the file's non-empty lines")
+    p.add_argument("--cache-context", action="store_true",
+                   help="--serve-file: prefill the --context-* segments once as a voice (Generator.voice; one per distinct adapter "
+                        "among --lora-adapter and the lines) and submit every line with its voice instead of the context - no "
+                        "Mimi encode and no prefill of the context per line; conversations start from the voice")
     p.add_argument("--slots", type=int, default=16, help="--serve-file: utterances decoded at once (1..16, default 16)")
     p.add_argument("--hear-slots", type=int, default=0,
                    help="--serve-file: encoder slots of the server's batched hearing (Generator.serve(hear_slots=N), 0..16; "
@@ -101,6 +105,8 @@ def parse_args(argv=None):
         p.error("--hear-slots must be 0..16")
     if args.hear_slots and args.serve_file is None:
         p.error("--hear-slots goes with --serve-file")
+    if args.cache_context and (args.serve_file is None or not args.context_audio):
+        p.error("--cache-context goes with --serve-file and --context-audio / --context-text / --context-speaker")
     if args.keep_turns < 0:
         p.error("--keep-turns must be >= 0")
     if args.fp8_adapters and args.decode_weights != "fp8":
@@ -313,6 +319,21 @@ def serve_processors(lines, args=None, codebooks=None):
     return kw
 
 
+def serve_voices(generator, lines, context, adapter=None):
+    """--cache-context: the --context-* segments as one ``Generator.voice`` per distinct adapter among the lines (--lora-adapter
+    for lines without one): {adapter name or None: Voice}.  Call it after the lines' adapters are loaded and before ``serve``."""
+    return {name: generator.voice(context, adapter=name)
+            for name in sorted({ln["adapter"] or adapter for ln in lines}, key=lambda n: (n is not None, n or ""))}
+
+
+def line_prompt(line, context, voices, adapter=None):
+    """The prompt keywords of one --serve-file line for ``submit`` / ``conversation``: the context - or, with --cache-context
+    (``voices``: ``serve_voices``), no context and the voice of the line's adapter."""
+    if voices is None:
+        return {"context": context}
+    return {"context": [], "voice": voices[line["adapter"] or adapter]}
+
+
 def serve_to_wavs(generator, args, context, adapter=None):
     """--serve-file: every line is a request of one ``Generator.serve`` batch; adapter files are loaded once each, under their
     path as name (--lora-adapter is the default for lines without one).  Lines with a "conversation" id are the turns of one
@@ -320,7 +341,9 @@ def serve_to_wavs(generator, args, context, adapter=None):
     before it is done.  A line's "temperature" / "topk" are that utterance's or that turn's; if any line has one, the server is
     made with ``row_sampling=True`` (--temperature / --topk are then the other lines' values); "top_p" / "min_p" likewise, with
     ``row_filters=True`` (``serve_filters``); "repetition_penalty" / "repetition_window", a list per codebook or the command
-    line's --repetition-* / --acoustic-* make it ``row_processors=True`` (``serve_processors``).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav."""
+    line's --repetition-* / --acoustic-* make it ``row_processors=True`` (``serve_processors``).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav.
+    With --cache-context the context becomes one voice per adapter (``serve_voices``) and every line and every conversation
+    starts from its voice instead of the context (``line_prompt``)."""
     def K():
         return generator._model.args.audio_num_codebooks
     lines = read_serve_file(args.serve_file, K)
@@ -329,6 +352,7 @@ def serve_to_wavs(generator, args, context, adapter=None):
     stem, ext = os.path.splitext(os.path.abspath(args.output))
     os.makedirs(os.path.dirname(stem), exist_ok=True)
     t0 = time.perf_counter()
+    voices = serve_voices(generator, lines, context, adapter) if args.cache_context else None     # (the adapters are loaded)
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, hear_slots=args.hear_slots,
                              **{"temperature": args.temperature, "topk": args.topk, **serve_sampling(lines),
                                 **serve_filters(lines, args.top_p, args.min_p), **serve_processors(lines, args, K),
@@ -344,14 +368,15 @@ def serve_to_wavs(generator, args, context, adapter=None):
     for i, ln in enumerate(lines):
         cid = ln.get("conversation")
         if cid is None:
-            line_of[server.submit(ln["text"], ln["speaker"], context, adapter=ln["adapter"] or adapter, seed=ln["seed"],
-                                  max_audio_length_ms=args.max_audio_length_ms, **line_sampling(ln),
+            line_of[server.submit(ln["text"], ln["speaker"], adapter=ln["adapter"] or adapter, seed=ln["seed"],
+                                  max_audio_length_ms=args.max_audio_length_ms, **line_prompt(ln, context, voices, adapter),
+                                  **line_sampling(ln),
                                   **line_filters(ln), **line_processors(ln))] = (i, None)
         elif cid in convs:
             convs[cid][1].append(i)
         else:
-            convs[cid] = [server.conversation(context=context, adapter=ln["adapter"] or adapter, seed=ln["seed"],
-                                              on_overflow=args.on_overflow, keep_turns=args.keep_turns), [i]]
+            convs[cid] = [server.conversation(adapter=ln["adapter"] or adapter, seed=ln["seed"], on_overflow=args.on_overflow,
+                                              keep_turns=args.keep_turns, **line_prompt(ln, context, voices, adapter)), [i]]
             say(cid)
     while server.queued or server.active:
         for req, _, done in server.step():

@@ -49,6 +49,71 @@ def fit_history(conv, n_new: int, limit: int):
     return head, gone
 
 
+class Voice:
+    """``Generator.voice(context, adapter)``: a voice prompt that was tokenised, Mimi-encoded and prefilled ONCE and is forked
+    into any number of requests, conversations and server slots (``generate(voice=)``, ``conversation(voice=)``,
+    ``BatchServer.submit(voice=)`` / ``.conversation(voice=)``).
+
+    ``tokens`` / ``mask`` ([L, K+1]) are the segments' frames in the layout of a conversation's history, ``turns`` their lengths,
+    ``kv`` ([layers, 2, KV, L, hd] bf16) the backbone's K / V of those L positions as ``DecodeState.park_row`` returns them,
+    ``adapter`` the bank adapter it was prefilled with (a name or None), ``positions`` = L and ``nbytes`` the size of ``kv``.
+    ``kv`` is never written after creation: every user copies it into a cache row of its own (``resume_row`` / ``fork_rows``) or
+    shifts it out of place (``shift_parked``), so one tensor is shared by reference by all of them.
+
+    A voice belongs to the model (and Generator) it was made on and is valid for the weights of that moment: after training
+    steps or a merge make a new one.  The prefill is the training forward and does not read ``model.decode_weights``, so one
+    voice serves bf16 and FP8 decode alike.  A plain tensor, not captured into any frame graph: voices can be made and dropped
+    while a server runs."""
+
+    def __init__(self, gen, tokens, mask, turns, kv, adapter):
+        self._gen, self._model = gen, gen._model
+        self.tokens, self.mask, self.turns, self.kv, self.adapter = tokens, mask, tuple(turns), kv, adapter
+
+    @property
+    def positions(self) -> int:
+        return self.tokens.shape[0]
+
+    @property
+    def nbytes(self) -> int:
+        return self.kv.numel() * self.kv.element_size()
+
+    def check(self, gen, adapter, what: str):
+        """The rules of every ``voice=`` argument: the voice is this Generator's (and its model's), and ``adapter`` is not named
+        or names the voice's own.  Returns the adapter the caller speaks with: the voice's."""
+        if self._gen is not gen or self._model is not gen._model:
+            raise ValueError(f"{what}: this voice was made on another Generator / model (its cache holds that model's K / V)")
+        if adapter is not None and adapter != self.adapter:
+            raise ValueError(f"{what}: adapter {adapter!r} with a voice that was prefilled with adapter {self.adapter!r} - the "
+                             "cache is only valid for the adapter it was computed with")
+        return self.adapter
+
+
+@torch.inference_mode()
+def make_voice(gen, context, adapter=None) -> Voice:
+    """``Generator.voice``: the segments are tokenised as ``_tokenize_segment`` does, prefilled on a one-row ``DecodeState`` made
+    with the bank adapter ``adapter``, and the row is parked."""
+    m, e = gen._model, gen._model.engine
+    context = list(context)
+    if not context:
+        raise ValueError("voice: an empty context (a voice is at least one segment)")
+    if not getattr(m, "use_kv_cache", True):
+        raise ValueError("voice: a voice is a KV cache: model.use_kv_cache must be on")
+    lora = getattr(m, "lora", None)
+    if lora is not None and not lora.merged:
+        raise ValueError("voice: live (un-merged) LoRA adapters are attached as model.lora - their weights move, so the cache "
+                         "would go stale: merge them (merge_lora_weights), detach them, or add them to the bank and name one")
+    ads = gen._resolve_adapters([adapter])                          # (an unknown name raises ValueError here)
+    toks, msks = zip(*(gen._tokenize_segment(seg) for seg in context))
+    tokens, mask = torch.cat(toks, 0).long().to(gen.device), torch.cat(msks, 0).bool().to(gen.device)
+    limit = m.bb.max_seq_len - 1                                    # the reference's rule with one frame of audio
+    if tokens.shape[0] >= limit:
+        raise ValueError(f"voice: Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
+    e._need()
+    st = DecodeState(e, 1, ads)
+    st.prefill(tokens.unsqueeze(0), mask.unsqueeze(0))
+    return Voice(gen, tokens, mask, [t.shape[0] for t in toks], st.park_row(0, tokens.shape[0]), adapter)
+
+
 class _Turn:
     """A spoken turn in flight: the sampled frames, how many of them were fed back into the cache, how many were handed out."""
 
@@ -182,11 +247,14 @@ class Conversation:
     ``reset()`` - the history is kept and prefilled again by the next turn.
     """
 
-    def __init__(self, gen, context=(), adapter: Optional[str] = None, on_overflow: str = "error", keep_turns: int = 0):
+    def __init__(self, gen, context=(), adapter: Optional[str] = None, on_overflow: str = "error", keep_turns: int = 0,
+                 voice: Optional[Voice] = None):
         if on_overflow not in OVERFLOW:
             raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
         self._keep_turns = check_keep_turns(keep_turns)
         self._gen, self._m = gen, gen._model
+        if voice is not None:
+            adapter = voice.check(gen, adapter, "conversation")
         self._ads = gen._resolve_adapters([adapter])
         self._on_overflow = on_overflow
         K1 = self._m.args.audio_num_codebooks + 1
@@ -200,6 +268,11 @@ class Conversation:
         self._heard: Optional[HeardTurn] = None    # the other party's turn being heard (hear), at most one
         self._enc = None                           # its encode stream: made at the first hear, reused
         self._hear_rs = {}                         # hear(sample_rate=): input rate -> its ResampleStream, made once, reused
+        # a voice: the history starts as its frames, already cached - its K / V enter the state the first turn makes
+        self._fork = None                          # the voice's parked K / V while they wait for that state (never written)
+        if voice is not None:
+            self._tokens, self._mask, self._turns = voice.tokens, voice.mask, list(voice.turns)
+            self._cached, self._fork = voice.positions, voice.kv
         for seg in context:
             self.add(seg)
 
@@ -245,7 +318,7 @@ class Conversation:
         weights and adapters of that moment."""
         self._run += 1
         self._settle()
-        self._state, self._cached = None, 0
+        self._state, self._cached, self._fork = None, 0, None
 
     def _push(self, t, m):
         self._tokens = torch.cat([self._tokens, t.to(self._tokens.device)], 0)
@@ -285,6 +358,11 @@ class Conversation:
         if not getattr(m, "use_kv_cache", True):
             raise RuntimeError("a Conversation keeps the KV cache between turns: model.use_kv_cache must be on")
         tt, tm = self._gen._tokenize_text_segment(text, speaker)
+        if self._fork is not None:                                   # a voice's first turn: its K / V into a state of our own
+            e._need()
+            self._state = DecodeState(e, 1, self._ads)
+            self._state.resume_row(0, self._fork)
+            self._fork = None
         self._fit(tt.shape[0], max_audio_frames)
         new_t = torch.cat([self._tokens[self._cached:], tt.long()], 0)
         new_m = torch.cat([self._mask[self._cached:], tm.bool()], 0)

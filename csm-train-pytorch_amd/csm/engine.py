@@ -1523,6 +1523,28 @@ class DecodeState:
         self.bb.pos[b] = length - 1
         self.row_pos[b] = length - 1
 
+    def fork_rows(self, rows, parkeds):
+        """``resume_row`` for several rows at once: each ``parkeds[r]`` into row ``rows[r]`` from position 0, the rows' device
+        positions and host mirrors to their last positions - ONE launch (``ops.kv_fork_rows``) instead of a strided copy and a
+        position write per row.  The same parked history may be given for several rows - one voice forked into many requests
+        (csm/serving.py) - and none is written.  Leaves the caches, ``bb.pos`` and ``row_pos`` in the state the R ``resume_row``
+        calls leave, bit for bit."""
+        rows, parkeds = [int(b) for b in rows], list(parkeds)
+        R = len(rows)
+        if not (1 <= R <= 16 and len(parkeds) == R):
+            raise ValueError(f"fork_rows takes 1..16 rows with one parked history each (got {R} rows, {len(parkeds)} histories)")
+        if len(set(rows)) != R or any(not 0 <= b < self.B for b in rows):
+            raise ValueError(f"fork_rows: rows must be distinct rows of 0..{self.B - 1}, got {rows}")
+        kv = self.bb.kv
+        for parked in parkeds:
+            length = parked.shape[3] if parked.dim() == 5 else -1
+            if parked.dim() != 5 or parked.shape[:3] != (kv.shape[0], 2, kv.shape[3]) or parked.shape[4] != kv.shape[5] or \
+                    not 1 <= length <= kv.shape[4] or parked.dtype != kv.dtype:
+                raise ValueError(f"fork_rows: {tuple(parked.shape)} {parked.dtype} is not a parked history of this model's backbone")
+        ops.kv_fork_rows([p.contiguous() for p in parkeds], kv, self.bb.pos, rows)
+        for b, parked in zip(rows, parkeds):
+            self.row_pos[b] = parked.shape[3] - 1
+
     def shift_parked(self, parked, keep: int, drop: int):
         """A parked history (``park_row``) without its positions ``keep .. keep+drop-1``: a new tensor of ``length - drop``
         positions whose keys behind the gap are rotated back by ``drop`` positions (``ops.kv_shift``, one launch) - the context

@@ -167,7 +167,7 @@ class Generator:
     def generate(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                  temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8, adapter: Optional[str] = None,
                  top_p: float = 1.0, min_p: float = 0.0, output_sample_rate: Optional[int] = None,
-                 repetition_penalty=1.0, repetition_window=64) -> torch.Tensor:
+                 repetition_penalty=1.0, repetition_window=64, voice=None) -> torch.Tensor:
         """Reference generator.py:147-218.  ``adapter``: the name of a bank adapter (``add_adapter`` / ``load_adapter``) to
         speak with, or None.  The reference tests every frame for EOS on the host (one device sync per
         frame, generator.py:196-199); here the all-zero test runs on the device and the host looks at it once per
@@ -182,7 +182,14 @@ class Generator:
         code the utterance drew for this codebook in its last ``repetition_window`` frames becomes x / r (x > 0) or x * r before
         the temperature.  ``temperature`` / ``topk`` / ``top_p`` / ``min_p`` and these two may each be a sequence of K numbers, one
         per codebook (codebook 0 is the semantic one).  At 1.0 / 64 with plain numbers the call is what it is without them;
-        otherwise it samples through the processed rows sampler (``DecodeState.set_row_processors``)."""
+        otherwise it samples through the processed rows sampler (``DecodeState.set_row_processors``).
+        ``voice``: a ``Voice`` (``Generator.voice``) that comes before ``context`` - the call is then
+        ``conversation(voice=voice, context=context, adapter=adapter).generate(text, speaker, ...)`` with every other argument
+        passed through: the voice's K / V are copied in, only ``context`` and the text are fed."""
+        if voice is not None:
+            return self.conversation(context, adapter, voice=voice).generate(
+                text, speaker, max_audio_length_ms, temperature, topk, eos_check_every, top_p, min_p, output_sample_rate,
+                repetition_penalty, repetition_window)
         temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
                                                      repetition_window)
         out_rs = self._out_resampler(output_sample_rate)
@@ -238,7 +245,7 @@ class Generator:
                         temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4,
                         adapter: Optional[str] = None, top_p: float = 1.0, min_p: float = 0.0,
                         output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
-                        repetition_window=64) -> Iterator[torch.Tensor]:
+                        repetition_window=64, voice=None) -> Iterator[torch.Tensor]:
         """``generate`` that hands the audio out while it is being made: an iterator of 1-D device tensors of
         ``chunk_frames * 1920`` samples (the last one may be shorter), decoded by the audio tokenizer's stateful
         ``decode_stream()``.  The frames are sampled by the same ``generate_frame`` calls in the same order as ``generate``,
@@ -248,7 +255,13 @@ class Generator:
         ``adapter``, ``top_p``, ``min_p``, ``repetition_penalty``, ``repetition_window`` and per-codebook sequences: as for
         ``generate``.  ``output_sample_rate``: the chunks go through a stateful
         ``ResampleStream`` - they concatenate to ``generate(..., output_sample_rate=)``'s audio bit for bit; the stream lags by
-        the filter's half-width, and what it still owes comes as one last short chunk."""
+        the filter's half-width, and what it still owes comes as one last short chunk.
+        ``voice``: as for ``generate`` - the call is ``conversation(voice=voice, context=context,
+        adapter=adapter).generate_stream(text, speaker, ...)``."""
+        if voice is not None:
+            return self.conversation(context, adapter, voice=voice).generate_stream(
+                text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, top_p, min_p, output_sample_rate,
+                repetition_penalty, repetition_window)
         temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
                                                      repetition_window)
         out_rs = self._out_resampler(output_sample_rate)
@@ -416,8 +429,20 @@ class Generator:
         return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p,
                            output_sample_rate, row_processors, repetition_penalty, repetition_window)
 
+    def voice(self, context: List[Segment], adapter: Optional[str] = None):
+        """A voice prompt prefilled ONCE (csm/conversation.py: ``Voice``): the segments are tokenised and Mimi-encoded as every
+        ``generate`` call does, prefilled on a one-row state with the bank adapter ``adapter`` and the K / V of their L positions
+        are kept.  ``generate`` / ``generate_stream`` / ``conversation`` / ``server.submit`` / ``server.conversation`` take it as
+        ``voice=``: the K / V are copied into the cache row (one launch for all voice requests a server admits together) and
+        only what follows the voice - further context, the text - is fed, so a request pays neither the Mimi encode nor the
+        prefill of its voice.  Refused (ValueError): an empty context, one that alone breaks the reference's length rule, an
+        unknown adapter name, ``model.use_kv_cache`` off, live un-merged ``model.lora`` adapters.  The prefill does not depend on
+        ``model.decode_weights``: one voice serves bf16 and FP8 decode alike.  It belongs to this Generator and model."""
+        from .conversation import make_voice
+        return make_voice(self, context, adapter)
+
     def conversation(self, context: Optional[List[Segment]] = None, adapter: Optional[str] = None, on_overflow: str = "error",
-                     keep_turns: int = 0):
+                     keep_turns: int = 0, voice=None):
         """A multi-turn dialogue that keeps its KV cache between turns (csm/conversation.py): ``conv.generate(text, speaker)`` /
         ``conv.generate_stream(...)`` speak the next line with every earlier turn as context, ``conv.add(Segment)`` adds the
         other party's turn - or ``turn = conv.hear(speaker)``, ``turn.feed(audio)`` as the audio arrives and ``turn.end(text)``,
@@ -425,9 +450,13 @@ class Generator:
         the reference's "Inputs too long" error when history + line + max_audio_frames reach max_seq_len, ``"drop_oldest"``
         drops whole turns - the oldest first, after the ``keep_turns`` leading ones (the voice prompt), which always stay - and
         prefills what is left; ``"shift"`` drops the same turns but keeps the cache: the kept keys are rotated back to their new
-        positions (``DecodeState.shift_row``), nothing is prefilled again and the turn is appended as any other."""
+        positions (``DecodeState.shift_row``), nothing is prefilled again and the turn is appended as any other.
+        ``voice``: a ``Voice`` (``Generator.voice``) the history starts with, already cached (``cached == voice.positions``):
+        the first turn copies its K / V into the conversation's state and appends ``context`` - which comes after the voice -
+        and the text.  ``adapter`` must be None or the voice's; the conversation speaks with the voice's.  After ``reset()`` or a
+        ``drop_oldest`` the history is prefilled again from its tokens, like any other."""
         from .conversation import Conversation
-        return Conversation(self, context or [], adapter, on_overflow, keep_turns)
+        return Conversation(self, context or [], adapter, on_overflow, keep_turns, voice)
 
     def save_wav(self, path: str, audio: torch.Tensor, sample_rate: Optional[int] = None):
         """16-bit PCM writer (torchaudio is not available in this image).  ``sample_rate``: the rate ``audio`` is at (None: the

@@ -716,6 +716,26 @@ def kv_shift(parked, table, keep, drop):
     return out
 
 
+def kv_fork_rows(parkeds, kv, pos, rows):
+    """R <= 16 parked histories (``DecodeState.park_row``: [layers, 2, KV, len_r, HD] bf16, contiguous) into positions
+    ``0 .. len_r - 1`` of batch rows ``rows[r]`` of the cache allocation ``kv`` [layers, 2, B, KV, S_max, HD], and ``pos[rows[r]] =
+    len_r - 1`` (int32 [B]) - ONE launch (csm_kv_fork_rows), the table in the kernel arguments.  The same tensor may be given for
+    several rows; no parked tensor is touched, nor anything of ``kv`` / ``pos`` outside the named rows' leading positions."""
+    parkeds, rows = list(parkeds), [int(b) for b in rows]
+    R = len(rows)
+    if len(parkeds) != R:
+        raise CsmHipError(f"csm_kv_fork_rows failed (code 1): {len(parkeds)} parked histories for {R} rows")
+    assert kv.dim() == 6 and kv.shape[1] == 2 and kv.dtype == BF16 and kv.is_contiguous()
+    layers, _, B, KV, S_max, HD = kv.shape
+    assert pos.dtype == torch.int32 and pos.shape == (B,) and pos.is_contiguous() and pos.device == kv.device
+    for p in parkeds:
+        assert p.dim() == 5 and p.shape[:3] == (layers, 2, KV) and p.shape[4] == HD, f"kv_fork_rows: {tuple(p.shape)} against {tuple(kv.shape)}"
+        assert p.dtype == BF16 and p.is_contiguous() and p.device == kv.device
+    ptr, arr = ctypes.c_void_p * max(R, 1), ctypes.c_int * max(R, 1)
+    check(lib.csm_kv_fork_rows(ptr(*[p.data_ptr() for p in parkeds]), kv.data_ptr(), pos.data_ptr(), arr(*rows),
+                               arr(*[p.shape[3] for p in parkeds]), R, layers, B, KV, HD, S_max, _stream()), "csm_kv_fork_rows")
+
+
 def attn_decode(qkv, kcache, vcache, out, pos_i32, H, KV, HD):
     B, _, S_max, _ = kcache.shape
     check(lib.csm_attn_decode(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), pos_i32.data_ptr(), B, H, KV,

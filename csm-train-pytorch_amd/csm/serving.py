@@ -58,6 +58,14 @@ the audio and from the parked length, as frames after EOS are - which is why ``s
 headroom beyond ``max_audio_frames``.  A conversation's ``seed`` gives it one generator for its whole life, which moves only
 when the conversation samples a frame and travels with it from slot to slot.
 
+Voices (``Generator.voice`` -> ``Voice``, csm/conversation.py): a voice prompt tokenised, Mimi-encoded and prefilled once.
+``submit(text, speaker, context, voice=v)`` tokenises only ``context`` and the text; the request carries that feed and the voice.
+All voice requests admitted at one chunk boundary get the voice's K / V by ONE ``DecodeState.fork_rows`` (``csm_kv_fork_rows``:
+the same source for any number of rows) and are fed, together with the resumed conversation turns, by the ONE ``append_rows`` -
+no Mimi encode and no prefill per request.  ``conversation(voice=v)`` starts with the voice as its history and ``v.kv`` as its
+parked cache (shared, never written: ``resume_row`` copies, ``shift_parked`` is out of place), so its first ``say`` is a resumed
+turn.  The length rule counts the voice's positions; ``adapter`` must be None or the voice's.
+
 Hearing (``conv.hear`` -> ``turn.feed`` / ``turn.end``) Mimi-encodes the other party's turn while it is spoken.  By default
 every conversation owns a ``MimiEncodeStream`` and every ``feed`` is one encoder step for that conversation.  With
 ``serve(hear_slots=N)`` (1..16) the server owns ONE ``MimiEncodeStreamRows`` of N slots instead: ``hear`` takes a free encoder
@@ -115,6 +123,7 @@ class Request:
         self._conv: Optional["ServedConversation"] = None     # the conversation this is a turn of (tokens / mask: what it feeds)
         self.sample_rate: Optional[int] = None   # the rate of ``chunks`` / ``audio()`` (the server's; set when it queues)
         self._base = 0                           # a turn: positions the cache holds once the feed is in
+        self._voice = None                       # submit(voice=): the Voice whose K / V the slot gets; tokens / mask: what follows it
 
     def audio(self) -> torch.Tensor:
         """The audio so far (all of it once ``done``): the chunks concatenated."""
@@ -186,7 +195,7 @@ class ServedConversation:
     one all-zero EOS frame; a spoken turn's frames are the sampled codes; the EOS frame always enters with the next feed."""
 
     def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None, top_p=None, min_p=None,
-                 keep_turns: int = 0, repetition_penalty=None, repetition_window=None):
+                 keep_turns: int = 0, repetition_penalty=None, repetition_window=None, voice=None):
         if on_overflow not in OVERFLOW:
             raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
         self._keep_turns = check_keep_turns(keep_turns)
@@ -207,6 +216,11 @@ class ServedConversation:
         self._enc = None                         # its encode stream: made at the first hear, reused
         self._hear_rs = {}                       # hear(sample_rate=) without hear_slots: input rate -> its ResampleStream
         self.closed = False
+        if voice is not None:
+            # the history starts as the voice, already cached; its K / V are the parked cache - shared, never written (resume_row
+            # copies it into the slot, shift_parked is out of place) - so the first ``say`` is a resumed turn like any other
+            self._tokens, self._mask, self._turns = voice.tokens, voice.mask, list(voice.turns)
+            self._cached, self._parked = voice.positions, voice.kv
         for seg in context:
             self.add(seg)
 
@@ -479,14 +493,18 @@ class BatchServer:
     def submit(self, text: str, speaker: int, context, adapter: Optional[str] = None, seed: Optional[int] = None,
                max_audio_length_ms: float = 90_000, temperature: Optional[float] = None, topk: Optional[int] = None,
                top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty=None,
-               repetition_window=None) -> Request:
+               repetition_window=None, voice=None) -> Request:
         """Queue one utterance; it takes a slot at the next chunk boundary that has a free one.  The prompt is tokenised here, so
         the reference's length rule ("Inputs too long ...") and an unknown adapter name raise here.  ``temperature`` / ``topk``
         (``row_sampling`` servers), ``top_p`` / ``min_p`` (``row_filters`` servers) and ``repetition_penalty`` / ``repetition_window`` /
         a sequence of K values, one per codebook, for any of the six (``row_processors`` servers): this request's, over the
-        server's."""
+        server's.  ``voice``: a ``Voice`` of this Generator - the prompt is the voice, then ``context`` (which may be empty), then
+        the text; only context and text are tokenised here and fed at admission, and the length rule counts the voice's positions.
+        ``adapter`` must be None or the voice's: the request speaks with the voice's."""
         self._check()
         six = self._resolve("submit", temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        if voice is not None:
+            adapter = voice.check(self._gen, adapter, "submit")
         if adapter is not None and adapter not in self._bank:
             known = self._gen._bank is not None and adapter in self._gen._bank.entries
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})" +
@@ -495,10 +513,18 @@ class BatchServer:
         if max_audio_frames < 1:
             raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
         with torch.inference_mode():
-            tokens, mask, _ = self._gen._prompt(text, speaker, list(context), max_audio_frames)
+            if voice is None:
+                tokens, mask, _ = self._gen._prompt(text, speaker, list(context), max_audio_frames)
+            else:
+                parts = [self._gen._tokenize_segment(seg) for seg in context] + [self._gen._tokenize_text_segment(text, speaker)]
+                tokens = torch.cat([t for t, _ in parts], 0).long().to(self._gen.device).unsqueeze(0)
+                mask = torch.cat([m for _, m in parts], 0).bool().to(self._gen.device).unsqueeze(0)
+                limit = self._model.bb.max_seq_len - max_audio_frames
+                if voice.positions + tokens.shape[1] >= limit:
+                    raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
         req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device,
                       *six)
-        req.sample_rate = self.sample_rate
+        req.sample_rate, req._voice = self.sample_rate, voice
         self._next_id += 1
         self._queue.append(req)
         return req
@@ -507,19 +533,23 @@ class BatchServer:
                      on_overflow: str = "error", temperature: Optional[float] = None,
                      topk: Optional[int] = None, top_p: Optional[float] = None,
                      min_p: Optional[float] = None, keep_turns: int = 0, repetition_penalty=None,
-                     repetition_window=None) -> ServedConversation:
+                     repetition_window=None, voice=None) -> ServedConversation:
         """A multi-turn dialogue on this server: ``conv.say(text, speaker, max_audio_length_ms)`` queues its next spoken turn (a
         ``Request``), ``conv.add(Segment)`` is the other party's turn, ``conv.close()`` drops its parked cache.  ``adapter`` and
         ``seed`` hold for the whole conversation; ``on_overflow`` / ``keep_turns`` as for ``Generator.conversation`` (``"shift"``
         slides the parked cache at ``say``).  ``temperature`` / ``topk``
         (``row_sampling`` servers), ``top_p`` / ``min_p`` (``row_filters`` servers) and ``repetition_penalty`` /
         ``repetition_window`` / per-codebook sequences (``row_processors`` servers): the defaults of its turns, over the
-        server's; ``say`` may name a turn's own."""
+        server's; ``say`` may name a turn's own.  ``voice``: a ``Voice`` of this Generator the history starts with, already
+        cached - its K / V are the conversation's parked cache (shared, never written), so the first ``say`` is resumed and
+        fed like a later turn; ``context`` comes after the voice; ``adapter`` must be None or the voice's."""
         self._check()
+        if voice is not None:
+            adapter = voice.check(self._gen, adapter, "conversation")
         if adapter is not None and adapter not in self._bank:
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})")
         return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk, top_p, min_p, keep_turns,
-                                  repetition_penalty, repetition_window)
+                                  repetition_penalty, repetition_window, voice)
 
     @property
     def queued(self) -> int:
@@ -629,9 +659,9 @@ class BatchServer:
 
     def _admit(self):
         """Queued requests into free slots: plain requests and first turns are prefilled one by one, the turns of conversations
-        with a parked cache are resumed and fed by ONE ``append_rows``, then one frame tail for all of them.  Returns (their
-        slots, [slots, K])."""
-        st, joined, resumed, hs = self._state, [], [], {}
+        with a parked cache are resumed, the requests with a voice are forked by ONE ``fork_rows``, and those two kinds are fed
+        by ONE ``append_rows``, then one frame tail for all of them.  Returns (their slots, [slots, K])."""
+        st, joined, resumed, forked, hs = self._state, [], [], [], {}
         for b in range(self.slots):
             if not self._queue:
                 break
@@ -659,6 +689,9 @@ class BatchServer:
                 st.resume_row(b, conv._parked)
                 conv._parked = None
                 resumed.append(b)
+            elif req._voice is not None:
+                forked.append(b)
+                resumed.append(b)
             else:
                 hs[b] = st.prefill_row(b, req._tokens, req._mask)
             if conv is not None:
@@ -670,6 +703,8 @@ class BatchServer:
             joined.append(b)
         if not joined:
             return joined, None
+        if forked:
+            st.fork_rows(forked, [self._rows[b]._voice.kv for b in forked])
         if resumed:
             h = st.append_rows(resumed, [self._rows[b]._tokens for b in resumed], [self._rows[b]._mask for b in resumed])
             hs.update({b: h[j] for j, b in enumerate(resumed)})

@@ -1149,6 +1149,55 @@ __global__ __launch_bounds__(256) void kv_shift_kernel(const bf16_t* __restrict_
     }
 }
 
+// The rows form of DecodeState.resume_row: R <= 16 parked histories [planes = layers * 2 * KV][len][HD] into rows of the cache
+// allocation [layers][2][B][KV][S_max][HD], positions 0 .. len-1, and pos[row] = len - 1.  The table travels by value in the
+// kernel arguments (as AppendRows does in attention.hip); several segments may name one source.  Grid x = the segments' chunks
+// of 256 16-byte vectors of one plane: a workgroup finds its segment by walking the table with its block index (scalar work)
+// and never straddles two.  For a fixed plane both sides are contiguous runs of len * HD elements, so consecutive lanes copy
+// consecutive vectors; a thread walks the planes four at a time (four loads in flight, then four stores).  No LDS.
+struct ForkRows {
+    const bf16_t* src[16];   // parked history of the segment
+    int row[16];             // batch row of the caches
+    int len[16];             // positions (0 from R on)
+};
+
+template <int HD>
+__global__ __launch_bounds__(256) void kv_fork_rows_kernel(ForkRows a, bf16_t* __restrict__ kv, int* __restrict__ pos, int planes,
+                                                           int B, int KV, int S_max) {
+    constexpr int VPR = HD / 8;                                    // 16-byte vectors per position
+    int t = blockIdx.x, row = 0, len = 0, chunk = 0;
+    const bf16_t* src = nullptr;
+    bool found = false;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int nc = (a.len[r] * VPR + 255) >> 8;
+        if (!found && t < nc) {
+            src = a.src[r]; row = a.row[r]; len = a.len[r]; chunk = t;
+            found = true;
+        }
+        if (!found) t -= nc;
+    }
+    if (!found) return;                                            // (the grid is exactly the chunks: not reached)
+    if (chunk == 0 && blockIdx.y == 0 && threadIdx.x == 0) pos[row] = len - 1;
+    const int v = chunk * 256 + threadIdx.x;
+    if (v >= len * VPR) return;
+    const int gy = gridDim.y;
+    for (int hp = blockIdx.y; hp < planes; hp += 4 * gy) {         // hp = (layer * 2 + plane) * KV + kv head
+        U4 u[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (hp + j * gy < planes) u[j] = *reinterpret_cast<const U4*>(src + (size_t)(hp + j * gy) * len * HD + (size_t)v * 8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int h = hp + j * gy;
+            if (h < planes) {
+                const int lp = h / KV, kvh = h - lp * KV;
+                *reinterpret_cast<U4*>(kv + (((size_t)lp * B + row) * KV + kvh) * S_max * HD + (size_t)v * 8) = u[j];
+            }
+        }
+    }
+}
+
 // one query position against the cache: block per (b, q-head); the scores of all S_max <= 8192 keys live in LDS (the launcher sizes it).
 // table != NULL fuses what used to be two more launches per layer: the new position's q and k heads are rotated here
 // (torchtune RoPE on interleaved pairs, same arithmetic and bf16 rounding as rope_kernel), and the first q-head block of
@@ -2118,6 +2167,41 @@ extern "C" int csm_kv_shift(const void* src, void* dst, const float* rope_table,
     else
         hipLaunchKernelGGL((kv_shift_kernel<128>), grid, dim3(256), 0, stream, (const bf16_t*)src, (bf16_t*)dst, trow, planes, KV, len, keep, drop);
     CSM_CHECK_LAUNCH("csm_kv_shift");
+    return 0;
+}
+
+extern "C" int csm_kv_fork_rows(const void* const* src, void* kv, int* pos, const int* rows, const int* len, int R, int layers, int B,
+                                 int KV, int HD, int S_max, hipStream_t stream) {
+    CSM_REQUIRE(src && kv && pos && rows && len, "csm_kv_fork_rows: null pointer");
+    CSM_REQUIRE(R >= 1 && R <= 16, "csm_kv_fork_rows: %d segments (1 to 16)", R);
+    CSM_REQUIRE(HD == 64 || HD == 128, "csm_kv_fork_rows: head_dim %d unsupported", HD);
+    CSM_REQUIRE(layers >= 1 && B >= 1 && KV >= 1 && S_max >= 1 && S_max <= (1 << 24) && (long long)layers * 2 * KV <= 0x7fffffffLL,
+                "csm_kv_fork_rows: bad shape layers=%d B=%d KV=%d S_max=%d", layers, B, KV, S_max);
+    const uintptr_t d0 = (uintptr_t)kv;
+    const size_t dbytes = (size_t)layers * 2 * B * KV * S_max * HD * sizeof(bf16_t);
+    CSM_REQUIRE((d0 & 15) == 0, "csm_kv_fork_rows: the cache must be 16-byte aligned");
+    const int planes = layers * 2 * KV;
+    ForkRows a = {};
+    unsigned chunks = 0;
+    for (int r = 0; r < R; ++r) {
+        CSM_REQUIRE(src[r], "csm_kv_fork_rows: segment %d: null pointer", r);
+        CSM_REQUIRE(len[r] >= 1 && len[r] <= S_max, "csm_kv_fork_rows: segment %d: %d positions outside 1 .. S_max = %d", r, len[r], S_max);
+        CSM_REQUIRE(rows[r] >= 0 && rows[r] < B, "csm_kv_fork_rows: segment %d: batch row %d outside the caches (%d rows)", r, rows[r], B);
+        for (int q = 0; q < r; ++q)
+            CSM_REQUIRE(rows[q] != rows[r], "csm_kv_fork_rows: batch row %d appears in two segments (%d and %d)", rows[r], q, r);
+        const uintptr_t s0 = (uintptr_t)src[r];
+        CSM_REQUIRE((s0 & 15) == 0, "csm_kv_fork_rows: segment %d: the source must be 16-byte aligned", r);
+        const size_t sbytes = (size_t)planes * len[r] * HD * sizeof(bf16_t);
+        CSM_REQUIRE(s0 + sbytes <= d0 || d0 + dbytes <= s0, "csm_kv_fork_rows: segment %d: the source overlaps the cache", r);
+        a.src[r] = (const bf16_t*)src[r]; a.row[r] = rows[r]; a.len[r] = len[r];
+        chunks += (unsigned)((len[r] * (HD / 8) + 255) / 256);
+    }
+    const dim3 grid(chunks, (unsigned)((planes + 3) / 4 < 65535 ? (planes + 3) / 4 : 65535));
+    if (HD == 64)
+        hipLaunchKernelGGL((kv_fork_rows_kernel<64>), grid, dim3(256), 0, stream, a, (bf16_t*)kv, pos, planes, B, KV, S_max);
+    else
+        hipLaunchKernelGGL((kv_fork_rows_kernel<128>), grid, dim3(256), 0, stream, a, (bf16_t*)kv, pos, planes, B, KV, S_max);
+    CSM_CHECK_LAUNCH("csm_kv_fork_rows");
     return 0;
 }
 

@@ -406,6 +406,17 @@ int csm_kv_append(const void* qkv, void* kcache, void* vcache, const int* pos, i
  * drop >= table_rows, src or dst not 16-byte aligned, overlapping ranges. */
 int csm_kv_shift(const void* src, void* dst, const float* rope_table, int table_rows, int layers, int KV, int HD, int len, int keep,
                  int drop, csm_stream_t stream);
+/* The rows form of DecodeState.resume_row: R (1 .. 16) parked histories into R rows of a stack's cache allocation in ONE launch.
+ * Segment r: src[r] bf16 [layers][2][KV][len[r]][HD] (what DecodeState.park_row returns) goes to positions 0 .. len[r]-1 of batch
+ * row rows[r] of kv bf16 [layers][2][B][KV][S_max][HD], bit for bit, and pos[rows[r]] = len[r] - 1 (a device vector of B ints) is
+ * written by the same launch.  Nothing else is written: not the row's positions from len[r] on, not another row, not another
+ * row's pos.  The same source may be named by several segments (one voice prompt forked into many requests).  src / rows / len
+ * are HOST arrays of R entries: they travel by value in the kernel arguments (no device table, no copy, no synchronisation).
+ * Returns 1 (nothing launched) for a null pointer (src[r] included), R outside 1 .. 16, len[r] outside 1 .. S_max, a row outside
+ * 0 .. B-1 or named twice, HD other than 64 / 128, layers / B / KV / S_max < 1, a source or cache that is not 16-byte aligned, a
+ * source that overlaps the cache. */
+int csm_kv_fork_rows(const void* const* src, void* kv, int* pos, const int* rows, const int* len, int R, int layers, int B, int KV,
+                     int HD, int S_max, csm_stream_t stream);
 /* out[b][h*HD..] = softmax(q . K[0..pos[b]]^T / sqrt(HD)) V   for the single query row in qkv[b].  HD 64 or 128, H % KV == 0,
  * 1 <= S_max <= 8192 (the scores live in LDS), ld % 8 == 0 (16-byte loads from qkv + b * ld) - anything else returns 1 */
 int csm_attn_decode(const void* qkv, const void* kcache, const void* vcache, void* out, const int* pos, int B, int H, int KV,

@@ -28,7 +28,9 @@ csm_attn_fwd launch that would recompute the whole sequence.  GEN_RESAMPLE=1: th
 against the same step without the resampler (resample_main).  GEN_OVERFLOW=1: a conversation past the length limit
 (max_audio_length_ms = 90 000: 923 positions) - time to the first chunk of the overflowing turn under on_overflow="drop_oldest"
 (the kept history is prefilled again) and "shift" (the KV cache slides: csm_kv_shift) next to an in-limit turn, at B = 1 and for
-16 conversations that overflow at one boundary of the 16-slot server, plus csm_kv_shift alone (overflow_main)."""
+16 conversations that overflow at one boundary of the 16-slot server, plus csm_kv_shift alone (overflow_main).  GEN_VOICE=1: a voice
+prompt prefilled once (Generator.voice) against the same 5 s given as context: fork_rows against resume_row calls, the staggered
+served load, submit -> first chunk, and the steps that admit 1 and 16 joins (voice_main)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -673,6 +675,141 @@ def serve_main():
     tot = sum(r.audio().numel() for r in reqs) / 1920
     print(f"GEN_SERVE served 32 staggered requests of {min(lens)}..{max(lens)} frames, 5 s of context each, 16 slots: {tot:.0f} frames "
           f"in {dt:.3f} s -> {tot / dt:.1f} frames/s aggregate (Mimi encode, prefills, streaming decode included)", flush=True)
+
+
+def _spread(v):
+    v = sorted(v)
+    return f"median {v[len(v) // 2] * 1e3:.3f} ms ({v[0] * 1e3:.3f} .. {v[-1] * 1e3:.3f})"
+
+
+def voice_main():
+    """GEN_VOICE=1: a voice prompt prefilled once (Generator.voice) against the same segments given as context, on CSM-1B random
+    init, 16 slots, chunk_frames 4, 5 s of context - the two sides alternated, GEN_ROUNDS (default 3) repeats, each side's median
+    (min .. max).  (a) DecodeState.fork_rows (csm_kv_fork_rows, one launch) against R resume_row calls at R = 1 / 4 / 16, 80 and
+    441 positions; (b) aggregate frames/s of GEN_SERVE's staggered-arrival load with submit(context=) and submit(voice=);
+    (c) in that load, the time from the submit call to the request's first chunk; (d) the step that admits 1 join next to 15
+    running rows and the step that admits 16 joins (what a running row waits for its next chunk)."""
+    from csm.engine import DecodeState
+    dev = "cuda:0"
+    n = 4
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    codec = make_codec(dev)
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=codec)
+    # ---- (a) the kernel against the strided copies
+    with torch.inference_mode():
+        st = DecodeState(model.engine, 16)
+        kv = st.bb.kv
+        for length in (80, 441):
+            parked = torch.randn(kv.shape[0], 2, kv.shape[3], length, kv.shape[5], device=dev).to(kv.dtype)
+            for R in (1, 4, 16):
+                rows = list(range(R))
+
+                def resumes():
+                    for b in rows:
+                        st.resume_row(b, parked)
+
+                def fork():
+                    st.fork_rows(rows, [parked] * R)
+
+                for f in (resumes, fork):
+                    _timed(f, 5)
+                res = {"resume": [], "fork": []}
+                for _ in range(rounds):
+                    res["resume"].append(_timed(resumes, 50))
+                    res["fork"].append(_timed(fork, 50))
+                print(f"GEN_VOICE (a) {length} positions, R={R:2d}: fork_rows {_spread(res['fork'])}; {R} resume_row {_spread(res['resume'])}",
+                      flush=True)
+        del st, kv
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+    texts = [f"utterance number {i}: {text}" for i in range(16)]
+    frames = int(os.environ.get("GEN_FRAMES", 125))
+    voice = gen.voice(ctx)
+    print(f"GEN_VOICE voice of 5 s: {voice.positions} positions, {voice.nbytes / 1e6:.1f} MB", flush=True)
+    kinds = {"context": lambda: {"context": ctx}, "voice": lambda: {"context": [], "voice": voice}}
+
+    # ---- (b) + (c) the staggered load of GEN_SERVE: 8 requests at the start, two arrivals per chunk until all 32 are in
+    def load(kind):
+        srv = gen.serve(slots=16, chunk_frames=n)
+        lens = [frames // 4 + (i * 37) % (frames - frames // 4 + 1) for i in range(32)]
+        reqs, t_sub, t_first = [], {}, {}
+
+        def submit():
+            i = len(reqs)
+            t = time.perf_counter()
+            reqs.append(srv.submit(texts[i % 16], i, max_audio_length_ms=80 * lens[i], **kinds[kind]()))
+            t_sub[reqs[-1]] = t
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(8):
+            submit()
+        while srv.queued or srv.active or len(reqs) < 32:
+            for _ in range(2):
+                if len(reqs) < 32:
+                    submit()
+            out = srv.step()
+            torch.cuda.synchronize()                                    # (the chunk is heard: its samples are there)
+            t = time.perf_counter()
+            for r, _, _ in out:
+                t_first.setdefault(r, t)
+        dt = time.perf_counter() - t0
+        tot = sum(r.audio().numel() for r in reqs) / 1920
+        return tot / dt, sorted(t_first[r] - t_sub[r] for r in reqs)
+
+    for kind in kinds:
+        load(kind)                                                     # warm-up: graph capture, allocator
+    res = {k: [] for k in kinds}
+    for _ in range(rounds):
+        for kind in kinds:
+            res[kind].append(load(kind))
+    for kind in kinds:
+        fps = sorted(f for f, _ in res[kind])
+        lat = sorted(l[len(l) // 2] for _, l in res[kind])
+        worst = sorted(l[-1] for _, l in res[kind])
+        print(f"GEN_VOICE (b) 32 staggered requests, 5 s of context as {kind}: {fps[len(fps) // 2]:.1f} frames/s aggregate "
+              f"({fps[0]:.1f} .. {fps[-1]:.1f})", flush=True)
+        print(f"GEN_VOICE (c) submit call -> first chunk, as {kind}: median request {_spread(lat)}; slowest request {_spread(worst)}",
+              flush=True)
+
+    # ---- (d) the admitting step: 1 join next to 15 running rows, 16 joins at once
+    def one_join(kind):
+        srv = gen.serve(slots=16, chunk_frames=n)
+        for i in range(15):
+            srv.submit(texts[i], i, max_audio_length_ms=80 * 400, **kinds[kind]())
+        _timed(srv.step, 3)
+        plain = sorted(_timed(srv.step, 1) for _ in range(5))[2]
+        joins = []
+        for j in range(3):
+            srv.submit(f"late comer {j}: {text}", 3, max_audio_length_ms=80 * n, **kinds[kind]())      # leaves after one chunk
+            torch.cuda.synchronize()
+            joins.append(_timed(srv.step, 1))
+            assert srv.last_join_rows == 1
+            _timed(srv.step, 1)
+        return sorted(joins[1:])[0], plain                             # (the first join warms the 16-row frame tail up)
+
+    def sixteen_joins(kind):
+        srv = gen.serve(slots=16, chunk_frames=n)
+        for i in range(16):
+            srv.submit(texts[i], i, max_audio_length_ms=80 * 400, **kinds[kind]())
+        torch.cuda.synchronize()
+        t = _timed(srv.step, 1)
+        assert srv.last_join_rows == 16
+        return t
+
+    for kind in kinds:
+        one_join(kind), sixteen_joins(kind)
+    res = {k: {"one": [], "plain": [], "sixteen": []} for k in kinds}
+    for _ in range(rounds):
+        for kind in kinds:
+            j, p = one_join(kind)
+            res[kind]["one"].append(j)
+            res[kind]["plain"].append(p)
+            res[kind]["sixteen"].append(sixteen_joins(kind))
+    for kind in kinds:
+        r = res[kind]
+        print(f"GEN_VOICE (d) as {kind}: step with 1 join into 15 running rows {_spread(r['one'])} against {_spread(r['plain'])} "
+              f"without; step with 16 joins {_spread(r['sixteen'])}", flush=True)
 
 
 def serve_sampling_main():
@@ -1441,6 +1578,8 @@ def resample_main():
 
 
 def main():
+    if os.environ.get("GEN_VOICE") == "1":
+        return voice_main()
     if os.environ.get("GEN_RESAMPLE") == "1":
         return resample_main()
     if os.environ.get("GEN_OVERFLOW") == "1":
