@@ -23,30 +23,12 @@ from .sampling import (RowSampler, _is_number, check_filters, check_processors, 
 
 BF16 = torch.bfloat16
 F32 = torch.float32
-# SwiGLU fused into the GEMM epilogues (csm_gemm_bf16_ex).  A/B on one MI355X box, B=4 S=2048: 88.0 ms/step fused vs
-# 88.9 ms with the stand-alone kernels (the 256x256 GEMM runs one workgroup per CU, so most of the epilogue work is
-# exposed; the gain is what remains after that).  CSM_FUSE_SWIGLU=0 restores the stand-alone path for re-evaluation.
 import os as _os
-FUSE_SWIGLU = _os.environ.get("CSM_FUSE_SWIGLU", "1") == "1"
-FUSE_ROPE_BWD = _os.environ.get("CSM_FUSE_ROPE_BWD", "1") == "1"      # A/B switch: RoPE backward inside the attention backward
-FUSE_ROPE_FWD = _os.environ.get("CSM_FUSE_ROPE_FWD", "1") == "1"      # A/B switch: RoPE forward inside the q|k|v GEMM epilogue
-# A/B switch: dgrad + wgrad of a Linear layer as one launch with interleaved tiles (bit mask: 1 w2, 2 w13, 4 output_proj, 8 qkv).
-# OFF by default: measured on the B=4, S=2048 step (tools/probes/pair_ab.sh) every pairing is SLOWER than the two separate
-# launches (73.7 ms/step -> 75.7 with w2 alone, 77.4 w13, 77.1 output_proj, 78.3 qkv, 83.2 all four): de-phasing the CUs'
-# epilogues does not pay for two operand sets competing for each XCD's 4 MiB L2.  Kept as a tested entry point.
-PAIR_DX_DW = int(_os.environ.get("CSM_PAIR_DX_DW", "0"))
-# A/B switch: the two small weight gradients of a layer (attention output projection: 64 tiles, fused q|k|v: 96 tiles of
-# 256x256) as ONE launch after the attention backward, instead of split-K slabs + column sum and a 128x128-tile launch
-GROUP_ATTN_DW = _os.environ.get("CSM_GROUP_ATTN_DW", "1") == "1"
 # the attention projections' weight gradients of this many layers go out in one launch (1 = per layer); one layer's are 160
 # tiles of 256 x 256 - 0.63 of a round of the 256 CUs - three layers' 480: 1.9 rounds
 DEFER_ATTN_DW = int(_os.environ.get("CSM_DEFER_ATTN_DW", "3"))
 # the RMSNorm scale gradients' column sums of a layer (and of the layers whose attention gradients are deferred) in one launch
 DEFER_NORM_DW = _os.environ.get("CSM_DEFER_NORM_DW", "1") == "1"
-# the depth decoder's random frame subset is drawn on the host (A/B: 0 = device randperm)
-ROWS_ON_HOST = _os.environ.get("CSM_ROWS_ON_HOST", "1") == "1"
-# embedding backward: one sort of (row, source) keys instead of a stable argsort + two gathers (A/B: 0 = the latter)
-EMB_KEYSORT = _os.environ.get("CSM_EMB_KEYSORT", "1") == "1"
 # the depth decoder's fused attention + output projection takes its position as a launch argument (A/B: 0 = from device memory)
 DECODE_POS_HOST = _os.environ.get("CSM_DECODE_POS_HOST", "1") == "1"
 # LoRA groups ride on the frozen projections' GEMMs as K-extension operands (training/lora.py); 0 = per-adapter products
@@ -141,22 +123,82 @@ class _Stack:
 
     def __init__(self, model, prefix: str):
         self.m, self.prefix = model, prefix
-        self.c = model.bb if prefix == "backbone" else model.dc
+        self.c = c = model.bb if prefix == "backbone" else model.dc
         self.acts: List[Dict[str, torch.Tensor]] = []
+        hq, hk = c.num_heads * c.head_dim, c.num_kv_heads * c.head_dim
+        # The four Linear projections of a layer: (weight, LoRA group (training/lora.py GROUPS), the saved activation that is its
+        # input, {member module: its columns of the output}).  w13 keeps gate / up interleaved: g0, u0, g1, u1, ...
+        self.proj = {"qkv": ("attn.qkv", "attn_in", "xn", {"q_proj": slice(0, hq), "k_proj": slice(hq, hq + hk),
+                                                            "v_proj": slice(hq + hk, hq + 2 * hk)}),
+                     "o": ("attn.output_proj.weight", "attn_out", "o", {"output_proj": slice(None)}),
+                     "w13": ("mlp.w13", "mlp_in", "hn", {"w1": slice(0, None, 2), "w3": slice(1, None, 2)}),
+                     "w2": ("mlp.w2.weight", "mlp_out", "act", {"w2": slice(None)})}
 
     def w(self, name, grad=False):
         return self.m.block(f"{self.prefix}.{name}", grad)
+
+    def _pw(self, layer: int, p: str, grad=False):
+        """The weight (or weight gradient) of projection ``p`` of ``layer``."""
+        return self.w(f"layers.{layer}.{self.proj[p][0]}", grad)
 
     def _lora(self, layer: int, module: str):
         lo = self.m.lora
         return lo.get(self.prefix, layer, module) if lo is not None else None
 
-    def _group(self, layer: int, gname: str):
+    def _group(self, layer: int, gname: str, a=None):
         """(group, fused?) - the LoRA adapters of ``layer`` on one fused projection (lora.py GROUPS); fused = the whole
-        group enters that projection's GEMMs as one K-extension operand pair."""
+        group enters that projection's GEMMs as one K-extension operand pair.  ``a`` (the backward: the layer's saved
+        activations): fused only if the forward went that way and left its extension operand."""
         lo = self.m.lora
         G = lo.group(self.prefix, layer, gname) if lo is not None else None
-        return G, (G is not None and LORA_FUSE and G.fusable())
+        return G, (G is not None and LORA_FUSE and G.fusable() and (a is None or f"tx_{gname}" in a))
+
+    def _project(self, i, a, p, x, y, pin, sel, residual=None, **epilogue) -> bool:
+        """y = x W^T (+ residual) + the adapters' part, for projection ``p`` of layer ``i``; what the backward needs of the adapters
+        goes to ``a``.  A fusable group: its up-projections are extra k-steps of the same product, so ``epilogue`` (``rope=`` /
+        ``swiglu_act=``, ops.gemm_kext) sees the sum, and the answer is True.  Otherwise the adapters add to their columns of y one
+        by one, ``epilogue`` is NOT applied and the answer is False: the caller runs the stand-alone kernel."""
+        _, gname, _, members = self.proj[p]
+        G, fused = self._group(i, gname)
+        if fused:
+            a[f"tx_{gname}"] = G.project(x, pin=pin, sel=sel)
+            ops.gemm_kext(x, self._pw(i, p), y, a[f"tx_{gname}"], G.Bx, **({} if residual is None else {"R": residual}), **epilogue, pin=pin)
+            return True
+        ops.linear_fwd(x, self._pw(i, p), y, **({} if residual is None else {"residual": residual}), pin=pin)
+        for mod, cols in members.items():
+            ad = self._lora(i, mod)
+            if ad is None:
+                continue
+            if y[:, cols].stride(1) == 1:
+                a[f"t_{mod}"] = ad.forward(x, y[:, cols], pin=pin)
+            else:                                   # interleaved columns: the adapter's products want unit stride
+                tmp = torch.zeros(y[:, cols].shape, dtype=BF16, device=y.device)
+                a[f"t_{mod}"] = ad.forward(x, tmp, pin=pin)
+                y[:, cols] += tmp
+        return False
+
+    def _input_grad(self, i, a, p, dy, dx, sel, q=None, **epilogue):
+        """dx = dy W + the adapters' part (and the adapters' own gradients), for projection ``p`` of layer ``i``; fused, ``epilogue``
+        (``swiglu_bwd_gu=``) sees the sum.  ``q``: the projection's weight gradient is due right behind the input-gradient product.
+        (The two stay two launches: paired in one launch with interleaved tiles, ops.linear_dx_dw, every pairing measured SLOWER
+        on the B=4, S=2048 step - 73.7 ms/step -> 75.7 with w2 alone, 77.4 w13, 77.1 output_proj, 78.3 qkv, 83.2 all four:
+        de-phasing the CUs' epilogues does not pay for two operand sets competing for each XCD's 4 MiB L2.)"""
+        _, gname, xin, members = self.proj[p]
+        G, fused = self._group(i, gname, a)
+        if fused:
+            dts = G.backward(a[xin], dy, a[f"tx_{gname}"], sel=sel)
+            ops.gemm_kext(dy, self._pw(i, p), dx, dts, G.At, transB=True, **epilogue)
+        else:
+            assert not epilogue
+            ops.linear_dx(dy, self._pw(i, p), dx)
+        if q is not None:
+            q.ready(p, i, dy, a[xin], fused)
+        if not fused:
+            for mod, cols in members.items():
+                ad = self._lora(i, mod)
+                if ad is not None:
+                    dym = dy[:, cols]
+                    ad.backward(a[xin], dym if dym.stride(1) == 1 else dym.contiguous(), a[f"t_{mod}"], dx)
 
     # -------------------------------------------------------------------------------------------- forward
     def forward(self, x: torch.Tensor, B: int, S: int, save: bool, pos: Optional[torch.Tensor] = None,
@@ -179,6 +221,7 @@ class _Stack:
         pin = append is not None and isinstance(append[1], (list, tuple))
         H, KV, hd, F = c.num_heads, c.num_kv_heads, c.head_dim, c.intermediate_dim
         table = self.m.rope_table(self.prefix)
+        rope_in_gemm = fuse_rope and pos is None     # positions = arange(S): RoPE can ride in the q|k|v projection's epilogue
         self.acts = []
         for i in range(c.num_layers):
             if on_layer_start is not None:
@@ -188,25 +231,10 @@ class _Stack:
             rstd1 = torch.empty(M, dtype=F32, device=dev)
             ops.rmsnorm_fwd(x, self.w(f"layers.{i}.sa_norm.scale"), xn, rstd1, c.norm_eps)
             qkv = torch.empty(M, c.qkv_dim, dtype=BF16, device=dev)
-            hq, hk = H * hd, KV * hd
-            G, fused = self._group(i, "attn_in")
-            rope_in_gemm = FUSE_ROPE_FWD and fuse_rope and pos is None
-            if G is None and rope_in_gemm:
-                # positions = arange(S) and nothing to add before the rotation: RoPE rides in the projection's epilogue
-                ops.linear_rope_fwd(xn, self.w(f"layers.{i}.attn.qkv"), qkv, table, S, hq + hk, hd)
-            elif fused:
-                # the adapters' up-projections are extra k-steps of the same product, so the rotation still sees the sum
-                a["tx_attn_in"] = G.project(xn, pin=pin, sel=sel)
-                ops.gemm_kext(xn, self.w(f"layers.{i}.attn.qkv"), qkv, a["tx_attn_in"], G.Bx,
-                              rope=(table, S, hq + hk, hd) if rope_in_gemm else None, pin=pin)
-                if not rope_in_gemm:
-                    ops.rope(qkv, table, S, H + KV, hd, pos=pos)
-            else:
-                ops.linear_fwd(xn, self.w(f"layers.{i}.attn.qkv"), qkv, pin=pin)
-                for mod, lo_, hi_ in (("q_proj", 0, hq), ("k_proj", hq, hq + hk), ("v_proj", hq + hk, hq + 2 * hk)):
-                    ad = self._lora(i, mod)
-                    if ad is not None:
-                        a[f"t_{mod}"] = ad.forward(xn, qkv[:, lo_:hi_], pin=pin)
+            if rope_in_gemm and self._group(i, "attn_in")[0] is None:
+                ops.linear_rope_fwd(xn, self._pw(i, "qkv"), qkv, table, S, (H + KV) * hd, hd)
+            elif not (self._project(i, a, "qkv", xn, qkv, pin, sel, rope=(table, S, (H + KV) * hd, hd) if rope_in_gemm else None)
+                      and rope_in_gemm):
                 ops.rope(qkv, table, S, H + KV, hd, pos=pos)
             o = torch.empty(M, H * hd, dtype=BF16, device=dev)
             if append is None:
@@ -225,58 +253,32 @@ class _Stack:
                     ds, row, pos0 = append
                     ops.attn_append(qkv, ds.k[i], ds.v[i], o, row, pos0, H, KV, hd)
             h = torch.empty(M, d, dtype=BF16, device=dev)
-            G, fused = self._group(i, "attn_out")
-            if fused:
-                a["tx_attn_out"] = G.project(o, pin=pin, sel=sel)
-                ops.gemm_kext(o, self.w(f"layers.{i}.attn.output_proj.weight"), h, a["tx_attn_out"], G.Bx, R=x, pin=pin)
-            else:
-                ops.linear_fwd(o, self.w(f"layers.{i}.attn.output_proj.weight"), h, residual=x, pin=pin)
-                ad = self._lora(i, "output_proj")
-                if ad is not None:
-                    a["t_output_proj"] = ad.forward(o, h, pin=pin)
+            self._project(i, a, "o", o, h, pin, sel, residual=x)
             hn = torch.empty(M, d, dtype=BF16, device=dev)
             rstd2 = torch.empty(M, dtype=F32, device=dev)
             ops.rmsnorm_fwd(h, self.w(f"layers.{i}.mlp_norm.scale"), hn, rstd2, c.norm_eps)
             gu = torch.empty(M, 2 * F, dtype=BF16, device=dev)     # gate/up interleaved: g0,u0,g1,u1,...
             act = torch.empty(M, F, dtype=BF16, device=dev)
-            ad1, ad3 = self._lora(i, "w1"), self._lora(i, "w3")
             G, fused = self._group(i, "mlp_in")
-            if FUSE_SWIGLU and G is None:
-                ops.linear_swiglu_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, act, **ops._pin(pin))   # activation fused into the GEMM epilogue
-            elif FUSE_SWIGLU and fused:
-                # adapters on w1 / w3: extra k-steps of the w13 product (Bx rows interleaved like w13), SwiGLU from the sum
-                a["tx_mlp_in"] = G.project(hn, pin=pin, sel=sel)
-                ops.gemm_kext(hn, self.w(f"layers.{i}.mlp.w13"), gu, a["tx_mlp_in"], G.Bx, swiglu_act=act, pin=pin)
-            elif FUSE_SWIGLU and not any(ad is not None and ad.bias is not None for ad in (ad1, ad3)):
+            if G is None:
+                # SwiGLU in the GEMM epilogue (csm_gemm_bf16_ex).  A/B on one MI355X box, B=4 S=2048: 88.0 ms/step fused vs 88.9 ms
+                # with the stand-alone kernel (the 256x256 GEMM runs one workgroup per CU, so most of the epilogue work is exposed;
+                # the gain is what remains after that)
+                ops.linear_swiglu_fwd(hn, self._pw(i, "w13"), gu, act, **ops._pin(pin))
+            elif not fused and all(ad.bias is None for ad in G.adapters.values()):
                 # (dropout: one mask per adapter) the adapters' (alpha/r) t B^T is written FIRST, for both at once -
                 # t13 = the adapters' projections side by side, as the group's Bx expects them - and the frozen product takes it
                 # in through the residual port of its SwiGLU epilogue: gate/up = acc + R, act from the sum
-                rp = (ad1 or ad3).r
+                first = next(iter(G.adapters.values()))
                 t13 = torch.zeros(M, G.kx, dtype=BF16, device=dev)
                 for j, (mod, ad) in enumerate(G.adapters.items()):
-                    a[f"t_{mod}"] = ad.project(hn, t13[:, j * rp:(j + 1) * rp], pin=pin)
-                ops.gemm(t13, G.Bx, gu, None, alpha=(ad1 or ad3).scaling, **ops._pin(pin))
-                ops.linear_swiglu_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, act, residual=gu, **ops._pin(pin))
-            else:
-                ops.linear_fwd(hn, self.w(f"layers.{i}.mlp.w13"), gu, pin=pin)
-                if ad1 is not None or ad3 is not None:
-                    gv = gu.view(M, F, 2)
-                    for mod, col, ad in (("w1", 0, ad1), ("w3", 1, ad3)):
-                        if ad is not None:
-                            tmp = torch.zeros(M, F, dtype=BF16, device=dev)
-                            a[f"t_{mod}"] = ad.forward(hn, tmp, pin=pin)
-                            gv[:, :, col] += tmp
-                ops.swiglu_fwd(gu, act)
+                    a[f"t_{mod}"] = ad.project(hn, t13[:, j * first.r:(j + 1) * first.r], pin=pin)
+                ops.gemm(t13, G.Bx, gu, None, alpha=first.scaling, **ops._pin(pin))
+                ops.linear_swiglu_fwd(hn, self._pw(i, "w13"), gu, act, residual=gu, **ops._pin(pin))
+            elif not self._project(i, a, "w13", hn, gu, pin, sel, swiglu_act=act):
+                ops.swiglu_fwd(gu, act)              # adapters with a bias: gate / up are complete only after the last of them
             out = torch.empty(M, d, dtype=BF16, device=dev)
-            G, fused = self._group(i, "mlp_out")
-            if fused:
-                a["tx_mlp_out"] = G.project(act, pin=pin, sel=sel)
-                ops.gemm_kext(act, self.w(f"layers.{i}.mlp.w2.weight"), out, a["tx_mlp_out"], G.Bx, R=h, pin=pin)
-            else:
-                ops.linear_fwd(act, self.w(f"layers.{i}.mlp.w2.weight"), out, residual=h, pin=pin)
-                ad = self._lora(i, "w2")
-                if ad is not None:
-                    a["t_w2"] = ad.forward(act, out, pin=pin)
+            self._project(i, a, "w2", act, out, pin, sel, residual=h)
             if save:
                 a.update(x=x, xn=xn, rstd1=rstd1, qkv=qkv, o=o, lse=lse, h=h, hn=hn, rstd2=rstd2, gu=gu, act=act)
                 self.acts.append(a)
@@ -302,197 +304,144 @@ class _Stack:
         nb = ops.lib.csm_rmsnorm_bwd_blocks()
         parts = torch.empty(nb, d, dtype=F32, device=dev) if train_base else None
         delta = torch.empty(2, B, H, S, dtype=F32, device=dev)   # attention-backward scratch (-delta, -lse log2e)
-
-        pend_norm = []   # (per-block partial sums, scale gradient) of the layers' norms: reduced together, one launch per flush
+        q = _WgradQueue(self, M, train_base, acc, alpha, on_layer_done)
 
         def norm_bwd(x, name, rstd, dy, dres, defer=False):
             dx = torch.empty(M, d, dtype=BF16, device=dev)
-            if train_base and defer:
-                pp = torch.empty(nb, d, dtype=F32, device=dev)
-                ops.rmsnorm_bwd(x, self.w(name), rstd, dy, dx, dres, pp)
-                pend_norm.append((pp, self.w(name, grad=True)))
-                return dx
-            ops.rmsnorm_bwd(x, self.w(name), rstd, dy, dx, dres, parts)
+            pp = torch.empty(nb, d, dtype=F32, device=dev) if train_base and defer else parts
+            ops.rmsnorm_bwd(x, self.w(name), rstd, dy, dx, dres, pp)
             if train_base:
-                ops.colsum_bf16(parts, self.w(name, grad=True), accumulate=acc)
+                q.norm_ready(pp, self.w(name, grad=True), defer)
             return dx
-
-        def flush_norms():
-            if pend_norm:
-                ops.colsum_bf16_multi(pend_norm, accumulate=acc)
-                pend_norm.clear()
-
-        pend = []        # deferred (dqkv, xn, dW_qkv, dh, o, dW_o, layer): the operands stay alive until their launch
-        # A narrow stack (the depth decoder, d = 1024): every weight gradient but w13's is a fraction of a round of 256 x 256
-        # tiles (o_proj 16, q|k|v 24, w2 128) and would go through fp32 split-K slabs + a column-sum launch each.  Deferred to
-        # the end of the stack they are one launch of 160 tiles (attention, all layers) and one of 256 per two layers (w2).
-        small = (train_base and DEFER_ATTN_DW > 1 and GROUP_ATTN_DW and not PAIR_DX_DW and c.embed_dim < 2048 and M % 64 == 0
-                 and M >= 4096)
-        pend_w2 = []     # (dy, act, dW_w2) of a narrow stack
-
-        def flush_w2():
-            if pend_w2 and not (len(pend_w2) > 1 and ops.multi_linear_dw(pend_w2, accumulate=acc, alpha=alpha)):
-                for dy_, x_, g_ in pend_w2:
-                    ops.linear_dw(dy_, x_, g_, accumulate=acc, alpha=alpha)
-            pend_w2.clear()
-
-        def flush_attn_dw():
-            for c0 in range(0, len(pend), 6):                # at most 12 products per launch
-                chunk = pend[c0:c0 + 6]
-                probs = []
-                for t in chunk:
-                    probs += [(t[0], t[1], t[2]), (t[3], t[4], t[5])]
-                if not (len(chunk) > 1 and ops.multi_linear_dw(probs, accumulate=acc, alpha=alpha)):
-                    for dq_, xn_, gq_, dh_, o_, go_, _ in chunk:
-                        if not ops.two_linear_dw(dq_, xn_, gq_, dh_, o_, go_, accumulate=acc, alpha=alpha):
-                            ops.linear_dw(dh_, o_, go_, accumulate=acc, alpha=alpha)
-                            ops.linear_dw(dq_, xn_, gq_, accumulate=acc, alpha=alpha)
-            flush_w2()
-            flush_norms()
-            if on_layer_done is not None:
-                for t in pend:
-                    on_layer_done(self.prefix, t[6])
-            pend.clear()
 
         dx = norm_bwd(self.final["x"], "norm.scale", self.final["rstd"], dxf, None)
         for i in reversed(range(c.num_layers)):
             a = self.acts[i]
-            deferred = False
-            hq, hk = H * hd, KV * hd
             # ---- MLP: out = h + w2(act)
             dgu = torch.empty(M, 2 * F, dtype=BF16, device=dev)
-            ad = self._lora(i, "w2")
-            G, fused = self._group(i, "mlp_out")
-            fused = fused and "tx_mlp_out" in a
-            w2_done = False
-            if FUSE_SWIGLU and ad is None and train_base and (PAIR_DX_DW & 1):
-                # dgrad (with the SwiGLU backward in its epilogue) and wgrad of w2 share dx and nothing else: one launch
-                w2_done = ops.linear_dx_dw(dx, self.w(f"layers.{i}.mlp.w2.weight"), dgu, a["act"], self.w(f"layers.{i}.mlp.w2.weight", True),
-                                           accumulate=acc, alpha=alpha, swiglu_gu=a["gu"])
-            if w2_done:
-                pass
-            elif FUSE_SWIGLU and ad is None:
-                ops.linear_dx_swiglu_bwd(dx, self.w(f"layers.{i}.mlp.w2.weight"), a["gu"], dgu)   # d(act) never stored
-            elif FUSE_SWIGLU and fused:
+            G, fused = self._group(i, "mlp_out", a)
+            if G is None:
+                ops.linear_dx_swiglu_bwd(dx, self._pw(i, "w2"), a["gu"], dgu)   # d(act) never stored
+            elif fused:
                 # d(act) = dx w2 + (s dx Bx) At^T inside one product, SwiGLU backward in its epilogue
-                dts = G.backward(a["act"], dx, a["tx_mlp_out"], sel=sel)
-                ops.gemm_kext(dx, self.w(f"layers.{i}.mlp.w2.weight"), dgu, dts, G.At, transB=True, swiglu_bwd_gu=a["gu"])
+                self._input_grad(i, a, "w2", dx, dgu, sel, swiglu_bwd_gu=a["gu"])
             else:
                 dact = torch.empty(M, F, dtype=BF16, device=dev)
-                if fused:
-                    dts = G.backward(a["act"], dx, a["tx_mlp_out"], sel=sel)
-                    ops.gemm_kext(dx, self.w(f"layers.{i}.mlp.w2.weight"), dact, dts, G.At, transB=True)
-                else:
-                    ops.linear_dx(dx, self.w(f"layers.{i}.mlp.w2.weight"), dact)
-                    if ad is not None:
-                        ad.backward(a["act"], dx, a["t_w2"], dact)
+                self._input_grad(i, a, "w2", dx, dact, sel)
                 ops.swiglu_bwd(a["gu"], dact, dgu)
                 del dact
-            if train_base and not w2_done:
-                if small:
-                    pend_w2.append((dx, a["act"], self.w(f"layers.{i}.mlp.w2.weight", True)))
-                    if len(pend_w2) == 2:
-                        flush_w2()
-                else:
-                    ops.linear_dw(dx, a["act"], self.w(f"layers.{i}.mlp.w2.weight", True), accumulate=acc, alpha=alpha)
+            q.ready("w2", i, dx, a["act"])
             dhn = torch.empty(M, d, dtype=BF16, device=dev)
-            G, fused = self._group(i, "mlp_in")
-            fused = fused and "tx_mlp_in" in a
-            if fused:
-                dts = G.backward(a["hn"], dgu, a["tx_mlp_in"], sel=sel)
-                ops.gemm_kext(dgu, self.w(f"layers.{i}.mlp.w13"), dhn, dts, G.At, transB=True)
-                if train_base:
-                    ops.linear_dw(dgu, a["hn"], self.w(f"layers.{i}.mlp.w13", True), accumulate=acc, alpha=alpha)
-            else:
-                if not (train_base and (PAIR_DX_DW & 2) and ops.linear_dx_dw(dgu, self.w(f"layers.{i}.mlp.w13"), dhn, a["hn"],
-                                                                            self.w(f"layers.{i}.mlp.w13", True), accumulate=acc, alpha=alpha)):
-                    ops.linear_dx(dgu, self.w(f"layers.{i}.mlp.w13"), dhn)
-                    if train_base:
-                        ops.linear_dw(dgu, a["hn"], self.w(f"layers.{i}.mlp.w13", True), accumulate=acc, alpha=alpha)
-                for mod, col in (("w1", 0), ("w3", 1)):
-                    ad = self._lora(i, mod)
-                    if ad is not None:
-                        ad.backward(a["hn"], dgu.view(M, F, 2)[:, :, col].contiguous(), a[f"t_{mod}"], dhn)
+            self._input_grad(i, a, "w13", dgu, dhn, sel, q)
             del dgu
             dh = norm_bwd(a["h"], f"layers.{i}.mlp_norm.scale", a["rstd2"], dhn, dx, defer=DEFER_NORM_DW)   # + residual path
             # ---- attention: h = x + output_proj(o)
             do = torch.empty(M, H * hd, dtype=BF16, device=dev)
-            group_dw = False
-            G, fused = self._group(i, "attn_out")
-            fused = fused and "tx_attn_out" in a
-            if fused:
-                dts = G.backward(a["o"], dh, a["tx_attn_out"], sel=sel)
-                ops.gemm_kext(dh, self.w(f"layers.{i}.attn.output_proj.weight"), do, dts, G.At, transB=True)
-                if train_base:
-                    ops.linear_dw(dh, a["o"], self.w(f"layers.{i}.attn.output_proj.weight", True), accumulate=acc, alpha=alpha)
-            else:
-                if not (train_base and (PAIR_DX_DW & 4) and ops.linear_dx_dw(dh, self.w(f"layers.{i}.attn.output_proj.weight"), do, a["o"],
-                                                                            self.w(f"layers.{i}.attn.output_proj.weight", True),
-                                                                            accumulate=acc, alpha=alpha)):
-                    ops.linear_dx(dh, self.w(f"layers.{i}.attn.output_proj.weight"), do)
-                    # (the output projection's dW waits for the q|k|v projection's below when the two can share one launch)
-                    group_dw = train_base and GROUP_ATTN_DW and not (PAIR_DX_DW & 8) and M % 64 == 0 and M >= 4096 and (c.embed_dim >= 2048 or small)
-                    if train_base and not group_dw:
-                        ops.linear_dw(dh, a["o"], self.w(f"layers.{i}.attn.output_proj.weight", True), accumulate=acc, alpha=alpha)
-                ad = self._lora(i, "output_proj")
-                if ad is not None:
-                    ad.backward(a["o"], dh, a["t_output_proj"], do)
+            self._input_grad(i, a, "o", dh, do, sel, q)
             dqkv = torch.empty(M, c.qkv_dim, dtype=BF16, device=dev)
             if seg is not None:                   # packed rows: segment-masked kernels, segment-local positions
                 ops.attn_bwd_seg(a["qkv"], a["o"], do, a["lse"], dqkv, delta, seg.seg_start, seg.seg_end, B, S, H, KV, hd)
                 ops.rope(dqkv, table, S, H + KV, hd, pos=seg.pos, inverse=True)
-            elif pos is None and FUSE_ROPE_BWD:   # positions = arange(S): the RoPE backward rides in the dQ / dK epilogues
+            elif pos is None:                     # positions = arange(S): the RoPE backward rides in the dQ / dK epilogues
                 ops.attn_bwd(a["qkv"], a["o"], do, a["lse"], dqkv, delta, B, S, H, KV, hd, rope_table=table)
             else:
                 ops.attn_bwd(a["qkv"], a["o"], do, a["lse"], dqkv, delta, B, S, H, KV, hd)
                 ops.rope(dqkv, table, S, H + KV, hd, pos=pos, inverse=True)
             dxn = torch.empty(M, d, dtype=BF16, device=dev)
-            G, fused = self._group(i, "attn_in")
-            fused = fused and "tx_attn_in" in a
-            if fused:
-                dts = G.backward(a["xn"], dqkv, a["tx_attn_in"], sel=sel)
-                ops.gemm_kext(dqkv, self.w(f"layers.{i}.attn.qkv"), dxn, dts, G.At, transB=True)
-                if train_base:
-                    if group_dw:
-                        ops.linear_dw(dh, a["o"], self.w(f"layers.{i}.attn.output_proj.weight", True), accumulate=acc, alpha=alpha)
-                    ops.linear_dw(dqkv, a["xn"], self.w(f"layers.{i}.attn.qkv", True), accumulate=acc, alpha=alpha)
-            else:
-                if not (train_base and (PAIR_DX_DW & 8) and ops.linear_dx_dw(dqkv, self.w(f"layers.{i}.attn.qkv"), dxn, a["xn"],
-                                                                            self.w(f"layers.{i}.attn.qkv", True), accumulate=acc, alpha=alpha)):
-                    ops.linear_dx(dqkv, self.w(f"layers.{i}.attn.qkv"), dxn)
-                    if train_base and group_dw and DEFER_ATTN_DW > 1:
-                        pend.append((dqkv, a["xn"], self.w(f"layers.{i}.attn.qkv", True), dh, a["o"],
-                                     self.w(f"layers.{i}.attn.output_proj.weight", True), i))
-                        deferred = True
-                    elif train_base and group_dw and ops.two_linear_dw(dqkv, a["xn"], self.w(f"layers.{i}.attn.qkv", True), dh, a["o"],
-                                                                     self.w(f"layers.{i}.attn.output_proj.weight", True), accumulate=acc, alpha=alpha):
-                        pass
-                    elif train_base:
-                        if group_dw:
-                            ops.linear_dw(dh, a["o"], self.w(f"layers.{i}.attn.output_proj.weight", True), accumulate=acc, alpha=alpha)
-                        ops.linear_dw(dqkv, a["xn"], self.w(f"layers.{i}.attn.qkv", True), accumulate=acc, alpha=alpha)
-                for mod, lo_, hi_ in (("q_proj", 0, hq), ("k_proj", hq, hq + hk), ("v_proj", hq + hk, hq + 2 * hk)):
-                    ad = self._lora(i, mod)
-                    if ad is not None:
-                        ad.backward(a["xn"], dqkv[:, lo_:hi_], a[f"t_{mod}"], dxn)
+            self._input_grad(i, a, "qkv", dqkv, dxn, sel, q)
             dx = norm_bwd(a["x"], f"layers.{i}.sa_norm.scale", a["rstd1"], dxn, dh, defer=DEFER_NORM_DW)
             self.acts[i] = None
-            if deferred:
-                # (layer 0 goes alone: what is launched last is what a data-parallel all-reduce cannot hide behind compute;
-                #  a narrow stack keeps everything to its end - the wide stack's backward follows and hides its all-reduce)
-                if not small and (len(pend) >= DEFER_ATTN_DW or i <= 1):
-                    flush_attn_dw()
-            else:
-                if pend or pend_w2:
-                    flush_attn_dw()          # (mixed stacks: nothing of an earlier layer may stay pending behind this layer's hook)
-                flush_norms()                # this layer's two norms in one launch
-                if on_layer_done is not None:
-                    on_layer_done(self.prefix, i)
-        if pend or pend_w2:
-            flush_attn_dw()
-        flush_norms()
+            q.layer_done(i)
+        q.flush()
         self.acts = []
         return dx
+
+
+class _WgradQueue:
+    """The weight gradients of one ``_Stack.backward``: each goes out when it is ready (``ready`` / ``norm_ready``) or waits here
+    for others to share a launch with, until ``flush``.  What waits:
+
+    - the two attention projections' of a layer (output projection: 64 tiles of 256 x 256, fused q|k|v: 96) go out as ONE launch
+      instead of split-K slabs + column sum and a 128 x 128-tile launch - and with DEFER_ATTN_DW > 1 that many layers' together;
+    - a narrow stack (the depth decoder, d = 1024): every weight gradient but w13's is a fraction of a round of 256 x 256 tiles
+      (o_proj 16, q|k|v 24, w2 128) and would go through fp32 split-K slabs + a column-sum launch each.  Kept to the end of the
+      stack they are one launch of 160 tiles (attention, all layers) and one of 256 per two layers (w2);
+    - the RMSNorm scale gradients' column sums (DEFER_NORM_DW): one launch per flush.
+    The operands stay alive until their launch.  ``on_layer_done`` hears of a layer once nothing of it is left here."""
+
+    def __init__(self, stack, M, train_base, acc, alpha, on_layer_done):
+        self.stack, self.train, self.on_layer_done = stack, train_base, on_layer_done
+        self.acc, self.kw = acc, dict(accumulate=acc, alpha=alpha)
+        grouped = train_base and M % 64 == 0 and M >= 4096           # what the grouped weight-gradient kernels take
+        self.small = grouped and DEFER_ATTN_DW > 1 and stack.c.embed_dim < 2048
+        self.pair = grouped and (stack.c.embed_dim >= 2048 or self.small)
+        self.held, self.deferred = None, False     # this layer's output-projection problem waiting for its q|k|v's; the pair waits
+        self.attn, self.w2, self.norms = [], [], []  # (dqkv, xn, dW_qkv, dh, o, dW_o, layer) / (dy, act, dW_w2) / (partial sums, dscale)
+
+    def ready(self, p, i, dy, x, fused=False):
+        """The weight gradient dy^T x of projection ``p`` of layer ``i`` can be launched; ``fused``: its input gradient took the
+        LoRA group along - an attention projection's gradient then goes out at once, whatever else holds."""
+        if not self.train:
+            return
+        job = (dy, x, self.stack._pw(i, p, True))
+        if p == "w2" and self.small:
+            self.w2.append(job)
+            if len(self.w2) == 2:
+                self._flush_w2()
+        elif p == "o" and self.pair and not fused:
+            self.held = job
+        elif p == "qkv" and self.held is not None:
+            held, self.held = self.held, None
+            if not fused and DEFER_ATTN_DW > 1:
+                self.attn.append(job + held + (i,))
+                self.deferred = True
+            elif fused or not ops.two_linear_dw(*job, *held, **self.kw):
+                ops.linear_dw(*held, **self.kw)
+                ops.linear_dw(*job, **self.kw)
+        else:
+            ops.linear_dw(*job, **self.kw)
+
+    def norm_ready(self, partials, dscale, defer):
+        if defer:
+            self.norms.append((partials, dscale))
+        else:
+            ops.colsum_bf16(partials, dscale, accumulate=self.acc)
+
+    def layer_done(self, i):
+        """Layer ``i`` has issued everything else.  (Layer 0 goes alone: what is launched last is what a data-parallel all-reduce
+        cannot hide behind compute; a narrow stack keeps everything to its end - the wide stack's backward follows and hides its
+        all-reduce.  Mixed stacks: nothing of an earlier layer may stay pending behind this layer's hook.)"""
+        if self.deferred:
+            self.deferred = False
+            if not self.small and (len(self.attn) >= DEFER_ATTN_DW or i <= 1):
+                self.flush()
+        else:
+            self.flush()
+            if self.on_layer_done is not None:
+                self.on_layer_done(self.stack.prefix, i)
+
+    def _flush_w2(self):
+        if self.w2 and not (len(self.w2) > 1 and ops.multi_linear_dw(self.w2, **self.kw)):
+            for job in self.w2:
+                ops.linear_dw(*job, **self.kw)
+        self.w2 = []
+
+    def flush(self):
+        for c0 in range(0, len(self.attn), 6):               # at most 12 products per launch
+            chunk = self.attn[c0:c0 + 6]
+            if not (len(chunk) > 1 and ops.multi_linear_dw([t[k:k + 3] for t in chunk for k in (0, 3)], **self.kw)):
+                for t in chunk:
+                    if not ops.two_linear_dw(*t[:6], **self.kw):
+                        ops.linear_dw(*t[3:6], **self.kw)
+                        ops.linear_dw(*t[:3], **self.kw)
+        self._flush_w2()
+        if self.norms:
+            ops.colsum_bf16_multi(self.norms, accumulate=self.acc)       # the layers' norms in one launch
+            self.norms = []
+        if self.on_layer_done is not None:
+            for t in self.attn:
+                self.on_layer_done(self.stack.prefix, t[6])
+        self.attn = []
 
 
 class Segments:
@@ -623,9 +572,8 @@ class Engine:
         if adapter_ids is None:
             raise ValueError(f"model.lora stacks {lo.n_adapters} adapter sets: pass adapter_ids (one per example, -1 = base model "
                              "only), or export(a) one set and attach it alone")
-        if not (LORA_FUSE and FUSE_SWIGLU):
-            raise NotImplementedError("a stack of adapter sets trains through the K-extension path only: unset CSM_LORA_FUSE=0 / "
-                                      "CSM_FUSE_SWIGLU=0")
+        if not LORA_FUSE:
+            raise NotImplementedError("a stack of adapter sets trains through the K-extension path only: unset CSM_LORA_FUSE=0")
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             raise NotImplementedError("a stack of adapter sets under a process group is not built (data parallel would all-reduce "
                                       "the stack): train it in one process")
@@ -672,7 +620,7 @@ class Engine:
             if t0 is not None:
                 r = r[t0[r] >= 0]
             return r.to(torch.int32).contiguous()
-        if t0 is None and self.m.acoustic_mode != "all" and ROWS_ON_HOST:
+        if t0 is None and self.m.acoustic_mode != "all":
             # a random subset of all frames: drawn on the host (torch's CPU generator) and copied over - one small copy instead of
             # ~20 launches of device randperm / sort / index kernels in front of the depth decoder
             n_all = B * (S - 1)
@@ -842,7 +790,7 @@ class Engine:
             rows = torch.cat([rows, (codes[:, :K - 1] + d["off"]).reshape(-1)])
             src = torch.cat([src, d["src"]])
             n_src = M + N * K
-        if n_src <= (1 << 20) and EMB_KEYSORT:
+        if n_src <= (1 << 20):
             # (row, source) pairs are unique, so ONE key sort gives the order a stable sort by row gives (sources ascend within a
             # row exactly as the occurrences were listed) - a radix sort of 64-bit keys instead of a stable merge sort (18 launches)
             # plus two gathers

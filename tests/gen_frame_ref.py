@@ -36,36 +36,36 @@ stated exactly: an idle row's device position is IDLE_PIN = 1, its host mirror `
 cache slot of it but slot 1 is bit-unchanged, and its logits are not judged (the contract calls them meaningless).
 
 Hooks (``R``), with the line of csm/engine.py (E), the contract line of decode_gemv_ref.py (G) / decode_attn_ref.py (A), or the
-hook of train_step_ref.py (T) each mirrors.  The fp32 logits (E971, E981, E1022, E1045) are never rounded.
-  prompt side (``_prompt_stack``: forward values of T's hooks; E162-289)
-    h0            E1407 embed_fwd (T h0)
-    xn, hn        E189, E239 (T xn, hn)
-    q, k          prefill has pos None: RoPE in the projection's epilogue, ONE rounding after the rotation (E193-201, T "q, k
+hook of train_step_ref.py (T) each mirrors.  The fp32 logits (E919, E929, E970, E993) are never rounded.
+  prompt side (``_prompt_stack``: forward values of T's hooks; E204-291)
+    h0            E1355 embed_fwd (T h0)
+    xn, hn        E232, E259 (T xn, hn)
+    q, k          prefill has pos None: RoPE in the projection's epilogue, ONE rounding after the rotation (E234-237, E164-165, T "q, k
                   fused") - also with a fused adapter group.  A group with a bias takes the per-adapter path and the stand-alone
-                  RoPE kernel: rounded before AND after the rotation (E205-210).  v: one rounding.
-    adapters      fused (no bias): tx = bf16(s x At), then one product (E199-201, T "LoRA tx").  With a bias (lora.py forward):
+                  RoPE kernel: rounded before AND after the rotation (E167-178, E238).  v: one rounding.
+    adapters      fused (no bias): tx = bf16(s x At), then one product (E164-165, T "LoRA tx").  With a bias (lora.py forward):
                   y = bf16(base), t = bf16(x A^T), y = bf16(y + s t B^T), y = bf16(y + bias); on w1 / w3 through a zeroed tmp
-                  that is then added into the stored gate | up (E261-269), and SwiGLU reads the ROUNDED gate | up.
-    P, o          P rounded before the PV product (T ``_Attn``), o E211-217
-    h, out        one rounding of product + residual E227-233, E270-276
+                  that is then added into the stored gate | up (E167-178), and SwiGLU reads the ROUNDED gate | up.
+    P, o          P rounded before the PV product (T ``_Attn``), o E239-245
+    h, out        one rounding of product + residual E255-256, E280-281
     act           from the unrounded gate / up in the fused epilogue (T act)
-    xf            E284-286: the row ``_frame_tail_body`` reads as last_h
-  decode side (``_decode_step``: E1121-1148)
-    h0            E1720 embed_fwd into the persistent buffer
-    x^            G "RMSNorm prologue": bf16(x rstd w) of every product with a norm prologue (E1132, E1141), the head product on
-                  the un-normed decoder residual included (E981)
-    qkv           G plain: one rounding (E1132)
-    q, k          rounded before the rotation (they are read from the stored qkv) and once after it (the comment at E1041,
+    xf            E286-288: the row ``_frame_tail_body`` reads as last_h
+  decode side (``_decode_step``: E1069-1096)
+    h0            E1668 embed_fwd into the persistent buffer
+    x^            G "RMSNorm prologue": bf16(x rstd w) of every product with a norm prologue (E1080, E1089), the head product on
+                  the un-normed decoder residual included (E929)
+    qkv           G plain: one rounding (E1080)
+    q, k          rounded before the rotation (they are read from the stored qkv) and once after it (the comment at E989,
                   A ``rotate``); the cache holds the rotated bf16 k, the stored v (A ``ref_decode_attention``)
-    o             A ``ref_product``: the attention result rounded to bf16 (fused or not: E1136, E1139)
-    h, layer out  G residual: one rounding of product + residual (E1136 / E1140, E1143)
-    g, u, act     G SwiGLU: g, u rounded before SiLU, then act (E1141)
-    t             G lora_project: t = bf16(scale x^ At) (E1167, E1173); the extension and the bias join the sum BEFORE the
-                  epilogue's one rounding (G K-extension; FP8: the scaled base sum, E1169)
-    xf            the backbone's final norm is a stored tensor (E1147); the decoder's is folded into the head product (x^ above)
-    proj          E1775 / E1777: bf16 (the gathered embedding row is a bf16 value already)
-  recompute path (``use_kv_cache = False``, E1004-1049): the whole history through the prompt-side forward every frame, proj
-  E1040, the decoder through the training forward with the rotation UN-fused (E1043: before and after), xf stored (E284-286).
+    o             A ``ref_product``: the attention result rounded to bf16 (fused or not: E1084, E1087)
+    h, layer out  G residual: one rounding of product + residual (E1084 / E1088, E1091)
+    g, u, act     G SwiGLU: g, u rounded before SiLU, then act (E1089)
+    t             G lora_project: t = bf16(scale x^ At) (E1115, E1121); the extension and the bias join the sum BEFORE the
+                  epilogue's one rounding (G K-extension; FP8: the scaled base sum, E1117)
+    xf            the backbone's final norm is a stored tensor (E1095); the decoder's is folded into the head product (x^ above)
+    proj          E1723 / E1725: bf16 (the gathered embedding row is a bf16 value already)
+  recompute path (``use_kv_cache = False``, E952-997): the whole history through the prompt-side forward every frame, proj
+  E988, the decoder through the training forward with the rotation UN-fused (E991: before and after), xf stored (E286-288).
 
 Record (measured on this module alone; ``measure`` recomputes it and test_gen_frame_ref_cpu.py holds it to these):
   W = worst ratio over every case of CASES, eight stochastic draws, every vector, each draw judged against frame64 with the

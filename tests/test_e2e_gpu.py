@@ -495,8 +495,8 @@ def test_generate_frame_matches_reference_fixture(dev, use_graph):
             assert torch.equal(got, want_t), (use_graph, got.tolist(), want)
         else:
             # bf16 weights / activations against the reference's fp32: a near-tie in the top-k race can go the other way
-            # (which ones do depends on the last bf16 bit of the prefill - tools/probes/rope_ab.py shows two equally
-            # accurate RoPE placements flipping different ones); exact on at least 10 of the 12 row-frames
+            # (which ones do depends on the last bf16 bit of the prefill - two equally accurate RoPE placements, in the GEMM
+            # epilogue or as a kernel of its own, were seen flipping different ones); exact on at least 10 of the 12 row-frames
             bad_rows = int((got != want_t).any(dim=2).sum())
             assert bad_rows <= 2, (use_graph, bad_rows, got.tolist(), want)
             assert float((got == want_t).float().mean()) >= 0.9

@@ -20,38 +20,38 @@ Three evaluations of a ``Case``:
                               Every row is one or the other (asserted).  Prints ``RATIO <case> <tensor> <worst>``.
 
 Hooks (``_hook``: an autograd.Function that rounds its value in forward and/or the incoming gradient in backward), with the line
-of csm/engine.py (E) or csm/training/lora.py (L) whose store each mirrors.  fp32 tensors (logits E587-589 / E716-719, rows_loss) are
+of csm/engine.py (E) or csm/training/lora.py (L) whose store each mirrors.  fp32 tensors (logits E536-538 / E664-667, rows_loss) are
 never rounded in value; their gradients are where the engine stores them in bf16.
   value and gradient
-    h0            E581-583 embed_fwd           / dh0: the gradient the last norm_bwd returns, E478
-    xn, hn        E187-189, E237-239           / dxn E449-462, dhn E398-409
-    v             E190-205 (no rotation)       / dqkv E440-448
-    q, k fused    value AFTER the rotation, once (RoPE in the GEMM epilogue, E196 / E200-201); gradient BEFORE it, once (RoPE
-                  backward in the dQ / dK epilogue, E444-445).  The pre-rotation value and the post-rotation gradient are never
+    h0            E530-532 embed_fwd           / dh0: the gradient the last norm_bwd returns, E352
+    xn, hn        E230-232, E257-259           / dxn E350-351, dhn E334-335
+    v             E233-238 (no rotation)       / dqkv E341-349
+    q, k fused    value AFTER the rotation, once (RoPE in the GEMM epilogue, E235 / E236, E165); gradient BEFORE it, once (RoPE
+                  backward in the dQ / dK epilogue, E345-346).  The pre-rotation value and the post-rotation gradient are never
                   stored: no hook there.
-    q, k packed   (segment-local positions, E203 / E210, E442-443): value before AND after the rotation, gradient after AND
+    q, k packed   (segment-local positions, E238, E343-344): value before AND after the rotation, gradient after AND
                   before - the stand-alone RoPE kernel reads and writes bf16 both ways.
-    o             E211-217                     / do E419-432
-    h, out (x)    the residual sums, one rounding of x + product: E227-233, E270-276 / dh E417, dx E478 (one rounding of
+    o             E239-245                     / do E339-340
+    h, out (x)    the residual sums, one rounding of x + product: E255-256, E280-281 / dh E337, dx E352 (one rounding of
                   norm path + residual path, the fused norm_bwd)
-    xf, hidden    E284-286                     / dhid after rows_add_bf16 E800-801 (a bf16 read-modify-write: the hook on
+    xf, hidden    E286-288                     / dhid after rows_add_bf16 E748-749 (a bf16 read-modify-write: the hook on
                   hidden rounds the SUM of the two branches, each already rounded below)
-    seq           E709-710 (copies of bf16 values: the value rounding changes nothing) / dseq E783-784
-    x0            E711-712                     / dx0: the gradient decoder.backward returns, E781
+    seq           E657-658 (copies of bf16 values: the value rounding changes nothing) / dseq E731-732
+    x0            E659-660                     / dx0: the gradient decoder.backward returns, E729
   gradient only
-    logits        dlog E792-794, dl E769-771 (ce_fwd_bwd writes bf16 gradients of fp32 logits)
-    hidden -> head      dhid as linear_dx stores it, E795-796, before the rows_add
-    hidden -> decoder   position 0 of dseq, E783-784
+    logits        dlog E740-742, dl E717-719 (ce_fwd_bwd writes bf16 gradients of fp32 logits)
+    hidden -> head      dhid as linear_dx stores it, E743-744, before the rows_add
+    hidden -> decoder   position 0 of dseq, E731-732
     LoRA t = x A^T      dts = s dy Bx, L194-201 (the stored tensor is s dt; s is a power of two in every case here)
   value only
     LoRA tx = s x A^T   L177-188
-    act (SwiGLU)        E240-249.  The forward epilogue computes it from the fp32 gate / up (gemm_common.h epi_store), the backward
-                        epilogue reads the STORED bf16 gate | up and never stores d(act) (E375 / E379): ``_SwiGLU`` does exactly
+    act (SwiGLU)        E260-278.  The forward epilogue computes it from the fp32 gate / up (gemm_common.h epi_store), the backward
+                        epilogue reads the STORED bf16 gate | up and never stores d(act) (E324 / E327): ``_SwiGLU`` does exactly
                         that and rounds d(gate), d(up) = dgu once.
   inside attention (registers, not stores - the attention pins document them, train_attn_ref.py): P before the PV product, and in
   the backward P before dV and dS before dQ / dK; delta from the stored o.  ``_Attn``.
-  final stores    every weight gradient is rounded once where it is written: linear_dw E397-473 and E786 / E798, audio_head E777-779,
-                  colsum_bf16 E317 / E322, embed_bwd_sorted E854 (text and audio rows, the backbone and decoder sources summed in
+  final stores    every weight gradient is rounded once where it is written: linear_dw in ``_WgradQueue`` (E360-444) and E734 / E746, audio_head E725-727,
+                  colsum_bf16 E408 / E439, embed_bwd_sorted E802 (text and audio rows, the backbone and decoder sources summed in
                   fp32 first), skinny_wgrad L51-70.  A "live" buffer is accumulated INTO: the second micro-batch stores
                   round(stored + fp32 sum) - the second rounding.  An "overwrite" (stale buffer, acc=False) rounds the same sum.
 
