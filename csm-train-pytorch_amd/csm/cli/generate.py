@@ -41,6 +41,10 @@ def parse_args(argv=None):
                         "x * R (1.0: off)")
     p.add_argument("--repetition-window", type=int, default=64, metavar="W",
                    help="frames the repetition penalty looks back, 0..64 (default 64; a turn's window covers that turn only)")
+    p.add_argument("--typical-p", type=float, default=1.0, metavar="P",
+                   help="locally typical sampling, in (0, 1] (default 1.0: off): after the other filters, keep the codes whose "
+                        "surprise is closest to the entropy until their probability reaches P - it can drop the most likely code "
+                        "(all modes)")
     p.add_argument("--acoustic-temperature", type=float, default=None, metavar="T",
                    help="temperature of codebooks 1..K-1 (the acoustic ones; codebook 0 keeps --temperature)")
     p.add_argument("--acoustic-topk", type=int, default=None, metavar="K",
@@ -72,14 +76,16 @@ def parse_args(argv=None):
     p.add_argument("--serve-file", type=str, default=None,
                    help="JSON-lines file of utterances {\"text\", \"speaker\", \"adapter\"?: LoRA adapter file, \"seed\"?: int, "
                         "\"temperature\"?: float, \"topk\"?: int, \"top_p\"?: float, \"min_p\"?: float, \"repetition_penalty\"?: float, "
-                        "\"repetition_window\"?: int, \"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
+                        "\"repetition_window\"?: int, \"typical_p\"?: float, \"conversation\"?: id}: all are served as one running batch (Generator.serve) with the context of "
                         "--context-*; lines with the same conversation id are successive turns of one served conversation, in file "
                         "order (KV cache kept between them; adapter and seed of its first line); a line's temperature / topk hold for "
                         "that utterance or turn (default: --temperature / --topk; a file that names one is served with "
                         "row_sampling=True); likewise a line's top_p / min_p (default: --top-p / --min-p; a file that names one, or "
                         "a --top-p / --min-p that is not 1.0 / 0.0, is served with row_filters=True); a line's repetition_penalty / "
                         "repetition_window, and a list of one number per codebook for any of the four keys before them (a file or a "
-                        "command line that uses any of these, --acoustic-* included, is served with row_processors=True); one WAV "
+                        "command line that uses any of these, --acoustic-* included, is served with row_processors=True); a line's "
+                        "typical_p, a number or a list per codebook (a file that names one, or a --typical-p that is not 1.0, is "
+                        "served with row_typical=True); one WAV "
                         "per utterance, <output stem>_<i>.wav with i = 0, 1, ... counting the file's non-empty lines")
     p.add_argument("--cache-context", action="store_true",
                    help="--serve-file: prefill the --context-* segments once as a voice (Generator.voice; one per distinct adapter "
@@ -119,7 +125,8 @@ def parse_args(argv=None):
 def sampling_kw(args, codebooks):
     """The sampling keywords of the generate calls from the command line: --temperature / --topk / --top-p / --min-p, with
     --acoustic-temperature / --acoustic-topk expanded to one value per codebook (codebook 0 keeps the plain flag's), and
-    --repetition-penalty / --repetition-window only where they are not 1.0 / 64 - without the new flags, the call it was.
+    --repetition-penalty / --repetition-window only where they are not 1.0 / 64 and --typical-p only where it is not 1.0 - without
+    the new flags, the call it was.
     ``codebooks``: the model's K, or a callable that gives it (called only if an --acoustic-* flag needs it)."""
     kw = dict(temperature=args.temperature, topk=args.topk, top_p=args.top_p, min_p=args.min_p)
     if callable(codebooks) and (args.acoustic_temperature is not None or args.acoustic_topk is not None):
@@ -130,6 +137,8 @@ def sampling_kw(args, codebooks):
         kw["topk"] = [args.topk] + [args.acoustic_topk] * (codebooks - 1)
     if (args.repetition_penalty, args.repetition_window) != (1.0, 64):
         kw.update(repetition_penalty=args.repetition_penalty, repetition_window=args.repetition_window)
+    if getattr(args, "typical_p", 1.0) != 1.0:
+        kw["typical_p"] = args.typical_p
     return kw
 
 
@@ -217,7 +226,7 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
 def read_serve_file(path, codebooks=None):
     """--serve-file: one JSON object per non-empty line -> [{"text", "speaker", "adapter", "seed"}], plus "conversation" (a
     string), "temperature" (a float), "topk" (an int), "top_p" and "min_p" (floats), "repetition_penalty" (a float) and
-    "repetition_window" (an int) on the lines that carry those keys.  With ``codebooks`` (the model's K, or a callable that gives
+    "repetition_window" (an int) and "typical_p" (a float, or a list of K) on the lines that carry those keys.  With ``codebooks`` (the model's K, or a callable that gives
     it: called at the first list) the first four may also be a list of K numbers, one per codebook; a list of another length is
     refused here."""
     import json
@@ -240,14 +249,14 @@ def read_serve_file(path, codebooks=None):
             if not isinstance(d, dict) or not isinstance(d.get("text"), str):
                 raise ValueError(f"{path}:{i}: every line is a JSON object with a \"text\" string")
             unknown = set(d) - {"text", "speaker", "adapter", "seed", "conversation", "temperature", "topk", "top_p", "min_p",
-                                "repetition_penalty", "repetition_window"}
+                                "repetition_penalty", "repetition_window", "typical_p"}
             if unknown:
                 raise ValueError(f"{path}:{i}: unknown keys {sorted(unknown)}")
             lines.append({"text": d["text"], "speaker": int(d.get("speaker", 0)), "adapter": d.get("adapter"),
                           "seed": None if d.get("seed") is None else int(d["seed"])})
             if d.get("conversation") is not None:
                 lines[-1]["conversation"] = str(d["conversation"])
-            for k in ("temperature", "topk", "top_p", "min_p"):
+            for k in ("temperature", "topk", "top_p", "min_p", "typical_p"):
                 if isinstance(d.get(k), list):
                     lines[-1][k] = per_codebook(i, k, d.pop(k), k == "topk")
             if d.get("repetition_penalty") is not None:
@@ -266,7 +275,7 @@ def read_serve_file(path, codebooks=None):
                 if isinstance(d["topk"], bool) or not isinstance(d["topk"], int):
                     raise ValueError(f"{path}:{i}: \"topk\" is an integer, got {d['topk']!r}")
                 lines[-1]["topk"] = d["topk"]
-            for k in ("top_p", "min_p"):
+            for k in ("top_p", "min_p", "typical_p"):
                 if d.get(k) is not None:
                     if isinstance(d[k], bool) or not isinstance(d[k], (int, float)):
                         raise ValueError(f"{path}:{i}: \"{k}\" is a number, got {d[k]!r}")
@@ -319,6 +328,23 @@ def serve_processors(lines, args=None, codebooks=None):
     return kw
 
 
+def line_typical(line):
+    """The typical-sampling keyword of one --serve-file line for ``submit`` / ``say``: only if the line carries it."""
+    return {k: line[k] for k in ("typical_p",) if k in line}
+
+
+def serve_typical(lines, args=None, codebooks=None):
+    """``Generator.serve`` keywords for these lines and the command line: ``row_typical=True`` (with ``row_sampling=True``, which it
+    needs, and the command line's values as the server's defaults) as soon as a line names "typical_p" or --typical-p is not
+    1.0; nothing otherwise."""
+    if not any(line_typical(ln) for ln in lines) and (args is None or getattr(args, "typical_p", 1.0) == 1.0):
+        return {}
+    kw = {"row_sampling": True, "row_typical": True}
+    if args is not None:
+        kw.update(sampling_kw(args, codebooks))
+    return kw
+
+
 def serve_voices(generator, lines, context, adapter=None):
     """--cache-context: the --context-* segments as one ``Generator.voice`` per distinct adapter among the lines (--lora-adapter
     for lines without one): {adapter name or None: Voice}.  Call it after the lines' adapters are loaded and before ``serve``."""
@@ -341,7 +367,8 @@ def serve_to_wavs(generator, args, context, adapter=None):
     before it is done.  A line's "temperature" / "topk" are that utterance's or that turn's; if any line has one, the server is
     made with ``row_sampling=True`` (--temperature / --topk are then the other lines' values); "top_p" / "min_p" likewise, with
     ``row_filters=True`` (``serve_filters``); "repetition_penalty" / "repetition_window", a list per codebook or the command
-    line's --repetition-* / --acoustic-* make it ``row_processors=True`` (``serve_processors``).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav.
+    line's --repetition-* / --acoustic-* make it ``row_processors=True`` (``serve_processors``); "typical_p" or --typical-p make it
+    ``row_typical=True`` (``serve_typical``).  Utterance i (the i-th non-empty line, from 0) goes to <output stem>_<i>.wav.
     With --cache-context the context becomes one voice per adapter (``serve_voices``) and every line and every conversation
     starts from its voice instead of the context (``line_prompt``)."""
     def K():
@@ -356,6 +383,7 @@ def serve_to_wavs(generator, args, context, adapter=None):
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, hear_slots=args.hear_slots,
                              **{"temperature": args.temperature, "topk": args.topk, **serve_sampling(lines),
                                 **serve_filters(lines, args.top_p, args.min_p), **serve_processors(lines, args, K),
+                                **serve_typical(lines, args, K),
                                 **out_rate_kw(args)})
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
@@ -363,7 +391,8 @@ def serve_to_wavs(generator, args, context, adapter=None):
         conv, todo = convs[cid]
         i = todo.pop(0)
         line_of[conv.say(lines[i]["text"], lines[i]["speaker"], max_audio_length_ms=args.max_audio_length_ms,
-                         **line_sampling(lines[i]), **line_filters(lines[i]), **line_processors(lines[i]))] = (i, cid)
+                         **line_sampling(lines[i]), **line_filters(lines[i]), **line_processors(lines[i]),
+                         **line_typical(lines[i]))] = (i, cid)
 
     for i, ln in enumerate(lines):
         cid = ln.get("conversation")
@@ -371,7 +400,7 @@ def serve_to_wavs(generator, args, context, adapter=None):
             line_of[server.submit(ln["text"], ln["speaker"], adapter=ln["adapter"] or adapter, seed=ln["seed"],
                                   max_audio_length_ms=args.max_audio_length_ms, **line_prompt(ln, context, voices, adapter),
                                   **line_sampling(ln),
-                                  **line_filters(ln), **line_processors(ln))] = (i, None)
+                                  **line_filters(ln), **line_processors(ln), **line_typical(ln))] = (i, None)
         elif cid in convs:
             convs[cid][1].append(i)
         else:

@@ -379,7 +379,8 @@ class Conversation:
         turn = self._open = _Turn(self._cached, tt.shape[0])
         if filters:                                                  # (the rows path of this conversation's state)
             temperature, topk = st.sampling_args(temperature, topk, **filters)
-            if getattr(st, "row_processors", None) is not None:      # (a turn's repetition window covers its own frames)
+            if getattr(st, "row_processors", None) is not None or getattr(st, "row_typical", None) is not None:
+                # (a turn's repetition window covers its own frames)
                 st.reset_row_history(0)
                 st.set_live([0])
         turn.samples.append(e._frame_tail(st, last_h, temperature, topk, None))
@@ -424,13 +425,14 @@ class Conversation:
     @torch.inference_mode()
     def generate(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
                  eos_check_every: int = 8, top_p: float = 1.0, min_p: float = 0.0,
-                 output_sample_rate: Optional[int] = None, repetition_penalty=1.0, repetition_window=64) -> torch.Tensor:
+                 output_sample_rate: Optional[int] = None, repetition_penalty=1.0, repetition_window=64,
+                 typical_p=1.0) -> torch.Tensor:
         """Speak ``text`` as ``speaker`` with the whole history as context; arguments (``top_p`` / ``min_p``, ``repetition_penalty``
-        / ``repetition_window``, per-codebook sequences and ``output_sample_rate`` included: this turn's) and EOS handling as
+        / ``repetition_window`` / ``typical_p``, per-codebook sequences and ``output_sample_rate`` included: this turn's) and EOS handling as
         ``Generator.generate``.  The repetition window looks at this turn's frames only."""
         from .generator import sampling_kwargs
         temperature, topk, filters = sampling_kwargs(self._gen, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window)
+                                                     repetition_window, typical_p=typical_p)
         out_rs = self._gen._out_resampler(output_sample_rate)
         self._run += 1
         self._settle()
@@ -462,12 +464,12 @@ class Conversation:
     def generate_stream(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9,
                         topk: int = 50, chunk_frames: int = 4, top_p: float = 1.0, min_p: float = 0.0,
                         output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
-                        repetition_window=64) -> Iterator[torch.Tensor]:
+                        repetition_window=64, typical_p=1.0) -> Iterator[torch.Tensor]:
         """``generate`` handing the audio out chunk by chunk, as ``Generator.generate_stream`` does; under the same seed the
         chunks concatenate to ``generate``'s audio.  A later call on THIS conversation invalidates the stream."""
         from .generator import sampling_kwargs
         temperature, topk, filters = sampling_kwargs(self._gen, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window)
+                                                     repetition_window, typical_p=typical_p)
         out_rs = self._gen._out_resampler(output_sample_rate)
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")

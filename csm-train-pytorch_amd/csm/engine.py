@@ -18,7 +18,7 @@ from typing import Dict, List, Optional
 import torch
 
 from .hip import ops
-from .sampling import (RowSampler, _is_number, check_filters, check_processors, check_row_processors,  # noqa: F401
+from .sampling import (RowSampler, _is_number, check_filters, check_processors, check_row_processors, check_typical,  # noqa: F401
                        check_sampling, names_processors)
 
 BF16 = torch.bfloat16
@@ -818,7 +818,7 @@ class Engine:
 
     @torch.no_grad()
     def generate_frame(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None, adapters=None, top_p=None,
-                       min_p=None, repetition_penalty=None, repetition_window=None):
+                       min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None):
         """Reference model.py:140-195: backbone position(s) -> c0 -> 31 depth-decoder steps, against KV caches.
 
         The prompt (``input_pos`` starting at 0) is prefilled with the training forward kernels and its post-RoPE K/V
@@ -833,6 +833,8 @@ class Engine:
         the filtered rows sampler (``DecodeState.set_row_filters``); give the same to every call of the generation.
         ``repetition_penalty`` / ``repetition_window`` (with caches; None: not named), or an entry per row that is K numbers in
         any of the six: the processed rows sampler (``DecodeState.sampling_args``); likewise the same to every call.
+        ``typical_p`` (with caches; None: not named): a number, B entries, or per entry K numbers - locally typical sampling
+        as the last filter, through the typical rows sampler (``DecodeState.set_row_typical``); likewise.
         """
         m, a = self.m, self.m.args
         self._need()
@@ -842,6 +844,9 @@ class Engine:
             if names_processors(temperature, topk, repetition_penalty=repetition_penalty, repetition_window=repetition_window):
                 raise ValueError("the recompute path (use_kv_cache = False) has no repetition penalty and no per-codebook "
                                  "parameters: they need the KV-cache path")
+            if typical_p is not None:
+                raise ValueError("the recompute path (use_kv_cache = False) has no typical_p: typical sampling needs the KV-cache "
+                                 "path")
             if top_p is not None or min_p is not None:
                 raise ValueError("the recompute path (use_kv_cache = False) has no top_p / min_p: the filters need the KV-cache path")
             return self._generate_frame_recompute(tokens, tokens_mask, input_pos, temperature, topk, noise)
@@ -857,7 +862,8 @@ class Engine:
                                "same batch size (call it with input_pos starting at 0 first)")
         if first:
             st = m._decode_state = DecodeState(self, Bn, adapters)
-        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
+                                             typical_p=typical_p)
         st.set_live(range(Bn))
         if first:
             last_h = st.prefill(tokens, tokens_mask)
@@ -871,16 +877,17 @@ class Engine:
 
     @torch.no_grad()
     def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None, adapters=None, top_p=None,
-                              min_p=None, repetition_penalty=None, repetition_window=None):
+                              min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None):
         """Batched generation (up to 16 utterances): prefill B prompts of different lengths and sample the
         first frame of each; later frames go through ``generate_frame`` with ``[B, 1, K+1]`` tokens and a non-zero
         ``input_pos``, exactly as for one utterance.  ``temperature`` / ``topk``: two numbers, or a sequence of B values for
         either one - row b then samples with its own pair (``DecodeState.sampling_args``); give the same to ``generate_frame``.
-        ``top_p`` / ``min_p`` / ``repetition_penalty`` / ``repetition_window``: as for ``generate_frame``."""
+        ``top_p`` / ``min_p`` / ``repetition_penalty`` / ``repetition_window`` / ``typical_p``: as for ``generate_frame``."""
         m = self.m
         self._need()
         st = m._decode_state = DecodeState(self, len(tokens_list), adapters)
-        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        temperature, topk = st.sampling_args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
+                                             typical_p=typical_p)
         st.set_live(range(st.B))
         last_h = st.prefill_ragged(tokens_list, masks_list)
         return self._frame_tail(st, last_h, temperature, topk, noise)
@@ -1582,6 +1589,12 @@ class DecodeState:
         sampler, which keeps the rows' rings of sampled codes).  The call that raises the level gives its six to every row."""
         self.sampler.write(b, 3, temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
 
+    def set_row_typical(self, b, temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p):
+        """... with these seven, each a number or K numbers: the six of ``set_row_processors`` and ``typical_p`` in (0, 1], locally
+        typical sampling as the last filter (level 4: the typical rows sampler; 1.0 is the processed sampler's draw).  The call
+        that raises the level gives its seven to every row."""
+        self.sampler.write(b, 4, temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p)
+
     def reset_row_history(self, b):
         """Row ``b`` starts an utterance: its frame counter returns to 0.  The ring is left as it is - the sampler looks at
         min(window, frame) entries, so what an earlier utterance left there is never read."""
@@ -1592,15 +1605,17 @@ class DecodeState:
         the others' rings and counters stay as they are, whatever their rows of the batch hold.  Nothing below level 3."""
         self.sampler.set_live(rows)
 
-    def sampling_args(self, temperature, topk, top_p=None, min_p=None, repetition_penalty=None, repetition_window=None):
+    def sampling_args(self, temperature, topk, top_p=None, min_p=None, repetition_penalty=None, repetition_window=None,
+                      typical_p=None):
         """What ``Engine.generate_frame`` / ``generate_first_frames`` hand to the frame bodies: two numbers (or None, None) with
         nothing else named pass through; anything else (``sampling.normalise``: a value per row, ``top_p`` / ``min_p``, a penalty,
-        a window, values per codebook) is written to the rows at the level it needs and (None, None) comes back."""
-        return self.sampler.args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        a window, values per codebook, ``typical_p``) is written to the rows at the level it needs and (None, None) comes back."""
+        return self.sampler.args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p)
 
     row_sampling = property(lambda self: self.sampler.row_sampling, doc="[(temperature, topk)] * B at levels 1 and 2, else None")
     row_filters = property(lambda self: self.sampler.row_filters, doc="[(top_p, min_p)] * B at level 2, else None")
     row_processors = property(lambda self: self.sampler.row_processors, doc="six K-tuples per row at level 3, else None")
+    row_typical = property(lambda self: self.sampler.row_typical, doc="seven K-tuples per row at level 4, else None")
 
     def set_row_seed(self, b, seed, generator=None):
         """Row ``b``'s sampler noise comes from its own ``torch.Generator`` seeded with ``seed`` (``fill_noise``); None returns
@@ -1676,7 +1691,8 @@ class DecodeState:
         when temperature / top-k change; with ``None, None`` the key is (None, None) and the sampler reads each row's pair from
         the row buffers (``set_row_sampling``), so a change of any row's parameters replays the same graph; once the state has
         row filters (``set_row_filters``) it is (None, None, "filters") - the frame holds the filtered rows sampler, and a change
-        of any row's top-p / min-p replays it too; with row processors (``set_row_processors``) it is (None, None, "processors")."""
+        of any row's top-p / min-p replays it too; with row processors (``set_row_processors``) it is (None, None, "processors"), with
+        typical sampling (``set_row_typical``) (None, None, "typical")."""
         m = self.e.m
         self._advance()
         key = self.sampler.graph_key(temperature, topk)

@@ -59,18 +59,26 @@ def filter_kwargs(top_p, min_p, B=None):
     return {"top_p": _untouched(top_p), "min_p": _untouched(min_p)}
 
 
-def sampling_kwargs(gen, temperature, topk, top_p, min_p, repetition_penalty=1.0, repetition_window=64, B=None):
+def sampling_kwargs(gen, temperature, topk, top_p, min_p, repetition_penalty=1.0, repetition_window=64, B=None, typical_p=1.0):
     """(temperature, topk, keywords) of the frame calls of a generation on the Generator ``gen``.  Nothing new named -
     ``repetition_penalty`` 1.0, ``repetition_window`` 64 and no per-codebook sequence: what the call has always made of them (``filter_kwargs``;
     ``Generator._batch_sampling`` with ``B``), untouched.  Otherwise every one of the six goes to the rows' processors
     (``DecodeState.sampling_args``): one entry per row, each a number or K numbers (one per codebook), checked here
     (``sampling.normalise``, the check the state makes), before any cache is taken over.  Without ``B`` (one utterance) a value is
     a number or K numbers - the one entry of a batch of one; with ``B`` a number or a sequence of B entries, each a number or K
-    numbers - a flat sequence of B numbers keeps its meaning, one value per utterance."""
+    numbers - a flat sequence of B numbers keeps its meaning, one value per utterance.  ``typical_p`` other than the number 1.0
+    (a number, K numbers, or with ``B`` an entry per utterance) sends all seven to the rows (the typical rows sampler)."""
     six = [temperature, topk, top_p, min_p, repetition_penalty, repetition_window]
     if B is None:
         six = [v if _is_number(v) else [per_codebook(name, v, gen._model.args.audio_num_codebooks)]
                for name, v in zip(PROCESSOR_NAMES, six)]
+    if not (_is_number(typical_p) and typical_p == 1.0):
+        a, n = gen._model.args, 1 if B is None else B
+        if B is None and not _is_number(typical_p):
+            typical_p = [per_codebook("typical_p", typical_p, a.audio_num_codebooks)]
+        normalise(n, a.audio_num_codebooks, a.audio_vocab_size, *six, unit="utterance", typical_p=typical_p)
+        rows = [[v] * n if _is_number(v) else _as_list(v) for v in six + [typical_p]]
+        return rows[0], rows[1], dict(zip(PROCESSOR_NAMES[2:] + ("typical_p",), rows[2:]))
     if not names_processors(*six[:4]) and all(_is_number(v) for v in six[4:]) and six[4] == 1.0 and six[5] == 64:
         if B is not None:
             temperature, topk = gen._batch_sampling(temperature, topk, B)
@@ -167,7 +175,7 @@ class Generator:
     def generate(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                  temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8, adapter: Optional[str] = None,
                  top_p: float = 1.0, min_p: float = 0.0, output_sample_rate: Optional[int] = None,
-                 repetition_penalty=1.0, repetition_window=64, voice=None) -> torch.Tensor:
+                 repetition_penalty=1.0, repetition_window=64, voice=None, typical_p=1.0) -> torch.Tensor:
         """Reference generator.py:147-218.  ``adapter``: the name of a bank adapter (``add_adapter`` / ``load_adapter``) to
         speak with, or None.  The reference tests every frame for EOS on the host (one device sync per
         frame, generator.py:196-199); here the all-zero test runs on the device and the host looks at it once per
@@ -183,15 +191,19 @@ class Generator:
         the temperature.  ``temperature`` / ``topk`` / ``top_p`` / ``min_p`` and these two may each be a sequence of K numbers, one
         per codebook (codebook 0 is the semantic one).  At 1.0 / 64 with plain numbers the call is what it is without them;
         otherwise it samples through the processed rows sampler (``DecodeState.set_row_processors``).
+        ``typical_p`` (in (0, 1], a number or K numbers): locally typical sampling (Meister et al. 2022) as the last filter - of
+        what the others left, the tokens whose surprise -ln p is closest to the entropy stay, most typical first, until their
+        probability reaches ``typical_p``; unlike top-p and min-p it can drop the most likely code.  At 1.0 the call is what it is
+        without it; otherwise it samples through the typical rows sampler (``DecodeState.set_row_typical``).
         ``voice``: a ``Voice`` (``Generator.voice``) that comes before ``context`` - the call is then
         ``conversation(voice=voice, context=context, adapter=adapter).generate(text, speaker, ...)`` with every other argument
         passed through: the voice's K / V are copied in, only ``context`` and the text are fed."""
         if voice is not None:
             return self.conversation(context, adapter, voice=voice).generate(
                 text, speaker, max_audio_length_ms, temperature, topk, eos_check_every, top_p, min_p, output_sample_rate,
-                repetition_penalty, repetition_window)
+                repetition_penalty, repetition_window, typical_p=typical_p)
         temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window)
+                                                     repetition_window, typical_p=typical_p)
         out_rs = self._out_resampler(output_sample_rate)
         ads = self._resolve_adapters([adapter])
         self._run += 1
@@ -245,15 +257,15 @@ class Generator:
                         temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4,
                         adapter: Optional[str] = None, top_p: float = 1.0, min_p: float = 0.0,
                         output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
-                        repetition_window=64, voice=None) -> Iterator[torch.Tensor]:
+                        repetition_window=64, voice=None, typical_p=1.0) -> Iterator[torch.Tensor]:
         """``generate`` that hands the audio out while it is being made: an iterator of 1-D device tensors of
         ``chunk_frames * 1920`` samples (the last one may be shorter), decoded by the audio tokenizer's stateful
         ``decode_stream()``.  The frames are sampled by the same ``generate_frame`` calls in the same order as ``generate``,
         so under the same torch seed the concatenated chunks equal ``generate``'s audio.  The host looks for EOS once per
         chunk; frames from EOS on are never decoded.  A later ``generate`` / ``generate_batch`` / ``generate_stream`` on this
         Generator invalidates the stream (its next ``next()`` raises ``RuntimeError``); abandoning it is harmless.
-        ``adapter``, ``top_p``, ``min_p``, ``repetition_penalty``, ``repetition_window`` and per-codebook sequences: as for
-        ``generate``.  ``output_sample_rate``: the chunks go through a stateful
+        ``adapter``, ``top_p``, ``min_p``, ``repetition_penalty``, ``repetition_window``, ``typical_p`` and per-codebook sequences: as
+        for ``generate``.  ``output_sample_rate``: the chunks go through a stateful
         ``ResampleStream`` - they concatenate to ``generate(..., output_sample_rate=)``'s audio bit for bit; the stream lags by
         the filter's half-width, and what it still owes comes as one last short chunk.
         ``voice``: as for ``generate`` - the call is ``conversation(voice=voice, context=context,
@@ -261,9 +273,9 @@ class Generator:
         if voice is not None:
             return self.conversation(context, adapter, voice=voice).generate_stream(
                 text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, top_p, min_p, output_sample_rate,
-                repetition_penalty, repetition_window)
+                repetition_penalty, repetition_window, typical_p=typical_p)
         temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window)
+                                                     repetition_window, typical_p=typical_p)
         out_rs = self._out_resampler(output_sample_rate)
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
@@ -318,7 +330,7 @@ class Generator:
                        max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
                        eos_check_every: int = 8, adapters: Optional[List[Optional[str]]] = None, top_p=1.0,
                        min_p=0.0, output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
-                       repetition_window=64) -> List[torch.Tensor]:
+                       repetition_window=64, typical_p=1.0) -> List[torch.Tensor]:
         """``generate`` for up to 16 utterances at once (not in the reference, whose loop is single-utterance): the prompts
         (different lengths) are prefilled one by one into their rows of the KV caches, then every decode frame advances all
         rows together - the decode kernels share each weight load between the batch rows, so B utterances cost about as
@@ -341,7 +353,7 @@ class Generator:
         if not (1 <= B <= 16 and len(speakers) == B and len(contexts) == B):
             raise ValueError("generate_batch takes 1..16 utterances with one speaker id and one context list each")
         temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window, B)
+                                                     repetition_window, B, typical_p=typical_p)
         if adapters is not None and len(adapters) != B:
             raise ValueError(f"generate_batch: {len(adapters)} adapter names for {B} utterances (one name or None each)")
         ads = self._resolve_adapters(list(adapters)) if adapters is not None else None
@@ -400,7 +412,7 @@ class Generator:
     def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
               row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
               output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
-              repetition_window=64):
+              repetition_window=64, row_typical: bool = False, typical_p=1.0):
         """A running batch (csm/serving.py): ``server.submit(text, speaker, context, adapter=None, seed=None,
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
@@ -415,7 +427,10 @@ class Generator:
         are the requests' default windowed repetition penalty (``generate``), ``submit`` / ``conversation`` / ``say`` take their own,
         and each of the six parameters may be a sequence of K numbers, one per codebook; every draw then goes through the
         processed rows sampler, which remembers each slot's last 64 frames, and a request at penalty 1 has the codes it has with
-        ``row_filters``.  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
+        ``row_filters``.  With ``row_typical=True`` (it needs ``row_sampling`` and includes ``row_processors``), ``typical_p`` is the
+        requests' default for locally typical sampling (``generate``), ``submit`` / ``conversation`` / ``say`` take their own - a
+        number or K numbers - every draw goes through the typical rows sampler, and a request at 1.0 has the codes it has with
+        ``row_processors``.  ``server.conversation(context, adapter, seed)`` opens a multi-turn dialogue on it: ``conv.say(text,
         speaker)`` queues its next turn as a request, ``conv.add(Segment)`` (or ``conv.hear(speaker)`` -> ``feed`` / ``end``, encoded
         while it is spoken) is the other party's turn; its KV history is parked
         between turns and resumed into any free slot, so more conversations than slots can be open.  It takes over the model's caches like any ``generate*`` call (open streams and older servers are
@@ -427,7 +442,7 @@ class Generator:
         one rows resampler over its slots - one more launch per ``step()``.  ``conv.hear(speaker, sample_rate=)`` is the input side."""
         from .serving import BatchServer
         return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p,
-                           output_sample_rate, row_processors, repetition_penalty, repetition_window)
+                           output_sample_rate, row_processors, repetition_penalty, repetition_window, row_typical, typical_p)
 
     def voice(self, context: List[Segment], adapter: Optional[str] = None):
         """A voice prompt prefilled ONCE (csm/conversation.py: ``Voice``): the segments are tokenised and Mimi-encoded as every

@@ -779,6 +779,28 @@ def sample_filtered_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, 
     return out_i32
 
 
+def _sample_ring_rows(name, logits_f32, q_f32, out_i32, ints, floats, hist_i32, advance, V, last=()):
+    """The launch of the two samplers that keep the rows' rings: ``ints`` = (topk, window, frame, live), ``floats`` = (temperature,
+    top_p, min_p, penalty) and ``last`` (what follows ``advance`` in the entry point's arguments), one entry per row each."""
+    rows = logits_f32.shape[0]
+    V = V or logits_f32.shape[1]
+    assert q_f32.is_contiguous() and q_f32.shape == (rows, V)
+    for a in ints:
+        assert a.dtype == torch.int32 and a.is_contiguous() and a.numel() == rows
+    for a in floats + tuple(last):
+        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == rows
+    assert hist_i32.dtype == torch.int32 and hist_i32.dim() == 2 and hist_i32.shape == (rows, 64) and hist_i32.stride(1) == 1
+    assert rows == 1 or hist_i32.stride(0) >= 64
+    ldh = hist_i32.stride(0) if rows > 1 else 64
+    topk, window, frame, live = ints
+    temperature, top_p, min_p, penalty = floats
+    check(getattr(lib, name)(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0),
+                             topk.data_ptr(), temperature.data_ptr(), top_p.data_ptr(), min_p.data_ptr(), penalty.data_ptr(),
+                             window.data_ptr(), hist_i32.data_ptr(), ldh, frame.data_ptr(), live.data_ptr(), 1 if advance else 0,
+                             *[a.data_ptr() for a in last], _stream()), name)
+    return out_i32
+
+
 def sample_processed_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, top_p_f32, min_p_f32, penalty_f32, window_i32,
                           hist_i32, frame_i32, live_i32, advance=False, V=None):
     """``sample_filtered_rows`` with a windowed repetition penalty per row and the row's memory of what it drew
@@ -786,22 +808,18 @@ def sample_processed_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32,
     f; ``frame_i32[r]``: f; the ids of the last min(window_i32[r], f, 64) frames are penalised by ``penalty_f32[r]`` before the
     draw.  A row with ``live_i32[r]`` != 0 then stores its winner to slot f % 64 and, with ``advance``, f + 1 to ``frame_i32[r]``.
     A row with penalty 1 or window 0 is ``sample_filtered_rows``' row."""
-    rows = logits_f32.shape[0]
-    V = V or logits_f32.shape[1]
-    assert q_f32.is_contiguous() and q_f32.shape == (rows, V)
-    for a in (topk_i32, window_i32, frame_i32, live_i32):
-        assert a.dtype == torch.int32 and a.is_contiguous() and a.numel() == rows
-    for a in (temperature_f32, top_p_f32, min_p_f32, penalty_f32):
-        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == rows
-    assert hist_i32.dtype == torch.int32 and hist_i32.dim() == 2 and hist_i32.shape == (rows, 64) and hist_i32.stride(1) == 1
-    assert rows == 1 or hist_i32.stride(0) >= 64
-    ldh = hist_i32.stride(0) if rows > 1 else 64
-    check(lib.csm_sample_processed_rows(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0),
-                                        topk_i32.data_ptr(), temperature_f32.data_ptr(), top_p_f32.data_ptr(),
-                                        min_p_f32.data_ptr(), penalty_f32.data_ptr(), window_i32.data_ptr(), hist_i32.data_ptr(),
-                                        ldh, frame_i32.data_ptr(), live_i32.data_ptr(), 1 if advance else 0, _stream()),
-          "csm_sample_processed_rows")
-    return out_i32
+    return _sample_ring_rows("csm_sample_processed_rows", logits_f32, q_f32, out_i32, (topk_i32, window_i32, frame_i32, live_i32),
+                             (temperature_f32, top_p_f32, min_p_f32, penalty_f32), hist_i32, advance, V)
+
+
+def sample_typical_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, top_p_f32, min_p_f32, penalty_f32, window_i32,
+                        hist_i32, frame_i32, live_i32, typical_p_f32, advance=False, V=None):
+    """``sample_processed_rows`` with locally typical sampling per row (``csm_sample_typical_rows``): after the nucleus, the
+    tokens whose surprise -ln P is closest to the entropy of what is left are kept, most typical first, until ``typical_p_f32[r]``
+    of the mass is reached (the token that crosses it is kept).  A row with 1.0 is ``sample_processed_rows``' row: out, ring and
+    counter."""
+    return _sample_ring_rows("csm_sample_typical_rows", logits_f32, q_f32, out_i32, (topk_i32, window_i32, frame_i32, live_i32),
+                             (temperature_f32, top_p_f32, min_p_f32, penalty_f32), hist_i32, advance, V, last=(typical_p_f32,))
 
 
 def rvq_encode(x_f32, codebooks_f32, codes_i64, n_semantic=1):

@@ -166,6 +166,20 @@ def sample_processed_rows(logits: torch.Tensor, topk: torch.Tensor, temperature:
     return out.reshape(-1, 1)
 
 
+def sample_typical_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor,
+                        min_p: torch.Tensor, penalty: torch.Tensor, window: torch.Tensor, hist: torch.Tensor,
+                        frame: torch.Tensor, live: torch.Tensor, typical_p: torch.Tensor, advance: bool = False,
+                        q: Optional[torch.Tensor] = None):
+    """``sample_processed_rows`` with locally typical sampling (``typical_p`` float32 [B], in (0, 1]) as the last filter, inside
+    the kernel (``csm_sample_typical_rows``): of what the nucleus left, the tokens whose surprise -ln P is closest to the entropy
+    stay, most typical first, while the mass of the strictly more typical ones is below ``typical_p`` - the largest value may go.
+    Row b with 1.0 is ``sample_processed_rows``' row b bit for bit, ring and counter included.  Returns int32 [B, 1]."""
+    lg2, q, out = _sample_operands(logits, q, "sample_typical_rows")
+    ops.sample_typical_rows(lg2, q, out, topk, temperature, top_p, min_p, penalty, window, hist, frame, live, typical_p,
+                            advance=advance, V=lg2.shape[1])
+    return out.reshape(-1, 1)
+
+
 @dataclass
 class ModelArgs:
     """Arguments for the CSM model (reference model.py:99-107)."""
@@ -511,12 +525,13 @@ class Model(nn.Module):
     @torch.no_grad()
     def generate_frame(self, tokens: torch.Tensor, tokens_mask: torch.Tensor, input_pos: torch.Tensor, temperature: float,
                        topk: int, noise: Optional[List[torch.Tensor]] = None, adapters=None, top_p=None,
-                       min_p=None, repetition_penalty=None, repetition_window=None) -> torch.Tensor:
+                       min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None) -> torch.Tensor:
         """Reference model.py:140-195: one frame of K codes, [B, K] int32.  ``noise`` (K tensors [B, V_a] of Exp(1)
         draws) pins the sampler for parity tests.  ``adapters``: a LoRAState or None per batch row (csm/lora_bank.py), read
         on a generation's first call.  ``temperature`` / ``topk``: two numbers, a sequence of B values for either one, or None for
         both - one pair per row through the rows sampler (``Engine.generate_frame``).  ``top_p`` / ``min_p``: None (not named), or
-        a number / B values for either one - the filtered rows sampler (``sample_filtered_rows``)."""
+        a number / B values for either one - the filtered rows sampler (``sample_filtered_rows``).  ``typical_p``: None, or a number /
+        B entries - locally typical sampling through the typical rows sampler (``sample_typical_rows``)."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
         return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise, adapters, top_p, min_p,
-                                          repetition_penalty, repetition_window)
+                                          repetition_penalty, repetition_window, typical_p)

@@ -1,12 +1,13 @@
 """Sampling parameters, host side: the rules a value is held to (``check_*``), the one normaliser of what a call names
 (``normalise``) and the per-row state of a ``DecodeState`` (``RowSampler``).
 
-A state samples at one of four levels, and the level only rises: 0 - the scalar path, two numbers per frame call
+A state samples at one of five levels, and the level only rises: 0 - the scalar path, two numbers per frame call
 (``csm_sample_topk``); 1 - each row its own temperature / top-k (``csm_sample_topk_rows``); 2 - and its own top-p / min-p
 (``csm_sample_filtered_rows``); 3 - all six per row and per codebook, with the windowed repetition penalty and the rows' rings of
-sampled codes (``csm_sample_processed_rows``).  Whatever the level, the parameters sit in the same six [K, B] device buffers
+sampled codes (``csm_sample_processed_rows``); 4 - and locally typical sampling, ``typical_p`` per row and per codebook
+(``csm_sample_typical_rows``).  Whatever the level, the parameters sit in the same six [K, B] device buffers
 (codebook-major: codebook i's draw hands row i of each to the kernel, which reads ``topk[row]`` from the pointer it is given) and
-in one host mirror; below level 3 the K entries of a column are equal.
+in one host mirror; below level 3 the K entries of a column are equal.  Level 4's seventh buffer and mirror stand beside them.
 """
 import math
 import numbers
@@ -20,7 +21,8 @@ DTYPES = (torch.float32, torch.int32, torch.float32, torch.float32, torch.float3
 # first write brings a pair)
 IDENTITY = (1.0, 1, 1.0, 0.0, 1.0, HIST_FRAMES)
 _FIRST = (None, "temperature = topk = None samples each row with its own pair: call set_row_sampling first",
-          "no row filters: call set_row_filters first", "no row processors: call set_row_processors first")
+          "no row filters: call set_row_filters first", "no row processors: call set_row_processors first",
+          "no row typical sampling: call set_row_typical first")
 
 
 def _is_number(x):
@@ -92,6 +94,18 @@ def check_processors(repetition_penalty, repetition_window):
     return r, w
 
 
+def check_typical(typical_p):
+    """The rule for one row's locally typical sampling: ``typical_p`` a number in (0, 1] (1: off).  Returns a float; raises
+    ValueError with the offending value."""
+    try:
+        f = float(typical_p)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if isinstance(typical_p, (bool, str, bytes)) or not 0.0 < f <= 1.0:
+        raise ValueError(f"typical_p must be a number in (0, 1], got {typical_p!r}")
+    return f
+
+
 def per_codebook(name, value, K):
     """``value`` - a number (every codebook) or a sequence of K numbers (one per codebook) - as a list of K entries."""
     if _is_number(value):
@@ -116,6 +130,11 @@ def check_row_processors(K, vocab, temperature, topk, top_p, min_p, repetition_p
     return tuple(tuple(o) for o in out)
 
 
+def check_row_typical(K, typical_p):
+    """One row's ``typical_p``, a number or K numbers, held to ``check_typical`` codebook by codebook: a tuple of K floats."""
+    return tuple(check_typical(v) for v in per_codebook("typical_p", typical_p, K))
+
+
 def names_processors(*values, repetition_penalty=None, repetition_window=None):
     """Whether a call names what only the processed sampler has: a penalty, a window, or a per-codebook sequence among
     ``values`` (each a number, None, a flat sequence of numbers - per row, today's meaning - or a sequence holding sequences)."""
@@ -129,7 +148,7 @@ def names_processors(*values, repetition_penalty=None, repetition_window=None):
 
 
 def normalise(B, K, vocab, temperature, topk, top_p=None, min_p=None, repetition_penalty=None, repetition_window=None, *,
-              level=0, unit="row"):
+              level=0, unit="row", typical_p=None):
     """What a frame call's six sampling values ask for: (the level the call needs, per row six entries - a tuple of K validated
     values each, or None for a parameter the call leaves as it is).  Level 0: two numbers, or None for both - the call passes them
     through and writes nothing (no rows come back).  Each value is None (not named), a number (every row) or B entries; at level 3
@@ -137,7 +156,9 @@ def normalise(B, K, vocab, temperature, topk, top_p=None, min_p=None, repetition
     ``min_p`` named) the filters - the one not named at its identity - and the pair, unless both are None; level 3 (a penalty, a
     window or a per-codebook entry named, or anything beyond a plain pair on a state whose ``level`` is 3: it draws every rows
     frame through the processors) all six, those not named at their identity.  Everything is checked here, so the caller writes
-    all rows or none.  ``unit``: what the errors call a row ("utterance": the generator's calls, checked before any cache is taken
+    all rows or none.  Level 4 (``typical_p`` named - a number, B entries, or per entry K numbers - or anything beyond a plain
+    pair on a state whose ``level`` is 4): rows of SEVEN entries, the six of level 3 and ``typical_p`` (1.0 if not named).
+    ``unit``: what the errors call a row ("utterance": the generator's calls, checked before any cache is taken
     over)."""
     many = f"{B} rows" if unit == "row" else f"{B}"
 
@@ -148,6 +169,16 @@ def normalise(B, K, vocab, temperature, topk, top_p=None, min_p=None, repetition
         return vs
 
     plain = (temperature is None and topk is None) or (_is_number(temperature) and _is_number(topk))
+    if typical_p is not None or (level == 4 and not (plain and top_p is None and min_p is None and repetition_penalty is None
+                                                      and repetition_window is None)):
+        if temperature is None or topk is None:
+            raise ValueError("typical_p, per-codebook parameters and the repetition penalty need temperature and topk named")
+        seven = [ident if v is None else v for ident, v in zip(IDENTITY + (1.0,), (temperature, topk, top_p, min_p, repetition_penalty,
+                                                                                   repetition_window, typical_p))]
+        cols = [rows_of(v, f"{name} is a number or a sequence of one entry per {unit} ({many}; an entry is a number or one number "
+                           f"per codebook), got {v!r}") for name, v in zip(PROCESSOR_NAMES + ("typical_p",), seven)]
+        return 4, [check_row_processors(K, vocab, *[vs[b] for vs in cols[:6]]) + (check_row_typical(K, cols[6][b]),)
+                   for b in range(B)]
     if names_processors(temperature, topk, top_p, min_p, repetition_penalty=repetition_penalty,
                         repetition_window=repetition_window) or (level == 3 and not (plain and top_p is None and min_p is None)):
         if temperature is None or topk is None:
@@ -181,13 +212,15 @@ class RowSampler:
     ([K, B], made by the first write), the host mirror ``rows`` (per row, six tuples of K values) and, from level 3 on, what the
     processed rows sampler keeps: ``code_hist`` int32 [B, K, 64] (slot f % 64 of [b, i]: the code row b drew for codebook i in
     frame f of its utterance), ``hist_frame`` int32 [B] (f) and ``hist_live`` int32 [B] (the rows that write their ring and count
-    the frame).  Every write happens outside the captured frame graph, so a change of parameters never recaptures; a rise of the
+    the frame).  At level 4 the seventh parameter stands beside the six: ``typical`` ([K, B] fp32, made at the rise and filled
+    with 1.0) with its mirror ``typical_rows`` (per row, K values).  Every write happens outside the captured frame graph, so a change of parameters never recaptures; a rise of the
     level does (``graph_key``): make it before the first capture."""
 
     def __init__(self, B, K, vocab, device):
         self.B, self.K, self.vocab, self.device = B, K, vocab, device
         self.level, self.params, self.rows = 0, None, None
         self.code_hist, self.hist_frame, self.hist_live, self.live_rows = None, None, None, None
+        self.typical, self.typical_rows = None, None
 
     def need(self, level):
         if self.level < level:
@@ -195,8 +228,10 @@ class RowSampler:
 
     def write(self, b, level, *values):
         """Row ``b``'s parameters of ``level`` from its next frame on - ``set_row_sampling``'s two, ``set_row_filters``' two or
-        ``set_row_processors``' six (each a number or K numbers) - held to their rule first."""
-        if level == 3:
+        ``set_row_processors``' six or ``set_row_typical``'s seven (each a number or K numbers) - held to their rule first."""
+        if level == 4:
+            vals = check_row_processors(self.K, self.vocab, *values[:6]) + (check_row_typical(self.K, *values[6:]),)
+        elif level == 3:
             vals = check_row_processors(self.K, self.vocab, *values)
         else:
             two = check_sampling(*values, self.vocab) if level == 1 else check_filters(*values)
@@ -208,7 +243,8 @@ class RowSampler:
         """Validated values (``normalise``'s entries: None leaves a parameter as it is) into column ``b`` of the buffers and the
         mirror; only what changed is written.  A write that raises the level gives its values to every row (a row that is never set
         still samples with valid parameters: the kernels run on all B rows).  A buffer whose K values agree is written with one
-        fill (launch-only); only K different values - level 3 - take a small blocking host-to-device copy."""
+        fill (launch-only); only K different values - level 3 on - take a small blocking host-to-device copy.  A seventh value
+        is ``typical_p`` (level 4)."""
         b = int(b)
         if not 0 <= b < self.B:
             raise ValueError(f"row {b} out of range (the state has {self.B})")
@@ -219,12 +255,20 @@ class RowSampler:
             self.rows = [tuple((v,) * self.K for v in IDENTITY)] * self.B
         rising = level > self.level
         cols, rows = (slice(None), range(self.B)) if rising else (slice(b, b + 1), (b,))
-        for j, new in enumerate(vals):
+        for j, new in enumerate(vals[:6]):
             if new is not None and (rising or new != self.rows[b][j]):
                 self.put(j, cols, new)
         for r in rows:
             self.rows[r] = tuple(old if new is None else new for old, new in zip(self.rows[r], vals))
-        if rising and level == 3:
+        if level == 4:
+            if self.typical is None:
+                self.typical = torch.full((self.K, self.B), 1.0, dtype=torch.float32, device=self.device)
+                self.typical_rows = [(1.0,) * self.K] * self.B
+            if rising or vals[6] != self.typical_rows[b]:
+                self.put(6, cols, vals[6])
+            for r in rows:
+                self.typical_rows[r] = vals[6]
+        if level >= 3 and self.level < 3:
             self.code_hist = torch.zeros(self.B, self.K, HIST_FRAMES, dtype=torch.int32, device=self.device)
             self.hist_frame = torch.zeros(self.B, dtype=torch.int32, device=self.device)
             self.hist_live = torch.ones(self.B, dtype=torch.int32, device=self.device)
@@ -233,17 +277,17 @@ class RowSampler:
 
     def put(self, j, cols, new):
         """Parameter ``j``'s K values ``new`` into the columns ``cols`` of its buffer."""
-        view = self.params[j][:, cols]
+        view = (self.typical if j == 6 else self.params[j])[:, cols]
         if len(set(new)) == 1:
             view.fill_(new[0])
         else:
-            view.copy_(torch.tensor(new, dtype=DTYPES[j]).view(-1, 1))
+            view.copy_(torch.tensor(new, dtype=view.dtype).view(-1, 1))
 
-    def args(self, temperature, topk, top_p=None, min_p=None, repetition_penalty=None, repetition_window=None):
+    def args(self, temperature, topk, top_p=None, min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None):
         """``DecodeState.sampling_args``: what the call names goes to the rows (all of them checked before any is written) and
         (None, None) comes back; two numbers, or None for both, with nothing else named pass through."""
         level, rows = normalise(self.B, self.K, self.vocab, temperature, topk, top_p, min_p, repetition_penalty,
-                                repetition_window, level=self.level)
+                                repetition_window, level=self.level, typical_p=typical_p)
         if level == 0:
             return temperature, topk
         for b, vals in enumerate(rows):
@@ -264,14 +308,17 @@ class RowSampler:
 
     def draw(self, logits, i, q):
         """Codebook ``i``'s codes for [B, V] ``logits`` and the Exp(1) draws ``q``, each row with its own parameters: int32
-        [B, 1].  At level 3 the draw also writes the live rows' rings, and the last codebook's counts the frame."""
-        from .models.model import sample_filtered_rows, sample_processed_rows, sample_topk_rows
+        [B, 1].  From level 3 on the draw also writes the live rows' rings, and the last codebook's counts the frame."""
+        from .models.model import sample_filtered_rows, sample_processed_rows, sample_topk_rows, sample_typical_rows
         self.need(1)
         t, k, p, m, r, w = (buf[i] for buf in self.params)
         if self.level == 1:
             return sample_topk_rows(logits, k, t, q)
         if self.level == 2:
             return sample_filtered_rows(logits, k, t, p, m, q)
+        if self.level == 4:
+            return sample_typical_rows(logits, k, t, p, m, r, w, self.code_hist[:, i], self.hist_frame, self.hist_live,
+                                       self.typical[i], advance=(i == self.K - 1), q=q)
         return sample_processed_rows(logits, k, t, p, m, r, w, self.code_hist[:, i], self.hist_frame, self.hist_live,
                                      advance=(i == self.K - 1), q=q)
 
@@ -279,7 +326,7 @@ class RowSampler:
         """The key of the captured frame graph a frame call with these two replays: the pair itself, or - None for both - what
         tells the rows samplers apart (the kernels read the parameters from the buffers: any change of them replays the graph)."""
         if temperature is None and topk is None:
-            return (None, None) + ((), (), ("filters",), ("processors",))[self.level]
+            return (None, None) + ((), (), ("filters",), ("processors",), ("typical",))[self.level]
         return (float(temperature), int(topk))
 
     @property
@@ -296,3 +343,8 @@ class RowSampler:
     def row_processors(self):
         """Per row, six tuples of K values at level 3, else None."""
         return list(self.rows) if self.level == 3 else None
+
+    @property
+    def row_typical(self):
+        """Per row, seven tuples of K values - the six and ``typical_p`` - at level 4, else None."""
+        return [r + (y,) for r, y in zip(self.rows, self.typical_rows)] if self.level == 4 else None

@@ -42,6 +42,13 @@ with the conversation - and only the rows a frame is for count it: the joined ro
 decode frame.  So a request has the same codes in any slot, whoever joins beside it; at penalty 1 they are the codes of a
 ``row_filters`` server; a change of any of a row's parameters replays the same captured frame.
 
+Typical sampling.  ``serve(row_sampling=True, row_typical=True, typical_p=1.0)`` includes the processors and adds locally typical
+sampling per request (``typical_p`` in (0, 1], a number or K numbers; resolved and checked like the others), written at admission
+(``DecodeState.set_row_typical``: a seventh [K, B] buffer); every draw goes through the typical rows sampler
+(``csm_sample_typical_rows``), which keeps, of what the other filters left, the tokens whose surprise is closest to the entropy -
+it can drop the most likely code, which no other filter can.  At 1.0 a request has the codes of a ``row_processors`` server; a
+change of ``typical_p`` replays the same captured frame.
+
 Multi-turn conversations (``BatchServer.conversation`` -> ``ServedConversation``) outlive their slot.  A conversation holds a
 slot only while it speaks: at the end of the chunk in which its turn ended the K / V of its history positions are parked
 (``DecodeState.park_row``: one copy, base + kept frames - what the row sampled after EOS or after its length limit is not
@@ -94,7 +101,7 @@ import torch
 
 from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, hear_resampler, open_heard_turn
 from .engine import DecodeState
-from .sampling import HIST_FRAMES, _as_list, check_filters, check_row_processors, check_sampling
+from .sampling import HIST_FRAMES, _as_list, _is_number, check_filters, check_row_processors, check_row_typical, check_sampling
 
 
 def _collapsed(six):
@@ -106,12 +113,13 @@ class Request:
     """One utterance of a ``BatchServer``: its audio arrives in ``chunks`` while it holds a slot; ``done`` once it has ended."""
 
     def __init__(self, rid, text, speaker, adapter, seed, max_audio_frames, tokens, mask, device, temperature=None, topk=None,
-                 top_p=1.0, min_p=0.0, repetition_penalty=1.0, repetition_window=HIST_FRAMES):
+                 top_p=1.0, min_p=0.0, repetition_penalty=1.0, repetition_window=HIST_FRAMES, typical_p=1.0):
         self.id, self.text, self.speaker, self.adapter, self.seed = rid, text, speaker, adapter, seed
         self.temperature, self.topk = temperature, topk      # resolved: what it is sampled with
         self.top_p, self.min_p = top_p, min_p                # (likewise; 1.0 / 0.0 on a server without row_filters)
         # (likewise; 1.0 / 64 without row_processors.  With them each of the six is a number, or a tuple of K: one per codebook)
         self.repetition_penalty, self.repetition_window = repetition_penalty, repetition_window
+        self.typical_p = typical_p                           # (likewise; 1.0 without row_typical)
         self.max_audio_frames = max_audio_frames
         self.slot: Optional[int] = None          # the slot it holds (None while queued and after it ended)
         self.done = False
@@ -195,7 +203,7 @@ class ServedConversation:
     one all-zero EOS frame; a spoken turn's frames are the sampled codes; the EOS frame always enters with the next feed."""
 
     def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None, top_p=None, min_p=None,
-                 keep_turns: int = 0, repetition_penalty=None, repetition_window=None, voice=None):
+                 keep_turns: int = 0, repetition_penalty=None, repetition_window=None, voice=None, typical_p=None):
         if on_overflow not in OVERFLOW:
             raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
         self._keep_turns = check_keep_turns(keep_turns)
@@ -204,6 +212,7 @@ class ServedConversation:
         # its turns' defaults, resolved
         (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window) = server._resolve(
             "conversation", temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        self.typical_p = server._typical("conversation", typical_p)
         K1 = server._K + 1
         self._tokens = torch.zeros(0, K1, dtype=torch.long, device=self._gen.device)
         self._mask = torch.zeros(0, K1, dtype=torch.bool, device=self._gen.device)
@@ -291,17 +300,18 @@ class ServedConversation:
     @torch.inference_mode()
     def say(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: Optional[float] = None,
             topk: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None,
-            repetition_penalty=None, repetition_window=None) -> Request:
+            repetition_penalty=None, repetition_window=None, typical_p=None) -> Request:
         """Queue the next spoken turn; its audio streams through ``step()`` / ``run()`` like any request's.  The length rule
         counts ``chunk_frames - 1`` frames beyond ``max_audio_length_ms``: a conversation's row samples to the end of its last
         chunk (module docstring), and that must fit the cache - it raises here, not in ``step``.  ``temperature`` / ``topk``
         (``row_sampling`` servers), ``top_p`` / ``min_p`` (``row_filters`` servers) and ``repetition_penalty`` / ``repetition_window`` /
-        a sequence of K values for any of the six (``row_processors`` servers): this turn's, over the conversation's.  The
-        window looks at this turn's frames only."""
+        a sequence of K values for any of the six (``row_processors`` servers), ``typical_p`` (``row_typical`` servers): this
+        turn's, over the conversation's.  The window looks at this turn's frames only."""
         self._idle("say")
         srv = self._srv
         six = srv._resolve("say", temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
                            (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window))
+        typical_p = srv._typical("say", typical_p, self.typical_p)
         max_audio_frames = int(max_audio_length_ms / 80)
         if max_audio_frames < 1:
             raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
@@ -311,7 +321,7 @@ class ServedConversation:
         feed_m = torch.cat([self._mask[self._cached:], tm.bool().to(self._mask.device)], 0)
         self._push(tt.long(), tm.bool())
         req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device,
-                      *six)
+                      *six, typical_p=typical_p)
         req._conv, req._base, req.sample_rate = self, self._tokens.shape[0], srv.sample_rate
         srv._next_id += 1
         srv._queue.append(req)
@@ -351,13 +361,20 @@ class BatchServer:
     own; every draw goes through the filtered rows sampler.  ``row_processors`` (needs ``row_sampling``; includes what
     ``row_filters`` gives): ``repetition_penalty`` / ``repetition_window`` join the requests' defaults, each of the six may be a
     sequence of K values (one per codebook), and every draw goes through the processed rows sampler, which remembers each slot's
-    last 64 frames (``DecodeState.set_row_processors``)."""
+    last 64 frames (``DecodeState.set_row_processors``).  ``row_typical`` (needs ``row_sampling``; includes what ``row_processors``
+    gives): ``typical_p`` joins the requests' defaults, a number or K numbers, and every draw goes through the typical rows
+    sampler (``DecodeState.set_row_typical``); a request at 1.0 has the codes it has with ``row_processors``."""
 
     def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
                  row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
                  output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
-                 repetition_window=HIST_FRAMES):
+                 repetition_window=HIST_FRAMES, row_typical: bool = False, typical_p=1.0):
         out_rs = gen._out_resampler(output_sample_rate)      # (a bad rate raises here, before anything is taken over)
+        if row_typical and not row_sampling:
+            raise ValueError("serve(row_typical=True) needs row_sampling=True: typical sampling lives in the rows sampler")
+        if not row_typical and not (_is_number(typical_p) and typical_p == 1.0):
+            raise ValueError(f"typical_p={typical_p!r} needs a server made with serve(row_typical=True) (and row_sampling=True)")
+        row_processors = bool(row_processors or row_typical)
         if row_processors and not row_sampling:
             raise ValueError("serve(row_processors=True) needs row_sampling=True: the repetition penalty and per-codebook "
                              "parameters live in the rows sampler")
@@ -385,6 +402,8 @@ class BatchServer:
         self.slots, self.chunk_frames, self.hear_slots = int(slots), int(chunk_frames), int(hear_slots)
         self.row_sampling, self.row_filters, self.row_processors = bool(row_sampling), bool(row_filters), bool(row_processors)
         self._K = gen._model.args.audio_num_codebooks
+        self.row_typical = bool(row_typical)
+        self.typical_p = self._typical("serve", typical_p, 1.0) if self.row_typical else 1.0
         self.repetition_penalty, self.repetition_window = 1.0, HIST_FRAMES
         if self.row_processors:                          # (the requests' defaults: held to the requests' rule, before anything is taken over)
             (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window) = _collapsed(
@@ -414,7 +433,10 @@ class BatchServer:
         if out_rs is not None:
             self._out = out_rs.stream_rows(self.slots, self.chunk_frames * (int(gen.sample_rate) * 80 // 1000))     # (80 ms frames)
         self._model._decode_state = self._state
-        if self.row_processors:
+        if self.row_typical:
+            for b in range(self.slots):                  # (before the first capture: the frame holds the typical sampler)
+                self._state.set_row_typical(b, *self._defaults(), self.typical_p)
+        elif self.row_processors:
             for b in range(self.slots):                  # (before the first capture: the frame holds the processed sampler)
                 self._state.set_row_processors(b, *self._defaults())
         elif self.row_sampling:
@@ -486,6 +508,21 @@ class BatchServer:
         except ValueError as e:
             raise ValueError(f"{what}: {e}") from None
 
+    def _typical(self, what, typical_p, default=None):
+        """A request's ``typical_p`` (None: not named), resolved against ``default`` (the server's if None) and held to
+        ``check_typical`` - at the call.  On a ``row_typical`` server a number or K numbers; on any other server anything but None
+        or 1 is refused."""
+        if typical_p is None:
+            return self.typical_p if default is None else default
+        if not self.row_typical:
+            if _is_number(typical_p) and typical_p == 1.0:
+                return 1.0
+            raise ValueError(f"{what}: typical_p needs a server made with serve(row_typical=True) (with row_sampling=True)")
+        try:
+            return _collapsed((check_row_typical(self._K, typical_p),))[0]
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") from None
+
     def _sample_args(self):
         """What ``serve_first`` / ``serve_frame`` get: the server's two numbers, or None, None (each row's own pair)."""
         return (None, None) if self.row_sampling else (self.temperature, self.topk)
@@ -493,16 +530,18 @@ class BatchServer:
     def submit(self, text: str, speaker: int, context, adapter: Optional[str] = None, seed: Optional[int] = None,
                max_audio_length_ms: float = 90_000, temperature: Optional[float] = None, topk: Optional[int] = None,
                top_p: Optional[float] = None, min_p: Optional[float] = None, repetition_penalty=None,
-               repetition_window=None, voice=None) -> Request:
+               repetition_window=None, voice=None, typical_p=None) -> Request:
         """Queue one utterance; it takes a slot at the next chunk boundary that has a free one.  The prompt is tokenised here, so
         the reference's length rule ("Inputs too long ...") and an unknown adapter name raise here.  ``temperature`` / ``topk``
         (``row_sampling`` servers), ``top_p`` / ``min_p`` (``row_filters`` servers) and ``repetition_penalty`` / ``repetition_window`` /
-        a sequence of K values, one per codebook, for any of the six (``row_processors`` servers): this request's, over the
-        server's.  ``voice``: a ``Voice`` of this Generator - the prompt is the voice, then ``context`` (which may be empty), then
+        a sequence of K values, one per codebook, for any of the six (``row_processors`` servers), ``typical_p`` (``row_typical``
+        servers): this request's, over the server's.
+        ``voice``: a ``Voice`` of this Generator - the prompt is the voice, then ``context`` (which may be empty), then
         the text; only context and text are tokenised here and fed at admission, and the length rule counts the voice's positions.
         ``adapter`` must be None or the voice's: the request speaks with the voice's."""
         self._check()
         six = self._resolve("submit", temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+        typical_p = self._typical("submit", typical_p)
         if voice is not None:
             adapter = voice.check(self._gen, adapter, "submit")
         if adapter is not None and adapter not in self._bank:
@@ -523,7 +562,7 @@ class BatchServer:
                 if voice.positions + tokens.shape[1] >= limit:
                     raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
         req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device,
-                      *six)
+                      *six, typical_p=typical_p)
         req.sample_rate, req._voice = self.sample_rate, voice
         self._next_id += 1
         self._queue.append(req)
@@ -533,14 +572,15 @@ class BatchServer:
                      on_overflow: str = "error", temperature: Optional[float] = None,
                      topk: Optional[int] = None, top_p: Optional[float] = None,
                      min_p: Optional[float] = None, keep_turns: int = 0, repetition_penalty=None,
-                     repetition_window=None, voice=None) -> ServedConversation:
+                     repetition_window=None, voice=None, typical_p=None) -> ServedConversation:
         """A multi-turn dialogue on this server: ``conv.say(text, speaker, max_audio_length_ms)`` queues its next spoken turn (a
         ``Request``), ``conv.add(Segment)`` is the other party's turn, ``conv.close()`` drops its parked cache.  ``adapter`` and
         ``seed`` hold for the whole conversation; ``on_overflow`` / ``keep_turns`` as for ``Generator.conversation`` (``"shift"``
         slides the parked cache at ``say``).  ``temperature`` / ``topk``
         (``row_sampling`` servers), ``top_p`` / ``min_p`` (``row_filters`` servers) and ``repetition_penalty`` /
-        ``repetition_window`` / per-codebook sequences (``row_processors`` servers): the defaults of its turns, over the
-        server's; ``say`` may name a turn's own.  ``voice``: a ``Voice`` of this Generator the history starts with, already
+        ``repetition_window`` / per-codebook sequences (``row_processors`` servers), ``typical_p`` (``row_typical`` servers): the
+        defaults of its turns, over the server's; ``say`` may name a turn's own.
+        ``voice``: a ``Voice`` of this Generator the history starts with, already
         cached - its K / V are the conversation's parked cache (shared, never written), so the first ``say`` is resumed and
         fed like a later turn; ``context`` comes after the voice; ``adapter`` must be None or the voice's."""
         self._check()
@@ -549,7 +589,7 @@ class BatchServer:
         if adapter is not None and adapter not in self._bank:
             raise ValueError(f"unknown LoRA adapter {adapter!r} (bound by this server: {list(self._bank)})")
         return ServedConversation(self, list(context), adapter, seed, on_overflow, temperature, topk, top_p, min_p, keep_turns,
-                                  repetition_penalty, repetition_window, voice)
+                                  repetition_penalty, repetition_window, voice, typical_p)
 
     @property
     def queued(self) -> int:
@@ -670,7 +710,11 @@ class BatchServer:
             req = self._queue.popleft()
             conv = req._conv
             st.set_row_adapter(b, self._bank[req.adapter] if req.adapter is not None else None)
-            if self.row_processors:
+            if self.row_typical:
+                st.set_row_typical(b, req.temperature, req.topk, req.top_p, req.min_p, req.repetition_penalty,
+                                   req.repetition_window, req.typical_p)
+                st.reset_row_history(b)
+            elif self.row_processors:
                 # (every joining row, resumed turns included: a turn's window covers its own frames)
                 st.set_row_processors(b, req.temperature, req.topk, req.top_p, req.min_p, req.repetition_penalty,
                                       req.repetition_window)

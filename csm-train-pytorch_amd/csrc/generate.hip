@@ -81,14 +81,14 @@ __device__ __forceinline__ int dpp_row_shr_add(int v, int ctrl_n) {   // v + (v 
 // positive number (zero, negative, NaN, inf) counts as 1.  The one-wave / block-wide choice stays block-uniform: a workgroup
 // is one row.
 struct SampleScalars {
-    static constexpr bool FILTERS = false, PENALTY = false;
+    static constexpr bool FILTERS = false, PENALTY = false, TYPICAL = false;
     int topk;
     float temperature;
     __device__ __forceinline__ int k(int, int) const { return topk; }
     __device__ __forceinline__ float t(int) const { return temperature; }
 };
 struct SampleRows {
-    static constexpr bool FILTERS = false, PENALTY = false;
+    static constexpr bool FILTERS = false, PENALTY = false, TYPICAL = false;
     const int* topk;
     const float* temperature;
     __device__ __forceinline__ int k(int row, int V) const { const int v = topk[row]; return v < 1 ? 1 : (v > V ? V : v); }
@@ -112,7 +112,7 @@ struct SampleRows {
 // Error: |kernel's sum P_j - exact| <= 2 (V 2^-40 + (2 + dbar) 2^-24), dbar the P-weighted mean of
 // max v - v_j; |kernel's e_i / exact - 1| <= (2 + max v - v_i) 2^-24.
 struct SampleFiltered : SampleRows {
-    static constexpr bool FILTERS = true, PENALTY = false;
+    static constexpr bool FILTERS = true, PENALTY = false, TYPICAL = false;
     const float* top_p;
     const float* min_p;
     __device__ __forceinline__ float p(int row) const { const float v = top_p[row]; return (v > 0.f && v <= 1.f) ? v : 1.f; }
@@ -135,7 +135,7 @@ struct SampleFiltered : SampleRows {
 // row's block touches the row's ring and counter.
 constexpr int SMP_HIST = 64;
 struct SampleProcessed : SampleFiltered {
-    static constexpr bool FILTERS = true, PENALTY = true;
+    static constexpr bool FILTERS = true, PENALTY = true, TYPICAL = false;
     const float* penalty;
     const int* window;
     int* hist;
@@ -152,6 +152,28 @@ struct SampleProcessed : SampleFiltered {
         }
     }
 };
+// SampleTypical (csm_sample_typical_rows): SampleProcessed plus locally typical sampling (Meister et al. 2022) per row, one more
+// block-uniform load issued with the others.  It comes last, on the set N the nucleus leaves.  With P_i = e_i / sum_N e_j,
+// h_i = -ln P_i = d_i + ln sum_N e_j (d_i = max v - v_i) and H = sum_N P_i h_i, a token's distance from typical is
+//   delta_i = |h_i - H| = |d_i - D|,  D = sum_N P_i d_i    (ln sum_N e_j is in h_i and in H alike: it is never formed),
+//   T = { i in N : sum over j in N with delta_j < delta_i of P_j  <  typical_p };
+// the token that crosses typical_p is kept, equal values have equal delta and stay or go together, and nothing lies below the
+// smallest delta, so T is never empty - but it need not hold the largest value: the finish takes its max over T.  A typical_p
+// outside (0, 1] (NaN included) counts as 1, and 1 skips all of it (block-uniform): the SampleProcessed kernel.
+// D is ONE number per row: e_i d_i is summed in the mass's 2^-40 fixed point beside e_i (integer sums: any order gives the same
+// bits), D = (float)((double)W / (double)S), and delta_i = fabsf(d_i - D) sees the token's value and D only.
+//  * at most 64 values in N: in the one-wave finish, after the nucleus - two wave sums, delta per lane, then the nucleus's
+//    readlane walk with `delta_j < delta_i` for `v_j > v_i`.
+//  * more: smp_mass_select a second time, on the key ~bits(delta) (delta >= 0: its bit pattern is ordered, and complemented the
+//    most typical comes first; never 0, which stays "not in N").  The 8 KB of mass histograms are zeroed again after the count
+//    that follows the nucleus.  Seven barriers: one for the sums and the zeroes, four passes, two for the count of T.
+// Error: |kernel's delta_i - exact| <= 2 a + (2 max_N d + D) 2^-24 with
+// a = (6 D + D2 + D^2) 2^-24 + (1 + D) V 2^-40, D2 = sum_N P_i d_i^2; the mass sums are the nucleus's.
+struct SampleTypical : SampleProcessed {
+    static constexpr bool FILTERS = true, PENALTY = true, TYPICAL = true;
+    const float* typical_p;
+    __device__ __forceinline__ float y(int row) const { const float v = typical_p[row]; return (v > 0.f && v <= 1.f) ? v : 1.f; }
+};
 constexpr float SMP_MASS_ONE = 1099511627776.f;                          // 2^40: the fixed-point image of e = 1
 __device__ __forceinline__ unsigned long long smp_mass(float e) { return (unsigned long long)(e * SMP_MASS_ONE); }   // (exact product, truncated)
 __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int l) {
@@ -166,6 +188,72 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 __device__ __forceinline__ unsigned long long smp_tau(unsigned long long S, float top_p) {   // smallest integer >= top_p * S (S < 2^53: exact)
     return (unsigned long long)ceil((double)S * (double)top_p);
 }
+// D = W / S: both below 2^53, so exact as doubles; the quotient is rounded to fp32 once more
+__device__ __forceinline__ float smp_mean(unsigned long long W, unsigned long long S) {
+    return (float)((double)W / (double)S);
+}
+// The block-wide mass select of the nucleus and of typical sampling: the last key, from the top, that is kept when `trem` of the
+// mass of the keys >= lo is wanted - the largest key whose mass at or above it reaches trem.  Token j's mass is
+// smp_mass(expf(val[j] - gtop)); mhist is zeroed and published by the caller.  Four 8-bit passes, one barrier each; the digit's
+// bin is the first from the top whose inclusive mass reaches trem, and trem minus the mass above it is wanted inside it.
+template <int NPT>
+__device__ __forceinline__ uint32_t smp_mass_select(const uint32_t (&key)[NPT], const float (&val)[NPT], float gtop, uint32_t lo,
+                                                    unsigned long long trem, unsigned long long (*mhist)[256], int V, int lane) {
+    uint32_t mprefix = 0u;
+#pragma unroll 1
+    for (int ps = 0; ps < 4; ++ps) {
+        const int shift = 24 - 8 * ps;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+            const int c = threadIdx.x + 256 * j;
+            const bool in = c < V && key[j] >= lo && (ps == 0 || (key[j] >> (shift + 8)) == (mprefix >> (shift + 8)));
+            if (in) atomicAdd(&mhist[ps][(key[j] >> shift) & 255u], smp_mass(expf(val[j] - gtop)));
+        }
+        __syncthreads();
+        // lane l owns bins 252 - 4l .. 255 - 4l, as in the count select; the scan runs from the top bin down
+        const ulonglong2 hlo = *reinterpret_cast<const ulonglong2*>(&mhist[ps][252 - 4 * lane]);
+        const ulonglong2 hhi = *reinterpret_cast<const ulonglong2*>(&mhist[ps][254 - 4 * lane]);
+        const unsigned long long b3 = hhi.y, b2 = hhi.x, b1 = hlo.y, b0 = hlo.x;
+        const unsigned long long mn = b3 + b2 + b1 + b0;
+        unsigned long long pr = mn;             // -> mass in my bins and every bin above them
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long y = __shfl_up(pr, o, 64);
+            if (lane >= o) pr += y;
+        }
+        unsigned long long above = pr - mn;
+        int digit;
+        if (above + b3 >= trem) digit = 255 - 4 * lane;
+        else {
+            above += b3;
+            if (above + b2 >= trem) digit = 254 - 4 * lane;
+            else {
+                above += b2;
+                if (above + b1 >= trem) digit = 253 - 4 * lane;
+                else { above += b1; digit = 252 - 4 * lane; }
+            }
+        }
+        const unsigned long long cross = __ballot(pr >= trem);
+        const int L = cross ? __ffsll((long long)cross) - 1 : 63;          // (never empty: the matching mass is >= trem)
+        digit = __builtin_amdgcn_readlane(digit, L);
+        above = readlane_u64(above, L);
+        mprefix |= (uint32_t)digit << shift;
+        trem -= above;
+    }
+    return mprefix;
+}
+// The kept keys (>= prefix) of this thread, and with them the inclusive count over the wave's lanes up to this one.
+template <int NPT>
+__device__ __forceinline__ int smp_count_kept(const uint32_t (&key)[NPT], uint32_t prefix, int V, int lane, int& mine) {
+    mine = 0;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) mine += (threadIdx.x + 256 * j < V && key[j] >= prefix) ? 1 : 0;
+    int pre = mine;
+    pre = dpp_row_shr_add(pre, 1); pre = dpp_row_shr_add(pre, 2); pre = dpp_row_shr_add(pre, 4); pre = dpp_row_shr_add(pre, 8);
+    const int t0 = __builtin_amdgcn_readlane(pre, 15), t1 = __builtin_amdgcn_readlane(pre, 31), t2 = __builtin_amdgcn_readlane(pre, 47);
+    pre += (lane >= 16 ? t0 : 0) + (lane >= 32 ? t1 : 0) + (lane >= 48 ? t2 : 0);
+    return pre;
+}
 template <int NPT, class Params>
 __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restrict__ logits, const float* __restrict__ q,
                                                           int* __restrict__ out, int V, int ldl, const Params prm) {
@@ -177,6 +265,8 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
     const float temperature = prm.t(row);
     float top_p = 1.f, min_p = 0.f;
     if constexpr (Params::FILTERS) { top_p = prm.p(row); min_p = prm.m(row); }
+    float typical_p = 1.f;
+    if constexpr (Params::TYPICAL) typical_p = prm.y(row);
     const float* x = logits + (size_t)row * ldl;
     const float* qq = q + (size_t)row * V;
     const int lane = threadIdx.x & 63;
@@ -291,24 +381,20 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
     __shared__ float cval[64], cq[64];
     __shared__ int cidx[64];
     __shared__ int wtot[4];
-    int mine = 0;
-#pragma unroll
-    for (int j = 0; j < NPT; ++j) mine += (threadIdx.x + 256 * j < V && key[j] >= prefix) ? 1 : 0;
-    int pre = mine;
-    pre = dpp_row_shr_add(pre, 1); pre = dpp_row_shr_add(pre, 2); pre = dpp_row_shr_add(pre, 4); pre = dpp_row_shr_add(pre, 8);
-    {
-        const int t0 = __builtin_amdgcn_readlane(pre, 15), t1 = __builtin_amdgcn_readlane(pre, 31), t2 = __builtin_amdgcn_readlane(pre, 47);
-        pre += (lane >= 16 ? t0 : 0) + (lane >= 32 ? t1 : 0) + (lane >= 48 ? t2 : 0);
-    }
+    int mine;
+    int pre = smp_count_kept<NPT>(key, prefix, V, lane, mine);
     if (lane == 63) wtot[threadIdx.x >> 6] = pre;
     __syncthreads();
     const int w_ = threadIdx.x >> 6;
     int before = (w_ > 0 ? wtot[0] : 0) + (w_ > 1 ? wtot[1] : 0) + (w_ > 2 ? wtot[2] : 0);
     int total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
     bool wave_filters = false;                              // steps 2 and 3 still to be done, by the one-wave finish
+    bool typical = false;                                   // the typical step still to be done (block-uniform)
+    bool typical_done = false;                              // ... or done: the finish takes its max over T
+    if constexpr (Params::TYPICAL) typical = typical_p < 1.f;
     if constexpr (Params::FILTERS) {
         wave_filters = top_p < 1.f || min_p > 0.f;          // (block-uniform; false: the SampleRows kernel from here on)
-        if (wave_filters && total > 64) {
+        if ((wave_filters || typical) && total > 64) {
             // ---- more than 64 kept values: min-p and the nucleus block-wide, on the keys in registers
             __shared__ __attribute__((aligned(16))) unsigned long long mhist[4][256];
             __shared__ unsigned long long sred[4];
@@ -331,65 +417,56 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
                 sm = wave_sum_u64(sm);
                 if (lane == 0) sred[w_] = sm;
                 __syncthreads();                            // the wave sums, and the zeroed histograms
-                unsigned long long trem = smp_tau(sred[0] + sred[1] + sred[2] + sred[3], top_p);   // mass still wanted
-                uint32_t mprefix = 0u;
-#pragma unroll 1
-                for (int ps = 0; ps < 4; ++ps) {
-                    const int shift = 24 - 8 * ps;
-#pragma unroll
-                    for (int j = 0; j < NPT; ++j) {
-                        const int c = threadIdx.x + 256 * j;
-                        const bool in = c < V && key[j] >= prefix && (ps == 0 || (key[j] >> (shift + 8)) == (mprefix >> (shift + 8)));
-                        if (in) atomicAdd(&mhist[ps][(key[j] >> shift) & 255u], smp_mass(expf(val[j] - gtop)));
-                    }
-                    __syncthreads();
-                    // lane l owns bins 252 - 4l .. 255 - 4l, as in the count select; the scan runs from the top bin down
-                    const ulonglong2 hlo = *reinterpret_cast<const ulonglong2*>(&mhist[ps][252 - 4 * lane]);
-                    const ulonglong2 hhi = *reinterpret_cast<const ulonglong2*>(&mhist[ps][254 - 4 * lane]);
-                    const unsigned long long b3 = hhi.y, b2 = hhi.x, b1 = hlo.y, b0 = hlo.x;
-                    const unsigned long long mn = b3 + b2 + b1 + b0;
-                    unsigned long long pr = mn;             // -> mass in my bins and every bin above them
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const unsigned long long y = __shfl_up(pr, o, 64);
-                        if (lane >= o) pr += y;
-                    }
-                    unsigned long long above = pr - mn;
-                    int digit;
-                    if (above + b3 >= trem) digit = 255 - 4 * lane;
-                    else {
-                        above += b3;
-                        if (above + b2 >= trem) digit = 254 - 4 * lane;
-                        else {
-                            above += b2;
-                            if (above + b1 >= trem) digit = 253 - 4 * lane;
-                            else { above += b1; digit = 252 - 4 * lane; }
-                        }
-                    }
-                    const unsigned long long cross = __ballot(pr >= trem);
-                    const int L = cross ? __ffsll((long long)cross) - 1 : 63;          // (never empty: the matching mass is >= trem)
-                    digit = __builtin_amdgcn_readlane(digit, L);
-                    above = readlane_u64(above, L);
-                    mprefix |= (uint32_t)digit << shift;
-                    trem -= above;
-                }
-                prefix = mprefix;                           // the last kept key (>= the top-k threshold: its bin held mass)
+                const unsigned long long trem = smp_tau(sred[0] + sred[1] + sred[2] + sred[3], top_p);   // mass still wanted
+                // the last kept key (>= the top-k threshold: its bin held mass)
+                prefix = smp_mass_select<NPT>(key, val, gtop, prefix, trem, mhist, V, lane);
             }
             // the kept set changed: count it again for the compaction
-            mine = 0;
-#pragma unroll
-            for (int j = 0; j < NPT; ++j) mine += (threadIdx.x + 256 * j < V && key[j] >= prefix) ? 1 : 0;
-            pre = mine;
-            pre = dpp_row_shr_add(pre, 1); pre = dpp_row_shr_add(pre, 2); pre = dpp_row_shr_add(pre, 4); pre = dpp_row_shr_add(pre, 8);
-            {
-                const int t0 = __builtin_amdgcn_readlane(pre, 15), t1 = __builtin_amdgcn_readlane(pre, 31), t2 = __builtin_amdgcn_readlane(pre, 47);
-                pre += (lane >= 16 ? t0 : 0) + (lane >= 32 ? t1 : 0) + (lane >= 48 ? t2 : 0);
-            }
+            pre = smp_count_kept<NPT>(key, prefix, V, lane, mine);
             __syncthreads();                                // every wave has read the first count
             if (lane == 63) wtot[w_] = pre;
             __syncthreads();
             before = (w_ > 0 ? wtot[0] : 0) + (w_ > 1 ? wtot[1] : 0) + (w_ > 2 ? wtot[2] : 0);
             total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+            if constexpr (Params::TYPICAL) {
+                if (typical && total > 64) {
+                    // ---- more than 64 values in N: typical block-wide.  Every wave is past the barriers of the count, so
+                    //      nobody still reads the nucleus's histograms or sums
+                    __shared__ unsigned long long tred[2][4];
+                    typical = false;
+                    typical_done = true;
+#pragma unroll
+                    for (int ps = 0; ps < 4; ++ps) mhist[ps][threadIdx.x] = 0ull;
+                    unsigned long long ts = 0ull, tw = 0ull;            // sum e_i and sum e_i d_i over N, in 2^-40
+#pragma unroll
+                    for (int j = 0; j < NPT; ++j) {
+                        const int c = threadIdx.x + 256 * j;
+                        if (c < V && key[j] >= prefix) {
+                            const float e = expf(val[j] - gtop);
+                            ts += smp_mass(e);
+                            if (e > 0.f) tw += smp_mass(e * (gtop - val[j]));
+                        }
+                    }
+                    ts = wave_sum_u64(ts);
+                    tw = wave_sum_u64(tw);
+                    if (lane == 0) { tred[0][w_] = ts; tred[1][w_] = tw; }
+                    __syncthreads();                        // the wave sums, and the zeroed histograms
+                    const unsigned long long S = tred[0][0] + tred[0][1] + tred[0][2] + tred[0][3];
+                    const float D = smp_mean(tred[1][0] + tred[1][1] + tred[1][2] + tred[1][3], S);
+#pragma unroll
+                    for (int j = 0; j < NPT; ++j) {         // the keys become ~bits(delta); 0: not in N
+                        const int c = threadIdx.x + 256 * j;
+                        key[j] = (c < V && key[j] >= prefix) ? ~__float_as_uint(fabsf((gtop - val[j]) - D)) : 0u;
+                    }
+                    prefix = smp_mass_select<NPT>(key, val, gtop, 1u, smp_tau(S, typical_p), mhist, V, lane);
+                    pre = smp_count_kept<NPT>(key, prefix, V, lane, mine);
+                    __syncthreads();                        // every wave has read the second count
+                    if (lane == 63) wtot[w_] = pre;
+                    __syncthreads();
+                    before = (w_ > 0 ? wtot[0] : 0) + (w_ > 1 ? wtot[1] : 0) + (w_ > 2 ? wtot[2] : 0);
+                    total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+                }
+            }
         }
     }
     if (total <= 64) {                                      // (block-uniform)
@@ -403,7 +480,7 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
         if (threadIdx.x < 64) {
             bool on = lane < total;
             float v = on ? cval[lane] : -INFINITY;
-            const float top = wave_max(v);
+            float top = wave_max(v);
             if constexpr (Params::FILTERS) {
                 if (wave_filters) {                         // steps 2 and 3 on the compacted values, one per lane
                     const float e = on ? expf(v - top) : 0.f;
@@ -421,6 +498,27 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
                         on = on && above < tau;
                     }
                     v = on ? v : -INFINITY;
+                }
+            }
+            if constexpr (Params::TYPICAL) {
+                if (typical) {                              // the typical step on N, one value per lane
+                    const float d = top - v;
+                    const float e = on ? expf(v - top) : 0.f;
+                    const unsigned long long ms = smp_mass(e);
+                    const unsigned long long S = wave_sum_u64(ms);
+                    const float D = smp_mean(wave_sum_u64(e > 0.f ? smp_mass(e * d) : 0ull), S);
+                    const float delta = on ? fabsf(d - D) : INFINITY;
+                    const unsigned long long tau = smp_tau(S, typical_p);
+                    unsigned long long below = 0ull;        // mass of the values strictly more typical than mine
+#pragma unroll 1
+                    for (int j = 0; j < total; ++j) {
+                        const float dj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(delta), j));
+                        const unsigned long long mj = readlane_u64(ms, j);
+                        below += dj < delta ? mj : 0ull;
+                    }
+                    on = on && below < tau;
+                    v = on ? v : -INFINITY;
+                    top = wave_max(v);                      // (T need not hold the largest value)
                 }
             }
             const float e1 = on ? expf(v - top) : 0.f;
@@ -441,6 +539,14 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
         STAMP(6);
         STAMP_FLUSH(300);
         return;
+    }
+    if constexpr (Params::TYPICAL) {
+        if (typical_done) {                                 // (block-uniform) T need not hold the largest value: the max over T
+            tmax = -INFINITY;
+#pragma unroll
+            for (int j = 0; j < NPT; ++j)
+                if (threadIdx.x + 256 * j < V && key[j] >= prefix) tmax = fmaxf(tmax, val[j]);
+        }
     }
     const float top = block_max(tmax, fred);
     // log_softmax over kept values, then softmax of that (torch evaluates both)
@@ -534,7 +640,7 @@ __global__ __launch_bounds__(256) void rvq_decode_kernel(const long long* __rest
 
 }  // namespace
 
-// The four samplers' launch: the kernel with 9 values per thread where the row fits, else SMP_PER_THREAD; one workgroup per row.
+// The five samplers' launch: the kernel with 9 values per thread where the row fits, else SMP_PER_THREAD; one workgroup per row.
 template <class Params>
 static int sample_launch(const char* name, const float* logits, const float* q, int* out, int rows, int V, int ldl,
                          hipStream_t stream, const Params& prm) {
@@ -575,6 +681,17 @@ extern "C" int csm_sample_processed_rows(const float* logits, const float* q, in
     CSM_REQUIRE(ldh >= SMP_HIST, "csm_sample_processed_rows: ldh=%d is below the ring's %d", ldh, SMP_HIST);
     return sample_launch("csm_sample_processed_rows", logits, q, out, rows, V, ldl, stream,
                          SampleProcessed{topk, temperature, top_p, min_p, penalty, window, hist, ldh, frame, live, advance});
+}
+
+extern "C" int csm_sample_typical_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
+                                       const float* temperature, const float* top_p, const float* min_p, const float* penalty,
+                                       const int* window, int* hist, int ldh, int* frame, const int* live, int advance,
+                                       const float* typical_p, hipStream_t stream) {
+    CSM_REQUIRE(logits && q && out && topk && temperature && top_p && min_p && penalty && window && hist && frame && live &&
+                typical_p && rows > 0 && V > 0 && ldl >= V, "csm_sample_typical_rows: bad arguments");
+    CSM_REQUIRE(ldh >= SMP_HIST, "csm_sample_typical_rows: ldh=%d is below the ring's %d", ldh, SMP_HIST);
+    return sample_launch("csm_sample_typical_rows", logits, q, out, rows, V, ldl, stream,
+                         SampleTypical{topk, temperature, top_p, min_p, penalty, window, hist, ldh, frame, live, advance, typical_p});
 }
 
 extern "C" int csm_rvq_encode(const float* x, const float* codebooks, long long* codes, int T, int K, int C, int D,

@@ -279,6 +279,18 @@ int csm_sample_processed_rows(const float* logits, const float* q, int* out, int
                               const float* temperature, const float* top_p, const float* min_p, const float* penalty,
                               const int* window, int* hist, int ldh, int* frame, const int* live, int advance,
                               csm_stream_t stream);
+/* Locally typical sampling per row (additive, ABI 3): csm_sample_processed_rows with typical_p[r] (float, DEVICE memory), applied
+ * last, on the set N the nucleus leaves.  With P_i = e_i / sum over N of e_j, h_i = -ln P_i, H = sum over N of P_i h_i and
+ * delta_i = |h_i - H|:  T = { i in N : sum over j in N with delta_j < delta_i of P_j  <  typical_p[r] }  - a token stays while
+ * the mass of the strictly more typical tokens is below typical_p, so the token that crosses it is kept, equal values stay or go
+ * together and no index enters; T is never empty but need not hold the largest value.  log_softmax -> softmax -> argmax p / q
+ * then run over T.  A row with typical_p = 1 writes what csm_sample_processed_rows writes - out, ring and counter - for every
+ * input; a typical_p[r] outside (0, 1] (NaN included) counts as 1.  Mass and H are summed in 64-bit fixed point (quantum 2^-40):
+ * a launch gives the same bits every time (error bound: DESIGN.md section 6). */
+int csm_sample_typical_rows(const float* logits, const float* q, int* out, int rows, int V, int ldl, const int* topk,
+                            const float* temperature, const float* top_p, const float* min_p, const float* penalty,
+                            const int* window, int* hist, int ldh, int* frame, const int* live, int advance,
+                            const float* typical_p, csm_stream_t stream);
 
 /* ---- K15: batch-1 decode of Model.generate_frame (model.py:161-195) against KV caches ------------------------------ *
  * y[b][n] = sum_k x[b][k] W[n][k] (+ residual[b][n]), B <= 16 (weight-streaming matrix-vector product).  B <= 4: VALU kernels,

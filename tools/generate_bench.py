@@ -14,7 +14,8 @@ on one model at B = 4 / 8 / 16 (decode loop only).  GEN_FP8=1: decode frames/s w
 alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in each mode.  GEN_SERVE=1: the running batch (Generator.serve): rows-codec step against single steps, the server step at
 16 rows, the join stall (serve_main).  GEN_SERVE_SAMPLING=1: the rows sampler against the scalar one and the 16-row
 server step with row_sampling off / on (serve_sampling_main); GEN_SERVE_SAMPLING=processors: the processed rows sampler (repetition penalty, per-codebook
-parameters; serve_processors_main); GEN_SERVE_SAMPLING=filters: the filtered rows sampler (top-p / min-p)
+parameters; serve_processors_main); GEN_SERVE_SAMPLING=typical: the typical rows sampler (typical_p) at identity, one-wave and
+block-wide, and the server step with row_processors / row_typical (serve_typical_main); GEN_SERVE_SAMPLING=filters: the filtered rows sampler (top-p / min-p)
 in four forms and the server step with row_filters off / on (serve_filters_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
 time to the first chunk of turns 1 / 3 / 5 against stateless submits, one append_rows against one-row calls, park / resume, aggregate
 frames/s (serve_conv_main).  GEN_HEAR=1: a 5 s heard turn's last sample to the first chunk of the reply, with
@@ -1048,6 +1049,98 @@ def serve_processors_main():
               flush=True)
 
 
+def serve_typical_main():
+    """GEN_SERVE_SAMPLING=typical: locally typical sampling per request (Generator.serve(row_sampling=True, row_typical=True)), in the
+    shape of GEN_SERVE_SAMPLING=processors.  (a) the sampler alone, 16 rows, V = 2051 in the model's padded logits buffer, temperature
+    0.9, penalty 1.3 at window 16 (rings of random ids, frame 200, every row live), no top-p / min-p: csm_sample_processed_rows at
+    top-k 50; csm_sample_typical_rows at typical_p 1 (the block-uniform skip); at 0.9 with top-k 50 in every row (the one-wave form);
+    at 0.9 with top-k V in every row (the block-wide form: a second mass select), beside the processed sampler at top-k V.  200
+    back-to-back launches between two synchronisations, alternated, median (min .. max) of GEN_ROUNDS repeats (default 3).  (b) the
+    steady 16-row server step of GEN_SERVE's setting: row_processors on (the yardstick), row_typical on at identity (typical_p 1
+    everywhere), on with a mixed load (typical_p 0.2 .. 1.0, per codebook in a quarter of the rows, over the processors leg's
+    mixed penalties); each leg a fresh server, alternated GEN_ROUNDS times (default 3), per leg the median of 20 steps."""
+    dev = "cuda:0"
+    n = 4
+    V, ld = 2051, 2112
+    g = torch.Generator(device=dev).manual_seed(0)
+    lg = torch.randn(16, ld, device=dev, generator=g) * 2
+    q = torch.empty(16, V, device=dev).exponential_(1, generator=g)
+    out = torch.empty(16, dtype=torch.int32, device=dev)
+
+    def f32(v):
+        return torch.tensor(v, dtype=torch.float32, device=dev)
+
+    def i32(v):
+        return torch.tensor(v, dtype=torch.int32, device=dev)
+    k50, kV, t, p, m = i32([50] * 16), i32([V] * 16), f32([0.9] * 16), f32([1.0] * 16), f32([0.0] * 16)
+    hist = torch.randint(0, V, (16, 64), device=dev, generator=g).to(torch.int32)
+    frame, live = i32([200] * 16), i32([1] * 16)
+    r, w = f32([1.3] * 16), i32([16] * 16)
+    y1, y9 = f32([1.0] * 16), f32([0.9] * 16)
+
+    def typical(k, y):
+        return lambda: ops.sample_typical_rows(lg, q, out, k, t, p, m, r, w, hist, frame, live, y, advance=False, V=V)
+
+    def processed(k):
+        return lambda: ops.sample_processed_rows(lg, q, out, k, t, p, m, r, w, hist, frame, live, advance=False, V=V)
+    legs = {"processed, top-k 50 (csm_sample_processed_rows)": processed(k50),
+            "typical at identity (typical_p 1), top-k 50": typical(k50, y1),
+            "typical 0.9, top-k 50 (one-wave)": typical(k50, y9),
+            "processed, top-k V": processed(kV),
+            "typical 0.9, top-k V (block-wide)": typical(kV, y9)}
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    res = {name: [] for name in legs}
+    for f in legs.values():
+        _timed(f, 20)
+    for _ in range(rounds):
+        for name, f in legs.items():
+            res[name].append(_timed(f, 200))
+    for name, v in res.items():
+        v.sort()
+        print(f"GEN_SERVE_SAMPLING=typical (a) sampler, 16 rows, V={V}: {name}: median {v[len(v) // 2] * 1e6:.2f} us per launch "
+              f"(min {v[0] * 1e6:.2f}, max {v[-1] * 1e6:.2f}; {rounds} x 200 back-to-back launches)", flush=True)
+    if os.environ.get("GEN_SERVE_PARTS", "ab") == "a":
+        return
+    # ---- (b) the server step
+    codec = make_codec(dev)
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=codec)
+    K = model.args.audio_num_codebooks
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+    pens = [(1.0, 64), (1.3, 16), (2.0, 64), (1.1, 0), (1.5, 33), (1.3, 64), (1.2, 8), (1.7, 64)]
+    typs = [0.9, 0.2, 1.0, 0.5, 0.95, 0.7, 0.3, 0.99]
+    mixed = []
+    for b in range(16):
+        kw = dict(top_p=0.9, min_p=0.05, repetition_penalty=pens[b % 8][0], repetition_window=pens[b % 8][1], typical_p=typs[b % 8])
+        if b % 4 == 1:
+            kw.update(typical_p=[typs[b % 8]] + [0.8] * (K - 1), topk=[50] + [2051] * (K - 1))     # (the block-wide form too)
+        mixed.append(kw)
+    base = "row_processors (the yardstick)"
+    modes = {base: (dict(row_processors=True), [{}] * 16), "row_typical, identity": (dict(row_typical=True), [{}] * 16),
+             "row_typical, mixed": (dict(row_typical=True), mixed)}
+    meds = {name: [] for name in modes}
+    for _ in range(rounds):
+        for name, (flags, kws) in modes.items():
+            srv = gen.serve(slots=16, chunk_frames=n, row_sampling=True, **flags)
+            for i in range(16):
+                srv.submit(f"utterance number {i}: {text}", i, ctx, seed=i, max_audio_length_ms=80 * 400, **kws[i])
+            _timed(srv.step, 1)                                              # 16 prefills + the first chunk
+            _timed(srv.step, 2)                                              # eager warm-up frame, graph capture
+            steps = sorted(_timed(srv.step, 1) for _ in range(20))
+            meds[name].append(steps[len(steps) // 2])
+    for name, v in meds.items():
+        print(f"GEN_SERVE_SAMPLING=typical (b) server step, 16 rows x {n} frames, {name}: medians of 20 steps "
+              f"{[round(x * 1e3, 2) for x in v]} ms -> median {sorted(v)[len(v) // 2] * 1e3:.2f} ms, spread of the repeats "
+              f"{(max(v) - min(v)) * 1e3:.2f} ms", flush=True)
+    off = sorted(meds[base])[rounds // 2]
+    for name in ("row_typical, identity", "row_typical, mixed"):
+        on = sorted(meds[name])[rounds // 2]
+        print(f"GEN_SERVE_SAMPLING=typical (b) {name} - row_processors: {(on - off) * 1e3:+.2f} ms per step = "
+              f"{(on - off) * 1e6 / n:+.1f} us per frame = {(on - off) * 1e6 / n / K:+.2f} us per draw ({K} launches a frame; "
+              f"row_processors' own repeats span {(max(meds[base]) - min(meds[base])) * 1e3:.2f} ms)", flush=True)
+
+
 def serve_conv_main():
     """GEN_SERVE_CONV=1: conversations on the running batch (BatchServer.conversation) on CSM-1B random init - 16 slots,
     chunk_frames 4, 16 conversations of 6 turns: odd turns spoken (GEN_FRAMES frames, default 24), even turns 5 s of the other
@@ -1595,6 +1688,8 @@ def main():
         return serve_filters_main()
     if os.environ.get("GEN_SERVE_SAMPLING") == "processors":
         return serve_processors_main()
+    if os.environ.get("GEN_SERVE_SAMPLING") == "typical":
+        return serve_typical_main()
     if os.environ.get("GEN_SERVE_CONV") == "1":
         return serve_conv_main()
     if os.environ.get("GEN_SERVE") == "1":
