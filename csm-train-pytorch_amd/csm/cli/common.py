@@ -9,13 +9,19 @@ Three sources, in this order:
 * ``--token-file``: a ``torch.save``d list of dicts with ``input_tokens [S,33]`` int64, ``input_masks [S,33]`` bool,
   ``target_audio_tokens [T,32]`` int64 (exactly what ``CSMDataset.__getitem__`` yields, training_data.py:245-302).
 * ``--synthetic N``: seeded synthetic sequences.
+
+``--objective next-frame`` (``--loss-on target|all``) turns the items of all three into the next-frame form
+(``csm.data.to_next_frame``); the default, ``reference``, leaves every item what it has always been.
 """
+import logging
 from pathlib import Path
 
 import torch
 from torch.utils.data import Dataset
 
 from ..data import SyntheticCSMDataset, collate_variable_length
+
+logger = logging.getLogger(__name__)
 
 
 class TokenFileDataset(Dataset):
@@ -50,6 +56,24 @@ def add_data_args(parser, context_turns: int = 0):
     g.add_argument("--pack-sequences", action="store_true",
                    help="pack several examples into each row of --max-seq-len positions (segment-masked attention, RoPE restarting per "
                         "example) instead of padding to the batch maximum; implies --ignore-padding")
+    add_objective_args(g)
+
+
+def add_objective_args(group):
+    group.add_argument("--objective", choices=["reference", "next-frame"], default="reference",
+                       help="reference: input position p is labelled with target frame p (the reference's pairing, kept for parity "
+                            "and the benchmark); next-frame: the target's frames and EOS join the input and every position is "
+                            "labelled with the next position's frame - the likelihood generate() samples from; implies "
+                            "--ignore-padding")
+    group.add_argument("--loss-on", choices=["target", "all"], default="target",
+                       help="with --objective next-frame: train the target utterance's frames only, or every segment's audio")
+
+
+def objective_of(args):
+    """(objective, loss_on) of parsed arguments as the data layer spells them; arguments without the flags: the reference's."""
+    from ..data.training_data import check_objective
+    loss_on = getattr(args, "loss_on", "target")
+    return check_objective(getattr(args, "objective", "reference"), loss_on), loss_on
 
 
 def load_raw_examples(args, logger=None):
@@ -67,22 +91,51 @@ def load_raw_examples(args, logger=None):
     return per_file
 
 
-def tokenise_examples(per_file, text_tokenizer, audio_tokenizer, max_seq_len, context_turns=0):
-    """Contextual examples (reference ``prepare_dataset`` cli/train.py:281-329: no context) -> tokenised items."""
+def tokenise_examples(per_file, text_tokenizer, audio_tokenizer, max_seq_len, context_turns=0, objective="reference", loss_on="target"):
+    """Contextual examples (reference ``prepare_dataset`` cli/train.py:281-329: no context) -> tokenised items.  Under
+    ``objective="next_frame"`` an example whose target alone does not fit ``max_seq_len`` is skipped and counted in the log."""
     from ..data import ContextualExampleGenerator, CSMDataset
     gen = ContextualExampleGenerator(max_context_turns=context_turns)
     ctx = []
     for examples in per_file:
         ctx += gen.create_contextual_examples(examples) if context_turns > 0 else [{"context": [], "target": e} for e in examples]
-    ds = CSMDataset(ctx, text_tokenizer, audio_tokenizer, max_seq_len=max_seq_len)
-    return [ds[i] for i in range(len(ds))]
+    ds = CSMDataset(ctx, text_tokenizer, audio_tokenizer, max_seq_len=max_seq_len, objective=objective, loss_on=loss_on)
+    if objective != "next_frame":
+        return [ds[i] for i in range(len(ds))]
+    items, skipped = [], 0
+    for i in range(len(ds)):
+        try:
+            items.append(ds[i])
+        except ValueError as e:                       # the target alone is longer than max_seq_len
+            logger.debug(str(e))
+            skipped += 1
+    _log_skipped(skipped, len(ds), max_seq_len)
+    return items
+
+
+def _log_skipped(skipped, total, max_seq_len):
+    if skipped:
+        logger.warning(f"next-frame objective: skipped {skipped} of {total} examples whose target (text, frames and EOS) does not "
+                       f"fit --max-seq-len {max_seq_len}")
+
+
+def next_frame_items(items, max_seq_len, loss_on="target"):
+    """Token-file items in the next-frame form: an item of the reference form goes through ``to_next_frame``, one that is in the
+    new form already (``is_next_frame``) passes through.  Nothing is cut to fit - that would cut the target - so an item longer
+    than ``max_seq_len`` is skipped and counted in the log."""
+    from ..data import is_next_frame, to_next_frame
+    out = [it if is_next_frame(it) else to_next_frame(it, loss_on) for it in items]
+    kept = [it for it in out if it["input_tokens"].shape[0] <= max_seq_len]
+    _log_skipped(len(out) - len(kept), len(out), max_seq_len)
+    return kept
 
 
 def load_datasets(args):
+    objective, loss_on = objective_of(args)
     if args.synthetic:
         n_val = max(1, int(args.synthetic * args.val_split)) if args.val_split > 0 else 0
-        train = SyntheticCSMDataset(args.synthetic - n_val, args.max_seq_len, seed=1234)
-        val = SyntheticCSMDataset(n_val, args.max_seq_len, seed=4321) if n_val else None
+        train = SyntheticCSMDataset(args.synthetic - n_val, args.max_seq_len, seed=1234, objective=objective)
+        val = SyntheticCSMDataset(n_val, args.max_seq_len, seed=4321, objective=objective) if n_val else None
         return train, val
     if args.audio_dir:
         if not (args.transcript_dir and args.mimi_weights and args.text_tokenizer):
@@ -91,13 +144,16 @@ def load_datasets(args):
         from ..codec import load_mimi
         from ..generator import load_llama3_tokenizer
         items = tokenise_examples(load_raw_examples(args), load_llama3_tokenizer(args.text_tokenizer),
-                                  load_mimi(args.mimi_weights), args.max_seq_len, args.context_turns)
+                                  load_mimi(args.mimi_weights), args.max_seq_len, args.context_turns, objective, loss_on)
         n_val = int(len(items) * args.val_split)              # reference split: the tail is the validation set (train.py:293-300)
         n_train = len(items) - n_val
         return TokenFileDataset(items[:n_train]), (TokenFileDataset(items[n_train:]) if n_val else None)
     if not args.token_file:
         raise SystemExit("give --audio-dir/--transcript-dir (+ --mimi-weights, --text-tokenizer), --token-file or --synthetic N")
     items = torch.load(args.token_file, map_location="cpu", weights_only=False)
-    items = [{k: v[:args.max_seq_len] for k, v in it.items()} for it in items]
+    if objective == "next_frame":
+        items = next_frame_items(items, args.max_seq_len, loss_on)
+    else:
+        items = [{k: v[:args.max_seq_len] for k, v in it.items()} for it in items]
     n_val = int(len(items) * args.val_split)
     return TokenFileDataset(items[n_val:]), (TokenFileDataset(items[:n_val]) if n_val else None)

@@ -4,7 +4,7 @@ import logging
 
 from ..training.dp import init_distributed
 from ..training.lora_trainer import CSMLoRATrainer
-from .common import add_data_args, load_datasets
+from .common import add_data_args, load_datasets, objective_of
 
 
 def parse_args(argv=None):
@@ -75,7 +75,8 @@ def main(argv=None):
                              semantic_weight=args.semantic_weight, acoustic_weight=args.acoustic_weight,
                              weight_decay=args.weight_decay, lora_r=args.lora_r, lora_alpha=args.lora_alpha,
                              lora_dropout=args.lora_dropout, target_modules=args.target_modules,
-                             target_layers=args.target_layers, lora_use_bias=args.lora_bias, device=f"cuda:{local}", model=model)
+                             target_layers=args.target_layers, lora_use_bias=args.lora_bias, device=f"cuda:{local}", model=model,
+                             objective=objective_of(args)[0])
     trainer.logger.setLevel(logging.DEBUG if args.debug else getattr(logging, args.log_level.upper(), logging.INFO))
     trainer.model.acoustic_mode = args.acoustic_mode
     train_ds, val_ds = load_datasets(args)

@@ -6,7 +6,8 @@ with its own speaker's set (``MultiSpeakerLoRATrainer``) - so the per-speaker ov
 rate and the epochs that the reference's config allows are refused: one stack has one layout and one optimiser.
 
 ``--speakers-config``: a JSON list of {"name", "speaker_id", and one data source: "audio_dir" + "transcript_dir"
-(+ "alignment_dir"), "token_file", or "synthetic": N}.
+(+ "alignment_dir"), "token_file", or "synthetic": N}; optionally "objective" ("reference" | "next-frame") and "loss_on"
+("target" | "all") in place of the run's ``--objective`` / ``--loss-on``.
 """
 import argparse
 import json
@@ -14,7 +15,7 @@ import logging
 import os
 import time
 
-from .common import load_datasets
+from .common import add_objective_args, load_datasets, objective_of
 
 PER_SPEAKER_REFUSED = ("lora_r", "lora_alpha", "lora_dropout", "learning_rate", "epochs", "target_modules", "batch_size", "save_mode")
 
@@ -50,6 +51,7 @@ def parse_args(argv=None):
     d.add_argument("--mimi-weights", type=str, default=None, help="local Mimi weights (for audio_dir speakers and samples)")
     d.add_argument("--text-tokenizer", type=str, default=None, help="local directory of the Llama-3.2 tokenizer files")
     d.add_argument("--pack-sequences", action="store_true", help="pack several examples (of any speakers) into each row")
+    add_objective_args(d)                             # a speaker entry may override either one ("objective", "loss_on")
     p.add_argument("--save-mode", choices=["lora", "full", "both"], default="lora",
                    help="only 'lora' (one adapter file per speaker): a merged model is one speaker's - merge a speaker's file with "
                         "csm-finetune-lora --resume-from FILE --epochs 0 --save-mode full")
@@ -94,9 +96,22 @@ def speaker_datasets_of(configs, args):
                                 val_split=c.get("val_split", args.val_split), audio_dir=c.get("audio_dir"),
                                 transcript_dir=c.get("transcript_dir"), alignment_dir=c.get("alignment_dir"),
                                 speaker_id=c["speaker_id"], mimi_weights=args.mimi_weights, text_tokenizer=args.text_tokenizer,
-                                context_turns=c.get("context_turns", args.context_turns))
+                                context_turns=c.get("context_turns", args.context_turns), **speaker_objective(c, args))
         out[c["speaker_id"]] = load_datasets(ns)
     return out
+
+
+def speaker_objective(c, args):
+    """{"objective", "loss_on"} of a speaker entry: its own, else the run's flags."""
+    return dict(objective=c.get("objective", getattr(args, "objective", "reference")),
+                loss_on=c.get("loss_on", getattr(args, "loss_on", "target")))
+
+
+def run_objective(configs, args):
+    """What the trainer is told: ``next_frame`` as soon as one speaker's examples are in that form (the ignore index they need
+    leaves the other speakers' losses as they are, up to the padding it takes out)."""
+    objs = {objective_of(argparse.Namespace(**speaker_objective(c, args)))[0] for c in configs}
+    return "next_frame" if "next_frame" in objs else "reference"
 
 
 def main(argv=None):
@@ -118,7 +133,8 @@ def main(argv=None):
                                       weight_decay=args.weight_decay, lora_r=args.lora_r, lora_alpha=args.lora_alpha,
                                       lora_dropout=args.lora_dropout, target_modules=args.target_modules,
                                       target_backbone_layers=args.target_layers, lora_use_bias=args.lora_bias, device="cuda:0",
-                                      model=model, pack_sequences=args.pack_sequences, max_seq_len=args.max_seq_len)
+                                      model=model, pack_sequences=args.pack_sequences, max_seq_len=args.max_seq_len,
+                                      objective=run_objective(configs, args))
     trainer.logger.setLevel(logging.DEBUG if args.debug else getattr(logging, args.log_level.upper(), logging.INFO))
     trainer.model.acoustic_mode = args.acoustic_mode
     datasets = speaker_datasets_of(configs, args)

@@ -5,7 +5,7 @@ import logging
 
 from ..training.dp import init_distributed
 from ..training.trainer import CSMTrainer
-from .common import add_data_args, load_datasets
+from .common import add_data_args, load_datasets, objective_of
 
 
 def parse_args(argv=None):
@@ -59,6 +59,7 @@ def main(argv=None):
     trainer.num_workers = args.num_workers
     trainer.ignore_padding = args.ignore_padding or args.pack_sequences
     trainer.pack_sequences, trainer.max_seq_len = args.pack_sequences, args.max_seq_len
+    trainer.objective = objective_of(args)[0]           # next_frame implies what ignore_padding sets (CSMTrainer.train)
     train_ds, val_ds = load_datasets(args)
     trainer.prepare_optimizer(freeze_backbone=args.freeze_backbone, freeze_decoder=args.freeze_decoder,
                               freeze_embeddings=args.freeze_embeddings)

@@ -2,15 +2,20 @@
 import torch
 from torch.utils.data import Dataset
 
-from .training_data import collate_variable_length
+from .training_data import check_objective, collate_variable_length, next_frame_labels
 
 
 class SyntheticCSMDataset(Dataset):
-    """Seeded interleaved text+audio token sequences of a fixed length - what bench.py trains on."""
+    """Seeded interleaved text+audio token sequences of a fixed length - what bench.py trains on.
+
+    ``objective="reference"``: the targets are drawn at random, one frame per input position (a benchmark's labels, not a
+    task).  ``objective="next_frame"``: the same tokens, labelled with ``next_frame_labels(tokens, mask)`` - every audio
+    frame of the sequence is the label of the position before it."""
 
     def __init__(self, n_items: int, seq_len: int, text_vocab: int = 128256, audio_vocab: int = 2051, n_codebooks: int = 32,
-                 seed: int = 1234, n_segments: int = 2):
+                 seed: int = 1234, n_segments: int = 2, objective: str = "reference"):
         self.n, self.S, self.tv, self.av, self.K, self.seed, self.nseg = n_items, seq_len, text_vocab, audio_vocab, n_codebooks, seed, n_segments
+        self.objective = check_objective(objective)
         self.collate = collate_variable_length        # what get_batch collates with (the CLIs swap in collate_packed)
 
     def __len__(self):
@@ -36,7 +41,10 @@ class SyntheticCSMDataset(Dataset):
                 tokens[p:end, :K] = codes
                 mask[p:end, :K] = True
             p = end
-        targets = torch.randint(0, self.av - 3, (S, K), generator=g)
+        if self.objective == "next_frame":
+            targets = next_frame_labels(tokens, mask)
+        else:
+            targets = torch.randint(0, self.av - 3, (S, K), generator=g)
         return {"input_tokens": tokens, "input_masks": mask, "target_audio_tokens": targets}
 
     # protocol consumed by CSMLoRATrainer.train (reference training/data.py:364-388)

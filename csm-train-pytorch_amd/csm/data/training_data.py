@@ -20,6 +20,83 @@ import torch
 from torch.utils.data import DataLoader, Dataset, Sampler
 
 IGNORE_INDEX = -100
+OBJECTIVES = ("reference", "next_frame")
+LOSS_ON = ("target", "all")
+
+
+def check_objective(objective: str, loss_on: str = "target") -> str:
+    """``objective`` spelled as the data layer spells it (the command lines write ``next-frame``); anything else raises."""
+    objective = str(objective).replace("-", "_")
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be one of {OBJECTIVES}, got {objective!r}")
+    if loss_on not in LOSS_ON:
+        raise ValueError(f"loss_on must be one of {LOSS_ON}, got {loss_on!r}")
+    return objective
+
+
+# ------------------------------------------------------------------------------------------------ next-frame objective
+def next_frame_labels(tokens: torch.Tensor, mask: torch.Tensor, loss_from: int = 0) -> torch.Tensor:
+    """Labels ``[S, K]`` int64 of the objective that ``generate()`` samples from, for one interleaved sequence ``tokens`` /
+    ``mask`` ``[S, K+1]``: ``targets[p] = tokens[p+1, :K]`` where position p+1 is an audio frame (``mask[p+1, :K]`` all true)
+    and ``p + 1 >= loss_from``; every other row, the last one included, is ``IGNORE_INDEX``.
+
+    Position p's codebook-0 logits and the depth decoder fed ``hidden[p]`` then predict the frame that generation would
+    feed back at position p+1 (``Model.generate_frame``).  It follows that
+    * the last text position of a segment is labelled with that segment's first frame;
+    * the position holding the last real frame is labelled with the EOS frame, all K codes 0 - which is what ends an
+      utterance in ``generate()``;
+    * the EOS position itself is unlabelled when the next position is text or the end of the sequence.
+    ``loss_from`` leaves the frames before it (a conversation's context turns) out of the loss."""
+    S, K = tokens.shape[0], tokens.shape[1] - 1
+    targets = torch.full((S, K), IGNORE_INDEX, dtype=torch.long)
+    if S > 1:
+        nxt = mask[1:, :K].bool().all(dim=1) & (torch.arange(1, S) >= int(loss_from))
+        targets[:-1][nxt] = tokens[1:, :K][nxt].to(torch.long)
+    return targets
+
+
+def is_next_frame(item: Dict[str, torch.Tensor]) -> bool:
+    """An item already in the next-frame form: one label row per input position, at least one of them ``IGNORE_INDEX``
+    (the last row always is)."""
+    tg = item["target_audio_tokens"]
+    return tg.shape[0] == item["input_tokens"].shape[0] and bool((tg == IGNORE_INDEX).any())
+
+
+def to_next_frame(item: Dict[str, torch.Tensor], loss_on: str = "target") -> Dict[str, torch.Tensor]:
+    """An item of the reference form (``input_tokens`` = context segments + the target's text frames, ``target_audio_tokens``
+    = the target's codes ``[T, K]``) in the next-frame form: the target's T frames and one all-zero EOS frame are appended
+    to the input under the audio mask, exactly as ``CSMDataset._tokenize_audio`` does for a context turn, and
+    ``target_audio_tokens`` becomes ``next_frame_labels`` of the result, ``[S + T + 1, K]``.
+
+    ``loss_on="target"`` labels the target utterance only (``loss_from`` = its first audio position: the last text position
+    predicts frame 0, the last frame predicts EOS); ``loss_on="all"`` labels every segment's audio.  Keys and dtypes stay
+    those of the reference form, so the collate functions, token files and ``TokenFileDataset`` take the result as it is -
+    with ``target_pad=IGNORE_INDEX`` and ``model.target_ignore_index`` set."""
+    check_objective("next_frame", loss_on)
+    tokens, mask, codes = item["input_tokens"], item["input_masks"], item["target_audio_tokens"]
+    S, (T, K) = tokens.shape[0], codes.shape
+    if tokens.shape[1] != K + 1:
+        raise ValueError(f"input_tokens has {tokens.shape[1]} columns and target_audio_tokens {K}: expected K + 1 and K")
+    if bool((codes < 0).any()):
+        raise ValueError("target_audio_tokens holds negative codes: the item is not in the reference form")
+    frames = torch.zeros(T + 1, K + 1, dtype=tokens.dtype)
+    frames[:T, :K] = codes.to(tokens.dtype)                                              # + EOS frame
+    fmask = torch.zeros(T + 1, K + 1, dtype=mask.dtype)
+    fmask[:, :-1] = True
+    tokens, mask = torch.cat([tokens, frames], 0), torch.cat([mask, fmask], 0)
+    out = dict(item)
+    out.update(input_tokens=tokens, input_masks=mask,
+               target_audio_tokens=next_frame_labels(tokens, mask, S if loss_on == "target" else 0))
+    return out
+
+
+def pad_with_ignore_index(dataset):
+    """A dataset of the ``get_batch`` protocol collates itself (``dataset.collate``): have the padded collation pad the labels
+    with ``IGNORE_INDEX``, which a next-frame batch needs.  Another collate function (``collate_packed``) is left alone."""
+    if dataset is not None and getattr(dataset, "collate", None) is collate_variable_length:
+        from functools import partial
+        dataset.collate = partial(collate_variable_length, target_pad=IGNORE_INDEX)
+    return dataset
 
 
 # ------------------------------------------------------------------------------------------------ audio I/O
@@ -157,10 +234,23 @@ class CSMDataset(Dataset):
     """Tokenised contextual examples (reference training_data.py:227-358): input = context segments (text + audio
     frames) followed by the target's text frames; ``target_audio_tokens`` = the target's Mimi codes ``[T, K]``.
 
-    ``truncate="reference"`` reproduces the reference's over-length rule literally (only the target's text frames
-    survive, lines 289-295); ``truncate="keep_context"`` keeps the last ``max_seq_len`` frames instead."""
+    ``truncate="reference"`` (the default) reproduces the reference's over-length rule literally (only the target's text
+    frames survive, lines 289-295); ``truncate="keep_context"`` keeps the last ``max_seq_len`` frames instead.
 
-    def __init__(self, examples: List[Dict], text_tokenizer, audio_tokenizer, max_seq_len: int = 2048, truncate: str = "reference"):
+    ``objective="reference"`` is that form: ``forward_loss`` pairs input position p with target frame p - the reference's
+    pairing, kept for parity and the benchmark.  ``objective="next_frame"`` returns ``to_next_frame(item, loss_on)``: the
+    target's frames and EOS are part of the input and every label is the next position's frame, the likelihood
+    ``generate()`` samples from.  Its over-length rule: the target's text, frames and EOS survive whole and whole oldest
+    context turns are dropped until the item fits ``max_seq_len``; a target that does not fit alone raises ``ValueError``
+    (``truncate=`` has no meaning there and is refused)."""
+
+    def __init__(self, examples: List[Dict], text_tokenizer, audio_tokenizer, max_seq_len: int = 2048,
+                 truncate: Optional[str] = None, objective: str = "reference", loss_on: str = "target"):
+        objective = check_objective(objective, loss_on)
+        if objective == "next_frame" and truncate is not None:
+            raise ValueError("truncate= cuts frames off an item; objective='next_frame' drops whole oldest context turns "
+                             "instead: give one or the other")
+        truncate = "reference" if truncate is None else truncate
         if truncate not in ("reference", "keep_context"):
             raise ValueError("truncate must be 'reference' or 'keep_context'")
         for name, tok in (("text_tokenizer", text_tokenizer), ("audio_tokenizer", audio_tokenizer)):
@@ -168,6 +258,7 @@ class CSMDataset(Dataset):
                 raise TypeError(f"{name} needs an encode() method")
         self.examples, self.text_tokenizer, self.audio_tokenizer = examples, text_tokenizer, audio_tokenizer
         self.max_seq_len, self.truncate = max_seq_len, truncate
+        self.objective, self.loss_on = objective, loss_on
 
     def __len__(self):
         return len(self.examples)
@@ -217,18 +308,31 @@ class CSMDataset(Dataset):
         tt, tm = self._tokenize_text_segment(target.text, target.speaker_id)
         toks.append(tt)
         masks.append(tm)
+        codes = self._tokenize_audio_for_target(target.audio)
+        if self.objective == "next_frame":
+            need = tt.size(0) + codes.size(0) + 1
+            if need > self.max_seq_len:
+                raise ValueError(f"example {idx}: its target alone takes {need} positions ({tt.size(0)} text, {codes.size(0)} "
+                                 f"frames, 1 EOS), more than max_seq_len = {self.max_seq_len}")
+            while sum(t.size(0) for t in toks) + codes.size(0) + 1 > self.max_seq_len:
+                toks.pop(0)                                                              # the oldest context turn, whole
+                masks.pop(0)
+            return to_next_frame({"input_tokens": torch.cat(toks, 0), "input_masks": torch.cat(masks, 0),
+                                  "target_audio_tokens": codes}, self.loss_on)
         tokens, mask = torch.cat(toks, 0), torch.cat(masks, 0)
         if tokens.size(0) > self.max_seq_len:
             keep = min(self.max_seq_len, tt.size(0)) if self.truncate == "reference" else self.max_seq_len
             tokens, mask = tokens[tokens.size(0) - keep:], mask[mask.size(0) - keep:]
-        return {"input_tokens": tokens, "input_masks": mask, "target_audio_tokens": self._tokenize_audio_for_target(target.audio)}
+        return {"input_tokens": tokens, "input_masks": mask, "target_audio_tokens": codes}
 
     def lengths(self) -> List[int]:
         """Input length of every item without running the audio tokenizer twice: frames = text ids + ceil(N/1920)+1
-        per context turn (an estimate used only for bucketing)."""
+        per context turn, and for the target too under ``next_frame`` (an estimate used only for bucketing)."""
         out = []
         for ex in self.examples:
             n = len(self.text_tokenizer.encode(f"[{ex['target'].speaker_id}]{ex['target'].text}"))
+            if self.objective == "next_frame":
+                n += math.ceil(ex["target"].audio.numel() / 1920) + 1
             for c in ex.get("context", []):
                 n += len(self.text_tokenizer.encode(f"[{c.speaker_id}]{c.text}")) + math.ceil(c.audio.numel() / 1920) + 1
             out.append(min(n, self.max_seq_len))

@@ -492,8 +492,9 @@ class Engine:
     # -------------------------------------------------------------------------------------------- loss forward
     def forward_loss(self, tokens: torch.Tensor, masks: torch.Tensor, targets: torch.Tensor, semantic_weight: float,
                      acoustic_weight: float, save: bool, acoustic_rows: Optional[torch.Tensor] = None, segment_lengths=None,
-                     adapter_ids=None):
+                     adapter_ids=None, rows_out: Optional[dict] = None):
         """Forward of ``compute_loss``.  Returns (total, semantic, acoustic) as 0-d fp32 GPU tensors.
+        ``rows_out``: a dict that receives the per-row losses the two means are taken over (``compute_loss(return_rows=True)``).
         ``segment_lengths`` [B, n_max] (host integers, zero-padded; ``collate_packed``) marks a packed batch: every row holds several
         examples one after the other, each attends only to itself and has RoPE positions of its own (``Segments``).  The labels
         stay position-indexed, so a packed batch needs ``model.target_ignore_index``: each segment's last position and the row
@@ -553,6 +554,15 @@ class Engine:
             dec = self._decoder_forward(hidden, rows, tg, B, S, save, sel=sel)
             ops.reduce_sum(dec["rows_loss"], ac, 1.0 / dec["n_rows"])
         total = semantic_weight * sem + acoustic_weight * ac
+        if rows_out is not None:
+            # copies: the backward runs the CE kernels again over the saved row buffers
+            rows_out["semantic_rows"] = rows_loss.view(B, S).clone()                        # 0 where unlabelled
+            if dec is not None:
+                rows_out["acoustic_rows"] = dec["rows_loss"].view(K - 1, -1).t().contiguous()   # [N, K-1], codebooks 1..K-1
+                rows_out["acoustic_row_index"] = rows.to(torch.int64)                       # b * S + p of every row
+            else:
+                rows_out["acoustic_rows"] = torch.zeros(0, K - 1, dtype=F32, device=dev)
+                rows_out["acoustic_row_index"] = torch.zeros(0, dtype=torch.int64, device=dev)
         if save:
             self.saved = dict(B=B, S=S, tk=tk, mk=mk, hidden=hidden, logits=logits, t0=t0, n_sem=n_sem, dec=dec, seg=seg, sel=sel,
                               sw=float(semantic_weight), aw=float(acoustic_weight))
@@ -589,7 +599,12 @@ class Engine:
         V, TV, K = a.audio_vocab_size, a.text_vocab_size, a.audio_num_codebooks
 
         def check(tk, mk, tg):
-            if int(tg.max()) >= V or (ign is None and int(tg.min()) < 0):
+            if ign is None and int(tg.min()) < 0:
+                raise ValueError("target_audio_tokens out of range for audio_vocab_size: negative labels and no ignore index.  A "
+                                 "next-frame batch (data.to_next_frame), IGNORE_INDEX padding and packed rows mark unlabelled "
+                                 "positions with -100: set model.target_ignore_index = csm.data.IGNORE_INDEX (the trainers' "
+                                 "objective='next_frame' / --objective next-frame, --ignore-padding and --pack-sequences do)")
+            if int(tg.max()) >= V:
                 raise ValueError("target_audio_tokens out of range for audio_vocab_size")
             if ign is not None and bool(((tg < 0) & (tg != ign)).any()):
                 raise ValueError(f"negative target_audio_tokens other than the ignore index {ign}")

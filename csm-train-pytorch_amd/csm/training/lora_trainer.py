@@ -38,7 +38,10 @@ class CSMLoRATrainer:
                  semantic_weight: float = 100.0, acoustic_weight: float = 1.0, weight_decay: float = 0.01,
                  lora_r: int = 8, lora_alpha: float = 16.0, lora_dropout: float = 0.0,
                  target_modules: Optional[List[str]] = None, target_layers: Optional[List[int]] = None,
-                 lora_use_bias: bool = False, device: str = "cuda", model: Optional[Model] = None):
+                 lora_use_bias: bool = False, device: str = "cuda", model: Optional[Model] = None,
+                 objective: str = "reference"):
+        from ..data.training_data import check_objective
+        self.objective = check_objective(objective)      # (not in the reference) "next_frame": data.to_next_frame items
         self.model_path = model_path
         self.output_dir = Path(output_dir)
         self.output_dir.mkdir(parents=True, exist_ok=True)
@@ -60,6 +63,9 @@ class CSMLoRATrainer:
         self.grad_sync = None
         self.max_grad_norm = 0.0
         self._load_model_with_lora()
+        if self.objective == "next_frame":               # one label row per position, unlabelled ones carry the ignore index
+            from ..data.training_data import IGNORE_INDEX
+            self.model.target_ignore_index = IGNORE_INDEX
         self.epoch = 0
         self.global_step = 0
         self.best_loss = float("inf")
@@ -129,6 +135,11 @@ class CSMLoRATrainer:
         self.max_grad_norm = max_grad_norm
         if resume_from:
             self.load_lora_weights(resume_from)
+        self.logger.info(f"Objective: {self.objective}")
+        if self.objective == "next_frame":               # the padded collation of get_batch pads the labels with the ignore index
+            from ..data.training_data import pad_with_ignore_index
+            pad_with_ignore_index(train_dataset)
+            pad_with_ignore_index(val_dataset)
         self.logger.info("Starting LoRA training")
         # data parallel (new capability): rank r takes batches r, r + world, r + 2 world, ... of the get_batch protocol, so
         # the ranks see disjoint data and one optimiser step covers world * batch_size sequences; replicas are identical,

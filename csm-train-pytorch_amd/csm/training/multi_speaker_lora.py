@@ -10,6 +10,9 @@ What is kept: the constructor arguments, ``prepare_optimizers``, ``train(speaker
 validation loss}``, ``save_all_models`` (``speaker_{id}/speaker_{id}_lora.safetensors`` + ``_metadata.json``, the single-adapter
 format: ``LoRABank.load`` / ``CSMLoRATrainer.load_lora_weights`` read them), ``load_speaker_model``, ``generate_sample``.
 
+``objective="next_frame"`` (not in the reference): the speakers' examples are ``csm.data.to_next_frame`` items - the ignore
+index is set and every padded batch, the validation sets' included, pads its labels with it.
+
 What differs, on purpose:
 * the loss of a step is the batch loss - the mean over the labelled rows of the whole batch, whichever speakers they belong to;
 * gradient clipping takes ONE norm over the whole stack;
@@ -60,7 +63,9 @@ class MultiSpeakerLoRATrainer:
                  share_backbone: bool = False, share_decoder: bool = False, target_modules: Optional[List[str]] = None,
                  target_backbone_layers: Optional[List[int]] = None, target_decoder_layers: Optional[List[int]] = None,
                  lora_use_bias: bool = False, device: str = "cuda", model: Optional[Model] = None,
-                 pack_sequences: bool = False, max_seq_len: int = 2048, seed: int = 0):
+                 pack_sequences: bool = False, max_seq_len: int = 2048, seed: int = 0, objective: str = "reference"):
+        from ..data.training_data import check_objective
+        self.objective = check_objective(objective)      # (not in the reference) "next_frame": data.to_next_frame items
         if share_backbone or share_decoder:
             raise NotImplementedError("share_backbone / share_decoder: the reference's shared adapters are created and saved but "
                                       "never trained; train every speaker's own adapters (the default here) instead")
@@ -102,7 +107,7 @@ class MultiSpeakerLoRATrainer:
         apply_lora_to_model(self.model, r=lora_r, alpha=lora_alpha, dropout=lora_dropout, target_modules=self.target_modules,
                             target_layers=target_backbone_layers, use_bias=lora_use_bias, seed=seed,
                             n_adapters=len(self.speaker_ids))
-        if pack_sequences:
+        if pack_sequences or self.objective == "next_frame":   # unlabelled positions by construction: the ignore index
             from ..data.training_data import IGNORE_INDEX
             self.model.target_ignore_index = IGNORE_INDEX
         self.logger.info(f"{len(self.speaker_ids)} speakers {self.speaker_ids}: one stack of adapter sets, r={lora_r}, "
@@ -186,6 +191,11 @@ class MultiSpeakerLoRATrainer:
             raise ValueError(f"datasets for speakers {unknown} that are not among speaker_ids {self.speaker_ids}")
         self.prepare_optimizers()
         self.max_grad_norm = max_grad_norm
+        self.logger.info(f"Objective: {self.objective}")
+        if self.objective == "next_frame":               # the validation sets collate themselves (get_batch): pad with the ignore index
+            from ..data.training_data import pad_with_ignore_index
+            for _, val in speaker_datasets.values():
+                pad_with_ignore_index(val)
         for sid, path in (resume_from or {}).items():
             self.load_speaker_model(sid, path)
 

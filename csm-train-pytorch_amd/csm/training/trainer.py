@@ -137,7 +137,12 @@ class CSMTrainer:
         # pack_sequences (not in the reference): several examples per row of max_seq_len positions (data.collate_packed); a
         # packed batch has unlabelled positions by construction, so it sets the ignore index as ignore_padding does
         pack = bool(getattr(self, "pack_sequences", False))
-        if getattr(self, "ignore_padding", False) or pack:
+        # objective (not in the reference): "reference" pairs input position p with target frame p; "next_frame" items
+        # (data.to_next_frame) carry one label row per position, unlabelled ones included, so they need the ignore index too
+        from ..data.training_data import check_objective
+        objective = check_objective(getattr(self, "objective", "reference"))
+        self.logger.info(f"Objective: {objective}")
+        if getattr(self, "ignore_padding", False) or pack or objective == "next_frame":
             from ..data.training_data import IGNORE_INDEX
             pad = self.model.target_ignore_index = IGNORE_INDEX
         packing = dict(pack_sequences=True, max_seq_len=min(getattr(self, "max_seq_len", 2048), self.model.bb.max_seq_len)) if pack else {}

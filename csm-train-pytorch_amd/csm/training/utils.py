@@ -47,7 +47,8 @@ class _EngineLoss(torch.autograd.Function):
 
 def compute_loss(model, input_tokens: torch.Tensor, input_masks: torch.Tensor, target_audio_tokens: torch.Tensor,
                  semantic_weight: float = 100.0, acoustic_weight: float = 1.0,
-                 acoustic_rows: Optional[torch.Tensor] = None, segment_lengths=None, adapter_ids=None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+                 acoustic_rows: Optional[torch.Tensor] = None, segment_lengths=None, adapter_ids=None,
+                 return_rows: bool = False) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
     """Loss of reference ``compute_loss`` (utils.py:56-119) on the HIP path.
 
     semantic = mean CE of codebook-0 logits at positions [0, S-1) vs ``target_audio_tokens[:, :S-1, 0]`` (no ignore
@@ -57,13 +58,21 @@ def compute_loss(model, input_tokens: torch.Tensor, input_masks: torch.Tensor, t
     ``segment_lengths`` [B, n_max] marks a packed batch (``data.collate_packed``; ``Engine.forward_loss``).
     ``adapter_ids`` (host integers [B], or [B, n_max] beside ``segment_lengths``; -1 = base model only): the adapter set every
     example runs with when ``model.lora`` is a stack of sets (``LoRAState(n_adapters > 1)``).
+    With a next-frame batch (``data.to_next_frame``; ``model.target_ignore_index`` set) the same two terms are the likelihood
+    ``generate()`` samples from: position p's codebook-0 logits and the depth decoder fed ``hidden[p]`` against the frame at p+1.
+    ``return_rows``: the losses also carry what the two means are taken over - ``"semantic_rows"`` [B, S] fp32, the CE of every
+    position (0 where unlabelled), and ``"acoustic_rows"`` [N, K-1] fp32, the CE of codebooks 1..K-1 of the N frames the depth
+    decoder ran on, whose flat positions b * S + p are ``"acoustic_row_index"`` [N] - the loss per position and per codebook.
     Returns (total, {"semantic_loss", "acoustic_loss"}).  ``total.backward()`` accumulates into ``param.grad``.
     """
     need_grad = torch.is_grad_enabled()
+    rows_out = {} if return_rows else None
     total, sem, ac = model.engine.forward_loss(input_tokens, input_masks, target_audio_tokens, semantic_weight,
                                                acoustic_weight, save=need_grad, acoustic_rows=acoustic_rows,
-                                               segment_lengths=segment_lengths, adapter_ids=adapter_ids)
+                                               segment_lengths=segment_lengths, adapter_ids=adapter_ids, rows_out=rows_out)
     losses = {"semantic_loss": sem, "acoustic_loss": ac}
+    if return_rows:
+        losses.update(rows_out)
     if need_grad:
         if not hasattr(model, "_anchor"):
             model._anchor = torch.zeros((), device=model.device, requires_grad=True)
