@@ -10,6 +10,7 @@ import torch
 
 from ..data import load_audio, resample
 from ..generator import Segment, load_csm_1b
+from ..sampling import FULL_LEVEL, LEVELS, NAMES, PARAMS, own_params
 
 # reference cli/generate.py:16-25
 VOICE_PRESETS = {"neutral": 0, "warm": 1, "deep": 2, "bright": 3, "soft": 4, "energetic": 5, "calm": 6, "clear": 7,
@@ -285,63 +286,90 @@ def read_serve_file(path, codebooks=None):
     return lines
 
 
+def _line(level, line):
+    """The keywords of one --serve-file line for ``submit`` / ``say`` that belong to ``level`` (``sampling.LEVELS``: the
+    parameters it is the first to read): only what the line carries."""
+    return {NAMES[j]: line[NAMES[j]] for j in own_params(level) if NAMES[j] in line}
+
+
+def _serve(level, lines, asked=False, defaults=None):
+    """``Generator.serve`` keywords for these lines and the command line: the flag of ``level`` (with ``row_sampling=True``, which
+    it needs, and what ``defaults()`` gives - the command line's values - as the server's) as soon as a line names one of the
+    level's keys - or, whole rows, a list per codebook under a lower key - or the command line does (``asked``); else nothing."""
+    lower = NAMES[:own_params(level).start] if level == FULL_LEVEL else ()
+    if not asked and not any(_line(level, ln) or any(isinstance(ln.get(k), list) for k in lower) for ln in lines):
+        return {}
+    return {"row_sampling": True, LEVELS[level].flag: True, **(defaults() if defaults else {})}
+
+
+def _serve_args(level, lines, args, codebooks):
+    """``_serve`` with the command line ``args`` (None: the lines alone): it asks for ``level`` with one of the level's own flags
+    off its identity or - whole rows - what ``uses_processors`` looks for, and ``sampling_kw`` gives the server's defaults.  (The
+    level of the pair takes nothing from the command line: --temperature / --topk are the server's at any level.)"""
+    if args is None or level == 1:
+        return _serve(level, lines)
+    asked = (any(getattr(args, NAMES[j], PARAMS[j].identity) != PARAMS[j].identity for j in own_params(level))
+             or level == FULL_LEVEL and uses_processors(args))
+    return _serve(level, lines, asked, lambda: sampling_kw(args, codebooks))
+
+
 def line_sampling(line):
     """The sampling keywords of one --serve-file line for ``submit`` / ``say``: only what the line carries."""
-    return {k: line[k] for k in ("temperature", "topk") if k in line}
+    return _line(1, line)
 
 
 def serve_sampling(lines):
     """``Generator.serve`` keywords for these lines: ``row_sampling=True`` as soon as one of them carries a parameter."""
-    return {"row_sampling": True} if any(line_sampling(ln) for ln in lines) else {}
+    return _serve(1, lines)
 
 
 def line_filters(line):
     """The filter keywords of one --serve-file line for ``submit`` / ``say``: only what the line carries."""
-    return {k: line[k] for k in ("top_p", "min_p") if k in line}
+    return _line(2, line)
 
 
 def serve_filters(lines, top_p=1.0, min_p=0.0):
     """``Generator.serve`` keywords for these lines and the command line's --top-p / --min-p: ``row_filters=True`` (with
     ``row_sampling=True``, which it needs, and the two as the server's defaults) as soon as a line names a filter or the
     command line's are not 1.0 / 0.0; nothing otherwise - the server is then the one it is without filters."""
-    if any(line_filters(ln) for ln in lines) or (top_p, min_p) != (1.0, 0.0):
-        return {"row_sampling": True, "row_filters": True, "top_p": top_p, "min_p": min_p}
-    return {}
+    return _serve(2, lines, (top_p, min_p) != (1.0, 0.0), lambda: {"top_p": top_p, "min_p": min_p})
 
 
 def line_processors(line):
     """The repetition keywords of one --serve-file line for ``submit`` / ``say``: only what the line carries."""
-    return {k: line[k] for k in ("repetition_penalty", "repetition_window") if k in line}
+    return _line(3, line)
 
 
 def serve_processors(lines, args=None, codebooks=None):
     """``Generator.serve`` keywords for these lines and the command line: ``row_processors=True`` (with ``row_sampling=True``, which it
     needs, and the command line's values - --acoustic-* expanded - as the server's defaults) as soon as a line names a repetition
     penalty, a window or a list per codebook, or the command line uses --repetition-* / --acoustic-*; nothing otherwise."""
-    named = any(line_processors(ln) or any(isinstance(ln.get(k), list) for k in ("temperature", "topk", "top_p", "min_p"))
-                for ln in lines)
-    if not named and (args is None or not uses_processors(args)):
-        return {}
-    kw = {"row_sampling": True, "row_processors": True}
-    if args is not None:
-        kw.update(sampling_kw(args, codebooks))
-    return kw
+    return _serve_args(3, lines, args, codebooks)
 
 
 def line_typical(line):
     """The typical-sampling keyword of one --serve-file line for ``submit`` / ``say``: only if the line carries it."""
-    return {k: line[k] for k in ("typical_p",) if k in line}
+    return _line(4, line)
 
 
 def serve_typical(lines, args=None, codebooks=None):
     """``Generator.serve`` keywords for these lines and the command line: ``row_typical=True`` (with ``row_sampling=True``, which it
     needs, and the command line's values as the server's defaults) as soon as a line names "typical_p" or --typical-p is not
     1.0; nothing otherwise."""
-    if not any(line_typical(ln) for ln in lines) and (args is None or getattr(args, "typical_p", 1.0) == 1.0):
-        return {}
-    kw = {"row_sampling": True, "row_typical": True}
-    if args is not None:
-        kw.update(sampling_kw(args, codebooks))
+    return _serve_args(4, lines, args, codebooks)
+
+
+def line_kw(line):
+    """Every sampling keyword of one --serve-file line for ``submit`` / ``say``, whatever its level."""
+    return {k: v for n in range(1, len(LEVELS)) for k, v in _line(n, line).items()}
+
+
+def serve_lines(lines, args, codebooks):
+    """The sampling keywords of ``Generator.serve`` for these lines and the command line: --temperature / --topk, and what
+    every level adds (``_serve_args``), lowest level first."""
+    kw = {"temperature": args.temperature, "topk": args.topk}
+    for n in range(1, len(LEVELS)):
+        kw.update(_serve_args(n, lines, args, codebooks))
     return kw
 
 
@@ -381,26 +409,21 @@ def serve_to_wavs(generator, args, context, adapter=None):
     t0 = time.perf_counter()
     voices = serve_voices(generator, lines, context, adapter) if args.cache_context else None     # (the adapters are loaded)
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, hear_slots=args.hear_slots,
-                             **{"temperature": args.temperature, "topk": args.topk, **serve_sampling(lines),
-                                **serve_filters(lines, args.top_p, args.min_p), **serve_processors(lines, args, K),
-                                **serve_typical(lines, args, K),
-                                **out_rate_kw(args)})
+                             **serve_lines(lines, args, K), **out_rate_kw(args))
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
     def say(cid):
         conv, todo = convs[cid]
         i = todo.pop(0)
         line_of[conv.say(lines[i]["text"], lines[i]["speaker"], max_audio_length_ms=args.max_audio_length_ms,
-                         **line_sampling(lines[i]), **line_filters(lines[i]), **line_processors(lines[i]),
-                         **line_typical(lines[i]))] = (i, cid)
+                         **line_kw(lines[i]))] = (i, cid)
 
     for i, ln in enumerate(lines):
         cid = ln.get("conversation")
         if cid is None:
             line_of[server.submit(ln["text"], ln["speaker"], adapter=ln["adapter"] or adapter, seed=ln["seed"],
                                   max_audio_length_ms=args.max_audio_length_ms, **line_prompt(ln, context, voices, adapter),
-                                  **line_sampling(ln),
-                                  **line_filters(ln), **line_processors(ln), **line_typical(ln))] = (i, None)
+                                  **line_kw(ln))] = (i, None)
         elif cid in convs:
             convs[cid][1].append(i)
         else:

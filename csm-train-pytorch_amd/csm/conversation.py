@@ -379,7 +379,7 @@ class Conversation:
         turn = self._open = _Turn(self._cached, tt.shape[0])
         if filters:                                                  # (the rows path of this conversation's state)
             temperature, topk = st.sampling_args(temperature, topk, **filters)
-            if getattr(st, "row_processors", None) is not None or getattr(st, "row_typical", None) is not None:
+            if st.sampler.keeps_history:
                 # (a turn's repetition window covers its own frames)
                 st.reset_row_history(0)
                 st.set_live([0])

@@ -15,7 +15,8 @@ from typing import Iterator, List, Optional, Tuple
 import torch
 
 from .models.model import Model, ModelArgs
-from .sampling import PROCESSOR_NAMES, _as_list, _is_number, check_filters, names_processors, normalise, per_codebook
+from .sampling import (FULL_LEVEL, LEVELS, NAMES, PARAMS, _as_list, _is_number, check_filters, names_processors, normalise,
+                       per_codebook)
 
 
 @dataclass
@@ -68,25 +69,22 @@ def sampling_kwargs(gen, temperature, topk, top_p, min_p, repetition_penalty=1.0
     a number or K numbers - the one entry of a batch of one; with ``B`` a number or a sequence of B entries, each a number or K
     numbers - a flat sequence of B numbers keeps its meaning, one value per utterance.  ``typical_p`` other than the number 1.0
     (a number, K numbers, or with ``B`` an entry per utterance) sends all seven to the rows (the typical rows sampler)."""
-    six = [temperature, topk, top_p, min_p, repetition_penalty, repetition_window]
+    given = [temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p]
     if B is None:
-        six = [v if _is_number(v) else [per_codebook(name, v, gen._model.args.audio_num_codebooks)]
-               for name, v in zip(PROCESSOR_NAMES, six)]
-    if not (_is_number(typical_p) and typical_p == 1.0):
-        a, n = gen._model.args, 1 if B is None else B
-        if B is None and not _is_number(typical_p):
-            typical_p = [per_codebook("typical_p", typical_p, a.audio_num_codebooks)]
-        normalise(n, a.audio_num_codebooks, a.audio_vocab_size, *six, unit="utterance", typical_p=typical_p)
-        rows = [[v] * n if _is_number(v) else _as_list(v) for v in six + [typical_p]]
-        return rows[0], rows[1], dict(zip(PROCESSOR_NAMES[2:] + ("typical_p",), rows[2:]))
-    if not names_processors(*six[:4]) and all(_is_number(v) for v in six[4:]) and six[4] == 1.0 and six[5] == 64:
+        given = [v if _is_number(v) else [per_codebook(name, v, gen._model.args.audio_num_codebooks)]
+                 for name, v in zip(NAMES, given)]
+    named = [not (_is_number(v) and v == p.identity) for p, v in zip(PARAMS, given)]      # (off its identity)
+    below = LEVELS[FULL_LEVEL - 1].reads                 # the pair and the filters: what the levels below whole rows read
+    if not names_processors(*given[:below]) and not any(named[below:]):
         if B is not None:
             temperature, topk = gen._batch_sampling(temperature, topk, B)
         return temperature, topk, filter_kwargs(top_p, min_p, B)
+    # to the rows: all that the first level of whole rows reads, and of the levels above it up to the last parameter named
     a, n = gen._model.args, 1 if B is None else B
-    normalise(n, a.audio_num_codebooks, a.audio_vocab_size, *six, unit="utterance")
-    rows = [[v] * n if _is_number(v) else _as_list(v) for v in six]
-    return rows[0], rows[1], dict(zip(PROCESSOR_NAMES[2:], rows[2:]))
+    sent = max(j + 1 for j in range(len(PARAMS)) if j < LEVELS[FULL_LEVEL].reads or named[j])
+    normalise(n, a.audio_num_codebooks, a.audio_vocab_size, unit="utterance", **dict(zip(NAMES[:sent], given[:sent])))
+    rows = [[v] * n if _is_number(v) else _as_list(v) for v in given[:sent]]
+    return rows[0], rows[1], dict(zip(NAMES[2:sent], rows[2:]))
 
 
 class Generator:

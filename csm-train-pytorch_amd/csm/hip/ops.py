@@ -9,6 +9,7 @@ from typing import Optional
 import torch
 
 from . import CsmHipError, check, lib
+from ..sampling import FULL_LEVEL, LEVELS, PARAMS
 
 BF16 = torch.bfloat16
 
@@ -752,53 +753,45 @@ def sample_topk(logits_f32, q_f32, out_i32, topk, temperature, V=None):
     return out_i32
 
 
-def sample_topk_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, V=None):
-    """``sample_topk`` with row r's parameters read from ``topk_i32[r]`` / ``temperature_f32[r]`` on the device."""
+# per level, as plain tuples (the launch is a hot path): the entry point's name, the dtypes of what it reads, whether it keeps rings
+_ROWS = tuple((lv.fn and "csm_" + lv.fn, tuple(p.dtype for p in PARAMS[:lv.reads]), lv.rings) for lv in LEVELS)
+_RING_AT = LEVELS[FULL_LEVEL].reads                      # (the entry points take the ring after what the first level with one reads)
+
+
+def _sample_rows(level, logits_f32, q_f32, out_i32, params, ring=(), advance=False, V=None):
+    """The launch of the rows sampler of ``level`` (``sampling.LEVELS``): ``params`` - the parameters its kernel reads, in
+    ``sampling.PARAMS``' order, one entry per row each; ``ring`` - (hist, frame, live) where the level keeps the rows' rings."""
+    name, dtypes, rings = _ROWS[level]
     rows = logits_f32.shape[0]
     V = V or logits_f32.shape[1]
-    assert q_f32.is_contiguous() and q_f32.shape == (rows, V)
-    assert topk_i32.dtype == torch.int32 and topk_i32.is_contiguous() and topk_i32.numel() == rows
-    assert temperature_f32.dtype == torch.float32 and temperature_f32.is_contiguous() and temperature_f32.numel() == rows
-    check(lib.csm_sample_topk_rows(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0),
-                                   topk_i32.data_ptr(), temperature_f32.data_ptr(), _stream()), "csm_sample_topk_rows")
+    assert q_f32.is_contiguous() and q_f32.shape == (rows, V) and len(params) == len(dtypes)
+    args = []
+    for a, dtype in zip(params, dtypes):
+        assert a.dtype == dtype and a.is_contiguous() and a.numel() == rows
+        args.append(a.data_ptr())
+    args[0], args[1] = args[1], args[0]                  # (the entry points take top-k before the temperature)
+    if rings:
+        hist_i32, frame, live = ring
+        assert frame.dtype == torch.int32 and frame.is_contiguous() and frame.numel() == rows
+        assert live.dtype == torch.int32 and live.is_contiguous() and live.numel() == rows
+        assert hist_i32.dtype == torch.int32 and hist_i32.dim() == 2 and hist_i32.shape == (rows, 64) and hist_i32.stride(1) == 1
+        assert rows == 1 or hist_i32.stride(0) >= 64
+        ldh = hist_i32.stride(0) if rows > 1 else 64
+        args[_RING_AT:_RING_AT] = (hist_i32.data_ptr(), ldh, frame.data_ptr(), live.data_ptr(), 1 if advance else 0)
+    check(getattr(lib, name)(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0), *args,
+                             _stream()), name)
     return out_i32
+
+
+def sample_topk_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, V=None):
+    """``sample_topk`` with row r's parameters read from ``topk_i32[r]`` / ``temperature_f32[r]`` on the device."""
+    return _sample_rows(1, logits_f32, q_f32, out_i32, (temperature_f32, topk_i32), V=V)
 
 
 def sample_filtered_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, top_p_f32, min_p_f32, V=None):
     """``sample_topk_rows`` with row r's nucleus and min-p thresholds read from ``top_p_f32[r]`` / ``min_p_f32[r]`` on the device
     (``csm_sample_filtered_rows``; a row with 1.0 / 0.0 is ``sample_topk_rows``' row)."""
-    rows = logits_f32.shape[0]
-    V = V or logits_f32.shape[1]
-    assert q_f32.is_contiguous() and q_f32.shape == (rows, V)
-    assert topk_i32.dtype == torch.int32 and topk_i32.is_contiguous() and topk_i32.numel() == rows
-    for a in (temperature_f32, top_p_f32, min_p_f32):
-        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == rows
-    check(lib.csm_sample_filtered_rows(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0),
-                                       topk_i32.data_ptr(), temperature_f32.data_ptr(), top_p_f32.data_ptr(),
-                                       min_p_f32.data_ptr(), _stream()), "csm_sample_filtered_rows")
-    return out_i32
-
-
-def _sample_ring_rows(name, logits_f32, q_f32, out_i32, ints, floats, hist_i32, advance, V, last=()):
-    """The launch of the two samplers that keep the rows' rings: ``ints`` = (topk, window, frame, live), ``floats`` = (temperature,
-    top_p, min_p, penalty) and ``last`` (what follows ``advance`` in the entry point's arguments), one entry per row each."""
-    rows = logits_f32.shape[0]
-    V = V or logits_f32.shape[1]
-    assert q_f32.is_contiguous() and q_f32.shape == (rows, V)
-    for a in ints:
-        assert a.dtype == torch.int32 and a.is_contiguous() and a.numel() == rows
-    for a in floats + tuple(last):
-        assert a.dtype == torch.float32 and a.is_contiguous() and a.numel() == rows
-    assert hist_i32.dtype == torch.int32 and hist_i32.dim() == 2 and hist_i32.shape == (rows, 64) and hist_i32.stride(1) == 1
-    assert rows == 1 or hist_i32.stride(0) >= 64
-    ldh = hist_i32.stride(0) if rows > 1 else 64
-    topk, window, frame, live = ints
-    temperature, top_p, min_p, penalty = floats
-    check(getattr(lib, name)(logits_f32.data_ptr(), q_f32.data_ptr(), out_i32.data_ptr(), rows, V, logits_f32.stride(0),
-                             topk.data_ptr(), temperature.data_ptr(), top_p.data_ptr(), min_p.data_ptr(), penalty.data_ptr(),
-                             window.data_ptr(), hist_i32.data_ptr(), ldh, frame.data_ptr(), live.data_ptr(), 1 if advance else 0,
-                             *[a.data_ptr() for a in last], _stream()), name)
-    return out_i32
+    return _sample_rows(2, logits_f32, q_f32, out_i32, (temperature_f32, topk_i32, top_p_f32, min_p_f32), V=V)
 
 
 def sample_processed_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, top_p_f32, min_p_f32, penalty_f32, window_i32,
@@ -808,8 +801,8 @@ def sample_processed_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32,
     f; ``frame_i32[r]``: f; the ids of the last min(window_i32[r], f, 64) frames are penalised by ``penalty_f32[r]`` before the
     draw.  A row with ``live_i32[r]`` != 0 then stores its winner to slot f % 64 and, with ``advance``, f + 1 to ``frame_i32[r]``.
     A row with penalty 1 or window 0 is ``sample_filtered_rows``' row."""
-    return _sample_ring_rows("csm_sample_processed_rows", logits_f32, q_f32, out_i32, (topk_i32, window_i32, frame_i32, live_i32),
-                             (temperature_f32, top_p_f32, min_p_f32, penalty_f32), hist_i32, advance, V)
+    return _sample_rows(3, logits_f32, q_f32, out_i32, (temperature_f32, topk_i32, top_p_f32, min_p_f32, penalty_f32, window_i32),
+                        (hist_i32, frame_i32, live_i32), advance, V)
 
 
 def sample_typical_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, top_p_f32, min_p_f32, penalty_f32, window_i32,
@@ -818,8 +811,8 @@ def sample_typical_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, t
     tokens whose surprise -ln P is closest to the entropy of what is left are kept, most typical first, until ``typical_p_f32[r]``
     of the mass is reached (the token that crosses it is kept).  A row with 1.0 is ``sample_processed_rows``' row: out, ring and
     counter."""
-    return _sample_ring_rows("csm_sample_typical_rows", logits_f32, q_f32, out_i32, (topk_i32, window_i32, frame_i32, live_i32),
-                             (temperature_f32, top_p_f32, min_p_f32, penalty_f32), hist_i32, advance, V, last=(typical_p_f32,))
+    return _sample_rows(4, logits_f32, q_f32, out_i32, (temperature_f32, topk_i32, top_p_f32, min_p_f32, penalty_f32, window_i32,
+                                                        typical_p_f32), (hist_i32, frame_i32, live_i32), advance, V)
 
 
 def rvq_encode(x_f32, codebooks_f32, codes_i64, n_semantic=1):

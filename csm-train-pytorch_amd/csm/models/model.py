@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from ..hip import ops, require_device
+from ..sampling import LEVELS
 
 BF16 = torch.bfloat16
 
@@ -131,13 +132,20 @@ def sample_topk(logits: torch.Tensor, topk: int, temperature: float, q: Optional
     return out.reshape(*logits.shape[:-1], 1)
 
 
+def _sample_rows(level, logits, params, ring=(), advance=False, q=None):
+    """The rows sampler of ``level`` (``sampling.LEVELS``) on [B, V] ``logits``: ``params`` - what its kernel reads, in
+    ``sampling.PARAMS``' order, [B] each on the logits' device; ``ring`` - (hist, frame, live) where the level keeps the rows'
+    rings.  Returns int32 [B, 1]."""
+    lg2, q, out = _sample_operands(logits, q, LEVELS[level].fn)
+    ops._sample_rows(level, lg2, q, out, params, ring, advance, V=lg2.shape[1])
+    return out.reshape(-1, 1)
+
+
 def sample_topk_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, q: Optional[torch.Tensor] = None):
     """``sample_topk`` for [B, V] logits with one parameter pair per row: ``topk`` int32 [B] and ``temperature`` float32 [B] on the
     logits' device, read by the kernel (``csm_sample_topk_rows``) - row b is ``sample_topk(logits[b], topk[b], temperature[b],
     q[b])`` bit for bit.  Returns int32 [B, 1]."""
-    lg2, q, out = _sample_operands(logits, q, "sample_topk_rows")
-    ops.sample_topk_rows(lg2, q, out, topk, temperature, V=lg2.shape[1])
-    return out.reshape(-1, 1)
+    return _sample_rows(1, logits, (temperature, topk), q=q)
 
 
 def sample_filtered_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor,
@@ -146,9 +154,7 @@ def sample_filtered_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: 
     [0, 1]) per row, applied inside the kernel (``csm_sample_filtered_rows``) to the values top-k kept: first min-p (drop
     p_i < min_p * p_max), then the nucleus over what is left (a token stays while the probability of the strictly larger values
     is below top_p).  Row b with 1.0 / 0.0 is ``sample_topk_rows``' row b, bit for bit.  Returns int32 [B, 1]."""
-    lg2, q, out = _sample_operands(logits, q, "sample_filtered_rows")
-    ops.sample_filtered_rows(lg2, q, out, topk, temperature, top_p, min_p, V=lg2.shape[1])
-    return out.reshape(-1, 1)
+    return _sample_rows(2, logits, (temperature, topk, top_p, min_p), q=q)
 
 
 def sample_processed_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor,
@@ -160,10 +166,7 @@ def sample_processed_rows(logits: torch.Tensor, topk: torch.Tensor, temperature:
     the last n = min(window, f, 64) frames get x = x / r (x > 0) or x * r on the raw logit, then the draw is
     ``sample_filtered_rows``'; row b with r = 1 or n = 0 is that row bit for bit.  A row with ``live[b]`` != 0 then stores its
     winner to slot f % 64 and, with ``advance``, f + 1 to ``frame[b]``.  Returns int32 [B, 1]."""
-    lg2, q, out = _sample_operands(logits, q, "sample_processed_rows")
-    ops.sample_processed_rows(lg2, q, out, topk, temperature, top_p, min_p, penalty, window, hist, frame, live, advance=advance,
-                              V=lg2.shape[1])
-    return out.reshape(-1, 1)
+    return _sample_rows(3, logits, (temperature, topk, top_p, min_p, penalty, window), (hist, frame, live), advance, q)
 
 
 def sample_typical_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: torch.Tensor, top_p: torch.Tensor,
@@ -174,10 +177,7 @@ def sample_typical_rows(logits: torch.Tensor, topk: torch.Tensor, temperature: t
     the kernel (``csm_sample_typical_rows``): of what the nucleus left, the tokens whose surprise -ln P is closest to the entropy
     stay, most typical first, while the mass of the strictly more typical ones is below ``typical_p`` - the largest value may go.
     Row b with 1.0 is ``sample_processed_rows``' row b bit for bit, ring and counter included.  Returns int32 [B, 1]."""
-    lg2, q, out = _sample_operands(logits, q, "sample_typical_rows")
-    ops.sample_typical_rows(lg2, q, out, topk, temperature, top_p, min_p, penalty, window, hist, frame, live, typical_p,
-                            advance=advance, V=lg2.shape[1])
-    return out.reshape(-1, 1)
+    return _sample_rows(4, logits, (temperature, topk, top_p, min_p, penalty, window, typical_p), (hist, frame, live), advance, q)
 
 
 @dataclass

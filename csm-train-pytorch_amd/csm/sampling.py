@@ -5,24 +5,19 @@ A state samples at one of five levels, and the level only rises: 0 - the scalar 
 (``csm_sample_topk``); 1 - each row its own temperature / top-k (``csm_sample_topk_rows``); 2 - and its own top-p / min-p
 (``csm_sample_filtered_rows``); 3 - all six per row and per codebook, with the windowed repetition penalty and the rows' rings of
 sampled codes (``csm_sample_processed_rows``); 4 - and locally typical sampling, ``typical_p`` per row and per codebook
-(``csm_sample_typical_rows``).  Whatever the level, the parameters sit in the same six [K, B] device buffers
-(codebook-major: codebook i's draw hands row i of each to the kernel, which reads ``topk[row]`` from the pointer it is given) and
-in one host mirror; below level 3 the K entries of a column are equal.  Level 4's seventh buffer and mirror stand beside them.
+(``csm_sample_typical_rows``).  Whatever the level, every parameter sits in its own [K, B] device buffer (codebook-major:
+codebook i's draw hands row i of each to the kernel, which reads ``topk[row]`` from the pointer it is given) and in one host
+mirror; below level 3 the K entries of a column are equal, and a parameter the level's kernel does not read stays at its identity.
+
+What a parameter is and what a level is stands in two tables, ``PARAMS`` and ``LEVELS`` (below the rules); the state, the
+normaliser, the launch wrappers (csm/hip/ops.py, csm/models/model.py), the server (csm/serving.py) and the command line
+(csm/cli/generate.py) walk them.
 """
 import math
 import numbers
+from collections import namedtuple
 
 import torch
-
-HIST_FRAMES = 64        # SMP_HIST of csrc/generate.hip: the frames a row's ring of sampled codes holds, per codebook
-PROCESSOR_NAMES = ("temperature", "topk", "top_p", "min_p", "repetition_penalty", "repetition_window")
-DTYPES = (torch.float32, torch.int32, torch.float32, torch.float32, torch.float32, torch.int32)
-# what a parameter is before a write names it: no nucleus, no min-p cut, no penalty (the pair's placeholders are never read - the
-# first write brings a pair)
-IDENTITY = (1.0, 1, 1.0, 0.0, 1.0, HIST_FRAMES)
-_FIRST = (None, "temperature = topk = None samples each row with its own pair: call set_row_sampling first",
-          "no row filters: call set_row_filters first", "no row processors: call set_row_processors first",
-          "no row typical sampling: call set_row_typical first")
 
 
 def _is_number(x):
@@ -116,23 +111,99 @@ def per_codebook(name, value, K):
     return vs
 
 
+# A parameter, in the kernels' order (the entry points alone put top-k before the temperature): its buffer's dtype, what it is
+# before a write names it (no nucleus, no min-p cut, no penalty, no typical cut; the pair's placeholders are never read - the first
+# write brings a pair), its rule and its position among the rule's arguments and results, and whether a request may name the
+# identity on a server below the parameter's level (typical_p = 1 asks for nothing; the older six are refused whenever named).
+Param = namedtuple("Param", "name dtype identity rule pos identity_ok")
+PARAMS = (
+    Param("temperature", torch.float32, 1.0, check_sampling, 0, False),
+    Param("topk", torch.int32, 1, check_sampling, 1, False),
+    Param("top_p", torch.float32, 1.0, check_filters, 0, False),
+    Param("min_p", torch.float32, 0.0, check_filters, 1, False),
+    Param("repetition_penalty", torch.float32, 1.0, check_processors, 0, False),
+    # (SMP_HIST of csrc/generate.hip: the frames a row's ring of sampled codes holds, per codebook)
+    Param("repetition_window", torch.int32, 64, check_processors, 1, False),
+    Param("typical_p", torch.float32, 1.0, check_typical, 0, True),
+)
+# A level, by its number: ``fn`` - the launch that draws (its name in csm.hip.ops and csm.models.model; "csm_" + fn is the entry
+# point); ``reads`` - how many leading parameters its kernel reads; ``writes`` - those a ``set_row_*`` of the level brings;
+# ``rings`` - whether the kernel keeps the rows' rings of sampled codes; ``tag`` - what it adds to the captured frame graph's key;
+# ``flag`` - the ``serve()`` keyword that asks for it ("set_" + flag is the state's writer); and the texts that speak of it:
+# ``first`` (the state is below it), ``needs`` (serve: the flag without row_sampling), ``value`` (serve: a value of its own
+# without the flag), ``refusal`` (a request names what is its own on a server below it; temperature / topk there: the server's).
+Level = namedtuple("Level", "fn reads writes rings tag flag first needs value refusal")
+LEVELS = (
+    Level(None, 0, (), False, None, None, None, None, None, None),
+    Level("sample_topk_rows", 2, (0, 1), False, (), "row_sampling",
+          "temperature = topk = None samples each row with its own pair: call set_row_sampling first", None, None,
+          "{what}: temperature / topk per request need a server made with serve(row_sampling=True) (this server samples every row "
+          "with temperature={temperature}, topk={topk})"),
+    Level("sample_filtered_rows", 4, (2, 3), False, ("filters",), "row_filters", "no row filters: call set_row_filters first",
+          "serve(row_filters=True) needs row_sampling=True: top-p / min-p live in the rows sampler",
+          "top_p={top_p!r} / min_p={min_p!r} need a server made with serve(row_filters=True) (and row_sampling=True)",
+          "{what}: top_p / min_p per request need a server made with serve(row_filters=True) (with row_sampling=True; this server "
+          "samples without filters)"),
+    Level("sample_processed_rows", 6, (0, 1, 2, 3, 4, 5), True, ("processors",), "row_processors",
+          "no row processors: call set_row_processors first",
+          "serve(row_processors=True) needs row_sampling=True: the repetition penalty and per-codebook parameters live in the rows sampler",
+          "repetition_penalty={repetition_penalty!r} / repetition_window={repetition_window!r} and a sequence of values per codebook "
+          "need a server made with serve(row_processors=True) (and row_sampling=True)",
+          "{what}: repetition_penalty / repetition_window and a sequence of values per codebook need a server made with "
+          "serve(row_processors=True) (with row_sampling=True)"),
+    Level("sample_typical_rows", 7, (0, 1, 2, 3, 4, 5, 6), True, ("typical",), "row_typical",
+          "no row typical sampling: call set_row_typical first",
+          "serve(row_typical=True) needs row_sampling=True: typical sampling lives in the rows sampler",
+          "typical_p={typical_p!r} needs a server made with serve(row_typical=True) (and row_sampling=True)",
+          "{what}: typical_p needs a server made with serve(row_typical=True) (with row_sampling=True)"),
+)
+# the first level of whole rows: a write brings everything the kernel reads, a value may be K numbers (one per codebook), the
+# kernel keeps the rings - and the entry points take the ring arguments after the parameters this level reads
+FULL_LEVEL = next(n for n, lv in enumerate(LEVELS) if lv.rings)
+NAMES = tuple(p.name for p in PARAMS)
+PROCESSOR_NAMES = NAMES[:LEVELS[FULL_LEVEL].reads]                    # (the six of the processed sampler, under their old names)
+DTYPES = tuple(p.dtype for p in PARAMS[:len(PROCESSOR_NAMES)])
+IDENTITY = tuple(p.identity for p in PARAMS[:len(PROCESSOR_NAMES)])
+HIST_FRAMES = PARAMS[NAMES.index("repetition_window")].identity      # (the widest window is the ring)
+
+
+def own_params(level):
+    """The indices of the parameters ``level`` is the first to read."""
+    return range(LEVELS[level - 1].reads, LEVELS[level].reads)
+
+
+def _row(indices, vals):
+    """One entry per parameter: ``vals`` at ``indices``, None (left as it is) elsewhere."""
+    return tuple(vals[indices.index(j)] if j in indices else None for j in range(len(PARAMS)))
+
+
+def check_row(K, vocab, indices, values, each=True):
+    """One row's ``values`` of the parameters ``indices`` (a rule's parameters come together), each a number or K numbers, held to
+    their rules codebook by codebook.  Returns one tuple of K values per index (floats; ints for topk and the window).  ``each``
+    False (below ``FULL_LEVEL``): a value is one number for every codebook and goes to its rule as it is."""
+    indices = tuple(indices)
+    if len(values) != len(indices):
+        raise TypeError(f"{len(indices)} values ({', '.join(NAMES[j] for j in indices)}), got {len(values)}")
+    cols = {j: per_codebook(NAMES[j], v, K) if each else [v] for j, v in zip(indices, values)}
+    out = {j: [] for j in indices}
+    groups = [[g for g in indices if PARAMS[g].rule is PARAMS[j].rule] for j in indices if PARAMS[j].pos == 0]
+    for i in range(K if each else 1):
+        for group in groups:
+            rule = PARAMS[group[0]].rule
+            got = rule(*[cols[g][i] for g in group], *([vocab] if rule is check_sampling else []))   # (top-k's bound is the vocabulary)
+            for g, v in zip(group, got if isinstance(got, tuple) else (got,)):
+                out[g].append(v)
+    return tuple(tuple(out[j]) * (1 if each else K) for j in indices)
+
+
 def check_row_processors(K, vocab, temperature, topk, top_p, min_p, repetition_penalty, repetition_window):
-    """One row's six sampling parameters, each a number or K numbers, held to ``check_sampling`` / ``check_filters`` /
-    ``check_processors`` codebook by codebook.  Returns six tuples of K values (floats; ints for topk and the window)."""
-    cols = [per_codebook(n, v, K) for n, v in zip(PROCESSOR_NAMES, (temperature, topk, top_p, min_p, repetition_penalty,
-                                                                     repetition_window))]
-    out = [[] for _ in cols]
-    for i in range(K):
-        vals = (check_sampling(cols[0][i], cols[1][i], vocab) + check_filters(cols[2][i], cols[3][i])
-                + check_processors(cols[4][i], cols[5][i]))
-        for o, v in zip(out, vals):
-            o.append(v)
-    return tuple(tuple(o) for o in out)
+    """``check_row`` of the six parameters of the processed sampler."""
+    return check_row(K, vocab, range(len(PROCESSOR_NAMES)), (temperature, topk, top_p, min_p, repetition_penalty, repetition_window))
 
 
 def check_row_typical(K, typical_p):
-    """One row's ``typical_p``, a number or K numbers, held to ``check_typical`` codebook by codebook: a tuple of K floats."""
-    return tuple(check_typical(v) for v in per_codebook("typical_p", typical_p, K))
+    """``check_row`` of ``typical_p`` alone: a tuple of K floats."""
+    return check_row(K, None, (NAMES.index("typical_p"),), (typical_p,))[0]
 
 
 def names_processors(*values, repetition_penalty=None, repetition_window=None):
@@ -149,17 +220,16 @@ def names_processors(*values, repetition_penalty=None, repetition_window=None):
 
 def normalise(B, K, vocab, temperature, topk, top_p=None, min_p=None, repetition_penalty=None, repetition_window=None, *,
               level=0, unit="row", typical_p=None):
-    """What a frame call's six sampling values ask for: (the level the call needs, per row six entries - a tuple of K validated
-    values each, or None for a parameter the call leaves as it is).  Level 0: two numbers, or None for both - the call passes them
-    through and writes nothing (no rows come back).  Each value is None (not named), a number (every row) or B entries; at level 3
-    an entry is a number or K numbers, one per codebook.  Level 1 (a sequence in the pair) writes the pair; level 2 (``top_p`` /
-    ``min_p`` named) the filters - the one not named at its identity - and the pair, unless both are None; level 3 (a penalty, a
-    window or a per-codebook entry named, or anything beyond a plain pair on a state whose ``level`` is 3: it draws every rows
-    frame through the processors) all six, those not named at their identity.  Everything is checked here, so the caller writes
-    all rows or none.  Level 4 (``typical_p`` named - a number, B entries, or per entry K numbers - or anything beyond a plain
-    pair on a state whose ``level`` is 4): rows of SEVEN entries, the six of level 3 and ``typical_p`` (1.0 if not named).
-    ``unit``: what the errors call a row ("utterance": the generator's calls, checked before any cache is taken
-    over)."""
+    """What a frame call's sampling values ask for: (the level the call needs, per row ``len(PARAMS)`` entries - a tuple of K
+    validated values each, or None for a parameter the call leaves as it is).  Level 0: two numbers, or None for both - the call
+    passes them through and writes nothing (no rows come back).  Each value is None (not named), a number (every row) or B
+    entries; from ``FULL_LEVEL`` on an entry is a number or K numbers, one per codebook.  Level 1 (a sequence in the pair) writes
+    the pair; level 2 (``top_p`` / ``min_p`` named) the filters - the one not named at its identity - and the pair, unless both
+    are None.  Everything goes to the rows - all the level's kernel reads, those not named at their identity - when a penalty, a
+    window, a per-codebook entry or a higher level's parameter (``typical_p``) is named, or anything beyond a plain pair on a
+    state at ``FULL_LEVEL`` or above: at the highest of ``FULL_LEVEL``, the state's ``level`` and the level of what is named.
+    All is checked here, so the caller writes all rows or none.  ``unit``: what the errors call a row ("utterance": the
+    generator's calls, checked before any cache is taken over)."""
     many = f"{B} rows" if unit == "row" else f"{B}"
 
     def rows_of(v, what):
@@ -168,26 +238,23 @@ def normalise(B, K, vocab, temperature, topk, top_p=None, min_p=None, repetition
             raise ValueError(what)
         return vs
 
+    given = (temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p)
     plain = (temperature is None and topk is None) or (_is_number(temperature) and _is_number(topk))
-    if typical_p is not None or (level == 4 and not (plain and top_p is None and min_p is None and repetition_penalty is None
-                                                      and repetition_window is None)):
+    above = [n for n in range(FULL_LEVEL + 1, len(LEVELS)) if any(given[j] is not None for j in own_params(n))]
+    if (above or names_processors(temperature, topk, top_p, min_p, repetition_penalty=repetition_penalty,
+                                  repetition_window=repetition_window)
+            or (level >= FULL_LEVEL and not (plain and top_p is None and min_p is None))):
+        target = max([FULL_LEVEL, level] + above)
+        idx = LEVELS[target].writes
         if temperature is None or topk is None:
-            raise ValueError("typical_p, per-codebook parameters and the repetition penalty need temperature and topk named")
-        seven = [ident if v is None else v for ident, v in zip(IDENTITY + (1.0,), (temperature, topk, top_p, min_p, repetition_penalty,
-                                                                                   repetition_window, typical_p))]
-        cols = [rows_of(v, f"{name} is a number or a sequence of one entry per {unit} ({many}; an entry is a number or one number "
-                           f"per codebook), got {v!r}") for name, v in zip(PROCESSOR_NAMES + ("typical_p",), seven)]
-        return 4, [check_row_processors(K, vocab, *[vs[b] for vs in cols[:6]]) + (check_row_typical(K, cols[6][b]),)
-                   for b in range(B)]
-    if names_processors(temperature, topk, top_p, min_p, repetition_penalty=repetition_penalty,
-                        repetition_window=repetition_window) or (level == 3 and not (plain and top_p is None and min_p is None)):
-        if temperature is None or topk is None:
-            raise ValueError("per-codebook parameters and the repetition penalty need temperature and topk named")
-        six = [IDENTITY[j] if v is None else v
-               for j, v in enumerate((temperature, topk, top_p, min_p, repetition_penalty, repetition_window))]
-        cols = [rows_of(v, f"{name} is a number or a sequence of one entry per {unit} ({many}; an entry is a number or one number "
-                           f"per codebook), got {v!r}") for name, v in zip(PROCESSOR_NAMES, six)]
-        return 3, [check_row_processors(K, vocab, *[vs[b] for vs in cols]) for b in range(B)]
+            higher = "".join(name + ", " for name in NAMES[LEVELS[FULL_LEVEL].reads:LEVELS[target].reads])
+            raise ValueError(f"{higher}per-codebook parameters and the repetition penalty need temperature and topk named")
+        cols = []
+        for j in idx:
+            v = PARAMS[j].identity if given[j] is None else given[j]
+            cols.append(rows_of(v, f"{NAMES[j]} is a number or a sequence of one entry per {unit} ({many}; an entry is a number or "
+                                   f"one number per codebook), got {v!r}"))
+        return target, [_row(idx, check_row(K, vocab, idx, [vs[b] for vs in cols])) for b in range(B)]
     if top_p is None and min_p is None:
         if plain:
             return 0, None
@@ -204,71 +271,61 @@ def normalise(B, K, vocab, temperature, topk, top_p=None, min_p=None, repetition
                 f"temperature={temperature!r}, topk={topk!r}")
         ts, ks = rows_of(temperature, what), rows_of(topk, what)
         pairs = [tuple((v,) * K for v in check_sampling(t, k, vocab)) for t, k in zip(ts, ks)]
-    return (1 if top_p is None and min_p is None else 2), [pr + f + (None, None) for pr, f in zip(pairs, filters)]
+    both = LEVELS[1].writes + LEVELS[2].writes
+    return (1 if top_p is None and min_p is None else 2), [_row(both, pr + f) for pr, f in zip(pairs, filters)]
 
 
 class RowSampler:
-    """The per-row sampling state of a ``DecodeState`` (the module docstring): ``level``, the six parameter buffers ``params``
-    ([K, B], made by the first write), the host mirror ``rows`` (per row, six tuples of K values) and, from level 3 on, what the
-    processed rows sampler keeps: ``code_hist`` int32 [B, K, 64] (slot f % 64 of [b, i]: the code row b drew for codebook i in
-    frame f of its utterance), ``hist_frame`` int32 [B] (f) and ``hist_live`` int32 [B] (the rows that write their ring and count
-    the frame).  At level 4 the seventh parameter stands beside the six: ``typical`` ([K, B] fp32, made at the rise and filled
-    with 1.0) with its mirror ``typical_rows`` (per row, K values).  Every write happens outside the captured frame graph, so a change of parameters never recaptures; a rise of the
-    level does (``graph_key``): make it before the first capture."""
+    """The per-row sampling state of a ``DecodeState`` (the module docstring): ``level``, one parameter buffer per ``PARAMS``
+    record in ``params`` ([K, B] each, made by the first write at the identities), the host mirror ``rows`` (per row, one tuple
+    of K values per parameter) and, from the first level that keeps them on, the rings: ``code_hist`` int32 [B, K, 64] (slot
+    f % 64 of [b, i]: the code row b drew for codebook i in frame f of its utterance), ``hist_frame`` int32 [B] (f) and
+    ``hist_live`` int32 [B] (the rows that write their ring and count the frame).  Every write happens outside the captured
+    frame graph, so a change of parameters never recaptures; a rise of the level does (``graph_key``): make it before the first
+    capture."""
 
     def __init__(self, B, K, vocab, device):
         self.B, self.K, self.vocab, self.device = B, K, vocab, device
         self.level, self.params, self.rows = 0, None, None
         self.code_hist, self.hist_frame, self.hist_live, self.live_rows = None, None, None, None
-        self.typical, self.typical_rows = None, None
 
     def need(self, level):
         if self.level < level:
-            raise RuntimeError(_FIRST[level])
+            raise RuntimeError(LEVELS[level].first)
+
+    @property
+    def keeps_history(self):
+        """Whether the state's draws keep the rows' rings of sampled codes."""
+        return LEVELS[self.level].rings
 
     def write(self, b, level, *values):
-        """Row ``b``'s parameters of ``level`` from its next frame on - ``set_row_sampling``'s two, ``set_row_filters``' two or
-        ``set_row_processors``' six or ``set_row_typical``'s seven (each a number or K numbers) - held to their rule first."""
-        if level == 4:
-            vals = check_row_processors(self.K, self.vocab, *values[:6]) + (check_row_typical(self.K, *values[6:]),)
-        elif level == 3:
-            vals = check_row_processors(self.K, self.vocab, *values)
-        else:
-            two = check_sampling(*values, self.vocab) if level == 1 else check_filters(*values)
-            two = tuple((v,) * self.K for v in two)
-            vals = two + (None,) * 4 if level == 1 else (None, None) + two + (None, None)
-        self.store(b, level, vals)
+        """Row ``b``'s parameters of ``level`` from its next frame on - what ``LEVELS[level]`` writes: ``set_row_sampling``'s two,
+        ``set_row_filters``' two, ``set_row_processors``' six or ``set_row_typical``'s seven (below ``FULL_LEVEL`` a number each,
+        from there on a number or K numbers) - held to their rule first."""
+        lv = LEVELS[level]
+        self.store(b, level, _row(lv.writes, check_row(self.K, self.vocab, lv.writes, values, each=lv.rings)))
 
     def store(self, b, level, vals):
         """Validated values (``normalise``'s entries: None leaves a parameter as it is) into column ``b`` of the buffers and the
         mirror; only what changed is written.  A write that raises the level gives its values to every row (a row that is never set
         still samples with valid parameters: the kernels run on all B rows).  A buffer whose K values agree is written with one
-        fill (launch-only); only K different values - level 3 on - take a small blocking host-to-device copy.  A seventh value
-        is ``typical_p`` (level 4)."""
+        fill (launch-only); only K different values - ``FULL_LEVEL`` on - take a small blocking host-to-device copy."""
         b = int(b)
         if not 0 <= b < self.B:
             raise ValueError(f"row {b} out of range (the state has {self.B})")
         if self.params is None:
-            if vals[0] is None or vals[1] is None:           # (filters before pairs: the rows path starts with a pair)
-                raise RuntimeError(_FIRST[1])
-            self.params = tuple(torch.full((self.K, self.B), v, dtype=dt, device=self.device) for v, dt in zip(IDENTITY, DTYPES))
-            self.rows = [tuple((v,) * self.K for v in IDENTITY)] * self.B
+            if any(vals[j] is None for j in LEVELS[1].writes):    # (filters before pairs: the rows path starts with a pair)
+                raise RuntimeError(LEVELS[1].first)
+            self.params = tuple(torch.full((self.K, self.B), p.identity, dtype=p.dtype, device=self.device) for p in PARAMS)
+            self.rows = [tuple((p.identity,) * self.K for p in PARAMS)] * self.B
         rising = level > self.level
         cols, rows = (slice(None), range(self.B)) if rising else (slice(b, b + 1), (b,))
-        for j, new in enumerate(vals[:6]):
+        for j, new in enumerate(vals):
             if new is not None and (rising or new != self.rows[b][j]):
                 self.put(j, cols, new)
         for r in rows:
             self.rows[r] = tuple(old if new is None else new for old, new in zip(self.rows[r], vals))
-        if level == 4:
-            if self.typical is None:
-                self.typical = torch.full((self.K, self.B), 1.0, dtype=torch.float32, device=self.device)
-                self.typical_rows = [(1.0,) * self.K] * self.B
-            if rising or vals[6] != self.typical_rows[b]:
-                self.put(6, cols, vals[6])
-            for r in rows:
-                self.typical_rows[r] = vals[6]
-        if level >= 3 and self.level < 3:
+        if LEVELS[level].rings and not self.keeps_history:
             self.code_hist = torch.zeros(self.B, self.K, HIST_FRAMES, dtype=torch.int32, device=self.device)
             self.hist_frame = torch.zeros(self.B, dtype=torch.int32, device=self.device)
             self.hist_live = torch.ones(self.B, dtype=torch.int32, device=self.device)
@@ -277,7 +334,7 @@ class RowSampler:
 
     def put(self, j, cols, new):
         """Parameter ``j``'s K values ``new`` into the columns ``cols`` of its buffer."""
-        view = (self.typical if j == 6 else self.params[j])[:, cols]
+        view = self.params[j][:, cols]
         if len(set(new)) == 1:
             view.fill_(new[0])
         else:
@@ -288,18 +345,18 @@ class RowSampler:
         (None, None) comes back; two numbers, or None for both, with nothing else named pass through."""
         level, rows = normalise(self.B, self.K, self.vocab, temperature, topk, top_p, min_p, repetition_penalty,
                                 repetition_window, level=self.level, typical_p=typical_p)
-        if level == 0:
+        if not level:
             return temperature, topk
         for b, vals in enumerate(rows):
             self.store(b, level, vals)
         return None, None
 
     def reset_history(self, b):
-        self.need(3)
+        self.need(FULL_LEVEL)
         self.hist_frame[int(b):int(b) + 1].zero_()
 
     def set_live(self, rows):
-        if self.level < 3:
+        if not self.keeps_history:
             return
         rows = sorted(int(b) for b in rows)
         if rows != self.live_rows:
@@ -308,25 +365,18 @@ class RowSampler:
 
     def draw(self, logits, i, q):
         """Codebook ``i``'s codes for [B, V] ``logits`` and the Exp(1) draws ``q``, each row with its own parameters: int32
-        [B, 1].  From level 3 on the draw also writes the live rows' rings, and the last codebook's counts the frame."""
-        from .models.model import sample_filtered_rows, sample_processed_rows, sample_topk_rows, sample_typical_rows
+        [B, 1].  Where the level keeps rings the draw also writes the live rows', and the last codebook's counts the frame."""
+        from .models.model import _sample_rows
         self.need(1)
-        t, k, p, m, r, w = (buf[i] for buf in self.params)
-        if self.level == 1:
-            return sample_topk_rows(logits, k, t, q)
-        if self.level == 2:
-            return sample_filtered_rows(logits, k, t, p, m, q)
-        if self.level == 4:
-            return sample_typical_rows(logits, k, t, p, m, r, w, self.code_hist[:, i], self.hist_frame, self.hist_live,
-                                       self.typical[i], advance=(i == self.K - 1), q=q)
-        return sample_processed_rows(logits, k, t, p, m, r, w, self.code_hist[:, i], self.hist_frame, self.hist_live,
-                                     advance=(i == self.K - 1), q=q)
+        lv = LEVELS[self.level]
+        ring = (self.code_hist[:, i], self.hist_frame, self.hist_live) if lv.rings else ()
+        return _sample_rows(self.level, logits, [buf[i] for buf in self.params[:lv.reads]], ring, i == self.K - 1, q)
 
     def graph_key(self, temperature, topk):
         """The key of the captured frame graph a frame call with these two replays: the pair itself, or - None for both - what
         tells the rows samplers apart (the kernels read the parameters from the buffers: any change of them replays the graph)."""
         if temperature is None and topk is None:
-            return (None, None) + ((), (), ("filters",), ("processors",), ("typical",))[self.level]
+            return (None, None) + (LEVELS[self.level].tag or ())
         return (float(temperature), int(topk))
 
     @property
@@ -342,9 +392,9 @@ class RowSampler:
     @property
     def row_processors(self):
         """Per row, six tuples of K values at level 3, else None."""
-        return list(self.rows) if self.level == 3 else None
+        return [r[:LEVELS[3].reads] for r in self.rows] if self.level == 3 else None
 
     @property
     def row_typical(self):
         """Per row, seven tuples of K values - the six and ``typical_p`` - at level 4, else None."""
-        return [r + (y,) for r, y in zip(self.rows, self.typical_rows)] if self.level == 4 else None
+        return [r[:LEVELS[4].reads] for r in self.rows] if self.level == 4 else None

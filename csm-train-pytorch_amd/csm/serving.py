@@ -44,9 +44,9 @@ decode frame.  So a request has the same codes in any slot, whoever joins beside
 
 Typical sampling.  ``serve(row_sampling=True, row_typical=True, typical_p=1.0)`` includes the processors and adds locally typical
 sampling per request (``typical_p`` in (0, 1], a number or K numbers; resolved and checked like the others), written at admission
-(``DecodeState.set_row_typical``: a seventh [K, B] buffer); every draw goes through the typical rows sampler
-(``csm_sample_typical_rows``), which keeps, of what the other filters left, the tokens whose surprise is closest to the entropy -
-it can drop the most likely code, which no other filter can.  At 1.0 a request has the codes of a ``row_processors`` server; a
+(``DecodeState.set_row_typical``: the seventh of the state's [K, B] buffers, at 1.0 until then); every draw goes through the
+typical rows sampler (``csm_sample_typical_rows``), which keeps, of what the other filters left, the tokens whose surprise is
+closest to the entropy - it can drop the most likely code, which no other filter can.  At 1.0 a request has the codes of a ``row_processors`` server; a
 change of ``typical_p`` replays the same captured frame.
 
 Multi-turn conversations (``BatchServer.conversation`` -> ``ServedConversation``) outlive their slot.  A conversation holds a
@@ -101,12 +101,12 @@ import torch
 
 from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, hear_resampler, open_heard_turn
 from .engine import DecodeState
-from .sampling import HIST_FRAMES, _as_list, _is_number, check_filters, check_row_processors, check_row_typical, check_sampling
+from .sampling import FULL_LEVEL, HIST_FRAMES, LEVELS, NAMES, PARAMS, _as_list, _is_number, check_row, own_params
 
 
-def _collapsed(six):
-    """``check_row_processors``' six tuples of K values, each as one number where every codebook has the same."""
-    return tuple(v[0] if all(x == v[0] for x in v) else v for v in six)
+def _collapsed(vals):
+    """``check_row``'s tuples of K values, each as one number where every codebook has the same."""
+    return tuple(v[0] if all(x == v[0] for x in v) else v for v in vals)
 
 
 class Request:
@@ -210,9 +210,9 @@ class ServedConversation:
         self._srv, self._gen = server, server._gen
         self.adapter, self.seed, self._on_overflow = adapter, seed, on_overflow
         # its turns' defaults, resolved
-        (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window) = server._resolve(
-            "conversation", temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
-        self.typical_p = server._typical("conversation", typical_p)
+        for name, v in zip(NAMES, server._resolve("conversation", (temperature, topk, top_p, min_p, repetition_penalty,
+                                                                   repetition_window, typical_p))):
+            setattr(self, name, v)
         K1 = server._K + 1
         self._tokens = torch.zeros(0, K1, dtype=torch.long, device=self._gen.device)
         self._mask = torch.zeros(0, K1, dtype=torch.bool, device=self._gen.device)
@@ -309,9 +309,8 @@ class ServedConversation:
         turn's, over the conversation's.  The window looks at this turn's frames only."""
         self._idle("say")
         srv = self._srv
-        six = srv._resolve("say", temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
-                           (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window))
-        typical_p = srv._typical("say", typical_p, self.typical_p)
+        params = srv._resolve("say", (temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p),
+                              [getattr(self, name) for name in NAMES])
         max_audio_frames = int(max_audio_length_ms / 80)
         if max_audio_frames < 1:
             raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
@@ -320,8 +319,7 @@ class ServedConversation:
         feed_t = torch.cat([self._tokens[self._cached:], tt.long().to(self._tokens.device)], 0)
         feed_m = torch.cat([self._mask[self._cached:], tm.bool().to(self._mask.device)], 0)
         self._push(tt.long(), tm.bool())
-        req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device,
-                      *six, typical_p=typical_p)
+        req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device, *params)
         req._conv, req._base, req.sample_rate = self, self._tokens.shape[0], srv.sample_rate
         srv._next_id += 1
         srv._queue.append(req)
@@ -370,23 +368,15 @@ class BatchServer:
                  output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
                  repetition_window=HIST_FRAMES, row_typical: bool = False, typical_p=1.0):
         out_rs = gen._out_resampler(output_sample_rate)      # (a bad rate raises here, before anything is taken over)
-        if row_typical and not row_sampling:
-            raise ValueError("serve(row_typical=True) needs row_sampling=True: typical sampling lives in the rows sampler")
-        if not row_typical and not (_is_number(typical_p) and typical_p == 1.0):
-            raise ValueError(f"typical_p={typical_p!r} needs a server made with serve(row_typical=True) (and row_sampling=True)")
-        row_processors = bool(row_processors or row_typical)
-        if row_processors and not row_sampling:
-            raise ValueError("serve(row_processors=True) needs row_sampling=True: the repetition penalty and per-codebook "
-                             "parameters live in the rows sampler")
-        if not row_processors and (not (repetition_penalty == 1.0 and repetition_window == HIST_FRAMES)
-                                   or any(_as_list(v) is not None for v in (temperature, topk, top_p, min_p))):
-            raise ValueError(f"repetition_penalty={repetition_penalty!r} / repetition_window={repetition_window!r} and a sequence of "
-                             "values per codebook need a server made with serve(row_processors=True) (and row_sampling=True)")
-        row_filters = bool(row_filters or row_processors)
-        if row_filters and not row_sampling:
-            raise ValueError("serve(row_filters=True) needs row_sampling=True: top-p / min-p live in the rows sampler")
-        if not row_filters and not (top_p == 1.0 and min_p == 0.0):
-            raise ValueError(f"top_p={top_p!r} / min_p={min_p!r} need a server made with serve(row_filters=True) (and row_sampling=True)")
+        # the level: the highest one asked for (it includes those below); a flag needs row_sampling, a value off its identity its flag
+        flags = dict(row_sampling=row_sampling, row_filters=row_filters, row_processors=row_processors, row_typical=row_typical)
+        given = (temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p)
+        level = max((n for n, lv in enumerate(LEVELS) if lv.flag and flags[lv.flag]), default=0)
+        for n in range(len(LEVELS) - 1, 1, -1):
+            if flags[LEVELS[n].flag] and not row_sampling:
+                raise ValueError(LEVELS[n].needs)
+            if level < n and self._names(n, given, lambda j: not (_is_number(given[j]) and given[j] == PARAMS[j].identity)):
+                raise ValueError(LEVELS[n].value.format(**dict(zip(NAMES, given))))
         if int(slots) != slots or not 1 <= slots <= 16:
             raise ValueError(f"slots must be an integer in 1..16, got {slots!r}")
         if int(hear_slots) != hear_slots or not 0 <= hear_slots <= 16:
@@ -400,20 +390,16 @@ class BatchServer:
             raise TypeError(f"{type(codec).__name__} has no encode_stream_rows(): hear_slots needs a batched stateful encoder")
         self._gen, self._model = gen, gen._model
         self.slots, self.chunk_frames, self.hear_slots = int(slots), int(chunk_frames), int(hear_slots)
-        self.row_sampling, self.row_filters, self.row_processors = bool(row_sampling), bool(row_filters), bool(row_processors)
+        self.level = level
+        for n in range(1, len(LEVELS)):                  # (row_sampling, row_filters, row_processors, row_typical)
+            setattr(self, LEVELS[n].flag, level >= n)
         self._K = gen._model.args.audio_num_codebooks
-        self.row_typical = bool(row_typical)
-        self.typical_p = self._typical("serve", typical_p, 1.0) if self.row_typical else 1.0
-        self.repetition_penalty, self.repetition_window = 1.0, HIST_FRAMES
-        if self.row_processors:                          # (the requests' defaults: held to the requests' rule, before anything is taken over)
-            (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window) = _collapsed(
-                check_row_processors(self._K, gen._model.args.audio_vocab_size, temperature, topk, top_p, min_p, repetition_penalty,
-                                     repetition_window))
-        else:
-            self.temperature, self.topk = float(temperature), int(topk)
-            if self.row_sampling:
-                self.temperature, self.topk = check_sampling(temperature, topk, gen._model.args.audio_vocab_size)
-            self.top_p, self.min_p = check_filters(top_p, min_p) if self.row_filters else (1.0, 0.0)
+        # the requests' defaults: what the level reads held to the requests' rule (before anything is taken over), the rest at its
+        # identity - but the pair of a server without row_sampling: the scalar path's two launch numbers, as they are
+        reads = LEVELS[level].reads
+        defaults = self._held(None, given[:reads] + tuple(p.identity for p in PARAMS[reads:]))
+        for name, v in zip(NAMES, defaults if level else (float(temperature), int(topk)) + defaults[LEVELS[1].reads:]):
+            setattr(self, name, v)
         gen._run += 1                                    # takes over the model's caches, as generate_batch does
         self._run = gen._run
         self._model.reset_caches()
@@ -433,18 +419,8 @@ class BatchServer:
         if out_rs is not None:
             self._out = out_rs.stream_rows(self.slots, self.chunk_frames * (int(gen.sample_rate) * 80 // 1000))     # (80 ms frames)
         self._model._decode_state = self._state
-        if self.row_typical:
-            for b in range(self.slots):                  # (before the first capture: the frame holds the typical sampler)
-                self._state.set_row_typical(b, *self._defaults(), self.typical_p)
-        elif self.row_processors:
-            for b in range(self.slots):                  # (before the first capture: the frame holds the processed sampler)
-                self._state.set_row_processors(b, *self._defaults())
-        elif self.row_sampling:
-            for b in range(self.slots):                  # every row starts with a valid pair: the sampler runs on all of them
-                self._state.set_row_sampling(b, self.temperature, self.topk)
-        if self.row_filters and not self.row_processors:
-            for b in range(self.slots):                  # (before the first capture: the frame holds the filtered sampler)
-                self._state.set_row_filters(b, self.top_p, self.min_p)
+        # every row starts with valid parameters (the sampler runs on all rows), the state at its level before the first capture
+        self._set_rows(range(self.slots), self._defaults())
         K = self._K
         dev = gen.device
         self._tok = torch.zeros(self.slots, 1, K + 1, dtype=torch.long, device=dev)      # each row's last sampled frame
@@ -462,66 +438,40 @@ class BatchServer:
             raise RuntimeError("this server was invalidated: a later generate / generate_batch / generate_stream / serve call on "
                                "the same Generator took over the model's caches")
 
-    def _sampling(self, what, temperature, topk, default=None):
-        """A request's (temperature, topk), resolved against ``default`` (the server's pair if None) and held to
-        ``DecodeState.set_row_sampling``'s rule - at the call, so a bad request raises before it queues."""
-        dt, dk = default if default is not None else (self.temperature, self.topk)
-        if temperature is None and topk is None:
-            return dt, dk
-        if not self.row_sampling:
-            raise ValueError(f"{what}: temperature / topk per request need a server made with serve(row_sampling=True) (this "
-                             f"server samples every row with temperature={self.temperature}, topk={self.topk})")
-        return check_sampling(dt if temperature is None else temperature, dk if topk is None else topk,
-                              self._model.args.audio_vocab_size)
-
-    def _filters(self, what, top_p, min_p, default=None):
-        """A request's (top_p, min_p), resolved against ``default`` (the server's if None) and held to ``check_filters`` - at the
-        call, so a bad request raises before it queues."""
-        dp, dm = default if default is not None else (self.top_p, self.min_p)
-        if top_p is None and min_p is None:
-            return dp, dm
-        if not self.row_filters:
-            raise ValueError(f"{what}: top_p / min_p per request need a server made with serve(row_filters=True) (with "
-                             f"row_sampling=True; this server samples without filters)")
-        return check_filters(dp if top_p is None else top_p, dm if min_p is None else min_p)
+    @staticmethod
+    def _names(n, values, named):
+        """Whether ``values`` name what only level ``n`` and above take: one of its own parameters (``named(j)``), or - the first
+        level of whole rows - a sequence (one value per codebook) in a parameter below it."""
+        mine = own_params(n)
+        return any(named(j) for j in mine) or (n == FULL_LEVEL and any(_as_list(v) is not None for v in values[:mine.start]))
 
     def _defaults(self):
-        return (self.temperature, self.topk, self.top_p, self.min_p, self.repetition_penalty, self.repetition_window)
+        return tuple(getattr(self, name) for name in NAMES)
 
-    def _resolve(self, what, temperature, topk, top_p, min_p, repetition_penalty, repetition_window, default=None):
-        """A request's six sampling parameters (None: not named), resolved against ``default`` (the server's if None) and held to
-        the rows' rules - at the call, so a bad request raises before it queues.  On a ``row_processors`` server each is a number
-        or K numbers (one per codebook) and comes back as a number, or as a tuple of K where the codebooks differ; on any other
-        server a penalty, a window or a sequence is refused and the last two come back as 1.0 / 64."""
-        d = default if default is not None else self._defaults()
-        if not self.row_processors:
-            if repetition_penalty is not None or repetition_window is not None or any(
-                    _as_list(v) is not None for v in (temperature, topk, top_p, min_p)):
-                raise ValueError(f"{what}: repetition_penalty / repetition_window and a sequence of values per codebook need a "
-                                 "server made with serve(row_processors=True) (with row_sampling=True)")
-            return (self._sampling(what, temperature, topk, d[:2]) + self._filters(what, top_p, min_p, d[2:4])
-                    + (1.0, HIST_FRAMES))
-        named = (temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
+    def _held(self, what, params):
+        """One value per parameter as this server's rows take them: those its level reads held to their rules - a number each, or
+        (whole rows) K numbers, one per codebook, which come back as a tuple of K where they differ - and the rest as they are.  A
+        rule's refusal names the call (``what``) where the rows are whole, as it always did."""
+        lv = LEVELS[self.level]
+        reads = lv.reads
+        if not reads:                                    # (the scalar path: nothing of a request's reaches the sampler)
+            return tuple(params)
         try:
-            return _collapsed(check_row_processors(self._K, self._model.args.audio_vocab_size,
-                                                   *[dv if v is None else v for v, dv in zip(named, d)]))
+            head = _collapsed(check_row(self._K, self._model.args.audio_vocab_size, range(reads), params[:reads], each=lv.rings))
         except ValueError as e:
-            raise ValueError(f"{what}: {e}") from None
+            raise ValueError(f"{what}: {e}" if what and lv.rings else str(e)) from None
+        return head + tuple(params[reads:])
 
-    def _typical(self, what, typical_p, default=None):
-        """A request's ``typical_p`` (None: not named), resolved against ``default`` (the server's if None) and held to
-        ``check_typical`` - at the call.  On a ``row_typical`` server a number or K numbers; on any other server anything but None
-        or 1 is refused."""
-        if typical_p is None:
-            return self.typical_p if default is None else default
-        if not self.row_typical:
-            if _is_number(typical_p) and typical_p == 1.0:
-                return 1.0
-            raise ValueError(f"{what}: typical_p needs a server made with serve(row_typical=True) (with row_sampling=True)")
-        try:
-            return _collapsed((check_row_typical(self._K, typical_p),))[0]
-        except ValueError as e:
-            raise ValueError(f"{what}: {e}") from None
+    def _resolve(self, what, named, default=None):
+        """A request's sampling parameters (one per ``PARAMS`` record; None: not named), resolved against ``default`` (the server's
+        if None) and held to the rows' rules (``_held``) - at the call, so a bad request raises before it queues.  What only a level
+        above the server's takes is refused when named, highest level first; what its level does not read comes back as the default."""
+        d = self._defaults() if default is None else default
+        for n in range(len(LEVELS) - 1, self.level, -1):
+            if self._names(n, named, lambda j: named[j] is not None and not (
+                    PARAMS[j].identity_ok and _is_number(named[j]) and named[j] == PARAMS[j].identity)):
+                raise ValueError(LEVELS[n].refusal.format(what=what, **dict(zip(NAMES, self._defaults()))))
+        return self._held(what, [dv if j >= LEVELS[self.level].reads or v is None else v for j, (v, dv) in enumerate(zip(named, d))])
 
     def _sample_args(self):
         """What ``serve_first`` / ``serve_frame`` get: the server's two numbers, or None, None (each row's own pair)."""
@@ -540,8 +490,7 @@ class BatchServer:
         the text; only context and text are tokenised here and fed at admission, and the length rule counts the voice's positions.
         ``adapter`` must be None or the voice's: the request speaks with the voice's."""
         self._check()
-        six = self._resolve("submit", temperature, topk, top_p, min_p, repetition_penalty, repetition_window)
-        typical_p = self._typical("submit", typical_p)
+        params = self._resolve("submit", (temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p))
         if voice is not None:
             adapter = voice.check(self._gen, adapter, "submit")
         if adapter is not None and adapter not in self._bank:
@@ -561,8 +510,7 @@ class BatchServer:
                 limit = self._model.bb.max_seq_len - max_audio_frames
                 if voice.positions + tokens.shape[1] >= limit:
                     raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
-        req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device,
-                      *six, typical_p=typical_p)
+        req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device, *params)
         req.sample_rate, req._voice = self.sample_rate, voice
         self._next_id += 1
         self._queue.append(req)
@@ -697,6 +645,18 @@ class BatchServer:
             self._rows[b]._sampled += 1
         return out
 
+    def _set_rows(self, rows, params, joined=False):
+        """``params`` (one value per ``PARAMS`` record) to the slots ``rows`` through the state's writer of the server's level -
+        after the writers below it for what it does not bring itself (the filters come after the pair); ``joined``: the rows start
+        an utterance - where the level keeps rings, their frame counters return to 0."""
+        own = LEVELS[self.level].writes
+        for n in [n for n in range(1, self.level) if not set(LEVELS[n].writes) <= set(own)] + [self.level] * bool(own):
+            for b in rows:
+                getattr(self._state, "set_" + LEVELS[n].flag)(b, *[params[j] for j in LEVELS[n].writes])
+        if joined and LEVELS[self.level].rings:
+            for b in rows:
+                self._state.reset_row_history(b)
+
     def _admit(self):
         """Queued requests into free slots: plain requests and first turns are prefilled one by one, the turns of conversations
         with a parked cache are resumed, the requests with a voice are forked by ONE ``fork_rows``, and those two kinds are fed
@@ -710,19 +670,8 @@ class BatchServer:
             req = self._queue.popleft()
             conv = req._conv
             st.set_row_adapter(b, self._bank[req.adapter] if req.adapter is not None else None)
-            if self.row_typical:
-                st.set_row_typical(b, req.temperature, req.topk, req.top_p, req.min_p, req.repetition_penalty,
-                                   req.repetition_window, req.typical_p)
-                st.reset_row_history(b)
-            elif self.row_processors:
-                # (every joining row, resumed turns included: a turn's window covers its own frames)
-                st.set_row_processors(b, req.temperature, req.topk, req.top_p, req.min_p, req.repetition_penalty,
-                                      req.repetition_window)
-                st.reset_row_history(b)
-            elif self.row_sampling:
-                st.set_row_sampling(b, req.temperature, req.topk)
-            if self.row_filters and not self.row_processors:
-                st.set_row_filters(b, req.top_p, req.min_p)
+            # (every joining row, resumed turns included: with rings, a turn's window covers its own frames)
+            self._set_rows((b,), [getattr(req, name) for name in NAMES], joined=True)
             if conv is not None and conv.seed is not None:
                 if conv._noise is None:
                     conv._noise = st.new_row_generator(conv.seed)

@@ -66,7 +66,7 @@ def test_normalise_level_4_accepts():
     level, rows = normalise(2, K, VOCAB, [0.9, 0.8], 50, level=4)
     assert level == 4 and [r[0][0] for r in rows] == [0.9, 0.8]
     # below level 4 nothing changed
-    assert normalise(2, K, VOCAB, 0.9, 50, 0.9, level=3)[0] == 3 and len(normalise(2, K, VOCAB, 0.9, 50, 0.9, level=3)[1][0]) == 6
+    assert normalise(2, K, VOCAB, 0.9, 50, 0.9, level=3)[0] == 3 and normalise(2, K, VOCAB, 0.9, 50, 0.9, level=3)[1][0][6] is None
     assert normalise(2, K, VOCAB, 0.9, 50, 0.9)[0] == 2 and normalise(2, K, VOCAB, [0.9, 0.8], 50)[0] == 1
 
 
@@ -113,26 +113,24 @@ class Counting:
         s = self.s
         for j, buf in enumerate(s.params):
             assert torch.equal(buf, torch.tensor([s.rows[b][j] for b in range(s.B)], dtype=buf.dtype).t()), j
-        if s.typical is not None:
-            assert s.typical.dtype == torch.float32 and s.typical.shape == (K, s.B)
-            assert torch.equal(s.typical, torch.tensor(s.typical_rows, dtype=torch.float32).t())
+        assert s.params[6].dtype == torch.float32 and s.params[6].shape == (K, s.B)
 
 
 def test_row_sampler_level_4():
     c = Counting()
     s = c.s
-    assert s.typical is None and s.row_typical is None
+    assert s.params is None and s.row_typical is None
     with pytest.raises(RuntimeError, match="call set_row_typical first"):
         s.need(4)
-    s.write(1, 3, *SIX)                                                   # level 3 first: the seventh buffer is not there yet
-    assert s.level == 3 and s.typical is None and s.row_processors is not None and s.graph_key(None, None) == (None, None, "processors")
+    s.write(1, 3, *SIX)                                                   # level 3 first: the seventh buffer is at its identity
+    assert s.level == 3 and s.params[6].tolist() == [[1.0] * 3] * K and s.row_processors is not None and s.graph_key(None, None) == (None, None, "processors")
     hist = s.code_hist
     del c.writes[:]
     s.write(0, 4, *SIX, 0.5)                                              # the rise: every row gets the seven
     assert s.level == 4 and sorted(c.writes) == [0, 1, 2, 3, 4, 5, 6]
     assert s.code_hist is hist                                            # (the rings of level 3 stay)
-    assert s.typical.tolist() == [[0.5] * 3] * K and s.typical_rows == [(0.5,) * K] * 3
-    assert len(s.params) == 6 and len(s.rows[0]) == 6                     # the six stay the six
+    assert s.params[6].tolist() == [[0.5] * 3] * K and [r[6] for r in s.rows] == [(0.5,) * K] * 3
+    assert len(s.params) == 7 and len(s.rows[0]) == 7
     assert s.row_typical == [_tup(*SIX, 0.5)] * 3
     assert s.row_processors is None and s.row_filters is None and s.row_sampling is None
     assert s.graph_key(None, None) == (None, None, "typical") and s.graph_key(0.9, 50) == (0.9, 50)
@@ -142,15 +140,15 @@ def test_row_sampler_level_4():
     assert c.writes == []
     per = (0.2,) + (1.0,) * (K - 1)
     s.write(2, 4, *SIX, list(per))                                        # one parameter changed: one write, one column
-    assert c.writes == [6] and s.typical[:, 2].tolist() == pytest.approx(list(per)) and s.typical[:, :2].tolist() == [[0.5] * 2] * K
-    assert s.typical_rows == [(0.5,) * K, (0.5,) * K, per]
+    assert c.writes == [6] and s.params[6][:, 2].tolist() == pytest.approx(list(per)) and s.params[6][:, :2].tolist() == [[0.5] * 2] * K
+    assert [r[6] for r in s.rows] == [(0.5,) * K, (0.5,) * K, per]
     del c.writes[:]
     s.write(1, 4, 0.7, 50, 1.0, 0.0, 1.0, 64, 0.5)                        # ... the temperature alone
     assert c.writes == [0] and s.rows[1][0] == (0.7,) * K
     c.check_mirror()
     # refusals write nothing
     del c.writes[:]
-    before = (s.typical.clone(), list(s.typical_rows), list(s.rows))
+    before = (s.params[6].clone(), list(s.rows))
     for bad in (0.0, 1.01, NAN, True, "1", [0.5] * (K + 1), [0.5, 0.5, 0.5, -1]):
         with pytest.raises(ValueError, match="typical_p"):
             s.write(1, 4, *SIX, bad)
@@ -158,10 +156,10 @@ def test_row_sampler_level_4():
         s.write(1, 4, 0.0, 50, 1.0, 0.0, 1.0, 64, 0.5)
     with pytest.raises(ValueError, match="out of range"):
         s.write(3, 4, *SIX, 0.5)
-    assert c.writes == [] and torch.equal(s.typical, before[0]) and s.typical_rows == before[1] and s.rows == before[2]
+    assert c.writes == [] and torch.equal(s.params[6], before[0]) and s.rows == before[1]
     # the level only rises: a level-3 write on a level-4 state keeps the seventh as it is
     s.write(2, 3, 0.9, 50, 0.8, 0.0, 1.0, 64)
-    assert s.level == 4 and s.typical_rows[2] == per and s.rows[2][2] == (0.8,) * K
+    assert s.level == 4 and s.rows[2][6] == per and s.rows[2][2] == (0.8,) * K
     c.check_mirror()
 
 
@@ -171,7 +169,7 @@ def test_row_sampler_args_rise_straight_to_level_4():
     assert s.args(0.9, 50) == (0.9, 50) and s.level == 0                  # two numbers pass through
     assert s.args(0.9, 50, typical_p=[0.3, 1.0]) == (None, None)
     assert s.level == 4 and s.code_hist.shape == (2, K, 64) and s.hist_frame.tolist() == [0, 0] and s.hist_live.tolist() == [1, 1]
-    assert s.typical.tolist() == [[pytest.approx(0.3), 1.0]] * K and [r[6][0] for r in s.row_typical] == [0.3, 1.0]
+    assert s.params[6].tolist() == [[pytest.approx(0.3), 1.0]] * K and [r[6][0] for r in s.row_typical] == [0.3, 1.0]
     c.check_mirror()
     with pytest.raises(ValueError, match="typical_p must be"):
         s.args(0.9, 50, typical_p=[0.3, 0.0])
@@ -181,7 +179,7 @@ def test_row_sampler_args_rise_straight_to_level_4():
     del c.writes[:]
     assert s.args(0.9, 50, top_p=0.9) == (None, None)                     # beyond a plain pair on a level-4 state: level 4,
     # typical_p at its identity: top_p changes in both rows, typical_p in the row that was not at 1
-    assert s.level == 4 and sorted(c.writes) == [2, 2, 6] and s.typical.tolist() == [[1.0, 1.0]] * K
+    assert s.level == 4 and sorted(c.writes) == [2, 2, 6] and s.params[6].tolist() == [[1.0, 1.0]] * K
     assert s.args(0.9, 50) == (0.9, 50)
 
 
@@ -195,7 +193,7 @@ def test_levels_below_4_are_what_they_were():
     assert s.graph_key(None, None) == (None, None, "filters") and s.row_filters == [(0.9, 0.0)] * 2
     s.write(0, 3, *SIX)
     assert s.graph_key(None, None) == (None, None, "processors") and s.row_processors == [_tup(*SIX)] * 2
-    assert s.typical is None and s.typical_rows is None and s.code_hist is not None
+    assert s.params[6].tolist() == [[1.0] * 2] * K and [r[6] for r in s.rows] == [(1.0,) * K] * 2 and s.code_hist is not None
 
 
 def test_generation_keywords_are_todays_at_typical_p_one():

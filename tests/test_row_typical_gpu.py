@@ -22,7 +22,7 @@ def _probe(srv, ctx, **kw):
 
 def _mirror_equals_buffer(st):
     want = torch.tensor([st.row_typical[b][6] for b in range(st.B)], dtype=torch.float32).t()
-    assert st.sampler.typical.shape == (K, st.B) and torch.equal(st.sampler.typical.cpu(), want)
+    assert st.sampler.params[6].shape == (K, st.B) and torch.equal(st.sampler.params[6].cpu(), want)
     for j, buf in enumerate(st.sampler.params):
         want = torch.tensor([st.row_typical[b][j] for b in range(st.B)], dtype=buf.dtype).t()
         assert torch.equal(buf.cpu(), want), j
@@ -48,7 +48,7 @@ def test_typical_p_one_is_the_row_processors_server(world):
     st = srv_t._state
     assert srv_t.row_typical and srv_t.row_processors and srv_t.row_filters
     assert st.row_typical is not None and st.row_processors is None and st.graph_key == (None, None, "typical")
-    assert st.sampler.level == 4 and st.sampler.typical.shape == (K, 16) and bool((st.sampler.typical == 1.0).all())
+    assert st.sampler.level == 4 and st.sampler.params[6].shape == (K, 16) and bool((st.sampler.params[6] == 1.0).all())
     assert all(r.typical_p == 1.0 for r in got)
     for a, b in zip(got, want):
         _same(a, b)
@@ -169,12 +169,12 @@ def test_a_change_of_typical_p_replays_the_same_graph_and_per_codebook_values_re
         srv.step()
         want = tuple(ty) if isinstance(ty, list) else (ty,) * K
         assert st.graph is graph and st.graph_key == key and reqs[-1].slot == i + 1 and st.row_typical[i + 1][6] == want
-        assert st.sampler.typical[:, i + 1].cpu().tolist() == pytest.approx(list(want))
+        assert st.sampler.params[6][:, i + 1].cpu().tolist() == pytest.approx(list(want))
         if graph is not None:
             assert key == (None, None, "typical")
     st.set_row_typical(0, 0.7, 8, 1.0, 0.0, 1.0, 64, per)                            # ... and written straight to a running row
     srv.step()
-    assert st.graph is graph and st.sampler.typical[:, 0].cpu().tolist() == pytest.approx(per)
+    assert st.graph is graph and st.sampler.params[6][:, 0].cpu().tolist() == pytest.approx(per)
     _mirror_equals_buffer(st)
     _finish(srv)
     assert st.graph is graph and all(r.done for r in reqs)
@@ -202,7 +202,7 @@ def test_a_change_of_typical_p_replays_the_same_graph_and_per_codebook_values_re
         s3.sampler.need(4)
     assert s3.sampling_args(0.8, 5, typical_p=[0.9, per, 1.0]) == (None, None)
     assert [r[6] for r in s3.row_typical] == [(0.9,) * K, tuple(per), (1.0,) * K] and s3.row_processors is None
-    assert s3.sampler.typical[:, 1].cpu().tolist() == pytest.approx(per)
+    assert s3.sampler.params[6][:, 1].cpu().tolist() == pytest.approx(per)
     with pytest.raises(ValueError, match="typical_p must be"):
         s3.sampling_args(0.8, 5, typical_p=[0.9, 0.0, 1.0])
     assert [r[6][0] for r in s3.row_typical] == [0.9, 0.25, 1.0]                       # (all checked before any is written)

@@ -1,5 +1,5 @@
 """The one per-row sampler state of a ``DecodeState`` on the GPU (csm/sampling.py, ``RowSampler``), on the tiny model of
-tests/test_row_sampling_gpu.py with three rows: a state raised from level 1 to 2 to 3 at identity extras draws, level by level, the
+tests/test_row_sampling_gpu.py with three rows: a state raised from level 1 to 2 to 3 to 4 at identity extras draws, level by level, the
 codes the scalar path draws for each row's pair; the write that raises a level reaches every row, later ones one row; each level
 has its graph key and a parameter write replays the same captured graph.  Codes are compared with torch.equal."""
 import pytest
@@ -11,8 +11,9 @@ PAIRS = [(0.8, 12), (0.6, 1), (1.2, 200)]           # (the one-wave and the bloc
 IDENTITY = (1.0, 0.0, 1.0, 64)                      # top_p, min_p, penalty, window: a higher level that changes nothing
 RAISE = {1: lambda st, b, t, k: st.set_row_sampling(b, t, k),
          2: lambda st, b, t, k: st.set_row_filters(b, 1.0, 0.0),
-         3: lambda st, b, t, k: st.set_row_processors(b, t, k, *IDENTITY)}
-KEYS = {1: (None, None), 2: (None, None, "filters"), 3: (None, None, "processors")}
+         3: lambda st, b, t, k: st.set_row_processors(b, t, k, *IDENTITY),
+         4: lambda st, b, t, k: st.set_row_typical(b, t, k, *IDENTITY, 1.0)}
+KEYS = {1: (None, None), 2: (None, None, "filters"), 3: (None, None, "processors"), 4: (None, None, "typical")}
 
 
 @pytest.fixture(scope="module")
@@ -50,16 +51,19 @@ def test_a_higher_level_at_identity_is_the_lower_levels_draw(world):
     scalar = [e._frame_tail(st, last_h, t, k, noise) for t, k in PAIRS]     # [B, K] each: every row with pair b
     want = torch.stack([scalar[b][b] for b in range(B)])
     assert st.sampler.level == 0 and st.graph_key is None and not torch.equal(scalar[0][1], scalar[1][1])
-    for level in (1, 2, 3):
+    for level in (1, 2, 3, 4):
         for b, (t, k) in enumerate(PAIRS):
             RAISE[level](st, b, t, k)
         assert st.sampler.level == level
         _mirror_is_buffers(st)
-        assert st.sampler.rows == [((t,) * K, (k,) * K) + tuple((v,) * K for v in IDENTITY) for t, k in PAIRS]
+        assert st.sampler.rows == [((t,) * K, (k,) * K) + tuple((v,) * K for v in IDENTITY + (1.0,)) for t, k in PAIRS]
         got = e._frame_tail(st, last_h, None, None, noise)
         assert got.shape == (B, K) and torch.equal(got, want), level
-    assert st.row_processors is not None and st.sampler.hist_frame.tolist() == [1] * B      # (the level-3 frame was counted)
-    assert torch.equal(st.sampler.code_hist[:, :, 0], want)
+        if level == 3:
+            assert st.row_processors is not None and st.sampler.hist_frame.tolist() == [1] * B      # (the level-3 frame was counted)
+            assert torch.equal(st.sampler.code_hist[:, :, 0], want)
+    assert st.row_typical is not None and st.row_processors is None and st.sampler.hist_frame.tolist() == [2] * B
+    assert torch.equal(st.sampler.code_hist[:, :, 1], want)                 # (... and the level-4 frame, in the same rings)
 
 
 def test_the_write_that_raises_a_level_reaches_every_row(world):
@@ -82,9 +86,16 @@ def test_the_write_that_raises_a_level_reaches_every_row(world):
     st.set_row_processors(2, 0.7, 20, 0.9, 0.05, 1.3, 16)                   # ... and a later one its own row only
     assert st.row_processors[:2] == [row0] * 2 and st.row_processors[2][0] == (0.7,) * K and st.row_processors[2][5] == (16,) * K
     _mirror_is_buffers(st)
+    per = tuple([0.5] + [0.9] * (K - 1))
+    st.set_row_typical(1, *six, list(per))                                  # level 4: the seven reach every row ...
+    assert st.row_typical == [row0 + (per,)] * B and st.row_processors is None
+    _mirror_is_buffers(st)
+    st.set_row_typical(0, *six, 0.25)                                       # ... and a later one its own row only
+    assert st.row_typical[0] == row0 + ((0.25,) * K,) and st.row_typical[1:] == [row0 + (per,)] * 2
+    _mirror_is_buffers(st)
 
 
-@pytest.mark.parametrize("level", [1, 2, 3])
+@pytest.mark.parametrize("level", [1, 2, 3, 4])
 @torch.no_grad()
 def test_each_level_has_its_graph_key_and_a_write_replays_the_same_graph(world, level):
     from csm.engine import DecodeState
@@ -115,6 +126,8 @@ def test_each_level_has_its_graph_key_and_a_write_replays_the_same_graph(world, 
                     st.set_row_filters(1, 0.7, 0.01)
                 if level == 3:
                     st.set_row_processors(1, 1.1, 65, 0.7, 0.01, 1.5, 2)
+                if level == 4:
+                    st.set_row_typical(1, 1.1, 65, 0.7, 0.01, 1.5, 2, 0.6)
                 _mirror_is_buffers(st)
         assert st.graph is captured and st.sampler.level == level
         if graph:

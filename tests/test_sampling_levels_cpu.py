@@ -17,11 +17,12 @@ def _all(v):
     return (v,) * K
 
 
-def _six(t, k, p, m, r, w):
-    return tuple(v if v is None or isinstance(v, tuple) else _all(v) for v in (t, k, p, m, r, w))
+def _six(t, k, p, m, r, w, y=None):
+    """A row as ``normalise`` gives it: the six and ``typical_p``, which no case below names (None: left as it is)."""
+    return tuple(v if v is None or isinstance(v, tuple) else _all(v) for v in (t, k, p, m, r, w, y))
 
 
-# (what the call names, the level it needs, per row the six entries - None: left as it is)
+# (what the call names, the level it needs, per row the entries - None: left as it is)
 ACCEPTED = [
     (dict(temperature=0.9, topk=50), 0, None),
     (dict(temperature=None, topk=None), 0, None),
@@ -82,6 +83,8 @@ def Recording(level=0):
         s.write(0, 2, 0.95, 0.02)
     if level >= 3:
         s.write(0, 3, 0.5, 9, 0.95, 0.02, 1.1, 8)
+    if level >= 4:
+        s.write(0, 4, 0.5, 9, 0.95, 0.02, 1.1, 8, 0.9)
     del s.puts[:]
     return s
 
@@ -115,7 +118,7 @@ def test_every_refusal_has_its_text_and_nothing_is_written(case):
         normalise(B, K, VOCAB, **kw)
     with pytest.raises(ValueError, match=re.escape(text.replace("per row", "per utterance"))):
         normalise(B, K, VOCAB, unit="utterance", **kw)
-    for level in (0, 1, 2, 3):
+    for level in (0, 1, 2, 3, 4):
         s = Recording(level)
         before = (s.level, None if s.rows is None else list(s.rows), None if s.params is None else [p.clone() for p in s.params])
         with pytest.raises(ValueError):
@@ -126,11 +129,13 @@ def test_every_refusal_has_its_text_and_nothing_is_written(case):
 
 
 def test_the_writers_check_before_they_write():
-    for level in (0, 1, 2, 3):
+    for level in (0, 1, 2, 3, 4):
         s = Recording(level)
         for call in (lambda: s.write(1, 1, 0.0, 5), lambda: s.write(1, 1, 0.9, VOCAB + 1), lambda: s.write(1, 2, 1.5, 0.0),
                      lambda: s.write(1, 3, 0.9, 5, 1.0, 0.0, 1.3, 65), lambda: s.write(1, 3, ACOUSTIC[:3], 5, 1.0, 0.0, 1.3, 16),
-                     lambda: s.write(B, 1, 0.9, 5), lambda: s.write(-1, 3, 0.9, 5, 1.0, 0.0, 1.3, 16)):
+                     lambda: s.write(B, 1, 0.9, 5), lambda: s.write(-1, 3, 0.9, 5, 1.0, 0.0, 1.3, 16),
+                     lambda: s.write(1, 4, 0.9, 5, 1.0, 0.0, 1.3, 16, 0.0), lambda: s.write(1, 4, 0.9, 5, 1.0, 0.0, 1.3, 16, ACOUSTIC[:3]),
+                     lambda: s.write(B, 4, 0.9, 5, 1.0, 0.0, 1.3, 16, 0.9)):
             with pytest.raises(ValueError):
                 call()
         assert s.puts == [] and s.level == level
@@ -140,6 +145,24 @@ def test_the_writers_check_before_they_write():
     with pytest.raises(RuntimeError, match="set_row_sampling first"):
         s.args(None, None, top_p=0.9)
     assert s.puts == [] and s.level == 0 and s.params is None
+
+
+def test_the_two_tables_are_coherent():
+    from csm import sampling as S
+    from csm.hip import ops
+    assert len(S.LEVELS) == 5 and tuple(lv.reads for lv in S.LEVELS) == (0, 2, 4, 6, 7) and len(S.PARAMS) == S.LEVELS[-1].reads
+    for n, lv in enumerate(S.LEVELS):
+        assert set(lv.writes) <= set(range(lv.reads)), n                   # a level writes only what its kernel reads
+        assert (lv.fn is None and lv.flag is None and lv.first is None) if n == 0 else (
+            callable(getattr(ops, lv.fn)) and lv.flag.startswith("row_") and lv.first.endswith(f"call set_{lv.flag} first")), n
+    assert S.LEVELS[0].writes == () and S.LEVELS[0].tag is None and [lv.rings for lv in S.LEVELS] == [False, False, False, True, True]
+    assert S.PROCESSOR_NAMES == ("temperature", "topk", "top_p", "min_p", "repetition_penalty", "repetition_window")
+    assert S.DTYPES == (torch.float32, torch.int32, torch.float32, torch.float32, torch.float32, torch.int32)
+    assert S.IDENTITY == (1.0, 1, 1.0, 0.0, 1.0, 64) and S.HIST_FRAMES == 64
+    assert tuple(p.name for p in S.PARAMS) == S.PROCESSOR_NAMES + ("typical_p",) and S.PARAMS[6].identity == 1.0
+    for j, p in enumerate(S.PARAMS):                                       # the identity passes its own rule, at its position
+        got = S.check_row(K, VOCAB, range(len(S.PARAMS)), [q.identity for q in S.PARAMS])[j]
+        assert got == _all(p.identity) and type(got[0]) is (float if p.dtype.is_floating_point else int), p.name
 
 
 def _mirror_is_buffers(s):
@@ -176,7 +199,7 @@ def test_the_write_that_raises_the_level_gives_its_values_to_every_row():
         s.reset_history(0)
     assert s.hist_live is None
     s.write(0, 3, ACOUSTIC, 9, 0.9, 0.0, 1.3, 16)
-    assert s.row_processors == [_six(tuple(ACOUSTIC), 9, 0.9, 0.0, 1.3, 16)] * B and s.row_sampling is None and s.row_filters is None
+    assert s.row_processors == [_six(tuple(ACOUSTIC), 9, 0.9, 0.0, 1.3, 16)[:6]] * B and s.row_sampling is None and s.row_filters is None
     assert s.graph_key(None, None) == (None, None, "processors")
     assert s.code_hist.shape == (B, K, 64) and s.hist_frame.tolist() == [0] * B and s.hist_live.tolist() == [1] * B
     del s.puts[:]
