@@ -93,6 +93,10 @@ def parse_args(argv=None):
                         "among --lora-adapter and the lines) and submit every line with its voice instead of the context - no "
                         "Mimi encode and no prefill of the context per line; conversations start from the voice")
     p.add_argument("--slots", type=int, default=16, help="--serve-file: utterances decoded at once (1..16, default 16)")
+    p.add_argument("--streams", type=int, default=None, metavar="N",
+                   help="--serve-file: keep up to N (--slots..256) utterances in flight over the --slots rows "
+                        "(Generator.serve(streams=N)): each step gives the rows to the utterances with the least audio so far and "
+                        "parks the others mid-utterance.  No pacing: the audio goes to files")
     p.add_argument("--hear-slots", type=int, default=0,
                    help="--serve-file: encoder slots of the server's batched hearing (Generator.serve(hear_slots=N), 0..16; "
                         "default 0: every conversation that hears has its own encode stream)")
@@ -110,6 +114,10 @@ def parse_args(argv=None):
         p.error("--slots must be 1..16")
     if not 0 <= args.hear_slots <= 16:
         p.error("--hear-slots must be 0..16")
+    if args.streams is not None and args.serve_file is None:
+        p.error("--streams goes with --serve-file")
+    if args.streams is not None and not args.slots <= args.streams <= 256:
+        p.error("--streams must be --slots..256")
     if args.hear_slots and args.serve_file is None:
         p.error("--hear-slots goes with --serve-file")
     if args.cache_context and (args.serve_file is None or not args.context_audio):
@@ -409,7 +417,7 @@ def serve_to_wavs(generator, args, context, adapter=None):
     t0 = time.perf_counter()
     voices = serve_voices(generator, lines, context, adapter) if args.cache_context else None     # (the adapters are loaded)
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, hear_slots=args.hear_slots,
-                             **serve_lines(lines, args, K), **out_rate_kw(args))
+                             **serve_lines(lines, args, K), **out_rate_kw(args), **({"streams": args.streams} if args.streams else {}))
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
     def say(cid):
@@ -430,7 +438,7 @@ def serve_to_wavs(generator, args, context, adapter=None):
             convs[cid] = [server.conversation(adapter=ln["adapter"] or adapter, seed=ln["seed"], on_overflow=args.on_overflow,
                                               keep_turns=args.keep_turns, **line_prompt(ln, context, voices, adapter)), [i]]
             say(cid)
-    while server.queued or server.active:
+    while server.queued or server.active or (args.streams and server.in_flight):     # (--streams: parked requests hold no slot)
         for req, _, done in server.step():
             if done:
                 i, cid = line_of[req]

@@ -290,11 +290,12 @@ class MimiCodec:
         steps equal ``decode`` of all the frames, bit for bit."""
         return MimiDecodeStream(self, max_chunk_frames)
 
-    def decode_stream_rows(self, slots: int = 16, max_chunk_frames: int = 32) -> "MimiDecodeStreamRows":
+    def decode_stream_rows(self, slots: int = 16, max_chunk_frames: int = 32, state_slots=None) -> "MimiDecodeStreamRows":
         """``decode_stream`` for up to ``slots`` (<= 16) utterances that join and leave independently: ``open(slot)`` starts one,
         ``step(slots, codes [R,K,n])`` returns the next n frames' audio of R of them ([R, n * 1920]) from one launch per op.  Every
-        slot's concatenated chunks equal ``decode`` of its frames, bit for bit."""
-        return MimiDecodeStreamRows(self, slots, max_chunk_frames)
+        slot's concatenated chunks equal ``decode`` of its frames, bit for bit.  ``state_slots`` (>= slots; None: ``slots``): how
+        many streams keep a state - slot indices then run over 0 .. state_slots - 1 and a ``step`` still takes at most ``slots``."""
+        return MimiDecodeStreamRows(self, slots, max_chunk_frames, state_slots)
 
 
 class MimiEncodeStream:
@@ -645,14 +646,22 @@ class MimiDecodeStreamRows:
     equal ``MimiDecodeStream.step``'s and ``MimiCodec.decode``'s, bit for bit, whatever its neighbours do.
     State per slot: both history buffers of every conv layer ([slots, 2, C_in, H]), a K/V ring of
     ``window + 2 * max_chunk_frames - 1`` rows per transformer layer, the frames decoded so far and the parity.
-    ``step`` makes no host synchronisation: slots, parities and positions reach the kernels by value."""
+    ``step`` makes no host synchronisation: slots, parities and positions reach the kernels by value.
+    ``state_slots`` >= slots sizes the arenas for more streams than a launch has rows (the kernels take the arena's slot count
+    apart from the rows of a launch): slot indices run over 0 .. state_slots - 1, a ``step`` takes at most ``slots`` of them."""
 
-    def __init__(self, codec: MimiCodec, slots: int = 16, max_chunk_frames: int = 32):
+    def __init__(self, codec: MimiCodec, slots: int = 16, max_chunk_frames: int = 32, state_slots: Optional[int] = None):
         if not 1 <= slots <= 16:
             raise ValueError(f"slots must be 1..16 (the rows kernels take at most 16 rows a launch), got {slots}")
         if max_chunk_frames < 1:
             raise ValueError("max_chunk_frames must be >= 1")
+        if state_slots is not None and (isinstance(state_slots, bool) or int(state_slots) != state_slots or state_slots < slots):
+            raise ValueError(f"state_slots must be an integer >= slots = {slots} (None: one state per row of a launch), got {state_slots!r}")
         self.codec, self.slots, self.max_chunk_frames = codec, slots, max_chunk_frames
+        # the streams that keep a state here: ``slots`` of them, or - more streams than rows of a launch - ``state_slots``; a
+        # stream then keeps its slot for its whole life, whichever rows it is stepped with, and nothing is ever copied
+        self.state_slots = slots if state_slots is None else int(state_slots)
+        slots = self.state_slots
         dev, w = codec.dev, codec.w
         self.hist = {}
         for name, kind, k, stride, _ in decoder_conv_layers(codec.ratios):
@@ -668,8 +677,8 @@ class MimiDecodeStreamRows:
 
     def open(self, slot: int):
         """Start a new utterance in ``slot`` (also after an earlier one ended there)."""
-        if not 0 <= slot < self.slots:
-            raise ValueError(f"slot {slot} out of range (0..{self.slots - 1})")
+        if not 0 <= slot < self.state_slots:
+            raise ValueError(f"slot {slot} out of range (0..{self.state_slots - 1})")
         for arena in self.hist.values():
             if arena is not None:
                 arena[slot].zero_()
@@ -705,8 +714,8 @@ class MimiDecodeStreamRows:
         cd = self.codec
         rows = [int(s) for s in slots]
         R = len(rows)
-        if not 1 <= R <= self.slots or len(set(rows)) != R or any(not 0 <= s < self.slots for s in rows):
-            raise ValueError(f"step takes 1..{self.slots} distinct slots in 0..{self.slots - 1}, got {rows}")
+        if not 1 <= R <= self.slots or len(set(rows)) != R or any(not 0 <= s < self.state_slots for s in rows):
+            raise ValueError(f"step takes 1..{self.slots} distinct slots in 0..{self.state_slots - 1}, got {rows}")
         if codes.dim() != 3 or codes.shape[0] != R:
             raise ValueError(f"codes must be [R = {R}, K, n], got {tuple(codes.shape)}")
         K, n = codes.shape[1], codes.shape[2]

@@ -117,9 +117,10 @@ class Resampler:
         """A stateful stream; ``max_in``: the most samples one launch takes (longer pieces are fed in several; default 1 s)."""
         return ResampleStream(self, self.orig_sr if max_in is None else max_in)
 
-    def stream_rows(self, slots: int = 16, max_in: int = None) -> "ResampleStreamRows":
-        """Up to 16 streams advanced by one launch per step, each in its own slot."""
-        return ResampleStreamRows(self, slots, self.orig_sr if max_in is None else max_in)
+    def stream_rows(self, slots: int = 16, max_in: int = None, state_slots: int = None) -> "ResampleStreamRows":
+        """Up to 16 streams advanced by one launch per step, each in its own slot.  ``state_slots`` (>= slots): that many streams
+        keep a carry, slot indices run over all of them, and a step still takes at most ``slots``."""
+        return ResampleStreamRows(self, slots, self.orig_sr if max_in is None else max_in, state_slots)
 
 
 def _check_max_in(max_in):
@@ -177,18 +178,24 @@ class ResampleStreamRows:
     the samples seen.  ``step`` advances R of them with ONE launch (csm_resample_stream_rows_f32) - each row with its own piece,
     of its own length - and a row's outputs are those of a ``ResampleStream`` fed the same pieces, whatever its neighbours do."""
 
-    def __init__(self, rs: Resampler, slots: int = 16, max_in: int = 24000):
+    def __init__(self, rs: Resampler, slots: int = 16, max_in: int = 24000, state_slots: int = None):
         if isinstance(slots, bool) or not isinstance(slots, int) or not 1 <= slots <= 16:
             raise ValueError(f"slots must be 1..16 (the rows kernel takes at most 16 rows a launch), got {slots!r}")
+        if state_slots is not None and (isinstance(state_slots, bool) or not isinstance(state_slots, int) or state_slots < slots):
+            raise ValueError(f"state_slots must be an integer >= slots = {slots} (None: one carry per row of a launch), got {state_slots!r}")
         self.rs, self.slots, self.max_in = rs, slots, _check_max_in(max_in)
+        # more streams than rows of a launch: the arena holds ``state_slots`` carries, slot indices run over all of them and a
+        # step still takes at most ``slots``; a stream keeps its slot for its whole life, so no carry is ever copied
+        self.state_slots = slots if state_slots is None else state_slots
+        slots = self.state_slots
         self._arena = torch.zeros(slots, 2, rs.T - 1, dtype=F32, device=rs.device)
         self.pos = [0] * slots
         self._par = [0] * slots
         self._live = [False] * slots
 
     def _slot(self, slot):
-        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.slots:
-            raise ValueError(f"slot {slot!r} out of range (0..{self.slots - 1})")
+        if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.state_slots:
+            raise ValueError(f"slot {slot!r} out of range (0..{self.state_slots - 1})")
         return slot
 
     def open(self, slot: int):
@@ -203,7 +210,7 @@ class ResampleStreamRows:
 
     @property
     def open_slots(self) -> List[int]:
-        return [s for s in range(self.slots) if self._live[s]]
+        return [s for s in range(self.state_slots) if self._live[s]]
 
     @torch.no_grad()
     def step(self, slots: Sequence[int], xs: Sequence[torch.Tensor], final: Sequence[int] = ()) -> List[torch.Tensor]:

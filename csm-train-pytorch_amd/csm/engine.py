@@ -1260,6 +1260,16 @@ def _prime_graph_rng(device):
     _graph_rng_primed = g
 
 
+class ParkedRow:
+    """What ``DecodeState.park_rows`` takes out of one row in the middle of an utterance and ``resume_rows`` puts back into any
+    row: ``kv`` - the row's K / V in ``park_row``'s format, all the positions it held; ``hist`` - int32 [K * 64 + 1], its ring of
+    sampled codes and its frame counter (None below the levels that keep rings); ``gen`` - its noise generator (None: unseeded)."""
+    __slots__ = ("kv", "hist", "gen")
+
+    def __init__(self, kv, hist, gen):
+        self.kv, self.hist, self.gen = kv, hist, gen
+
+
 class DecodeState:
     """Everything ``generate_frame`` keeps between calls: the two stacks' caches and small persistent buffers."""
 
@@ -1514,6 +1524,43 @@ class DecodeState:
         ops.kv_fork_rows([p.contiguous() for p in parkeds], kv, self.bb.pos, rows)
         for b, parked in zip(rows, parkeds):
             self.row_pos[b] = parked.shape[3] - 1
+
+    def park_rows(self, rows):
+        """Take up to 16 distinct prefilled rows out of the batch in the middle of their utterances: one ``ParkedRow`` each - the
+        K / V of all ``row_pos[b] + 1`` positions the row holds (ONE ``ops.kv_park_rows`` launch for all rows, ``park_row``'s
+        format), at the levels that keep rings the row's ring of sampled codes and its frame counter (ONE
+        ``ops.sample_hist_move_rows`` launch, a slice of one packed buffer), and the row's noise generator, which leaves
+        ``row_gen``.  The caches, positions and rings are only read: the rows stay as they are until something else is written
+        there.  Adapter, sampling parameters and the last sampled frame are the caller's to keep."""
+        rows = [int(b) for b in rows]
+        R = len(rows)
+        if not 1 <= R <= 16:
+            raise ValueError(f"park_rows takes 1..16 rows, got {R}")
+        if len(set(rows)) != R or any(not 0 <= b < self.B for b in rows):
+            raise ValueError(f"park_rows: rows must be distinct rows of 0..{self.B - 1}, got {rows}")
+        if any(self.row_pos[b] < 0 for b in rows):
+            raise ValueError(f"park_rows: row {next(b for b in rows if self.row_pos[b] < 0)} holds nothing")
+        kvs = ops.kv_park_rows(self.bb.kv, rows, [self.row_pos[b] + 1 for b in rows])
+        packed = self.sampler.park_history(rows)
+        return [ParkedRow(kv, None if packed is None else packed[r], self.row_gen.pop(b, None)) for r, (b, kv) in enumerate(zip(rows, kvs))]
+
+    def resume_rows(self, rows, parked):
+        """``park_rows``' results into the rows ``rows`` (any rows, of this or another state of the same model at the same
+        level): ONE ``fork_rows`` for the K / V, the device positions and the host mirrors; at the levels that keep rings ONE
+        ring move towards the state, which restores the rows' frame counters; the generators through ``set_row_seed(generator=)``
+        (a row parked without one returns to the whole-buffer draw).  No buffer a captured frame reads changes address and the
+        level does not move: nothing recaptures."""
+        rows, parked = [int(b) for b in rows], list(parked)
+        if len(parked) != len(rows):
+            raise ValueError(f"resume_rows: {len(parked)} parked rows for {len(rows)} rows")
+        if self.sampler.keeps_history and any(p.hist is None for p in parked):
+            raise ValueError("resume_rows: a row parked without its ring of sampled codes (a state below the processed level) "
+                             "into a state that keeps rings")
+        self.fork_rows(rows, [p.kv for p in parked])
+        if self.sampler.keeps_history:
+            self.sampler.resume_history(rows, torch.stack([p.hist for p in parked]))
+        for b, p in zip(rows, parked):
+            self.set_row_seed(b, None, generator=p.gen)
 
     def shift_parked(self, parked, keep: int, drop: int):
         """A parked history (``park_row``) without its positions ``keep .. keep+drop-1``: a new tensor of ``length - drop``

@@ -410,7 +410,8 @@ class Generator:
     def serve(self, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
               row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
               output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
-              repetition_window=64, row_typical: bool = False, typical_p=1.0):
+              repetition_window=64, row_typical: bool = False, typical_p=1.0, streams: Optional[int] = None,
+              max_lead_ms: Optional[float] = None, clock=None, sleep=None):
         """A running batch (csm/serving.py): ``server.submit(text, speaker, context, adapter=None, seed=None,
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
@@ -437,10 +438,17 @@ class Generator:
         ``feed``; N >= 1 gives the server one rows encoder of N slots - ``feed`` only buffers, ``server.hear_step()`` (called by
         ``step()``) encodes all open heard turns in one batched step, ``server.end_heard([(turn, text), ...])`` ends several.
         ``output_sample_rate``: the rate of every chunk and of ``Request.audio()`` (None: the codec's 24 kHz); the server then keeps
-        one rows resampler over its slots - one more launch per ``step()``.  ``conv.hear(speaker, sample_rate=)`` is the input side."""
+        one rows resampler over its slots - one more launch per ``step()``.  ``conv.hear(speaker, sample_rate=)`` is the input side.
+        ``streams=N`` (slots <= N <= 256; None: today's server): up to N requests are in flight over the ``slots`` rows - every
+        ``step()`` gives the rows to the requests whose listeners have the least audio ahead of them and parks the others in
+        the middle of their utterances (one launch out, one in; the module docstring's "More listeners than slots"), with the
+        same codes and audio per seeded request.  ``max_lead_ms``: a request that far ahead of its listener's clock is not
+        scheduled (``clock`` / ``sleep``: ``time.monotonic`` / ``time.sleep`` unless given; all three need ``streams``).  It
+        adds ``req.pause()`` / ``req.resume()``; ``server.cancel(req, heard_frames=None)`` works on every server."""
         from .serving import BatchServer
         return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p,
-                           output_sample_rate, row_processors, repetition_penalty, repetition_window, row_typical, typical_p)
+                           output_sample_rate, row_processors, repetition_penalty, repetition_window, row_typical, typical_p,
+                           streams, max_lead_ms, clock, sleep)
 
     def voice(self, context: List[Segment], adapter: Optional[str] = None):
         """A voice prompt prefilled ONCE (csm/conversation.py: ``Voice``): the segments are tokenised and Mimi-encoded as every

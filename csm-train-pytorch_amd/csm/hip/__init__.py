@@ -99,6 +99,8 @@ _SIGS = {
     "csm_kv_append": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_kv_shift": ([_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_kv_fork_rows": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
+    "csm_kv_park_rows": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
+    "csm_sample_hist_move_rows": ([_p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "csm_attn_decode": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_sample_topk": ([_p, _p, _p, _i, _i, _i, _i, _f, _p], _i),
     "csm_sample_topk_rows": ([_p, _p, _p, _i, _i, _i, _p, _p, _p], _i),

@@ -737,6 +737,39 @@ def kv_fork_rows(parkeds, kv, pos, rows):
                                arr(*[p.shape[3] for p in parkeds]), R, layers, B, KV, HD, S_max, _stream()), "csm_kv_fork_rows")
 
 
+def kv_park_rows(kv, rows, lens):
+    """The mirror of ``kv_fork_rows``: positions ``0 .. lens[r] - 1`` of batch rows ``rows[r]`` (R <= 16, distinct) of the cache
+    allocation ``kv`` [layers, 2, B, KV, S_max, HD] as R new contiguous tensors [layers, 2, KV, lens[r], HD] - ``DecodeState.
+    park_row``'s format - by ONE launch (csm_kv_park_rows), the table in the kernel arguments.  ``kv`` is only read."""
+    rows, lens = [int(b) for b in rows], [int(n) for n in lens]
+    R = len(rows)
+    if len(lens) != R:
+        raise CsmHipError(f"csm_kv_park_rows failed (code 1): {len(lens)} lengths for {R} rows")
+    assert kv.dim() == 6 and kv.shape[1] == 2 and kv.dtype == BF16 and kv.is_contiguous()
+    layers, _, B, KV, S_max, HD = kv.shape
+    outs = [torch.empty(layers, 2, KV, max(n, 0), HD, dtype=BF16, device=kv.device) for n in lens]
+    ptr, arr = ctypes.c_void_p * max(R, 1), ctypes.c_int * max(R, 1)
+    check(lib.csm_kv_park_rows(ptr(*[o.data_ptr() for o in outs]), kv.data_ptr(), arr(*rows), arr(*lens), R, layers, B, KV, HD,
+                               S_max, _stream()), "csm_kv_park_rows")
+    return outs
+
+
+def sample_hist_move_rows(code_hist, hist_frame, packed, rows, to_state):
+    """The rings ``code_hist[rows[r]]`` (int32 [K, 64] of [B, K, 64]) and counters ``hist_frame[rows[r]]`` of R <= 16 distinct
+    rows against row r of ``packed`` int32 [R, K * 64 + 1], by ONE launch (csm_sample_hist_move_rows): ``to_state`` False reads
+    the state and writes ``packed``, True reads ``packed`` and writes only the named rows.  Returns ``packed``."""
+    rows = [int(b) for b in rows]
+    R = len(rows)
+    assert code_hist.dim() == 3 and code_hist.dtype == torch.int32 and code_hist.is_contiguous()
+    B, K, H = code_hist.shape
+    assert hist_frame.dtype == torch.int32 and hist_frame.shape == (B,) and hist_frame.is_contiguous()
+    assert packed.dtype == torch.int32 and packed.shape == (R, K * H + 1) and packed.is_contiguous() and packed.device == code_hist.device
+    arr = ctypes.c_int * max(R, 1)
+    check(lib.csm_sample_hist_move_rows(code_hist.data_ptr(), hist_frame.data_ptr(), packed.data_ptr(), arr(*rows), R, B, K,
+                                        int(bool(to_state)), _stream()), "csm_sample_hist_move_rows")
+    return packed
+
+
 def attn_decode(qkv, kcache, vcache, out, pos_i32, H, KV, HD):
     B, _, S_max, _ = kcache.shape
     check(lib.csm_attn_decode(qkv.data_ptr(), kcache.data_ptr(), vcache.data_ptr(), out.data_ptr(), pos_i32.data_ptr(), B, H, KV,

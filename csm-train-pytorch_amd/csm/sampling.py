@@ -355,6 +355,22 @@ class RowSampler:
         self.need(FULL_LEVEL)
         self.hist_frame[int(b):int(b) + 1].zero_()
 
+    def park_history(self, rows):
+        """The rings and frame counters of ``rows`` (<= 16, distinct) as one packed int32 tensor [R, K * 64 + 1] - ONE launch
+        (``ops.sample_hist_move_rows``); None below the levels that keep rings.  The state is only read."""
+        if not self.keeps_history:
+            return None
+        from .hip import ops
+        packed = torch.empty(len(rows), self.K * HIST_FRAMES + 1, dtype=torch.int32, device=self.device)
+        return ops.sample_hist_move_rows(self.code_hist, self.hist_frame, packed, rows, False)
+
+    def resume_history(self, rows, packed):
+        """``packed`` (``park_history``'s format, row r for ``rows[r]``) back into the named rows' rings and counters - ONE
+        launch; the counters are restored, not reset.  The buffers keep their addresses, the level and ``hist_live`` stay."""
+        self.need(FULL_LEVEL)
+        from .hip import ops
+        ops.sample_hist_move_rows(self.code_hist, self.hist_frame, packed.contiguous(), rows, True)
+
     def set_live(self, rows):
         if not self.keeps_history:
             return

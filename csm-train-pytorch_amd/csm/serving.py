@@ -89,6 +89,39 @@ resampler streams (their ``final`` step) before the encoder's flush.  ``serve(ou
 produced audio - a row that ends in that step ends its stream there (``final``), so its last chunk carries the resampler's lag.
 Histories are codes and do not change.
 
+More listeners than slots (``serve(streams=N)``, slots <= N <= 256).  A step makes a stream's audio several times faster than it
+is heard, so a request need not hold its row all the time.  Up to N requests are *in flight*: admitted, not done.  An in-flight
+request owns one codec state (and one resampler carry) from admission to its end - the rows codec objects are made with
+``state_slots=N``, their kernels take the arena's slot count apart from the rows of a launch, so that state is never copied -
+and holds a decode slot only in the steps it is scheduled.  What a row is, in the middle of an utterance: the K / V of the
+``row_pos + 1`` positions it holds, its last sampled frame (``_tok``: sampled, not yet fed), at the ring levels its ring of
+sampled codes and its frame counter, its noise generator, and on the host its adapter, its sampling parameters and its
+counters.  ``DecodeState.park_rows`` takes the device part of up to 16 rows out in ONE launch per kind (``csm_kv_park_rows``,
+``csm_sample_hist_move_rows``) and ``resume_rows`` puts it into any rows (``csm_kv_fork_rows`` and the ring move back); no
+buffer a captured frame reads changes address and the level stays, so a rotation never recaptures.
+The schedule runs at the start of every ``step()``, before the running rows' first frame.  Candidates: the in-flight requests
+that are neither paused nor - under ``max_lead_ms`` - too far ahead, each with its *lead*; and, while fewer than ``streams`` are
+in flight (paused ones count), the queued requests in FIFO order with lead minus infinity.  Lead = the milliseconds of audio
+emitted - fair share, the clock is never read - or, with ``max_lead_ms=L``, that minus the time since ``t0``, the clock at the
+return of the step that delivered the request's first chunk (before it: the emitted milliseconds); only leads below L are
+candidates.  The ``slots`` candidates with the least (lead, id) get the slots: rows that were not chosen leave by ONE
+``park_rows``, chosen parked requests return by ONE ``resume_rows`` - lowest free slot first, in (lead, id) order, with their
+``_tok`` row, adapter and parameters; the ring counters are restored, not reset - chosen new ones go through the admission
+above, and a chosen request that holds a slot stays there.  Resumed rows are running rows of that step.  A row that
+is not scheduled in a step that runs always leaves its slot (an idle frame would overwrite position 1 of its cache): in fair
+share that only happens with more candidates than slots, under ``max_lead_ms`` also to a request that is at or over the bound
+while others run, free slots or not.  With no candidate ``step()`` returns ``[]`` and touches nothing.
+``next_due()``: the seconds until somebody is a candidate (0.0: now; None: nothing in flight or queued, or all paused; never
+less than a millisecond otherwise - at the instant a lead reaches the bound it is not yet below it); ``run()`` sleeps it
+(``sleep`` / ``clock``: ``time.sleep`` / ``time.monotonic`` unless given).  ``req.pause()`` takes a request out of the
+candidates - the next step that runs parks it if it holds a slot - and ``req.resume()`` puts it back.  A seeded request has
+the codes and audio it has without ``streams``, however often and wherever it is parked.  ``Request.state`` / ``preemptions`` /
+``slots_held`` and ``server.stats`` (steps, parks, resumes, launches of each) tell what happened.
+``cancel(req, heard_frames=None)`` - every server, with or without ``streams`` - ends a request wherever it is.  A plain
+request is dropped; a conversation's turn ends as at a length limit with ``min(heard_frames, emitted)`` frames kept (barge-in:
+history and parked cache hold the text and what was heard), taken out of its slot or out of its parked row.  Its codec and
+resampler slots are free at once; the resampler's lag is not flushed.
+
 Limitations: a join stalls the other rows for one whole prefill or append (no chunked prefill); the context audio of a request
 and a conversation's ``add``ed turns are Mimi-encoded at ``submit`` / ``add``, one segment at a time (only ``conv.hear`` encodes
 while the turn is being spoken - and only with ``hear_slots`` batched over the conversations); adapters added to the
@@ -102,6 +135,11 @@ import torch
 from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, hear_resampler, open_heard_turn
 from .engine import DecodeState
 from .sampling import FULL_LEVEL, HIST_FRAMES, LEVELS, NAMES, PARAMS, _as_list, _is_number, check_row, own_params
+
+
+MAX_STREAMS = 256           # the most requests in flight on a ``streams`` server (each keeps a codec state for its whole life)
+FRAME_MS = 80.0             # one frame of audio
+MIN_SLEEP = 1e-3            # ``next_due`` never asks for less: at the exact instant a lead reaches the bound it is not yet below it
 
 
 def _collapsed(vals):
@@ -132,6 +170,33 @@ class Request:
         self.sample_rate: Optional[int] = None   # the rate of ``chunks`` / ``audio()`` (the server's; set when it queues)
         self._base = 0                           # a turn: positions the cache holds once the feed is in
         self._voice = None                       # submit(voice=): the Voice whose K / V the slot gets; tokens / mask: what follows it
+        self.cancelled = False                   # ended by BatchServer.cancel
+        self.preemptions = 0                     # times it was parked in the middle of the utterance (``streams`` servers)
+        self.slots_held: List[int] = []          # every decode slot it has held, in order
+        self._srv = None
+        self._paused = False
+        self._row = None                         # engine.ParkedRow while it is in flight without a slot; _tokrow: its last frame
+        self._tokrow = None
+        self._cslot: Optional[int] = None        # its codec / resampler slot (the decode slot, unless the server has ``streams``)
+        self._t0 = None                          # pacing: the clock when its first chunk was delivered
+
+    @property
+    def state(self) -> str:
+        """``queued`` / ``running`` (it holds a slot) / ``parked`` (in flight, out of its slot) / ``paused`` / ``done``."""
+        if self.done:
+            return "done"
+        if self._paused:
+            return "paused"
+        return "running" if self.slot is not None else "parked" if self._row is not None else "queued"
+
+    def pause(self) -> None:
+        """Take the request out of the schedule (a ``streams`` server): if it holds a slot, the next ``step()`` parks it; a
+        queued one is passed over.  Nothing is lost - ``resume()`` continues with the same codes.  No-op on a done request."""
+        self._srv._pause(self, True)
+
+    def resume(self) -> None:
+        """Put a paused request back into the schedule."""
+        self._srv._pause(self, False)
 
     def audio(self) -> torch.Tensor:
         """The audio so far (all of it once ``done``): the chunks concatenated."""
@@ -320,28 +385,32 @@ class ServedConversation:
         feed_m = torch.cat([self._mask[self._cached:], tm.bool().to(self._mask.device)], 0)
         self._push(tt.long(), tm.bool())
         req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device, *params)
-        req._conv, req._base, req.sample_rate = self, self._tokens.shape[0], srv.sample_rate
+        req._conv, req._base, req.sample_rate, req._srv = self, self._tokens.shape[0], srv.sample_rate, srv
         srv._next_id += 1
         srv._queue.append(req)
         self._open = req
         return req
 
-    def _end_turn(self, req: Request, state, b: int):
+    def _end_turn(self, req: Request, state, b, kept: Optional[int] = None):
         """The turn has ended in slot ``b`` (``BatchServer.step``): the history gets the kept frames and one EOS frame, the cache
-        its history positions only - base + the kept frames that were fed back - which are parked."""
+        its history positions only - base + the kept frames that were fed back - which are parked.  ``kept``
+        (``BatchServer.cancel``): the frames that count, at most those emitted; ``b`` is then the slot, or None for a turn that
+        holds none - a preempted one's positions come out of its parked row, a queued one's parked cache stays as it is."""
         K = self._srv._K
-        k = req._emitted
+        k = req._emitted if kept is None else min(int(kept), req._emitted)
         frames = torch.zeros(k + 1, K + 1, dtype=torch.long, device=self._tokens.device)
         if k:
-            frames[:k, :K] = req.codes().t()
+            frames[:k, :K] = req.codes().t()[:k]
         fmask = torch.zeros(k + 1, K + 1, dtype=torch.bool, device=self._mask.device)
         fmask[:, :K] = True
         self._tokens = torch.cat([self._tokens, frames], 0)
         self._mask = torch.cat([self._mask, fmask], 0)
         self._turns[-1] += k + 1
         # positions base .. base + sampled - 2 hold the frames that were fed back (the last one sampled never was)
+        if b is None and req._row is None:       # (cancelled while queued: nothing of the turn ever reached a cache)
+            return
         self._cached = req._base + min(req._sampled - 1, k)
-        self._parked = state.park_row(b, self._cached)
+        self._parked = state.park_row(b, self._cached) if b is not None else req._row.kv[:, :, :, :self._cached].contiguous()
 
     def close(self) -> None:
         """Drop the parked cache (the history stays readable); a heard turn that holds an encoder slot is cancelled."""
@@ -366,8 +435,21 @@ class BatchServer:
     def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
                  row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
                  output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
-                 repetition_window=HIST_FRAMES, row_typical: bool = False, typical_p=1.0):
+                 repetition_window=HIST_FRAMES, row_typical: bool = False, typical_p=1.0, streams: Optional[int] = None,
+                 max_lead_ms: Optional[float] = None, clock=None, sleep=None):
         out_rs = gen._out_resampler(output_sample_rate)      # (a bad rate raises here, before anything is taken over)
+        if streams is None:
+            for name, v in (("max_lead_ms", max_lead_ms), ("clock", clock), ("sleep", sleep)):
+                if v is not None:
+                    raise ValueError(f"{name} belongs to the schedule of a server with more streams than slots: it needs streams=")
+        else:
+            if isinstance(streams, bool) or not isinstance(streams, int):
+                raise ValueError(f"streams must be an integer in slots..{MAX_STREAMS}, got {streams!r}")
+            if max_lead_ms is not None and (not _is_number(max_lead_ms) or not 0 < float(max_lead_ms) < float("inf")):
+                raise ValueError(f"max_lead_ms must be a finite number > 0 (milliseconds of audio ahead of the listener), got {max_lead_ms!r}")
+            for name, v in (("clock", clock), ("sleep", sleep)):
+                if v is not None and not callable(v):
+                    raise ValueError(f"{name} must be callable, got {v!r}")
         # the level: the highest one asked for (it includes those below); a flag needs row_sampling, a value off its identity its flag
         flags = dict(row_sampling=row_sampling, row_filters=row_filters, row_processors=row_processors, row_typical=row_typical)
         given = (temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p)
@@ -379,6 +461,8 @@ class BatchServer:
                 raise ValueError(LEVELS[n].value.format(**dict(zip(NAMES, given))))
         if int(slots) != slots or not 1 <= slots <= 16:
             raise ValueError(f"slots must be an integer in 1..16, got {slots!r}")
+        if streams is not None and not slots <= streams <= MAX_STREAMS:
+            raise ValueError(f"streams must be an integer in slots..{MAX_STREAMS} (slots = {int(slots)}), got {streams!r}")
         if int(hear_slots) != hear_slots or not 0 <= hear_slots <= 16:
             raise ValueError(f"hear_slots must be an integer in 0..16 (0: one encode stream per conversation), got {hear_slots!r}")
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
@@ -405,9 +489,13 @@ class BatchServer:
         self._model.reset_caches()
         self._model.engine._need()                       # (sharded / offloaded parameters: gathered before anything reads them)
         self._bank = dict(gen._bank.entries) if gen._bank is not None else {}
+        # more streams than slots: a request keeps one codec (and resampler) state from admission to its end, whichever decode
+        # slot it is scheduled into - the arenas are sized to ``streams`` and nothing of them is ever copied
+        self.streams = None if streams is None else int(streams)
+        more = {} if self.streams is None else {"state_slots": self.streams}
         with torch.inference_mode():
             self._state = DecodeState(self._model.engine, self.slots, bank=list(self._bank.values()))
-            self._codec = codec.decode_stream_rows(slots=self.slots, max_chunk_frames=self.chunk_frames)
+            self._codec = codec.decode_stream_rows(slots=self.slots, max_chunk_frames=self.chunk_frames, **more)
         # heard turns: one rows encoder for all conversations (None: each conversation makes its own MimiEncodeStream).  Made
         # outside inference mode: ``conv.hear`` opens its slot (an in-place zero fill of the state) from ordinary caller code
         self._hear = codec.encode_stream_rows(slots=self.hear_slots) if self.hear_slots else None
@@ -417,7 +505,7 @@ class BatchServer:
         self.sample_rate = int(gen.sample_rate) if out_rs is None else out_rs.new_sr
         self._out = None
         if out_rs is not None:
-            self._out = out_rs.stream_rows(self.slots, self.chunk_frames * (int(gen.sample_rate) * 80 // 1000))     # (80 ms frames)
+            self._out = out_rs.stream_rows(self.slots, self.chunk_frames * (int(gen.sample_rate) * 80 // 1000), **more)     # (80 ms frames)
         self._model._decode_state = self._state
         # every row starts with valid parameters (the sampler runs on all rows), the state at its level before the first capture
         self._set_rows(range(self.slots), self._defaults())
@@ -431,6 +519,15 @@ class BatchServer:
         self._queue = deque()
         self._next_id = 0
         self.last_join_rows = 0                          # requests admitted by the latest step (for timing a join)
+        # the schedule of a ``streams`` server: the requests in flight (admitted, not done - running, parked or paused), the codec
+        # slots nobody holds, the pacing bound and its clock
+        self._flight: List[Request] = []
+        self._cfree = list(range(self.streams or 0))
+        self.max_lead_ms = None if max_lead_ms is None else float(max_lead_ms)
+        if self.streams is not None:
+            import time
+            self._clock, self._sleep = clock or time.monotonic, sleep or time.sleep
+        self.stats = {"steps": 0, "parks": 0, "resumes": 0, "park_launches": 0, "resume_launches": 0}
 
     # ------------------------------------------------------------------------------------------------------------ requests
     def _check(self):
@@ -511,7 +608,7 @@ class BatchServer:
                 if voice.positions + tokens.shape[1] >= limit:
                     raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
         req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device, *params)
-        req.sample_rate, req._voice = self.sample_rate, voice
+        req.sample_rate, req._voice, req._srv = self.sample_rate, voice, self
         self._next_id += 1
         self._queue.append(req)
         return req
@@ -657,17 +754,19 @@ class BatchServer:
             for b in rows:
                 self._state.reset_row_history(b)
 
-    def _admit(self):
+    def _admit(self, queue=None):
         """Queued requests into free slots: plain requests and first turns are prefilled one by one, the turns of conversations
         with a parked cache are resumed, the requests with a voice are forked by ONE ``fork_rows``, and those two kinds are fed
-        by ONE ``append_rows``, then one frame tail for all of them.  Returns (their slots, [slots, K])."""
+        by ONE ``append_rows``, then one frame tail for all of them.  Returns (their slots, [slots, K]).  ``queue``: the requests
+        to admit, when the schedule of a ``streams`` server has chosen them (it leaves them a free slot each)."""
         st, joined, resumed, forked, hs = self._state, [], [], [], {}
+        queue = self._queue if queue is None else queue
         for b in range(self.slots):
-            if not self._queue:
+            if not queue:
                 break
             if self._rows[b] is not None:
                 continue
-            req = self._queue.popleft()
+            req = queue.popleft()
             conv = req._conv
             st.set_row_adapter(b, self._bank[req.adapter] if req.adapter is not None else None)
             # (every joining row, resumed turns included: with rings, a turn's window covers its own frames)
@@ -689,10 +788,15 @@ class BatchServer:
                 hs[b] = st.prefill_row(b, req._tokens, req._mask)
             if conv is not None:
                 conv._cached = req._base
-            self._codec.open(b)
+            # its codec / resampler slot: the decode slot - or, with ``streams``, the lowest one nobody holds, kept to its end
+            c = req._cslot = b if self.streams is None else self._cfree.pop(0)
+            self._codec.open(c)
             if self._out is not None:
-                self._out.open(b)
+                self._out.open(c)
             req.slot, self._rows[b] = b, req
+            req.slots_held.append(b)
+            if self.streams is not None:
+                self._flight.append(req)
             joined.append(b)
         if not joined:
             return joined, None
@@ -719,9 +823,16 @@ class BatchServer:
         if self.hear_slots:
             self.hear_step()
         n, K = self.chunk_frames, self._K
+        self.stats["steps"] += 1
+        fresh = None
+        if self.streams is not None:
+            fresh = self._schedule()
+            if fresh is None:                            # nobody is a candidate: nothing runs, nothing is moved
+                self.last_join_rows = 0
+                return []
         running = [b for b in range(self.slots) if self._rows[b] is not None]
         first = self._frame(running) if running else None
-        joined, first_j = self._admit()
+        joined, first_j = self._admit(fresh)
         self.last_join_rows = len(joined)
         if first is None and first_j is None:
             return []
@@ -747,20 +858,21 @@ class BatchServer:
             keep[b] = int(hit[0]) if hit.numel() else valid
             done[b] = bool(hit.numel()) or req._emitted + keep[b] >= req.max_audio_frames
         heard = sorted(b for b in held if keep[b] > 0)
+        cs = {b: self._rows[b]._cslot for b in held}                                 # decode slot -> codec / resampler slot
         audio = None
         if heard:
             # what a row sampled after its EOS frame, or idled out after its length limit, is junk: the decoder gets zeros there
             # (its output for those frames is cut below; the frames before them do not depend on it - the decoder is causal)
             live = torch.tensor([[j < keep[b] for j in range(n)] for b in heard], device=chunk.device)
-            audio = self._codec.step(heard, chunk[heard] * live[:, None, :])
+            audio = self._codec.step([cs[b] for b in heard], chunk[heard] * live[:, None, :])
         spoken = {}
         if self._out is not None:
             # ONE rows launch: the rows that produced audio, plus a row that ended on an empty chunk and is still owed its lag;
             # a row that ends in this step ends its resampler stream with it
-            rows = [b for b in sorted(held) if keep[b] > 0 or (done[b] and self._out.pos[b] > 0)]
+            rows = [b for b in sorted(held) if keep[b] > 0 or (done[b] and self._out.pos[cs[b]] > 0)]
             if rows:
                 xs = [audio[heard.index(b), :keep[b] * (audio.shape[1] // n)] if keep[b] > 0 else None for b in rows]
-                spoken = dict(zip(rows, self._out.step(rows, xs, final=[b for b in rows if done[b]])))
+                spoken = dict(zip(rows, self._out.step([cs[b] for b in rows], xs, final=[cs[b] for b in rows if done[b]])))
         out = []
         for b in sorted(held):
             req = self._rows[b]
@@ -780,11 +892,160 @@ class BatchServer:
                     req._conv._end_turn(req, self._state, b)
                 req.done, req.slot, self._rows[b] = True, None, None
                 self._state.set_row_seed(b, None)
+                if self.streams is not None:
+                    self._leave(req)
             out.append((req, part, done[b]))
+        if self.max_lead_ms is not None:
+            # a listener's clock starts when this step hands over its first chunk
+            now = self._clock()
+            for req, _, _ in out:
+                if req._t0 is None and req._emitted:
+                    req._t0 = now
         return out
 
     def run(self) -> Iterator[Tuple[Request, torch.Tensor, bool]]:
-        """``step()`` until the queue is drained and every slot is free, yielding each ``(request, audio_chunk, done)``."""
+        """``step()`` until the queue is drained and every slot is free, yielding each ``(request, audio_chunk, done)``.  A
+        ``streams`` server sleeps ``next_due()`` (through ``sleep``) while everybody is far enough ahead of their listener, and
+        returns when nothing is queued or runnable - paused requests are left as they are."""
+        if self.streams is not None:
+            while True:
+                due = self.next_due()
+                if due is None:
+                    return
+                if due > 0:
+                    self._sleep(due)
+                    continue
+                for item in self.step():
+                    yield item
         while self._queue or any(r is not None for r in self._rows):
             for item in self.step():
                 yield item
+
+    # ------------------------------------------------------------------------------------- more streams than slots: the schedule
+    @property
+    def in_flight(self) -> List[Request]:
+        """The requests admitted and not done (running, parked or paused), in admission order - a ``streams`` server's."""
+        return list(self._flight)
+
+    def _lead(self, req, now):
+        """Milliseconds of audio the request's listener has ahead: what was emitted, less - under pacing, once the first chunk
+        was delivered - the time the listener has been listening."""
+        ms = req._emitted * FRAME_MS
+        return ms if now is None or req._t0 is None else ms - (now - req._t0) * 1000.0
+
+    def _candidates(self, now):
+        """(the in-flight requests that may run now, each as (lead, id, request); the queued requests that may join, in FIFO
+        order): neither paused ones nor - under pacing - those at or over ``max_lead_ms``; joiners only while fewer than
+        ``streams`` are in flight, paused ones included."""
+        flying = [(self._lead(r, now), r.id, r) for r in self._flight if not r._paused]
+        if self.max_lead_ms is not None:
+            flying = [c for c in flying if c[0] < self.max_lead_ms]
+        room = self.streams - len(self._flight)
+        return flying, [r for r in self._queue if not r._paused][:max(room, 0)]
+
+    def _schedule(self):
+        """The start of a ``streams`` server's step: the ``slots`` candidates with the least (lead, id) get the slots.  Rows
+        that were not chosen leave by ONE ``park_rows``; chosen requests without a slot return by ONE ``resume_rows``, lowest
+        free slot first; a chosen request that holds a slot stays there.  Returns the chosen queued requests (for ``_admit``),
+        taken off the queue - or None when nobody is a candidate (nothing was touched)."""
+        flying, new = self._candidates(self._clock() if self.max_lead_ms is not None else None)
+        cands = sorted([(float("-inf"), r.id, r) for r in new] + flying, key=lambda c: c[:2])[:self.slots]
+        if not cands:
+            return None
+        chosen = [c[2] for c in cands]
+        out = [b for b in range(self.slots) if self._rows[b] is not None and all(self._rows[b] is not r for r in chosen)]
+        if out:
+            self._park(out)
+        back = [r for r in chosen if r.slot is None and r._row is not None]
+        if back:
+            self._resume(back)
+        fresh = deque(r for r in chosen if r.slot is None)
+        for r in fresh:
+            self._queue.remove(r)
+        return fresh
+
+    def _park(self, slots):
+        """The requests in ``slots`` leave their rows in the middle of their utterances: ONE ``DecodeState.park_rows`` (K / V,
+        rings, generators) and one gather of their last sampled frames.  Their codec state stays where it is."""
+        parked = self._state.park_rows(slots)
+        toks = self._tok[slots]                          # (a gather: a copy of its own)
+        for j, b in enumerate(slots):
+            req = self._rows[b]
+            req._row, req._tokrow, req.slot, self._rows[b] = parked[j], toks[j], None, None
+            req.preemptions += 1
+        self.stats["parks"] += len(slots)
+        self.stats["park_launches"] += 1
+
+    def _resume(self, reqs):
+        """Parked requests into the free slots, lowest first: ONE ``DecodeState.resume_rows``, one scatter of their last sampled
+        frames, and each row's adapter and sampling parameters (the ring counters are restored, not reset)."""
+        free = [b for b in range(self.slots) if self._rows[b] is None][:len(reqs)]
+        self._state.resume_rows(free, [r._row for r in reqs])
+        self._tok[free] = torch.stack([r._tokrow for r in reqs])
+        for b, req in zip(free, reqs):
+            self._state.set_row_adapter(b, self._bank[req.adapter] if req.adapter is not None else None)
+            self._set_rows((b,), [getattr(req, name) for name in NAMES])
+            req._row, req._tokrow, req.slot, self._rows[b] = None, None, b, req
+            req.slots_held.append(b)
+        self.stats["resumes"] += len(reqs)
+        self.stats["resume_launches"] += 1
+
+    def _leave(self, req):
+        """A request of a ``streams`` server has ended: it is no longer in flight and its codec slot is free."""
+        import bisect
+        self._flight.remove(req)
+        bisect.insort(self._cfree, req._cslot)
+
+    def next_due(self) -> Optional[float]:
+        """Seconds until ``step()`` has somebody to run: 0.0 if it has now; None if nothing is in flight or queued, or all are
+        paused; else - under ``max_lead_ms`` - until the first listener's lead is back under the bound, never less than a
+        millisecond (at the exact instant a lead reaches the bound it is not yet below it)."""
+        self._check()
+        if self.streams is None:
+            return 0.0 if self._queue or any(r is not None for r in self._rows) else None
+        now = self._clock() if self.max_lead_ms is not None else None
+        flying, new = self._candidates(now)
+        if flying or new:
+            return 0.0
+        waits = [self._lead(r, now) - self.max_lead_ms for r in self._flight if not r._paused] if now is not None else []
+        return max(min(waits) / 1000.0, MIN_SLEEP) if waits else None
+
+    def _pause(self, req, paused):
+        self._check()
+        if self.streams is None:
+            raise RuntimeError("pause() / resume() need a server made with serve(streams=): this server's requests hold their slot "
+                               "from admission to their end")
+        if not req.done:
+            req._paused = bool(paused)
+
+    @torch.inference_mode()
+    def cancel(self, req: Request, heard_frames: Optional[int] = None) -> None:
+        """End ``req`` now, wherever it is - queued, running, parked or paused (nothing happens to a done one).  A plain request
+        is dropped.  A conversation's turn ends the way a length limit ends it, with ``min(heard_frames, emitted)`` frames kept
+        (None: all emitted) - barge-in: the history and the parked cache hold the text and exactly the frames the listener
+        heard, and the next ``say`` works.  Only the history and the cache are those of the heard frames: a seeded conversation's
+        noise generator is not rewound - it stands after every frame the turn sampled - so the next turn has the codes of a turn
+        that was given ``heard_frames`` frames only where that turn sampled as many frames.  The request is ``done`` with ``cancelled = True``; its slot, codec slot and resampler
+        slot are free (the resampler's lag is not flushed)."""
+        self._check()
+        if req._srv is not self:
+            raise ValueError("cancel: not a request of this server")
+        if heard_frames is not None and (isinstance(heard_frames, bool) or int(heard_frames) != heard_frames or heard_frames < 0):
+            raise ValueError(f"heard_frames must be an integer >= 0 (None: every frame emitted), got {heard_frames!r}")
+        if req.done:
+            return
+        b = req.slot
+        if b is None and req._row is None:
+            self._queue.remove(req)
+        if req._conv is not None:
+            req._conv._end_turn(req, self._state, b, req._emitted if heard_frames is None else heard_frames)
+        if b is not None:
+            self._rows[b], req.slot = None, None
+            self._state.set_row_seed(b, None)
+        if req._cslot is not None:
+            if self._out is not None:
+                self._out.close(req._cslot)
+            if self.streams is not None:
+                self._leave(req)
+        req._row, req._tokrow, req._paused = None, None, False
+        req.done = req.cancelled = True

@@ -1315,6 +1315,72 @@ __global__ __launch_bounds__(256) void kv_fork_rows_kernel(ForkRows a, bf16_t* _
     }
 }
 
+// The mirror of kv_fork_rows_kernel, the rows form of DecodeState.park_row: positions 0 .. len-1 of R <= 16 rows of the cache
+// allocation into R separate contiguous destinations [planes][len][HD].  The same table walk, the same chunks, the same four
+// planes in flight per thread; the cache is only read, pos is not an argument.  No LDS.
+struct ParkRows {
+    bf16_t* dst[16];         // parked history of the segment
+    int row[16];             // batch row of the caches
+    int len[16];             // positions (0 from R on)
+};
+
+template <int HD>
+__global__ __launch_bounds__(256) void kv_park_rows_kernel(ParkRows a, const bf16_t* __restrict__ kv, int planes, int B, int KV,
+                                                           int S_max) {
+    constexpr int VPR = HD / 8;                                    // 16-byte vectors per position
+    int t = blockIdx.x, row = 0, len = 0, chunk = 0;
+    bf16_t* dst = nullptr;
+    bool found = false;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int nc = (a.len[r] * VPR + 255) >> 8;
+        if (!found && t < nc) {
+            dst = a.dst[r]; row = a.row[r]; len = a.len[r]; chunk = t;
+            found = true;
+        }
+        if (!found) t -= nc;
+    }
+    if (!found) return;                                            // (the grid is exactly the chunks: not reached)
+    const int v = chunk * 256 + threadIdx.x;
+    if (v >= len * VPR) return;
+    const int gy = gridDim.y;
+    for (int hp = blockIdx.y; hp < planes; hp += 4 * gy) {         // hp = (layer * 2 + plane) * KV + kv head
+        U4 u[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int h = hp + j * gy;
+            if (h < planes) {
+                const int lp = h / KV, kvh = h - lp * KV;
+                u[j] = *reinterpret_cast<const U4*>(kv + (((size_t)lp * B + row) * KV + kvh) * S_max * HD + (size_t)v * 8);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (hp + j * gy < planes) *reinterpret_cast<U4*>(dst + (size_t)(hp + j * gy) * len * HD + (size_t)v * 8) = u[j];
+    }
+}
+
+// The rings of the processed / typical samplers, row by row: code_hist [B][K][SMP_HIST] and hist_frame [B] of the state against a
+// packed buffer [R][K * SMP_HIST + 1] (a row's ring, then its counter).  Block r moves row a.row[r]; to_state picks the direction -
+// towards the state only the named rows are written, towards the packed buffer nothing of the state is.  hist_live is no argument.
+struct HistRows {
+    int row[16];
+};
+
+__global__ __launch_bounds__(256) void sample_hist_move_rows_kernel(HistRows a, int* __restrict__ code_hist, int* __restrict__ hist_frame,
+                                                                    int* __restrict__ packed, int K, int to_state) {
+    const int r = blockIdx.x, row = a.row[r], n = K * SMP_HIST;
+    int* ring = code_hist + (size_t)row * n;
+    int* pk = packed + (size_t)r * (n + 1);
+    if (to_state) {
+        for (int i = threadIdx.x; i < n; i += 256) ring[i] = pk[i];
+        if (threadIdx.x == 0) hist_frame[row] = pk[n];
+    } else {
+        for (int i = threadIdx.x; i < n; i += 256) pk[i] = ring[i];
+        if (threadIdx.x == 0) pk[n] = hist_frame[row];
+    }
+}
+
 // one query position against the cache: block per (b, q-head); the scores of all S_max <= 8192 keys live in LDS (the launcher sizes it).
 // table != NULL fuses what used to be two more launches per layer: the new position's q and k heads are rotated here
 // (torchtune RoPE on interleaved pairs, same arithmetic and bf16 rounding as rope_kernel), and the first q-head block of
@@ -2319,6 +2385,70 @@ extern "C" int csm_kv_fork_rows(const void* const* src, void* kv, int* pos, cons
     else
         hipLaunchKernelGGL((kv_fork_rows_kernel<128>), grid, dim3(256), 0, stream, a, (bf16_t*)kv, pos, planes, B, KV, S_max);
     CSM_CHECK_LAUNCH("csm_kv_fork_rows");
+    return 0;
+}
+
+extern "C" int csm_kv_park_rows(void* const* dst, const void* kv, const int* rows, const int* len, int R, int layers, int B, int KV,
+                                 int HD, int S_max, hipStream_t stream) {
+    CSM_REQUIRE(dst && kv && rows && len, "csm_kv_park_rows: null pointer");
+    CSM_REQUIRE(R >= 1 && R <= 16, "csm_kv_park_rows: %d segments (1 to 16)", R);
+    CSM_REQUIRE(HD == 64 || HD == 128, "csm_kv_park_rows: head_dim %d unsupported", HD);
+    CSM_REQUIRE(layers >= 1 && B >= 1 && KV >= 1 && S_max >= 1 && S_max <= (1 << 24) && (long long)layers * 2 * KV <= 0x7fffffffLL,
+                "csm_kv_park_rows: bad shape layers=%d B=%d KV=%d S_max=%d", layers, B, KV, S_max);
+    const uintptr_t s0 = (uintptr_t)kv;
+    const size_t sbytes = (size_t)layers * 2 * B * KV * S_max * HD * sizeof(bf16_t);
+    CSM_REQUIRE((s0 & 15) == 0, "csm_kv_park_rows: the cache must be 16-byte aligned");
+    const int planes = layers * 2 * KV;
+    ParkRows a = {};
+    unsigned chunks = 0;
+    for (int r = 0; r < R; ++r) {
+        CSM_REQUIRE(dst[r], "csm_kv_park_rows: segment %d: null pointer", r);
+        CSM_REQUIRE(len[r] >= 1 && len[r] <= S_max, "csm_kv_park_rows: segment %d: %d positions outside 1 .. S_max = %d", r, len[r], S_max);
+        CSM_REQUIRE(rows[r] >= 0 && rows[r] < B, "csm_kv_park_rows: segment %d: batch row %d outside the caches (%d rows)", r, rows[r], B);
+        for (int q = 0; q < r; ++q)
+            CSM_REQUIRE(rows[q] != rows[r], "csm_kv_park_rows: batch row %d appears in two segments (%d and %d)", rows[r], q, r);
+        const uintptr_t d0 = (uintptr_t)dst[r];
+        CSM_REQUIRE((d0 & 15) == 0, "csm_kv_park_rows: segment %d: the destination must be 16-byte aligned", r);
+        const size_t dbytes = (size_t)planes * len[r] * HD * sizeof(bf16_t);
+        CSM_REQUIRE(d0 + dbytes <= s0 || s0 + sbytes <= d0, "csm_kv_park_rows: segment %d: the destination overlaps the cache", r);
+        for (int q = 0; q < r; ++q) {
+            const uintptr_t q0 = (uintptr_t)dst[q];
+            const size_t qbytes = (size_t)planes * len[q] * HD * sizeof(bf16_t);
+            CSM_REQUIRE(d0 + dbytes <= q0 || q0 + qbytes <= d0, "csm_kv_park_rows: the destinations of segments %d and %d overlap", q, r);
+        }
+        a.dst[r] = (bf16_t*)dst[r]; a.row[r] = rows[r]; a.len[r] = len[r];
+        chunks += (unsigned)((len[r] * (HD / 8) + 255) / 256);
+    }
+    const dim3 grid(chunks, (unsigned)((planes + 3) / 4 < 65535 ? (planes + 3) / 4 : 65535));
+    if (HD == 64)
+        hipLaunchKernelGGL((kv_park_rows_kernel<64>), grid, dim3(256), 0, stream, a, (const bf16_t*)kv, planes, B, KV, S_max);
+    else
+        hipLaunchKernelGGL((kv_park_rows_kernel<128>), grid, dim3(256), 0, stream, a, (const bf16_t*)kv, planes, B, KV, S_max);
+    CSM_CHECK_LAUNCH("csm_kv_park_rows");
+    return 0;
+}
+
+extern "C" int csm_sample_hist_move_rows(int* code_hist, int* hist_frame, int* packed, const int* rows, int R, int B, int K, int to_state,
+                                          hipStream_t stream) {
+    CSM_REQUIRE(code_hist && hist_frame && packed && rows, "csm_sample_hist_move_rows: null pointer");
+    CSM_REQUIRE(R >= 1 && R <= 16, "csm_sample_hist_move_rows: %d rows (1 to 16)", R);
+    CSM_REQUIRE(B >= 1 && K >= 1 && K <= 4096, "csm_sample_hist_move_rows: bad shape B=%d K=%d", B, K);
+    CSM_REQUIRE(to_state == 0 || to_state == 1, "csm_sample_hist_move_rows: direction %d (0: to the packed buffer, 1: to the state)", to_state);
+    const size_t n = (size_t)K * SMP_HIST;
+    const uintptr_t p0 = (uintptr_t)packed, h0 = (uintptr_t)code_hist, f0 = (uintptr_t)hist_frame;
+    const size_t pbytes = (size_t)R * (n + 1) * sizeof(int), hbytes = (size_t)B * n * sizeof(int), fbytes = (size_t)B * sizeof(int);
+    CSM_REQUIRE(((p0 | h0 | f0) & 3) == 0, "csm_sample_hist_move_rows: the buffers must be 4-byte aligned");
+    CSM_REQUIRE((p0 + pbytes <= h0 || h0 + hbytes <= p0) && (p0 + pbytes <= f0 || f0 + fbytes <= p0),
+                "csm_sample_hist_move_rows: the packed buffer overlaps the state's rings or counters");
+    HistRows a = {};
+    for (int r = 0; r < R; ++r) {
+        CSM_REQUIRE(rows[r] >= 0 && rows[r] < B, "csm_sample_hist_move_rows: entry %d: batch row %d outside the state (%d rows)", r, rows[r], B);
+        for (int q = 0; q < r; ++q)
+            CSM_REQUIRE(rows[q] != rows[r], "csm_sample_hist_move_rows: batch row %d appears in two entries (%d and %d)", rows[r], q, r);
+        a.row[r] = rows[r];
+    }
+    hipLaunchKernelGGL(sample_hist_move_rows_kernel, dim3(R), dim3(256), 0, stream, a, code_hist, hist_frame, packed, K, to_state);
+    CSM_CHECK_LAUNCH("csm_sample_hist_move_rows");
     return 0;
 }
 

@@ -429,6 +429,23 @@ int csm_kv_shift(const void* src, void* dst, const float* rope_table, int table_
  * source that overlaps the cache. */
 int csm_kv_fork_rows(const void* const* src, void* kv, int* pos, const int* rows, const int* len, int R, int layers, int B, int KV,
                      int HD, int S_max, csm_stream_t stream);
+/* The mirror of csm_kv_fork_rows, the rows form of DecodeState.park_row: positions 0 .. len[r]-1 of batch row rows[r] of kv bf16
+ * [layers][2][B][KV][S_max][HD] go to dst[r] bf16 [layers][2][KV][len[r]][HD], bit for bit, R (1 .. 16) rows in ONE launch - what
+ * a server takes out of its slots when it preempts utterances.  The cache is only read and no position vector is an argument
+ * (the lengths come from the caller's host mirror); only the R destinations are written.  dst / rows / len are HOST arrays of R
+ * entries and travel by value in the kernel arguments.  Returns 1 (nothing launched) for a null pointer (dst[r] included), R
+ * outside 1 .. 16, len[r] outside 1 .. S_max, a row outside 0 .. B-1 or named twice, HD other than 64 / 128, layers / B / KV /
+ * S_max < 1, a destination or cache that is not 16-byte aligned, a destination that overlaps the cache or another destination. */
+int csm_kv_park_rows(void* const* dst, const void* kv, const int* rows, const int* len, int R, int layers, int B, int KV, int HD,
+                     int S_max, csm_stream_t stream);
+/* The rings of the processed / typical rows samplers, moved row by row in ONE launch: for r < R (1 .. 16) the ring
+ * code_hist[rows[r]] (int32 [K][64] of code_hist [B][K][64]) and the counter hist_frame[rows[r]] against row r of packed int32
+ * [R][K * 64 + 1] (the ring, then the counter).  to_state = 0 reads the state and writes only packed; to_state = 1 reads packed and
+ * writes only the named rows' rings and counters.  hist_live is no argument.  rows is a HOST array, by value in the kernel
+ * arguments.  Returns 1 (nothing launched) for a null pointer, R outside 1 .. 16, B < 1, K outside 1 .. 4096, a direction other than 0 / 1, a row
+ * outside 0 .. B-1 or named twice, a buffer that is not 4-byte aligned, a packed buffer that overlaps the state's. */
+int csm_sample_hist_move_rows(int* code_hist, int* hist_frame, int* packed, const int* rows, int R, int B, int K, int to_state,
+                              csm_stream_t stream);
 /* out[b][h*HD..] = softmax(q . K[0..pos[b]]^T / sqrt(HD)) V   for the single query row in qkv[b].  HD 64 or 128, H % KV == 0,
  * 1 <= S_max <= 8192 (the scores live in LDS), ld % 8 == 0 (16-byte loads from qkv + b * ld) - anything else returns 1 */
 int csm_attn_decode(const void* qkv, const void* kcache, const void* vcache, void* out, const int* pos, int B, int H, int KV,

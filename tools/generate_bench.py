@@ -31,7 +31,10 @@ against the same step without the resampler (resample_main).  GEN_OVERFLOW=1: a 
 (the kept history is prefilled again) and "shift" (the KV cache slides: csm_kv_shift) next to an in-limit turn, at B = 1 and for
 16 conversations that overflow at one boundary of the 16-slot server, plus csm_kv_shift alone (overflow_main).  GEN_VOICE=1: a voice
 prompt prefilled once (Generator.voice) against the same 5 s given as context: fork_rows against resume_row calls, the staggered
-served load, submit -> first chunk, and the steps that admit 1 and 16 joins (voice_main)."""
+served load, submit -> first chunk, and the steps that admit 1 and 16 joins (voice_main).  GEN_SERVE_STREAMS=1: more listeners than
+slots (Generator.serve(streams=N)): the server step with 16 rows rotated out and in at every chunk boundary against the step
+without rotation, park_rows / resume_rows against the one-row calls, and the streams one GPU keeps fed under the wall clock
+without an underrun (serve_streams_main)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "csm-train-pytorch_amd"))
@@ -681,6 +684,139 @@ def serve_main():
 def _spread(v):
     v = sorted(v)
     return f"median {v[len(v) // 2] * 1e3:.3f} ms ({v[0] * 1e3:.3f} .. {v[-1] * 1e3:.3f})"
+
+
+def serve_streams_main():
+    """GEN_SERVE_STREAMS=1: more listeners than slots (Generator.serve(streams=N)) on CSM-1B random init, 16 slots, chunk_frames 4,
+    5 s of context each - GEN_SERVE's setting.  (a) Rotation cost: the steady server step with 32 streams in fair share (16 rows
+    parked and 16 resumed at every chunk boundary) against the same step with 16 streams (no rotation), GEN_ROUNDS (default 3)
+    alternated repeats, medians of 20 steps, the difference next to the repeats' own spread; and DecodeState.park_rows /
+    resume_rows at R = 1 / 4 / 16 (rings included: a row_processors state) against R park_row / resume_row calls plus the ring
+    and token copies they stand for.  (b) Capacity under the wall clock: max_lead_ms 2000, streams in GEN_STREAMS (default
+    16,32,64,96,128), two arrivals per server step, every request GEN_FRAMES (default 100) frames; per value the underruns (a
+    chunk delivered after its listener's buffer ran dry), submit -> first chunk (median, worst) and aggregate frames/s.
+    GEN_SERVE_PARTS=a / b: one part alone."""
+    dev = "cuda:0"
+    n = 4
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    parts = os.environ.get("GEN_SERVE_PARTS", "ab")
+    codec = make_codec(dev)
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=codec)
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+
+    def steady(streams, **kw):
+        srv = gen.serve(slots=16, chunk_frames=n, streams=streams, **kw)
+        for i in range(streams):
+            srv.submit(f"utterance number {i}: {text}", i % 16, ctx, seed=i, max_audio_length_ms=80 * 400)
+        _timed(srv.step, 6)                                                  # admissions, eager warm-up frame, graph capture
+        before = dict(srv.stats)
+        steps = sorted(_timed(srv.step, 1) for _ in range(20))
+        moved = (srv.stats["parks"] - before["parks"], srv.stats["resumes"] - before["resumes"])
+        return steps[len(steps) // 2], moved
+
+    if "a" in parts:
+        for streams in (16, 32):
+            steady(streams)
+        res = {16: [], 32: []}
+        for _ in range(rounds):
+            for streams in (16, 32):
+                med, moved = steady(streams)
+                res[streams].append(med)
+        assert moved == (16 * 20, 16 * 20), moved                            # (the last one ran with 32: 16 out and 16 in per step)
+        for streams in (16, 32):
+            print(f"GEN_SERVE_STREAMS (a) server step, 16 rows x {n} frames, {streams} streams "
+                  f"({'16 rows parked + 16 resumed per step' if streams == 32 else 'no rotation'}): medians of 20 steps "
+                  f"{_spread(res[streams])}", flush=True)
+        d = sorted(b - a for a, b in zip(res[16], res[32]))
+        own = max(max(v) - min(v) for v in res.values())
+        print(f"GEN_SERVE_STREAMS (a) rotation - none: {d[len(d) // 2] * 1e3:+.2f} ms per step ({d[0] * 1e3:+.2f} .. {d[-1] * 1e3:+.2f}); "
+              f"the repeats' own spread {own * 1e3:.2f} ms", flush=True)
+        # park_rows / resume_rows against the one-row calls and the copies they stand for, on a state that keeps rings
+        srv = gen.serve(slots=16, chunk_frames=n, row_sampling=True, row_processors=True)
+        for i in range(16):
+            srv.submit(f"utterance number {i}: {text}", i, ctx, max_audio_length_ms=80 * 400)
+        _timed(srv.step, 3)
+        st, samp, tok = srv._state, srv._state.sampler, srv._tok
+        with torch.inference_mode():
+            for R in (1, 4, 16):
+                rows = list(range(R))
+                held = {}
+
+                def park_all():
+                    held["rows"], held["tok"] = st.park_rows(rows), tok[rows]
+
+                def resume_all():
+                    st.resume_rows(rows, held["rows"])
+                    tok[rows] = held["tok"]
+
+                def park_each():
+                    held["each"] = [(st.park_row(b, st.row_pos[b] + 1), samp.code_hist[b].clone(), samp.hist_frame[b:b + 1].clone(),
+                                     tok[b].clone()) for b in rows]
+
+                def resume_each():
+                    for b, (kv, ring, frame, t) in zip(rows, held["each"]):
+                        st.resume_row(b, kv)
+                        samp.code_hist[b].copy_(ring)
+                        samp.hist_frame[b:b + 1].copy_(frame)
+                        tok[b].copy_(t)
+
+                for f in (park_all, resume_all, park_each, resume_each):
+                    _timed(f, 5)
+                t = {f.__name__: [] for f in (park_all, resume_all, park_each, resume_each)}
+                for _ in range(rounds):
+                    for f in (park_all, resume_all, park_each, resume_each):
+                        t[f.__name__].append(_timed(f, 30))
+                print(f"GEN_SERVE_STREAMS (a) {st.row_pos[0] + 1} positions, R={R:2d}: park_rows {_spread(t['park_all'])} against {R} "
+                      f"park_row + copies {_spread(t['park_each'])}; resume_rows {_spread(t['resume_all'])} against {R} resume_row + "
+                      f"copies {_spread(t['resume_each'])}", flush=True)
+        del srv, st, samp, tok
+    if "b" not in parts:
+        return
+    frames = int(os.environ.get("GEN_FRAMES", 100))
+    lead = 2000.0
+
+    def capacity(streams):
+        srv = gen.serve(slots=16, chunk_frames=n, streams=streams, max_lead_ms=lead)
+        reqs, t_sub, t_first, heard, under = [], {}, {}, {}, 0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        while True:
+            for _ in range(2):                                              # two arrivals per server step until all are in
+                if len(reqs) < streams:
+                    t_sub[len(reqs)] = time.perf_counter()
+                    reqs.append(srv.submit(f"utterance number {len(reqs)}: {text}", len(reqs) % 16, ctx, seed=len(reqs),
+                                           max_audio_length_ms=80 * frames))
+            due = srv.next_due()
+            if due is None:
+                if len(reqs) == streams:
+                    break
+                continue
+            if due > 0:
+                time.sleep(due)
+                continue
+            out = srv.step()
+            torch.cuda.synchronize()                                        # (the chunk is heard: its samples are there)
+            t = time.perf_counter()
+            for r, a, _ in out:
+                if r.id in t_first:                                         # what the listener had left when this chunk came
+                    if heard[r.id] - (t - t_first[r.id]) * 1000.0 < 0:
+                        under += 1
+                elif a.numel():
+                    t_first[r.id] = t
+                heard[r.id] = heard.get(r.id, 0.0) + a.numel() / 24.0
+        dt = time.perf_counter() - t0
+        lat = sorted(t_first[i] - t_sub[i] for i in range(streams))
+        return under, lat[len(lat) // 2], lat[-1], sum(r._emitted for r in reqs) / dt, srv.stats
+
+    capacity(16)                                                             # warm-up: graph capture, allocator
+    for streams in [int(v) for v in os.environ.get("GEN_STREAMS", "16,32,64,96,128").split(",")]:
+        under, med, worst, fps, stats = capacity(streams)
+        print(f"GEN_SERVE_STREAMS (b) {streams:3d} streams x {frames} frames, max_lead_ms {lead:.0f}, two arrivals per step: {under} underruns; "
+              f"submit -> first chunk median {med * 1e3:.0f} ms, worst {worst * 1e3:.0f} ms; {fps:.1f} frames/s aggregate "
+              f"({streams * 12.5:.1f} frames/s is real time for all); {stats['steps']} steps, {stats['parks']} parks in "
+              f"{stats['park_launches']} launches, {stats['resumes']} resumes in {stats['resume_launches']}", flush=True)
 
 
 def voice_main():
@@ -1671,6 +1807,8 @@ def resample_main():
 
 
 def main():
+    if os.environ.get("GEN_SERVE_STREAMS") == "1":
+        return serve_streams_main()
     if os.environ.get("GEN_VOICE") == "1":
         return voice_main()
     if os.environ.get("GEN_RESAMPLE") == "1":
