@@ -46,6 +46,11 @@ def parse_args(argv=None):
                    help="locally typical sampling, in (0, 1] (default 1.0: off): after the other filters, keep the codes whose "
                         "surprise is closest to the entropy until their probability reaches P - it can drop the most likely code "
                         "(all modes)")
+    p.add_argument("--stats-file", type=str, default=None, metavar="PATH",
+                   help="write what the model thought of the codes it drew (return_stats / serve(stats=True)) as JSON lines: one "
+                        "object per utterance or turn - with --serve-file one per line, under its \"line\" id - holding "
+                        "\"codebook0\" (per frame: logprob, entropy and pmax of the semantic codebook), \"frame_logprob\" (per frame, "
+                        "the sum of all K log-probabilities) and \"mean_logprob\" (all modes)")
     p.add_argument("--acoustic-temperature", type=float, default=None, metavar="T",
                    help="temperature of codebooks 1..K-1 (the acoustic ones; codebook 0 keeps --temperature)")
     p.add_argument("--acoustic-topk", type=int, default=None, metavar="K",
@@ -167,6 +172,20 @@ def out_rate(generator, args) -> int:
     return int(generator.sample_rate if args.output_sample_rate is None else args.output_sample_rate)
 
 
+def stats_kw(args):
+    """The ``return_stats`` keyword of the generate calls: nothing without --stats-file."""
+    return {"return_stats": True} if getattr(args, "stats_file", None) else {}
+
+
+def write_stats(args, objects):
+    """--stats-file: one JSON object per line - ``SampleStats.summary()`` of each utterance, with the extra keys given."""
+    import json
+    os.makedirs(os.path.dirname(os.path.abspath(args.stats_file)), exist_ok=True)
+    with open(args.stats_file, "w") as f:
+        for extra, stats in objects:
+            f.write(json.dumps({**extra, **stats.summary()}) + "\n")
+
+
 def build_context(args, sample_rate):
     """Reference generate.py:129-156: (audio, text, speaker) triples -> Segments at the generator's sample rate."""
     context = []
@@ -201,7 +220,11 @@ def main(argv=None):
     if args.stream:
         return stream_to_wav(generator, args, speaker_id, context, adapter)
     audio = generator.generate(text=args.text, speaker=speaker_id, context=context, max_audio_length_ms=args.max_audio_length_ms,
-                               adapter=adapter, **sampling_kw(args, lambda: generator._model.args.audio_num_codebooks), **out_rate_kw(args))
+                               adapter=adapter, **sampling_kw(args, lambda: generator._model.args.audio_num_codebooks), **out_rate_kw(args),
+                               **stats_kw(args))
+    if args.stats_file:
+        audio, stats = audio
+        write_stats(args, [({}, stats)])
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     generator.save_wav(args.output, audio, **({} if args.output_sample_rate is None else {"sample_rate": args.output_sample_rate}))
     print(f"Audio saved to {args.output} ({audio.numel() / out_rate(generator, args):.2f} s at {out_rate(generator, args)} Hz)")
@@ -214,6 +237,7 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     t0 = time.perf_counter()
     n = 0
+    stats = None
     with wave.open(args.output, "wb") as w:
         w.setnchannels(1)
         w.setsampwidth(2)
@@ -221,12 +245,18 @@ def stream_to_wav(generator, args, speaker_id, context, adapter=None):
         for chunk in generator.generate_stream(text=args.text, speaker=speaker_id, context=context,
                                                max_audio_length_ms=args.max_audio_length_ms, chunk_frames=args.chunk_frames,
                                                adapter=adapter, **sampling_kw(args, lambda: generator._model.args.audio_num_codebooks),
-                                               **out_rate_kw(args)):
+                                               **out_rate_kw(args), **stats_kw(args)):
+            if args.stats_file:
+                chunk, part = chunk
+                stats = part if stats is None else stats.extend(part)
             pcm = (chunk.detach().float().cpu().clamp(-1, 1) * 32767.0).to(torch.int16).numpy().tobytes()
             if n == 0:
                 print(f"first chunk after {time.perf_counter() - t0:.3f} s")
             w.writeframes(pcm)
             n += chunk.numel()
+    if args.stats_file:
+        from ..sampling import SampleStats
+        write_stats(args, [({}, stats if stats is not None else SampleStats(generator._model.args.audio_num_codebooks))])
     print(f"Audio saved to {args.output} ({n / out_rate(generator, args):.2f} s at {out_rate(generator, args)} Hz, streamed in "
           f"{time.perf_counter() - t0:.2f} s)")
     return 0
@@ -417,7 +447,9 @@ def serve_to_wavs(generator, args, context, adapter=None):
     t0 = time.perf_counter()
     voices = serve_voices(generator, lines, context, adapter) if args.cache_context else None     # (the adapters are loaded)
     server = generator.serve(slots=args.slots, chunk_frames=args.chunk_frames, hear_slots=args.hear_slots,
-                             **serve_lines(lines, args, K), **out_rate_kw(args), **({"streams": args.streams} if args.streams else {}))
+                             **serve_lines(lines, args, K), **out_rate_kw(args), **({"streams": args.streams} if args.streams else {}),
+                             **({"stats": True} if args.stats_file else {}))
+    line_stats = {}
     convs, line_of = {}, {}                           # conversation id -> [conversation, its lines still to say]; request -> line
 
     def say(cid):
@@ -445,8 +477,11 @@ def serve_to_wavs(generator, args, context, adapter=None):
                 out = f"{stem}_{i}{ext or '.wav'}"
                 generator.save_wav(out, req.audio(), **({} if args.output_sample_rate is None else {"sample_rate": req.sample_rate}))
                 print(f"line {i}: {req.audio().numel() / out_rate(generator, args):.2f} s -> {out} (after {time.perf_counter() - t0:.2f} s)")
+                line_stats[i] = req.stats
                 if cid is not None and convs[cid][1]:
                     say(cid)
+    if args.stats_file:
+        write_stats(args, [({"line": i}, line_stats[i]) for i in sorted(line_stats)])
     print(f"{len(lines)} utterances served in {time.perf_counter() - t0:.2f} s")
     return 0
 
@@ -463,9 +498,10 @@ def converse_to_wav(generator, args, speaker_id, context, adapter=None):
     lines = [(args.text, speaker_id)] + list(zip(args.next_text, args.next_speaker or [speaker_id] * len(args.next_text)))
     conv = generator.conversation(context=context, adapter=adapter, on_overflow=args.on_overflow, keep_turns=args.keep_turns)
     kw = dict(max_audio_length_ms=args.max_audio_length_ms, **sampling_kw(args, lambda: generator._model.args.audio_num_codebooks),
-              **out_rate_kw(args))
+              **out_rate_kw(args), **stats_kw(args))
     t0 = time.perf_counter()
     n = 0
+    turn_stats = []
     with wave.open(args.output, "wb") as w:
         w.setnchannels(1)
         w.setsampwidth(2)
@@ -475,6 +511,12 @@ def converse_to_wav(generator, args, speaker_id, context, adapter=None):
             if args.stream:
                 first = None
                 for chunk in conv.generate_stream(text, spk, chunk_frames=args.chunk_frames, **kw):
+                    if args.stats_file:
+                        chunk, part = chunk
+                        if len(turn_stats) <= i:
+                            turn_stats.append(part)
+                        else:
+                            turn_stats[i].extend(part)
                     pcm = _pcm(chunk)
                     first = first if first is not None else time.perf_counter() - t1
                     w.writeframes(pcm)
@@ -482,9 +524,14 @@ def converse_to_wav(generator, args, speaker_id, context, adapter=None):
                 print(f"turn {i + 1}: first chunk after {first if first is not None else float('nan'):.3f} s")
             else:
                 audio = conv.generate(text, spk, **kw)
+                if args.stats_file:
+                    audio, part = audio
+                    turn_stats.append(part)
                 w.writeframes(_pcm(audio))
                 n += audio.numel()
                 print(f"turn {i + 1}: {audio.numel() / out_rate(generator, args):.2f} s of audio in {time.perf_counter() - t1:.2f} s")
+    if args.stats_file:
+        write_stats(args, [({"turn": i}, st) for i, st in enumerate(turn_stats)])
     print(f"Audio saved to {args.output} ({n / out_rate(generator, args):.2f} s at {out_rate(generator, args)} Hz, {len(lines)} turns in "
           f"{time.perf_counter() - t0:.2f} s)")
     return 0

@@ -120,6 +120,7 @@ class _Turn:
     def __init__(self, base: int, n_text: int):
         self.base, self.n_text = base, n_text      # history length (= cached positions) after the text frames
         self.samples: List[torch.Tensor] = []
+        self.stats: List[torch.Tensor] = []        # per sample, its frame's statistics on the device (return_stats)
         self.fed = 0                               # samples[:fed] have been fed to the backbone (one position each)
         self.kept = 0                              # frames handed to the caller so far (stream) / kept (generate)
         self.done = False
@@ -352,7 +353,7 @@ class Conversation:
         finally:
             m._decode_state = prev
 
-    def _begin(self, text, speaker, max_audio_frames, temperature, topk, filters={}) -> _Turn:
+    def _begin(self, text, speaker, max_audio_frames, temperature, topk, filters={}, stats=False) -> _Turn:
         """Feed what the cache lacks plus the new line's text frames, sample the first frame."""
         m, e = self._m, self._m.engine
         if not getattr(m, "use_kv_cache", True):
@@ -370,6 +371,8 @@ class Conversation:
         if self._state is None:
             self._state = DecodeState(e, 1, self._ads)
         st = self._state
+        if stats:
+            st.enable_stats()                                        # (it stays on: the state's later turns keep the one frame body)
         if self._cached == 0:
             last_h = st.prefill(new_t.unsqueeze(0), new_m.unsqueeze(0))
         else:
@@ -384,9 +387,11 @@ class Conversation:
                 st.reset_row_history(0)
                 st.set_live([0])
         turn.samples.append(e._frame_tail(st, last_h, temperature, topk, None))
+        if stats:
+            turn.stats.append(st.frame_stats())
         return turn
 
-    def _next_frame(self, turn: _Turn, temperature, topk, filters={}):
+    def _next_frame(self, turn: _Turn, temperature, topk, filters={}, stats=False):
         """Feed the last sampled frame, sample the next one (``Model.generate_frame`` on this conversation's state)."""
         K = self._m.args.audio_num_codebooks
         dev = self._gen.device
@@ -396,6 +401,8 @@ class Conversation:
             s = self._m.generate_frame(tokens, mask, torch.ones(1, 1, dtype=torch.long), temperature, topk, **filters)
         turn.fed += 1
         turn.samples.append(s)
+        if stats:
+            turn.stats.append(self._state.frame_stats())
 
     def _settle(self):
         """Close the turn in flight, if any: the history gets its kept frames and one all-zero EOS frame (the layout of
@@ -426,11 +433,13 @@ class Conversation:
     def generate(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
                  eos_check_every: int = 8, top_p: float = 1.0, min_p: float = 0.0,
                  output_sample_rate: Optional[int] = None, repetition_penalty=1.0, repetition_window=64,
-                 typical_p=1.0) -> torch.Tensor:
+                 typical_p=1.0, return_stats: bool = False):
         """Speak ``text`` as ``speaker`` with the whole history as context; arguments (``top_p`` / ``min_p``, ``repetition_penalty``
-        / ``repetition_window`` / ``typical_p``, per-codebook sequences and ``output_sample_rate`` included: this turn's) and EOS handling as
-        ``Generator.generate``.  The repetition window looks at this turn's frames only."""
+        / ``repetition_window`` / ``typical_p``, per-codebook sequences, ``output_sample_rate`` and ``return_stats`` included: this
+        turn's) and EOS handling as ``Generator.generate``.  The repetition window looks at this turn's frames only.  The first
+        turn with ``return_stats`` puts the conversation's state into statistics mode, where it stays."""
         from .generator import sampling_kwargs
+        from .sampling import SampleStats
         temperature, topk, filters = sampling_kwargs(self._gen, temperature, topk, top_p, min_p, repetition_penalty,
                                                      repetition_window, typical_p=typical_p)
         out_rs = self._gen._out_resampler(output_sample_rate)
@@ -442,9 +451,9 @@ class Conversation:
         try:
             for i in range(max_audio_frames):
                 if turn is None:
-                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk, filters)
+                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk, filters, return_stats)
                 else:
-                    self._next_frame(turn, temperature, topk, filters)
+                    self._next_frame(turn, temperature, topk, filters, return_stats)
                 n = len(turn.samples)
                 if n - checked >= step or i == max_audio_frames - 1:
                     hit = (torch.cat(turn.samples[checked:], 0) == 0).all(dim=1).nonzero()          # one host look per chunk
@@ -454,19 +463,24 @@ class Conversation:
                     checked = turn.kept = n
         finally:
             samples = turn.samples[:turn.kept] if turn is not None else []
+            fstats = turn.stats[:turn.kept] if turn is not None else []
             self._settle()
+        stats = SampleStats.of_frames(self._m.args.audio_num_codebooks, fstats) if return_stats else None
         if not samples:
-            return torch.zeros(0, device=self._gen.device)
+            audio = torch.zeros(0, device=self._gen.device)
+            return (audio, stats) if return_stats else audio
         codes = torch.stack(samples).permute(1, 2, 0).long()
         audio = self._gen._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
-        return audio if out_rs is None else out_rs(audio)
+        audio = audio if out_rs is None else out_rs(audio)
+        return (audio, stats) if return_stats else audio
 
     def generate_stream(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9,
                         topk: int = 50, chunk_frames: int = 4, top_p: float = 1.0, min_p: float = 0.0,
                         output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
-                        repetition_window=64, typical_p=1.0) -> Iterator[torch.Tensor]:
-        """``generate`` handing the audio out chunk by chunk, as ``Generator.generate_stream`` does; under the same seed the
-        chunks concatenate to ``generate``'s audio.  A later call on THIS conversation invalidates the stream."""
+                        repetition_window=64, typical_p=1.0, return_stats: bool = False) -> Iterator[torch.Tensor]:
+        """``generate`` handing the audio out chunk by chunk, as ``Generator.generate_stream`` does (``return_stats``: (chunk,
+        ``SampleStats``) pairs, likewise); under the same seed the chunks concatenate to ``generate``'s audio.  A later call on
+        THIS conversation invalidates the stream."""
         from .generator import sampling_kwargs
         temperature, topk, filters = sampling_kwargs(self._gen, temperature, topk, top_p, min_p, repetition_penalty,
                                                      repetition_window, typical_p=typical_p)
@@ -479,10 +493,15 @@ class Conversation:
                             "(decoding chunks independently would be wrong at the chunk edges)")
         self._run += 1
         self._settle()
-        return self._stream(self._run, text, speaker, max_audio_length_ms, temperature, topk, int(chunk_frames), filters, out_rs)
+        return self._stream(self._run, text, speaker, max_audio_length_ms, temperature, topk, int(chunk_frames), filters, out_rs,
+                            return_stats)
 
     @torch.inference_mode()
-    def _stream(self, run, text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, filters={}, out_rs=None):
+    def _stream(self, run, text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, filters={}, out_rs=None,
+                return_stats=False):
+        from .sampling import SampleStats
+        K = self._m.args.audio_num_codebooks
+
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later call on the same Conversation took its turn")
@@ -495,23 +514,25 @@ class Conversation:
         try:
             for i in range(max_audio_frames):
                 if turn is None:
-                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk, filters)
+                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk, filters, return_stats)
                 else:
-                    self._next_frame(turn, temperature, topk, filters)
+                    self._next_frame(turn, temperature, topk, filters, return_stats)
                 if len(turn.samples) - done == chunk_frames or i == max_audio_frames - 1:
                     codes = torch.stack(turn.samples[done:]).permute(1, 2, 0).long()               # [1, K, n]
                     hit = (codes[0] == 0).all(dim=0).nonzero()                                     # the chunk's one host look
                     n = int(hit[0]) if hit.numel() else codes.shape[2]
                     turn.kept = done + n
+                    fstats = turn.stats[done:done + n]
                     done = len(turn.samples)
                     if n:
                         chunk = decoder.step(codes[:, :, :n]).reshape(-1)
-                        yield chunk if out is None else out.feed(chunk)
+                        chunk = chunk if out is None else out.feed(chunk)
+                        yield (chunk, SampleStats.of_frames(K, fstats)) if return_stats else chunk
                         check()
                     if hit.numel():
                         break
             if out is not None and out.pos:                            # the samples the resampler still owes (its lag)
-                yield out.flush()
+                yield (out.flush(), SampleStats(K)) if return_stats else out.flush()
         finally:
             if turn is not None and self._open is turn:
                 self._settle()

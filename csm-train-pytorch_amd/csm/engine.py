@@ -833,7 +833,7 @@ class Engine:
 
     @torch.no_grad()
     def generate_frame(self, tokens, tokens_mask, input_pos, temperature, topk, noise=None, adapters=None, top_p=None,
-                       min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None):
+                       min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None, stats=False):
         """Reference model.py:140-195: backbone position(s) -> c0 -> 31 depth-decoder steps, against KV caches.
 
         The prompt (``input_pos`` starting at 0) is prefilled with the training forward kernels and its post-RoPE K/V
@@ -850,12 +850,18 @@ class Engine:
         any of the six: the processed rows sampler (``DecodeState.sampling_args``); likewise the same to every call.
         ``typical_p`` (with caches; None: not named): a number, B entries, or per entry K numbers - locally typical sampling
         as the last filter, through the typical rows sampler (``DecodeState.set_row_typical``); likewise.
+        ``stats`` (with caches; read on the first call of a generation): the state keeps every codebook's logits of the frame
+        and one more launch writes each drawn code's log-probability, entropy and largest probability
+        (``DecodeState.enable_stats`` / ``frame_stats``); the codes are the same.
         """
         m, a = self.m, self.m.args
         self._need()
         if int(input_pos[0, 0]) == 0:
             m._gen_adapters = list(adapters) if adapters is not None and any(x is not None for x in adapters) else None
         if not getattr(m, "use_kv_cache", True):
+            if stats:
+                raise ValueError("the recompute path (use_kv_cache = False) has no return_stats: the statistics need the KV-cache "
+                                 "path")
             if names_processors(temperature, topk, repetition_penalty=repetition_penalty, repetition_window=repetition_window):
                 raise ValueError("the recompute path (use_kv_cache = False) has no repetition penalty and no per-codebook "
                                  "parameters: they need the KV-cache path")
@@ -877,6 +883,8 @@ class Engine:
                                "same batch size (call it with input_pos starting at 0 first)")
         if first:
             st = m._decode_state = DecodeState(self, Bn, adapters)
+            if stats:
+                st.enable_stats()
         temperature, topk = st.sampling_args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
                                              typical_p=typical_p)
         st.set_live(range(Bn))
@@ -892,15 +900,19 @@ class Engine:
 
     @torch.no_grad()
     def generate_first_frames(self, tokens_list, masks_list, temperature, topk, noise=None, adapters=None, top_p=None,
-                              min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None):
+                              min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None, stats=False):
         """Batched generation (up to 16 utterances): prefill B prompts of different lengths and sample the
         first frame of each; later frames go through ``generate_frame`` with ``[B, 1, K+1]`` tokens and a non-zero
         ``input_pos``, exactly as for one utterance.  ``temperature`` / ``topk``: two numbers, or a sequence of B values for
         either one - row b then samples with its own pair (``DecodeState.sampling_args``); give the same to ``generate_frame``.
-        ``top_p`` / ``min_p`` / ``repetition_penalty`` / ``repetition_window`` / ``typical_p``: as for ``generate_frame``."""
+        ``top_p`` / ``min_p`` / ``repetition_penalty`` / ``repetition_window`` / ``typical_p`` / ``stats``: as for ``generate_frame``."""
         m = self.m
         self._need()
+        if stats and not getattr(m, "use_kv_cache", True):
+            raise ValueError("the recompute path (use_kv_cache = False) has no return_stats: the statistics need the KV-cache path")
         st = m._decode_state = DecodeState(self, len(tokens_list), adapters)
+        if stats:
+            st.enable_stats()
         temperature, topk = st.sampling_args(temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
                                              typical_p=typical_p)
         st.set_live(range(st.B))
@@ -938,8 +950,10 @@ class Engine:
                 return st.sampler.draw(lg[:, :V], i, qall[i])
             return sample_topk(lg[:, :V], topk, temperature, qall[i])
 
-        ops.gemv(last_h, m.block("codebook0_head.padded"), st.logits)
-        samples = [draw(st.logits, 0)]
+        # statistics mode (DecodeState.enable_stats): codebook i's logits go to their own slice and stay until the frame's end
+        lg_of = (lambda i: st.logits_all[i]) if st.stats is not None else (lambda i: st.logits)
+        ops.gemv(last_h, m.block("codebook0_head.padded"), lg_of(0))
+        samples = [draw(lg_of(0), 0)]
         dnorm = m.block("decoder.norm.scale")
         for i in range(K):
             # decoder position i: input = backbone state (i = 0) or the embedding of code i-1; the stack's final norm is
@@ -948,8 +962,12 @@ class Engine:
                     st.decoder_step(None, i, code=samples[-1].view(-1), final_norm=False))
             if i >= 1:
                 # [V][d'] copy of audio_head[i-1]: row-per-wave GEMV
-                ops.gemv_ex(hres, st.head_t[i - 1], st.logits, norm_scale=dnorm, eps=m.dc.norm_eps)
-                samples.append(draw(st.logits, i))
+                ops.gemv_ex(hres, st.head_t[i - 1], lg_of(i), norm_scale=dnorm, eps=m.dc.norm_eps)
+                samples.append(draw(lg_of(i), i))
+        if st.stats is not None:
+            # ONE launch over the frame's K * B rows (row i * B + b: codebook i, sequence b), on the codes in that order
+            ops.sample_stats_rows(st.logits_all.view(K * st.B, -1), torch.cat(samples, dim=0).view(-1), st.stats[0].view(-1),
+                                  st.stats[1].view(-1), st.stats[2].view(-1), V=V)
         return torch.cat(samples, dim=1)
 
     @torch.no_grad()
@@ -1316,6 +1334,7 @@ class DecodeState:
         self.h0 = torch.empty(B, m.bb.embed_dim, dtype=BF16, device=dev)
         self.proj = torch.empty(B, m.dc.embed_dim, dtype=BF16, device=dev)
         self.logits = torch.empty(B, m.vocab_pad, dtype=F32, device=dev)
+        self.logits_all, self.stats = None, None             # (statistics mode: enable_stats)
         self.dpos = [torch.full((B,), i, dtype=torch.int32, device=dev) for i in range(m.args.audio_num_codebooks)]
         # each row's position on the host (-1 = nothing prefilled): the one mirror of the device-side ``bb.pos`` (no sync per frame;
         # an idle row's device position is pinned, not mirrored).  Slot lifecycle (prefill_row / set_active / serve_frame): the
@@ -1345,6 +1364,29 @@ class DecodeState:
         elif m.lora is not None and not m.lora.merged:
             self.bb.attach_lora(m.lora)
             self.dc.attach_lora(m.lora)
+
+    def enable_stats(self):
+        """Statistics mode, before the first capture: every frame keeps its K codebooks' logits (``logits_all`` fp32
+        [K, B, vocab_pad]: codebook i's head writes slice i, the draw reads it) and ends with ONE ``sample_stats_rows`` launch over
+        the K * B rows that fills ``stats`` fp32 [3, K, B] - the log-probability of each drawn code, the entropy and the largest
+        probability of the distribution it was drawn from, at temperature 1 with no filter and no penalty, whatever the sampler
+        level.  The codes are the same bits.  The frame graph's key gets a tag (``RowSampler.graph_key``): a graph captured
+        without statistics is never replayed with them - a call after the first capture costs one eager frame and a new capture,
+        so make it before."""
+        if self.stats is not None:
+            return
+        m, dev = self.e.m, self.logits.device
+        K = m.args.audio_num_codebooks
+        self.logits_all = torch.empty(K, self.B, m.vocab_pad, dtype=F32, device=dev)
+        self.stats = torch.zeros(3, K, self.B, dtype=F32, device=dev)
+        self.sampler.stats = True
+
+    def frame_stats(self):
+        """The last frame's statistics, copied out on the device (no host synchronisation): fp32 [3, K, B] - logprob, entropy,
+        pmax - of the codes the frame call returned."""
+        if self.stats is None:
+            raise RuntimeError("no statistics: call enable_stats before the first frame")
+        return self.stats.clone()
 
     def fill_noise(self, noise=None):
         """``noise``: K tensors [B, V] of Exp(1) draws (pins the sampler), or None for fresh draws from torch's generator."""
@@ -1754,7 +1796,8 @@ class DecodeState:
         the row buffers (``set_row_sampling``), so a change of any row's parameters replays the same graph; once the state has
         row filters (``set_row_filters``) it is (None, None, "filters") - the frame holds the filtered rows sampler, and a change
         of any row's top-p / min-p replays it too; with row processors (``set_row_processors``) it is (None, None, "processors"), with
-        typical sampling (``set_row_typical``) (None, None, "typical")."""
+        typical sampling (``set_row_typical``) (None, None, "typical"); in statistics mode (``enable_stats``) every key ends with
+        "stats"."""
         m = self.e.m
         self._advance()
         key = self.sampler.graph_key(temperature, topk)

@@ -15,8 +15,8 @@ from typing import Iterator, List, Optional, Tuple
 import torch
 
 from .models.model import Model, ModelArgs
-from .sampling import (FULL_LEVEL, LEVELS, NAMES, PARAMS, _as_list, _is_number, check_filters, names_processors, normalise,
-                       per_codebook)
+from .sampling import (FULL_LEVEL, LEVELS, NAMES, PARAMS, SampleStats, _as_list, _is_number, check_filters, names_processors,
+                       normalise, per_codebook)
 
 
 @dataclass
@@ -173,7 +173,7 @@ class Generator:
     def generate(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                  temperature: float = 0.9, topk: int = 50, eos_check_every: int = 8, adapter: Optional[str] = None,
                  top_p: float = 1.0, min_p: float = 0.0, output_sample_rate: Optional[int] = None,
-                 repetition_penalty=1.0, repetition_window=64, voice=None, typical_p=1.0) -> torch.Tensor:
+                 repetition_penalty=1.0, repetition_window=64, voice=None, typical_p=1.0, return_stats: bool = False):
         """Reference generator.py:147-218.  ``adapter``: the name of a bank adapter (``add_adapter`` / ``load_adapter``) to
         speak with, or None.  The reference tests every frame for EOS on the host (one device sync per
         frame, generator.py:196-199); here the all-zero test runs on the device and the host looks at it once per
@@ -195,20 +195,27 @@ class Generator:
         without it; otherwise it samples through the typical rows sampler (``DecodeState.set_row_typical``).
         ``voice``: a ``Voice`` (``Generator.voice``) that comes before ``context`` - the call is then
         ``conversation(voice=voice, context=context, adapter=adapter).generate(text, speaker, ...)`` with every other argument
-        passed through: the voice's K / V are copied in, only ``context`` and the text are fed."""
+        passed through: the voice's K / V are copied in, only ``context`` and the text are fed.
+        ``return_stats``: return (audio, ``SampleStats``) - per frame and codebook, the model's own log-probability of the
+        code drawn, and the entropy and largest probability of the distribution it was drawn from (temperature 1, before
+        any filter or penalty), cut where the codes are cut.  The codes and the audio are the same; the frames cost one more
+        launch each.  Refused on the recompute path (``model.use_kv_cache = False``)."""
         if voice is not None:
             return self.conversation(context, adapter, voice=voice).generate(
                 text, speaker, max_audio_length_ms, temperature, topk, eos_check_every, top_p, min_p, output_sample_rate,
-                repetition_penalty, repetition_window, typical_p=typical_p)
+                repetition_penalty, repetition_window, typical_p=typical_p, return_stats=return_stats)
         temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
                                                      repetition_window, typical_p=typical_p)
         out_rs = self._out_resampler(output_sample_rate)
         ads = self._resolve_adapters([adapter])
+        self._stats_check(return_stats)
         self._run += 1
         self._model.reset_caches()
         max_audio_frames = int(max_audio_length_ms / 80)
         curr_tokens, curr_mask, curr_pos = self._prompt(text, speaker, context, max_audio_frames)
-        samples = []
+        samples, fstats = [], []
+        if return_stats:
+            filters = dict(filters, stats=True)
         K = self._model.args.audio_num_codebooks
         audio_mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(self.device)
         pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
@@ -217,6 +224,8 @@ class Generator:
         for i in range(max_audio_frames):
             sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads, **filters)
             samples.append(sample)
+            if return_stats:
+                fstats.append(self._model._decode_state.frame_stats())        # (a device copy: the host reads it after the loop)
             if len(samples) - checked >= step or i == max_audio_frames - 1:
                 eos = (torch.cat(samples[checked:], 0) == 0).all(dim=1)                 # one host look per chunk
                 hit = eos.nonzero()
@@ -227,11 +236,19 @@ class Generator:
             curr_tokens = torch.cat([sample.long(), pad], dim=1).unsqueeze(1)
             curr_mask = audio_mask
             curr_pos = curr_pos[:, -1:] + 1
+        stats = SampleStats.of_frames(K, fstats[:len(samples)]) if return_stats else None
         if not samples:
-            return torch.zeros(0, device=self.device)
+            audio = torch.zeros(0, device=self.device)
+            return (audio, stats) if return_stats else audio
         codes = torch.stack(samples).permute(1, 2, 0).long()
         audio = self._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
-        return audio if out_rs is None else out_rs(audio)
+        audio = audio if out_rs is None else out_rs(audio)
+        return (audio, stats) if return_stats else audio
+
+    def _stats_check(self, return_stats):
+        """``return_stats`` is refused where the frames cannot give it, before any cache is taken over."""
+        if return_stats and not getattr(self._model, "use_kv_cache", True):
+            raise ValueError("the recompute path (use_kv_cache = False) has no return_stats: the statistics need the KV-cache path")
 
     def _prompt(self, text: str, speaker: int, context: List[Segment], max_audio_frames: int):
         """Prompt frames of ``generate`` / ``generate_stream``: (tokens [1,S,K+1], mask [1,S,K+1], positions [1,S])."""
@@ -255,7 +272,7 @@ class Generator:
                         temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4,
                         adapter: Optional[str] = None, top_p: float = 1.0, min_p: float = 0.0,
                         output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
-                        repetition_window=64, voice=None, typical_p=1.0) -> Iterator[torch.Tensor]:
+                        repetition_window=64, voice=None, typical_p=1.0, return_stats: bool = False) -> Iterator[torch.Tensor]:
         """``generate`` that hands the audio out while it is being made: an iterator of 1-D device tensors of
         ``chunk_frames * 1920`` samples (the last one may be shorter), decoded by the audio tokenizer's stateful
         ``decode_stream()``.  The frames are sampled by the same ``generate_frame`` calls in the same order as ``generate``,
@@ -267,14 +284,17 @@ class Generator:
         ``ResampleStream`` - they concatenate to ``generate(..., output_sample_rate=)``'s audio bit for bit; the stream lags by
         the filter's half-width, and what it still owes comes as one last short chunk.
         ``voice``: as for ``generate`` - the call is ``conversation(voice=voice, context=context,
-        adapter=adapter).generate_stream(text, speaker, ...)``."""
+        adapter=adapter).generate_stream(text, speaker, ...)``.
+        ``return_stats``: the iterator yields (chunk, ``SampleStats`` of the chunk's frames) - read with the chunk's one host
+        look; the resampler's last short chunk comes with no frames."""
         if voice is not None:
             return self.conversation(context, adapter, voice=voice).generate_stream(
                 text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, top_p, min_p, output_sample_rate,
-                repetition_penalty, repetition_window, typical_p=typical_p)
+                repetition_penalty, repetition_window, typical_p=typical_p, return_stats=return_stats)
         temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
                                                      repetition_window, typical_p=typical_p)
         out_rs = self._out_resampler(output_sample_rate)
+        self._stats_check(return_stats)
         if int(chunk_frames) != chunk_frames or chunk_frames < 1:
             raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
         if not callable(getattr(self._audio_tokenizer, "decode_stream", None)):
@@ -283,11 +303,11 @@ class Generator:
         ads = self._resolve_adapters([adapter])
         self._run += 1
         return self._stream(self._run, text, speaker, context, max_audio_length_ms, temperature, topk, int(chunk_frames), ads,
-                            filters, out_rs)
+                            filters, out_rs, return_stats)
 
     @torch.inference_mode()
     def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames, ads=None, filters={},
-                out_rs=None):
+                out_rs=None, return_stats=False):
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later generate / generate_batch / generate_stream call on "
@@ -302,33 +322,38 @@ class Generator:
         K = self._model.args.audio_num_codebooks
         audio_mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(self.device)
         pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
-        pending = []
+        pending, fstats = [], []
+        if return_stats:
+            filters = dict(filters, stats=True)
         for i in range(max_audio_frames):
             sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads, **filters)
             pending.append(sample)
+            if return_stats:
+                fstats.append(self._model._decode_state.frame_stats())
             if len(pending) == chunk_frames or i == max_audio_frames - 1:
                 codes = torch.stack(pending).permute(1, 2, 0).long()                       # [1, K, n]
                 hit = (codes[0] == 0).all(dim=0).nonzero()                                  # the chunk's one host look
                 n = int(hit[0]) if hit.numel() else codes.shape[2]
                 if n:
                     chunk = decoder.step(codes[:, :, :n]).reshape(-1)
-                    yield chunk if out is None else out.feed(chunk)
+                    chunk = chunk if out is None else out.feed(chunk)
+                    yield (chunk, SampleStats.of_frames(K, fstats[:n])) if return_stats else chunk
                     check()
                 if hit.numel():
                     break
-                pending = []
+                pending, fstats = [], []
             curr_tokens = torch.cat([sample.long(), pad], dim=1).unsqueeze(1)
             curr_mask = audio_mask
             curr_pos = curr_pos[:, -1:] + 1
         if out is not None and out.pos:                                # the samples the resampler still owes (its lag)
-            yield out.flush()
+            yield (out.flush(), SampleStats(K)) if return_stats else out.flush()
 
     @torch.inference_mode()
     def generate_batch(self, texts: List[str], speakers: List[int], contexts: List[List[Segment]],
                        max_audio_length_ms: float = 90_000, temperature: float = 0.9, topk: int = 50,
                        eos_check_every: int = 8, adapters: Optional[List[Optional[str]]] = None, top_p=1.0,
                        min_p=0.0, output_sample_rate: Optional[int] = None, repetition_penalty=1.0,
-                       repetition_window=64, typical_p=1.0) -> List[torch.Tensor]:
+                       repetition_window=64, typical_p=1.0, return_stats: bool = False) -> List[torch.Tensor]:
         """``generate`` for up to 16 utterances at once (not in the reference, whose loop is single-utterance): the prompts
         (different lengths) are prefilled one by one into their rows of the KV caches, then every decode frame advances all
         rows together - the decode kernels share each weight load between the batch rows, so B utterances cost about as
@@ -345,8 +370,10 @@ class Generator:
         ``repetition_penalty`` / ``repetition_window`` (``generate``): a number or one value per utterance; with them, or with an
         entry per utterance that is a sequence of K numbers (one per codebook) in any of the six, every row samples through the
         processed rows sampler with its own parameters.  A flat sequence of B numbers is one value per utterance, as before.
-        ``output_sample_rate``: as for ``generate``, for every utterance."""
+        ``output_sample_rate``: as for ``generate``, for every utterance.
+        ``return_stats``: return (the audio list, one ``SampleStats`` per utterance), as for ``generate``."""
         out_rs = self._out_resampler(output_sample_rate)
+        self._stats_check(return_stats)
         B = len(texts)
         if not (1 <= B <= 16 and len(speakers) == B and len(contexts) == B):
             raise ValueError("generate_batch takes 1..16 utterances with one speaker id and one context list each")
@@ -373,7 +400,10 @@ class Generator:
             msks.append(torch.cat(m_, 0).bool().to(self.device))
             if toks[-1].size(0) >= self._model.bb.max_seq_len - max_audio_frames:
                 raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {self._model.bb.max_seq_len - max_audio_frames}")
+        if return_stats:
+            filters = dict(filters, stats=True)
         frames = [self._model.engine.generate_first_frames(toks, msks, temperature, topk, adapters=ads, **filters)]          # [B, K] each
+        fstats = [self._model._decode_state.frame_stats()] if return_stats else []
         mask = torch.cat([torch.ones(B, K, dtype=torch.bool), torch.zeros(B, 1, dtype=torch.bool)], 1).unsqueeze(1).to(self.device)
         pad = torch.zeros(B, 1, dtype=torch.long, device=self.device)
         pos = torch.ones(B, 1, dtype=torch.long, device=self.device)       # only "not the prompt" matters: positions live on the device
@@ -389,16 +419,20 @@ class Generator:
                     break
             tokens = torch.cat([frames[-1].long(), pad], dim=1).unsqueeze(1)
             frames.append(self._model.generate_frame(tokens, mask, pos, temperature, topk, **filters))
-        out = []
+            if return_stats:
+                fstats.append(self._model._decode_state.frame_stats())
+        out, stats = [], []
         codes_all = torch.stack(frames, 2).long()                                                    # [B, K, T]
         for b in range(B):
             n = eos_at[b] if eos_at[b] is not None else min(len(frames), max_audio_frames)
+            if return_stats:
+                stats.append(SampleStats.of_frames(K, fstats[:n], b))
             if n == 0:
                 out.append(torch.zeros(0, device=self.device))
             else:
                 audio = self._audio_tokenizer.decode(codes_all[b:b + 1, :, :n]).squeeze(0).squeeze(0)
                 out.append(audio if out_rs is None else out_rs(audio))
-        return out
+        return (out, stats) if return_stats else out
 
     def _batch_sampling(self, temperature, topk, B):
         """``generate_batch``'s temperature / topk: numbers pass through; a sequence must have one valid value per utterance
@@ -411,7 +445,7 @@ class Generator:
               row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
               output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
               repetition_window=64, row_typical: bool = False, typical_p=1.0, streams: Optional[int] = None,
-              max_lead_ms: Optional[float] = None, clock=None, sleep=None):
+              max_lead_ms: Optional[float] = None, clock=None, sleep=None, stats: bool = False):
         """A running batch (csm/serving.py): ``server.submit(text, speaker, context, adapter=None, seed=None,
         max_audio_length_ms=90_000)`` queues an utterance, ``server.step()`` makes the next ``chunk_frames`` frames of audio for
         every utterance that holds one of the ``slots`` (<= 16) rows - utterances join at chunk boundaries, stream their audio
@@ -444,11 +478,13 @@ class Generator:
         the middle of their utterances (one launch out, one in; the module docstring's "More listeners than slots"), with the
         same codes and audio per seeded request.  ``max_lead_ms``: a request that far ahead of its listener's clock is not
         scheduled (``clock`` / ``sleep``: ``time.monotonic`` / ``time.sleep`` unless given; all three need ``streams``).  It
-        adds ``req.pause()`` / ``req.resume()``; ``server.cancel(req, heard_frames=None)`` works on every server."""
+        adds ``req.pause()`` / ``req.resume()``; ``server.cancel(req, heard_frames=None)`` works on every server.
+        ``stats=True``: every request carries ``req.stats``, a ``SampleStats`` (``generate(return_stats=)``) that grows chunk by
+        chunk with its codes, across park / resume, and is cut by ``cancel(heard_frames=)``; one more launch per frame."""
         from .serving import BatchServer
         return BatchServer(self, slots, chunk_frames, temperature, topk, hear_slots, row_sampling, row_filters, top_p, min_p,
                            output_sample_rate, row_processors, repetition_penalty, repetition_window, row_typical, typical_p,
-                           streams, max_lead_ms, clock, sleep)
+                           streams, max_lead_ms, clock, sleep, stats)
 
     def voice(self, context: List[Segment], adapter: Optional[str] = None):
         """A voice prompt prefilled ONCE (csm/conversation.py: ``Voice``): the segments are tokenised and Mimi-encoded as every

@@ -107,6 +107,7 @@ _SIGS = {
     "csm_sample_filtered_rows": ([_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p], _i),
     "csm_sample_processed_rows": ([_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p], _i),
     "csm_sample_typical_rows": ([_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p], _i),
+    "csm_sample_stats_rows": ([_p, _p, _p, _p, _p, _i, _i, _i, _p], _i),
     "csm_rvq_encode": ([_p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "csm_conv1d_f32": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "csm_conv_transpose1d_f32": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p], _i),

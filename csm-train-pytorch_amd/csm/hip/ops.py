@@ -848,6 +848,25 @@ def sample_typical_rows(logits_f32, q_f32, out_i32, topk_i32, temperature_f32, t
                                                         typical_p_f32), (hist_i32, frame_i32, live_i32), advance, V)
 
 
+def sample_stats_rows(logits_f32, codes_i32, logprob=None, entropy=None, pmax=None, V=None):
+    """What the model thought of each drawn code (``csm_sample_stats_rows``): row r of ``logits_f32`` [rows, >= V] (any row stride)
+    with ``codes_i32[r]`` -> ``logprob[r]`` (log_softmax at the code; -inf for a code outside [0, V)), ``entropy[r]`` (nats) and
+    ``pmax[r]`` of softmax(row) - temperature 1, no filter, no penalty.  Each output is an fp32 tensor of ``rows`` elements or
+    None (not computed); at least one must be given.  Returns (logprob, entropy, pmax)."""
+    assert logits_f32.dim() == 2 and logits_f32.dtype == torch.float32 and logits_f32.stride(1) == 1
+    rows = logits_f32.shape[0]
+    V = V or logits_f32.shape[1]
+    assert codes_i32.dtype == torch.int32 and codes_i32.is_contiguous() and codes_i32.numel() == rows
+    ptrs = []
+    for o in (logprob, entropy, pmax):
+        assert o is None or (o.dtype == torch.float32 and o.is_contiguous() and o.numel() == rows and o.device == logits_f32.device)
+        ptrs.append(None if o is None else o.data_ptr())
+    ldl = logits_f32.stride(0) if rows > 1 else max(logits_f32.stride(0), V)
+    check(lib.csm_sample_stats_rows(logits_f32.data_ptr(), codes_i32.data_ptr(), *ptrs, rows, V, ldl, _stream()),
+          "csm_sample_stats_rows")
+    return logprob, entropy, pmax
+
+
 def rvq_encode(x_f32, codebooks_f32, codes_i64, n_semantic=1):
     T, D = x_f32.shape
     K, Cn, D2 = codebooks_f32.shape

@@ -525,13 +525,16 @@ class Model(nn.Module):
     @torch.no_grad()
     def generate_frame(self, tokens: torch.Tensor, tokens_mask: torch.Tensor, input_pos: torch.Tensor, temperature: float,
                        topk: int, noise: Optional[List[torch.Tensor]] = None, adapters=None, top_p=None,
-                       min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None) -> torch.Tensor:
+                       min_p=None, repetition_penalty=None, repetition_window=None, typical_p=None,
+                       stats: bool = False) -> torch.Tensor:
         """Reference model.py:140-195: one frame of K codes, [B, K] int32.  ``noise`` (K tensors [B, V_a] of Exp(1)
         draws) pins the sampler for parity tests.  ``adapters``: a LoRAState or None per batch row (csm/lora_bank.py), read
         on a generation's first call.  ``temperature`` / ``topk``: two numbers, a sequence of B values for either one, or None for
         both - one pair per row through the rows sampler (``Engine.generate_frame``).  ``top_p`` / ``min_p``: None (not named), or
         a number / B values for either one - the filtered rows sampler (``sample_filtered_rows``).  ``typical_p``: None, or a number /
-        B entries - locally typical sampling through the typical rows sampler (``sample_typical_rows``)."""
+        B entries - locally typical sampling through the typical rows sampler (``sample_typical_rows``).  ``stats`` (read on a
+        generation's first call): the state also writes each drawn code's log-probability, entropy and largest probability
+        (``DecodeState.enable_stats``; ``model._decode_state.frame_stats()`` after the call)."""
         assert self.caches_are_enabled(), "backbone caches are not enabled"
         return self.engine.generate_frame(tokens, tokens_mask, input_pos, temperature, topk, noise, adapters, top_p, min_p,
-                                          repetition_penalty, repetition_window, typical_p)
+                                          repetition_penalty, repetition_window, typical_p, stats)

@@ -288,6 +288,7 @@ class RowSampler:
         self.B, self.K, self.vocab, self.device = B, K, vocab, device
         self.level, self.params, self.rows = 0, None, None
         self.code_hist, self.hist_frame, self.hist_live, self.live_rows = None, None, None, None
+        self.stats = False                                # (DecodeState.enable_stats: the frame body also writes the statistics)
 
     def need(self, level):
         if self.level < level:
@@ -391,9 +392,10 @@ class RowSampler:
     def graph_key(self, temperature, topk):
         """The key of the captured frame graph a frame call with these two replays: the pair itself, or - None for both - what
         tells the rows samplers apart (the kernels read the parameters from the buffers: any change of them replays the graph)."""
+        tag = ("stats",) if self.stats else ()              # (statistics mode is another frame body: DecodeState.enable_stats)
         if temperature is None and topk is None:
-            return (None, None) + (LEVELS[self.level].tag or ())
-        return (float(temperature), int(topk))
+            return (None, None) + (LEVELS[self.level].tag or ()) + tag
+        return (float(temperature), int(topk)) + tag
 
     @property
     def row_sampling(self):
@@ -414,3 +416,49 @@ class RowSampler:
     def row_typical(self):
         """Per row, seven tuples of K values - the six and ``typical_p`` - at level 4, else None."""
         return [r[:LEVELS[4].reads] for r in self.rows] if self.level == 4 else None
+
+
+class SampleStats:
+    """What the model thought of the codes of an utterance (``return_stats=True`` / ``serve(stats=True)``): ``logprob``,
+    ``entropy`` (nats) and ``pmax``, fp32 [frames, K] each on the CPU - per frame and codebook, the log-probability of the drawn
+    code and the entropy and largest probability of the distribution it was drawn from, at temperature 1 with no filter and no
+    penalty (``csm_sample_stats_rows``).  The frames are the frames of the codes: what lies past EOS or the length limit is cut.
+    ``-logprob.sum()`` is the next-frame training objective's loss on the utterance, summed over its rows."""
+
+    NAMES = ("logprob", "entropy", "pmax")
+
+    def __init__(self, K, data=None):
+        self.K = int(K)
+        self._data = torch.zeros(3, 0, self.K) if data is None else data          # [3, frames, K]
+
+    @classmethod
+    def of_frames(cls, K, frames, b=0):
+        """From per-frame device tensors [3, K, B] (``DecodeState.frame_stats``), column ``b``: one host copy."""
+        if not len(frames):
+            return cls(K)
+        return cls(K, torch.stack([f[:, :, b] for f in frames], 1).float().cpu())
+
+    logprob = property(lambda self: self._data[0])
+    entropy = property(lambda self: self._data[1])
+    pmax = property(lambda self: self._data[2])
+
+    def __len__(self):
+        return self._data.shape[1]
+
+    def extend(self, other):
+        """The frames of ``other`` after this one's (a served request grows chunk by chunk)."""
+        self._data = torch.cat([self._data, other._data], 1)
+        return self
+
+    def cut(self, frames):
+        """Keep the first ``frames`` frames."""
+        self._data = self._data[:, :max(int(frames), 0)]
+        return self
+
+    def summary(self):
+        """The command line's JSON object (``--stats-file``): per frame, codebook 0's three numbers; per frame, the sum of all
+        K log-probabilities; and their mean over every code of the utterance (None for no frames)."""
+        n = len(self)
+        return {"codebook0": {name: [float(v) for v in self._data[j, :, 0]] for j, name in enumerate(self.NAMES)},
+                "frame_logprob": [float(v) for v in self.logprob.double().sum(1)],
+                "mean_logprob": float(self.logprob.double().mean()) if n else None}

@@ -134,7 +134,7 @@ import torch
 
 from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, hear_resampler, open_heard_turn
 from .engine import DecodeState
-from .sampling import FULL_LEVEL, HIST_FRAMES, LEVELS, NAMES, PARAMS, _as_list, _is_number, check_row, own_params
+from .sampling import FULL_LEVEL, HIST_FRAMES, LEVELS, NAMES, PARAMS, SampleStats, _as_list, _is_number, check_row, own_params
 
 
 MAX_STREAMS = 256           # the most requests in flight on a ``streams`` server (each keeps a codec state for its whole life)
@@ -163,6 +163,7 @@ class Request:
         self.done = False
         self.chunks: List[torch.Tensor] = []
         self._codes: List[torch.Tensor] = []
+        self.stats = None                        # serve(stats=True): a SampleStats that grows chunk by chunk with ``_codes``
         self._tokens, self._mask, self._device = tokens, mask, device
         self._sampled = 0                        # frames sampled / handed out so far
         self._emitted = 0
@@ -386,6 +387,7 @@ class ServedConversation:
         self._push(tt.long(), tm.bool())
         req = Request(srv._next_id, text, speaker, self.adapter, self.seed, max_audio_frames, feed_t, feed_m, self._gen.device, *params)
         req._conv, req._base, req.sample_rate, req._srv = self, self._tokens.shape[0], srv.sample_rate, srv
+        req.stats = SampleStats(srv._K) if srv.sample_stats else None
         srv._next_id += 1
         srv._queue.append(req)
         self._open = req
@@ -430,14 +432,19 @@ class BatchServer:
     sequence of K values (one per codebook), and every draw goes through the processed rows sampler, which remembers each slot's
     last 64 frames (``DecodeState.set_row_processors``).  ``row_typical`` (needs ``row_sampling``; includes what ``row_processors``
     gives): ``typical_p`` joins the requests' defaults, a number or K numbers, and every draw goes through the typical rows
-    sampler (``DecodeState.set_row_typical``); a request at 1.0 has the codes it has with ``row_processors``."""
+    sampler (``DecodeState.set_row_typical``); a request at 1.0 has the codes it has with ``row_processors``.
+    ``stats`` (``sample_stats`` on the server; ``server.stats`` is its counters): the state runs in statistics mode
+    (``DecodeState.enable_stats``: one more launch per frame) and every request carries ``req.stats``, a ``SampleStats`` that
+    grows chunk by chunk with its codes - read with the chunk's one host look.  The numbers are per frame, not state: nothing
+    moves with a parked row, and ``cancel(req, heard_frames=k)`` cuts them to k frames."""
 
     def __init__(self, gen, slots: int = 16, chunk_frames: int = 4, temperature: float = 0.9, topk: int = 50, hear_slots: int = 0,
                  row_sampling: bool = False, row_filters: bool = False, top_p: float = 1.0, min_p: float = 0.0,
                  output_sample_rate: Optional[int] = None, row_processors: bool = False, repetition_penalty=1.0,
                  repetition_window=HIST_FRAMES, row_typical: bool = False, typical_p=1.0, streams: Optional[int] = None,
-                 max_lead_ms: Optional[float] = None, clock=None, sleep=None):
+                 max_lead_ms: Optional[float] = None, clock=None, sleep=None, stats: bool = False):
         out_rs = gen._out_resampler(output_sample_rate)      # (a bad rate raises here, before anything is taken over)
+        gen._stats_check(stats)
         if streams is None:
             for name, v in (("max_lead_ms", max_lead_ms), ("clock", clock), ("sleep", sleep)):
                 if v is not None:
@@ -495,6 +502,9 @@ class BatchServer:
         more = {} if self.streams is None else {"state_slots": self.streams}
         with torch.inference_mode():
             self._state = DecodeState(self._model.engine, self.slots, bank=list(self._bank.values()))
+            self.sample_stats = bool(stats)
+            if self.sample_stats:
+                self._state.enable_stats()               # (before the first capture)
             self._codec = codec.decode_stream_rows(slots=self.slots, max_chunk_frames=self.chunk_frames, **more)
         # heard turns: one rows encoder for all conversations (None: each conversation makes its own MimiEncodeStream).  Made
         # outside inference mode: ``conv.hear`` opens its slot (an in-place zero fill of the state) from ordinary caller code
@@ -609,6 +619,7 @@ class BatchServer:
                     raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
         req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device, *params)
         req.sample_rate, req._voice, req._srv = self.sample_rate, voice, self
+        req.stats = SampleStats(self._K) if self.sample_stats else None
         self._next_id += 1
         self._queue.append(req)
         return req
@@ -740,6 +751,8 @@ class BatchServer:
         self._tok[:, 0, :self._K] = torch.where(live[:, 0].bool(), out.long(), self._tok[:, 0, :self._K])
         for b in rows:
             self._rows[b]._sampled += 1
+        if self.sample_stats:
+            self._fstats.append(st.frame_stats())        # (a device copy: the chunk's look reads it)
         return out
 
     def _set_rows(self, rows, params, joined=False):
@@ -810,6 +823,14 @@ class BatchServer:
                 self._last_h = torch.zeros(self.slots, h.shape[-1], dtype=h.dtype, device=h.device)
             self._last_h[b] = h
         first = st.serve_first(self._last_h, joined, *self._sample_args())
+        if self.sample_stats:
+            # the chunk's first frame: the joined rows' columns over what the running rows' frame left (or alone)
+            fs = st.frame_stats()
+            if self._fstats:
+                fs[:, :, [b for b in range(self.slots) if b not in joined]] = self._fstats[0][:, :, [b for b in range(self.slots) if b not in joined]]
+                self._fstats[0] = fs
+            else:
+                self._fstats.append(fs)
         for b in joined:
             self._tok[b, 0, :self._K] = first[b]
             self._rows[b]._sampled = 1
@@ -831,6 +852,7 @@ class BatchServer:
                 self.last_join_rows = 0
                 return []
         running = [b for b in range(self.slots) if self._rows[b] is not None]
+        self._fstats = []                                # statistics mode: one [3, K, slots] device tensor per frame of the chunk
         first = self._frame(running) if running else None
         joined, first_j = self._admit(fresh)
         self.last_join_rows = len(joined)
@@ -848,8 +870,11 @@ class BatchServer:
             # (a conversation's row is never idled: an idle frame would overwrite position 1 of its history - module docstring)
             rows = [b for b in held if self._rows[b]._conv is not None or self._rows[b]._sampled < self._rows[b].max_audio_frames]
             frames.append(self._frame(rows) if rows else frames[-1])
+            if self.sample_stats and not rows:
+                self._fstats.append(self._fstats[-1])
         chunk = torch.stack(frames, 2).long()                                        # [slots, K, n]
         allz = (chunk == 0).all(dim=1).cpu()                                         # the chunk's one host look
+        fstats = torch.stack(self._fstats, 1).cpu() if self.sample_stats else None   # [3, n, K, slots], with the same look
         keep, done = {}, {}
         for b in held:
             req = self._rows[b]
@@ -884,6 +909,8 @@ class BatchServer:
                 part = (spoken[b] if b in spoken else audio[heard.index(b), :keep[b] * (audio.shape[1] // n)]).clone()
                 req.chunks.append(part)
                 req._codes.append(chunk[b, :, :keep[b]].clone())
+                if fstats is not None:
+                    req.stats.extend(SampleStats(K, fstats[:, :keep[b], :, b].clone()))
                 req._emitted += keep[b]
             else:
                 part = torch.zeros(0, device=self._gen.device)
@@ -1034,6 +1061,8 @@ class BatchServer:
             raise ValueError(f"heard_frames must be an integer >= 0 (None: every frame emitted), got {heard_frames!r}")
         if req.done:
             return
+        if req.stats is not None and heard_frames is not None:
+            req.stats.cut(heard_frames)
         b = req.slot
         if b is None and req._row is None:
             self._queue.remove(req)

@@ -694,6 +694,86 @@ extern "C" int csm_sample_typical_rows(const float* logits, const float* q, int*
                          SampleTypical{topk, temperature, top_p, min_p, penalty, window, hist, ldh, frame, live, advance, typical_p});
 }
 
+// What the model itself thought of a drawn code (csm_sample_stats_rows): the log-probability of codes[row], the entropy and the
+// largest probability of softmax(logits[row]) - temperature 1, no filter, no penalty: the distribution every sampler knob acts
+// on, and the likelihood the next-frame training objective sums.  One workgroup per row; the row is held in registers as the
+// sampler holds it (thread t owns columns t + 256 j), so memory is read once.  With m = max x, d_i = x_i - m, e_i = expf(d_i):
+//   S = sum e_i,  A = sum e_i d_i;   logprob = (x_code - m) - ln S,  entropy = ln S - A / S,  pmax = 1 / S.
+// Order of every sum: a thread's columns ascending (j = 0, 1, ..), the wave butterfly of wave_sum / wave_max, then the four wave
+// partials from LDS in wave order - no atomics, nothing depends on gridDim: a row's bits are the same alone and among 511 others.
+// The drawn code's logit is picked out of the registers by the thread that owns its column (a compare per slot, no dynamic
+// index: no scratch); that thread writes logprob.  A code outside [0, V) has no owner: thread 0 writes -inf.  A column at -inf
+// has e = 0 and adds nothing to A (the limit of e d, not the NaN of 0 * inf).
+namespace {
+template <int NPT>
+__global__ __launch_bounds__(256) void sample_stats_kernel(const float* __restrict__ logits, const int* __restrict__ codes,
+                                                           float* __restrict__ logprob, float* __restrict__ entropy,
+                                                           float* __restrict__ pmax, int V, int ldl) {
+    __shared__ float red[3][4];
+    const int row = blockIdx.x;
+    const float* x = logits + (size_t)row * ldl;
+    const int code = codes[row];                            // (block-uniform, in flight with the row)
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float val[NPT];
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int c = threadIdx.x + 256 * j;
+        val[j] = c < V ? x[c] : -INFINITY;
+    }
+    float tmax = val[0], xc = 0.f;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        tmax = fmaxf(tmax, val[j]);
+        if (threadIdx.x + 256 * j == code) xc = val[j];
+    }
+    tmax = wave_max(tmax);
+    if (lane == 0) red[0][w] = tmax;
+    __syncthreads();
+    const float m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    float s = 0.f, a = 0.f;
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        if (threadIdx.x + 256 * j < V) {
+            const float d = val[j] - m;
+            const float e = expf(d);
+            s += e;
+            if (e > 0.f) a += e * d;
+        }
+    }
+    s = wave_sum(s);
+    a = wave_sum(a);
+    if (lane == 0) { red[1][w] = s; red[2][w] = a; }
+    __syncthreads();
+    const float S = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    const float A = ((red[2][0] + red[2][1]) + red[2][2]) + red[2][3];
+    const float lnS = logf(S);
+    const bool inside = (unsigned)code < (unsigned)V;
+    if (logprob) {
+        if (inside && (code & 255) == (int)threadIdx.x) logprob[row] = (xc - m) - lnS;
+        if (!inside && threadIdx.x == 0) logprob[row] = -INFINITY;
+    }
+    if (threadIdx.x == 0) {
+        if (entropy) entropy[row] = lnS - A / S;
+        if (pmax) pmax[row] = 1.f / S;
+    }
+}
+}  // namespace
+
+extern "C" int csm_sample_stats_rows(const float* logits, const int* codes, float* logprob, float* entropy, float* pmax,
+                                     int rows, int V, int ldl, hipStream_t stream) {
+    CSM_REQUIRE(logits && codes, "csm_sample_stats_rows: null logits or codes");
+    CSM_REQUIRE(logprob || entropy || pmax, "csm_sample_stats_rows: no output (logprob, entropy and pmax are all null)");
+    CSM_REQUIRE(rows > 0, "csm_sample_stats_rows: rows=%d must be positive", rows);
+    CSM_REQUIRE(V > 0 && V <= 256 * SMP_PER_THREAD, "csm_sample_stats_rows: V=%d outside 1..%d", V, 256 * SMP_PER_THREAD);
+    CSM_REQUIRE(ldl >= V, "csm_sample_stats_rows: ldl=%d is below V=%d", ldl, V);
+    CSM_REQUIRE(((uintptr_t)logits | (uintptr_t)codes | (uintptr_t)logprob | (uintptr_t)entropy | (uintptr_t)pmax) % 4 == 0,
+                "csm_sample_stats_rows: a pointer is not 4-byte aligned");
+    if (V <= 256 * 9) hipLaunchKernelGGL((sample_stats_kernel<9>), dim3(rows), dim3(256), 0, stream, logits, codes, logprob, entropy, pmax, V, ldl);
+    else hipLaunchKernelGGL((sample_stats_kernel<SMP_PER_THREAD>), dim3(rows), dim3(256), 0, stream, logits, codes, logprob, entropy, pmax, V, ldl);
+    CSM_CHECK_LAUNCH("csm_sample_stats_rows");
+    return 0;
+}
+
 extern "C" int csm_rvq_encode(const float* x, const float* codebooks, long long* codes, int T, int K, int C, int D,
                               int n_semantic, hipStream_t stream) {
     CSM_REQUIRE(x && codebooks && codes && T > 0 && K > 0 && C > 0, "csm_rvq_encode: bad arguments");

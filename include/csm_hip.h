@@ -291,6 +291,18 @@ int csm_sample_typical_rows(const float* logits, const float* q, int* out, int r
                             const float* temperature, const float* top_p, const float* min_p, const float* penalty,
                             const int* window, int* hist, int ldh, int* frame, const int* live, int advance,
                             const float* typical_p, csm_stream_t stream);
+/* What the model thought of a drawn code (additive, ABI 3): row r reads x = logits + r * ldl, V floats (columns V .. ldl-1 are
+ * never read) and codes[r].  With m = max x, S = sum exp(x_i - m), A = sum exp(x_i - m) (x_i - m):
+ *   logprob[r] = x[codes[r]] - m - ln S   the model's own log-likelihood of the code: temperature 1, no filter, no penalty;
+ *   entropy[r] = ln S - A / S             in nats;
+ *   pmax[r]    = 1 / S                    the largest probability of the row.
+ * A code outside [0, V) gives logprob = -inf; the other two are still written.  Any of the three output pointers may be NULL
+ * (that output is not written); at least one must be given.  One workgroup per row, the row in registers, one pass over memory,
+ * sums joined in a fixed order without atomics: a launch gives the same bits every time, and a row's three numbers do not depend
+ * on `rows` or on the other rows.  Refused (1, nothing launched): null logits or codes, all three outputs null, rows < 1, V
+ * outside 1..4096, ldl < V, a pointer that is not 4-byte aligned.  Error bound: DESIGN.md section 6. */
+int csm_sample_stats_rows(const float* logits, const int* codes, float* logprob, float* entropy, float* pmax, int rows, int V,
+                          int ldl, csm_stream_t stream);
 
 /* ---- K15: batch-1 decode of Model.generate_frame (model.py:161-195) against KV caches ------------------------------ *
  * y[b][n] = sum_k x[b][k] W[n][k] (+ residual[b][n]), B <= 16 (weight-streaming matrix-vector product).  B <= 4: VALU kernels,

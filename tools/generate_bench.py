@@ -16,7 +16,8 @@ alternated on one model at B = 1 / 4 / 16, and the bytes of decode weights in ea
 server step with row_sampling off / on (serve_sampling_main); GEN_SERVE_SAMPLING=processors: the processed rows sampler (repetition penalty, per-codebook
 parameters; serve_processors_main); GEN_SERVE_SAMPLING=typical: the typical rows sampler (typical_p) at identity, one-wave and
 block-wide, and the server step with row_processors / row_typical (serve_typical_main); GEN_SERVE_SAMPLING=filters: the filtered rows sampler (top-p / min-p)
-in four forms and the server step with row_filters off / on (serve_filters_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
+in four forms and the server step with row_filters off / on (serve_filters_main).  GEN_SERVE_STATS=1: csm_sample_stats_rows alone at
+512 rows and the 16-row server step with stats off / on (serve_stats_main).  GEN_SERVE_CONV=1: 16 six-turn conversations on the running batch (BatchServer.conversation):
 time to the first chunk of turns 1 / 3 / 5 against stateless submits, one append_rows against one-row calls, park / resume, aggregate
 frames/s (serve_conv_main).  GEN_HEAR=1: a 5 s heard turn's last sample to the first chunk of the reply, with
 ``add(Segment)`` against ``hear`` fed during the turn, served (16 slots) and at B = 1 (hear_main), then the batched hearing of
@@ -1016,6 +1017,53 @@ def serve_sampling_main():
               f"frame (off's own repeats span {(max(meds['off']) - min(meds['off'])) * 1e3:.2f} ms)", flush=True)
 
 
+def serve_stats_main():
+    """GEN_SERVE_STATS=1: per-request sampling statistics (Generator.serve(stats=True)), in the shape of GEN_SERVE_SAMPLING=1.
+    (a) csm_sample_stats_rows alone at the frame's shape, 512 rows (32 codebooks x 16 slots), V = 2051 in the padded buffer -
+    200 back-to-back launches between two synchronisations, median (min .. max) of GEN_ROUNDS repeats (default 5).  (b) the
+    steady 16-row server step of GEN_SERVE's setting (CSM-1B random init, 16 slots, chunk_frames 4, 5 s of context each,
+    per-row seeds): stats off (the yardstick) against on; each leg is a fresh server, the two alternated GEN_ROUNDS times
+    (default 3), per leg the median of 20 steps and the spread of the repeats' medians."""
+    dev = "cuda:0"
+    n = 4
+    V, ld, rows = 2051, 2112, 512
+    g = torch.Generator(device=dev).manual_seed(0)
+    lg = torch.randn(rows, ld, device=dev, generator=g) * 2
+    codes = torch.randint(0, V, (rows,), device=dev, generator=g, dtype=torch.int32)
+    out = torch.empty(3, rows, dtype=torch.float32, device=dev)
+    f = lambda: ops.sample_stats_rows(lg, codes, out[0], out[1], out[2], V=V)      # noqa: E731
+    rounds = int(os.environ.get("GEN_ROUNDS", 5))
+    _timed(f, 20)
+    v = sorted(_timed(f, 200) for _ in range(rounds))
+    kernel = v[len(v) // 2]
+    print(f"GEN_SERVE_STATS (a) csm_sample_stats_rows, {rows} rows, V={V}: median {kernel * 1e6:.2f} us per launch "
+          f"(min {v[0] * 1e6:.2f}, max {v[-1] * 1e6:.2f}; {rounds} x 200 back-to-back launches)", flush=True)
+    rounds = int(os.environ.get("GEN_ROUNDS", 3))
+    codec = make_codec(dev)
+    model = Model(csm_1b_args(), device=dev, seed=0)
+    gen = Generator(model, text_tokenizer=ByteTokenizer(), audio_tokenizer=codec)
+    ctx = [Segment(0, "hello there", torch.randn(5 * 24000, device=dev) * 0.1)]
+    text = "the quick brown fox jumps over the lazy dog"
+    meds = {"off": [], "on": []}
+    for _ in range(rounds):
+        for name in meds:
+            srv = gen.serve(slots=16, chunk_frames=n, stats=name == "on")
+            for i in range(16):
+                srv.submit(f"utterance number {i}: {text}", i, ctx, seed=i, max_audio_length_ms=80 * 400)
+            _timed(srv.step, 1)                                              # 16 prefills + the first chunk
+            _timed(srv.step, 2)                                              # eager warm-up frame, graph capture
+            steps = sorted(_timed(srv.step, 1) for _ in range(20))
+            meds[name].append(steps[len(steps) // 2])
+    for name, v in meds.items():
+        print(f"GEN_SERVE_STATS (b) server step, 16 rows x {n} frames, stats {name}: medians of 20 steps "
+              f"{[round(x * 1e3, 2) for x in v]} ms -> median {sorted(v)[len(v) // 2] * 1e3:.2f} ms, spread of the repeats "
+              f"{(max(v) - min(v)) * 1e3:.2f} ms", flush=True)
+    off, on = sorted(meds["off"])[rounds // 2], sorted(meds["on"])[rounds // 2]
+    print(f"GEN_SERVE_STATS (b) stats on - off: {(on - off) * 1e3:+.3f} ms per step = {(on - off) * 1e6 / n:+.1f} us per frame = "
+          f"{(on - off) / n / kernel:+.1f} stand-alone kernel times (off's own repeats span "
+          f"{(max(meds['off']) - min(meds['off'])) * 1e3:.2f} ms)", flush=True)
+
+
 def serve_filters_main():
     """GEN_SERVE_SAMPLING=filters: per-request top-p / min-p (Generator.serve(row_sampling=True, row_filters=True)), in the shape of
     GEN_SERVE_SAMPLING=1.  (a) the sampler alone, 16 rows, V = 2051 in the model's padded logits buffer, four forms: csm_sample_topk
@@ -1820,6 +1868,8 @@ def main():
     if os.environ.get("GEN_HEAR") == "1":
         hear_main()
         return hear_rows_main()
+    if os.environ.get("GEN_SERVE_STATS") == "1":
+        return serve_stats_main()
     if os.environ.get("GEN_SERVE_SAMPLING") == "1":
         return serve_sampling_main()
     if os.environ.get("GEN_SERVE_SAMPLING") == "filters":
