@@ -9,44 +9,111 @@ sampled; the other party's audio is Mimi-encoded once, when it is ``add``ed - or
 still being spoken (``HeardTurn``), which takes the encode off the path between its last sample and our first chunk.
 """
 from contextlib import contextmanager
-from typing import Iterator, List, Optional
+from typing import Iterator, List, NamedTuple, Optional
 
 import torch
 
 from .engine import DecodeState
+from .generator import sampling_kwargs
+from .sampling import SampleStats
 
 OVERFLOW = ("error", "drop_oldest", "shift")
 
 
-def check_keep_turns(keep_turns) -> int:
-    """``keep_turns`` of both conversation classes: an integer >= 0 (bool is refused: it is not a count)."""
-    if isinstance(keep_turns, bool) or not isinstance(keep_turns, int) or keep_turns < 0:
-        raise ValueError(f"keep_turns must be an integer >= 0, got {keep_turns!r}")
-    return keep_turns
+class _Call(NamedTuple):
+    """One ``generate`` / ``generate_stream`` call of a ``Generator`` or a ``Conversation``, checked (``prepare_call``)."""
+    temperature: object
+    topk: object
+    filters: dict              # the other keywords of the frame calls (``sampling_kwargs``), ``stats=True`` among them when asked
+    out_rs: object             # the ``Resampler`` to ``output_sample_rate``, or None
+    return_stats: bool
+    max_audio_frames: int
+    every: int                 # frames between two host looks for EOS: ``eos_check_every``, a stream's ``chunk_frames``
 
 
-def fit_history(conv, n_new: int, limit: int):
-    """``_fit`` of both conversation classes, the part they share.  The reference's length rule (generator.py:168-170) on history
-    + new text: ``drop_oldest`` and ``shift`` drop whole turns, the oldest first AFTER the ``keep_turns`` leading ones (the
-    voice prompt), until it holds.  Raises the reference's error - with nothing changed - when it cannot.  Returns None when
-    nothing had to go; else (head, gone): positions ``head .. head+gone-1`` of the OLD history were cut out of ``_tokens`` /
-    ``_mask`` / ``_turns``; what becomes of the cache is the caller's."""
-    L = conv._tokens.shape[0]
-    if L + n_new < limit:
-        return None
-    first = min(conv._keep_turns, len(conv._turns))
-    drop, left = first, L
-    if conv._on_overflow != "error":
-        while drop < len(conv._turns) and left + n_new >= limit:
-            left -= conv._turns[drop]
-            drop += 1
-    if left + n_new >= limit:
-        raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
-    head, gone = sum(conv._turns[:first]), L - left
-    conv._tokens = torch.cat([conv._tokens[:head], conv._tokens[head + gone:]], 0) if head else conv._tokens[gone:]
-    conv._mask = torch.cat([conv._mask[:head], conv._mask[head + gone:]], 0) if head else conv._mask[gone:]
-    conv._turns = conv._turns[:first] + conv._turns[drop:]
-    return head, gone
+def prepare_call(gen, max_audio_length_ms, temperature, topk, top_p, min_p, repetition_penalty, repetition_window, typical_p,
+                 output_sample_rate, return_stats, eos_check_every=None, chunk_frames=None, stateless=False) -> _Call:
+    """What every ``generate`` / ``generate_stream`` does first: the sampling values (``sampling_kwargs``), the output rate,
+    ``return_stats`` of a ``stateless`` call (a ``Generator``'s own: it may be on the recompute path) and - for a stream, which
+    names ``chunk_frames`` - the chunk size and the codec's ``decode_stream`` are checked, so a bad one raises at the call, before
+    any cache or run counter is touched."""
+    temperature, topk, filters = sampling_kwargs(gen, temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
+                                                 typical_p=typical_p)
+    out_rs = gen._out_resampler(output_sample_rate)
+    if stateless:
+        gen._stats_check(return_stats)
+    if chunk_frames is None:
+        every = max(1, int(eos_check_every))
+    else:
+        if int(chunk_frames) != chunk_frames or chunk_frames < 1:
+            raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
+        codec, every = gen._audio_tokenizer, int(chunk_frames)
+        if not callable(getattr(codec, "decode_stream", None)):
+            raise TypeError(f"{type(codec).__name__} has no decode_stream(): streaming needs a stateful decoder "
+                            "(decoding chunks independently would be wrong at the chunk edges)")
+    if return_stats:
+        filters = dict(filters, stats=True)
+    return _Call(temperature, topk, filters, out_rs, return_stats, int(max_audio_length_ms / 80), every)
+
+
+class _Turn:
+    """A spoken utterance in flight: the sampled frames, how many of them were handed out and - a conversation's turn - how many
+    were fed back into its cache."""
+
+    def __init__(self):
+        self.samples: List[torch.Tensor] = []
+        self.stats: List[torch.Tensor] = []        # per sample, its frame's statistics on the device (return_stats)
+        self.kept = 0                              # frames handed to the caller so far (stream) / kept (generate)
+        self.base = 0                              # history length (= cached positions) after the text frames
+        self.fed = 0                               # samples[:fed] have been fed to the backbone (one position each)
+        self.done = False
+
+
+def drive(turn: _Turn, step, call: _Call):
+    """THE utterance loop.  ``step(turn)`` samples the next frame into ``turn.samples`` (the first one from the prompt, every
+    later one from the frame before it; with ``return_stats`` its statistics into ``turn.stats``), so the frame calls are enqueued
+    back to back; the all-zero EOS test runs on the device and the host looks at it once per ``call.every`` frames and at the
+    last one.  Every look sets ``turn.kept`` and yields the slice of ``turn.samples`` it adds to the kept frames - the frames
+    before the EOS frame; the look that finds it is the last.  Frames sampled past EOS are never kept."""
+    looked = 0                                     # samples[:looked] are known not to be EOS
+    for i in range(call.max_audio_frames):
+        step(turn)
+        n = len(turn.samples)
+        if n - looked >= call.every or i == call.max_audio_frames - 1:
+            hit = (torch.cat(turn.samples[looked:], 0) == 0).all(dim=1).nonzero()                  # one host look per chunk
+            turn.kept = looked + int(hit[0]) if hit.numel() else n
+            yield slice(looked, turn.kept)
+            if hit.numel():
+                return
+            looked = n
+
+
+def spoken(gen, turn: _Turn, call: _Call):
+    """What ``generate`` returns for a driven turn: ONE decode of its kept frames (and their statistics)."""
+    samples = turn.samples[:turn.kept]
+    audio = torch.zeros(0, device=gen.device)
+    if samples:
+        audio = gen._audio_tokenizer.decode(torch.stack(samples).permute(1, 2, 0).long()).squeeze(0).squeeze(0)
+        audio = audio if call.out_rs is None else call.out_rs(audio)
+    if not call.return_stats:
+        return audio
+    return audio, SampleStats.of_frames(gen._model.args.audio_num_codebooks, turn.stats[:turn.kept])
+
+
+def stream_spoken(gen, turn: _Turn, step, call: _Call, check):
+    """What ``generate_stream`` yields: ``drive`` with every look's frames pushed through the codec's stateful decoder (and the
+    resampler stream).  ``check()`` raises once the stream was invalidated - asked after every chunk handed out."""
+    K = gen._model.args.audio_num_codebooks
+    decoder = gen._audio_tokenizer.decode_stream()
+    out = call.out_rs.stream() if call.out_rs is not None else None
+    for new in drive(turn, step, call):
+        if new.stop > new.start:
+            chunk = decoder.step(torch.stack(turn.samples[new]).permute(1, 2, 0).long()).reshape(-1)       # codes [1, K, n]
+            chunk = chunk if out is None else out.feed(chunk)
+            yield (chunk, SampleStats.of_frames(K, turn.stats[new])) if call.return_stats else chunk
+            check()
+    if out is not None and out.pos:                                # the samples the resampler still owes (its lag)
+        yield (out.flush(), SampleStats(K)) if call.return_stats else out.flush()
 
 
 class Voice:
@@ -112,18 +179,6 @@ def make_voice(gen, context, adapter=None) -> Voice:
     st = DecodeState(e, 1, ads)
     st.prefill(tokens.unsqueeze(0), mask.unsqueeze(0))
     return Voice(gen, tokens, mask, [t.shape[0] for t in toks], st.park_row(0, tokens.shape[0]), adapter)
-
-
-class _Turn:
-    """A spoken turn in flight: the sampled frames, how many of them were fed back into the cache, how many were handed out."""
-
-    def __init__(self, base: int, n_text: int):
-        self.base, self.n_text = base, n_text      # history length (= cached positions) after the text frames
-        self.samples: List[torch.Tensor] = []
-        self.stats: List[torch.Tensor] = []        # per sample, its frame's statistics on the device (return_stats)
-        self.fed = 0                               # samples[:fed] have been fed to the backbone (one position each)
-        self.kept = 0                              # frames handed to the caller so far (stream) / kept (generate)
-        self.done = False
 
 
 class HeardTurn:
@@ -204,32 +259,126 @@ def hear_resampler(gen, sample_rate):
     return rate_resampler("sample_rate", sample_rate, gen.sample_rate, gen.device, to_native=True)
 
 
-def open_heard_turn(conv, speaker: int, sample_rate=None) -> HeardTurn:
-    """``hear`` of both conversation classes: at most one heard turn is open per conversation; its encode stream is made at the
-    first ``hear`` and started anew (``reset()``) for every later one.  ``sample_rate``: the rate of what ``feed`` will get; one
-    other than the codec's puts a ``ResampleStream`` (one per rate, kept like the encode stream) in front of the encoder."""
-    rs = hear_resampler(conv._gen, sample_rate)
-    if conv._heard is not None:
-        raise RuntimeError("hear: this conversation already has a heard turn open - end() or cancel() it first")
-    if conv._enc is None:
-        codec = conv._gen._audio_tokenizer
-        if not callable(getattr(codec, "encode_stream", None)):
-            raise TypeError(f"{type(codec).__name__} has no encode_stream(): hearing a turn as it arrives needs a stateful encoder")
-        conv._enc = codec.encode_stream()
-    else:
-        conv._enc.reset()
-    stream = None
-    if rs is not None:
-        stream = conv._hear_rs.get(rs.orig_sr)
-        if stream is None:
-            stream = conv._hear_rs[rs.orig_sr] = rs.stream()
+class _History:
+    """The dialogue history of ``Conversation`` and ``ServedConversation`` (csm/serving.py): the frames the model has been
+    conditioned on (``_tokens`` / ``_mask``), the lengths of the turns that make them up (``_turns``), how many leading positions
+    have their K / V cached (``_cached``), the length rule and the other party's turns (``add`` / ``hear``).  Where the cached
+    K / V live - a state of its own, a parked tensor between two slots - is the subclass's, and so is ``_before_history(what)``:
+    what ``add`` and ``HeardTurn.end`` do before they extend the history."""
+
+    def __init__(self, gen, on_overflow: str, keep_turns: int, voice):
+        if on_overflow not in OVERFLOW:
+            raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
+        if isinstance(keep_turns, bool) or not isinstance(keep_turns, int) or keep_turns < 0:       # (a bool is not a count)
+            raise ValueError(f"keep_turns must be an integer >= 0, got {keep_turns!r}")
+        self._gen, self._on_overflow, self._keep_turns = gen, on_overflow, keep_turns
+        K1 = gen._model.args.audio_num_codebooks + 1
+        self._tokens = torch.zeros(0, K1, dtype=torch.long, device=gen.device)
+        self._mask = torch.zeros(0, K1, dtype=torch.bool, device=gen.device)
+        self._turns: List[int] = []                # lengths of the turns that make up the history
+        self._cached = 0
+        self._heard: Optional[HeardTurn] = None    # the other party's turn being heard (hear), at most one
+        self._enc = None                           # its encode stream: made at the first hear, reused
+        self._hear_rs = {}                         # hear(sample_rate=): input rate -> its ResampleStream, made once, reused
+        if voice is not None:                      # the history starts as the voice's frames, already cached (``voice.kv``)
+            self._tokens, self._mask, self._turns, self._cached = voice.tokens, voice.mask, list(voice.turns), voice.positions
+
+    # ---- read-only views ---------------------------------------------------------------------------------------------------
+    @property
+    def tokens(self) -> torch.Tensor:
+        return self._tokens
+
+    @property
+    def mask(self) -> torch.Tensor:
+        return self._mask
+
+    @property
+    def cached(self) -> int:
+        return self._cached
+
+    # ---- history -----------------------------------------------------------------------------------------------------------
+    @torch.inference_mode()
+    def add(self, segment) -> None:
+        """The other party's turn (or any context segment): only THIS segment is tokenised and Mimi-encoded, here, once.  It
+        enters the cache with the next spoken turn."""
+        if self._heard is not None:
+            raise RuntimeError("add: a heard turn is open on this conversation - end() or cancel() it first")
+        self._before_history("add")
+        t, m = self._gen._tokenize_segment(segment)
+        self._push(t.long(), m.bool())
+
+    def hear(self, speaker: int, sample_rate: Optional[int] = None) -> HeardTurn:
+        """The other party starts to speak: ``turn.feed(audio)`` Mimi-encodes the turn as it arrives, ``turn.end(text)`` enters it
+        as ``add`` would - with nothing left to encode but its last partial frame.  ``sample_rate``: the rate of the samples
+        ``feed`` will get (None: the codec's 24 kHz); another rate is resampled on the device as it arrives, and the turn enters
+        as ``add`` of ``ops.resample(whole, sample_rate, 24000)`` would.
+        At most one heard turn is open per conversation; its encode stream is made at the first ``hear`` and started anew
+        (``reset()``) for every later one, and so is the ``ResampleStream`` of each rate."""
+        rs = hear_resampler(self._gen, sample_rate)
+        if self._heard is not None:
+            raise RuntimeError("hear: this conversation already has a heard turn open - end() or cancel() it first")
+        if self._enc is None:
+            codec = self._gen._audio_tokenizer
+            if not callable(getattr(codec, "encode_stream", None)):
+                raise TypeError(f"{type(codec).__name__} has no encode_stream(): hearing a turn as it arrives needs a stateful encoder")
+            self._enc = codec.encode_stream()
         else:
-            stream.reset()
-    conv._heard = HeardTurn(conv, speaker, conv._enc, stream)
-    return conv._heard
+            self._enc.reset()
+        stream = None
+        if rs is not None:
+            stream = self._hear_rs.get(rs.orig_sr)
+            if stream is None:
+                stream = self._hear_rs[rs.orig_sr] = rs.stream()
+            else:
+                stream.reset()
+        self._heard = HeardTurn(self, speaker, self._enc, stream)
+        return self._heard
+
+    def _push(self, t, m):
+        self._tokens = torch.cat([self._tokens, t.to(self._tokens.device)], 0)
+        self._mask = torch.cat([self._mask, m.to(self._mask.device)], 0)
+        self._turns.append(t.shape[0])
+
+    def _close_turn(self, frames):
+        """The spoken turn the text frames opened is over: its kept frames ([k, K] codes) and one all-zero EOS frame enter the
+        history (the layout of ``Generator._tokenize_segment``)."""
+        k, K = frames.shape
+        t = torch.zeros(k + 1, K + 1, dtype=torch.long, device=self._tokens.device)
+        t[:k, :K] = frames
+        m = torch.zeros(k + 1, K + 1, dtype=torch.bool, device=self._mask.device)
+        m[:, :K] = True
+        self._tokens = torch.cat([self._tokens, t], 0)
+        self._mask = torch.cat([self._mask, m], 0)
+        self._turns[-1] += k + 1
+
+    def fit_history(self, n_new: int, limit: int):
+        """The reference's length rule (generator.py:168-170) on history + new text: ``drop_oldest`` and ``shift`` drop whole
+        turns, the oldest first AFTER the ``keep_turns`` leading ones (the voice prompt), until it holds.  Raises the
+        reference's error - with nothing changed - when it cannot.  Returns None when nothing had to go; else (head, out): the
+        cut starts at position ``head`` of the OLD history and is gone from ``_tokens`` / ``_mask`` / ``_turns``; ``out`` of its
+        positions were cached (<= 0: none) - what becomes of the cache is the caller's."""
+        L = self._tokens.shape[0]
+        if L + n_new < limit:
+            return None
+        first = min(self._keep_turns, len(self._turns))
+        drop, left = first, L
+        if self._on_overflow != "error":
+            while drop < len(self._turns) and left + n_new >= limit:
+                left -= self._turns[drop]
+                drop += 1
+        if left + n_new >= limit:
+            raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
+        head, gone = sum(self._turns[:first]), L - left
+        self._tokens = torch.cat([self._tokens[:head], self._tokens[head + gone:]], 0) if head else self._tokens[gone:]
+        self._mask = torch.cat([self._mask[:head], self._mask[head + gone:]], 0) if head else self._mask[gone:]
+        self._turns = self._turns[:first] + self._turns[drop:]
+        return head, min(self._cached, head + gone) - head
 
 
-class Conversation:
+open_heard_turn = _History.hear        # (the name it had as a free function: ``open_heard_turn(conv, speaker, sample_rate)``)
+
+
+class Conversation(_History):
     """``Generator.conversation(...)``.  One dialogue, B = 1.
 
     ``tokens`` / ``mask`` ([L, K+1]) are the frame history the model has been conditioned on, laid out as the reference lays out
@@ -250,63 +399,18 @@ class Conversation:
 
     def __init__(self, gen, context=(), adapter: Optional[str] = None, on_overflow: str = "error", keep_turns: int = 0,
                  voice: Optional[Voice] = None):
-        if on_overflow not in OVERFLOW:
-            raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
-        self._keep_turns = check_keep_turns(keep_turns)
-        self._gen, self._m = gen, gen._model
+        super().__init__(gen, on_overflow, keep_turns, voice)
+        self._m = gen._model
         if voice is not None:
             adapter = voice.check(gen, adapter, "conversation")
         self._ads = gen._resolve_adapters([adapter])
-        self._on_overflow = on_overflow
-        K1 = self._m.args.audio_num_codebooks + 1
-        self._tokens = torch.zeros(0, K1, dtype=torch.long, device=gen.device)
-        self._mask = torch.zeros(0, K1, dtype=torch.bool, device=gen.device)
-        self._turns: List[int] = []                # lengths of the turns that make up the history
-        self._cached = 0
         self._state: Optional[DecodeState] = None
         self._run = 0
         self._open: Optional[_Turn] = None
-        self._heard: Optional[HeardTurn] = None    # the other party's turn being heard (hear), at most one
-        self._enc = None                           # its encode stream: made at the first hear, reused
-        self._hear_rs = {}                         # hear(sample_rate=): input rate -> its ResampleStream, made once, reused
-        # a voice: the history starts as its frames, already cached - its K / V enter the state the first turn makes
-        self._fork = None                          # the voice's parked K / V while they wait for that state (never written)
-        if voice is not None:
-            self._tokens, self._mask, self._turns = voice.tokens, voice.mask, list(voice.turns)
-            self._cached, self._fork = voice.positions, voice.kv
+        # a voice's K / V, parked, while they wait for the state the first turn makes (never written)
+        self._fork = voice.kv if voice is not None else None
         for seg in context:
             self.add(seg)
-
-    # ---- read-only views ---------------------------------------------------------------------------------------------------
-    @property
-    def tokens(self) -> torch.Tensor:
-        return self._tokens
-
-    @property
-    def mask(self) -> torch.Tensor:
-        return self._mask
-
-    @property
-    def cached(self) -> int:
-        return self._cached
-
-    # ---- history -----------------------------------------------------------------------------------------------------------
-    @torch.inference_mode()
-    def add(self, segment) -> None:
-        """The other party's turn (or any context segment): only THIS segment is tokenised and Mimi-encoded.  It enters the cache
-        with the next spoken turn."""
-        if self._heard is not None:
-            raise RuntimeError("add: a heard turn is open on this conversation - end() or cancel() it first")
-        self._before_history("add")
-        t, m = self._gen._tokenize_segment(segment)
-        self._push(t.long(), m.bool())
-
-    def hear(self, speaker: int, sample_rate: Optional[int] = None) -> HeardTurn:
-        """The other party starts to speak: ``turn.feed(audio)`` Mimi-encodes the turn as it arrives, ``turn.end(text)`` enters it
-        as ``add`` would - with nothing left to encode but its last partial frame.  ``sample_rate``: the rate of the samples
-        ``feed`` will get (None: the codec's 24 kHz); another rate is resampled on the device as it arrives, and the turn enters
-        as ``add`` of ``ops.resample(whole, sample_rate, 24000)`` would."""
-        return open_heard_turn(self, speaker, sample_rate)
 
     def _before_history(self, what):
         """What ``add`` and ``HeardTurn.end`` do before they extend the history: an open stream of this conversation is
@@ -321,21 +425,15 @@ class Conversation:
         self._settle()
         self._state, self._cached, self._fork = None, 0, None
 
-    def _push(self, t, m):
-        self._tokens = torch.cat([self._tokens, t.to(self._tokens.device)], 0)
-        self._mask = torch.cat([self._mask, m.to(self._mask.device)], 0)
-        self._turns.append(t.shape[0])
-
     def _fit(self, n_new: int, max_audio_frames: int):
         """The reference's length rule on history + new text (``fit_history``).  Under ``drop_oldest`` what is kept is prefilled
         again.  Under ``shift`` the cache slides instead: ONE ``DecodeState.shift_row`` takes the cut's cached positions out and
         rotates the keys behind them back (cut positions that were only pending just leave the pending tokens), so the turn is
         fed by ``append`` like any other - unless nothing cached is left, which is ``drop_oldest``."""
-        cut = fit_history(self, n_new, self._m.bb.max_seq_len - max_audio_frames)
+        cut = self.fit_history(n_new, self._m.bb.max_seq_len - max_audio_frames)
         if cut is None:
             return
-        head, gone = cut
-        out = min(self._cached, head + gone) - head                # cached positions among the cut ones
+        head, out = cut
         if self._on_overflow != "shift" or self._cached - max(out, 0) < 1:
             self._cached = 0
         elif out > 0:
@@ -353,9 +451,15 @@ class Conversation:
         finally:
             m._decode_state = prev
 
-    def _begin(self, text, speaker, max_audio_frames, temperature, topk, filters={}, stats=False) -> _Turn:
-        """Feed what the cache lacks plus the new line's text frames, sample the first frame."""
+    def _step(self, text, speaker, call: _Call):
+        """``step`` of ``drive`` for this conversation's next turn."""
+        return lambda turn: self._next_frame(turn, call) if turn.samples else self._begin(turn, text, speaker, call)
+
+    def _begin(self, turn: _Turn, text, speaker, call: _Call):
+        """Feed what the cache lacks plus the new line's text frames, sample the first frame: ``turn`` is now the open one."""
         m, e = self._m, self._m.engine
+        temperature, topk, filters = call.temperature, call.topk, dict(call.filters)
+        stats = filters.pop("stats", False)
         if not getattr(m, "use_kv_cache", True):
             raise RuntimeError("a Conversation keeps the KV cache between turns: model.use_kv_cache must be on")
         tt, tm = self._gen._tokenize_text_segment(text, speaker)
@@ -364,7 +468,7 @@ class Conversation:
             self._state = DecodeState(e, 1, self._ads)
             self._state.resume_row(0, self._fork)
             self._fork = None
-        self._fit(tt.shape[0], max_audio_frames)
+        self._fit(tt.shape[0], call.max_audio_frames)
         new_t = torch.cat([self._tokens[self._cached:], tt.long()], 0)
         new_m = torch.cat([self._mask[self._cached:], tm.bool()], 0)
         e._need()
@@ -378,8 +482,8 @@ class Conversation:
         else:
             last_h = st.append(new_t, new_m)
         self._push(tt.long(), tm.bool())
-        self._cached = self._tokens.shape[0]
-        turn = self._open = _Turn(self._cached, tt.shape[0])
+        self._cached = turn.base = self._tokens.shape[0]
+        self._open = turn
         if filters:                                                  # (the rows path of this conversation's state)
             temperature, topk = st.sampling_args(temperature, topk, **filters)
             if st.sampler.keeps_history:
@@ -389,19 +493,19 @@ class Conversation:
         turn.samples.append(e._frame_tail(st, last_h, temperature, topk, None))
         if stats:
             turn.stats.append(st.frame_stats())
-        return turn
 
-    def _next_frame(self, turn: _Turn, temperature, topk, filters={}, stats=False):
+    def _next_frame(self, turn: _Turn, call: _Call):
         """Feed the last sampled frame, sample the next one (``Model.generate_frame`` on this conversation's state)."""
         K = self._m.args.audio_num_codebooks
         dev = self._gen.device
         tokens = torch.cat([turn.samples[-1].long(), torch.zeros(1, 1, dtype=torch.long, device=dev)], dim=1).unsqueeze(1)
         mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(dev)
         with self._installed():
-            s = self._m.generate_frame(tokens, mask, torch.ones(1, 1, dtype=torch.long), temperature, topk, **filters)
+            s = self._m.generate_frame(tokens, mask, torch.ones(1, 1, dtype=torch.long), call.temperature, call.topk,
+                                       **call.filters)
         turn.fed += 1
         turn.samples.append(s)
-        if stats:
+        if call.return_stats:
             turn.stats.append(self._state.frame_stats())
 
     def _settle(self):
@@ -411,16 +515,8 @@ class Conversation:
         if turn is None or turn.done:
             return
         turn.done = True
-        K = self._m.args.audio_num_codebooks
         k = turn.kept
-        frames = torch.zeros(k + 1, K + 1, dtype=torch.long, device=self._tokens.device)
-        if k:
-            frames[:k, :K] = torch.cat(turn.samples[:k], 0).long()
-        fmask = torch.zeros(k + 1, K + 1, dtype=torch.bool, device=self._mask.device)
-        fmask[:, :K] = True
-        self._tokens = torch.cat([self._tokens, frames], 0)
-        self._mask = torch.cat([self._mask, fmask], 0)
-        self._turns[-1] += k + 1                                   # the text frames opened this turn
+        self._close_turn(torch.cat(turn.samples[:k], 0) if k else self._tokens[:0, :-1])
         # positions base .. base+fed-1 hold samples[:fed]; of those the kept frames stay.  The EOS frame always enters with the
         # next turn's append, also where eos_check_every > 1 had fed it already (a decode step and an append round differently):
         # what the cache holds after a turn does not depend on how often the host looked for EOS
@@ -438,41 +534,22 @@ class Conversation:
         / ``repetition_window`` / ``typical_p``, per-codebook sequences, ``output_sample_rate`` and ``return_stats`` included: this
         turn's) and EOS handling as ``Generator.generate``.  The repetition window looks at this turn's frames only.  The first
         turn with ``return_stats`` puts the conversation's state into statistics mode, where it stays."""
-        from .generator import sampling_kwargs
-        from .sampling import SampleStats
-        temperature, topk, filters = sampling_kwargs(self._gen, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window, typical_p=typical_p)
-        out_rs = self._gen._out_resampler(output_sample_rate)
+        return self._speak(text, speaker, prepare_call(self._gen, max_audio_length_ms, temperature, topk, top_p, min_p,
+                                                        repetition_penalty, repetition_window, typical_p, output_sample_rate,
+                                                        return_stats, eos_check_every=eos_check_every))
+
+    @torch.inference_mode()
+    def _speak(self, text, speaker, call: _Call):
+        """``generate`` for a prepared call (``Generator.generate(voice=)`` makes its own): the turn driven to its end."""
         self._run += 1
         self._settle()
-        max_audio_frames = int(max_audio_length_ms / 80)
-        step = max(1, int(eos_check_every))
-        turn, checked = None, 0
+        turn = _Turn()
         try:
-            for i in range(max_audio_frames):
-                if turn is None:
-                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk, filters, return_stats)
-                else:
-                    self._next_frame(turn, temperature, topk, filters, return_stats)
-                n = len(turn.samples)
-                if n - checked >= step or i == max_audio_frames - 1:
-                    hit = (torch.cat(turn.samples[checked:], 0) == 0).all(dim=1).nonzero()          # one host look per chunk
-                    if hit.numel():
-                        turn.kept = checked + int(hit[0])
-                        break
-                    checked = turn.kept = n
+            for _ in drive(turn, self._step(text, speaker, call), call):
+                pass
         finally:
-            samples = turn.samples[:turn.kept] if turn is not None else []
-            fstats = turn.stats[:turn.kept] if turn is not None else []
             self._settle()
-        stats = SampleStats.of_frames(self._m.args.audio_num_codebooks, fstats) if return_stats else None
-        if not samples:
-            audio = torch.zeros(0, device=self._gen.device)
-            return (audio, stats) if return_stats else audio
-        codes = torch.stack(samples).permute(1, 2, 0).long()
-        audio = self._gen._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
-        audio = audio if out_rs is None else out_rs(audio)
-        return (audio, stats) if return_stats else audio
+        return spoken(self._gen, turn, call)
 
     def generate_stream(self, text: str, speaker: int, max_audio_length_ms: float = 90_000, temperature: float = 0.9,
                         topk: int = 50, chunk_frames: int = 4, top_p: float = 1.0, min_p: float = 0.0,
@@ -481,58 +558,26 @@ class Conversation:
         """``generate`` handing the audio out chunk by chunk, as ``Generator.generate_stream`` does (``return_stats``: (chunk,
         ``SampleStats``) pairs, likewise); under the same seed the chunks concatenate to ``generate``'s audio.  A later call on
         THIS conversation invalidates the stream."""
-        from .generator import sampling_kwargs
-        temperature, topk, filters = sampling_kwargs(self._gen, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window, typical_p=typical_p)
-        out_rs = self._gen._out_resampler(output_sample_rate)
-        if int(chunk_frames) != chunk_frames or chunk_frames < 1:
-            raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
-        codec = self._gen._audio_tokenizer
-        if not callable(getattr(codec, "decode_stream", None)):
-            raise TypeError(f"{type(codec).__name__} has no decode_stream(): streaming needs a stateful decoder "
-                            "(decoding chunks independently would be wrong at the chunk edges)")
+        return self._speak_stream(text, speaker, prepare_call(self._gen, max_audio_length_ms, temperature, topk, top_p, min_p,
+                                                               repetition_penalty, repetition_window, typical_p,
+                                                               output_sample_rate, return_stats, chunk_frames=chunk_frames))
+
+    def _speak_stream(self, text, speaker, call: _Call):
+        """``generate_stream`` for a prepared call: this conversation's open stream, if any, ends here; the new one is returned."""
         self._run += 1
         self._settle()
-        return self._stream(self._run, text, speaker, max_audio_length_ms, temperature, topk, int(chunk_frames), filters, out_rs,
-                            return_stats)
+        return self._stream(self._run, text, speaker, call)
 
     @torch.inference_mode()
-    def _stream(self, run, text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, filters={}, out_rs=None,
-                return_stats=False):
-        from .sampling import SampleStats
-        K = self._m.args.audio_num_codebooks
-
+    def _stream(self, run, text, speaker, call: _Call):
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later call on the same Conversation took its turn")
 
         check()
-        max_audio_frames = int(max_audio_length_ms / 80)
-        decoder = self._gen._audio_tokenizer.decode_stream()
-        out = out_rs.stream() if out_rs is not None else None
-        turn, done = None, 0
+        turn = _Turn()
         try:
-            for i in range(max_audio_frames):
-                if turn is None:
-                    turn = self._begin(text, speaker, max_audio_frames, temperature, topk, filters, return_stats)
-                else:
-                    self._next_frame(turn, temperature, topk, filters, return_stats)
-                if len(turn.samples) - done == chunk_frames or i == max_audio_frames - 1:
-                    codes = torch.stack(turn.samples[done:]).permute(1, 2, 0).long()               # [1, K, n]
-                    hit = (codes[0] == 0).all(dim=0).nonzero()                                     # the chunk's one host look
-                    n = int(hit[0]) if hit.numel() else codes.shape[2]
-                    turn.kept = done + n
-                    fstats = turn.stats[done:done + n]
-                    done = len(turn.samples)
-                    if n:
-                        chunk = decoder.step(codes[:, :, :n]).reshape(-1)
-                        chunk = chunk if out is None else out.feed(chunk)
-                        yield (chunk, SampleStats.of_frames(K, fstats)) if return_stats else chunk
-                        check()
-                    if hit.numel():
-                        break
-            if out is not None and out.pos:                            # the samples the resampler still owes (its lag)
-                yield (out.flush(), SampleStats(K)) if return_stats else out.flush()
+            yield from stream_spoken(self._gen, turn, self._step(text, speaker, call), call, check)
         finally:
-            if turn is not None and self._open is turn:
+            if self._open is turn:
                 self._settle()

@@ -1482,12 +1482,11 @@ class DecodeState:
         ``prefill_row``.  Returns the segments' last hidden rows [R, d] in the order of ``rows``.  A segment's bits do not depend
         on what is stacked with it; one segment on a one-row state equals ``append``."""
         m = self.e.m
-        rows = [int(b) for b in rows]
+        rows = list(rows)
         R = len(rows)
         if not (1 <= R <= 16 and len(tokens_list) == R and len(masks_list) == R):
             raise ValueError(f"append_rows takes 1..16 rows with one token and one mask tensor each (got {R} rows)")
-        if len(set(rows)) != R or any(not 0 <= b < self.B for b in rows):
-            raise ValueError(f"append_rows: rows must be distinct rows of 0..{self.B - 1}, got {rows}")
+        rows = self._distinct_rows(rows, "append_rows")
         K1 = tokens_list[0].shape[-1]
         tks = [t.reshape(-1, K1).to(device=m.device, dtype=torch.int64) for t in tokens_list]
         mks = [k.reshape(-1, K1).to(device=m.device, dtype=torch.uint8) for k in masks_list]
@@ -1519,13 +1518,32 @@ class DecodeState:
             self.row_pos[b] = p0 + n - 1
         return torch.stack(last).contiguous()
 
+    # ---- the checks of the methods that move histories between rows ------------------------------------------------------------
+    def _row(self, b) -> int:
+        b = int(b)
+        if not 0 <= b < self.B:
+            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        return b
+
+    def _distinct_rows(self, rows, what: str):
+        rows = [int(b) for b in rows]
+        if len(set(rows)) != len(rows) or any(not 0 <= b < self.B for b in rows):
+            raise ValueError(f"{what}: rows must be distinct rows of 0..{self.B - 1}, got {rows}")
+        return rows
+
+    def _check_parked(self, parked, what: str, fits: bool = True) -> int:
+        """The length of ``parked``, a parked history of this backbone (``park_row``'s format; ``fits``: one a row can hold)."""
+        kv = self.bb.kv
+        if parked.dim() != 5 or parked.shape[:3] != (kv.shape[0], 2, kv.shape[3]) or parked.shape[4] != kv.shape[5] or \
+                parked.dtype != kv.dtype or (fits and not 1 <= parked.shape[3] <= kv.shape[4]):
+            raise ValueError(f"{what}: {tuple(parked.shape)} {parked.dtype} is not a parked history of this model's backbone")
+        return parked.shape[3]
+
     def park_row(self, b, length: int):
         """The K / V of positions 0 .. length-1 of row ``b`` in every backbone layer, as one contiguous tensor
         [layers, 2, KV, length, hd] (one strided copy of the stack's cache allocation) - what a conversation keeps while it holds
         no slot.  The depth decoder's cache is per frame and needs nothing."""
-        b, length = int(b), int(length)
-        if not 0 <= b < self.B:
-            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        b, length = self._row(b), int(length)
         if not 1 <= length <= self.row_pos[b] + 1:
             raise ValueError(f"park_row: {length} positions of row {b}, which holds {self.row_pos[b] + 1}")
         return self.bb.kv[:, :, b, :, :length].contiguous()
@@ -1533,15 +1551,8 @@ class DecodeState:
     def resume_row(self, b, parked):
         """Copy a parked history (``park_row``, of this or another row, or of another state of the same model) into row ``b`` from
         position 0 (one strided copy) and set the row's device position and host mirror to its last position."""
-        b = int(b)
-        if not 0 <= b < self.B:
-            raise ValueError(f"row {b} out of range (the state has {self.B})")
-        kv = self.bb.kv
-        length = parked.shape[3] if parked.dim() == 5 else -1
-        if parked.dim() != 5 or parked.shape[:3] != (kv.shape[0], 2, kv.shape[3]) or parked.shape[4] != kv.shape[5] or \
-                not 1 <= length <= kv.shape[4] or parked.dtype != kv.dtype:
-            raise ValueError(f"resume_row: {tuple(parked.shape)} {parked.dtype} is not a parked history of this model's backbone")
-        kv[:, :, b, :, :length].copy_(parked)
+        b, length = self._row(b), self._check_parked(parked, "resume_row")
+        self.bb.kv[:, :, b, :, :length].copy_(parked)
         self.bb.pos[b] = length - 1
         self.row_pos[b] = length - 1
 
@@ -1551,19 +1562,14 @@ class DecodeState:
         position write per row.  The same parked history may be given for several rows - one voice forked into many requests
         (csm/serving.py) - and none is written.  Leaves the caches, ``bb.pos`` and ``row_pos`` in the state the R ``resume_row``
         calls leave, bit for bit."""
-        rows, parkeds = [int(b) for b in rows], list(parkeds)
+        rows, parkeds = list(rows), list(parkeds)
         R = len(rows)
         if not (1 <= R <= 16 and len(parkeds) == R):
             raise ValueError(f"fork_rows takes 1..16 rows with one parked history each (got {R} rows, {len(parkeds)} histories)")
-        if len(set(rows)) != R or any(not 0 <= b < self.B for b in rows):
-            raise ValueError(f"fork_rows: rows must be distinct rows of 0..{self.B - 1}, got {rows}")
-        kv = self.bb.kv
+        rows = self._distinct_rows(rows, "fork_rows")
         for parked in parkeds:
-            length = parked.shape[3] if parked.dim() == 5 else -1
-            if parked.dim() != 5 or parked.shape[:3] != (kv.shape[0], 2, kv.shape[3]) or parked.shape[4] != kv.shape[5] or \
-                    not 1 <= length <= kv.shape[4] or parked.dtype != kv.dtype:
-                raise ValueError(f"fork_rows: {tuple(parked.shape)} {parked.dtype} is not a parked history of this model's backbone")
-        ops.kv_fork_rows([p.contiguous() for p in parkeds], kv, self.bb.pos, rows)
+            self._check_parked(parked, "fork_rows")
+        ops.kv_fork_rows([p.contiguous() for p in parkeds], self.bb.kv, self.bb.pos, rows)
         for b, parked in zip(rows, parkeds):
             self.row_pos[b] = parked.shape[3] - 1
 
@@ -1574,12 +1580,10 @@ class DecodeState:
         ``ops.sample_hist_move_rows`` launch, a slice of one packed buffer), and the row's noise generator, which leaves
         ``row_gen``.  The caches, positions and rings are only read: the rows stay as they are until something else is written
         there.  Adapter, sampling parameters and the last sampled frame are the caller's to keep."""
-        rows = [int(b) for b in rows]
-        R = len(rows)
-        if not 1 <= R <= 16:
-            raise ValueError(f"park_rows takes 1..16 rows, got {R}")
-        if len(set(rows)) != R or any(not 0 <= b < self.B for b in rows):
-            raise ValueError(f"park_rows: rows must be distinct rows of 0..{self.B - 1}, got {rows}")
+        rows = list(rows)
+        if not 1 <= len(rows) <= 16:
+            raise ValueError(f"park_rows takes 1..16 rows, got {len(rows)}")
+        rows = self._distinct_rows(rows, "park_rows")
         if any(self.row_pos[b] < 0 for b in rows):
             raise ValueError(f"park_rows: row {next(b for b in rows if self.row_pos[b] < 0)} holds nothing")
         kvs = ops.kv_park_rows(self.bb.kv, rows, [self.row_pos[b] + 1 for b in rows])
@@ -1608,11 +1612,7 @@ class DecodeState:
         """A parked history (``park_row``) without its positions ``keep .. keep+drop-1``: a new tensor of ``length - drop``
         positions whose keys behind the gap are rotated back by ``drop`` positions (``ops.kv_shift``, one launch) - the context
         shift that lets a conversation forget turns without prefilling the kept ones again.  Touches nothing of the state."""
-        kv = self.bb.kv
-        if parked.dim() != 5 or parked.shape[:3] != (kv.shape[0], 2, kv.shape[3]) or parked.shape[4] != kv.shape[5] or \
-                parked.dtype != kv.dtype:
-            raise ValueError(f"shift_parked: {tuple(parked.shape)} {parked.dtype} is not a parked history of this model's backbone")
-        keep, drop, length = int(keep), int(drop), parked.shape[3]
+        keep, drop, length = int(keep), int(drop), self._check_parked(parked, "shift_parked", fits=False)
         if not (drop >= 1 and keep >= 0 and keep + drop <= length and length - drop >= 1):
             raise ValueError(f"shift_parked: keep {keep} + drop {drop} of {length} positions (at least one is dropped and one is left)")
         return ops.kv_shift(parked.contiguous(), self.e.m.rope_table("backbone"), keep, drop)
@@ -1621,9 +1621,7 @@ class DecodeState:
         """Row ``b`` forgets its positions ``keep .. keep+drop-1``: ``park_row`` of all it holds, ``shift_parked``, ``resume_row``
         (which sets the device position and the host mirror to the new last position).  The other rows, the depth decoder's
         caches and the captured frame graph are not touched."""
-        b = int(b)
-        if not 0 <= b < self.B:
-            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        b = self._row(b)
         self.resume_row(b, self.shift_parked(self.park_row(b, self.row_pos[b] + 1), keep, drop))
 
     def truncate(self, length: int):
@@ -1646,8 +1644,7 @@ class DecodeState:
         the training forward for [1, S] (with the row's own adapter), its K / V rows into row ``b`` of the caches from position
         0, the row's device position and host mirror to S - 1.  Returns the last position's hidden row [d]."""
         e, m = self.e, self.e.m
-        if not 0 <= b < self.B:
-            raise ValueError(f"row {b} out of range (the state has {self.B})")
+        b = self._row(b)
         S = tk.shape[0]
         if S > m.bb.max_seq_len:
             raise ValueError("prompt longer than max_seq_len")
@@ -1730,9 +1727,7 @@ class DecodeState:
         elif seed is None:
             self.row_gen.pop(b, None)
         else:
-            g = torch.Generator(device=self.noise_buf.device)
-            g.manual_seed(int(seed))
-            self.row_gen[b] = g
+            self.row_gen[b] = self.new_row_generator(seed)
 
     def new_row_generator(self, seed):
         """A generator of the kind ``set_row_seed`` makes, for a caller that keeps it across rows (``set_row_seed(generator=)``)."""

@@ -200,73 +200,52 @@ class Generator:
         code drawn, and the entropy and largest probability of the distribution it was drawn from (temperature 1, before
         any filter or penalty), cut where the codes are cut.  The codes and the audio are the same; the frames cost one more
         launch each.  Refused on the recompute path (``model.use_kv_cache = False``)."""
+        from .conversation import _Turn, drive, prepare_call, spoken
+        call = prepare_call(self, max_audio_length_ms, temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
+                            typical_p, output_sample_rate, return_stats, eos_check_every=eos_check_every, stateless=voice is None)
         if voice is not None:
-            return self.conversation(context, adapter, voice=voice).generate(
-                text, speaker, max_audio_length_ms, temperature, topk, eos_check_every, top_p, min_p, output_sample_rate,
-                repetition_penalty, repetition_window, typical_p=typical_p, return_stats=return_stats)
-        temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window, typical_p=typical_p)
-        out_rs = self._out_resampler(output_sample_rate)
+            return self.conversation(context, adapter, voice=voice)._speak(text, speaker, call)
         ads = self._resolve_adapters([adapter])
-        self._stats_check(return_stats)
         self._run += 1
         self._model.reset_caches()
-        max_audio_frames = int(max_audio_length_ms / 80)
-        curr_tokens, curr_mask, curr_pos = self._prompt(text, speaker, context, max_audio_frames)
-        samples, fstats = [], []
-        if return_stats:
-            filters = dict(filters, stats=True)
-        K = self._model.args.audio_num_codebooks
-        audio_mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(self.device)
-        pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
-        checked = 0                                   # frames [0, checked) are known not to be EOS
-        step = max(1, int(eos_check_every))
-        for i in range(max_audio_frames):
-            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads, **filters)
-            samples.append(sample)
-            if return_stats:
-                fstats.append(self._model._decode_state.frame_stats())        # (a device copy: the host reads it after the loop)
-            if len(samples) - checked >= step or i == max_audio_frames - 1:
-                eos = (torch.cat(samples[checked:], 0) == 0).all(dim=1)                 # one host look per chunk
-                hit = eos.nonzero()
-                if hit.numel():
-                    samples = samples[:checked + int(hit[0])]
-                    break
-                checked = len(samples)
-            curr_tokens = torch.cat([sample.long(), pad], dim=1).unsqueeze(1)
-            curr_mask = audio_mask
-            curr_pos = curr_pos[:, -1:] + 1
-        stats = SampleStats.of_frames(K, fstats[:len(samples)]) if return_stats else None
-        if not samples:
-            audio = torch.zeros(0, device=self.device)
-            return (audio, stats) if return_stats else audio
-        codes = torch.stack(samples).permute(1, 2, 0).long()
-        audio = self._audio_tokenizer.decode(codes).squeeze(0).squeeze(0)
-        audio = audio if out_rs is None else out_rs(audio)
-        return (audio, stats) if return_stats else audio
+        turn = _Turn()
+        for _ in drive(turn, self._step(call, ads, *self._prompt_frames(text, speaker, context, call.max_audio_frames)), call):
+            pass
+        return spoken(self, turn, call)
 
     def _stats_check(self, return_stats):
         """``return_stats`` is refused where the frames cannot give it, before any cache is taken over."""
         if return_stats and not getattr(self._model, "use_kv_cache", True):
             raise ValueError("the recompute path (use_kv_cache = False) has no return_stats: the statistics need the KV-cache path")
 
-    def _prompt(self, text: str, speaker: int, context: List[Segment], max_audio_frames: int):
-        """Prompt frames of ``generate`` / ``generate_stream``: (tokens [1,S,K+1], mask [1,S,K+1], positions [1,S])."""
-        tokens, masks = [], []
-        for seg in context:
-            t, m = self._tokenize_segment(seg)
-            tokens.append(t)
-            masks.append(m)
-        t, m = self._tokenize_text_segment(text, speaker)
-        tokens.append(t)
-        masks.append(m)
-        prompt_tokens = torch.cat(tokens, dim=0).long().to(self.device)
-        prompt_mask = torch.cat(masks, dim=0).bool().to(self.device)
-        curr_pos = torch.arange(0, prompt_tokens.size(0)).unsqueeze(0).long().to(self.device)
+    def _prompt_frames(self, text: str, speaker: int, context: List[Segment], max_audio_frames: int, held: int = 0):
+        """Prompt frames of an utterance - the context segments, then the text: (tokens [S,K+1], mask [S,K+1]), held to the
+        reference's length rule.  ``held``: positions that come before them (a voice's) and count towards it."""
+        parts = [self._tokenize_segment(seg) for seg in context] + [self._tokenize_text_segment(text, speaker)]
+        tokens = torch.cat([t for t, _ in parts], dim=0).long().to(self.device)
+        mask = torch.cat([m for _, m in parts], dim=0).bool().to(self.device)
         max_seq_len = self._model.bb.max_seq_len - max_audio_frames
-        if prompt_tokens.size(0) >= max_seq_len:
+        if held + tokens.size(0) >= max_seq_len:
             raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {max_seq_len}")
-        return prompt_tokens.unsqueeze(0), prompt_mask.unsqueeze(0), curr_pos
+        return tokens, mask
+
+    def _step(self, call, ads, tokens, mask):
+        """``step`` of ``conversation.drive`` for a stateless call: the prompt frames first, then each sampled frame fed back."""
+        K = self._model.args.audio_num_codebooks
+        audio_mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(self.device)
+        pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
+        pos = torch.arange(0, tokens.size(0)).unsqueeze(0).long().to(self.device)
+        tokens, mask = tokens.unsqueeze(0), mask.unsqueeze(0)
+
+        def step(turn):
+            nonlocal tokens, mask, pos
+            if turn.samples:
+                tokens, mask, pos = torch.cat([turn.samples[-1].long(), pad], dim=1).unsqueeze(1), audio_mask, pos[:, -1:] + 1
+            turn.samples.append(self._model.generate_frame(tokens, mask, pos, call.temperature, call.topk, adapters=ads,
+                                                           **call.filters))
+            if call.return_stats:
+                turn.stats.append(self._model._decode_state.frame_stats())        # (a device copy: the host reads it at a look)
+        return step
 
     def generate_stream(self, text: str, speaker: int, context: List[Segment], max_audio_length_ms: float = 90_000,
                         temperature: float = 0.9, topk: int = 50, chunk_frames: int = 4,
@@ -287,27 +266,19 @@ class Generator:
         adapter=adapter).generate_stream(text, speaker, ...)``.
         ``return_stats``: the iterator yields (chunk, ``SampleStats`` of the chunk's frames) - read with the chunk's one host
         look; the resampler's last short chunk comes with no frames."""
+        from .conversation import prepare_call
+        call = prepare_call(self, max_audio_length_ms, temperature, topk, top_p, min_p, repetition_penalty, repetition_window,
+                            typical_p, output_sample_rate, return_stats, chunk_frames=chunk_frames, stateless=voice is None)
         if voice is not None:
-            return self.conversation(context, adapter, voice=voice).generate_stream(
-                text, speaker, max_audio_length_ms, temperature, topk, chunk_frames, top_p, min_p, output_sample_rate,
-                repetition_penalty, repetition_window, typical_p=typical_p, return_stats=return_stats)
-        temperature, topk, filters = sampling_kwargs(self, temperature, topk, top_p, min_p, repetition_penalty,
-                                                     repetition_window, typical_p=typical_p)
-        out_rs = self._out_resampler(output_sample_rate)
-        self._stats_check(return_stats)
-        if int(chunk_frames) != chunk_frames or chunk_frames < 1:
-            raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
-        if not callable(getattr(self._audio_tokenizer, "decode_stream", None)):
-            raise TypeError(f"{type(self._audio_tokenizer).__name__} has no decode_stream(): streaming needs a stateful decoder "
-                            "(decoding chunks independently would be wrong at the chunk edges)")
+            return self.conversation(context, adapter, voice=voice)._speak_stream(text, speaker, call)
         ads = self._resolve_adapters([adapter])
         self._run += 1
-        return self._stream(self._run, text, speaker, context, max_audio_length_ms, temperature, topk, int(chunk_frames), ads,
-                            filters, out_rs, return_stats)
+        return self._stream(self._run, text, speaker, context, call, ads)
 
     @torch.inference_mode()
-    def _stream(self, run, text, speaker, context, max_audio_length_ms, temperature, topk, chunk_frames, ads=None, filters={},
-                out_rs=None, return_stats=False):
+    def _stream(self, run, text, speaker, context, call, ads):
+        from .conversation import _Turn, stream_spoken
+
         def check():
             if self._run != run:
                 raise RuntimeError("this stream was invalidated: a later generate / generate_batch / generate_stream call on "
@@ -315,38 +286,8 @@ class Generator:
 
         check()
         self._model.reset_caches()
-        max_audio_frames = int(max_audio_length_ms / 80)
-        curr_tokens, curr_mask, curr_pos = self._prompt(text, speaker, context, max_audio_frames)
-        decoder = self._audio_tokenizer.decode_stream()
-        out = out_rs.stream() if out_rs is not None else None
-        K = self._model.args.audio_num_codebooks
-        audio_mask = torch.cat([torch.ones(1, K, dtype=torch.bool), torch.zeros(1, 1, dtype=torch.bool)], dim=1).unsqueeze(1).to(self.device)
-        pad = torch.zeros(1, 1, dtype=torch.long, device=self.device)
-        pending, fstats = [], []
-        if return_stats:
-            filters = dict(filters, stats=True)
-        for i in range(max_audio_frames):
-            sample = self._model.generate_frame(curr_tokens, curr_mask, curr_pos, temperature, topk, adapters=ads, **filters)
-            pending.append(sample)
-            if return_stats:
-                fstats.append(self._model._decode_state.frame_stats())
-            if len(pending) == chunk_frames or i == max_audio_frames - 1:
-                codes = torch.stack(pending).permute(1, 2, 0).long()                       # [1, K, n]
-                hit = (codes[0] == 0).all(dim=0).nonzero()                                  # the chunk's one host look
-                n = int(hit[0]) if hit.numel() else codes.shape[2]
-                if n:
-                    chunk = decoder.step(codes[:, :, :n]).reshape(-1)
-                    chunk = chunk if out is None else out.feed(chunk)
-                    yield (chunk, SampleStats.of_frames(K, fstats[:n])) if return_stats else chunk
-                    check()
-                if hit.numel():
-                    break
-                pending, fstats = [], []
-            curr_tokens = torch.cat([sample.long(), pad], dim=1).unsqueeze(1)
-            curr_mask = audio_mask
-            curr_pos = curr_pos[:, -1:] + 1
-        if out is not None and out.pos:                                # the samples the resampler still owes (its lag)
-            yield (out.flush(), SampleStats(K)) if return_stats else out.flush()
+        step = self._step(call, ads, *self._prompt_frames(text, speaker, context, call.max_audio_frames))
+        yield from stream_spoken(self, _Turn(), step, call, check)
 
     @torch.inference_mode()
     def generate_batch(self, texts: List[str], speakers: List[int], contexts: List[List[Segment]],
@@ -386,20 +327,8 @@ class Generator:
         self._model.reset_caches()
         max_audio_frames = int(max_audio_length_ms / 80)
         K = self._model.args.audio_num_codebooks
-        toks, msks = [], []
-        for text, spk, ctx in zip(texts, speakers, contexts):
-            t_, m_ = [], []
-            for seg in ctx:
-                t, m = self._tokenize_segment(seg)
-                t_.append(t)
-                m_.append(m)
-            t, m = self._tokenize_text_segment(text, spk)
-            t_.append(t)
-            m_.append(m)
-            toks.append(torch.cat(t_, 0).long().to(self.device))
-            msks.append(torch.cat(m_, 0).bool().to(self.device))
-            if toks[-1].size(0) >= self._model.bb.max_seq_len - max_audio_frames:
-                raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {self._model.bb.max_seq_len - max_audio_frames}")
+        prompts = [self._prompt_frames(text, spk, ctx, max_audio_frames) for text, spk, ctx in zip(texts, speakers, contexts)]
+        toks, msks = [t for t, _ in prompts], [m for _, m in prompts]
         if return_stats:
             filters = dict(filters, stats=True)
         frames = [self._model.engine.generate_first_frames(toks, msks, temperature, topk, adapters=ads, **filters)]          # [B, K] each

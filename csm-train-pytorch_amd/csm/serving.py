@@ -132,7 +132,7 @@ from typing import Iterator, List, Optional, Tuple
 
 import torch
 
-from .conversation import OVERFLOW, HeardTurn, check_keep_turns, fit_history, hear_resampler, open_heard_turn
+from .conversation import HeardTurn, _History, hear_resampler
 from .engine import DecodeState
 from .sampling import FULL_LEVEL, HIST_FRAMES, LEVELS, NAMES, PARAMS, SampleStats, _as_list, _is_number, check_row, own_params
 
@@ -263,53 +263,28 @@ class SlotHeardTurn(HeardTurn):
             super().cancel()
 
 
-class ServedConversation:
+class ServedConversation(_History):
     """``BatchServer.conversation(...)``: one dialogue served turn by turn (see the module docstring).  ``tokens`` / ``mask`` /
     ``cached`` mean what they mean on ``Conversation`` and the history has its layout: per turn the text frames, the audio frames,
     one all-zero EOS frame; a spoken turn's frames are the sampled codes; the EOS frame always enters with the next feed."""
 
     def __init__(self, server, context, adapter, seed, on_overflow, temperature=None, topk=None, top_p=None, min_p=None,
                  keep_turns: int = 0, repetition_penalty=None, repetition_window=None, voice=None, typical_p=None):
-        if on_overflow not in OVERFLOW:
-            raise ValueError(f"on_overflow must be one of {OVERFLOW}, got {on_overflow!r}")
-        self._keep_turns = check_keep_turns(keep_turns)
-        self._srv, self._gen = server, server._gen
-        self.adapter, self.seed, self._on_overflow = adapter, seed, on_overflow
+        super().__init__(server._gen, on_overflow, keep_turns, voice)
+        self._srv, self.adapter, self.seed = server, adapter, seed
         # its turns' defaults, resolved
         for name, v in zip(NAMES, server._resolve("conversation", (temperature, topk, top_p, min_p, repetition_penalty,
                                                                    repetition_window, typical_p))):
             setattr(self, name, v)
-        K1 = server._K + 1
-        self._tokens = torch.zeros(0, K1, dtype=torch.long, device=self._gen.device)
-        self._mask = torch.zeros(0, K1, dtype=torch.bool, device=self._gen.device)
-        self._turns: List[int] = []              # lengths of the turns that make up the history
-        self._cached = 0
-        self._parked = None                      # DecodeState.park_row of the ``cached`` leading positions, while it holds no slot
+        # DecodeState.park_row of the ``cached`` leading positions, while it holds no slot.  A voice's K / V are the parked cache -
+        # shared, never written (resume_row copies it into the slot, shift_parked is out of place) - so the first ``say`` is a
+        # resumed turn like any other
+        self._parked = voice.kv if voice is not None else None
         self._noise = None                       # its generator (made at the first admission: lives on the state's device)
         self._open: Optional[Request] = None
-        self._heard: Optional[HeardTurn] = None  # the other party's turn being heard (hear), at most one
-        self._enc = None                         # its encode stream: made at the first hear, reused
-        self._hear_rs = {}                       # hear(sample_rate=) without hear_slots: input rate -> its ResampleStream
         self.closed = False
-        if voice is not None:
-            # the history starts as the voice, already cached; its K / V are the parked cache - shared, never written (resume_row
-            # copies it into the slot, shift_parked is out of place) - so the first ``say`` is a resumed turn like any other
-            self._tokens, self._mask, self._turns = voice.tokens, voice.mask, list(voice.turns)
-            self._cached, self._parked = voice.positions, voice.kv
         for seg in context:
             self.add(seg)
-
-    @property
-    def tokens(self) -> torch.Tensor:
-        return self._tokens
-
-    @property
-    def mask(self) -> torch.Tensor:
-        return self._mask
-
-    @property
-    def cached(self) -> int:
-        return self._cached
 
     def _idle(self, what):
         self._srv._check()
@@ -317,15 +292,6 @@ class ServedConversation:
             raise RuntimeError(f"{what}: this conversation was closed")
         if self._open is not None and not self._open.done:
             raise RuntimeError(f"{what}: this conversation's turn (request {self._open.id}) is still open - one turn at a time")
-
-    @torch.inference_mode()
-    def add(self, segment) -> None:
-        """The other party's turn: tokenised and Mimi-encoded here, once; it enters the cache with the next ``say``."""
-        if self._heard is not None:
-            raise RuntimeError("add: a heard turn is open on this conversation - end() or cancel() it first")
-        self._idle("add")
-        t, m = self._gen._tokenize_segment(segment)
-        self._push(t.long(), m.bool())
 
     def hear(self, speaker: int, sample_rate: Optional[int] = None) -> HeardTurn:
         """The other party starts to speak: ``turn.feed(audio)`` Mimi-encodes the turn as it arrives - between the server's steps,
@@ -338,25 +304,19 @@ class ServedConversation:
             raise RuntimeError("hear: this conversation was closed")
         if self._srv.hear_slots:
             return self._srv._open_heard(self, speaker, sample_rate)
-        return open_heard_turn(self, speaker, sample_rate)
+        return super().hear(speaker, sample_rate)
 
-    _before_history = _idle
-
-    def _push(self, t, m):
-        self._tokens = torch.cat([self._tokens, t.to(self._tokens.device)], 0)
-        self._mask = torch.cat([self._mask, m.to(self._mask.device)], 0)
-        self._turns.append(t.shape[0])
+    _before_history = _idle                      # (``add`` and ``HeardTurn.end``: under ``say``'s rules)
 
     def _fit(self, n_new: int, max_audio_frames: int):
         """``Conversation._fit``: the reference's length rule on history + new text (``fit_history``).  Under ``drop_oldest`` the
         parked cache is dropped and what is kept is prefilled again; under ``shift`` ONE ``DecodeState.shift_parked`` takes the
         cut's cached positions out of the parked cache, so the turn is resumed and fed by the stacked ``append_rows`` like any
         other - unless nothing cached is left, which is ``drop_oldest``."""
-        cut = fit_history(self, n_new, self._srv._model.bb.max_seq_len - max_audio_frames)
+        cut = self.fit_history(n_new, self._srv._model.bb.max_seq_len - max_audio_frames)
         if cut is None:
             return
-        head, gone = cut
-        out = min(self._cached, head + gone) - head                # cached (= parked) positions among the cut ones
+        head, out = cut                                            # (cached = parked positions)
         if self._on_overflow != "shift" or self._parked is None or self._cached - max(out, 0) < 1:
             self._cached, self._parked = 0, None
         elif out > 0:
@@ -398,16 +358,8 @@ class ServedConversation:
         its history positions only - base + the kept frames that were fed back - which are parked.  ``kept``
         (``BatchServer.cancel``): the frames that count, at most those emitted; ``b`` is then the slot, or None for a turn that
         holds none - a preempted one's positions come out of its parked row, a queued one's parked cache stays as it is."""
-        K = self._srv._K
         k = req._emitted if kept is None else min(int(kept), req._emitted)
-        frames = torch.zeros(k + 1, K + 1, dtype=torch.long, device=self._tokens.device)
-        if k:
-            frames[:k, :K] = req.codes().t()[:k]
-        fmask = torch.zeros(k + 1, K + 1, dtype=torch.bool, device=self._mask.device)
-        fmask[:, :K] = True
-        self._tokens = torch.cat([self._tokens, frames], 0)
-        self._mask = torch.cat([self._mask, fmask], 0)
-        self._turns[-1] += k + 1
+        self._close_turn(req.codes().t()[:k])
         # positions base .. base + sampled - 2 hold the frames that were fed back (the last one sampled never was)
         if b is None and req._row is None:       # (cancelled while queued: nothing of the turn ever reached a cache)
             return
@@ -608,16 +560,9 @@ class BatchServer:
         if max_audio_frames < 1:
             raise ValueError(f"max_audio_length_ms = {max_audio_length_ms!r} is less than one 80 ms frame")
         with torch.inference_mode():
-            if voice is None:
-                tokens, mask, _ = self._gen._prompt(text, speaker, list(context), max_audio_frames)
-            else:
-                parts = [self._gen._tokenize_segment(seg) for seg in context] + [self._gen._tokenize_text_segment(text, speaker)]
-                tokens = torch.cat([t for t, _ in parts], 0).long().to(self._gen.device).unsqueeze(0)
-                mask = torch.cat([m for _, m in parts], 0).bool().to(self._gen.device).unsqueeze(0)
-                limit = self._model.bb.max_seq_len - max_audio_frames
-                if voice.positions + tokens.shape[1] >= limit:
-                    raise ValueError(f"Inputs too long, must be below max_seq_len - max_audio_frames: {limit}")
-        req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens[0], mask[0], self._gen.device, *params)
+            tokens, mask = self._gen._prompt_frames(text, speaker, context, max_audio_frames,
+                                                    held=voice.positions if voice is not None else 0)
+        req = Request(self._next_id, text, speaker, adapter, seed, max_audio_frames, tokens, mask, self._gen.device, *params)
         req.sample_rate, req._voice, req._srv = self.sample_rate, voice, self
         req.stats = SampleStats(self._K) if self.sample_stats else None
         self._next_id += 1
